@@ -20,9 +20,11 @@ phase traces.  The default run times BOTH single-GPU workloads of BASELINE.json:
                 blinding (500, 500) -- the shape BASELINE's metric names   -> the "eqtransformer" object
 
 (`--model phasenet|eqtransformer` times one of them alone.)  Inputs are resident in HBM before the
-timed region.  The K steps are timed R times (`--repeats`, each bracketed by a barrier + device
-synchronisation on both sides, max over ranks); `value` is the median repeat and min / max are
-reported beside it, so that a 3 ms region does not decide the headline.
+timed region.  Exactly K steps are timed, as one region bracketed by a barrier + device synchronisation on
+both sides (max over ranks), and `ms_per_step` is that region's time / K.  `--repeats R` times R such regions
+instead (R x K timed steps); `value` is then the median region and min / max are reported beside it.
+`--dump-outputs DIR` writes what the last timed step handed back (stacked phase traces, pick arrays) as
+DIR/<model>_<name>.npy; the inputs are seeded, so two builds can be compared output for output.
 Multi-GPU: every rank owns whole station streams (weak scaling, no data-path collective); the
 weights are broadcast once from rank 0 over RCCL (vp_bcast_weights) before the timed region.
 `--strong` instead times BASELINE configs[3]: ONE 24 h stream (8,640,000 samples, 17,269
@@ -39,11 +41,7 @@ import sys
 import time
 from pathlib import Path
 
-# hardware queues for the device contexts' streams (volpick_amd/__init__.py sets the same default; here it is set before
-# anything can start the HIP runtime)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "12")
-
-import numpy as np  # noqa: E402
+import numpy as np
 
 ROOT = Path(__file__).resolve().parent
 sys.path.insert(0, str(ROOT))
@@ -281,9 +279,9 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=21,
-                    help="the K steps are timed this many times, each between two synchronisations; value = median "
-                         "(the first ~6 regions after an idle GPU run at ramping clocks: timing.windows_per_s_first)")
+    ap.add_argument("--repeats", type=int, default=1,
+                    help="timed regions of K steps each, each between two synchronisations; value = median region "
+                         "(default 1: exactly K steps are timed)")
     ap.add_argument("--settle-seconds", type=float, default=0.4,
                     help="untimed steps run for this long between the W warm-up steps and the timed regions, so that the shader "
                          "clock has climbed to what it holds under the load (0 = none)")
@@ -310,9 +308,15 @@ def main():
     ap.add_argument("--rehearse-gloo", action="store_true",
                     help="rehearsal of the N > 1 plumbing on a ONE-GPU box: process group over gloo, every rank on cuda:0, weights "
                          "through the host broadcast (no RCCL); the line it prints is not a measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0) as DIR/<model>_<name>.npy, float32 / float64")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.repeats < 1:
+        ap.error("--steps and --repeats must be >= 1")
+    if args.dump_outputs and args.strong:
+        ap.error("--dump-outputs covers the default workload, not --strong")
     if "RANK" not in os.environ:
         if args.gpus > 1:
             sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -470,7 +474,7 @@ def clock_probe_read(probe, model_name, batch):
 
 
 def bench_api(model_name, model, batch, oracle_threads=None):
-    """The drop-in call itself, as /root/reference README.md:54-66 writes it: `picker.classify(stream, batch_size=256,
+    """The drop-in call itself, as the reference's README.md:54-66 writes it: `picker.classify(stream, batch_size=256,
     overlap=..., blinding=..., stacking="avg", ...)` on a HOST Stream of one 24 h three-component station (BASELINE
     configs[3]'s workload on one GPU): wall time of the whole call (stream grouping, upload, forward passes, stacking,
     trigger scan, pick records), its phases from one extra profiled call (serialised by device synchronisations: their
@@ -618,7 +622,7 @@ def bench_many_stations(model, model_name, data, kw, n_windows, t0, one_station_
 
 def bench_train(batch=512, steps=30, warmup=5, torch_steps=6, torch_baseline=True):
     """BASELINE configs[4]: one PhaseNet training step (forward in training mode, vector cross-entropy, backward, Adam;
-    /root/reference volpick/model/models.py:34-51,160-185) on VCSEIS-shaped synthetic batches resident in HBM, activation /
+    the reference's volpick/model/models.py:34-51,160-185) on VCSEIS-shaped synthetic batches resident in HBM, activation /
     gradient rows stored as bfloat16 with fp32 accumulation (vp_train_create_dtype(VP_TRAIN_BF16)).  Beside it, as the
     stated baseline, the same step through stock PyTorch-ROCm autograd (eager, bf16 autocast) on the same GPU."""
     import torch
@@ -773,7 +777,7 @@ def station_day_mseed(hours=24):
 
 
 def bench_mseed(hours=24, iters=30):
-    """SURVEY 8f-1 (what feeds A1; /root/reference volpick/data/convert.py:7 reads through obspy): Steim-2 decode of one
+    """SURVEY 8f-1 (what feeds A1; the reference's volpick/data/convert.py:7 reads through obspy): Steim-2 decode of one
     three-component station-day (100 Hz, 4096-byte records) with the file resident in HBM -- vp_mseed_decode, HIP events
     around `iters` launches (vp_mseed_decode_bench).  Input: the committed six-minute fixture tests/golden/
     bench_steim2_6min.mseed tiled to 24 h by patching the records' start times (records then arrive out of time order,
@@ -813,7 +817,7 @@ def bench_mseed(hours=24, iters=30):
     t_read = time.perf_counter() - t0
     day_ok = len(st) == 3 and all(tr.stats.npts == total // 3 for tr in st)
 
-    # ---- file -> picks: what a caller of obspy.read + classify waits for (/root/reference volpick/data/convert.py:7,150 ahead of
+    # ---- file -> picks: what a caller of obspy.read + classify waits for (the reference's volpick/data/convert.py:7,150 ahead of
     # README.md:54-66): the station-day file in host memory -> read() -> PhaseNet.classify() -> pick list, median of 7 calls;
     # device-resident read (samples stay in HBM, trace.data copies on demand) and the plain host Stream, phases once
     def med(fn, n=7):
@@ -903,6 +907,27 @@ def timed_repeats(run_once, sync_all, repeats, use_dist, dev):
 
 OWN_TIMES = []  # this rank's own spans of the last timed_repeats call (its return value is the max over ranks)
 
+DUMP_LIMIT = 64 << 20  # bytes: --dump-outputs, all models together
+
+
+def dump_outputs(out_dir, prefix, arrays, limit=DUMP_LIMIT // 2):
+    """arrays -> out_dir/<prefix>_<name>.npy.  A 2-D array that would take the file set of this prefix above `limit`
+    bytes is cut to a fixed, seeded sample of its columns, sorted; their indices go beside it as <name>_sample_index."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    arrays = dict(arrays)
+    for name, a in list(arrays.items()):
+        others = sum(b.nbytes for k, b in arrays.items() if k != name)
+        if a.ndim == 2 and others + a.nbytes > limit:
+            keep = max(1, (limit - others) // (a.shape[0] * a.itemsize + 8))
+            idx = np.sort(np.random.default_rng(0).choice(a.shape[1], size=min(keep, a.shape[1]), replace=False))
+            arrays[name] = np.ascontiguousarray(a[:, idx])
+            arrays[name + "_sample_index"] = idx.astype(np.float64)
+    assert sum(a.nbytes for a in arrays.values()) <= limit, "dump over its size limit"
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(out_dir / f"{prefix}_{name}.npy", a)
+
 
 def bench_model(model_name, env, cpu_budget_s):
     import torch
@@ -952,8 +977,7 @@ def bench_model(model_name, env, cpu_budget_s):
     found = C.c_int()
     fv, lv, nw = C.c_int64(), C.c_int64(), C.c_int64()
 
-    # Three (PhaseNet) or four (EQTransformer) device contexts (HIP stream + workspace each; tools/ctx_sweep.sh: more
-    # only add queueing, and four need more than HIP's default four hardware queues -- GPU_MAX_HW_QUEUES above), two
+    # Three (PhaseNet) or four (EQTransformer) device contexts (HIP stream + workspace each; more only add queueing), two
     # submits in flight per context: the host enqueues ahead of the GPU, and one context's latency-bound stages
     # (LSTM/attention, small tail kernels) overlap the other's MFMA-bound ones.  Every step is still one full pass
     # over one batch, and every step is collected inside the timed region.
@@ -1006,6 +1030,19 @@ def bench_model(model_name, env, cpu_budget_s):
     t_settle = time.perf_counter() - t_settle
     times = timed_repeats(lambda: run_steps(args.steps), sync_all, args.repeats, use_dist, dev)
     env["own_times"] = list(OWN_TIMES)
+    if args.dump_outputs and rank == 0:  # before the sustained region below overwrites these buffers
+        # the last timed step is step K-1: its traces are in its context's `out`, its triggers in the host arrays (the
+        # last collect); only the valid span [first_valid, last_valid] of `out` is written by the step
+        n = min(found.value, cap)
+        dump_outputs(args.dump_outputs, model_name, {
+            "annotations": outs[(args.steps - 1) % NCTX][:, fv.value:lv.value + 1].cpu().numpy(),
+            "span": np.array([fv.value, lv.value, nw.value], dtype=np.float64),
+            "pick_spec": np.array(spec_of[:n], dtype=np.float64),
+            "pick_onset": np.array(on[:n], dtype=np.float64),
+            "pick_offset": np.array(off[:n], dtype=np.float64),
+            "pick_peak": np.array(peak[:n], dtype=np.float64),
+            "pick_value": np.array(val[:n], dtype=np.float32),
+        })
     n_picks = found.value
     dt = statistics.median(times)
     windows = args.batch * args.steps * world
@@ -1110,7 +1147,7 @@ def bench_model(model_name, env, cpu_budget_s):
         "sustained": sustained,
         "timing": {
             "repeats": len(times),
-            "statistic": "median over the repeats of the max-over-ranks time of K steps",
+            "statistic": "median over the repeats (default one) of the max-over-ranks time of K steps",
             "windows_per_s_min": windows / max(times),
             "windows_per_s_max": windows / min(times),
             "windows_per_s_first": windows / times[0],
@@ -1125,7 +1162,6 @@ def bench_model(model_name, env, cpu_budget_s):
             "in_samples": T,
             "parallelism": f"stream-sharded x{world}, weights broadcast once (RCCL)" if world > 1 else "one rank (nothing broadcast)",
             "device_contexts": NCTX,
-            "hip_hw_queues": int(os.environ.get("GPU_MAX_HW_QUEUES", "4")),
             "inflight_steps_per_context": DEPTH,
             "input_residency": "every step re-reads the same device-resident stream (18 / 1.6 MB): Infinity-Cache "
                                "resident; the kernels are compute-bound, so this does not flatter the number",

@@ -5,7 +5,7 @@
  * The reference reaches this path through a Python object API, not an FFI
  * (SURVEY.md §8b): seisbench.models.{PhaseNet,EQTransformer} instances created with
  * from_pretrained("volpick") and driven by classify()/annotate()/__call__
- * (/root/reference README.md:46-66, Final_models/demo.ipynb:300-301,359-360,397-398,
+ * (the reference's README.md:46-66, Final_models/demo.ipynb:300-301,359-360,397-398,
  * volpick/model/eval_taks0.py:58-89).  Each entry point below names the reference
  * interface it replaces.  Plain pointers and sizes only; no torch types.
  *
@@ -208,7 +208,7 @@ int vp_pick_windows(vp_handle* h, const float* prob, int prob_mem, int B, int n_
 
 /* vp_classify over K stream blocks (stations / contiguous segments) in ONE call: the windows of all blocks
  * share the forward batches -- SeisBench's batch_size spans every fragment of the stream it is given
- * (/root/reference README.md:54-66) -- and stacking and the trigger scan are one launch each.
+ * (the reference's README.md:54-66) -- and stacking and the trigger scan are one launch each.
  * `streams` (host or device) holds block k as 3 rows of lengths[k] samples at float offset offsets[k];
  * `out` (may be NULL) receives the stacked rows in the same layout.  first_valid / last_valid / n_windows
  * are arrays of K.  Triggers come back grouped by block, then spec, sorted by onset, with block_of /
@@ -308,7 +308,7 @@ int vp_debug_tail_clock(vp_handle* h, int B, unsigned long long* out32);
 /* ---------------------------------------------------------------------------------------------
  * Waveform-file ingestion: miniSEED 2 and miniSEED 3 records -> sample arrays,
  * the step the reference performs with obspy.read() (libmseed) before stream_to_array
- * (/root/reference volpick/data/convert.py:7,26-70).
+ * (the reference's volpick/data/convert.py:7,26-70).
  *
  * vp_mseed_scan (host only, no GPU) walks a miniSEED byte string and fills one vp_mseed_record per
  * data record; the two formats may be mixed in one buffer.  miniSEED 2: fixed header, blockette 1000
@@ -359,7 +359,7 @@ int vp_mseed_release_scratch(int device_id, size_t* bytes_freed);
 /* ---------------------------------------------------------------------------------------------
  * PhaseNet training step (BASELINE config 5): what one
  * PhaseNetLit.training_step + Adam optimizer.step of the reference computes
- * (/root/reference volpick/model/models.py:34-51 vector_cross_entropy, :160-164 training_step,
+ * (the reference's volpick/model/models.py:34-51 vector_cross_entropy, :160-164 training_step,
  * :177-185 torch.optim.Adam).  vp_train_create: fp32 throughout (what the reference trains in: no autocast).
  * vp_train_create_dtype(..., VP_TRAIN_BF16, ...): the activation and gradient rows of every layer (z, a, gz, ga -- all
  * of the step's HBM traffic but the weights) rest in memory as bfloat16, round-to-nearest-even on store; weights,

@@ -6,12 +6,12 @@ import this; only ``tests/``, ``__graft_entry__.smoke()`` and ``bench.py``'s
 
 PARITY UNPINNED.  The arithmetic of the path lives in the un-vendored
 third-party packages SeisBench (``seisbench.models``) and ObsPy
-(``obspy.signal.trigger.trigger_onset``), which are neither under
-/root/reference nor installable here.  The
+(``obspy.signal.trigger.trigger_onset``), which are neither in the
+reference repository nor installable here.  The
 reference repository holds no tests, golden vectors or fixtures for this path.
 This oracle therefore restates the *published* SeisBench (>= 0.4, the
 ``seisbench_requirement`` in Final_models/**/*.json.v1:8) and ObsPy 1.4
-algorithms, anchored on what /root/reference does pin:
+algorithms, anchored on what the reference repository does pin:
 
   * the released state dicts load with strict key/shape equality
     (Final_models/**/*.pt.v1),

@@ -183,3 +183,33 @@ def test_compact_line_from_round_6_detail_stays_under_four_kilobytes():
         _required(d, k)
     assert d["dtype"].startswith("f32 (exact 3xbf16") and d["roofline"]["kernel_ms"] <= d["ms_per_step"] * 1.0001
     assert "RCCL" not in d["config"]["parallelism"]  # one rank: nothing was broadcast
+
+
+def test_dump_outputs_writes_float_arrays_and_samples_what_does_not_fit(tmp_path):
+    """--dump-outputs: arrays small enough are written whole; a 2-D one over the limit becomes the same seeded, sorted
+    sample of its columns on every run, with the column indices beside it."""
+    import numpy as np
+    import pytest
+
+    rows = np.arange(3 * 1000, dtype=np.float32).reshape(3, 1000)
+    picks = np.array([5.0, 17.0])
+    bench.dump_outputs(tmp_path / "a", "m", {"annotations": rows, "pick_peak": picks}, limit=1 << 20)
+    assert np.array_equal(np.load(tmp_path / "a" / "m_annotations.npy"), rows)
+    assert np.array_equal(np.load(tmp_path / "a" / "m_pick_peak.npy"), picks)
+    for d in ("b", "c"):
+        bench.dump_outputs(tmp_path / d, "m", {"annotations": rows, "pick_peak": picks}, limit=4000)
+    idx = np.load(tmp_path / "b" / "m_annotations_sample_index.npy")
+    got = np.load(tmp_path / "b" / "m_annotations.npy")
+    assert idx.dtype == np.float64 and np.all(np.diff(idx) > 0) and got.shape == (3, idx.size) and 0 < idx.size < 1000
+    assert np.array_equal(got, rows[:, idx.astype(np.int64)])
+    assert sum(f.stat().st_size - 128 for f in (tmp_path / "b").iterdir()) <= 4000  # .npy header: 128 bytes
+    for f in (tmp_path / "b").iterdir():
+        assert np.array_equal(np.load(f), np.load(tmp_path / "c" / f.name))
+    with pytest.raises(AssertionError):
+        bench.dump_outputs(tmp_path / "d", "m", {"peak": np.arange(4, dtype=np.int64)})
+
+
+def test_steps_and_dump_arguments_are_checked():
+    for argv in (["--steps", "0"], ["--repeats", "0"], ["--strong", "--dump-outputs", "x"]):
+        p = subprocess.run([sys.executable, BENCH] + argv, capture_output=True, text=True, timeout=120)
+        assert p.returncode == 2 and "error" in p.stderr, (argv, p.stderr[-300:])

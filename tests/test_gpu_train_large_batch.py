@@ -1,5 +1,5 @@
 """GPU parity of the bf16 training step AT THE BATCH THE BENCH TIMES (BASELINE configs[4]; contract:
-/root/reference volpick/model/models.py:34-51,160-164 and model_training/configs_tune/p_512_5e-04_ga20_400_s.json: batch 512).
+the reference's volpick/model/models.py:34-51,160-164 and model_training/configs_tune/p_512_5e-04_ga20_400_s.json: batch 512).
 
 Round 4 verified the step at B = 6 / 8 / 40 and timed it at B = 512; the trainer changes form with the batch
 (`csrc/train_phasenet.hip`: the grid-stride BatchNorm passes `a.GB`, `GB = B < 64 ? B : 64` of the bias sum, the capped
@@ -52,7 +52,7 @@ def test_every_kernel_of_the_large_batch_step(big):
 
 def test_adam_update_and_running_statistics_of_the_same_step(big):
     """Step 1 of Adam from the step's own gradients, in float64: w1 = w0 - lr * mhat / (sqrt(vhat) + eps) with m = (1 - b1) g,
-    v = (1 - b2) g^2 (torch.optim.Adam, /root/reference volpick/model/models.py:177-185); BatchNorm running statistics
+    v = (1 - b2) g^2 (torch.optim.Adam, the reference's volpick/model/models.py:177-185); BatchNorm running statistics
     = 0.9 * old + 0.1 * (batch mean, UNBIASED batch variance) of the stored z."""
     s = big
     g, w0, w1, (m, v) = s["g"], s["w0"], s["w1"], s["mv"]

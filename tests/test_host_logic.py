@@ -202,7 +202,8 @@ def test_save_round_trips_the_model_zoo_format(tmp_path, cls, name):
 
 def test_training_host_pieces_without_gpu():
     """vector_cross_entropy (volpick/model/models.py:34-51), the label shape PhaseNetLit asks for and the
-    500-step warm-up (models.py:168-175); the step itself needs the GPU and fails loudly without one."""
+    500-step warm-up (models.py:168-175); the trainer itself needs the GPU and fails loudly without one (with one, it
+    is created)."""
     import torch
 
     from volpick_amd.train import PhaseNetLit, PhaseNetTrainer, gaussian_labels, vector_cross_entropy
@@ -223,8 +224,13 @@ def test_training_host_pieces_without_gpu():
     assert lrs[0] == 5e-4 and lrs[1] == pytest.approx(5e-4 * 1 / 500) and lrs[499] == pytest.approx(5e-4 * 499 / 500)
     assert lrs[500] == 5e-4 and lrs[599] == 5e-4
     assert all(b >= a for a, b in zip(lrs[1:500], lrs[2:501]))
-    with pytest.raises(_lib.VolpickHipError):
-        PhaseNetTrainer(va.PhaseNet.from_pretrained("volpick"), max_batch=4)
+    if torch.cuda.is_available():
+        tr = PhaseNetTrainer(va.PhaseNet.from_pretrained("volpick"), max_batch=4)
+        assert tr._h.value
+        tr.close()
+    else:
+        with pytest.raises(_lib.VolpickHipError):
+            PhaseNetTrainer(va.PhaseNet.from_pretrained("volpick"), max_batch=4)
 
 
 def test_resampling_rule_and_numerics():

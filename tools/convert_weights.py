@@ -2,7 +2,7 @@
 """Convert the reference's released SeisBench-format weights into the neutral
 fixture format shipped in this repo.
 
-Input  (read-only, /root/reference/Final_models/**):
+Input  (read-only, <reference checkout>/Final_models/**):
     <name>.pt.v1   = torch.save(model.state_dict())   [REF model_training/tune.ipynb:143-149]
     <name>.json.v1 = {docstring, model_args, seisbench_requirement, version, default_args}
                                                       [REF model_training/tune.ipynb:90-121]
@@ -14,7 +14,7 @@ The weight files are DATA (trained parameters, GPL-3.0 like the reference
 repository, see volpick_amd/weights/LICENSE.weights); no reference source code
 is copied.  Run once in the build container:
 
-    python tools/convert_weights.py [/root/reference]
+    python tools/convert_weights.py <reference checkout>
 
 It also writes tests/golden/weights.sha256: one SHA-256 per tensor and per metadata JSON, computed FROM THE REFERENCE'S
 FILES (not from the converted copies).  tests/test_weights_pinned.py recomputes them from what the package ships, so the
@@ -60,9 +60,9 @@ def digest_lines(model, name, arrays, meta):
     return lines
 
 
-def main(ref_root="/root/reference"):
+def main(ref_root):
     digests = ["# SHA-256 of every tensor and metadata JSON of the four released weight sets, computed by tools/convert_weights.py",
-               "# from /root/reference/Final_models/**/*.{pt,json}.v1 (tensor: name|dtype|shape|little-endian bytes; JSON: canonical form)"]
+               "# from <reference checkout>/Final_models/**/*.{pt,json}.v1 (tensor: name|dtype|shape|little-endian bytes; JSON: canonical form)"]
     ref = Path(ref_root) / "Final_models"
     for model, entries in SETS.items():
         out_dir = REPO / "volpick_amd" / "weights" / model
@@ -83,4 +83,6 @@ def main(ref_root="/root/reference"):
 
 
 if __name__ == "__main__":
-    main(*sys.argv[1:])
+    if len(sys.argv) != 2:
+        sys.exit("usage: python tools/convert_weights.py <reference checkout>")
+    main(sys.argv[1])

@@ -1,7 +1,7 @@
 """Max / 99.99th percentile / mean absolute difference between each PhaseNet / EQTransformer plan and the torch-CPU oracle on
 512 / 256 synthetic windows (tolerance of the path: 1e-4 on probabilities).  Run on the GPU box: python tools/err_check.py"""
-import sys, numpy as np, torch
-sys.path.insert(0, "/root/repo")
+import os, sys, numpy as np, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))  # the repository root
 from oracle import pipeline as OP
 from oracle.models import load_pretrained
 from volpick_amd import PhaseNet

@@ -1,7 +1,7 @@
 """EQTransformer plan variants against the torch-CPU oracle run in FLOAT64 (and in fp32): is a bf16-piece kernel less accurate
 than its fp32-MFMA form, or only differently rounded?  64 synthetic windows.  Run on the GPU box: python tools/err_check_f64.py"""
-import sys, numpy as np, torch
-sys.path.insert(0, "/root/repo")
+import os, sys, numpy as np, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))  # the repository root
 from oracle import pipeline as OP
 from oracle.models import load_pretrained
 from volpick_amd import EQTransformer

@@ -1,5 +1,5 @@
-import sys, time
-sys.path.insert(0, "/root/repo")
+import os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))  # the repository root
 import numpy as np, torch
 import volpick_amd as va
 from volpick_amd import Stream, Trace, UTCDateTime

@@ -1,6 +1,6 @@
 // miniSEED 2 / miniSEED 3 ingestion: host record scanner and a one-wavefront-per-record
 // decoder.  Replaces obspy.read()'s libmseed unpacking ahead of stream_to_array
-// (/root/reference volpick/data/convert.py:7,26-70).
+// (the reference's volpick/data/convert.py:7,26-70).
 //
 // The decode is byte/integer work bound by HBM: ~1.3-2 compressed bytes in and 4 bytes out per
 // sample.  Records are independent (every Steim record carries its own forward integration

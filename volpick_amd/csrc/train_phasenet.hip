@@ -1,7 +1,7 @@
 // PhaseNet training step (BASELINE config 5): forward in training mode (batch
 // statistics), vector cross entropy, backward, Adam -- the arithmetic of one
 // PhaseNetLit.training_step + optimizer.step of the reference
-// (/root/reference volpick/model/models.py:34-51 loss, :160-164 shared_step/training_step,
+// (the reference's volpick/model/models.py:34-51 loss, :160-164 shared_step/training_step,
 // :177-185 Adam; the SeisBench PhaseNet module it wraps is restated in oracle/models.py).
 //
 // Layout: every layer keeps z (raw conv output), a = relu(bn(z)) and the gradients gz, ga as haloed

@@ -1,7 +1,7 @@
 """Waveform-file ingestion without ObsPy.
 
 ``read()`` stands where the reference calls ``obspy.read`` ahead of the picker
-(/root/reference volpick/data/convert.py:7 and the ``read(...)`` call sites of
+(the reference's volpick/data/convert.py:7 and the ``read(...)`` call sites of
 ``convert_mseed_to_seisbench``; Final_models/demo.ipynb:249-266 builds the same kind of Stream
 from an FDSN download) and returns this package's ``Stream``.  miniSEED 2 and miniSEED 3 records
 (also mixed in one file) are found by the library's host scanner (``vp_mseed_scan``, which checks

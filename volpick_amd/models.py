@@ -111,8 +111,8 @@ class WaveformModel:
         self._extra_handles = []
         self.batch_across_blocks = True  # classify(): windows of several device-resident blocks share the forward batches
         self._max_windows_per_call = 32768  # bounds the prediction buffer of one multi-block call (2.4 GB for EQT)
-        # device contexts classify() pipelines station blocks over (tools/ctx_sweep.sh: PhaseNet 3, EQTransformer 4 with
-        # >= 5 hardware queues -- volpick_amd/__init__.py; more contexts than that only add queueing)
+        # device contexts classify() pipelines station blocks over (PhaseNet 3, EQTransformer 4; more contexts than that
+        # only add queueing)
         self.n_contexts = self.default_contexts
         self._seg_per_context = 2  # segments of a long block per device context (<= VP_MAX_INFLIGHT submit slots)
         self._device_index = None

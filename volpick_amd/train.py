@@ -1,7 +1,7 @@
 """PhaseNet training step on the GPU (BASELINE config 5).
 
 Host-side mirror of the pieces of the reference's Lightning module that define the arithmetic of
-one optimisation step (/root/reference volpick/model/models.py):
+one optimisation step (the reference's volpick/model/models.py):
 
 * ``vector_cross_entropy`` (:34-51),
 * ``PhaseNetLit.shared_step`` / ``training_step`` (:160-169): ``loss(model(batch["X"]), batch["y"])``,
