@@ -412,6 +412,46 @@ void* vp_train_stream(const vp_trainer* t);
 int vp_train_launch_count(const vp_trainer* t); /* kernel launches the latest vp_train_step enqueued */
 
 /* ---------------------------------------------------------------------------------------------
+ * Training batches generated on the GPU from a device-resident waveform bank: the window cut, Normalize and
+ * ProbabilisticLabeller steps of the reference's augmentation block 1 (volpick/model/models.py:221-265).  The host plans
+ * every random choice (volpick_amd/generate.py) and hands one vp_plan_row per window; the kernel has no RNG.
+ *
+ * vp_bank_create reserves n_traces traces holding n_floats_total floats in all.  vp_bank_write stores traces
+ * [first_trace, first_trace + n_traces) -- in order: first_trace is the number of traces written so far -- from `data`,
+ * their (3, trace_lengths[i]) fp32 arrays back to back, host or device (mem; a device source is read after every stream
+ * of the device has drained), and their onsets: onsets[4 i .. 4 i + 3] = P, P, S, S in trace samples (float64, NaN = no
+ * pick).  It may be called in chunks.  vp_bank_destroy synchronises the bank's device, then frees it.
+ *
+ * A plan row defines x[c][t] = bank[trace][c][start + t] where lo <= start + t < hi, else 0, for t in [0, T).
+ * vp_bank_make_batch writes x and y, each (B, 3, T) fp32 on the bank's device, on `stream` (hipStream_t, NULL = legacy
+ * default stream):
+ *   x: per channel, minus its mean over the T samples, divided by max|x| + 1e-10 (norm = VP_NORM_PEAK) or by the
+ *      population standard deviation (ddof 0) + 1e-10 (VP_NORM_STD);
+ *   y: row label_rows[0] (P) and label_rows[1] (S): the maximum over the phase's onsets of exp(-(t - o)^2 / (2 sigma^2)),
+ *      o = onset - start; row label_rows[2] (noise): clip(1 - P - S, 0, 1).
+ * Every row and argument is checked on the host first (0 <= trace < traces written, 0 <= lo <= hi <= the trace's length,
+ * 1 <= B, 1 <= T <= 6144, sigma > 0, label_rows a permutation of 0, 1, 2): VP_ERR_INVALID launches nothing and leaves x
+ * and y untouched.  `rows` is host memory the caller may reuse as soon as the call returns.
+ *
+ * vp_train_step_bank is vp_train_step with x and y generated this way (T = 3001) into the trainer's own input buffers
+ * on the trainer's stream: no upload and no wait on another stream.  The bank must live on the trainer's device and stay
+ * alive until the step has run. */
+typedef struct vp_bank vp_bank;
+typedef struct {
+  int32_t trace;
+  int32_t reserved; /* 0 */
+  int64_t start, lo, hi;
+} vp_plan_row;
+int vp_bank_create(int device_id, long long n_traces, long long n_floats_total, vp_bank** out);
+int vp_bank_write(vp_bank* bank, long long first_trace, long long n_traces, const float* data, int mem,
+                  const int64_t* trace_lengths, const double* onsets);
+int vp_bank_destroy(vp_bank* bank);
+int vp_bank_make_batch(vp_bank* bank, const vp_plan_row* rows, int B, int T, float sigma, int norm, const int* label_rows,
+                       float* x, float* y, void* stream);
+int vp_train_step_bank(vp_trainer* t, vp_bank* bank, const vp_plan_row* rows, int B, float sigma, int norm,
+                       const int* label_rows, float lr, int update, double* loss);
+
+/* ---------------------------------------------------------------------------------------------
  * Multi-GPU bring-up.  The reference is single-GPU; windows are independent given the
  * weights, so the one exchange is the start-up broadcast of the flat weight blob from the root rank: a single
  * ncclBroadcast over RCCL (xGMI inside a node), after which vp_create(..., VP_MEM_DEVICE, ...) builds the plan from the

@@ -44,6 +44,10 @@ class VpTriggerSpec(C.Structure):
     _fields_ = [("row", C.c_int32), ("thr_on", C.c_float), ("thr_off", C.c_float)]
 
 
+class VpPlanRow(C.Structure):
+    _fields_ = [("trace", C.c_int32), ("reserved", C.c_int32), ("start", C.c_int64), ("lo", C.c_int64), ("hi", C.c_int64)]
+
+
 class VpMseedRecord(C.Structure):
     _fields_ = [
         ("offset", C.c_int64),
@@ -195,6 +199,16 @@ SIGNATURES = {
     "vp_train_tensor_read": (C.c_int, [_H, C.c_int, C.c_int, C.c_void_p]),
     "vp_train_stream": (C.c_void_p, [_H]),
     "vp_train_launch_count": (C.c_int, [_H]),
+    "vp_bank_create": (C.c_int, [C.c_int, C.c_longlong, C.c_longlong, C.POINTER(_H)]),
+    "vp_bank_write": (C.c_int, [_H, C.c_longlong, C.c_longlong, C.c_void_p, C.c_int, _I64P, C.POINTER(C.c_double)]),
+    "vp_bank_destroy": (C.c_int, [_H]),
+    "vp_bank_make_batch": (
+        C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
+    "vp_train_step_bank": (
+        C.c_int,
+        [_H, _H, C.c_void_p, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_int), C.c_float, C.c_int, C.POINTER(C.c_double)],
+    ),
     "vp_last_error": (C.c_char_p, []),
     "vp_version": (C.c_char_p, []),
 }

@@ -14,6 +14,7 @@
 
 #include <memory>
 
+#include "batchgen.h"
 #include "conv_mfma.h"
 #include "conv_train_b16.h"
 #include "train_kernels.h"
@@ -246,8 +247,9 @@ struct Trainer {
   double* head_partial = nullptr;
   double* head_sums = nullptr;  // [28] + loss at [28]
   double* head_stage = nullptr; // [64][28]
-  float* x_dev = nullptr;       // staging for host inputs
+  float* x_dev = nullptr;       // staging for host inputs, and where vp_train_step_bank generates its batch
   float* y_dev = nullptr;
+  RowRing plan_rows;            // vp_train_step_bank's plan rows: slot seq % EV_RING, free again at ev_inputs of that slot
   float* p_dev = nullptr;       // predictions of the last step
   long step = 0;
   float beta1 = 0.9f, beta2 = 0.999f, adam_eps = 1e-8f, bn_eps = 1e-3f, bn_momentum = 0.1f, loss_eps = 1e-5f;
@@ -934,6 +936,16 @@ int forward_backward(Trainer& tr, const float* x_dev, const float* y_dev, int B,
   return VP_OK;
 }
 
+int step_and_loss(Trainer& tr, const float* x_dev, const float* y_dev, int B, float lr, int update, double* loss) {
+  const int rc = forward_backward(tr, x_dev, y_dev, B, update != 0, lr);
+  if (rc != VP_OK) return rc;
+  if (loss) {
+    VP_HIP(hipMemcpyAsync(loss, tr.head_sums + 28, sizeof(double), hipMemcpyDeviceToHost, tr.stream));
+    VP_HIP(hipStreamSynchronize(tr.stream));
+  }
+  return VP_OK;
+}
+
 }  // namespace
 }  // namespace vp
 
@@ -1016,13 +1028,33 @@ int vp_train_step(vp_trainer* h, const float* x, const float* y, int mem, int B,
     xd = tr.x_dev;
     yd = tr.y_dev;
   }
-  const int rc = forward_backward(tr, xd, yd, B, update != 0, lr);
+  return step_and_loss(tr, xd, yd, B, lr, update, loss);
+}
+
+int vp_train_step_bank(vp_trainer* h, vp_bank* bank, const vp_plan_row* rows, int B, float sigma, int norm,
+                       const int* label_rows, float lr, int update, double* loss) {
+  VP_REQUIRE(h && bank, "vp_train_step_bank: null argument");
+  Trainer& tr = *reinterpret_cast<Trainer*>(h);
+  const Bank& bk = *reinterpret_cast<const Bank*>(bank);
+  VP_REQUIRE(B >= 2 && B <= tr.max_batch, "vp_train_step_bank: batch %d outside [2, %d]", B, tr.max_batch);
+  VP_REQUIRE(bk.device == tr.device, "vp_train_step_bank: bank on device %d, trainer on device %d", bk.device, tr.device);
+  static_assert(RowRing::N == Trainer::EV_RING, "one plan-row slot per step event");
+  int rc = bank_check(bk, rows, B, T0, sigma, norm, label_rows);
   if (rc != VP_OK) return rc;
-  if (loss) {
-    VP_HIP(hipMemcpyAsync(loss, tr.head_sums + 28, sizeof(double), hipMemcpyDeviceToHost, tr.stream));
-    VP_HIP(hipStreamSynchronize(tr.stream));
+  VP_HIP(hipSetDevice(tr.device));
+  if (!tr.plan_rows.cap) {
+    rc = tr.plan_rows.reserve(tr.max_batch);
+    if (rc != VP_OK) return rc;
   }
-  return VP_OK;
+  // the step that used this slot last: its ev_inputs stands behind the head kernel, which runs after the generation kernel
+  // that read the slot's device copy, which ran after the copy that read the host slot
+  const int slot = (int)(tr.seq % Trainer::EV_RING);
+  if (tr.ev_inputs_seq[slot] >= 0) VP_HIP(hipEventSynchronize(tr.ev_inputs[slot]));
+  const vp_plan_row* rd = tr.plan_rows.stage(slot, rows, B, tr.stream);
+  if (!rd) return VP_ERR_HIP;
+  rc = bank_launch(bk, rd, B, T0, sigma, norm, label_rows, tr.x_dev, tr.y_dev, tr.stream);
+  if (rc != VP_OK) return rc;
+  return step_and_loss(tr, tr.x_dev, tr.y_dev, B, lr, update, loss);
 }
 
 // Makes `stream` (a hipStream_t of the same device; NULL = the legacy default stream) wait until the latest vp_train_step

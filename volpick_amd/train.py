@@ -8,9 +8,13 @@ one optimisation step (the reference's volpick/model/models.py):
 * ``configure_optimizers`` (:177-185): ``torch.optim.Adam(lr)``,
 * ``optimizer_step`` (:168-175): linear learning-rate warm-up over the first 500 steps.
 
-Data loading, augmentation, logging and checkpointing (Lightning / SeisBench generators) are not
-part of this package.  Forward (training-mode BatchNorm), loss, backward and Adam all run in
-``libvolpick_hip.so`` (``vp_train_*``); there is no CPU fallback.
+Batches come either finished, as ``(x, y)`` tensors (``PhaseNetTrainer.step``, ``PhaseNetLit.training_step``), or are
+generated on the GPU from a device-resident :class:`~volpick_amd.generate.WaveformBank`: window cut, demean and
+normalise and Gaussian labels -- the core of the reference's augmentation block 1, its random choices planned on the
+host by :class:`~volpick_amd.generate.WindowPlanner` (``PhaseNetTrainer.step_bank``, ``PhaseNetLit.fit_bank``).
+volpick's stacking augmentations, logging and checkpointing (Lightning) are not part of this package.  Forward
+(training-mode BatchNorm), loss, backward and Adam all run in ``libvolpick_hip.so`` (``vp_train_*``); there is no CPU
+fallback.
 """
 from __future__ import annotations
 
@@ -151,6 +155,27 @@ class PhaseNetTrainer:
             self.global_step += 1
         return loss.value if want_loss else None
 
+    def step_bank(self, bank, rows, lr, sigma, update=True, want_loss=True):
+        """``step`` on a batch generated on the GPU: the plan rows (``generate.PLAN_ROW``, e.g. from
+        ``WindowPlanner``) are cut from ``bank`` (a ``WaveformBank`` on the trainer's device), normalised with
+        ``model.norm`` and labelled with Gaussians of width ``sigma`` in ``model.labels`` order, straight into the
+        trainer's input buffers on its own stream (``vp_train_step_bank``).  ``rows`` may be reused at once."""
+        from .generate import as_rows, label_rows, _norm
+
+        rows = as_rows(rows)
+        lrows = label_rows(self.model.labels)
+        self._drop_consumed()
+        loss = C.c_double(float("nan"))
+        _lib.check(self._lib.vp_train_step_bank(self._h, bank.handle, rows.ctypes.data_as(C.c_void_p), len(rows), float(sigma),
+                                                _norm(self.model.norm), lrows.ctypes.data_as(C.POINTER(C.c_int)), float(lr),
+                                                int(bool(update)), C.byref(loss) if want_loss else None), "vp_train_step_bank")
+        # the bank stays referenced until the step's reads of it are complete (as the device inputs of `step`)
+        self._in_flight.append((int(self._lib.vp_train_steps_enqueued(self._h)) - 1, bank, None))
+        self.forward_count = getattr(self, "forward_count", 0) + 1
+        if update:
+            self.global_step += 1
+        return loss.value if want_loss else None
+
     def _drop_consumed(self):
         """Device inputs of the steps the trainer's stream has read to the end may go (no event of ours enters that stream:
         the library keeps one per step behind the last reader of x / y and answers which of them have completed)."""
@@ -237,7 +262,12 @@ class PhaseNetLit:
 
     WARMUP_STEPS = 500
 
-    def __init__(self, lr=1e-2, sigma=20, max_batch=512, model=None, device=0, precision="32", **model_kwargs):
+    def __init__(self, lr=1e-2, sigma=20, max_batch=512, model=None, device=0, precision="32", prob_label_shape="gaussian",
+                 **model_kwargs):
+        if prob_label_shape != "gaussian":
+            raise ValueError(f"prob_label_shape {prob_label_shape!r}: only 'gaussian' labels are implemented (every "
+                             "reference config uses them)")
+        self.prob_label_shape = prob_label_shape
         self.lr = float(lr)
         self.precision = str(precision)  # "32" (the reference's) or "bf16-mixed" (PhaseNetTrainer dtype="bf16")
         self.sigma = sigma
@@ -286,6 +316,39 @@ class PhaseNetLit:
         y = batch["y"]
         y = y.cpu().numpy() if hasattr(y, "cpu") else np.asarray(y)
         return vector_cross_entropy(p.astype(np.float64), y.astype(np.float64))
+
+    def fit_bank(self, bank, steps, batch_size=512, seed=0, val_bank=None):
+        """``steps`` optimiser steps on batches generated on the GPU from ``bank`` (a ``WaveformBank``): epochs of
+        ``WindowPlanner(bank, batch_size, seed=seed)`` (a new permutation each, last partial batch dropped), learning
+        rate ``learning_rate(step)``, labels of width ``self.sigma``.  Returns the per-step losses and, with ``val_bank``,
+        ``(losses, val_losses)``: the mean ``validation_step`` loss over ``val_bank`` (in order, the last partial batch
+        kept, its own planner seeded ``seed + 1``) after every completed epoch and after the last step."""
+        from .generate import WindowPlanner
+
+        tr = self._ensure()
+        in_samples = self.model.in_samples
+        planner = WindowPlanner(bank, batch_size, in_samples=in_samples, seed=seed)
+        if len(bank.lengths) < batch_size:
+            raise ValueError(f"a bank of {len(bank.lengths)} traces holds no full batch of {batch_size}")
+        val_planner = WindowPlanner(val_bank, batch_size, in_samples=in_samples, seed=seed + 1) if val_bank is not None else None
+        losses, val_losses = [], []
+
+        def validate():
+            vl = [self.validation_step(val_bank.make_batch(rows, self.model, self.sigma)) for rows in val_planner.validation()]
+            val_losses.append(float(np.mean(vl)))
+
+        while len(losses) < steps:
+            for rows in planner.epoch():
+                losses.append(tr.step_bank(bank, rows, self.learning_rate(tr.global_step), self.sigma))
+                if len(losses) == steps:
+                    break
+            else:
+                if val_planner is not None and len(losses) < steps:
+                    validate()
+        if val_planner is None:
+            return losses
+        validate()
+        return losses, val_losses
 
     def enable_ema(self, decay=0.999):
         self._ensure().enable_ema(decay)
