@@ -451,6 +451,56 @@ int vp_bank_make_batch(vp_bank* bank, const vp_plan_row* rows, int B, int T, flo
 int vp_train_step_bank(vp_trainer* t, vp_bank* bank, const vp_plan_row* rows, int B, float sigma, int norm,
                        const int* label_rows, float lr, int update, double* loss);
 
+/* Augmented windows: block 1 above, then volpick's stacking slots, AddGap and a second Normalize (the reference's
+ * get_train_augmentations / get_val_augmentations with stack_data, volpick/model/models.py:345-440).  The host draws every
+ * random choice and everything that follows from onsets alone (volpick_amd/generate.py, AugmentedPlanner); one
+ * vp_aug_row per window is executed in this order:
+ *   1. primary: x, y as vp_bank_make_batch writes them for `primary`;
+ *   2. x[c][t] = 0 for t >= cut (cut = T: no truncation);
+ *   3. per event entry with kind != VP_AUG_NONE, in order: the source s is `row` cut, demeaned, normalised and labelled
+ *      as in step 1 (VP_AUG_BANK), or the primary window as it was after step 1 (VP_AUG_SELF, `row` all zero).
+ *      VP_AUG_BANK only: every channel c whose current x[c] is all |x| <= 1e-8 is zeroed in s.  s[:, :zero_before] = 0;
+ *      then x[c][t] += scale * s[c][t - shift] and y'[k][t] = y_s[k][t - shift] (0 where t - shift is outside [0, T));
+ *      y = max(y, y') row by row, P and S divided by max(1, P + S), noise = 1 - P - S;
+ *   4. per noise entry with kind == VP_AUG_BANK, in order: s as in step 3 (bank windows only, zero-channel rule), then
+ *      x += s * max|x| * scale, max|x| over every channel of the current x;
+ *   5. gauss > 0: x[c][t] += gauss * max(x) * n(noise_key, c, t), max(x) signed, n a standard normal from Philox4x32-10
+ *      (key = noise_key, counter = (t, c, 0, 0)) through Box-Muller in float64: u_i = (w_{2i} | w_{2i+1} << 32) >> 11
+ *      times 2^-53, n = sqrt(-2 log(1 - u_0)) cos(2 pi u_1);
+ *   6. x[:, gap_lo:gap_hi] = 0; there y = 0 except the noise row, 1;
+ *   7. x demeaned and normalised again with `norm` (float64 statistics, as in step 1).
+ * Every field is checked on the host before any launch (VP_ERR_INVALID, outputs untouched): rows as for vp_plan_row,
+ * kind in range, unused entries and reserved fields zero, 0 <= zero_before <= T, |shift| <= T (|shift| = T: the source
+ * lies wholly outside the window, its labels still renormalise y), scales and gauss finite and >= 0, noise_key zero when
+ * gauss is, 0 <= cut <= T, 0 <= gap_lo <= gap_hi <= T, and T <= 3072.  vp_train_step_bank_aug is vp_train_step_bank on such
+ * rows. */
+enum { VP_AUG_NONE = 0, VP_AUG_BANK = 1, VP_AUG_SELF = 2 };
+typedef struct {
+  vp_plan_row row;
+  int32_t kind;        /* VP_AUG_* */
+  int32_t zero_before;
+  int32_t shift;
+  float scale;
+} vp_aug_event;
+typedef struct {
+  vp_plan_row row;
+  int32_t kind;        /* VP_AUG_NONE or VP_AUG_BANK */
+  float scale;
+} vp_aug_noise;
+typedef struct {
+  vp_plan_row primary;
+  vp_aug_event event[2];
+  vp_aug_noise noise[2];
+  uint64_t noise_key;
+  float gauss;
+  int32_t cut;
+  int32_t gap_lo, gap_hi;
+} vp_aug_row;
+int vp_bank_make_batch_aug(vp_bank* bank, const vp_aug_row* rows, int B, int T, float sigma, int norm,
+                           const int* label_rows, float* x, float* y, void* stream);
+int vp_train_step_bank_aug(vp_trainer* t, vp_bank* bank, const vp_aug_row* rows, int B, float sigma, int norm,
+                           const int* label_rows, float lr, int update, double* loss);
+
 /* ---------------------------------------------------------------------------------------------
  * Multi-GPU bring-up.  The reference is single-GPU; windows are independent given the
  * weights, so the one exchange is the start-up broadcast of the flat weight blob from the root rank: a single

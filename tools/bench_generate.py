@@ -3,6 +3,11 @@ step against the plain one with the batch already resident, and the host path it
 
     python tools/bench_generate.py [--batch 512] [--traces 2048] [--steps 40] [--rounds 3]
     python tools/bench_generate.py --kernel-only [--reps 200]       # under rocprofv3 --kernel-trace --stats
+    python tools/bench_generate.py --augment [...]                  # AUG_ROW batches (AugmentedPlanner), both modes
+
+``--augment`` plans with the reference's stacking, noise and gap probabilities (the bank's first three quarters as
+event traces, the last quarter as noise traces), adds the planner's time per batch, and times the float64 numpy
+restatement of the same records (tests/augment_restate.py) as the host path.
 
 Prints one JSON line.  The bank holds synthetic 60 s three-component traces (6000 samples, one event each).
 """
@@ -18,7 +23,7 @@ sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 import torch  # noqa: E402
 
 from volpick_amd import PhaseNet  # noqa: E402
-from volpick_amd.generate import WaveformBank, WindowPlanner  # noqa: E402
+from volpick_amd.generate import AugmentedPlanner, WaveformBank, WindowPlanner  # noqa: E402
 from volpick_amd.synthetic import synthetic_stream_array  # noqa: E402
 from volpick_amd.train import PhaseNetTrainer, gaussian_labels  # noqa: E402
 
@@ -72,6 +77,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=3, help="alternating step / step_bank rounds per dtype")
     ap.add_argument("--kernel-only", action="store_true", help="only the generation kernel, --reps times (for rocprofv3)")
     ap.add_argument("--reps", type=int, default=200)
+    ap.add_argument("--augment", action="store_true", help="augmented rows (AugmentedPlanner) instead of block 1 alone")
     a = ap.parse_args()
     B = a.batch
     assert torch.cuda.is_available(), "bench_generate.py measures on the GPU"
@@ -79,10 +85,21 @@ def main():
     L = w.shape[2]
     bank = WaveformBank(w, {"P": p, "S": s})
     model = PhaseNet.from_pretrained("volpick")
-    planner = WindowPlanner(bank, B, seed=1)
+    if a.augment:
+        q = 3 * a.traces // 4
+        planner = AugmentedPlanner(bank, B, np.arange(q), np.arange(q, a.traces), seed=1, sigma=SIGMA)
+    else:
+        planner = WindowPlanner(bank, B, seed=1)
     plans = [next(planner.epoch()) for _ in range(8)]
     out = {"metric": "PhaseNet training batches generated on the GPU", "batch": B, "traces": a.traces, "trace_samples": L,
-           "norm": model.norm, "labels": model.labels}
+           "norm": model.norm, "labels": model.labels, "augment": a.augment}
+    if a.augment:
+        t0 = time.perf_counter()
+        for k in range(20):
+            planner.plan(np.arange(k * B, (k + 1) * B) % a.traces)
+        out["plan_ms_per_batch"] = (time.perf_counter() - t0) / 20 * 1e3
+        ev = np.concatenate(plans)["event"]["kind"]
+        out["event_entries_per_window"] = float((ev != 0).sum() / (len(plans) * B))
 
     # the kernel: one batch of B windows per launch
     for k in range(a.warmup):
@@ -99,7 +116,7 @@ def main():
     moved = B * 3 * 3001 * 4 * 3  # read x once (at most), write x and y
     out["make_batch_us_events"] = per
     out["make_batch_bytes"] = moved
-    out["make_batch_note"] = "device-event time per make_batch call (the launch plus the 16 KB row copy); kernel time: rocprofv3"
+    out["make_batch_note"] = "device-event time per make_batch call (the launch plus the row copy); kernel time: rocprofv3"
     if a.kernel_only:
         print(json.dumps(out))
         return
@@ -142,6 +159,20 @@ def main():
         xb[dtype] = res
         tr_a.close()
     out["train_step"] = xb
+
+    if a.augment:  # the host path for contrast: the float64 numpy restatement of the same records, 32 windows scaled to B
+        sys.path.insert(0, str(Path(__file__).resolve().parents[1] / "tests"))
+        import augment_restate as R
+
+        traces = list(w)
+        t0 = time.perf_counter()
+        for rec in plans[0][:32]:
+            R.execute(rec, traces, bank.onsets, 3001, SIGMA, model.norm, model.labels)
+        out["host_path"] = {"total_ms": (time.perf_counter() - t0) / 32 * B * 1e3,
+                            "note": "tests/augment_restate.py execute (float64 numpy, one thread), 32 windows scaled to B"}
+        bank.close()
+        print(json.dumps(out))
+        return
 
     # the host path for contrast: planner + numpy cut / normalise + gaussian_labels + upload
     w_flat = w.reshape(-1)

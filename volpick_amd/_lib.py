@@ -48,6 +48,30 @@ class VpPlanRow(C.Structure):
     _fields_ = [("trace", C.c_int32), ("reserved", C.c_int32), ("start", C.c_int64), ("lo", C.c_int64), ("hi", C.c_int64)]
 
 
+VP_AUG_NONE, VP_AUG_BANK, VP_AUG_SELF = 0, 1, 2
+
+
+class VpAugEvent(C.Structure):
+    _fields_ = [("row", VpPlanRow), ("kind", C.c_int32), ("zero_before", C.c_int32), ("shift", C.c_int32), ("scale", C.c_float)]
+
+
+class VpAugNoise(C.Structure):
+    _fields_ = [("row", VpPlanRow), ("kind", C.c_int32), ("scale", C.c_float)]
+
+
+class VpAugRow(C.Structure):
+    _fields_ = [
+        ("primary", VpPlanRow),
+        ("event", VpAugEvent * 2),
+        ("noise", VpAugNoise * 2),
+        ("noise_key", C.c_uint64),
+        ("gauss", C.c_float),
+        ("cut", C.c_int32),
+        ("gap_lo", C.c_int32),
+        ("gap_hi", C.c_int32),
+    ]
+
+
 class VpMseedRecord(C.Structure):
     _fields_ = [
         ("offset", C.c_int64),
@@ -206,6 +230,13 @@ SIGNATURES = {
         C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p],
     ),
     "vp_train_step_bank": (
+        C.c_int,
+        [_H, _H, C.c_void_p, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_int), C.c_float, C.c_int, C.POINTER(C.c_double)],
+    ),
+    "vp_bank_make_batch_aug": (
+        C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
+    "vp_train_step_bank_aug": (
         C.c_int,
         [_H, _H, C.c_void_p, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_int), C.c_float, C.c_int, C.POINTER(C.c_double)],
     ),

@@ -5,17 +5,18 @@
 
 namespace vp {
 
-// Plan rows staged for the device: pinned host slots copied to device slots on the launching stream.  The caller decides
-// when a slot may be refilled (the host copy of slot k must have been read by the copy a previous use enqueued).
+// Plan rows (vp_plan_row or vp_aug_row) staged for the device: pinned host slots copied to device slots on the launching
+// stream.  The caller decides when a slot may be refilled (the host copy of slot k must have been read by the copy a
+// previous use enqueued).
 struct RowRing {
   static constexpr int N = 8;
-  vp_plan_row* host[N] = {};
-  vp_plan_row* dev[N] = {};
-  int cap = 0;  // rows per slot
-  // Every slot is idle when this is called.  Grows the slots to hold n rows.
-  int reserve(int n);
+  void* host[N] = {};
+  void* dev[N] = {};
+  size_t cap = 0;  // bytes per slot
+  // Every slot is idle when this is called.  Grows the slots to hold `bytes`.
+  int reserve(size_t bytes);
   // rows -> host[slot] -> dev[slot] (async on s); returns dev[slot]
-  vp_plan_row* stage(int slot, const vp_plan_row* rows, int n, hipStream_t s);
+  void* stage(int slot, const void* rows, size_t bytes, hipStream_t s);
   ~RowRing();
 };
 
@@ -40,5 +41,9 @@ int bank_check(const Bank& bk, const vp_plan_row* rows, int B, int T, float sigm
 // x, y: (B, 3, T) fp32 on the bank's device.  Arguments already checked by bank_check.
 int bank_launch(const Bank& bk, const vp_plan_row* rows_dev, int B, int T, float sigma, int norm, const int* label_rows,
                 float* x, float* y, hipStream_t s);
+// The same for augmented rows (vp_bank_make_batch_aug): bank_check's arguments plus every field of every vp_aug_row.
+int bank_check_aug(const Bank& bk, const vp_aug_row* rows, int B, int T, float sigma, int norm, const int* label_rows);
+int bank_launch_aug(const Bank& bk, const vp_aug_row* rows_dev, int B, int T, float sigma, int norm, const int* label_rows,
+                    float* x, float* y, hipStream_t s);
 
 }  // namespace vp

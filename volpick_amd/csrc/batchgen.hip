@@ -16,6 +16,7 @@ struct GenArgs {
   const long long* len;
   const double* onset;  // [trace][4]
   const vp_plan_row* rows;
+  const vp_aug_row* aug;  // bank_aug_kernel's records (rows unused)
   float* x;
   float* y;
   int T;
@@ -26,6 +27,7 @@ struct GenArgs {
 
 constexpr int GEN_NTH = 1024, GEN_NWV = GEN_NTH / 64, GEN_MAXE = 6;  // T <= 6144: the window lives in registers
 constexpr int GEN_MAX_T = GEN_NTH * GEN_MAXE;
+constexpr int AUG_MAXE = 3, AUG_MAX_T = GEN_NTH * AUG_MAXE;  // bank_aug_kernel holds x, a source and P / S: T <= 3072
 
 __device__ __forceinline__ double wave_sum_d(double v) {
 #pragma unroll
@@ -37,51 +39,69 @@ __device__ __forceinline__ double wave_max_d(double v) {
   for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
   return v;
 }
+__device__ __forceinline__ float wave_max_f(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+  return v;
+}
 
-// Statistics in float64: a constant channel demeans to exact zeros (as numpy's float64 mean of float32 samples does), and
-// the quotient is rounded to fp32 once.  The gather reads [lo, hi) of the row's trace only; lo / hi were checked against
-// the trace's length on the host (bank_check).
-__global__ __launch_bounds__(GEN_NTH) void bank_batch_kernel(const GenArgs a) {
-  __shared__ double red[3][GEN_NWV];
-  __shared__ double stat[3];
-  const int w = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int T = a.T;
-  const vp_plan_row r = a.rows[w];
+// Reduction scratch of the statistics below.  Each function's first write to red follows the barrier behind its
+// predecessor's last read of it, and every thread reads the result before the next function's second barrier, so calls
+// may follow each other without a barrier in between.
+struct GenShared {
+  double red[3][GEN_NWV];
+  double stat[3];
+  float redf[3][GEN_NWV];
+  float statf[3];
+};
+
+// x[c][t] = src[c][start + t] where lo <= start + t < hi (t < T), else 0.  lo / hi were checked against the trace's length
+// on the host (bank_check).
+template <int E>
+__device__ __forceinline__ void gather_window(const GenArgs& a, const vp_plan_row& r, int tid, float v[3][E]) {
   const long long L = a.len[r.trace];
-  const float* src = a.data + a.off[r.trace];
+  const float* src = a.data + a.off[r.trace] + r.start;  // uniform: the loads below take a 32-bit per-lane offset
+#pragma unroll
+  for (int k = 0; k < E; ++k) {
+    const unsigned t = tid + k * GEN_NTH;
+    const long long i = r.start + t;
+    const bool in = t < (unsigned)a.T && i >= r.lo && i < r.hi;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c][k] = in ? src[c * L + t] : 0.f;
+  }
+}
 
-  float v[3][GEN_MAXE];
+// Per-channel mean and normaliser of v over the T samples, in float64: a constant channel demeans to exact zeros (as
+// numpy's float64 mean of float32 samples does), and the quotient (v - mean) / den is rounded to fp32 once.
+// den = max|v - mean| (peak) or the population standard deviation, plus 1e-10.
+template <int E>
+__device__ __forceinline__ void window_stats(const float v[3][E], int T, bool peak, int tid, GenShared& sh,
+                                             double mean[3], double den[3]) {
+  const int lane = tid & 63, wave = tid >> 6;
   double s[3] = {0.0, 0.0, 0.0};
 #pragma unroll
-  for (int k = 0; k < GEN_MAXE; ++k) {
-    const int t = tid + k * GEN_NTH;
-    const long long i = r.start + t;
-    const bool in = t < T && i >= r.lo && i < r.hi;
+  for (int k = 0; k < E; ++k)
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      v[c][k] = in ? src[c * L + i] : 0.f;
-      s[c] += (double)v[c][k];
-    }
-  }
+    for (int c = 0; c < 3; ++c) s[c] += (double)v[c][k];
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     const double ws = wave_sum_d(s[c]);
-    if (lane == 0) red[c][wave] = ws;
+    if (lane == 0) sh.red[c][wave] = ws;
   }
   __syncthreads();
   if (tid < 3) {
     double acc = 0.0;
-    for (int i = 0; i < GEN_NWV; ++i) acc += red[tid][i];
-    stat[tid] = acc / (double)T;
+    for (int i = 0; i < GEN_NWV; ++i) acc += sh.red[tid][i];
+    sh.stat[tid] = acc / (double)T;
   }
   __syncthreads();
-  const double mean[3] = {stat[0], stat[1], stat[2]};
-  const bool peak = a.norm == VP_NORM_PEAK;  // uniform
+#pragma unroll
+  for (int c = 0; c < 3; ++c) mean[c] = sh.stat[c];
   double m[3] = {0.0, 0.0, 0.0};
 #pragma unroll
   for (int c = 0; c < 3; ++c)
 #pragma unroll
-    for (int k = 0; k < GEN_MAXE; ++k)
+    for (int k = 0; k < E; ++k)
       if (tid + k * GEN_NTH < T) {
         const double d = (double)v[c][k] - mean[c];
         m[c] = peak ? fmax(m[c], fabs(d)) : m[c] + d * d;
@@ -90,56 +110,282 @@ __global__ __launch_bounds__(GEN_NTH) void bank_batch_kernel(const GenArgs a) {
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     const double wm = peak ? wave_max_d(m[c]) : wave_sum_d(m[c]);
-    if (lane == 0) red[c][wave] = wm;
+    if (lane == 0) sh.red[c][wave] = wm;
   }
   __syncthreads();
   if (tid < 3) {
     double acc = 0.0;
-    for (int i = 0; i < GEN_NWV; ++i) acc = peak ? fmax(acc, red[tid][i]) : acc + red[tid][i];
-    stat[tid] = (peak ? acc : sqrt(acc / (double)T)) + 1e-10;
+    for (int i = 0; i < GEN_NWV; ++i) acc = peak ? fmax(acc, sh.red[tid][i]) : acc + sh.red[tid][i];
+    sh.stat[tid] = (peak ? acc : sqrt(acc / (double)T)) + 1e-10;
   }
   __syncthreads();
-  float* xw = a.x + (long long)w * 3 * T;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) den[c] = sh.stat[c];
+}
+
+// Per-channel maximum of m over the workgroup (fp32; m >= 0 or any sign, as the caller reduces).
+__device__ __forceinline__ void block_max3(float m[3], int tid, GenShared& sh) {
+  const int lane = tid & 63, wave = tid >> 6;
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
-    const double den = stat[c];
-#pragma unroll
-    for (int k = 0; k < GEN_MAXE; ++k) {
-      const int t = tid + k * GEN_NTH;
-      if (t < T) xw[(long long)c * T + t] = (float)(((double)v[c][k] - mean[c]) / den);
-    }
+    const float wm = wave_max_f(m[c]);
+    if (lane == 0) sh.redf[c][wave] = wm;
   }
+  __syncthreads();
+  if (tid < 3) {
+    float acc = sh.redf[tid][0];
+    for (int i = 1; i < GEN_NWV; ++i) acc = fmaxf(acc, sh.redf[tid][i]);
+    sh.statf[tid] = acc;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int c = 0; c < 3; ++c) m[c] = sh.statf[c];
+}
 
-  // labels: the onsets relative to the window start in float64 (traces of 10^6+ samples keep the fraction), the
-  // distance to each sample narrowed to fp32 only once it is small where the Gaussian is not
-  double o[4];
-  bool has[4];
+// A window's onsets relative to its start in float64 (traces of 10^6+ samples keep the fraction); has[j] = finite.
+__device__ __forceinline__ void window_onsets(const GenArgs& a, const vp_plan_row& r, double o[4], bool has[4]) {
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const double on = a.onset[(long long)r.trace * 4 + j];
     has[j] = isfinite(on);
     o[j] = on - (double)r.start;
   }
+}
+
+// P (ph[0]) and S (ph[1]) at window sample t: the maximum over the phase's onsets of exp(-(t - o)^2 / two_s2), the
+// distance narrowed to fp32 only once it is small where the Gaussian is not.
+__device__ __forceinline__ void phase_labels(const double o[4], const bool has[4], long long t, float two_s2, float ph[2]) {
+  ph[0] = ph[1] = 0.f;
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    if (has[j]) {
+      const float d = (float)((double)t - o[j]);
+      ph[j >> 1] = fmaxf(ph[j >> 1], expf(-(d * d) / two_s2));
+    }
+}
+
+__global__ __launch_bounds__(GEN_NTH) void bank_batch_kernel(const GenArgs a) {
+  __shared__ GenShared sh;
+  const int w = blockIdx.x, tid = threadIdx.x;
+  const int T = a.T;
+  const vp_plan_row r = a.rows[w];
+
+  float v[3][GEN_MAXE];
+  gather_window(a, r, tid, v);
+  double mean[3], den[3];
+  window_stats(v, T, a.norm == VP_NORM_PEAK, tid, sh, mean, den);
+  float* xw = a.x + (long long)w * 3 * T;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+#pragma unroll
+    for (int k = 0; k < GEN_MAXE; ++k) {
+      const int t = tid + k * GEN_NTH;
+      if (t < T) xw[(long long)c * T + t] = (float)(((double)v[c][k] - mean[c]) / den[c]);
+    }
+  }
+
+  double o[4];
+  bool has[4];
+  window_onsets(a, r, o, has);
   const float two_s2 = 2.f * a.sigma * a.sigma;
   float* yw = a.y + (long long)w * 3 * T;
   for (int t = tid; t < T; t += GEN_NTH) {
-    float ph[2] = {0.f, 0.f};
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (has[j]) {
-        const float d = (float)((double)t - o[j]);
-        ph[j >> 1] = fmaxf(ph[j >> 1], expf(-(d * d) / two_s2));
-      }
+    float ph[2];
+    phase_labels(o, has, t, two_s2, ph);
     yw[(long long)a.row_p * T + t] = ph[0];
     yw[(long long)a.row_s * T + t] = ph[1];
     yw[(long long)a.row_n * T + t] = fminf(fmaxf(1.f - ph[0] - ph[1], 0.f), 1.f);
   }
 }
 
+// Philox4x32-10 (Salmon et al., SC'11): ctr <- the bijection of ctr under key.
+__device__ __forceinline__ void philox4x32_10(uint32_t ctr[4], uint32_t k0, uint32_t k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t h0 = __umulhi(0xD2511F53u, ctr[0]), l0 = 0xD2511F53u * ctr[0];
+    const uint32_t h1 = __umulhi(0xCD9E8D57u, ctr[2]), l1 = 0xCD9E8D57u * ctr[2];
+    const uint32_t c1 = ctr[1], c3 = ctr[3];
+    ctr[0] = h1 ^ c1 ^ k0;
+    ctr[1] = l1;
+    ctr[2] = h0 ^ c3 ^ k1;
+    ctr[3] = l0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+}
+
+// The standard normal of (key, channel c, sample t): include/volpick_hip.h, vp_aug_row step 5.
+__device__ __forceinline__ double gauss_noise(uint64_t key, int c, int t) {
+  uint32_t w[4] = {(uint32_t)t, (uint32_t)c, 0u, 0u};
+  philox4x32_10(w, (uint32_t)key, (uint32_t)(key >> 32));
+  const double u0 = (double)((((uint64_t)w[1] << 32) | w[0]) >> 11) * 0x1p-53;
+  const double u1 = (double)((((uint64_t)w[3] << 32) | w[2]) >> 11) * 0x1p-53;
+  return sqrt(-2.0 * log(1.0 - u0)) * cos(2.0 * M_PI * u1);
+}
+
+// One augmented window per workgroup (include/volpick_hip.h, vp_aug_row): the record's steps in order, x and the P / S
+// labels in registers, each source shifted through LDS one channel at a time.
+__global__ __launch_bounds__(GEN_NTH) void bank_aug_kernel(const GenArgs a) {
+  __shared__ GenShared sh;
+  __shared__ float stage[AUG_MAX_T];
+  const int w = blockIdx.x, tid = threadIdx.x;
+  const int T = a.T;
+  const vp_aug_row& rec = a.aug[w];
+  const bool peak = a.norm == VP_NORM_PEAK;
+  const float two_s2 = 2.f * a.sigma * a.sigma;
+
+  // 1. the primary window, as bank_batch_kernel writes it
+  float x[3][AUG_MAXE], s[3][AUG_MAXE], P[AUG_MAXE], S[AUG_MAXE];
+  // a window cut and normalised into v (the primary, or a source); with zero_rule, its channels zeroed where the current
+  // x is all |x| <= 1e-8.  Returns max|x| of the current x over every channel (zero_rule only).
+  auto load = [&](const vp_plan_row& r, float v[3][AUG_MAXE], bool zero_rule) -> float {
+    gather_window(a, r, tid, v);
+    double mean[3], den[3];
+    window_stats(v, T, peak, tid, sh, mean, den);
+    float m[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+      for (int k = 0; k < AUG_MAXE; ++k) {
+        v[c][k] = tid + k * GEN_NTH < T ? (float)(((double)v[c][k] - mean[c]) / den[c]) : 0.f;
+        if (zero_rule) m[c] = fmaxf(m[c], fabsf(x[c][k]));
+      }
+    if (!zero_rule) return 0.f;
+    block_max3(m, tid, sh);
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      if (!(m[c] > 1e-8f))
+#pragma unroll
+        for (int k = 0; k < AUG_MAXE; ++k) v[c][k] = 0.f;
+    return fmaxf(fmaxf(m[0], m[1]), m[2]);
+  };
+  const vp_plan_row pr = rec.primary;
+  double po[4];
+  bool phas[4];
+  load(pr, x, false);
+  window_onsets(a, pr, po, phas);
+#pragma unroll
+  for (int k = 0; k < AUG_MAXE; ++k) {
+    float ph[2];
+    phase_labels(po, phas, tid + k * GEN_NTH, two_s2, ph);
+    P[k] = ph[0];
+    S[k] = ph[1];
+  }
+  // 2. the truncation behind the first event
+  const int cut = rec.cut;
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int k = 0; k < AUG_MAXE; ++k)
+      if (tid + k * GEN_NTH >= cut) x[c][k] = 0.f;
+
+  bool renorm = false;  // y renormalised by an event: noise = 1 - P - S, else clip(1 - P - S, 0, 1)
+  // 3. events
+#pragma unroll 1
+  for (int i = 0; i < 2; ++i) {
+    const vp_aug_event& ev = rec.event[i];
+    if (ev.kind == VP_AUG_NONE) continue;
+    double so[4];
+    bool shas[4];
+    // a duplicate is the primary window as step 1 left it: cut and normalised again, to the same bits
+    const vp_plan_row& sr = ev.kind == VP_AUG_BANK ? ev.row : pr;
+    load(sr, s, ev.kind == VP_AUG_BANK);
+    window_onsets(a, sr, so, shas);
+    const int zb = ev.zero_before, d = ev.shift;
+    const float scale = ev.scale;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+#pragma unroll
+      for (int k = 0; k < AUG_MAXE; ++k) {
+        const int t = tid + k * GEN_NTH;
+        if (t < T) stage[t] = t < zb ? 0.f : s[c][k];
+      }
+      __syncthreads();
+#pragma unroll
+      for (int k = 0; k < AUG_MAXE; ++k) {
+        const int t = tid + k * GEN_NTH, ts = t - d;
+        if (t < T && ts >= 0 && ts < T) x[c][k] += scale * stage[ts];
+      }
+      __syncthreads();
+    }
+#pragma unroll
+    for (int k = 0; k < AUG_MAXE; ++k) {
+      const int t = tid + k * GEN_NTH, ts = t - d;
+      float ph[2] = {0.f, 0.f};
+      if (ts >= 0 && ts < T) phase_labels(so, shas, ts, two_s2, ph);
+      const float p = fmaxf(P[k], ph[0]), q = fmaxf(S[k], ph[1]);
+      const float dn = fmaxf(1.f, p + q);
+      P[k] = p / dn;
+      S[k] = q / dn;
+    }
+    renorm = true;
+  }
+
+  // 4. noise windows
+#pragma unroll 1
+  for (int j = 0; j < 2; ++j) {
+    const vp_aug_noise& nz = rec.noise[j];
+    if (nz.kind == VP_AUG_NONE) continue;
+    const float amax = load(nz.row, s, true);
+    const float f = amax * nz.scale;
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+      for (int k = 0; k < AUG_MAXE; ++k) x[c][k] += s[c][k] * f;
+  }
+
+  // 5. Gaussian noise scaled by the signed maximum of x
+  if (rec.gauss > 0.f) {
+    float m[3] = {-INFINITY, -INFINITY, -INFINITY};
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+      for (int k = 0; k < AUG_MAXE; ++k)
+        if (tid + k * GEN_NTH < T) m[c] = fmaxf(m[c], x[c][k]);
+    block_max3(m, tid, sh);
+    const double f = (double)rec.gauss * (double)fmaxf(fmaxf(m[0], m[1]), m[2]);
+    const uint64_t key = rec.noise_key;
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+      for (int k = 0; k < AUG_MAXE; ++k) {
+        const int t = tid + k * GEN_NTH;
+        if (t < T) x[c][k] = (float)((double)x[c][k] + f * gauss_noise(key, c, t));
+      }
+  }
+
+  // 6. the gap, 7. the second normalisation
+  const int g0 = rec.gap_lo, g1 = rec.gap_hi;
+#pragma unroll
+  for (int k = 0; k < AUG_MAXE; ++k) {
+    const int t = tid + k * GEN_NTH;
+    if (t >= g0 && t < g1) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) x[c][k] = 0.f;
+      P[k] = S[k] = 0.f;
+    }
+  }
+  double mean[3], den[3];
+  window_stats(x, T, peak, tid, sh, mean, den);
+  float* xw = a.x + (long long)w * 3 * T;
+  float* yw = a.y + (long long)w * 3 * T;
+#pragma unroll
+  for (int k = 0; k < AUG_MAXE; ++k) {
+    const int t = tid + k * GEN_NTH;
+    if (t >= T) continue;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) xw[(long long)c * T + t] = (float)(((double)x[c][k] - mean[c]) / den[c]);
+    const float n = 1.f - P[k] - S[k];
+    yw[(long long)a.row_p * T + t] = P[k];
+    yw[(long long)a.row_s * T + t] = S[k];
+    yw[(long long)a.row_n * T + t] = renorm ? n : fminf(fmaxf(n, 0.f), 1.f);
+  }
+}
+
 }  // namespace
 
-int RowRing::reserve(int n) {
-  if (n <= cap) return VP_OK;
+int RowRing::reserve(size_t bytes) {
+  if (bytes <= cap) return VP_OK;
   for (int i = 0; i < N; ++i) {
     if (host[i]) VP_HIP(hipHostFree(host[i]));
     if (dev[i]) VP_HIP(hipFree(dev[i]));
@@ -148,16 +394,16 @@ int RowRing::reserve(int n) {
   }
   cap = 0;
   for (int i = 0; i < N; ++i) {
-    VP_HIP(hipHostMalloc((void**)&host[i], (size_t)n * sizeof(vp_plan_row), hipHostMallocDefault));
-    VP_HIP(hipMalloc((void**)&dev[i], (size_t)n * sizeof(vp_plan_row)));
+    VP_HIP(hipHostMalloc(&host[i], bytes, hipHostMallocDefault));
+    VP_HIP(hipMalloc(&dev[i], bytes));
   }
-  cap = n;
+  cap = bytes;
   return VP_OK;
 }
 
-vp_plan_row* RowRing::stage(int slot, const vp_plan_row* rows, int n, hipStream_t s) {
-  memcpy(host[slot], rows, (size_t)n * sizeof(vp_plan_row));
-  if (hipMemcpyAsync(dev[slot], host[slot], (size_t)n * sizeof(vp_plan_row), hipMemcpyHostToDevice, s) != hipSuccess) {
+void* RowRing::stage(int slot, const void* rows, size_t bytes, hipStream_t s) {
+  memcpy(host[slot], rows, bytes);
+  if (hipMemcpyAsync(dev[slot], host[slot], bytes, hipMemcpyHostToDevice, s) != hipSuccess) {
     set_error("plan rows: hipMemcpyAsync failed");
     return nullptr;
   }
@@ -178,8 +424,10 @@ Bank::~Bank() {
     if (e) (void)hipEventDestroy(e);
 }
 
-int bank_check(const Bank& bk, const vp_plan_row* rows, int B, int T, float sigma, int norm, const int* label_rows) {
-  VP_REQUIRE(rows && label_rows, "bank batch: null rows or label_rows");
+namespace {
+
+int args_check(int B, int T, float sigma, int norm, const int* label_rows) {
+  VP_REQUIRE(label_rows, "bank batch: null label_rows");
   VP_REQUIRE(B >= 1, "bank batch: B = %d", B);
   VP_REQUIRE(T >= 1 && T <= GEN_MAX_T, "bank batch: T = %d outside [1, %d]", T, GEN_MAX_T);
   VP_REQUIRE(std::isfinite(sigma) && sigma > 0.f, "bank batch: sigma = %g must be finite and > 0", (double)sigma);
@@ -190,28 +438,48 @@ int bank_check(const Bank& bk, const vp_plan_row* rows, int B, int T, float sigm
     seen |= 1 << label_rows[i];
   }
   VP_REQUIRE(seen == 7, "bank batch: label_rows is not a permutation of 0, 1, 2");
+  return VP_OK;
+}
+
+// One vp_plan_row against the bank (`what`: where it sits in the batch, for the message).
+int row_check(const Bank& bk, const vp_plan_row& r, int b, const char* what) {
+  VP_REQUIRE(r.trace >= 0 && r.trace < bk.n_written, "bank batch: %s %d: trace %d outside [0, %lld)", what, b, (int)r.trace,
+             bk.n_written);
+  const long long L = bk.len[r.trace];
+  VP_REQUIRE(r.lo >= 0 && r.lo <= r.hi && r.hi <= L, "bank batch: %s %d: [lo, hi) = [%lld, %lld) outside [0, %lld]", what,
+             b, (long long)r.lo, (long long)r.hi, L);
+  // start + t must not overflow for t < T (the kernel's index arithmetic)
+  VP_REQUIRE(r.start > -(1LL << 62) && r.start < (1LL << 62), "bank batch: %s %d: start %lld out of range", what, b,
+             (long long)r.start);
+  return VP_OK;
+}
+
+bool row_is_zero(const vp_plan_row& r) { return !r.trace && !r.reserved && !r.start && !r.lo && !r.hi; }
+
+}  // namespace
+
+int bank_check(const Bank& bk, const vp_plan_row* rows, int B, int T, float sigma, int norm, const int* label_rows) {
+  VP_REQUIRE(rows, "bank batch: null rows");
+  const int rc = args_check(B, T, sigma, norm, label_rows);
+  if (rc != VP_OK) return rc;
   for (int b = 0; b < B; ++b) {
-    const vp_plan_row& r = rows[b];
-    VP_REQUIRE(r.trace >= 0 && r.trace < bk.n_written, "bank batch: row %d: trace %d outside [0, %lld)", b, (int)r.trace,
-               bk.n_written);
-    const long long L = bk.len[r.trace];
-    VP_REQUIRE(r.lo >= 0 && r.lo <= r.hi && r.hi <= L, "bank batch: row %d: [lo, hi) = [%lld, %lld) outside [0, %lld]", b,
-               (long long)r.lo, (long long)r.hi, L);
-    // start + t must not overflow for t < T (the kernel's index arithmetic)
-    VP_REQUIRE(r.start > -(1LL << 62) && r.start < (1LL << 62), "bank batch: row %d: start %lld out of range", b,
-               (long long)r.start);
+    const int rc = row_check(bk, rows[b], b, "row");
+    if (rc != VP_OK) return rc;
   }
   return VP_OK;
 }
 
-int bank_launch(const Bank& bk, const vp_plan_row* rows_dev, int B, int T, float sigma, int norm, const int* label_rows,
-                float* x, float* y, hipStream_t s) {
+namespace {
+
+int launch(void (*kernel)(GenArgs), const char* name, const Bank& bk, const vp_plan_row* rows_dev, const vp_aug_row* aug_dev,
+           int B, int T, float sigma, int norm, const int* label_rows, float* x, float* y, hipStream_t s) {
   GenArgs a{};
   a.data = bk.data;
   a.off = bk.off_dev;
   a.len = bk.len_dev;
   a.onset = bk.onset_dev;
   a.rows = rows_dev;
+  a.aug = aug_dev;
   a.x = x;
   a.y = y;
   a.T = T;
@@ -220,18 +488,123 @@ int bank_launch(const Bank& bk, const vp_plan_row* rows_dev, int B, int T, float
   a.row_p = label_rows[0];
   a.row_s = label_rows[1];
   a.row_n = label_rows[2];
-  hipLaunchKernelGGL(bank_batch_kernel, dim3(B), dim3(GEN_NTH), 0, s, a);
+  hipLaunchKernelGGL(kernel, dim3(B), dim3(GEN_NTH), 0, s, a);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
-    set_error("bank_batch_kernel launch failed: %s", hipGetErrorString(e));
+    set_error("%s launch failed: %s", name, hipGetErrorString(e));
     return VP_ERR_HIP;
   }
   return VP_OK;
 }
 
+}  // namespace
+
+int bank_launch(const Bank& bk, const vp_plan_row* rows_dev, int B, int T, float sigma, int norm, const int* label_rows,
+                float* x, float* y, hipStream_t s) {
+  return launch(bank_batch_kernel, "bank_batch_kernel", bk, rows_dev, nullptr, B, T, sigma, norm, label_rows, x, y, s);
+}
+
+int bank_check_aug(const Bank& bk, const vp_aug_row* rows, int B, int T, float sigma, int norm, const int* label_rows) {
+  VP_REQUIRE(rows, "bank batch: null rows");
+  int rc = args_check(B, T, sigma, norm, label_rows);
+  if (rc != VP_OK) return rc;
+  VP_REQUIRE(T <= AUG_MAX_T, "bank batch: augmented rows: T = %d outside [1, %d]", T, AUG_MAX_T);
+  for (int b = 0; b < B; ++b) {
+    const vp_aug_row& r = rows[b];
+    if ((rc = row_check(bk, r.primary, b, "row")) != VP_OK) return rc;
+    for (int i = 0; i < 2; ++i) {
+      const vp_aug_event& e = r.event[i];
+      VP_REQUIRE(e.kind >= VP_AUG_NONE && e.kind <= VP_AUG_SELF, "bank batch: row %d: event %d: kind %d", b, i, (int)e.kind);
+      if (e.kind == VP_AUG_NONE) {
+        VP_REQUIRE(row_is_zero(e.row) && !e.zero_before && !e.shift && e.scale == 0.f,
+                   "bank batch: row %d: event %d is unused but not zero", b, i);
+        continue;
+      }
+      if (e.kind == VP_AUG_BANK) {
+        if ((rc = row_check(bk, e.row, b, "event source of row")) != VP_OK) return rc;
+      } else {
+        VP_REQUIRE(row_is_zero(e.row), "bank batch: row %d: event %d duplicates the window but has a source row", b, i);
+      }
+      VP_REQUIRE(e.zero_before >= 0 && e.zero_before <= T, "bank batch: row %d: event %d: zero_before %d outside [0, %d]",
+                 b, i, (int)e.zero_before, T);
+      VP_REQUIRE(e.shift >= -T && e.shift <= T, "bank batch: row %d: event %d: |shift| = |%d| > T = %d", b, i, (int)e.shift,
+                 T);
+      VP_REQUIRE(std::isfinite(e.scale) && e.scale >= 0.f, "bank batch: row %d: event %d: scale %g", b, i, (double)e.scale);
+    }
+    for (int j = 0; j < 2; ++j) {
+      const vp_aug_noise& n = r.noise[j];
+      VP_REQUIRE(n.kind == VP_AUG_NONE || n.kind == VP_AUG_BANK, "bank batch: row %d: noise %d: kind %d", b, j, (int)n.kind);
+      if (n.kind == VP_AUG_NONE) {
+        VP_REQUIRE(row_is_zero(n.row) && n.scale == 0.f, "bank batch: row %d: noise %d is unused but not zero", b, j);
+        continue;
+      }
+      if ((rc = row_check(bk, n.row, b, "noise source of row")) != VP_OK) return rc;
+      VP_REQUIRE(std::isfinite(n.scale) && n.scale >= 0.f, "bank batch: row %d: noise %d: scale %g", b, j, (double)n.scale);
+    }
+    VP_REQUIRE(std::isfinite(r.gauss) && r.gauss >= 0.f, "bank batch: row %d: gauss %g", b, (double)r.gauss);
+    VP_REQUIRE(r.gauss > 0.f || r.noise_key == 0, "bank batch: row %d: a noise key without Gaussian noise", b);
+    VP_REQUIRE(r.cut >= 0 && r.cut <= T, "bank batch: row %d: cut %d outside [0, %d]", b, (int)r.cut, T);
+    VP_REQUIRE(r.gap_lo >= 0 && r.gap_lo <= r.gap_hi && r.gap_hi <= T, "bank batch: row %d: gap [%d, %d) outside [0, %d]", b,
+               (int)r.gap_lo, (int)r.gap_hi, T);
+  }
+  return VP_OK;
+}
+
+int bank_launch_aug(const Bank& bk, const vp_aug_row* rows_dev, int B, int T, float sigma, int norm, const int* label_rows,
+                    float* x, float* y, hipStream_t s) {
+  return launch(bank_aug_kernel, "bank_aug_kernel", bk, nullptr, rows_dev, B, T, sigma, norm, label_rows, x, y, s);
+}
+
 }  // namespace vp
 
 using namespace vp;
+
+namespace {
+
+int check_rows(const Bank& bk, const vp_plan_row* rows, int B, int T, float sigma, int norm, const int* lr) {
+  return bank_check(bk, rows, B, T, sigma, norm, lr);
+}
+int check_rows(const Bank& bk, const vp_aug_row* rows, int B, int T, float sigma, int norm, const int* lr) {
+  return bank_check_aug(bk, rows, B, T, sigma, norm, lr);
+}
+int launch_rows(const Bank& bk, const vp_plan_row* rd, int B, int T, float sigma, int norm, const int* lr, float* x, float* y,
+                hipStream_t s) {
+  return bank_launch(bk, rd, B, T, sigma, norm, lr, x, y, s);
+}
+int launch_rows(const Bank& bk, const vp_aug_row* rd, int B, int T, float sigma, int norm, const int* lr, float* x, float* y,
+                hipStream_t s) {
+  return bank_launch_aug(bk, rd, B, T, sigma, norm, lr, x, y, s);
+}
+
+// vp_bank_make_batch(_aug): rows staged through the bank's ring, slot k reused once the kernel that last read it has run.
+template <class Row>
+int make_batch(Bank& bk, const Row* rows, int B, int T, float sigma, int norm, const int* label_rows, float* x, float* y,
+               void* stream) {
+  const int rc = check_rows(bk, rows, B, T, sigma, norm, label_rows);
+  if (rc != VP_OK) return rc;
+  VP_HIP(hipSetDevice(bk.device));
+  const int slot = (int)(bk.batches % RowRing::N);
+  const size_t bytes = (size_t)B * sizeof(Row);
+  if (bytes > bk.ring.cap) {  // every slot idle before the ring is reallocated
+    for (int i = 0; i < RowRing::N; ++i)
+      if (bk.ev_used[i]) VP_HIP(hipEventSynchronize(bk.ev[i]));
+    const int r = bk.ring.reserve(bytes);
+    if (r != VP_OK) return r;
+  } else if (bk.ev_used[slot]) {
+    VP_HIP(hipEventSynchronize(bk.ev[slot]));  // the kernel that read this slot last (and so the copy into it) has run
+  }
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const Row* rd = static_cast<const Row*>(bk.ring.stage(slot, rows, bytes, s));
+  if (!rd) return VP_ERR_HIP;
+  const int r = launch_rows(bk, rd, B, T, sigma, norm, label_rows, x, y, s);
+  if (r != VP_OK) return r;
+  VP_HIP(hipEventRecord(bk.ev[slot], s));
+  bk.ev_used[slot] = true;
+  ++bk.batches;
+  return VP_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -299,28 +672,13 @@ int vp_bank_destroy(vp_bank* h) {
 int vp_bank_make_batch(vp_bank* h, const vp_plan_row* rows, int B, int T, float sigma, int norm, const int* label_rows,
                        float* x, float* y, void* stream) {
   VP_REQUIRE(h && x && y, "vp_bank_make_batch: null argument");
-  Bank& bk = *reinterpret_cast<Bank*>(h);
-  const int rc = bank_check(bk, rows, B, T, sigma, norm, label_rows);
-  if (rc != VP_OK) return rc;
-  VP_HIP(hipSetDevice(bk.device));
-  const int slot = (int)(bk.batches % RowRing::N);
-  if (B > bk.ring.cap) {  // every slot idle before the ring is reallocated
-    for (int i = 0; i < RowRing::N; ++i)
-      if (bk.ev_used[i]) VP_HIP(hipEventSynchronize(bk.ev[i]));
-    const int r = bk.ring.reserve(B);
-    if (r != VP_OK) return r;
-  } else if (bk.ev_used[slot]) {
-    VP_HIP(hipEventSynchronize(bk.ev[slot]));  // the kernel that read this slot last (and so the copy into it) has run
-  }
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const vp_plan_row* rd = bk.ring.stage(slot, rows, B, s);
-  if (!rd) return VP_ERR_HIP;
-  const int r = bank_launch(bk, rd, B, T, sigma, norm, label_rows, x, y, s);
-  if (r != VP_OK) return r;
-  VP_HIP(hipEventRecord(bk.ev[slot], s));
-  bk.ev_used[slot] = true;
-  ++bk.batches;
-  return VP_OK;
+  return make_batch(*reinterpret_cast<Bank*>(h), rows, B, T, sigma, norm, label_rows, x, y, stream);
+}
+
+int vp_bank_make_batch_aug(vp_bank* h, const vp_aug_row* rows, int B, int T, float sigma, int norm, const int* label_rows,
+                           float* x, float* y, void* stream) {
+  VP_REQUIRE(h && x && y, "vp_bank_make_batch_aug: null argument");
+  return make_batch(*reinterpret_cast<Bank*>(h), rows, B, T, sigma, norm, label_rows, x, y, stream);
 }
 
 }  // extern "C"

@@ -249,7 +249,7 @@ struct Trainer {
   double* head_stage = nullptr; // [64][28]
   float* x_dev = nullptr;       // staging for host inputs, and where vp_train_step_bank generates its batch
   float* y_dev = nullptr;
-  RowRing plan_rows;            // vp_train_step_bank's plan rows: slot seq % EV_RING, free again at ev_inputs of that slot
+  RowRing plan_rows;            // vp_train_step_bank(_aug)'s rows: slot seq % EV_RING, free again at ev_inputs of that slot
   float* p_dev = nullptr;       // predictions of the last step
   long step = 0;
   float beta1 = 0.9f, beta2 = 0.999f, adam_eps = 1e-8f, bn_eps = 1e-3f, bn_momentum = 0.1f, loss_eps = 1e-5f;
@@ -946,6 +946,34 @@ int step_and_loss(Trainer& tr, const float* x_dev, const float* y_dev, int B, fl
   return VP_OK;
 }
 
+// vp_train_step_bank(_aug): exactly one of rows / aug is set.
+int step_bank(Trainer& tr, const Bank& bk, const vp_plan_row* rows, const vp_aug_row* aug, int B, float sigma, int norm,
+              const int* label_rows, float lr, int update, double* loss) {
+  VP_REQUIRE(B >= 2 && B <= tr.max_batch, "vp_train_step_bank: batch %d outside [2, %d]", B, tr.max_batch);
+  VP_REQUIRE(bk.device == tr.device, "vp_train_step_bank: bank on device %d, trainer on device %d", bk.device, tr.device);
+  static_assert(RowRing::N == Trainer::EV_RING, "one plan-row slot per step event");
+  int rc = aug ? bank_check_aug(bk, aug, B, T0, sigma, norm, label_rows) : bank_check(bk, rows, B, T0, sigma, norm, label_rows);
+  if (rc != VP_OK) return rc;
+  VP_HIP(hipSetDevice(tr.device));
+  if (!tr.plan_rows.cap) {  // once, for either kind of row: a regrowth would have to wait for every slot
+    rc = tr.plan_rows.reserve((size_t)tr.max_batch * std::max(sizeof(vp_plan_row), sizeof(vp_aug_row)));
+    if (rc != VP_OK) return rc;
+  }
+  // the step that used this slot last: its ev_inputs stands behind the head kernel, which runs after the generation kernel
+  // that read the slot's device copy, which ran after the copy that read the host slot
+  const int slot = (int)(tr.seq % Trainer::EV_RING);
+  if (tr.ev_inputs_seq[slot] >= 0) VP_HIP(hipEventSynchronize(tr.ev_inputs[slot]));
+  const void* rd = aug ? tr.plan_rows.stage(slot, aug, (size_t)B * sizeof(vp_aug_row), tr.stream)
+                       : tr.plan_rows.stage(slot, rows, (size_t)B * sizeof(vp_plan_row), tr.stream);
+  if (!rd) return VP_ERR_HIP;
+  rc = aug ? bank_launch_aug(bk, static_cast<const vp_aug_row*>(rd), B, T0, sigma, norm, label_rows, tr.x_dev, tr.y_dev,
+                             tr.stream)
+           : bank_launch(bk, static_cast<const vp_plan_row*>(rd), B, T0, sigma, norm, label_rows, tr.x_dev, tr.y_dev,
+                         tr.stream);
+  if (rc != VP_OK) return rc;
+  return step_and_loss(tr, tr.x_dev, tr.y_dev, B, lr, update, loss);
+}
+
 }  // namespace
 }  // namespace vp
 
@@ -1034,27 +1062,15 @@ int vp_train_step(vp_trainer* h, const float* x, const float* y, int mem, int B,
 int vp_train_step_bank(vp_trainer* h, vp_bank* bank, const vp_plan_row* rows, int B, float sigma, int norm,
                        const int* label_rows, float lr, int update, double* loss) {
   VP_REQUIRE(h && bank, "vp_train_step_bank: null argument");
-  Trainer& tr = *reinterpret_cast<Trainer*>(h);
-  const Bank& bk = *reinterpret_cast<const Bank*>(bank);
-  VP_REQUIRE(B >= 2 && B <= tr.max_batch, "vp_train_step_bank: batch %d outside [2, %d]", B, tr.max_batch);
-  VP_REQUIRE(bk.device == tr.device, "vp_train_step_bank: bank on device %d, trainer on device %d", bk.device, tr.device);
-  static_assert(RowRing::N == Trainer::EV_RING, "one plan-row slot per step event");
-  int rc = bank_check(bk, rows, B, T0, sigma, norm, label_rows);
-  if (rc != VP_OK) return rc;
-  VP_HIP(hipSetDevice(tr.device));
-  if (!tr.plan_rows.cap) {
-    rc = tr.plan_rows.reserve(tr.max_batch);
-    if (rc != VP_OK) return rc;
-  }
-  // the step that used this slot last: its ev_inputs stands behind the head kernel, which runs after the generation kernel
-  // that read the slot's device copy, which ran after the copy that read the host slot
-  const int slot = (int)(tr.seq % Trainer::EV_RING);
-  if (tr.ev_inputs_seq[slot] >= 0) VP_HIP(hipEventSynchronize(tr.ev_inputs[slot]));
-  const vp_plan_row* rd = tr.plan_rows.stage(slot, rows, B, tr.stream);
-  if (!rd) return VP_ERR_HIP;
-  rc = bank_launch(bk, rd, B, T0, sigma, norm, label_rows, tr.x_dev, tr.y_dev, tr.stream);
-  if (rc != VP_OK) return rc;
-  return step_and_loss(tr, tr.x_dev, tr.y_dev, B, lr, update, loss);
+  return step_bank(*reinterpret_cast<Trainer*>(h), *reinterpret_cast<const Bank*>(bank), rows, nullptr, B, sigma, norm,
+                   label_rows, lr, update, loss);
+}
+
+int vp_train_step_bank_aug(vp_trainer* h, vp_bank* bank, const vp_aug_row* rows, int B, float sigma, int norm,
+                           const int* label_rows, float lr, int update, double* loss) {
+  VP_REQUIRE(h && bank, "vp_train_step_bank_aug: null argument");
+  return step_bank(*reinterpret_cast<Trainer*>(h), *reinterpret_cast<const Bank*>(bank), nullptr, rows, B, sigma, norm,
+                   label_rows, lr, update, loss);
 }
 
 // Makes `stream` (a hipStream_t of the same device; NULL = the legacy default stream) wait until the latest vp_train_step

@@ -14,16 +14,29 @@ row ``(trace, start, lo, hi)`` per window: ``x[c][t] = bank[trace][c][start + t]
 The GPU executes the rows (``vp_bank_make_batch``, ``vp_train_step_bank``): one kernel cuts, demeans, normalises and
 labels the whole batch from a :class:`WaveformBank` that stays in device memory.
 
+With ``stack_data`` (every released config), the reference follows block 1 with volpick's stacking block
+(``get_stack_block``, models.py:345-397), ``AddGap`` and a second ``Normalize`` (models.py:399-440, training and
+validation alike).  :class:`AugmentedPlanner` plans these as well: one :data:`AUG_ROW` per window holds the primary plan
+row, the truncation behind the first event, up to two stacked events (a source window or the window itself, where its
+samples start, its shift and scale), up to two stacked noise windows, a Gaussian-noise factor with its counter-based
+generator key, and the gap.  Everything that follows from onsets alone -- the first event's end, the sources' P-label
+check, their label argmax, the shifts -- is computed on the host; the kernel (``vp_bank_make_batch_aug``,
+``vp_train_step_bank_aug``) decides only what depends on sample values: the zero-channel rule, ``max|x|`` and
+``max(x)``, the normalisation statistics and the combined labels.
+
 SeisBench is not available to pin the generator semantics below; each choice that rests on its behaviour is one named
 constant here:
 
 * ``NO_PICK_FALLBACK`` -- what the around-a-pick branch does with a trace that has no finite onset;
 * ``PAD_LEFT_AT_NEGATIVE_P0`` -- how a window that starts before the trace (``p0 < 0``) is filled;
 * ``P0_ROUNDING`` -- how ``onset - samples_before`` becomes an integer sample;
-* ``NOISE_RULE`` -- the noise label where the P and S Gaussians overlap.
+* ``NOISE_RULE`` -- the noise label where the P and S Gaussians overlap;
+* ``SELECTION_FIRST`` -- which onset ``WindowAroundSample(selection="first")`` centres on;
+* ``GAUSSIAN_NOISE_SCALE`` -- what ``GaussianNoise`` scales its draw by;
+* ``GAP_DRAW`` and ``GAP_NOISE_ROW`` -- how ``AddGap`` draws its gap and which label row it sets to 1 there;
+* ``EVENT_END_INDEX`` -- how a non-integer first-event end becomes a sample index.
 
-Out of scope: volpick's stacking augmentations (``get_stack_block``), ``AddGap``, array rotation and the second
-``Normalize`` they make necessary.
+Out of scope: array rotation (``rotate_array`` defaults to False and no config sets it).
 """
 from __future__ import annotations
 
@@ -38,6 +51,13 @@ NO_PICK_FALLBACK = "null"   # around-a-pick branch on a trace without a finite o
 PAD_LEFT_AT_NEGATIVE_P0 = True  # p0 < 0: zeros in front of the trace (lo = 0); False: the extent starts at sample 0 instead
 P0_ROUNDING = np.trunc      # p0 = int(onset - samples_before): truncation toward zero
 NOISE_RULE = "clip"         # noise = clip(1 - P - S, 0, 1); overlapping P and S are not rescaled (fixed in the kernel)
+SELECTION_FIRST = "earliest"  # selection="first": the earliest finite onset of the four columns (no draw)
+GAUSSIAN_NOISE_SCALE = "signed_max"  # GaussianNoise: x += U(0, 0.15) * max(x) * N(0, 1), the signed maximum, not max|x|
+GAP_DRAW = "start_then_end"  # AddGap: gap_lo uniform in [0, T), then gap_hi uniform in [gap_lo, T)
+GAP_NOISE_ROW = "model"     # AddGap: labels in the gap 0, the model's noise row (label_rows[2]) 1 -- SeisBench's noise_id
+                            # default -1 is the last row, which is the noise row of volpick's PSN labels
+EVENT_END_INDEX = np.trunc  # the first-event end e as a sample index: int(e), toward zero; x[:, min(T, int(e)):] = 0 then
+                            # follows numpy slicing, a negative index counting from the end
 
 # the reference's phase_dict (volpick/model/models.py:26-31): metadata column -> phase, two columns per phase
 PHASE_DICT = {
@@ -50,6 +70,15 @@ PHASE_DICT = {
 PLAN_ROW = np.dtype([("trace", np.int32), ("reserved", np.int32), ("start", np.int64), ("lo", np.int64), ("hi", np.int64)],
                     align=True)
 assert PLAN_ROW.itemsize == C.sizeof(_lib.VpPlanRow)
+
+AUG_NONE, AUG_BANK, AUG_SELF = _lib.VP_AUG_NONE, _lib.VP_AUG_BANK, _lib.VP_AUG_SELF
+AUG_EVENT = np.dtype([("row", PLAN_ROW), ("kind", np.int32), ("zero_before", np.int32), ("shift", np.int32),
+                      ("scale", np.float32)], align=True)
+AUG_NOISE = np.dtype([("row", PLAN_ROW), ("kind", np.int32), ("scale", np.float32)], align=True)
+# include/volpick_hip.h vp_aug_row: the primary plan row and what follows it (AugmentedPlanner); unused entries are zero
+AUG_ROW = np.dtype([("primary", PLAN_ROW), ("event", AUG_EVENT, (2,)), ("noise", AUG_NOISE, (2,)), ("noise_key", np.uint64),
+                    ("gauss", np.float32), ("cut", np.int32), ("gap_lo", np.int32), ("gap_hi", np.int32)], align=True)
+assert AUG_ROW.itemsize == C.sizeof(_lib.VpAugRow)
 
 
 def as_rows(rows) -> np.ndarray:
@@ -64,6 +93,16 @@ def as_rows(rows) -> np.ndarray:
         rows = out
     if rows.ndim != 1 or rows.size == 0:
         raise ValueError("plan rows: a non-empty 1-D array")
+    return np.ascontiguousarray(rows)
+
+
+def as_aug_rows(rows) -> np.ndarray:
+    """A contiguous, non-empty 1-D AUG_ROW array."""
+    rows = np.asarray(rows)
+    if rows.dtype != AUG_ROW:
+        raise TypeError("augmented rows must have the dtype generate.AUG_ROW")
+    if rows.ndim != 1 or rows.size == 0:
+        raise ValueError("augmented rows: a non-empty 1-D array")
     return np.ascontiguousarray(rows)
 
 
@@ -164,20 +203,22 @@ class WaveformBank:
 
     def make_batch(self, rows, model, sigma):
         """``{"X", "y"}``: (B, 3, model.in_samples) fp32 CUDA tensors written on torch's current stream -- what
-        ``PhaseNetLit.training_step`` / ``validation_step`` take."""
+        ``PhaseNetLit.training_step`` / ``validation_step`` take.  ``rows``: plan rows (``PLAN_ROW``, block 1 alone) or
+        augmented rows (``AUG_ROW``, from :class:`AugmentedPlanner`)."""
         import torch
 
-        rows = as_rows(rows)
+        aug = getattr(rows, "dtype", None) == AUG_ROW
+        rows = as_aug_rows(rows) if aug else as_rows(rows)
+        name = "vp_bank_make_batch_aug" if aug else "vp_bank_make_batch"
         T = int(model.in_samples)
         dev = torch.device("cuda", self.device)
         x = torch.empty((len(rows), 3, T), dtype=torch.float32, device=dev)
         y = torch.empty_like(x)
         lr_ = label_rows(model.labels)
         stream = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(self._lib.vp_bank_make_batch(self._h, rows.ctypes.data_as(C.c_void_p), len(rows), T, float(sigma),
-                                                _norm(model.norm), lr_.ctypes.data_as(C.POINTER(C.c_int)),
-                                                C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(stream)),
-                   "vp_bank_make_batch")
+        _lib.check(getattr(self._lib, name)(self._h, rows.ctypes.data_as(C.c_void_p), len(rows), T, float(sigma),
+                                            _norm(model.norm), lr_.ctypes.data_as(C.POINTER(C.c_int)),
+                                            C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(stream)), name)
         return {"X": x, "y": y}
 
     @property
@@ -210,7 +251,7 @@ class WindowPlanner:
     ``lo = max(0, p0)``, ``hi = min(L, p0 + n1)``."""
 
     def __init__(self, bank, batch_size, samples_before=3000, first_windowlen=6000, first_window_prob=(2, 1),
-                 sample_boundaries=(None, None), in_samples=3001, seed=0):
+                 sample_boundaries=(None, None), in_samples=3001, seed=0, selection="random"):
         self.lengths = np.asarray(bank.lengths, np.int64)
         self.onsets = np.asarray(bank.onsets, np.float64).reshape(len(self.lengths), 4)
         self.batch_size = int(batch_size)
@@ -224,6 +265,9 @@ class WindowPlanner:
         self.first_windowlen = int(first_windowlen)
         self.low, self.high = sample_boundaries
         self.in_samples = int(in_samples)
+        if selection not in ("random", "first"):
+            raise ValueError(f"selection must be 'random' or 'first', got {selection!r}")
+        self.selection = selection
         self.rng = np.random.default_rng(seed)
 
     def plan(self, traces) -> np.ndarray:
@@ -236,13 +280,18 @@ class WindowPlanner:
         finite = np.isfinite(ons)
         n_on = finite.sum(axis=1)
         around = rng.random(n) < self.p_around
-        k = rng.integers(0, np.maximum(n_on, 1))  # index among the trace's finite onsets
+        if self.selection == "random":
+            k = rng.integers(0, np.maximum(n_on, 1))  # index among the trace's finite onsets
         if NO_PICK_FALLBACK == "error" and (around & (n_on == 0)).any():
             raise ValueError(f"trace {int(traces[around & (n_on == 0)][0])} has no pick for the around-a-pick branch")
         around &= n_on > 0
-        # the k-th finite onset of each row (columns P, P, S, S)
-        rank = np.cumsum(finite, axis=1) - 1
-        pick = np.where(finite & (rank == k[:, None]), ons, 0.0).sum(axis=1)
+        if self.selection == "random":  # the k-th finite onset of each row (columns P, P, S, S)
+            rank = np.cumsum(finite, axis=1) - 1
+            pick = np.where(finite & (rank == k[:, None]), ons, 0.0).sum(axis=1)
+        else:
+            assert SELECTION_FIRST == "earliest"
+            pick = np.where(finite, ons, np.inf).min(axis=1)
+            pick = np.where(n_on > 0, pick, 0.0)
         p0 = np.where(around, P0_ROUNDING(pick - self.samples_before), 0).astype(np.int64)
         if not PAD_LEFT_AT_NEGATIVE_P0:
             p0 = np.maximum(p0, 0)
@@ -271,3 +320,276 @@ class WindowPlanner:
         n, B = len(self.lengths), self.batch_size
         for i in range(0, n, B):
             yield self.plan(np.arange(i, min(i + B, n)))
+
+
+def trace_subsets(metadata, column="source_type", noise_value="noise"):
+    """``(event_traces, noise_traces)``: the bank indices whose ``metadata[column]`` is not / is ``noise_value`` -- the
+    reference's split of a set into the stacked-event and stacked-noise generators (its train.py filters on
+    ``source_type``)."""
+    col = np.asarray(metadata[column]).astype(str)
+    noise = col == noise_value
+    return np.flatnonzero(~noise), np.flatnonzero(noise)
+
+
+class Augmentation:
+    """The reference's stacking block, gap and second Normalize (models.py:345-440) with its defaults, and the trace
+    subsets they draw from: ``event_traces`` / ``noise_traces`` index the training bank, ``val_event_traces`` /
+    ``val_noise_traces`` the validation bank (``trace_subsets`` builds them from a ``source_type`` column).  An empty or
+    ``None`` subset switches its slot off, as a missing generator does in the reference."""
+
+    def __init__(self, event_traces=None, noise_traces=None, val_event_traces=None, val_noise_traces=None,
+                 event_prob=(0.2, 0.2, 0.6), noise_prob=(0.25, 0.25, 0.5), gap_prob=(0.2, 0.8), event_inv_scale=(0.25, 4),
+                 noise_inv_scale=(2, 50), gauss_scale=(0, 0.15), sep=200, tail_length_factor=1.4,
+                 prob_num_events=None):
+        self.event_traces, self.noise_traces = event_traces, noise_traces
+        self.val_event_traces, self.val_noise_traces = val_event_traces, val_noise_traces
+        self.params = dict(event_prob=event_prob, noise_prob=noise_prob, gap_prob=gap_prob, event_inv_scale=event_inv_scale,
+                           noise_inv_scale=noise_inv_scale, gauss_scale=gauss_scale, sep=sep,
+                           tail_length_factor=tail_length_factor, prob_num_events=prob_num_events)
+
+    def planner(self, bank, batch_size, seed, in_samples=3001, sigma=20, validation=False):
+        ev, nz = (self.val_event_traces, self.val_noise_traces) if validation else (self.event_traces, self.noise_traces)
+        return AugmentedPlanner(bank, batch_size, ev, nz, seed=seed, in_samples=in_samples, sigma=sigma, **self.params)
+
+
+# columns of AugmentedPlanner's uniform draws, one row per window (AugmentedPlanner.last_draws["u"])
+U_COLS = {"event_branch": 0, "n_events": 1, "event_source": (2, 3), "event_q": (4, 5), "event_scale": (6, 7),
+          "noise_branch": 8, "n_noise": 9, "noise_source": (10, 11), "noise_scale": (12, 13), "gauss": 14, "gap_branch": 15,
+          "gap_lo": 16, "gap_hi": 17}
+N_U = 18
+P_CHECK_TOL = 1e-2 + 1e-5  # np.isclose(max P, 1, atol=1e-2): |max P - 1| <= atol + rtol * 1
+
+
+def _int_draw(u, lo, hi):
+    """The integer lo + floor(u (hi - lo)) in [lo, hi) for a uniform u in [0, 1) (hi > lo)."""
+    return lo + np.minimum(np.floor(u * (hi - lo)).astype(np.int64), hi - lo - 1)
+
+
+def _slice_start(k, T):
+    """numpy's start index of x[:, k:] for an int k (negative: counted from the end)."""
+    return np.where(k >= 0, np.minimum(k, T), np.maximum(T + k, 0))
+
+
+def _phase_peak(o, lo, hi, two_s2):
+    """The peak of the label row max_j exp(-(s - o_j)^2 / two_s2) over integer samples s in [lo, hi), in float64: o (n, 2)
+    onsets (NaN = none) in the row's samples.  Returns (value, argmax); value 0 (argmax lo) for an empty range, no onset or
+    a row that is 0 everywhere.  Ties go to the lowest sample, as np.argmax: the best sample of each onset is its floor or
+    ceiling clamped into the range, so the row's maximum is at one of those four candidates."""
+    n = len(o)
+    hi1 = np.maximum(hi - 1, lo)
+    fin = np.isfinite(o)
+    fl = np.floor(np.where(fin, o, 0.0))
+    cand = np.concatenate([fl, fl + 1], axis=1)  # (n, 4)
+    cand = np.minimum(np.maximum(cand, lo[:, None]), hi1[:, None])
+    d = np.where(fin[:, None, :], cand[:, :, None] - np.where(fin, o, 0.0)[:, None, :], np.inf)  # (n, 4 cand., 2 onsets)
+    g = np.exp(-(d * d) / two_s2).max(axis=2)
+    g = np.where((hi > lo)[:, None], g, 0.0)
+    val = g.max(axis=1)
+    arg = np.where(g == val[:, None], cand, np.inf).min(axis=1)
+    arg = np.where(val > 0, arg, lo).astype(np.int64)
+    return val, arg.reshape(n)
+
+
+def _shifted_argmax(o, d, T, two_s2):
+    """np.argmax over t in [0, T) of a label row shifted by d with zero fill: row(t) = peak row(t - d) for 0 <= t - d < T."""
+    val, arg = _phase_peak(o, np.maximum(0, -d), np.minimum(T, T - d), two_s2)
+    return np.where(val > 0, arg + d, 0)
+
+
+class AugmentedPlanner:
+    """Block 1 followed by the reference's stacking slots, AddGap and second Normalize (models.py:399-440) as
+    :data:`AUG_ROW` records, with the ``plan`` / ``epoch`` / ``validation`` surface of :class:`WindowPlanner`.
+
+    The primary rows come from ``WindowPlanner(bank, batch_size, seed=seed, ...)`` itself, so they equal its rows batch
+    for batch; everything else is drawn from a second generator seeded from ``seed``.  ``event_traces`` /
+    ``noise_traces`` are index subsets of ``bank``; an empty or ``None`` subset switches its slot off.  Event sources are
+    planned as the reference's stacked-event generator does (block 1 with ``samples_before=1500``, ``windowlen=4000``,
+    ``selection="first"``, probabilities ``[1, 0]``), noise sources with the default block 1.  ``sigma`` must be the
+    label width the batches are made with: the sources' P-label check and label argmax depend on it.
+
+    Per window, in order (``u`` = the window's uniforms, columns :data:`U_COLS`): the event slot ``OneOf([superimpose,
+    duplicate, null], event_prob)``, the noise slot ``OneOf([superimpose noise, Gaussian noise, null], noise_prob)``, the
+    gap ``OneOf([AddGap, null], gap_prob)``.  An integer in ``[lo, hi)`` is ``lo + floor(u (hi - lo))``, a scale
+    ``1 / (a + u (b - a))`` for ``inv_scale = (a, b)``, a source ``subset[floor(u len(subset))]``.  ``last_draws`` holds
+    the latest batch's draws (``u``, the source traces and rows, the noise keys) for a replay."""
+
+    def __init__(self, bank, batch_size, event_traces=None, noise_traces=None, seed=0, in_samples=3001, sigma=20,
+                 event_prob=(0.2, 0.2, 0.6), noise_prob=(0.25, 0.25, 0.5), gap_prob=(0.2, 0.8), event_inv_scale=(0.25, 4),
+                 noise_inv_scale=(2, 50), gauss_scale=(0, 0.15), sep=200, tail_length_factor=1.4, prob_num_events=None,
+                 **block1):
+        self.primary = WindowPlanner(bank, batch_size, in_samples=in_samples, seed=seed, **block1)
+        self.lengths, self.onsets = self.primary.lengths, self.primary.onsets
+        self.batch_size, self.T = self.primary.batch_size, int(in_samples)
+        self.rng = np.random.default_rng([int(seed), 0x5354_4143_4B])  # the augmentation draws' own stream
+        n = len(self.lengths)
+
+        def subset(ix):
+            ix = np.asarray([] if ix is None else ix, np.int64).ravel()
+            if ((ix < 0) | (ix >= n)).any():
+                raise ValueError(f"trace subset: indices outside [0, {n})")
+            return ix
+
+        self.event_traces, self.noise_traces = subset(event_traces), subset(noise_traces)
+
+        def probs(p, k):
+            p = np.asarray(p, np.float64)
+            if p.shape != (k,) or (p < 0).any() or p.sum() <= 0:
+                raise ValueError(f"branch probabilities: {k} non-negative weights, got {p}")
+            return np.cumsum(p / p.sum())
+
+        self.event_cum, self.noise_cum, self.gap_cum = probs(event_prob, 3), probs(noise_prob, 3), probs(gap_prob, 2)
+        pne = {1: 0.7, 2: 0.3} if prob_num_events is None else dict(prob_num_events)
+        if not set(pne) <= {1, 2}:
+            raise ValueError(f"prob_num_events: at most two events per window, got {sorted(pne)}")
+        self.num_choices = np.array(list(pne), np.int64)
+        self.num_cum = probs(list(pne.values()), len(pne))
+        self.event_inv_scale, self.noise_inv_scale = event_inv_scale, noise_inv_scale
+        self.gauss_scale = gauss_scale
+        self.sep, self.tail = int(sep), float(tail_length_factor)
+        self.two_s2 = 2.0 * float(sigma) ** 2
+        # the sources' block 1 (models.py:274-280), drawing from the augmentation stream
+        self.event_planner = WindowPlanner(bank, batch_size, samples_before=1500, first_windowlen=4000,
+                                           first_window_prob=(1, 0), in_samples=in_samples, selection="first")
+        self.noise_planner = WindowPlanner(bank, batch_size, in_samples=in_samples)
+        self.event_planner.rng = self.noise_planner.rng = self.rng
+        self.last_draws = None
+
+    def _sources(self, subset, u, need, planner):
+        """Source traces (n, 2) drawn from subset with the uniforms u (n, 2), and their block-1 rows for the windows
+        `need` (zero elsewhere)."""
+        n = len(u)
+        tr, rows = np.zeros((n, 2), np.int64), np.zeros((n, 2), PLAN_ROW)
+        if len(subset):
+            tr = subset[_int_draw(u, 0, len(subset))]
+            k = np.flatnonzero(need)
+            if len(k):
+                rows[k] = planner.plan(tr[k].ravel()).reshape(len(k), 2)
+        return tr, rows
+
+    def _onsets(self, trace, start):
+        """Window-local onsets (n, 4) of rows of `trace` starting at `start`."""
+        return self.onsets[trace] - start[:, None].astype(np.float64)
+
+    def plan(self, traces) -> np.ndarray:
+        """Augmented rows for the given trace indices, in that order."""
+        prim = self.primary.plan(traces)
+        n, T, sep = len(prim), self.T, self.sep
+        rng = self.rng
+        u = rng.random((n, N_U))
+        ev_branch = np.searchsorted(self.event_cum, u[:, U_COLS["event_branch"]], side="right")
+        nz_branch = np.searchsorted(self.noise_cum, u[:, U_COLS["noise_branch"]], side="right")
+        ev_tr, ev_rows = self._sources(self.event_traces, u[:, list(U_COLS["event_source"])], ev_branch == 0,
+                                       self.event_planner)
+        nz_tr, nz_rows = self._sources(self.noise_traces, u[:, list(U_COLS["noise_source"])], nz_branch == 0,
+                                       self.noise_planner)
+        keys = rng.integers(0, 2 ** 64, size=n, dtype=np.uint64)
+        self.last_draws = {"u": u, "event_traces": ev_tr, "event_rows": ev_rows, "noise_traces": nz_tr,
+                           "noise_rows": nz_rows, "noise_key": keys}
+
+        out = np.zeros(n, AUG_ROW)
+        out["primary"] = prim
+        out["cut"] = T
+
+        # --- event slot: worked out on the windows that draw superimpose or duplicate only -------------------------
+        if len(self.event_traces):
+            ix = np.flatnonzero(ev_branch < 2)
+            self._events(out, ix, ev_branch[ix] == 0, u[ix], ev_rows[ix])
+
+        # --- noise slot -------------------------------------------------------------------------------------------
+        if len(self.noise_traces):
+            n_nz = self.num_choices[np.searchsorted(self.num_cum, u[:, U_COLS["n_noise"]], side="right")]
+            a0, a1 = self.noise_inv_scale
+            for j in range(2):
+                on = np.flatnonzero((nz_branch == 0) & (j < n_nz))
+                nz = out["noise"][:, j]
+                nz["kind"][on] = AUG_BANK
+                nz["row"][on] = nz_rows[on, j]
+                nz["scale"][on] = 1.0 / (a0 + u[on, U_COLS["noise_scale"][j]] * (a1 - a0))
+            g0, g1 = self.gauss_scale
+            assert GAUSSIAN_NOISE_SCALE == "signed_max"  # applied in the kernel
+            gauss = np.where(nz_branch == 1, (g0 + u[:, U_COLS["gauss"]] * (g1 - g0)).astype(np.float32), 0.0)
+            out["gauss"] = gauss
+            out["noise_key"] = np.where(out["gauss"] > 0, keys, 0)
+
+        # --- gap ----------------------------------------------------------------------------------------------------
+        assert GAP_DRAW == "start_then_end" and GAP_NOISE_ROW == "model"
+        gap = np.searchsorted(self.gap_cum, u[:, U_COLS["gap_branch"]], side="right") == 0
+        glo = _int_draw(u[:, U_COLS["gap_lo"]], 0, T)
+        ghi = _int_draw(u[:, U_COLS["gap_hi"]], glo, T)
+        out["gap_lo"] = np.where(gap, glo, 0)
+        out["gap_hi"] = np.where(gap, ghi, 0)
+        return out
+
+    def _events(self, out, ix, sup, u, ev_rows):
+        """The event slot of windows ix (sup: superimpose, else duplicate) into out."""
+        n, T, sep = len(ix), self.T, self.sep
+        prim = out["primary"][ix]
+        n_ev = self.num_choices[np.searchsorted(self.num_cum, u[:, U_COLS["n_events"]], side="right")]
+        ons = self._onsets(prim["trace"], prim["start"])
+        fin = np.isfinite(ons)
+        n_on = fin.sum(axis=1)
+        mx = np.where(fin, ons, -np.inf).max(axis=1)
+        mn = np.where(fin, ons, np.inf).min(axis=1)
+        with np.errstate(invalid="ignore"):
+            e_many = EVENT_END_INDEX(mx + np.maximum((mx - mn) * self.tail, sep) + 0.2 * sep)
+            e_one = mx + 1 + sep
+        # SuperimposeEvent casts the one-onset end to int, MyDuplicateEvent does not
+        e = np.where(n_on >= 2, e_many, np.where(sup, EVENT_END_INDEX(e_one), e_one))
+        # P-label peaks of the window itself and of both sources, in one pass
+        src = [np.where(sup[:, None], self._onsets(ev_rows[:, i]["trace"], ev_rows[:, i]["start"]), ons) for i in range(2)]
+        val, arg = _phase_peak(np.concatenate([ons[:, 0:2], src[0][:, 0:2], src[1][:, 0:2]]), np.zeros(3 * n, np.int64),
+                               np.full(3 * n, T, np.int64), self.two_s2)
+        pv, pa = val[:n], arg[:n]
+        active = (n_on > 0) & (sup | (np.abs(pv - 1.0) <= P_CHECK_TOL))
+        e = np.where(active, e, 0.0)
+        out["cut"][ix] = np.where(active, _slice_start(EVENT_END_INDEX(e).astype(np.int64), T), T)
+        stopped = ~active
+        events = out["event"][ix]
+        for i in range(2):
+            alive = ~stopped & (i < n_ev)
+            stop = np.where(sup, e >= T - 2 * sep, e + 2 * sep >= T)
+            stopped |= alive & stop
+            alive &= ~stop
+            # the source: its window (superimpose) or the window itself (duplicate)
+            so = src[i]
+            sv, sa = val[(i + 1) * n:(i + 2) * n], arg[(i + 1) * n:(i + 2) * n]
+            a = np.where(sup, sa, pa)
+            added = alive & (~sup | (np.abs(sv - 1.0) <= P_CHECK_TOL))
+            lo = EVENT_END_INDEX(e).astype(np.int64)
+            hi = np.where(sup, T - 2 * sep, T - sep)
+            q = _int_draw(u[:, U_COLS["event_q"][i]], lo, np.maximum(hi, lo + 1))
+            d = np.clip(q - a, -T, T)  # |d| = T: wholly outside the window, as any |d| >= T
+            a0, a1 = self.event_inv_scale
+            ev = events[:, i]
+            k = np.flatnonzero(added)
+            ev["kind"][k] = np.where(sup[k], AUG_BANK, AUG_SELF)
+            ks = np.flatnonzero(added & sup)
+            ev["row"][ks] = ev_rows[ks, i]
+            ev["zero_before"][k] = np.maximum(a[k] - sep, 0)
+            ev["shift"][k] = d[k]
+            ev["scale"][k] = 1.0 / (a0 + u[k, U_COLS["event_scale"][i]] * (a1 - a0))
+            if i == 0:  # the next event starts behind this one's latest label peak
+                k = np.flatnonzero(added & (n_ev > 1))
+                dk = np.concatenate([d[k], d[k]])
+                am = _shifted_argmax(np.concatenate([so[k, 0:2], so[k, 2:4]]), dk, T, self.two_s2)
+                e[k] = np.maximum(e[k], np.maximum(am[:len(k)], am[len(k):]) + 1 + sep)
+        out["event"][ix] = events
+
+    def epoch(self):
+        """As WindowPlanner.epoch (the primary planner's permutation), each batch augmented."""
+        for rows in self.primary.epoch():
+            yield self._augment(rows)
+
+    def validation(self):
+        """As WindowPlanner.validation, each batch augmented (the reference's get_val_augmentations)."""
+        for rows in self.primary.validation():
+            yield self._augment(rows)
+
+    def _augment(self, rows):
+        # plan() for traces whose primary rows are already drawn: replay them through a one-shot primary
+        saved = self.primary.plan
+        self.primary.plan = lambda traces: rows
+        try:
+            return self.plan(rows["trace"])
+        finally:
+            self.primary.plan = saved

@@ -159,16 +159,19 @@ class PhaseNetTrainer:
         """``step`` on a batch generated on the GPU: the plan rows (``generate.PLAN_ROW``, e.g. from
         ``WindowPlanner``) are cut from ``bank`` (a ``WaveformBank`` on the trainer's device), normalised with
         ``model.norm`` and labelled with Gaussians of width ``sigma`` in ``model.labels`` order, straight into the
-        trainer's input buffers on its own stream (``vp_train_step_bank``).  ``rows`` may be reused at once."""
-        from .generate import as_rows, label_rows, _norm
+        trainer's input buffers on its own stream (``vp_train_step_bank``).  ``AUG_ROW`` records (``AugmentedPlanner``)
+        add the stacking, gap and second normalisation (``vp_train_step_bank_aug``).  ``rows`` may be reused at once."""
+        from .generate import AUG_ROW, as_aug_rows, as_rows, label_rows, _norm
 
-        rows = as_rows(rows)
+        aug = getattr(rows, "dtype", None) == AUG_ROW
+        rows = as_aug_rows(rows) if aug else as_rows(rows)
+        name = "vp_train_step_bank_aug" if aug else "vp_train_step_bank"
         lrows = label_rows(self.model.labels)
         self._drop_consumed()
         loss = C.c_double(float("nan"))
-        _lib.check(self._lib.vp_train_step_bank(self._h, bank.handle, rows.ctypes.data_as(C.c_void_p), len(rows), float(sigma),
-                                                _norm(self.model.norm), lrows.ctypes.data_as(C.POINTER(C.c_int)), float(lr),
-                                                int(bool(update)), C.byref(loss) if want_loss else None), "vp_train_step_bank")
+        _lib.check(getattr(self._lib, name)(self._h, bank.handle, rows.ctypes.data_as(C.c_void_p), len(rows), float(sigma),
+                                            _norm(self.model.norm), lrows.ctypes.data_as(C.POINTER(C.c_int)), float(lr),
+                                            int(bool(update)), C.byref(loss) if want_loss else None), name)
         # the bank stays referenced until the step's reads of it are complete (as the device inputs of `step`)
         self._in_flight.append((int(self._lib.vp_train_steps_enqueued(self._h)) - 1, bank, None))
         self.forward_count = getattr(self, "forward_count", 0) + 1
@@ -317,20 +320,32 @@ class PhaseNetLit:
         y = y.cpu().numpy() if hasattr(y, "cpu") else np.asarray(y)
         return vector_cross_entropy(p.astype(np.float64), y.astype(np.float64))
 
-    def fit_bank(self, bank, steps, batch_size=512, seed=0, val_bank=None):
+    def fit_bank(self, bank, steps, batch_size=512, seed=0, val_bank=None, augment=None):
         """``steps`` optimiser steps on batches generated on the GPU from ``bank`` (a ``WaveformBank``): epochs of
         ``WindowPlanner(bank, batch_size, seed=seed)`` (a new permutation each, last partial batch dropped), learning
         rate ``learning_rate(step)``, labels of width ``self.sigma``.  Returns the per-step losses and, with ``val_bank``,
         ``(losses, val_losses)``: the mean ``validation_step`` loss over ``val_bank`` (in order, the last partial batch
-        kept, its own planner seeded ``seed + 1``) after every completed epoch and after the last step."""
+        kept, its own planner seeded ``seed + 1``) after every completed epoch and after the last step.
+
+        ``augment`` (a ``generate.Augmentation``) adds the reference's stacking block, gap and second Normalize to the
+        training and the validation batches (``AugmentedPlanner`` with its subsets of ``bank`` / ``val_bank``); ``None``
+        plans block 1 alone."""
         from .generate import WindowPlanner
 
         tr = self._ensure()
         in_samples = self.model.in_samples
-        planner = WindowPlanner(bank, batch_size, in_samples=in_samples, seed=seed)
+        if augment is None:
+            planner = WindowPlanner(bank, batch_size, in_samples=in_samples, seed=seed)
+        else:
+            planner = augment.planner(bank, batch_size, seed, in_samples=in_samples, sigma=self.sigma)
         if len(bank.lengths) < batch_size:
             raise ValueError(f"a bank of {len(bank.lengths)} traces holds no full batch of {batch_size}")
-        val_planner = WindowPlanner(val_bank, batch_size, in_samples=in_samples, seed=seed + 1) if val_bank is not None else None
+        val_planner = None
+        if val_bank is not None and augment is None:
+            val_planner = WindowPlanner(val_bank, batch_size, in_samples=in_samples, seed=seed + 1)
+        elif val_bank is not None:
+            val_planner = augment.planner(val_bank, batch_size, seed + 1, in_samples=in_samples, sigma=self.sigma,
+                                          validation=True)
         losses, val_losses = [], []
 
         def validate():
