@@ -169,9 +169,14 @@ def test_every_kernel_against_torch_on_the_inputs_it_read(step):
     check_every_kernel(*step)
 
 
-def check_every_kernel(B, x, y, tr, loss, t, g, pred, net=None):
+def check_every_kernel(B, x, y, tr, loss, t, g, pred, net=None, ref64=False):
     """Every launch of one step against torch on the inputs that launch read (the trainer's stored tensors `t`, its
-    gradients `g`): shared with tests/test_gpu_train_large_batch.py (B = 128 / 512, the forms the bench times)."""
+    gradients `g`): shared with tests/test_gpu_train_large_batch.py (B = 128 / 512, the forms the bench times) and
+    tests/test_gpu_train_batch_shapes.py (odd, small and 1024-window batches).
+    ref64: the weight-gradient and BatchNorm-parameter-gradient references in float64 (as the head's always are): they sum
+    B x L terms, and at B = 1024 torch's fp32 sums of up to 3.1 M terms are the noisier side.  The bars stay."""
+    import copy
+
     net = (net if net is not None else load_pretrained("phasenet")).train()
     T = {k: torch.from_numpy(v) for k, v in t.items()}
     pname = {id(p): k for k, p in net.named_parameters()}
@@ -211,15 +216,46 @@ def check_every_kernel(B, x, y, tr, loss, t, g, pred, net=None):
         let_through = close_bf16(t[name + ".gz"], z_in.grad.numpy(), name + ".gz", abs_frac=2e-4, knife_edge=2e-6)
         if let_through.any():  # (the same bn module: its running statistics move, nothing the checks below read)
             assert_knife_edges(let_through, name, bn, t[name + ".z"], ga[name], t[name + ".gz"], crop, abs_frac=2e-4)
-        for p in bn.parameters():
-            want = p.grad.numpy()
-            assert np.abs(g[pname[id(p)]] - want).max() < 2e-4 * np.abs(want).max() + 1e-7, (name, pname[id(p)])
+        bn_ref = bn
+        if ref64:  # the same BatchNorm + crop on the stored z, in float64, behind the gate the kernel took
+            bn_ref = copy.deepcopy(bn).double()
+            for p in bn_ref.parameters():
+                p.grad = None  # (the copy carries the fp32 gradients just taken)
+            u64 = bn_ref(T[name + ".z"].double())
+            if crop is not None:
+                u64 = u64[:, :, crop[0]: crop[0] + crop[1]]
+            # The gate is the stored a > 0 (a = relu(fma(z, sc, sh)) stays positive through rounding), checked against torch by
+            # the ".a" assertion above.  A float64 gate of its own would differ at the knife edges of close_bf16 (u zero to the
+            # last bit of the statistics): at B = 1024 one such element moved a beta gradient of down2.same by 1.05e-6 against a
+            # bar of 7.3e-7, while every other channel agreed to 1e-10.
+            (u64 * (T[name + ".a"] > 0).double()).backward(ga[name].double())
+        for k in ("weight", "bias"):
+            key, want = pname[id(getattr(bn, k))], getattr(bn_ref, k).grad.numpy()
+            assert np.abs(g[key] - want).max() < 2e-4 * np.abs(want).max() + 1e-7, (name, key)
         # ---- input gradient and weight gradient from the stored gz --------------------------------------------------
         z_ref.backward(T[name + ".gz"])
         if grad_dst is not None:
             close_bf16(t[grad_dst], xin.grad.numpy(), grad_dst, abs_frac=1e-4)
         want = conv.weight.grad.numpy()
+        if ref64:
+            conv64 = copy.deepcopy(conv).double()
+            for p in conv64.parameters():
+                p.grad = None
+            conv64(h.detach().double()).backward(T[name + ".gz"].double())
+            want = conv64.weight.grad.numpy()
         assert np.abs(g[pname[id(conv.weight)]] - want).max() < 1e-4 * np.abs(want).max(), (name, "weight gradient")
+        if conv.bias is not None:  # `inc` alone: channel_sum_partial_v_kernel, grid (8, GB = min(B, 64)), then sum_rows_kernel
+            # The sum of gz per channel is zero up to rounding (BatchNorm removes the mean), so it is bounded, not compared
+            # relatively: each lane adds its share of rows in fp32, n <= ceil(B / (4 GB)) rows x 6 vectors x 8 samples terms
+            # (the 376 vectors of a 3001-sample row over 64 lanes); a recursive fp32 sum of n terms is off by at most
+            # (n - 1) 2^-24 sum |terms|, the lanes' totals are added in fp64 and the result is rounded to fp32 once more
+            # (2^-24 |sum|).  A window left out moves the sum by its own share, far outside that bound.
+            gzs = T[name + ".gz"].double()
+            GB = min(B, 64)
+            n = -(-B // (4 * GB)) * 6 * 8
+            want = gzs.sum(dim=(0, 2)).numpy()
+            bound = n * 2.0 ** -24 * gzs.abs().sum(dim=(0, 2)).numpy() + 1e-30
+            assert np.all(np.abs(g[pname[id(conv.bias)]] - want) <= bound), (name, "bias gradient", g[pname[id(conv.bias)]], want, bound)
     # ---- head: 1x1 conv + softmax + vector cross entropy and its backward ---------------------------------------------
     a17 = T["up3.same.a"].clone().requires_grad_(True)
     for p in net.out.parameters():
@@ -241,6 +277,44 @@ def check_every_kernel(B, x, y, tr, loss, t, g, pred, net=None):
     for k in ("weight", "bias"):
         want = getattr(out64, k).grad.numpy()
         assert np.abs(g["out." + k].reshape(want.shape) - want).max() < 1e-4 * np.abs(want).max(), "out." + k
+
+
+def check_adam_and_running_statistics(g, w0, w1, mv, t, lr=1e-3):
+    """Step 1 of Adam from the step's own gradients, in float64: w1 = w0 - lr * mhat / (sqrt(vhat) + eps) with m = (1 - b1) g,
+    v = (1 - b2) g^2 (torch.optim.Adam, the reference's volpick/model/models.py:177-185); BatchNorm running statistics
+    = 0.9 * old + 0.1 * (batch mean, UNBIASED batch variance: ddof = 1 over N = B x L) of the stored z.  g, w0, w1, (m, v), t:
+    the step's gradients, the weights before and after it, its Adam moments and stored tensors (shared with
+    tests/test_gpu_train_batch_shapes.py)."""
+    m, v = mv
+    net = load_pretrained("phasenet")
+    trainable = {k for k, _ in net.named_parameters()}
+    b1, b2, eps = 0.9, 0.999, 1e-8
+    for k in sorted(trainable):
+        gk = g[k].astype(np.float64)
+        assert np.abs(m[k] - (1 - b1) * gk).max() <= 1e-6 * np.abs(gk).max() + 1e-30, k
+        assert np.abs(v[k] - (1 - b2) * gk * gk).max() <= 1e-6 * (np.abs(gk).max() ** 2) + 1e-30, k
+        mhat, vhat = gk, gk * gk  # bias-corrected moments of the first step
+        want = w0[k].astype(np.float64) - lr * mhat / (np.sqrt(vhat) + eps)
+        # |g| >> eps: the step is lr * sign(g); elements with |g| near eps are compared at a tolerance of the step itself
+        big_g = np.abs(gk) > 1e-5
+        assert np.abs(w1[k] - want)[big_g].max(initial=0.0) < 2e-6 * max(1.0, float(np.abs(want).max())), k
+        assert np.abs(w1[k] - want).max() <= 1.01 * lr, k
+    # running statistics: from the stored z of each layer
+    names = {"in_bn": "inc"}
+    for i in range(5):
+        names[f"down_branch.{i}.1"] = f"down{i}.same"
+        if i < 4:
+            names[f"down_branch.{i}.3"] = f"down{i}.down"
+    for j in range(4):
+        names[f"up_branch.{j}.1"] = f"up{j}.convT"
+        names[f"up_branch.{j}.3"] = f"up{j}.same"
+    for bn, layer in names.items():
+        z = t[layer + ".z"].astype(np.float64)
+        mean, var = z.mean((0, 2)), z.var((0, 2), ddof=1)
+        rm = 0.9 * w0[bn + ".running_mean"] + 0.1 * mean
+        rv = 0.9 * w0[bn + ".running_var"] + 0.1 * var
+        assert np.abs(w1[bn + ".running_mean"] - rm).max() < 1e-5 * (np.abs(rm).max() + 1e-3), bn
+        assert np.abs(w1[bn + ".running_var"] - rv).max() < 1e-5 * (np.abs(rv).max() + 1e-3), bn
 
 
 def test_large_batch_takes_the_vector_batchnorm_path_for_every_crop():

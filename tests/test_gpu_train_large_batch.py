@@ -16,7 +16,8 @@ import torch
 from oracle.bf16_emulation import bf16_storage, round_bf16
 from oracle.models import load_pretrained
 from tests.test_gpu_train import make_batch, torch_step
-from tests.test_gpu_train_bf16 import assert_differences_sit_on_rounding_boundaries, check_every_kernel, is_bf16
+from tests.test_gpu_train_bf16 import (assert_differences_sit_on_rounding_boundaries, check_adam_and_running_statistics,
+                                      check_every_kernel, is_bf16)
 from volpick_amd import PhaseNet
 from volpick_amd.train import PhaseNetTrainer
 
@@ -51,40 +52,8 @@ def test_every_kernel_of_the_large_batch_step(big):
 
 
 def test_adam_update_and_running_statistics_of_the_same_step(big):
-    """Step 1 of Adam from the step's own gradients, in float64: w1 = w0 - lr * mhat / (sqrt(vhat) + eps) with m = (1 - b1) g,
-    v = (1 - b2) g^2 (torch.optim.Adam, the reference's volpick/model/models.py:177-185); BatchNorm running statistics
-    = 0.9 * old + 0.1 * (batch mean, UNBIASED batch variance) of the stored z."""
     s = big
-    g, w0, w1, (m, v) = s["g"], s["w0"], s["w1"], s["mv"]
-    net = load_pretrained("phasenet")
-    trainable = {k for k, _ in net.named_parameters()}
-    lr, b1, b2, eps = 1e-3, 0.9, 0.999, 1e-8
-    for k in sorted(trainable):
-        gk = g[k].astype(np.float64)
-        assert np.abs(m[k] - (1 - b1) * gk).max() <= 1e-6 * np.abs(gk).max() + 1e-30, k
-        assert np.abs(v[k] - (1 - b2) * gk * gk).max() <= 1e-6 * (np.abs(gk).max() ** 2) + 1e-30, k
-        mhat, vhat = gk, gk * gk  # bias-corrected moments of the first step
-        want = w0[k].astype(np.float64) - lr * mhat / (np.sqrt(vhat) + eps)
-        # |g| >> eps: the step is lr * sign(g); elements with |g| near eps are compared at a tolerance of the step itself
-        big_g = np.abs(gk) > 1e-5
-        assert np.abs(w1[k] - want)[big_g].max(initial=0.0) < 2e-6 * max(1.0, float(np.abs(want).max())), k
-        assert np.abs(w1[k] - want).max() <= 1.01 * lr, k
-    # running statistics: from the stored z of each layer
-    names = {"in_bn": "inc"}
-    for i in range(5):
-        names[f"down_branch.{i}.1"] = f"down{i}.same"
-        if i < 4:
-            names[f"down_branch.{i}.3"] = f"down{i}.down"
-    for j in range(4):
-        names[f"up_branch.{j}.1"] = f"up{j}.convT"
-        names[f"up_branch.{j}.3"] = f"up{j}.same"
-    for bn, layer in names.items():
-        z = s["t"][layer + ".z"].astype(np.float64)
-        mean, var = z.mean((0, 2)), z.var((0, 2), ddof=1)
-        rm = 0.9 * w0[bn + ".running_mean"] + 0.1 * mean
-        rv = 0.9 * w0[bn + ".running_var"] + 0.1 * var
-        assert np.abs(w1[bn + ".running_mean"] - rm).max() < 1e-5 * (np.abs(rm).max() + 1e-3), bn
-        assert np.abs(w1[bn + ".running_var"] - rv).max() < 1e-5 * (np.abs(rv).max() + 1e-3), bn
+    check_adam_and_running_statistics(s["g"], s["w0"], s["w1"], s["mv"], s["t"])
 
 
 def test_end_to_end_against_autograd_with_the_same_rounding_points(big):
