@@ -19,7 +19,13 @@ phase traces.  The default run times BOTH single-GPU workloads of BASELINE.json:
   * configs[2]  EQTransformer volpick, batch 256, 3x6000, overlap 5500,
                 blinding (500, 500) -- the shape BASELINE's metric names   -> the "eqtransformer" object
 
-(`--model phasenet|eqtransformer` times one of them alone.)  Inputs are resident in HBM before the
+(`--model phasenet|eqtransformer` times one of them alone.)  A plain run does only that: per model it sets up, warms
+up, settles the clock, times the K steps and writes `--dump-outputs`.  `--full` adds everything else the line can carry,
+each behind the timed steps: the >= 5 s `sustained` region, per-kernel timing and `roofline` / `forward`, the CPU oracle
+(`cpu_baseline`, `pick_parity`), the `api` call on a host station-day, and the `train` and `mseed` objects, each from a
+child process.
+
+Inputs are resident in HBM before the
 timed region.  Exactly K steps are timed, as one region bracketed by a barrier + device synchronisation on
 both sides (max over ranks), and `ms_per_step` is that region's time / K.  `--repeats R` times R such regions
 instead (R x K timed steps); `value` is then the median region and min / max are reported beside it.
@@ -287,21 +293,25 @@ def main():
                          "clock has climbed to what it holds under the load (0 = none)")
     ap.add_argument("--model", default="both", choices=["both", "phasenet", "eqtransformer"])
     ap.add_argument("--batch", type=int, default=256)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps, measure and check everything else: `sustained`, `roofline` / `forward`, "
+                         "`cpu_baseline`, `pick_parity`, `api`, `train`, `mseed` (the --no-* and --sustain-seconds options "
+                         "below trim this set)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU oracle legs (and without `api`, `train`, `mseed`)")
     ap.add_argument("--cpu-seconds", type=float, default=24.0, help="CPU budget of the baseline legs, all models together")
     ap.add_argument("--contexts", type=int, default=0,
                     help="device contexts (stream + workspace) steps alternate over; 0 = the model's default (PhaseNet 3, EQTransformer 4)")
     ap.add_argument("--depth", type=int, default=0, help="submits in flight per device context (0 = the model's default)")
     ap.add_argument("--strong", action="store_true", help="time configs[3]: one 24 h stream sharded over the ranks")
     ap.add_argument("--sustain-seconds", type=float, default=5.2,
-                    help="length of the one long timed region per model reported as `sustained` (0 = skip)")
-    ap.add_argument("--no-api", action="store_true", help="skip the `api` object (classify() on a host 24 h stream)")
-    ap.add_argument("--no-train", action="store_true", help="skip the `train` object (BASELINE configs[4]: bf16 training step, B = 512)")
+                    help="--full: length of the one long timed region per model reported as `sustained` (0 = skip)")
+    ap.add_argument("--no-api", action="store_true", help="--full without the `api` object (classify() on a host 24 h stream)")
+    ap.add_argument("--no-train", action="store_true", help="--full without the `train` object (BASELINE configs[4]: bf16 training step, B = 512)")
     ap.add_argument("--no-train-torch", action="store_true",
                     help="`train` without the stock PyTorch-ROCm step beside it (MIOpen's first-use find costs ~35 s on a fresh box)")
-    ap.add_argument("--no-mseed", action="store_true", help="skip the `mseed` object (SURVEY 8f-1: Steim-2 station-day decode)")
+    ap.add_argument("--no-mseed", action="store_true", help="--full without the `mseed` object (SURVEY 8f-1: Steim-2 station-day decode)")
     ap.add_argument("--widened-only", choices=["train", "mseed"], default=None,
-                    help="(internal) run ONE widened-row leg in this process and print its JSON object: the default run starts a child "
+                    help="(internal) run ONE widened-row leg in this process and print its JSON object: --full starts a child "
                          "for each, so that the leg sees a fresh process")
     ap.add_argument("--detail-file", default=str(ROOT / "bench_detail.json"),
                     help="the full result object goes here (and to stderr); stdout's last line is the compact (< 8 KB) form of it")
@@ -369,7 +379,7 @@ def main():
         result = bench_strong(env)
     else:
         names = ["phasenet", "eqtransformer"] if args.model == "both" else [args.model]
-        cpu_budget = 0.0 if (args.no_cpu_baseline or rank != 0 or world != 1) else args.cpu_seconds / len(names)
+        cpu_budget = 0.0 if (not args.full or args.no_cpu_baseline or rank != 0 or world != 1) else args.cpu_seconds / len(names)
         parts = {n: bench_model(n, env, cpu_budget) for n in names}
         result = parts[names[0]]
         if len(names) == 2:
@@ -377,12 +387,13 @@ def main():
             result["eqtransformer"] = {k: eq[k] for k in ("value", "unit", "ms_per_step", "timing", "sustained", "config",
                                                           "roofline", "forward", "api", "ranks", "cpu_baseline",
                                                           "pick_parity") if k in eq}
-    # the two widened rows that have a throughput of their own (N = 1, the default run only): each a few seconds
-    # Each in a CHILD process (this one stays alive, idle, and never execs): behind the forward legs -- pickers created, run and
-    # released, station-days of buffers through torch's allocator -- a trainer created in the same process ran its step at
-    # 2.4-6.6 instead of 1.38 ms, depending on what had been released before it (the hardware queues its two streams land on:
-    # tools/train_after_api_probe.py, LOG.md round 6); a fresh process is the state a training job starts from.
-    if world == 1 and not args.strong and args.model == "both" and not args.no_cpu_baseline:
+    # the two widened rows that have a throughput of their own (N = 1, the default workload under --full only): each a few
+    # seconds.  Each in a CHILD process (this one stays alive, idle, and never execs): behind the forward legs -- pickers
+    # created, run and released, station-days of buffers through torch's allocator -- a trainer created in the same process
+    # ran its step at 2.4-6.6 instead of 1.38 ms, depending on what had been released before it (the hardware queues its two
+    # streams land on: tools/train_after_api_probe.py, LOG.md round 6); a fresh process is the state a training job starts
+    # from.
+    if args.full and world == 1 and not args.strong and args.model == "both" and not args.no_cpu_baseline:
         import subprocess
 
         for key, skip in (("train", args.no_train), ("mseed", args.no_mseed)):
@@ -1048,10 +1059,11 @@ def bench_model(model_name, env, cpu_budget_s):
     windows = args.batch * args.steps * world
     value = windows / dt
 
-    # ---- ONE long region (>= --sustain-seconds): long enough for DVFS to settle and for an outside sampler (the driver's
-    # gpu_busy) to see the load; the shader clock right behind it from the in-kernel stamps of a debug-plan twin
+    # ---- --full only from here on.  ONE long region (>= --sustain-seconds): long enough for DVFS to settle and for an
+    # outside sampler of GPU busy time to see the load; the shader clock right behind it from the in-kernel stamps of a
+    # debug-plan twin
     sustained = None
-    if args.sustain_seconds > 0:
+    if args.full and args.sustain_seconds > 0:
         k_long = max(args.steps, int(args.sustain_seconds / (dt / args.steps)) + 1)
         probe = clock_probe_create(cls, args.batch, dev)
         t_long = timed_repeats(lambda: run_steps(k_long), sync_all, 1, use_dist, dev)[0]
@@ -1069,68 +1081,6 @@ def bench_model(model_name, env, cpu_budget_s):
                                   "model, run right behind the region while the chip is hot)",
         }
 
-    # ---- per-kernel HIP-event timing on the handle's stream -> roofline of the dominant kernel
-    n_steps = lib.vp_step_count(h)
-    ms = (C.c_float * n_steps)()
-    _lib.check(lib.vp_profile_steps(h, args.batch, 20, ms, n_steps), "vp_profile_steps")
-    kernels = []
-    for i in range(n_steps):
-        name, fl, iss = C.c_char_p(), C.c_double(), _lib.VpIssuedWork()
-        lib.vp_step_info(h, i, C.byref(name), C.byref(fl))
-        _lib.check(lib.vp_step_issued_work(h, i, C.byref(iss)), "vp_step_issued_work")
-        k = {"name": name.value.decode(), "ms": float(ms[i]), "flop_per_window": fl.value,
-             "issued_flop_per_window": {"mfma_f32": iss.mfma_f32_flop, "mfma_bf16": iss.mfma_bf16_flop,
-                                        "valu": iss.valu_flop}}
-        k["pipe_time_ms"] = pipe_time_s(k["issued_flop_per_window"], args.batch) * 1e3
-        k["frac_of_pipe_peaks"] = k["pipe_time_ms"] / k["ms"] if k["ms"] > 0 else None
-        if k["name"].startswith("fused.mid"):
-            k["note"] = ("four windows per 1024-thread workgroup (teams of four waves): a 256-window launch holds 64 of the 256 CUs "
-                         "(the other contexts' kernels run on the rest); two windows per workgroup took 91 us on 128 CUs, one 66 us "
-                         "on all 256; frac_of_pipe_peaks is against the whole chip")
-        kernels.append(k)
-    fwd_ms = sum(k["ms"] for k in kernels)
-    # Roofline candidates are the launches that hold >= 5 % of the forward FLOPs (the MFMA / packed-FMA bound ones).
-    # EQTransformer's fused.mid (BiLSTM recurrences + attention, 2 % of the FLOPs) is a serial dependency chain bound
-    # by instruction latency, not by a throughput roof; it stays in forward.kernels and is named in
-    # roofline.latency_bound with its duration, so a reader sees when it is as long as the dominant compute launch.
-    fl_total = sum(k["flop_per_window"] for k in kernels) or 1.0
-    cand = [k for k in kernels if k["flop_per_window"] >= 0.05 * fl_total] or kernels
-    dom = max(cand, key=lambda k: k["ms"])
-    lat = [{"name": k["name"], "ms_back_to_back": k["ms"], "flop_share": k["flop_per_window"] / fl_total}
-           for k in kernels if k not in cand and k["ms"] >= 0.5 * dom["ms"]]
-    # The dominant launch is re-timed IN the pipeline (whole step list in order, events around it only): its inputs
-    # then come from the preceding kernel instead of a warm re-run of itself -- the duration rocprofv3 reports
-    # for it under this same command (profiles/).  200 passes enqueued back to back, one synchronisation: the launch
-    # runs at the clock it has in the timed loop (a synchronisation per pass, as in round 1, lets the GPU idle in
-    # between and times it 5-8 % slower).  The back-to-back figure stays in forward.kernels.
-    dom_ms = C.c_float()
-    _lib.check(lib.vp_profile_step_in_pipeline(h, args.batch, 200, kernels.index(dom), C.byref(dom_ms)),
-               "vp_profile_step_in_pipeline")
-    # The duration the fractions are taken on is one the timed loop pays: a one-launch plan's kernel cannot take longer than a
-    # whole step of that loop, so where the HIP-event figure (one queue, a gap between two launches of it) exceeds the step,
-    # the step is the duration (never a kernel_ms above ms_per_step).
-    step_ms = dt / args.steps * 1e3
-    dom_dur_ms = min(dom_ms.value, step_ms) if (len(kernels) == 1 and world == 1) else dom_ms.value
-    per_s = args.batch / (dom_dur_ms * 1e-3) / 1e12 if dom_dur_ms > 0 else 0.0
-    dom_algorithmic = dom["flop_per_window"] * per_s
-    dom_issued_flop = sum(dom["issued_flop_per_window"].values())
-    dom_pipe_s = pipe_time_s(dom["issued_flop_per_window"], args.batch)
-    dom_achieved = dom_issued_flop * per_s                                              # issued TFLOP/s, all pipes
-    dom_peak = dom_issued_flop * args.batch / dom_pipe_s / 1e12 if dom_pipe_s > 0 else 0.0  # the same mix at its pipes' peaks
-    flop_w = lib.vp_flops_per_window(h)
-    stage = (C.c_float * 4)()
-    total_ms = C.c_float()
-    lib.vp_set_timing(h, 1)  # stage split from one extra, un-timed, synchronous step
-    _lib.check(lib.vp_classify(h, C.c_void_p(x.data_ptr()), _lib.VP_MEM_DEVICE, n_samples, overlap, blinding[0],
-                               blinding[1], _lib.VP_STACK_AVG, args.batch, c_specs, len(specs),
-                               C.c_void_p(out.data_ptr()), _lib.VP_MEM_DEVICE, C.byref(fv), C.byref(lv), C.byref(nw),
-                               on, off, peak, val, spec_of, cap, C.byref(found)), "vp_classify")
-    lib.vp_last_timing(h, C.byref(total_ms), stage)
-    lib.vp_set_timing(h, 0)
-
-    kname = dom["name"]
-    kernel_label = ("pn_window_kernel: " if kname.startswith("fused.window") else
-                    "eqt fused kernel: " if kname.startswith("fused.") else "conv_mfma_kernel: ") + kname
     result = {
         "metric": "waveform-windows/sec",
         "value": value,
@@ -1144,7 +1094,6 @@ def bench_model(model_name, env, cpu_budget_s):
         "vs_baseline": None,
         "dtype": DTYPE_LABEL,
         "data": "synthetic",
-        "sustained": sustained,
         "timing": {
             "repeats": len(times),
             "statistic": "median over the repeats (default one) of the max-over-ranks time of K steps",
@@ -1166,7 +1115,74 @@ def bench_model(model_name, env, cpu_budget_s):
             "input_residency": "every step re-reads the same device-resident stream (18 / 1.6 MB): Infinity-Cache "
                                "resident; the kernels are compute-bound, so this does not flatter the number",
         },
-        "roofline": {
+        "weight_broadcast_s": t_bcast,
+        "weight_broadcast_path": _bcast_path(),
+    }
+    if args.full:
+        result["sustained"] = sustained
+        # ---- per-kernel HIP-event timing on the handle's stream -> roofline of the dominant kernel
+        n_steps = lib.vp_step_count(h)
+        ms = (C.c_float * n_steps)()
+        _lib.check(lib.vp_profile_steps(h, args.batch, 20, ms, n_steps), "vp_profile_steps")
+        kernels = []
+        for i in range(n_steps):
+            name, fl, iss = C.c_char_p(), C.c_double(), _lib.VpIssuedWork()
+            lib.vp_step_info(h, i, C.byref(name), C.byref(fl))
+            _lib.check(lib.vp_step_issued_work(h, i, C.byref(iss)), "vp_step_issued_work")
+            k = {"name": name.value.decode(), "ms": float(ms[i]), "flop_per_window": fl.value,
+                 "issued_flop_per_window": {"mfma_f32": iss.mfma_f32_flop, "mfma_bf16": iss.mfma_bf16_flop,
+                                            "valu": iss.valu_flop}}
+            k["pipe_time_ms"] = pipe_time_s(k["issued_flop_per_window"], args.batch) * 1e3
+            k["frac_of_pipe_peaks"] = k["pipe_time_ms"] / k["ms"] if k["ms"] > 0 else None
+            if k["name"].startswith("fused.mid"):
+                k["note"] = ("four windows per 1024-thread workgroup (teams of four waves): a 256-window launch holds 64 of the 256 CUs "
+                             "(the other contexts' kernels run on the rest); two windows per workgroup took 91 us on 128 CUs, one 66 us "
+                             "on all 256; frac_of_pipe_peaks is against the whole chip")
+            kernels.append(k)
+        fwd_ms = sum(k["ms"] for k in kernels)
+        # Roofline candidates are the launches that hold >= 5 % of the forward FLOPs (the MFMA / packed-FMA bound ones).
+        # EQTransformer's fused.mid (BiLSTM recurrences + attention, 2 % of the FLOPs) is a serial dependency chain bound
+        # by instruction latency, not by a throughput roof; it stays in forward.kernels and is named in
+        # roofline.latency_bound with its duration, so a reader sees when it is as long as the dominant compute launch.
+        fl_total = sum(k["flop_per_window"] for k in kernels) or 1.0
+        cand = [k for k in kernels if k["flop_per_window"] >= 0.05 * fl_total] or kernels
+        dom = max(cand, key=lambda k: k["ms"])
+        lat = [{"name": k["name"], "ms_back_to_back": k["ms"], "flop_share": k["flop_per_window"] / fl_total}
+               for k in kernels if k not in cand and k["ms"] >= 0.5 * dom["ms"]]
+        # The dominant launch is re-timed IN the pipeline (whole step list in order, events around it only): its inputs
+        # then come from the preceding kernel instead of a warm re-run of itself -- the duration rocprofv3 reports
+        # for it under this same command (profiles/).  200 passes enqueued back to back, one synchronisation: the launch
+        # runs at the clock it has in the timed loop (a synchronisation per pass, as in round 1, lets the GPU idle in
+        # between and times it 5-8 % slower).  The back-to-back figure stays in forward.kernels.
+        dom_ms = C.c_float()
+        _lib.check(lib.vp_profile_step_in_pipeline(h, args.batch, 200, kernels.index(dom), C.byref(dom_ms)),
+                   "vp_profile_step_in_pipeline")
+        # The duration the fractions are taken on is one the timed loop pays: a one-launch plan's kernel cannot take longer than a
+        # whole step of that loop, so where the HIP-event figure (one queue, a gap between two launches of it) exceeds the step,
+        # the step is the duration (never a kernel_ms above ms_per_step).
+        step_ms = dt / args.steps * 1e3
+        dom_dur_ms = min(dom_ms.value, step_ms) if (len(kernels) == 1 and world == 1) else dom_ms.value
+        per_s = args.batch / (dom_dur_ms * 1e-3) / 1e12 if dom_dur_ms > 0 else 0.0
+        dom_algorithmic = dom["flop_per_window"] * per_s
+        dom_issued_flop = sum(dom["issued_flop_per_window"].values())
+        dom_pipe_s = pipe_time_s(dom["issued_flop_per_window"], args.batch)
+        dom_achieved = dom_issued_flop * per_s                                              # issued TFLOP/s, all pipes
+        dom_peak = dom_issued_flop * args.batch / dom_pipe_s / 1e12 if dom_pipe_s > 0 else 0.0  # the same mix at its pipes' peaks
+        flop_w = lib.vp_flops_per_window(h)
+        stage = (C.c_float * 4)()
+        total_ms = C.c_float()
+        lib.vp_set_timing(h, 1)  # stage split from one extra, un-timed, synchronous step
+        _lib.check(lib.vp_classify(h, C.c_void_p(x.data_ptr()), _lib.VP_MEM_DEVICE, n_samples, overlap, blinding[0],
+                                   blinding[1], _lib.VP_STACK_AVG, args.batch, c_specs, len(specs),
+                                   C.c_void_p(out.data_ptr()), _lib.VP_MEM_DEVICE, C.byref(fv), C.byref(lv), C.byref(nw),
+                                   on, off, peak, val, spec_of, cap, C.byref(found)), "vp_classify")
+        lib.vp_last_timing(h, C.byref(total_ms), stage)
+        lib.vp_set_timing(h, 0)
+
+        kname = dom["name"]
+        kernel_label = ("pn_window_kernel: " if kname.startswith("fused.window") else
+                        "eqt fused kernel: " if kname.startswith("fused.") else "conv_mfma_kernel: ") + kname
+        result["roofline"] = {
             "bound": "mfma",
             "kernel": kernel_label,
             "achieved": dom_achieved,
@@ -1207,8 +1223,8 @@ def bench_model(model_name, env, cpu_budget_s):
             },
             "traffic": traffic_bytes(model_name, kname),
             "latency_bound": lat,
-        },
-        "forward": {
+        }
+        result["forward"] = {
             "flop_per_window": flop_w,
             "launches": len(kernels),
             "sum_kernel_ms": fwd_ms,
@@ -1219,10 +1235,7 @@ def bench_model(model_name, env, cpu_budget_s):
             "stage_ms_one_sync_step": {"forward": stage[1], "stack": stage[2], "trigger_scan": stage[3]},
             "picks_per_step": n_picks,
             "kernels": kernels,
-        },
-        "weight_broadcast_s": t_bcast,
-        "weight_broadcast_path": _bcast_path(),
-    }
+        }
     if use_dist:  # what every rank saw, so that a multi-GPU line checks itself
         info = {"rank": rank, "device": torch.cuda.current_device(), "ms_per_step_own_median": None,
                 "weight_broadcast_s": t_bcast, "weight_broadcast_path": _bcast_path(), "rccl_comm_ranks": _rccl_ranks(),
@@ -1231,7 +1244,7 @@ def bench_model(model_name, env, cpu_budget_s):
         gathered = [None] * world
         dist.all_gather_object(gathered, info)
         result["ranks"] = gathered
-    if cpu_budget_s > 0:
+    if cpu_budget_s > 0:  # --full, one rank only (main)
         result["cpu_baseline"] = cpu_baseline(model_name, data, overlap, blinding, args.batch, cpu_budget_s)
         result["pick_parity"] = pick_parity(model, model_name, data, overlap, blinding, args.batch)
     if cpu_budget_s > 0 and not args.no_api:

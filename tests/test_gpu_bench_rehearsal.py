@@ -57,7 +57,7 @@ def _reap_group(pgid):
 
 
 def test_weak_line_of_two_ranks():
-    d = _run(["--steps", "5", "--warmup", "2", "--model", "phasenet", "--no-cpu-baseline", "--no-api", "--sustain-seconds", "0"])
+    d = _run(["--steps", "5", "--warmup", "2", "--model", "phasenet", "--full", "--no-cpu-baseline", "--no-api", "--sustain-seconds", "0"])
     assert d["n_gpus"] == 2 and d["steps"] == 5 and d["warmup"] == 2 and d["scaling"] == "weak" and d["higher_is_better"] is True
     assert d["value"] == pytest.approx(2 * 256 / (d["ms_per_step"] * 1e-3), rel=1e-4)  # whole job over the slowest rank's span (six digits in the line)
     assert [r["rank"] for r in d["ranks"]] == [0, 1] and all(r["windows_per_step"] == 256 for r in d["ranks"])
@@ -87,6 +87,7 @@ def test_four_ranks_weak_and_strong_on_one_gpu():
               "--settle-seconds", "0", "--repeats", "3"], n=4, timeout=900)
     assert d["n_gpus"] == 4 and [r["rank"] for r in d["ranks"]] == list(range(4)) and all(r["windows_per_step"] == 256 for r in d["ranks"])
     assert d["value"] == pytest.approx(4 * 256 / (d["ms_per_step"] * 1e-3), rel=1e-4)
+    assert not {"sustained", "roofline", "forward"} & set(d["_full"]), "without --full the run times its steps and nothing else"
     s6 = _run(["--strong", "--steps", "1", "--warmup", "1", "--repeats", "1"], n=4, timeout=900)
     assert s6["n_gpus"] == 4 and s6["scaling"] == "strong" and len(s6["ranks"]) == 4
     keeps = [r["keeps"] for r in s6["ranks"]]

@@ -1,6 +1,7 @@
 # On-box sweep of the wave / tile shape of the EQT decoder stages 3-5 (conv_mfma ConvCfg WM, WN, NW): rebuilds the
 # library per variant and prints the per-kernel times of bench.py.
 set -e
+T=$(mktemp -d)
 cd $GRAFT_REPO_ROOT
 F=volpick_amd/csrc/eqt.hip
 run() { # name  d3(WM WN NW)  d4(WM WN NW)  d5(WM WN NW)
@@ -10,9 +11,10 @@ run() { # name  d3(WM WN NW)  d4(WM WN NW)  d5(WM WN NW)
       -i $F
   make -C volpick_amd/csrc -j8 > /dev/null 2>&1
   echo "== $1: d3 ($2 $3 $4)  d4 ($5 $6 $7)  d5 ($8 $9 ${10})"
-  python bench.py --model eqtransformer --no-cpu-baseline --steps 60 --warmup 6 2>/dev/null | python -c "
-import sys,json
-d=json.loads(sys.stdin.read()); print(round(d['value']), [(k['name'][:9], round(k['ms']*1e3,1)) for k in d['forward']['kernels'] if k['name'] in ('decoder.3','decoder.4','decoder.5')])"
+  python bench.py --full --model eqtransformer --no-cpu-baseline --steps 60 --warmup 6 --detail-file $T/e.json > /dev/null 2>&1
+  python -c "
+import json
+d=json.load(open('$T/e.json')); print(round(d['value']), [(k['name'][:9], round(k['ms']*1e3,1)) for k in d['forward']['kernels'] if k['name'] in ('decoder.3','decoder.4','decoder.5')])"
 }
 run base   2 2 6  2 2 6  2 2 6
 run a      4 1 6  1 4 6  1 4 6
