@@ -55,7 +55,9 @@ typedef struct {
   int32_t plan_flags[8];      /* plan selectors (debug plans, A/B timing; all 0 = the default plan):
                                  [0]: 1 = PhaseNet layer-by-layer plan instead of the fused kernels (debug / A-B);
                                  [1]: bit0 = fused kernels also dump their LDS intermediates to the debug tensors
-                                      (selects the three-launch plan), bit1 = per-layer clock stamps;
+                                      (selects the three-launch plan), bit1 = per-layer clock stamps,
+                                      bit2 = PhaseNet: the one-launch kernel's DUMP instance writes every layer's output and
+                                      the head's logits to the debug tensors (tests; rejected with bit0, [5] or [6] set);
                                  [2]: PhaseNet: (1 = hand-pipelined K loop in the MFMA layers: removed in round 6, rejected);
                                       EQTransformer: 1 = the three
                                       BiLSTM blocks, two transformer blocks and the pick branches as six launches instead

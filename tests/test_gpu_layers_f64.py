@@ -1,0 +1,152 @@
+"""Every layer of the shipped one-launch PhaseNet kernel (pn_window_kernel, bf16 three-piece operands) against float64, on the
+kernel's own input to that layer (tests/layer_f64.py).  The kernel's DUMP instance (plan_flags[1] & 4) writes each layer's
+fp32 output and the head's logits; its output probabilities must equal the shipped instance's bit for bit, which ties the
+dumps to the shipped arithmetic.  EQTransformer's middle kernel (eqt_mid4) is checked the same way from its own input and
+output, which the default plan keeps in memory."""
+import copy
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import pipeline as OP
+from oracle.models import load_pretrained
+from tests.gpu_util import debug_tensors
+from tests.layer_f64 import C_ELEM, K_RMS, check_layer, eqt_mid_chain, phasenet_layers, rel_rms, report
+from tests.test_gpu_parity_wide import _scaled_state
+from volpick_amd import EQTransformer, PhaseNet, _lib
+from volpick_amd.synthetic import synthetic_windows
+
+pytestmark = pytest.mark.gpu
+DUMP = (0, 4)
+
+
+def _rows(B):
+    """Windows checked in float64: all of a batch of up to 16; of a large one the first, one in the middle and the last (one
+    workgroup per window: the last is the last workgroup's)."""
+    return None if B <= 16 else [0, B // 2, B - 2, B - 1]
+
+
+def _run(weights, xn, state=None):
+    """(probabilities of the shipped kernel, of the DUMP instance, the dumps)"""
+    outs = []
+    for flags in ((0,), DUMP):
+        m = PhaseNet.from_pretrained(weights)
+        if state is not None:
+            m.load_state_dict(state)
+        m._plan_flags = flags
+        m._max_batch = max(256, xn.shape[0])
+        m.cuda()
+        try:
+            outs.append(m(xn).cpu().numpy())
+            if flags == DUMP:
+                t = {k: torch.from_numpy(v) for k, v in debug_tensors(m, xn.shape[0]).items()}
+        finally:
+            m._release()
+    return outs[0], outs[1], t
+
+
+def _check(oracle, xn, weights, state=None, label=""):
+    B = xn.shape[0]
+    y, yd, t = _run(weights, xn, state)
+    assert np.array_equal(y, yd, equal_nan=True), f"{label}: the DUMP instance's probabilities differ from the shipped kernel's"
+    t["input"] = xn.float()
+    rows = []
+    for layer in phasenet_layers(oracle):
+        rows.append(check_layer(layer, t, t[layer[0]], _rows(B)))
+    print(f"\n[{label}] B={B}\n" + report(rows))
+    bad = [r["name"] for r in rows if not (r["finite"] and r["rms_ratio"] <= K_RMS and r["elem_ratio"] <= C_ELEM)]
+    assert not bad, f"{label}: layers beyond the float64 bars (rms ratio <= {K_RMS}, elementwise <= {C_ELEM}): {bad}"
+    # the dumped logits are the probabilities' own: their softmax gives the shipped output back
+    p = torch.softmax(t["logits"].double(), dim=1).numpy()
+    assert np.abs(p - y).max() < 1e-6, label
+
+
+@pytest.mark.parametrize("weights", ["volpick", "volpick_95train"])
+@pytest.mark.parametrize("B", [1, 7, 256])
+def test_every_layer_matches_float64(weights, B):
+    oracle = load_pretrained("phasenet", weights)
+    xn = OP.batch_pre(oracle, torch.from_numpy(synthetic_windows(B, 3001, seed=900 + B)))
+    _check(oracle, xn, weights, label=f"phasenet {weights}")
+
+
+def _edge_windows(B, seed):
+    """energy at both ends of the window (the tiles that meet the zero padding) and a DC offset"""
+    rng = np.random.default_rng(seed)
+    x = synthetic_windows(B, 3001, seed=seed)
+    t = np.arange(3001)
+    burst = np.exp(-((t[:, None] - np.array([40, 2960])[None]) / 12.0) ** 2).sum(axis=1)
+    x = x + (5.0 * x.std() * rng.standard_normal((B, 3, 1)) * np.sin(0.7 * t) * burst).astype(np.float32)
+    x[B // 2:] += np.float32(3.0 * np.abs(x).max())  # DC offset
+    return x.astype(np.float32)
+
+
+@pytest.mark.parametrize("weights", ["volpick", "volpick_95train"])
+def test_edge_energy_and_dc_offset(weights):
+    oracle = load_pretrained("phasenet", weights)
+    x = _edge_windows(5, seed=931)
+    # the network sees the windows without annotate_batch_pre's demeaning as well: the offset reaches the first layers
+    xn = torch.cat([OP.batch_pre(oracle, torch.from_numpy(x)), torch.from_numpy(x / np.abs(x).max(axis=(1, 2), keepdims=True))])
+    _check(oracle, xn, weights, label=f"phasenet {weights} edges + DC")
+
+
+@pytest.mark.parametrize("scale", [1e20, 1e-20])
+def test_activations_far_from_unity(scale):
+    """test_gpu_parity_wide's scaling: down2.down's output (the first bf16-piece layer's input) at scale times its size"""
+    oracle = load_pretrained("phasenet", "volpick")
+    big = copy.deepcopy(oracle)
+    big.load_state_dict(_scaled_state("phasenet", big.state_dict(), scale), strict=True)
+    sd = PhaseNet.from_pretrained("volpick").state_dict()
+    state = {k: (v.numpy() if torch.is_tensor(v) else v) for k, v in _scaled_state("phasenet", sd, scale).items()}
+    xn = OP.batch_pre(oracle, torch.from_numpy(synthetic_windows(3, 3001, seed=4500)))
+    _check(big, xn, "volpick", state, label=f"phasenet activations x {scale:g}")
+
+
+# ---- EQTransformer: eqt_mid4 from res.xa to decoder.in -------------------------------------------------------------------
+K_MID = 4.0  # kernel relative RMS error of each decoder input <= K_MID x torch-fp32's from the same res.xa (LOG.md)
+
+
+def _read(model, name, rows):
+    """rows [0, rows) of the debug tensor `name` as the default plan left it; the tensor must be materialised (not LDS-only)"""
+    lib, h = _lib.load(), model._handle
+    for i in range(lib.vp_debug_tensor_count(h)):
+        nm, c, l = C.c_char_p(), C.c_int(), C.c_int()
+        _lib.check(lib.vp_debug_tensor_info(h, i, C.byref(nm), C.byref(c), C.byref(l)))
+        if nm.value.decode() == name:
+            a = np.empty((rows, c.value, l.value), np.float32)
+            _lib.check(lib.vp_debug_tensor_read(h, i, rows, a.ctypes.data_as(C.c_void_p)))
+            return torch.from_numpy(a)
+    raise KeyError(name)
+
+
+@pytest.mark.slow
+@pytest.mark.parametrize("weights,B,rows", [("volpick", 1, [0]), ("volpick", 5, [0, 4]), ("volpick", 257, [0, 256]),
+                                            ("volpick_95train", 5, [3])],
+                         ids=["volpick-1", "volpick-5", "volpick-257", "volpick_95train-5"])
+def test_eqt_middle_kernel_matches_float64(weights, B, rows):
+    """B = 5 and 257 leave the last four-window workgroup of eqt_mid4 with one window; the checked rows include it."""
+    oracle = load_pretrained("eqtransformer", weights)
+    xn = OP.batch_pre(oracle, torch.from_numpy(synthetic_windows(B, 6000, seed=950 + B)))
+    m = EQTransformer.from_pretrained(weights)
+    m._max_batch = max(256, B)
+    m.cuda()
+    try:
+        m(xn)
+        xa = _read(m, "res.xa", B)[rows]
+        dec = _read(m, "decoder.in", 3 * B)  # set-major: decoder d's window b at row d * B + b
+    finally:
+        m._release()
+    o64 = copy.deepcopy(oracle).double()
+    bad, lines = [], []
+    for r, b in enumerate(rows):  # one window at a time: the attention's (T, T) blocks in float64
+        ref = eqt_mid_chain(o64, xa[r:r + 1].double())
+        y32 = eqt_mid_chain(oracle, xa[r:r + 1])
+        for d, nm in enumerate(("decoder_d", "P branch", "S branch")):
+            got = dec[d * B + b:d * B + b + 1]
+            e, e32 = rel_rms(got, ref[d]), rel_rms(y32[d], ref[d])
+            lines.append(f"window {b:3d} {nm:9s} rel rms {e:.2e} (torch fp32 {e32:.2e})  ratio {e / e32:5.2f}")
+            if not (torch.isfinite(got).all() and e <= K_MID * e32):
+                bad.append((b, nm, e / e32))
+    print(f"\n[eqt_mid4 {weights}] B={B}\n" + "\n".join(lines))
+    assert not bad, f"eqt_mid4 beyond {K_MID} x torch-fp32's error from res.xa: {bad}"

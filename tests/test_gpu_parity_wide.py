@@ -243,7 +243,7 @@ def test_regression_bar_full_batch(default_pair):
 # ---- (e) every documented plan selector (include/volpick_hip.h: vp_config.plan_flags) still produces oracle-grade outputs --------
 PLAN_SELECTORS = {
     "phasenet": [(1,), (0, 1), (0, 0, 0, 1), (0, 0, 0, 0, 1), (0, 0, 0, 0, 0, 1), (0, 0, 0, 0, 0, 2),
-                 (0, 0, 0, 0, 0, 3), (0, 0, 0, 0, 0, 8), (0, 0, 0, 0, 0, 0, 1)],
+                 (0, 0, 0, 0, 0, 3), (0, 0, 0, 0, 0, 8), (0, 0, 0, 0, 0, 0, 1), (0, 4)],
     "eqtransformer": [(1,), (0, 0, 1), (0, 0, 2), (0, 0, 3), (0, 0, 0, 0, 1), (0, 0, 0, 0, 0, 0, 2)] +
                      [(0, 0, 0, 0, 0, 0, 0, 1 << b) for b in range(12)] + [(0, 0, 0, 0, 0, 0, 0, 0x1F0), (0, 0, 0, 0, 0, 0, 0, 0xF)],
 }

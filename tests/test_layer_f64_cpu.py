@@ -1,0 +1,68 @@
+"""Teeth of the per-layer float64 check (tests/layer_f64.py), on CPU: every conv layer of both models, computed in torch fp32
+with the lo piece of its three-piece bf16 operands dropped (weights or input truncated to hi + mid: one lost i + j = 2
+product term), must fail the bars the GPU test holds the shipped kernels to -- by a margin, so that the bars cannot be
+loosened until they no longer see that fault -- while plain fp32 passes them.
+
+What is measured here is the bare conv (no BatchNorm, no ReLU, unfolded weights; the volpick weights, two windows), a close
+neighbour of what the GPU test compares (post-BatchNorm / ReLU outputs of layers whose kernels fold BatchNorm into the weights):
+the margin shows the metric's sensitivity to the fault, not the GPU test's exact numbers.  This runs no kernel: it covers the
+bars, and EQTransformer's layers here have no per-layer check on hardware yet (only eqt_mid4 does, as one chain)."""
+import pytest
+import torch
+
+from oracle import pipeline as OP
+from oracle.models import load_pretrained
+from tests.layer_f64 import C_ELEM, EPS24, K_RMS, attention_rows, bf16_drop_lo, elem_scale, layer_forward, rel_rms
+from volpick_amd.synthetic import synthetic_windows
+
+MARGIN = 1.75  # the weakest case, EQTransformer pick_convs.0 with its weights' lo piece dropped, sits at 1.8 x K_RMS
+
+
+def _conv_inputs(net, x):
+    ins = {}
+    hs = [m.register_forward_hook(lambda mod, i, o, n=n: ins.__setitem__(n, i[0].detach().clone()))
+          for n, m in net.named_modules() if isinstance(m, (torch.nn.Conv1d, torch.nn.ConvTranspose1d))]
+    with torch.no_grad():
+        net(x)
+    for h in hs:
+        h.remove()
+    return ins
+
+
+@pytest.mark.parametrize("model", ["phasenet", "eqtransformer"])
+def test_dropped_lo_piece_fails_the_layer_bars(model):
+    net = load_pretrained(model, "volpick")
+    x = OP.batch_pre(net, torch.from_numpy(synthetic_windows(2, net.in_samples, seed=3)))
+    mods = dict(net.named_modules())
+    ins = _conv_inputs(net, x)
+    assert len(ins) == {"phasenet": 19, "eqtransformer": 48}[model]
+    weak = []
+    for name, xin in ins.items():
+        conv = mods[name]
+        kind = "conv" if isinstance(conv, torch.nn.Conv1d) else "convT"
+        with torch.no_grad():
+            ref = layer_forward(conv, None, False, kind, xin, torch.float64)
+            scale = EPS24 * elem_scale(conv, None, kind, xin)
+            r32 = rel_rms(layer_forward(conv, None, False, kind, xin, torch.float32), ref)
+            elem = lambda y: float(((y.double() - ref).abs() / (scale + 1e-300)).max())
+            e32 = elem(layer_forward(conv, None, False, kind, xin, torch.float32))
+            assert e32 <= C_ELEM, (name, e32)  # plain fp32 passes the elementwise bar
+            for what, y in (("weights", layer_forward(conv, None, False, kind, xin, torch.float32, weight_fn=bf16_drop_lo)),
+                            ("input", layer_forward(conv, None, False, kind, bf16_drop_lo(xin), torch.float32))):
+                rr, ee = rel_rms(y, ref) / r32, elem(y)
+                # the RMS bar sees the lost term; where the weights are (nearly) exact in two pieces, the elementwise one does
+                if not (rr > MARGIN * K_RMS or ee > MARGIN * C_ELEM):
+                    weak.append((name, what, round(rr, 2), round(ee, 2)))
+    assert not weak, f"{model}: a dropped lo piece passes the per-layer bars (rms ratio, elementwise ratio): {weak}"
+
+
+def test_row_blocked_attention_is_the_oracle_module_bit_for_bit():
+    """tests/layer_f64.attention_rows (the float64 reference of eqt_mid4 in blocks of query rows) is the oracle's module"""
+    net = load_pretrained("eqtransformer", "volpick")
+    x = torch.randn(2, 16, 300, generator=torch.Generator().manual_seed(5))
+    for att in (net.transformer_d0.attention, net.transformer_d.attention, *net.pick_attentions):
+        with torch.no_grad():
+            for dtype in (torch.float32, torch.float64):
+                a = att.to(dtype)
+                assert torch.equal(a(x.to(dtype))[0], attention_rows(a, x.to(dtype), chunk=64))
+                att.float()

@@ -128,7 +128,7 @@ struct Net {
 };
 
 int plan_phasenet(Net& net, const ParamView& pv);
-int plan_phasenet_fused(Net& net, const ParamView& pv, int debug_flags);  // swaps the 18 layer steps for 3 fused launches; bit0: dump LDS intermediates, bit1: clock stamps
+int plan_phasenet_fused(Net& net, const ParamView& pv, int debug_flags);  // swaps the 18 layer steps for 3 fused launches; bit0: dump LDS intermediates, bit1: clock stamps, bit2: the one-launch kernel's DUMP instance
 int plan_eqt(Net& net, const ParamView& pv);
 int plan_eqt_fuse_res(Net& net);  // swaps the 14 ResCNN conv steps for one fused launch
 int plan_eqt_fuse_tail_b3(Net& net);  // the same on the bf16 matrix cores, exact three-piece operands (eqt_tail_b3.hip)

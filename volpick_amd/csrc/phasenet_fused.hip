@@ -848,6 +848,12 @@ static_assert(WU_G0 + 4 * W0_S <= WU_U && WU_U + 16 * S1_ <= A_U2T && WU_G1 + 4 
 using W_down = LdsLayer<8, 0, 8, 2, 11, 8, -3, 0, 1, 1>;   // out n' = 2n + p reads sample 8n + tap - 3
 using W_upT = LdsLayer<16, 0, 8, 4, 2, 1, -1, -2, 3, 1>;    // out sample 4m + p - 2 reads level-1 sample m + tap - 1
 
+// the layers a DUMP instance of pn_window_kernel writes out (WindowArgs::dbg), in the order of WD_NAMES
+enum WinDump { WD_INC, WD_D0DOWN, WD_D1SAME, WD_D1DOWN, WD_D2SAME, WD_D2DOWN, WD_D3SAME, WD_D3DOWN, WD_D4SAME, WD_U0T, WD_U0SAME,
+               WD_U1T, WD_U1SAME, WD_U2T, WD_U2SAME, WD_U3T, WD_U3SAME, WD_LOGITS, WD_COUNT };
+const char* const WD_NAMES[WD_COUNT] = {"inc",        "down0.down", "down1.same", "down1.down", "down2.same", "down2.down",
+                                        "down3.same", "down3.down", "down4.same", "up0.convT",  "up0.same",   "up1.convT",
+                                        "up1.same",   "up2.convT",  "up2.same",   "up3.convT",  "up3.same",   "logits"};
 struct WindowArgs {
   CoreArgs c;       // d0 / u2s unused (they live in LDS)
   const float* af4[13];  // weights of the core layers regrouped for 16-byte loads (conv_lds_q4), null where unused
@@ -874,7 +880,47 @@ struct WindowArgs {
   const float *w_out, *b_out;                                  // 1x1 output conv
   PreArgs pre;                                                 // has_pre: the kernel cuts and normalises its window itself
   int has_pre;                                                 // (annotate_batch_pre, as gather_normalize_kernel); else it reads x
+  // DUMP instances only (plan_flags[1] & 4, tests/test_gpu_layers_f64.py): every layer's output, as the epilogue computed it in fp32,
+  // into the haloed debug tensors of the layer plan (down0.same needs none: it is the skip tensor).  Last in the struct, so that the
+  // kernel arguments of the default instances keep their offsets.
+  float* dbg[WD_COUNT];
+  int dbg_ls[WD_COUNT];
+  long dbg_ws[WD_COUNT];
 };
+
+// DUMP: row c of debug tensor i for window win (sample 0 at index 0)
+__device__ __forceinline__ float* win_dump_row(const WindowArgs& a, const int i, const int win, const int c) {
+  return a.dbg[i] + (long)win * a.dbg_ws[i] + HALO + (long)c * a.dbg_ls[i];
+}
+// DUMP: samples [0, L) of a layer's output image out of LDS, C channels: fp32 [C][S] (sample t at column B + t), a three-piece
+// image B3Image<C> or a chunk-plane piece image B3Chunk<C, NC> (sample t at column t + c0).  A piece image gives back the fp32
+// value its epilogue split: hi + (mid + lo) is exact in that order (mid + lo is the residual of hi, 16 significant bits).
+__device__ __forceinline__ float b3_join(const bf16_t* p, const int ps) {
+  return from_bf16(p[0]) + (from_bf16(p[ps]) + from_bf16(p[2 * ps]));
+}
+template <int C, int S, int B>
+__device__ void win_dump_f32(const WindowArgs& a, const int i, const float* img, const int L, const int win, const int tid, const int nth) {
+  for (int k = tid; k < C * L; k += nth) {
+    const int c = k / L, t = k - c * L;
+    win_dump_row(a, i, win, c)[t] = img[c * S + B + t];
+  }
+}
+template <int C>
+__device__ void win_dump_b3(const WindowArgs& a, const int i, const B3Image<C> im, const int L, const int win, const int tid, const int nth) {
+  for (int k = tid; k < C * L; k += nth) {
+    const int c = k / L, t = k - c * L;
+    win_dump_row(a, i, win, c)[t] = b3_join(im.img + (t + im.c0) * B3Image<C>::CS + c, im.ps);
+  }
+}
+template <int C, int NC>
+__device__ void win_dump_b3c(const WindowArgs& a, const int i, const bf16_t* img, const int c0, const int L, const int win, const int tid,
+                             const int nth) {
+  using Q = B3Chunk<C, NC>;
+  for (int k = tid; k < C * L; k += nth) {
+    const int c = k / L, t = k - c * L;
+    win_dump_row(a, i, win, c)[t] = b3_join(img + (c >> 3) * Q::CHS + (t + c0) * 8 + (c & 7), Q::PS);
+  }
+}
 
 struct SplitRowStore {  // up3.convT -> level-0 rows 0-3 (g0) and 4-7 (g1); zero outside the signal
   float *g0, *g1;
@@ -980,7 +1026,10 @@ constexpr int U3T_RING_OFF = 3 * U3T_QU::PS;              // bf16 elements from 
 static_assert(U3T_TILES * U3T_TS >= T0 + 8 && U3T_TILES * U3T_TS < 6 * U3T_RING && U3T_RING >= 2 * U3T_TS + 11 + 4 && U3T_NCU >= T1 + 2 &&
                   (U3T_RING_OFF + 3 * U3T_PS) * 2 <= CORE_LDS_FLOATS * 4 && U3T_RING_OFF % 8 == 0,
               "level-0 up tiles: up2.same's piece image and the ring behind it fit the arena");
-template <bool PIPE, bool B3, bool U1B = false, bool U2B = false, bool U3B = false, bool D12B = false, bool D0T = false, bool U3T = false>
+// DUMP (tests only, plan_flags[1] & 4): the same kernel writing every layer's output to WindowArgs::dbg; each dump sits behind the
+// barrier that closes its layer, or in the epilogue of a time-tiled level-0 layer, and adds nothing to the other instances.
+template <bool PIPE, bool B3, bool U1B = false, bool U2B = false, bool U3B = false, bool D12B = false, bool D0T = false, bool U3T = false,
+          bool DUMP = false>
 // amdgpu_num_vgpr counts the VGPR half of the unified file on gfx90a+ (LLVM doubles it): 60 -> at most 120 registers per lane, so that
 // four forward waves leave each SIMD the 32 registers the post-processing kernels need to run beside them (prepost.hip; a dozen
 // one-off spills per window in the D0T form, none inside a loop)
@@ -990,6 +1039,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_num_vgpr(60))) void pn_
   static_assert(!U3T || (D0T && U3B), "U3T is a form of the D0T kernel");
   static_assert(!U2B || U1B, "U2B relocates up1.same's output: needs the U1B form");
   static_assert(!U3B || U2B, "U3B builds on the U2B layout");
+  static_assert(!DUMP || U3T, "DUMP instances exist for the default form only");
   constexpr int U2_NC = U3B ? B3_U2_NC3 : B3_U2_NC, U2_OFF = U3B ? B3_U2_OFF3 : B3_U2_OFF;
   // up phase: up2.same | level-0 rows 0-3 | level-0 rows 4-7
   constexpr int XU_U = U2B ? A_SKIP1 : WU_U, XU_G0 = U2B ? A_SKIP2 : WU_G0, XU_G1 = U2B ? A_SKIP2 + 4 * W0_S : WU_G1;
@@ -1011,6 +1061,12 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_num_vgpr(60))) void pn_
 #else
 #define CORE_WIN_STAMP(slot) WIN_STAMP(slot)
 #endif
+// DUMP: behind a layer's closing barrier, its output image goes out; the barrier behind it keeps the next layer's stores off it
+#define WIN_DUMP(...)   \
+  if constexpr (DUMP) { \
+    __VA_ARGS__;        \
+    __syncthreads();    \
+  }
   WIN_STAMP(0)
   WIN_STAMP(18)
   // first workgroup of each XCD: touch one word per 128-byte line of the core weights (pn_core_kernel) -- on the FIRST launch of a
@@ -1339,6 +1395,13 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_num_vgpr(60))) void pn_
 #pragma unroll
             for (int r = 0; r < 4; ++r) o[r] = s < T0 ? o[r] : 0.f;
           }
+          if constexpr (DUMP) {
+            const int s = D0T_TS * j + 32 * wave + 2 * n + ph;
+            if (s < T0) {
+#pragma unroll
+              for (int r = 0; r < 4; ++r) win_dump_row(a, WD_INC, win, 4 * quad + r)[s] = o[r];
+            }
+          }
           b3_store4(HP + ring_at(cinc), D0T_HPS, 0, 0, 4 * quad, o);
           cinc += D0T_TS;
           cinc = cinc >= D0T_RING ? cinc - D0T_RING : cinc;
@@ -1450,6 +1513,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_num_vgpr(60))) void pn_
       b3_load_a<8, 7>(a.af3_d12[0], 0, lane, aw1);
     }
     lds_barrier();  // not __syncthreads(): the skip rows drain to memory under the first core layers
+    WIN_DUMP(win_dump_b3c<8, B3_D0_NC>(a, WD_D0DOWN, reinterpret_cast<const bf16_t*>(lds) + A_D0 * 2, 3, T1, win, tid, NTH))
     WIN_STAMP(22)
     WIN_STAMP(1)
   }
@@ -1512,6 +1576,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_num_vgpr(60))) void pn_
       }
       CORE_WIN_STAMP(stamp)
       ++stamp;
+      WIN_DUMP(win_dump_f32<16, S1_, IB>(a, WD_D1SAME, lds + A_SKIP1, T1, win, tid, NTH))
     }
     [[maybe_unused]] uint4 aw2[B3Steps<16, 7>::STEPS * 3];  // down2.same's operand (requested a layer ahead, behind down1.down's MFMAs)
     {  // down1.down (fp32 MFMA, strided) -> piece image
@@ -1526,6 +1591,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_num_vgpr(60))) void pn_
       lds_barrier();  // not __syncthreads(): it would wait for the request just made
       CORE_WIN_STAMP(stamp)
       ++stamp;
+      WIN_DUMP(win_dump_b3c<16, B3_D1_NC>(a, WD_D1DOWN, iD1, 3, T2, win, tid, NTH))
     }
     {  // down2.same: wave = (m-tile, block of three n-tiles), eight waves
       zero_halo<32, S2_, T2, IB>(lds + A_SKIP2, tid, NTH);
@@ -1551,6 +1617,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_num_vgpr(60))) void pn_
       }
       CORE_WIN_STAMP(stamp)
       ++stamp;
+      WIN_DUMP(win_dump_f32<32, S2_, IB>(a, WD_D2SAME, lds + A_SKIP2, T2, win, tid, NTH))
     }
   } else {
   CORE_LAYER(0, C_d1same, A_D0, S1_, A_D0, S1_, IB, A_SKIP1, S1_, IB, RangeStoreS, 16, T1, T1)
@@ -1581,6 +1648,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_num_vgpr(60))) void pn_
       else conv_lds_q4<C_d2down, S2_, IB, S2_, IB>(lds + A_SKIP2, lds + A_SKIP2, a.af4[3], a.c.bs[3], T3, st, wave, NWV, lane);
       conv_b3_request<C_d3same>(a.af3[0], T3, wave, lane, q_d3s);
       B3_END
+      WIN_DUMP(win_dump_b3<32>(a, WD_D2DOWN, iD2, T3, win, tid, NTH))
     }
     {  // down3.same
       B3Store<64> st{iSK3.img, iSK3.ps, iSK3.c0, T3, B3_SK3_NC};
@@ -1588,6 +1656,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_num_vgpr(60))) void pn_
       conv_b3_requested<C_d3same, false, 32, 32>(iD2, iD2, a.af3[0], a.c.bs[4], T3, st, wave, NWV, lane, q_d3s);
       conv_b3_request<C_d3down>(a.af3[1], T4, wave, lane, q_d3d);
       B3_END
+      WIN_DUMP(win_dump_b3<64>(a, WD_D3SAME, iSK3, T3, win, tid, NTH))
     }
     {  // down3.down
       B3Store<64> st{iD3.img, iD3.ps, iD3.c0, T4, B3_D3_NC};
@@ -1595,6 +1664,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_num_vgpr(60))) void pn_
       conv_b3_requested<C_d3down, false, 64, 64>(iSK3, iSK3, a.af3[1], a.c.bs[5], T4, st, wave, NWV, lane, q_d3d);
       conv_b3_request<C_d4same>(a.af3[2], T4, wave, lane, q_d4s);
       B3_END
+      WIN_DUMP(win_dump_b3<64>(a, WD_D3DOWN, iD3, T4, win, tid, NTH))
     }
     {  // down4.same
       B3Store<128> st{iBOT.img, iBOT.ps, iBOT.c0, T4, B3_BOT_NC};
@@ -1602,6 +1672,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_num_vgpr(60))) void pn_
       conv_b3_requested<C_d4same, false, 64, 64>(iD3, iD3, a.af3[2], a.c.bs[6], T4, st, wave, NWV, lane, q_d4s);
       conv_b3_request<C_u0T>(a.af3[3], T4 + 1, wave, lane, q_u0t);
       B3_END
+      WIN_DUMP(win_dump_b3<128>(a, WD_D4SAME, iBOT, T4, win, tid, NTH))
     }
     {  // up0.convT: rows ordered (phase, channel); samples 4 c + phase - 1, columns c in [0, 16)
       B3Store<64> st{iU0T.img, iU0T.ps, iU0T.c0, T3, B3_U0T_NC};
@@ -1609,6 +1680,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_num_vgpr(60))) void pn_
       conv_b3_requested<C_u0T, true, 128, 128>(iBOT, iBOT, a.af3[3], a.c.bs[7], T4 + 1, st, wave, NWV, lane, q_u0t);
       conv_b3_request<C_u0same, 2>(a.af3[4], T3, wave, lane, q_u0s);
       B3_END
+      WIN_DUMP(win_dump_b3<64>(a, WD_U0T, iU0T, T3, win, tid, NTH))
     }
     if constexpr (U3B) {  // up0.same: cat(skip 3, up0.convT) -> three-piece image for up1.convT
       B3Store<64> st{l16 + A_Q * 2, B3_U0S_PS, 1, T3, B3_U0S_NC};
@@ -1616,6 +1688,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_num_vgpr(60))) void pn_
       conv_b3_requested<C_u0same, false, 64, 64, decltype(st), 2>(iSK3, iU0T, a.af3[4], a.c.bs[8], T3, st, wave, NWV, lane, q_u0s);
       if (U1B) conv_b3_request<C_u1T>(a.af3_uT[0], T3 + 1, wave, lane, q_u1t);
       B3_END
+      WIN_DUMP(win_dump_b3<64>(a, WD_U0SAME, B3Image<64>{l16 + A_Q * 2, B3_U0S_PS, 1}, T3, win, tid, NTH))
     } else {  // up0.same: cat(skip 3, up0.convT) -> fp32 image for up1.convT
       F32QuadStore<S3_, IB> st{lds + X_U0S, T3};
       zero_halo<64, S3_, T3, IB>(lds + X_U0S, tid, NTH);
@@ -1642,6 +1715,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_num_vgpr(60))) void pn_
       lds_barrier();
       CORE_WIN_STAMP(stamp)
       ++stamp;
+      WIN_DUMP(win_dump_b3<32>(a, WD_U1T, iP, T2, win, tid, NTH))
     } else {  // up1.convT (fp32 MFMA, 8 m-tiles x 1 block) -> three-piece image
       const B3PhaseStore<32> st{iP.img, iP.ps, iP.c0, T2};
       (B3Store<32>{iP.img, iP.ps, iP.c0, T2, B3_U1_NC}).zero_rest(3, 3 + T2, tid, NTH);
@@ -1699,6 +1773,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_num_vgpr(60))) void pn_
       else __syncthreads();
       CORE_WIN_STAMP(stamp)
       ++stamp;
+      WIN_DUMP(win_dump_b3c<32, B3_U1S_NC>(a, WD_U1SAME, iU1S, 1, T2, win, tid, NTH))
     }
   } else {
   CORE_LAYER_AREG(9, C_u1T, X_U0S, S3_, X_U1T, S2_, TB, RangeStoreV, 32, T3 + 1, T2, wave, 0, 1)        // 8 m-tiles x 1 block (pn_core_kernel)
@@ -1728,6 +1803,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_num_vgpr(60))) void pn_
     else __syncthreads();
     CORE_WIN_STAMP(stamp)
     ++stamp;
+    WIN_DUMP(win_dump_b3c<16, U2_NC>(a, WD_U2T, P2, 3, T1, win, tid, NTH))
   } else if constexpr (U2B) {  // up2.convT (fp32 MFMA, 4 m-tiles x 4 blocks) -> chunk-plane piece image
     const B3PhaseStoreC<16, U2_NC> st{P2, 3, T1};
     b3c_zero_rest<16, U2_NC>(P2, 3, 3 + T1, tid, NTH);
@@ -1816,6 +1892,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_num_vgpr(60))) void pn_
         }
       }
       __syncthreads();
+      WIN_DUMP(win_dump_b3c<16, U3T_NCU>(a, WD_U2SAME, UP, 1, T1, win, tid, NTH))
     } else if (wave >= 8) {
       float4 skq[NSKQ];
       const float* src = a.skip0 + (long)win * a.ws_s;
@@ -1951,6 +2028,13 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_num_vgpr(60))) void pn_
 #pragma unroll
             for (int r = 0; r < 4; ++r) o[r] = (unsigned)s < (unsigned)T0 ? o[r] : 0.f;
           }
+          if constexpr (DUMP) {
+            const int s = U3T_TS * j + mphase - 2 + 4 * (16 * (wv >> 1) + n);
+            if ((unsigned)s < (unsigned)T0) {
+#pragma unroll
+              for (int r = 0; r < 4; ++r) win_dump_row(a, WD_U3T, win, 4 * quad + r)[s] = o[r];
+            }
+          }
           ring_store(RU + U3T_CH, ct, quad, o);
           ct += U3T_TS, cs += U3T_TS;
           ct = ct >= U3T_RING ? ct - U3T_RING : ct;
@@ -1982,6 +2066,17 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_num_vgpr(60))) void pn_
           for (int r = 0; r < 4; ++r) zz = fmaf(w1[k][r], fmaxf(sa[r] + sb[r], 0.f), zz);
           const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(zz), __float_as_uint(zz), false, false);
           z[k] = (__uint_as_float(sw[0]) + __uint_as_float(sw[1])) + b1[k];  // rows (0, 1) and (2, 3): the pair's sum in both
+        }
+        if constexpr (DUMP) {
+          const int t = U3T_TS * (j - 1) - 8 + 32 * wv + 2 * n + ph;
+          if ((unsigned)t < (unsigned)T0) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) win_dump_row(a, WD_U3SAME, win, 4 * quad + r)[t] = fmaxf(sa[r] + sb[r], 0.f);
+            if (quad == 0) {
+#pragma unroll
+              for (int k = 0; k < 3; ++k) win_dump_row(a, WD_LOGITS, win, k)[t] = z[k];
+            }
+          }
         }
         const float mx = fmaxf(z[0], fmaxf(z[1], z[2]));
         const float e0 = __expf(z[0] - mx), e1 = __expf(z[1] - mx), e2 = __expf(z[2] - mx);
@@ -2067,6 +2162,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_num_vgpr(60))) void pn_
   if (clk && tid == 0) clk[(long)win * 32 + 17] = wall_clock64();
 #undef WIN_STAMP
 #undef CORE_WIN_STAMP
+#undef WIN_DUMP
 #undef WIN_WARM_SCALAR
 }
 
@@ -2095,6 +2191,12 @@ std::vector<float> pack_valu(const float* W, int cin, bool transposed, const std
 
 int plan_phasenet_fused(Net& net, const ParamView& pv, int debug_flags) {
   const bool debug_dumps = (debug_flags & 1) != 0, debug_clock = (debug_flags & 2) != 0;
+  // bit 2: the one-launch kernel's DUMP instance writes every layer's output (and the head's logits) to the debug tensors
+  const bool win_dumps = (debug_flags & 4) != 0;
+  if (win_dumps && (debug_dumps || net.cfg.plan_flags[5] != 0 || net.cfg.plan_flags[6] != 0)) {
+    set_error("PhaseNet plan_flags[1] & 4 dumps the default one-launch form only (plan_flags[1] & 1, plan_flags[5], plan_flags[6] unset)");
+    return VP_ERR_UNSUPPORTED;
+  }
   // Pruned in round 6 (kept in source as `if constexpr` branches of the templates, no longer instantiated): the hand-pipelined K
   // loop (plan_flags[2] = 1; the compiler's own schedule measured 0-5 % faster on every layer, tools/micro/micro_layers.hip) and
   // the intermediate forms of pn_window_kernel between its references (plan_flags[5] = 4, 5, 6, 7, 9).
@@ -2160,6 +2262,18 @@ int plan_phasenet_fused(Net& net, const ParamView& pv, int debug_flags) {
     net.need(u2s, HALO + (VU_TS / 4) * (VU_TILES - 1) - 2 + 258);  // up2.same image loads
     net.need(x, HALO - 4 + W0_S);      // whole-window float4 loads of pn_window_kernel
     net.need(skip0, HALO - 4 + W0_S);
+  }
+  std::vector<int> wd_ids(WD_COUNT, -1);
+  if (win_dumps) {  // up3.same and the head's logits exist in registers only: tensors of their own for the dumps
+    net.add_tensor("up3.same", 8, T0);
+    net.add_tensor("logits", 3, T0);
+    for (int i = 0; i < WD_COUNT; ++i) {
+      wd_ids[i] = tensor_id(net, WD_NAMES[i]);
+      if (wd_ids[i] < 0) {
+        set_error("PhaseNet dumps: no tensor %s", WD_NAMES[i]);
+        return VP_ERR_INVALID;
+      }
+    }
   }
   std::vector<Step> steps;
   auto flops = [&](int lo, int hi) {
@@ -2446,6 +2560,16 @@ int plan_phasenet_fused(Net& net, const ParamView& pv, int debug_flags) {
         a.pre = *n.pre;
         a.has_pre = 1;
       }
+      if (win_dumps) {
+        for (int i = 0; i < WD_COUNT; ++i) {
+          const Tensor& t = n.tensors[wd_ids[i]];
+          a.dbg[i] = t.p;
+          a.dbg_ls[i] = t.ls;
+          a.dbg_ws[i] = (long)t.win_stride();
+        }
+        hipLaunchKernelGGL((pn_window_kernel<false, true, true, true, true, true, true, true, true>), dim3(B), dim3(1024), CORE_LDS_FLOATS * sizeof(float), s, a);
+        return 0;
+      }
       // Three forms are kept (round 6 pruned the rest: the intermediate forms of rounds 2-5 -- plan_flags[5] = 4, 5, 6, 7, 9 and the
       // hand-pipelined K loop plan_flags[2] = 1 -- were A/B stations on the way, no test's reference any more): the default, the
       // round-4 form with level 0 on the vector ALUs (plan_flags[5] = 8: the rounding reference of the tiled level-0 layers), and
@@ -2466,6 +2590,8 @@ int plan_phasenet_fused(Net& net, const ParamView& pv, int debug_flags) {
     net.extra_kernels.push_back({reinterpret_cast<const void*>(&pn_window_kernel<false, false>), CORE_LDS_FLOATS * sizeof(float)});
     net.extra_kernels.push_back({reinterpret_cast<const void*>(&pn_window_kernel<false, true, true, true, true, true>), CORE_LDS_FLOATS * sizeof(float)});
     net.extra_kernels.push_back({reinterpret_cast<const void*>(&pn_window_kernel<false, true, true, true, true, true, true, true>), CORE_LDS_FLOATS * sizeof(float)});
+    if (win_dumps)
+      net.extra_kernels.push_back({reinterpret_cast<const void*>(&pn_window_kernel<false, true, true, true, true, true, true, true, true>), CORE_LDS_FLOATS * sizeof(float)});
   }
   net.steps = std::move(steps);
   net.extra_kernels.push_back({reinterpret_cast<const void*>(&pn_core_kernel<false>), CORE_LDS_FLOATS * sizeof(float)});
