@@ -58,6 +58,11 @@ typedef struct {
                                       (selects the three-launch plan), bit1 = per-layer clock stamps,
                                       bit2 = PhaseNet: the one-launch kernel's DUMP instance writes every layer's output and
                                       the head's logits to the debug tensors (tests; rejected with bit0, [5] or [6] set);
+                                      EQTransformer: the DUMP instances of the five default conv kernels write every conv
+                                      layer's output (encoder.0-5, res.{i}.mid / .conv2 / .out, decoder.0-6 and the heads'
+                                      logits, the decoders' set-major) to the debug tensors; the decoder tail computes whole
+                                      rows in 1200-sample tiles (tests; rejected with [0], [3] or any [7] bit but bit10 set,
+                                      or [6] = 2);
                                  [2]: PhaseNet: (1 = hand-pipelined K loop in the MFMA layers: removed in round 6, rejected);
                                       EQTransformer: 1 = the three
                                       BiLSTM blocks, two transformer blocks and the pick branches as six launches instead

@@ -66,6 +66,65 @@ def phasenet_acts(net, x):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+EQT_DECODERS = ("decoder_d", "pick_decoders.0", "pick_decoders.1")
+EQT_HEADS = ("conv_d", "pick_convs.0", "pick_convs.1")
+
+
+def _eqt_act0(bn, x):
+    """relu(bn(x)) in float64, rounded to fp32: the input of a ResCNN block's conv1 (the kernels apply the BatchNorm as one fma)"""
+    s = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
+    b = bn.bias.detach().double() - bn.running_mean.detach().double() * s
+    return torch.relu(x.double() * s.reshape(-1, 1) + b.reshape(-1, 1)).float()
+
+
+def eqt_layers(net):
+    """Every EQTransformer conv layer in forward order, under the names of the debug tensors of plan_flags[1] & 4 (decoder d's
+    stage k: "decoder{d}.{k}", its input "decoder{d}.in", its head's logits "logits{d}": one set of the set-major tensors).
+    Kinds beyond phasenet_layers': ("pool",) conv + ReLU, then max-pool(2) with the odd tail padded as the encoder does;
+    ("res", x) the ResCNN block output x + conv2(mid); "bn" relu(norm1_0(encoder.6)), res.act, no conv (elementwise bar only)."""
+    m = dict(net.named_modules())
+    out = []
+    for k in range(7):
+        prev = "input" if k == 0 else f"encoder.{k - 1}"
+        out.append((f"encoder.{k}", m[f"encoder.convs.{k}"], None, True, ("pool",), lambda a, p=prev: a[p]))
+    out.append(("res.act", None, m["res_cnn_stack.members.0.norm1"], True, "bn", lambda a: a["encoder.6"]))
+    for i in range(7):
+        blk = m[f"res_cnn_stack.members.{i}"]
+        pad = (0, 1) if blk.right_pad else (0, 0)  # K = 2: TF "same" pads on the right only
+        prev = "encoder.6" if i == 0 else f"res.{i - 1}.out"
+        # block 0 reads res.act, which is in memory (written behind encoder stage 6); the later blocks' conv1 inputs exist in
+        # the ResCNN kernel's LDS only and are recomputed from the block before's output
+        act = (lambda a: a["res.act"]) if i == 0 else (lambda a, p=prev, bn=blk.norm1: _eqt_act0(bn, a[p]))
+        out.append((f"res.{i}.mid", blk.conv1, blk.norm2, True, "conv", lambda a, act=act, pad=pad: F.pad(act(a), pad)))
+        out.append((f"res.{i}.conv2", blk.conv2, None, False, "conv", lambda a, i=i, pad=pad: F.pad(a[f"res.{i}.mid"], pad)))
+        out.append((f"res.{i}.out", blk.conv2, None, False, ("res", prev), lambda a, i=i, pad=pad: F.pad(a[f"res.{i}.mid"], pad)))
+    for d, dec in enumerate(EQT_DECODERS):
+        for k in range(7):
+            prev = f"decoder{d}.in" if k == 0 else f"decoder{d}.{k - 1}"
+            crop = k in m[dec].crops  # stage 2: 375 = 2 x 188 - 1
+
+            def up(a, p=prev, crop=crop):
+                x = F.interpolate(a[p], scale_factor=2, mode="nearest")
+                return x[:, :, :-1] if crop else x
+            out.append((f"decoder{d}.{k}", m[f"{dec}.convs.{k}"], None, True, "conv", up))
+        out.append((f"logits{d}", m[EQT_HEADS[d]], None, False, "conv", lambda a, d=d: a[f"decoder{d}.6"]))
+    return out
+
+
+def eqt_acts(net, x):
+    """The fp32 oracle's activations under eqt_layers' names (CPU: the inputs of the teeth test); the middle (BiLSTM stack,
+    transformers, pick branches) is the oracle's own, from res.6.out."""
+    acts = {"input": x}
+    with torch.no_grad():
+        for name, conv, bn, relu, kind, inp in eqt_layers(net):
+            if name == "decoder0.0":
+                for d, h in enumerate(eqt_mid_chain(net, acts["res.6.out"])):
+                    acts[f"decoder{d}.in"] = h
+            acts[name] = layer_forward(conv, bn, relu, kind, inp(acts), torch.float32, acts)
+    return acts
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 def _folded(conv, bn, dtype):
     """(weight, bias) with BatchNorm folded in, float64 -> dtype; weight laid out as the module's."""
     w = conv.weight.detach().double()
@@ -85,6 +144,12 @@ def _conv(conv, x, w, b, kind):
 
 
 def _glue_out(y, kind, acts):
+    if isinstance(kind, tuple) and kind[0] == "pool":  # EQTransformer encoder: TF "same" max-pool on odd lengths
+        if y.shape[-1] % 2:
+            y = F.pad(y, (0, 1), "constant", OC.EQT_POOL_PAD_VALUE)
+        return F.max_pool1d(y, 2)
+    if isinstance(kind, tuple) and kind[0] == "res":
+        return y
     if isinstance(kind, tuple):  # PhaseNet transposed conv: crop, then centre on the skip tensor it is concatenated with
         y = y[:, :, OC.PN_UP_CROP[0]:y.shape[-1] - OC.PN_UP_CROP[1]]
         return _centre(y, acts[f"down{kind[1]}.same"].shape[-1]) if acts is not None else y
@@ -93,13 +158,19 @@ def _glue_out(y, kind, acts):
 
 def layer_forward(conv, bn, relu, kind, x, dtype, acts=None, weight_fn=None):
     """The layer as the oracle runs it (conv, BatchNorm unfolded, ReLU) in `dtype`; weight_fn(w) may alter the conv weight
-    (teeth test).  acts: for the centring of a transposed conv's output (PhaseNet)."""
-    ck = "conv" if kind == "conv" else "convT"
-    w = conv.weight.detach().to(dtype)
-    if weight_fn is not None:
-        w = weight_fn(w)
-    b = conv.bias.detach().to(dtype) if conv.bias is not None else None
-    y = _conv(conv, x.to(dtype), w, b, ck)
+    (teeth test).  acts: for the centring of a transposed conv's output (PhaseNet) and the residual stream a ResCNN block's
+    output adds to (EQTransformer)."""
+    if kind == "bn":
+        y = x.to(dtype)
+    else:
+        ck = "convT" if kind == "convT" or (isinstance(kind, tuple) and kind[0] == "convT") else "conv"
+        w = conv.weight.detach().to(dtype)
+        if weight_fn is not None:
+            w = weight_fn(w)
+        b = conv.bias.detach().to(dtype) if conv.bias is not None else None
+        y = _conv(conv, x.to(dtype), w, b, ck)
+    if isinstance(kind, tuple) and kind[0] == "res":
+        y = acts[kind[1]].to(dtype) + y
     if bn is not None:
         y = F.batch_norm(y, bn.running_mean.to(dtype), bn.running_var.to(dtype), bn.weight.detach().to(dtype),
                          bn.bias.detach().to(dtype), False, 0.0, bn.eps)
@@ -110,9 +181,15 @@ def layer_forward(conv, bn, relu, kind, x, dtype, acts=None, weight_fn=None):
 
 def elem_scale(conv, bn, kind, x, acts=None):
     """sum |w_folded| |x| + |b_folded| per output element, float64."""
-    ck = "conv" if kind == "conv" else "convT"
+    if kind == "bn":  # |s x| + |b|: the BatchNorm as one fma
+        sc = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
+        sh = bn.bias.detach().double() - bn.running_mean.detach().double() * sc
+        return x.double().abs() * sc.abs().reshape(-1, 1) + sh.abs().reshape(-1, 1)
+    ck = "convT" if kind == "convT" or (isinstance(kind, tuple) and kind[0] == "convT") else "conv"
     w, b = _folded(conv, bn, torch.float64)
     s = _conv(conv, x.double().abs(), w.abs(), b.abs(), ck)
+    if isinstance(kind, tuple) and kind[0] == "res":  # the residual add: |x_prev| joins the bound
+        s = s + acts[kind[1]].double().abs()
     return _glue_out(s, kind, acts)
 
 

@@ -1,8 +1,9 @@
 """Every layer of the shipped one-launch PhaseNet kernel (pn_window_kernel, bf16 three-piece operands) against float64, on the
 kernel's own input to that layer (tests/layer_f64.py).  The kernel's DUMP instance (plan_flags[1] & 4) writes each layer's
 fp32 output and the head's logits; its output probabilities must equal the shipped instance's bit for bit, which ties the
-dumps to the shipped arithmetic.  EQTransformer's middle kernel (eqt_mid4) is checked the same way from its own input and
-output, which the default plan keeps in memory."""
+dumps to the shipped arithmetic.  EQTransformer's five conv kernels have DUMP instances under the same flag and are checked
+the same way, every conv layer of the encoder, the ResCNN stack, the three decoders and the heads; its middle kernel (eqt_mid4)
+is checked from its own input and output, which the default plan keeps in memory."""
 import copy
 import ctypes as C
 
@@ -13,8 +14,8 @@ import torch
 from oracle import pipeline as OP
 from oracle.models import load_pretrained
 from tests.gpu_util import debug_tensors
-from tests.layer_f64 import C_ELEM, K_RMS, check_layer, eqt_mid_chain, phasenet_layers, rel_rms, report
-from tests.test_gpu_parity_wide import _scaled_state
+from tests.layer_f64 import C_ELEM, K_RMS, check_layer, eqt_layers, eqt_mid_chain, phasenet_layers, rel_rms, report
+from tests.test_gpu_parity_wide import _as_array, _scaled_state
 from volpick_amd import EQTransformer, PhaseNet, _lib
 from volpick_amd.synthetic import synthetic_windows
 
@@ -71,12 +72,12 @@ def test_every_layer_matches_float64(weights, B):
     _check(oracle, xn, weights, label=f"phasenet {weights}")
 
 
-def _edge_windows(B, seed):
+def _edge_windows(B, seed, T=3001):
     """energy at both ends of the window (the tiles that meet the zero padding) and a DC offset"""
     rng = np.random.default_rng(seed)
-    x = synthetic_windows(B, 3001, seed=seed)
-    t = np.arange(3001)
-    burst = np.exp(-((t[:, None] - np.array([40, 2960])[None]) / 12.0) ** 2).sum(axis=1)
+    x = synthetic_windows(B, T, seed=seed)
+    t = np.arange(T)
+    burst = np.exp(-((t[:, None] - np.array([40, T - 41])[None]) / 12.0) ** 2).sum(axis=1)
     x = x + (5.0 * x.std() * rng.standard_normal((B, 3, 1)) * np.sin(0.7 * t) * burst).astype(np.float32)
     x[B // 2:] += np.float32(3.0 * np.abs(x).max())  # DC offset
     return x.astype(np.float32)
@@ -150,3 +151,105 @@ def test_eqt_middle_kernel_matches_float64(weights, B, rows):
                 bad.append((b, nm, e / e32))
     print(f"\n[eqt_mid4 {weights}] B={B}\n" + "\n".join(lines))
     assert not bad, f"eqt_mid4 beyond {K_MID} x torch-fp32's error from res.xa: {bad}"
+
+
+# ---- EQTransformer's five conv kernels (bf16 three-piece operands), layer by layer ----------------------------------------------
+# front (encoder.0-2), enc36_b3 (encoder.3-6, res.act), res3t (the ResCNN's 14 convs), dec03 (decoder.0-3 of the three decoders),
+# tail3 (decoder.4-6 and the heads' logits): their DUMP instances (plan_flags[1] & 4) write every conv's fp32 output.
+SET_MAJOR = ("decoder.in", *(f"decoder.{k}" for k in range(7)), "logits")  # rows d B + b: decoder d's window b
+
+
+def _halo_words(model):
+    lib, bad, where = _lib.load(), C.c_int64(-1), C.c_char_p()
+    _lib.check(lib.vp_debug_check_halos(model._handle, 0, C.byref(bad), C.byref(where)), "vp_debug_check_halos")
+    return bad.value, where.value
+
+
+def _eqt_dumps(model, B):
+    """every tensor the DUMP plan keeps, under eqt_layers' names: the set-major ones split into decoder{d}.k / logits{d}"""
+    t = {k: torch.from_numpy(v) for k, v in debug_tensors(model, B).items() if k not in SET_MAJOR}
+    for name in SET_MAJOR:
+        a = _read(model, name, 3 * B)
+        for d in range(3):
+            key = name.replace("decoder.", f"decoder{d}.") if name != "logits" else f"logits{d}"
+            t[key] = a[d * B:(d + 1) * B]
+    return t
+
+
+def _eqt_check(oracle, xn, weights, rows=None, state=None, label=""):
+    """The shipped plan and the DUMP plan on xn; the DUMP plan runs a different batch of the same size first, so that a sample
+    its dumps skip holds a stale value.  rows: windows checked in float64 (None = all)."""
+    B = xn.shape[0]
+    other = torch.flip(xn, dims=(0, 2)).contiguous()
+    outs = []
+    for flags in ((0,), DUMP):
+        m = EQTransformer.from_pretrained(weights)
+        if state is not None:
+            m.load_state_dict(state)
+        m._plan_flags = flags
+        m._max_batch = max(256, B)
+        m.cuda()
+        try:
+            if flags == DUMP:
+                m(other)
+            outs.append(_as_array(m(xn)))
+            if flags == DUMP:
+                t = _eqt_dumps(m, B)
+                halos = _halo_words(m)
+        finally:
+            m._release()
+    y = outs[0]
+    assert np.array_equal(y, outs[1], equal_nan=True), f"{label}: the DUMP plan's probabilities differ from the shipped plan's"
+    assert halos[0] == 0, f"{label}: the DUMP plan wrote into the zero margin of {halos[1]}"
+    assert torch.equal(t["res.6.out"], t["res.xa"]), f"{label}: the dumped block-6 output is not the ResCNN kernel's output"
+    # the dumped logits are the probabilities' own (sigmoid as v_exp + v_rcp in the kernel: 3e-7)
+    for d in range(3):
+        p = torch.sigmoid(t[f"logits{d}"][:, 0].double()).numpy()
+        assert np.abs(p - y[:, d]).max() < 1e-6, (label, d)
+    layers = eqt_layers(oracle)
+    assert len(layers) == 7 + 1 + 3 * 7 + 3 * 8
+    res = [check_layer(layer, t, t[layer[0]], rows) for layer in layers]
+    print(f"\n[{label}] B={B} windows {'all' if rows is None else rows}\n" + report(res))
+    # res.act is a BatchNorm without a conv (eqt_enc36_b3_kernel applies it as one fma): the elementwise bar only
+    bad = [r["name"] for r in res
+           if not (r["finite"] and r["elem_ratio"] <= C_ELEM and (r["name"] == "res.act" or r["rms_ratio"] <= K_RMS))]
+    assert not bad, f"{label}: layers beyond the float64 bars (rms ratio <= {K_RMS}, elementwise <= {C_ELEM}): {bad}"
+
+
+@pytest.mark.parametrize("weights", ["volpick", "volpick_95train"])
+@pytest.mark.parametrize("B", [1, 3, 4, 5])
+def test_eqt_conv_layers_match_float64(weights, B):
+    """B = 1, 4 and 5 leave the ResCNN kernel's last workgroup (three windows) with a clamped, repeated window"""
+    oracle = load_pretrained("eqtransformer", weights)
+    xn = OP.batch_pre(oracle, torch.from_numpy(synthetic_windows(B, 6000, seed=960 + B)))
+    _eqt_check(oracle, xn, weights, label=f"eqt {weights}")
+
+
+@pytest.mark.slow
+@pytest.mark.parametrize("weights", ["volpick", "volpick_95train"])
+def test_eqt_conv_layers_match_float64_257(weights):
+    """B = 257: enc36_b3 and dec03 wrap their 256-workgroup grids (window 256 is workgroup 0's second), the ResCNN kernel's last
+    workgroup holds windows 255, 256, 256, the tail's workgroups cross decoder changes; windows checked in all three decoders"""
+    oracle = load_pretrained("eqtransformer", weights)
+    xn = OP.batch_pre(oracle, torch.from_numpy(synthetic_windows(257, 6000, seed=977)))
+    _eqt_check(oracle, xn, weights, rows=[0, 1, 128, 255, 256], label=f"eqt {weights}")
+
+
+@pytest.mark.parametrize("weights", ["volpick", "volpick_95train"])
+def test_eqt_edge_energy_and_dc_offset(weights):
+    oracle = load_pretrained("eqtransformer", weights)
+    x = _edge_windows(5, seed=981, T=6000)
+    xn = torch.cat([OP.batch_pre(oracle, torch.from_numpy(x)), torch.from_numpy(x / np.abs(x).max(axis=(1, 2), keepdims=True))])
+    _eqt_check(oracle, xn, weights, label=f"eqt {weights} edges + DC")
+
+
+@pytest.mark.parametrize("scale", [1e20, 1e-20])
+def test_eqt_activations_far_from_unity(scale):
+    """test_gpu_parity_wide's scaling: encoder stage 5's output and decoder stage 4's at scale times their size"""
+    oracle = load_pretrained("eqtransformer", "volpick")
+    big = copy.deepcopy(oracle)
+    big.load_state_dict(_scaled_state("eqtransformer", big.state_dict(), scale), strict=True)
+    sd = EQTransformer.from_pretrained("volpick").state_dict()
+    state = {k: (v.numpy() if torch.is_tensor(v) else v) for k, v in _scaled_state("eqtransformer", sd, scale).items()}
+    xn = OP.batch_pre(oracle, torch.from_numpy(synthetic_windows(3, 6000, seed=4500)))
+    _eqt_check(big, xn, "volpick", state=state, label=f"eqt activations x {scale:g}")

@@ -245,7 +245,8 @@ PLAN_SELECTORS = {
     "phasenet": [(1,), (0, 1), (0, 0, 0, 1), (0, 0, 0, 0, 1), (0, 0, 0, 0, 0, 1), (0, 0, 0, 0, 0, 2),
                  (0, 0, 0, 0, 0, 3), (0, 0, 0, 0, 0, 8), (0, 0, 0, 0, 0, 0, 1), (0, 4)],
     "eqtransformer": [(1,), (0, 0, 1), (0, 0, 2), (0, 0, 3), (0, 0, 0, 0, 1), (0, 0, 0, 0, 0, 0, 2)] +
-                     [(0, 0, 0, 0, 0, 0, 0, 1 << b) for b in range(12)] + [(0, 0, 0, 0, 0, 0, 0, 0x1F0), (0, 0, 0, 0, 0, 0, 0, 0xF)],
+                     [(0, 0, 0, 0, 0, 0, 0, 1 << b) for b in range(12)] + [(0, 0, 0, 0, 0, 0, 0, 0x1F0), (0, 0, 0, 0, 0, 0, 0, 0xF)] +
+                     [(0, 4), (0, 4, 0, 0, 0, 0, 0, 1024)],
 }
 
 
@@ -266,6 +267,25 @@ def test_removed_plan_selectors_are_rejected(name, flags):
     with pytest.raises(VolpickHipError, match="removed in round 6"):
         m.cuda()
         m(torch.zeros((1, 3, m.in_samples)).cuda())
+
+
+# EQTransformer's layer dumps (plan_flags[1] & 4) exist for the default conv kernels only: every selector that swaps one out is refused
+EQT_DUMP_REFUSED = [(1, 4), (0, 4, 0, 1), (0, 4, 0, 0, 0, 0, 2)] + \
+                   [(0, 4, 0, 0, 0, 0, 0, 1 << b) for b in (0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 11, 13)]
+
+
+@pytest.mark.parametrize("flags", EQT_DUMP_REFUSED, ids=[".".join(map(str, f)) for f in EQT_DUMP_REFUSED])
+def test_eqt_dumps_refuse_other_kernel_forms(flags):
+    from volpick_amd._lib import VolpickHipError
+
+    m = va.EQTransformer.from_pretrained("volpick")
+    m._plan_flags = flags
+    try:
+        with pytest.raises(VolpickHipError, match="dumps the default conv kernels only"):
+            m.cuda()
+            m(torch.zeros((1, 3, m.in_samples)).cuda())
+    finally:
+        m._release()
 
 
 @pytest.mark.parametrize("name,flags", [(n, f) for n, fl in PLAN_SELECTORS.items() for f in fl],

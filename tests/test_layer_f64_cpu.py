@@ -3,16 +3,17 @@ with the lo piece of its three-piece bf16 operands dropped (weights or input tru
 product term), must fail the bars the GPU test holds the shipped kernels to -- by a margin, so that the bars cannot be
 loosened until they no longer see that fault -- while plain fp32 passes them.
 
-What is measured here is the bare conv (no BatchNorm, no ReLU, unfolded weights; the volpick weights, two windows), a close
+What is measured first is the bare conv (no BatchNorm, no ReLU, unfolded weights; the volpick weights, two windows), a close
 neighbour of what the GPU test compares (post-BatchNorm / ReLU outputs of layers whose kernels fold BatchNorm into the weights):
-the margin shows the metric's sensitivity to the fault, not the GPU test's exact numbers.  This runs no kernel: it covers the
-bars, and EQTransformer's layers here have no per-layer check on hardware yet (only eqt_mid4 does, as one chain)."""
+the margin shows the metric's sensitivity to the fault, not the GPU test's exact numbers.  EQTransformer's layers are then
+measured through the very descriptors the GPU test uses (tests/layer_f64.eqt_layers).  This runs no kernel: it covers the bars."""
 import pytest
 import torch
 
 from oracle import pipeline as OP
 from oracle.models import load_pretrained
-from tests.layer_f64 import C_ELEM, EPS24, K_RMS, attention_rows, bf16_drop_lo, elem_scale, layer_forward, rel_rms
+from tests.layer_f64 import (C_ELEM, EPS24, K_RMS, attention_rows, bf16_drop_lo, elem_scale, eqt_acts, eqt_layers, layer_forward,
+                              rel_rms)
 from volpick_amd.synthetic import synthetic_windows
 
 MARGIN = 1.75  # the weakest case, EQTransformer pick_convs.0 with its weights' lo piece dropped, sits at 1.8 x K_RMS
@@ -54,6 +55,36 @@ def test_dropped_lo_piece_fails_the_layer_bars(model):
                 if not (rr > MARGIN * K_RMS or ee > MARGIN * C_ELEM):
                     weak.append((name, what, round(rr, 2), round(ee, 2)))
     assert not weak, f"{model}: a dropped lo piece passes the per-layer bars (rms ratio, elementwise ratio): {weak}"
+
+
+def test_dropped_lo_piece_fails_the_eqt_layer_bars():
+    """The same over the descriptors the GPU test holds EQTransformer's conv kernels to (tests/layer_f64.eqt_layers: BatchNorm,
+    ReLU, max-pool, the residual stream's glue), on the fp32 oracle's own activations.  Exempt: the ResCNN block outputs
+    x + conv2(mid) -- the residual stream dilutes the conv's error, and the conv is held to the bars by its increment
+    descriptor res.{i}.conv2, which exists for that reason -- and res.act, a BatchNorm without a conv."""
+    net = load_pretrained("eqtransformer", "volpick")
+    x = OP.batch_pre(net, torch.from_numpy(synthetic_windows(2, net.in_samples, seed=3)))
+    acts = eqt_acts(net, x)
+    layers = [l for l in eqt_layers(net) if l[4] != "bn" and not (isinstance(l[4], tuple) and l[4][0] == "res")]
+    assert len(layers) == 7 + 14 + 3 * 8
+    weak, lines = [], []
+    for name, conv, bn, relu, kind, inp in layers:
+        xin = inp(acts).float()
+        with torch.no_grad():
+            ref = layer_forward(conv, bn, relu, kind, xin, torch.float64, acts)
+            scale = EPS24 * elem_scale(conv, bn, kind, xin, acts)
+            elem = lambda y: float(((y.double() - ref).abs() / (scale + 1e-300)).max())
+            y32 = layer_forward(conv, bn, relu, kind, xin, torch.float32, acts)
+            r32, e32 = rel_rms(y32, ref), elem(y32)
+            assert e32 <= C_ELEM, (name, e32)
+            for what, y in (("weights", layer_forward(conv, bn, relu, kind, xin, torch.float32, acts, weight_fn=bf16_drop_lo)),
+                            ("input", layer_forward(conv, bn, relu, kind, bf16_drop_lo(xin), torch.float32, acts))):
+                rr, ee = rel_rms(y, ref) / r32, elem(y)
+                lines.append(f"{name:12s} {what:7s} rms ratio {rr:7.2f}  elementwise {ee:7.2f}")
+                if not (rr > MARGIN * K_RMS or ee > MARGIN * C_ELEM):
+                    weak.append((name, what, round(rr, 2), round(ee, 2)))
+    print("\n" + "\n".join(lines))
+    assert not weak, f"a dropped lo piece passes the EQTransformer layer bars (rms ratio, elementwise ratio): {weak}"
 
 
 def test_row_blocked_attention_is_the_oracle_module_bit_for_bit():

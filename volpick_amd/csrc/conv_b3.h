@@ -381,6 +381,18 @@ struct B3Chunk {
   static_assert(NC % 2 == 0, "16-byte columns; the bank property above holds for NC % 16 == 0 (PhaseNet's up1.same output: 194)");
   static constexpr int CHS = NC * 8, PS = (C / 8) * CHS;  // bf16 per chunk plane / per piece
 };
+// DUMP instances (tests): samples [0, L) of the C channels of a chunk-plane piece image (sample t at column t + c0), joined back
+// into the fp32 values their epilogue split -- hi + (mid + lo) is exact in that order -- into rows ls floats apart (dst: channel
+// 0, sample 0)
+template <int C, int NC>
+__device__ void b3c_dump(const bf16_t* img, const int c0, const int L, float* dst, const long ls, const int tid, const int nth) {
+  using Q = B3Chunk<C, NC>;
+  for (int k = tid; k < C * L; k += nth) {
+    const int c = k / L, t = k - c * L;
+    const bf16_t* p = img + (c >> 3) * Q::CHS + (t + c0) * 8 + (c & 7);
+    dst[c * ls + t] = from_bf16(p[0]) + (from_bf16(p[Q::PS]) + from_bf16(p[2 * Q::PS]));
+  }
+}
 // four consecutive channels 4 quad .. 4 quad + 3 of column col, split into the three pieces (pairs at a time: v_cvt_pk_bf16_f32)
 // B3_EXP (timing probes of tools/, never in the product build; results are WRONG with any of them): 4 = b3c_store4 computes the
 // pieces and stores nothing, 16 = it does not compute them either, 32 = it stores them where sixteen lanes fill 128 contiguous bytes

@@ -143,6 +143,13 @@ AttnWeights resolve(const AttnWeights& w) { return AttnWeights{dptr(w.Wt), dptr(
 }  // namespace
 
 int plan_eqt(Net& net, const ParamView& pv) {
+  // plan_flags[1] & 4: the DUMP instances of the five fused conv kernels (plan_eqt_fuse_*), which exist for their default forms only
+  if ((net.cfg.plan_flags[1] & 4) && (net.cfg.plan_flags[0] != 0 || net.cfg.plan_flags[3] != 0 || net.cfg.plan_flags[6] == 2 ||
+                                      (net.cfg.plan_flags[7] & ~1024) != 0)) {
+    set_error("EQTransformer plan_flags[1] & 4 dumps the default conv kernels only (plan_flags[0], [3], [7] other than bit 10 unset, "
+              "[6] != 2)");
+    return VP_ERR_UNSUPPORTED;
+  }
   const float eps = net.cfg.bn_eps;
   const int T = 6000;
   net.in_samples = T;

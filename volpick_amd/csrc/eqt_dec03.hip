@@ -11,6 +11,8 @@
 // K-step ahead (conv_lds_areg).  The two outputs at the cropped right edge of stage 2 (eqt.hip: decoder2_edge_kernel)
 // are computed by one wave beside the stage itself, from the definition, with the same pre-summed taps.
 // Same packed fragments, same K order: bit-identical to the launches it replaces (plan flag plan_flags[7] & 2 keeps them).
+#include <type_traits>
+
 #include "conv_b3.h"
 #include "conv_lds.h"
 #include "eqt_kernels.h"
@@ -75,6 +77,15 @@ struct Dec03Args {
   int B, n_rows;
   int even_split;  // plan_flags[7] bit 11: stage 3's n-tiles 12 + 12 over the two waves of a SIMD instead of 14 + 10
   unsigned long long* clk;  // -DD3_CLOCK=1 builds (tools/dec03_clock.py): shader-clock stamps of waves 0 and 4 of workgroup 0
+};
+// The DUMP instance of the B3 form (plan_flags[1] & 4, tests/test_gpu_layers_f64.py) also writes the outputs of stages 0, 1 and 2
+// (with the two edge samples) to decoder.0 / .1 / .2: stages 0 and 1 read back out of their piece images behind the barrier that
+// closes the stage, stage 2 and the edge from the registers the piece stores split.  A struct of its own: the default instances'
+// arguments stay.
+struct Dec03DumpArgs : Dec03Args {
+  float* dbg[3];
+  int dbg_ls[3];
+  long dbg_ws[3];
 };
 
 // Stage output t = 2 * column + phase at img[co * S + t]; [0, len) is the row, beyond it the next stage's zero padding.
@@ -152,8 +163,9 @@ struct ClipQuad {
   }
 };
 
-template <bool B3>
-__global__ __launch_bounds__(D03_NTH) void eqt_dec03_kernel(const Dec03Args a) {
+template <bool B3, bool DUMP = false>
+__global__ __launch_bounds__(D03_NTH) void eqt_dec03_kernel(const std::conditional_t<DUMP, Dec03DumpArgs, Dec03Args> a) {
+  static_assert(!DUMP || B3, "DUMP instances exist for the default form only");
   extern __shared__ float4 d03_lds_raw[];
   float* lds = reinterpret_cast<float*>(d03_lds_raw);
   if constexpr (B3) {
@@ -237,6 +249,7 @@ __global__ __launch_bounds__(D03_NTH) void eqt_dec03_kernel(const Dec03Args a) {
         D3_STAMP()  // 2: stage 0 done (this wave)
         __syncthreads();
         D3_STAMP()  // 3: barrier
+        if constexpr (DUMP) b3c_dump<64, B3_X1_NC>(X1, 1, L1, a.dbg[0] + (long)row * a.dbg_ws[0] + HALO, a.dbg_ls[0], tid, D03_NTH);
         b3c_mac_tile_pairs<64, B3_X1_NC, 3, 6>(b3c_lane_ptr<64, B3_X1_NC, 3>(X1, 0, lane), a1, [&](const int j, const f32x4 acc) {
           const int t = 2 * (j * 16 + n) + ph;
           float v[4];
@@ -250,6 +263,7 @@ __global__ __launch_bounds__(D03_NTH) void eqt_dec03_kernel(const Dec03Args a) {
       b3_load_a<64, 3>(a.af3[1] + d * a.af3_stride[1], wave_u & 3, lane, a2);
       __syncthreads();
       D3_STAMP()  // 5: barrier
+      if constexpr (DUMP) b3c_dump<64, B3_X2_NC>(X2, 1, L2, a.dbg[1] + (long)row * a.dbg_ws[1] + HALO, a.dbg_ls[1], tid, D03_NTH);
       float eb;
       {  // stage 2: 64 x 188 -> 32 x 375 (three-piece image in the place of the dead stage-0 / stage-1 inputs: its padding
          // columns are cleared here, every row) + the two samples at the cropped edge from the definition
@@ -283,6 +297,14 @@ __global__ __launch_bounds__(D03_NTH) void eqt_dec03_kernel(const Dec03Args a) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) v[r] = fmaxf(acc[r] + bias2[r], 0.f);
             st.quad(co0, 2 * (colb + j * 16 + n) + ph, v);
+            if constexpr (DUMP) {
+              const int t = 2 * (colb + j * 16 + n) + ph;
+              if (t < L3 - 2) {
+                float* p = a.dbg[2] + (long)row * a.dbg_ws[2] + HALO + (long)co0 * a.dbg_ls[2] + t;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) p[(long)r * a.dbg_ls[2]] = v[r];
+              }
+            }
           }, [&](const int i) {  // 18 slots: a weight triple every other one
             if (i % 2 == 0 && i / 2 < 8) ew[i / 2] = e[(i / 2) * 64];
           });
@@ -338,6 +360,9 @@ __global__ __launch_bounds__(D03_NTH) void eqt_dec03_kernel(const Dec03Args a) {
         const int ch = lane >> 1;
         bf16_t* q = X3 + (ch >> 3) * QX3::CHS + (L3 - 2 + (lane & 1) + B3_X3_C0) * 8 + (ch & 7);
         q[0] = h, q[QX3::PS] = m, q[2 * QX3::PS] = l;
+        if constexpr (DUMP) {
+          if (wave_u == 4) a.dbg[2][(long)row * a.dbg_ws[2] + HALO + (long)ch * a.dbg_ls[2] + L3 - 2 + (lane & 1)] = fmaxf(acc, 0.f);
+        }
       }
       {  // stage 3: 32 x 375 -> 32 x 750, straight to memory: rows (channel, phase), so a lane's accumulator pairs are
          // two consecutive samples of one channel (8-byte stores, full 128-byte lines per 16 lanes)
@@ -508,7 +533,14 @@ int plan_eqt_fuse_dec03(Net& net, bool b3) {
     for (int i = 0; i < 3; ++i) p3[i] = net.add_blob(b3_operand(*c[1 + i], i < 2));
   }
   const int x_in = c[0]->src1, y_out = c[3]->dst;
-  for (int i = 0; i < 3; ++i) net.tensor_sets[c[i]->dst] = 0;  // stages 0-2 live in LDS under this plan
+  // stages 0-2 live in LDS under this plan; plan_flags[1] & 4 keeps them (3 sets) for the DUMP instance
+  const bool dumps = (net.cfg.plan_flags[1] & 4) != 0;
+  if (dumps && !b3) {
+    set_error("fused decoder stages 0-3: dumps exist for the bf16-piece form only");
+    return VP_ERR_UNSUPPORTED;
+  }
+  if (!dumps)
+    for (int i = 0; i < 3; ++i) net.tensor_sets[c[i]->dst] = 0;
   Step st;
   st.name = "fused.dec03 (decoder.0-3, one row per workgroup)";
   st.flops_per_window = 0;
@@ -545,7 +577,19 @@ int plan_eqt_fuse_dec03(Net& net, bool b3) {
         a.af3[i] = reinterpret_cast<const uint4*>(p3[i]->d);
         a.af3_stride[i] = (long)(p3[i]->h.size() / 3 / 4);
       }
-      hipLaunchKernelGGL(eqt_dec03_kernel<true>, dim3(grid), dim3(D03_NTH), B3_LDS_BYTES, s, a);
+      if (dumps) {
+        Dec03DumpArgs dd{};
+        static_cast<Dec03Args&>(dd) = a;
+        for (int i = 0; i < 3; ++i) {
+          const Tensor& t = n.tensors[c[i]->dst];
+          dd.dbg[i] = t.p;
+          dd.dbg_ls[i] = t.ls;
+          dd.dbg_ws[i] = (long)t.win_stride();
+        }
+        hipLaunchKernelGGL((eqt_dec03_kernel<true, true>), dim3(grid), dim3(D03_NTH), B3_LDS_BYTES, s, dd);
+      } else {
+        hipLaunchKernelGGL(eqt_dec03_kernel<true>, dim3(grid), dim3(D03_NTH), B3_LDS_BYTES, s, a);
+      }
     } else {
       hipLaunchKernelGGL(eqt_dec03_kernel<false>, dim3(grid), dim3(D03_NTH), D03_LDS_FLOATS * sizeof(float), s, a);
     }
@@ -555,6 +599,8 @@ int plan_eqt_fuse_dec03(Net& net, bool b3) {
     net.extra_kernels.push_back({reinterpret_cast<const void*>(&eqt_dec03_kernel<true>), (size_t)B3_LDS_BYTES});
   else
     net.extra_kernels.push_back({reinterpret_cast<const void*>(&eqt_dec03_kernel<false>), D03_LDS_FLOATS * sizeof(float)});
+  if (dumps)
+    net.extra_kernels.push_back({reinterpret_cast<const void*>(&eqt_dec03_kernel<true, true>), (size_t)B3_LDS_BYTES});
   net.steps.erase(net.steps.begin() + first, net.steps.begin() + first + 5);
   net.steps.insert(net.steps.begin() + first, std::move(st));
   return VP_OK;

@@ -15,6 +15,8 @@
 //
 // Plan flag plan_flags[7] & 128 keeps the fp32-MFMA kernel (bit-identical to the layer launches); this one agrees with it
 // to fp32 rounding (tests/test_gpu_eqt.py).
+#include <type_traits>
+
 #include "conv_b3.h"
 #include "eqt_kernels.h"
 #include "net.h"
@@ -57,6 +59,13 @@ struct Enc36B3Args {
   const float* bn_s;    // norm1 of the first residual block, folded: act = relu(s * y + b)
   const float* bn_b;
   int B;
+};
+// The DUMP instance (plan_flags[1] & 4, tests/test_gpu_layers_f64.py) also writes the pooled outputs of stages 3, 4 and 5 -- the fp32
+// values the epilogues split into pieces -- to encoder.3 / .4 / .5.  A struct of its own: the default instance's arguments stay.
+struct Enc36B3DumpArgs : Enc36B3Args {
+  float* dbg[3];
+  int dbg_ls[3];
+  long dbg_ws[3];
 };
 
 // b3_load_a with a uniform base and an opaque 32-bit lane offset: inside the window loop the per-lane 64-bit addresses of
@@ -104,7 +113,8 @@ __device__ __forceinline__ void zero_pads(bf16_t* img, const int len, const int 
   }
 }
 
-__global__ __launch_bounds__(E3_NTH) void eqt_enc36_b3_kernel(const Enc36B3Args a) {
+template <bool DUMP = false>
+__global__ __launch_bounds__(E3_NTH) void eqt_enc36_b3_kernel(const std::conditional_t<DUMP, Enc36B3DumpArgs, Enc36B3Args> a) {
   extern __shared__ uint4 e3_lds[];
   char* base = reinterpret_cast<char*>(e3_lds);
   bf16_t* X3 = reinterpret_cast<bf16_t*>(base);             // region A
@@ -117,6 +127,14 @@ __global__ __launch_bounds__(E3_NTH) void eqt_enc36_b3_kernel(const Enc36B3Args 
   if (win >= a.B) return;
   const int mt2 = w & 1, blk2 = w >> 1;  // stages with two m-tiles
   const int mt4 = w & 3, blk4 = w >> 2;  // stages with four
+  // DUMP: channels co .. co + 3 of pooled sample t of stage i (0: stage 3), from the registers the piece store splits
+  auto dump = [&](const int i, const int co, const int t, const float (&m)[4]) {
+    if constexpr (DUMP) {
+      float* p = a.dbg[i] + (long)win * a.dbg_ws[i] + HALO + (long)co * a.dbg_ls[i] + t;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) p[(long)r * a.dbg_ls[i]] = m[r];
+    }
+  };
   while (true) {
     uint4 a3[B3Steps<16, 7>::STEPS * 3];
     float bias3[4];
@@ -154,7 +172,10 @@ __global__ __launch_bounds__(E3_NTH) void eqt_enc36_b3_kernel(const Enc36B3Args 
         const int c = colb + j * 16 + n;
         float m[4];
         pool4(acc, bias3, c < N3, m);
-        if (!(n & 1) && (c >> 1) < N4) b3c_store4<32, NC4>(X4, (c >> 1) + K4, 4 * mt2 + g, m);
+        if (!(n & 1) && (c >> 1) < N4) {
+          b3c_store4<32, NC4>(X4, (c >> 1) + K4, 4 * mt2 + g, m);
+          dump(0, 16 * mt2 + 4 * g, c >> 1, m);
+        }
       });
     }
     __syncthreads();
@@ -169,7 +190,10 @@ __global__ __launch_bounds__(E3_NTH) void eqt_enc36_b3_kernel(const Enc36B3Args 
         const int c = colb + j * 16 + n;
         float m[4];
         pool4(acc, bias4, c < N4, m);
-        if (!(n & 1) && (c >> 1) < N5) b3c_store4<32, NC5>(X5, (c >> 1) + K5, 4 * mt2 + g, m);
+        if (!(n & 1) && (c >> 1) < N5) {
+          b3c_store4<32, NC5>(X5, (c >> 1) + K5, 4 * mt2 + g, m);
+          dump(1, 16 * mt2 + 4 * g, c >> 1, m);
+        }
       });
     }
     __syncthreads();
@@ -184,7 +208,10 @@ __global__ __launch_bounds__(E3_NTH) void eqt_enc36_b3_kernel(const Enc36B3Args 
         const int c = colb + j * 16 + n;
         float m[4];
         pool4(acc, bias5, c < N5, m);
-        if (!(n & 1) && (c >> 1) < N6) b3c_store4<64, NC6>(X6, (c >> 1) + K6, 4 * mt4 + g, m);
+        if (!(n & 1) && (c >> 1) < N6) {
+          b3c_store4<64, NC6>(X6, (c >> 1) + K6, 4 * mt4 + g, m);
+          dump(2, 16 * mt4 + 4 * g, c >> 1, m);
+        }
       });
     }
     __syncthreads();
@@ -245,7 +272,10 @@ int plan_eqt_fuse_enc36_b3(Net& net) {
   for (int i = 0; i < 4; ++i) p3[i] = net.add_blob(b3_operand(*c[i], false));
   const int x_in = c[0]->src1, y_out = c[3]->dst, act_out = c[3]->dst2;
   net.need(x_in, HALO - K3 + NC3);  // the image row is fetched whole: zero margin up to there
-  for (int i = 0; i < 3; ++i) net.tensor_sets[c[i]->dst] = 0;  // encoder.3 - .5 live in LDS under this plan
+  // encoder.3 - .5 live in LDS under this plan; plan_flags[1] & 4 keeps them for the DUMP instance
+  const bool dumps = (net.cfg.plan_flags[1] & 4) != 0;
+  if (!dumps)
+    for (int i = 0; i < 3; ++i) net.tensor_sets[c[i]->dst] = 0;
   Step st;
   st.name = "fused.enc36 (encoder.3-6, one window per workgroup)";
   st.flops_per_window = 0;
@@ -272,10 +302,23 @@ int plan_eqt_fuse_enc36_b3(Net& net) {
     a.bn_b = c[3]->e2.d;
     a.B = B;
     const int grid = B < 256 ? B : 256;
-    hipLaunchKernelGGL(eqt_enc36_b3_kernel, dim3(grid), dim3(E3_NTH), E3_LDS_BYTES, s, a);
+    if (dumps) {
+      Enc36B3DumpArgs d{};
+      static_cast<Enc36B3Args&>(d) = a;
+      for (int i = 0; i < 3; ++i) {
+        const Tensor& t = n.tensors[c[i]->dst];
+        d.dbg[i] = t.p;
+        d.dbg_ls[i] = t.ls;
+        d.dbg_ws[i] = (long)t.win_stride();
+      }
+      hipLaunchKernelGGL(eqt_enc36_b3_kernel<true>, dim3(grid), dim3(E3_NTH), E3_LDS_BYTES, s, d);
+    } else {
+      hipLaunchKernelGGL(eqt_enc36_b3_kernel<false>, dim3(grid), dim3(E3_NTH), E3_LDS_BYTES, s, a);
+    }
     return 0;
   };
-  net.extra_kernels.push_back({reinterpret_cast<const void*>(&eqt_enc36_b3_kernel), (size_t)E3_LDS_BYTES});
+  net.extra_kernels.push_back({reinterpret_cast<const void*>(&eqt_enc36_b3_kernel<false>), (size_t)E3_LDS_BYTES});
+  if (dumps) net.extra_kernels.push_back({reinterpret_cast<const void*>(&eqt_enc36_b3_kernel<true>), (size_t)E3_LDS_BYTES});
   net.steps.erase(net.steps.begin() + first, net.steps.begin() + first + 4);
   net.steps.insert(net.steps.begin() + first, std::move(st));
   return VP_OK;

@@ -21,6 +21,8 @@
 // pool neighbouring columns = neighbouring lanes (one DPP move) and the even lane stores.
 // Same packed fragments, same K order, same max / ReLU arithmetic: bit-identical to the launches it replaces
 // (plan flag plan_flags[7] & 4 keeps them).
+#include <type_traits>
+
 #include "conv_b3.h"
 #include "conv_lds.h"
 #include "eqt_kernels.h"
@@ -78,6 +80,15 @@ struct FrontArgs {
   PreArgs pre;  // has_pre: the kernel cuts its windows out of the raw stream and normalises them itself (annotate_batch_pre,
   int has_pre;  // arithmetic and reduction order of gather_normalize_kernel: bitwise the same rows); x is then unused
   int B;
+};
+// The DUMP instance of the B3 form (plan_flags[1] & 4, tests/test_gpu_layers_f64.py) also writes the pooled outputs of stages 0 and
+// 1 to encoder.0 / .1, read back out of their piece images behind the barrier that closes the stage: the samples the tile owns
+// (stage 0: [4 j0, 4 j0 + 1000), stage 1: [2 j0, 2 j0 + 500)), each exactly once.  A struct of its own: the default instances'
+// arguments stay.
+struct FrontDumpArgs : FrontArgs {
+  float* dbg[2];
+  int dbg_ls[2];
+  long dbg_ws[2];
 };
 
 // annotate_batch_pre statistics of one window by a 512-thread workgroup, in the arithmetic AND reduction order of
@@ -320,8 +331,9 @@ struct Pool1Store {
 };
 
 // CUT: the kernel cuts its windows out of the raw stream and normalises them itself (FrontArgs::pre).
-template <bool B3, bool CUT>
-__global__ __launch_bounds__(FR_NTH) void eqt_front_kernel(const FrontArgs a) {
+template <bool B3, bool CUT, bool DUMP = false>
+__global__ __launch_bounds__(FR_NTH) void eqt_front_kernel(const std::conditional_t<DUMP, FrontDumpArgs, FrontArgs> a) {
+  static_assert(!DUMP || (B3 && !CUT), "DUMP instances exist for the default form only");
   extern __shared__ float4 fr_lds_raw[];
   float* lds = reinterpret_cast<float*>(fr_lds_raw);
   int off0 = OFF0P / 4, off1 = OFF1P / 4;  // opaque image offsets (eqt_tail.hip)
@@ -455,6 +467,7 @@ __global__ __launch_bounds__(FR_NTH) void eqt_front_kernel(const FrontArgs a) {
         conv_lds_areg<F_e0, SI, BII, SI, BII>(XI, XI, areg0, bias0, 0, C0, st, wave_u, FR_WAVES, lane);
       }
       __syncthreads();
+      if constexpr (DUMP) b3c_dump<8, NC0>(E0, 10, 4 * FW, a.dbg[0] + (long)win * a.dbg_ws[0] + HALO + 4 * j0, a.dbg_ls[0], tid, FR_NTH);
       if (more) request(next);  // travels under stages 1 and 2
       __builtin_amdgcn_sched_barrier(0);
       {  // stage 1: column c <-> conv sample 4 j0 - 6 + c reads image columns c .. c + 8; pooled -> column c / 2 of the stage-2 image
@@ -472,6 +485,7 @@ __global__ __launch_bounds__(FR_NTH) void eqt_front_kernel(const FrontArgs a) {
         });
       }
       __syncthreads();
+      if constexpr (DUMP) b3c_dump<16, NC1>(E1, 3, 2 * FW, a.dbg[1] + (long)win * a.dbg_ws[1] + HALO + 2 * j0, a.dbg_ls[1], tid, FR_NTH);
       {  // stage 2: column c <-> conv sample 2 j0 + c reads image columns c .. c + 6; pooled sample j0 + c / 2 of the encoder.2 row
         const int colb = wave_u * 64;
         float* y = a.y + (long)win * a.ws_y + HALO + j0 + (long)(4 * g) * a.ls_y;
@@ -538,8 +552,16 @@ int plan_eqt_fuse_front(Net& net, bool b3) {
     for (int i = 0; i < 2; ++i) p3[i] = net.add_blob(b3_operand(*c[1 + i], false));
   }
   const int x_in = c[0]->src1, y_out = c[2]->dst;
-  net.tensor_sets[c[0]->dst] = 0;  // encoder.0 / .1 live in LDS under this plan
-  net.tensor_sets[c[1]->dst] = 0;
+  // encoder.0 / .1 live in LDS under this plan; plan_flags[1] & 4 keeps them for the DUMP instance
+  const bool dumps = (net.cfg.plan_flags[1] & 4) != 0;
+  if (dumps && (!b3 || net.cfg.plan_flags[6] == 2)) {
+    set_error("fused encoder front: dumps exist for the bf16-piece form reading the input tensor only");
+    return VP_ERR_UNSUPPORTED;
+  }
+  if (!dumps) {
+    net.tensor_sets[c[0]->dst] = 0;
+    net.tensor_sets[c[1]->dst] = 0;
+  }
   Step st;
   st.name = "fused.front (encoder.0-2, time-tiled)";
   st.flops_per_window = 0;
@@ -572,7 +594,21 @@ int plan_eqt_fuse_front(Net& net, bool b3) {
     const int grid = a.has_pre ? (B < 256 ? B : 256) : (a.n_tiles < 256 ? a.n_tiles : 256);
     if (b3) {
       for (int i = 0; i < 2; ++i) a.af3[i] = reinterpret_cast<const uint4*>(p3[i]->d);
-      if (a.has_pre)
+      if (dumps) {
+        if (a.has_pre) {
+          set_error("fused encoder front: dumps with the in-kernel preprocessing");
+          return VP_ERR_UNSUPPORTED;
+        }
+        FrontDumpArgs d{};
+        static_cast<FrontArgs&>(d) = a;
+        for (int i = 0; i < 2; ++i) {
+          const Tensor& t = n.tensors[c[i]->dst];
+          d.dbg[i] = t.p;
+          d.dbg_ls[i] = t.ls;
+          d.dbg_ws[i] = (long)t.win_stride();
+        }
+        hipLaunchKernelGGL((eqt_front_kernel<true, false, true>), dim3(grid), dim3(FR_NTH), FB_LDS_BYTES, s, d);
+      } else if (a.has_pre)
         hipLaunchKernelGGL((eqt_front_kernel<true, true>), dim3(grid), dim3(FR_NTH), FB_LDS_BYTES, s, a);
       else
         hipLaunchKernelGGL((eqt_front_kernel<true, false>), dim3(grid), dim3(FR_NTH), FB_LDS_BYTES, s, a);
@@ -587,6 +623,7 @@ int plan_eqt_fuse_front(Net& net, bool b3) {
   if (b3) {
     net.extra_kernels.push_back({reinterpret_cast<const void*>(&eqt_front_kernel<true, true>), (size_t)FB_LDS_BYTES});
     net.extra_kernels.push_back({reinterpret_cast<const void*>(&eqt_front_kernel<true, false>), (size_t)FB_LDS_BYTES});
+    if (dumps) net.extra_kernels.push_back({reinterpret_cast<const void*>(&eqt_front_kernel<true, false, true>), (size_t)FB_LDS_BYTES});
   } else {
     net.extra_kernels.push_back({reinterpret_cast<const void*>(&eqt_front_kernel<false, true>), FR_LDS_FLOATS * sizeof(float)});
     net.extra_kernels.push_back({reinterpret_cast<const void*>(&eqt_front_kernel<false, false>), FR_LDS_FLOATS * sizeof(float)});

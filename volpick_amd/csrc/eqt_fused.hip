@@ -3,6 +3,8 @@
 // input and the mid activation in LDS (60 KB); only the packed weights stream in from L2.
 // Same arithmetic and the same packed A-fragments as the 14 conv_mfma_kernel launches it replaces
 // (plan flag plan_flags[0] = 1 keeps those for A/B timing and the layer-by-layer parity test).
+#include <type_traits>
+
 #include "bf16.h"
 #include "conv_lds.h"
 #include "eqt_kernels.h"
@@ -192,6 +194,15 @@ struct Res3Args {
   int warm;                       // 0: no pre-touch of the weights (plan flag plan_flags[4] = 1)
   int n_windows;                  // eqt_res3_kernel<2>: the last workgroup of an odd batch clamps its second window to it
   unsigned long long* clk;        // debug (plan_flags[1] & 2): shader-clock stamps of workgroup 0 (tools/res3_clock.py)
+};
+// The DUMP instance of eqt_res3t_kernel (plan_flags[1] & 4, tests/test_gpu_layers_f64.py) writes, per block i, the fp32 values its
+// epilogues computed -- dbg[3 i] conv1's output relu(conv1 + b) (BatchNorm folded), dbg[3 i + 1] conv2's increment acc + b before the
+// residual add, dbg[3 i + 2] the block's output -- into haloed [64][47] tensors of one row and window stride.  A struct of its own:
+// a longer Res3Args would move the hidden kernel arguments of the default instances.
+struct Res3DumpArgs : Res3Args {
+  float* dbg[21];
+  int dbg_ls;
+  long dbg_ws;
 };
 
 __device__ __forceinline__ void split3(const float v, unsigned short& h, unsigned short& m, unsigned short& l) {
@@ -523,9 +534,26 @@ __global__ __launch_bounds__(256 * WPB) void eqt_res3_kernel(const Res3Args a) {
 //       101 k cycles per THREE windows (33.8 k per window against 53.4 k), matrix pipes 63 % busy (profiles/r06_g_sq_*).
 // The L2 warm-up of rounds 2-5 is gone (8 k cycles of prologue; the parts are requested a whole conv ahead of their use).
 // Same products in the same order into every accumulator, same epilogue arithmetic: bit-identical to eqt_res3_kernel.
-template <int TAPS, int TN, bool CONV2, bool LAST, int NT, int Q0, class NextPart, class Stamp>
+// DUMP instances: one block's epilogue values (Res3DumpArgs::dbg) for this lane's four channels at sample t of tile q (window q / 3)
+template <bool ON, class Args>
+struct Res3Dump {
+  static constexpr bool on = ON;
+  const Args& a;
+  const int* win;
+  int blk, co;
+  __device__ __forceinline__ void operator()(const int q, const int what, const int t, const float (&v)[4]) const {
+    if constexpr (ON) {
+      if (t < RT) {
+        float* p = a.dbg[3 * blk + what] + (long)win[q / 3] * a.dbg_ws + HALO + (long)co * a.dbg_ls + t;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) p[(long)r * a.dbg_ls] = v[r];
+      }
+    }
+  }
+};
+template <int TAPS, int TN, bool CONV2, bool LAST, int NT, int Q0, class NextPart, class Stamp, class Dump>
 __device__ __forceinline__ void res3t_conv(const bf16_t* src_all, bf16_t* dst_all, const Res3A<TAPS>& A, float (&X)[NT][4],
-                                           NextPart next_part, const int lane, const int co, Stamp stamp) {
+                                           NextPart next_part, const int lane, const int co, Stamp stamp, const Dump& dump) {
     constexpr int IN_OFF = (TAPS == 3) ? -1 : 0, STEPS = TAPS * 2, SLOTS = NT * STEPS, AHEAD = 2, NBUF = AHEAD + 1;  // (read-ahead 3 / 4: 104 / 108 k cycles against 101 k)
   constexpr int NL = TN * 2 * 3;  // fragments of the next conv's operand
   const int g = lane >> 4, n = lane & 15;
@@ -542,6 +570,7 @@ __device__ __forceinline__ void res3t_conv(const bf16_t* src_all, bf16_t* dst_al
     if (!CONV2) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) v[r] = (t < RT) ? fmaxf(acc[r] + A.bias[r], 0.f) : 0.f;
+      dump(q, 0, t, v);
     } else {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -551,6 +580,13 @@ __device__ __forceinline__ void res3t_conv(const bf16_t* src_all, bf16_t* dst_al
           X[u][r] = o;
         }
         v[r] = (t < RT) ? fmaxf(fmaf(A.sn[r], o, A.bn[r]), 0.f) : 0.f;
+      }
+      if constexpr (Dump::on) {  // the increment is the first sum of o's: the same fp32 value
+        float d[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) d[r] = acc[r] + A.bias[r];
+        dump(q, 1, t, d);
+        dump(q, 2, t, X[u]);
       }
     }
   };
@@ -591,8 +627,8 @@ __device__ __forceinline__ void res3t_conv(const bf16_t* src_all, bf16_t* dst_al
   stamp();
 }
 
-template <int NT, int Q0>
-__device__ __forceinline__ void res3t_body(const Res3Args& a, bf16_t* ACT, bf16_t* MID, const int (&win)[3], const int mt) {
+template <int NT, int Q0, bool DUMP, class Args>
+__device__ __forceinline__ void res3t_body(const Args& a, bf16_t* ACT, bf16_t* MID, const int (&win)[3], const int mt) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int g = lane >> 4, n = lane & 15, co = mt * 16 + 4 * g;  // this lane's four output channels, in every conv
 #if R3_CLOCK
@@ -650,12 +686,13 @@ __device__ __forceinline__ void res3t_body(const Res3Args& a, bf16_t* ACT, bf16_
 #define R3T_BLOCK(I, TAPS, TN1, W1NEXT)                                                                                       \
   {                                                                                                                           \
     Res3A<TAPS> w2;                                                                                                           \
+    const Res3Dump<DUMP, Args> dump{a, win, I, co};                                                                           \
     res3t_conv<TAPS, TAPS, false, false, NT, Q0>(ACT, MID, w1_##I, X, [&](const int k) {                                       \
       w2.load_part(a.af2[I], a.bs2[I], (I) == 6 ? nullptr : a.s_next[I], (I) == 6 ? nullptr : a.b_next[I], mt, lane, k);      \
-    }, lane, co, wstamp);                                                                                                     \
+    }, lane, co, wstamp, dump);                                                                                               \
     __syncthreads();                                                                                                          \
     R3T_STAMP()                                                                                                               \
-    res3t_conv<TAPS, TN1, true, (I) == 6, NT, Q0>(MID, ACT, w2, X, [&](const int k) { W1NEXT }, lane, co, wstamp);             \
+    res3t_conv<TAPS, TN1, true, (I) == 6, NT, Q0>(MID, ACT, w2, X, [&](const int k) { W1NEXT }, lane, co, wstamp, dump);       \
     __syncthreads();                                                                                                          \
     R3T_STAMP()                                                                                                               \
   }
@@ -685,14 +722,16 @@ __device__ __forceinline__ void res3t_body(const Res3Args& a, bf16_t* ACT, bf16_
 #undef R3T_STAMP
 }
 
-__global__ __launch_bounds__(512) void eqt_res3t_kernel(const Res3Args a) {
+// DUMP (tests only, plan_flags[1] & 4): the same kernel writing every conv's epilogue values to Res3DumpArgs::dbg from registers
+template <bool DUMP = false>
+__global__ __launch_bounds__(512) void eqt_res3t_kernel(const std::conditional_t<DUMP, Res3DumpArgs, Res3Args> a) {
   __shared__ __attribute__((aligned(16))) bf16_t ACT[3 * 3 * R3_PS];  // [window of the workgroup][piece][chunk][column][8]
   __shared__ __attribute__((aligned(16))) bf16_t MID[3 * 3 * R3_PS];
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int last = a.n_windows - 1;  // (a batch that is no multiple of three: the last window up to three times, identical stores)
   const int win[3] = {min((int)blockIdx.x * 3, last), min((int)blockIdx.x * 3 + 1, last), min((int)blockIdx.x * 3 + 2, last)};
-  if (wave < 4) res3t_body<5, 0>(a, ACT, MID, win, wave);  // (6 + 3 measured the same)
-  else res3t_body<4, 5>(a, ACT, MID, win, wave - 4);
+  if (wave < 4) res3t_body<5, 0, DUMP>(a, ACT, MID, win, wave);  // (6 + 3 measured the same)
+  else res3t_body<4, 5, DUMP>(a, ACT, MID, win, wave - 4);
 }
 
 // (eqt_res3k_kernel -- eight waves per window, K split over wave pairs with a partial-sum exchange through LDS; round 2's default,
@@ -778,6 +817,12 @@ int plan_eqt_fuse_res(Net& net) {
       b1[i] = net.add_blob(res3_operand(*c1[i], c1[i]->g.taps));
       b2[i] = net.add_blob(res3_operand(*c2[i], c2[i]->g.taps));
     }
+  // plan_flags[1] & 4 (plan_eqt checked that the plan is the default one): the DUMP instance and the tensors it writes
+  const bool dumps = (net.cfg.plan_flags[1] & 4) != 0;
+  std::vector<int> dbg;
+  if (dumps)
+    for (int i = 0; i < 7; ++i)
+      for (const char* what : {".mid", ".conv2", ".out"}) dbg.push_back(net.add_tensor("res." + std::to_string(i) + what, 64, EQT_T));
   Step st;
   st.name = "fused.rescnn (7 residual blocks)";
   st.flops_per_window = 0;
@@ -818,12 +863,26 @@ int plan_eqt_fuse_res(Net& net) {
       a.clk = (n.debug_clock && n.debug_clock->d)  // the conv launches' region: unused under the fused plan
                   ? reinterpret_cast<unsigned long long*>(n.debug_clock->d) + (size_t)n.max_batch * 32
                   : nullptr;
-      if (n.cfg.plan_flags[7] & 512)  // bit 9: four waves per window, one window per workgroup
+      if (dumps) {
+        Res3DumpArgs d{};
+        static_cast<Res3Args&>(d) = a;
+        d.dbg_ls = n.tensors[dbg[0]].ls;
+        d.dbg_ws = (long)n.tensors[dbg[0]].win_stride();
+        for (int i = 0; i < 21; ++i) {
+          const Tensor& t = n.tensors[dbg[i]];
+          if (t.ls != d.dbg_ls || (long)t.win_stride() != d.dbg_ws) {
+            set_error("fused ResCNN dumps: tensor %s has a layout of its own", t.name.c_str());
+            return VP_ERR_INVALID;
+          }
+          d.dbg[i] = t.p;
+        }
+        hipLaunchKernelGGL(eqt_res3t_kernel<true>, dim3((B + 2) / 3), dim3(512), 0, s, d);
+      } else if (n.cfg.plan_flags[7] & 512)  // bit 9: four waves per window, one window per workgroup
         hipLaunchKernelGGL(eqt_res3_kernel<1>, dim3(B), dim3(256), 0, s, a);
       else if (n.cfg.plan_flags[7] & 8192)  // bit 13: four waves per window, two windows per workgroup (rounds 5-6: 45 us on 128 CUs)
         hipLaunchKernelGGL(eqt_res3_kernel<2>, dim3((B + 1) / 2), dim3(512), 0, s, a);
       else  // eight waves per THREE windows
-        hipLaunchKernelGGL(eqt_res3t_kernel, dim3((B + 2) / 3), dim3(512), 0, s, a);
+        hipLaunchKernelGGL(eqt_res3t_kernel<false>, dim3((B + 2) / 3), dim3(512), 0, s, a);
       return 0;
     };
   } else

@@ -38,6 +38,8 @@
 //
 // Plan flag plan_flags[7] & 64 keeps the fp32-MFMA kernel of eqt_tail.hip (bit-identical to the layer launches); this one
 // agrees with it to fp32 rounding (tests/test_gpu_eqt.py).
+#include <type_traits>
+
 #include "conv_b3.h"
 #include "eqt_kernels.h"
 #include "net.h"
@@ -116,6 +118,14 @@ struct Tail3Args {
   int t_lo, tiles_per_row;       // tile j of a row = outputs [t_lo + j TW, t_lo + (j + 1) TW): t_lo a multiple of 16, the tiles cover what the caller keeps
   unsigned long long* clk;  // debug (plan flag plan_flags[1] & 2): the stamps of eqt_tail.hip's TailArgs::clk, same slots
 };
+// The DUMP instance of the 1200-sample tiling (plan_flags[1] & 4, tests/test_gpu_layers_f64.py) also writes, from registers, the
+// outputs of stages 4, 5 and 6 and the heads' logits before the sigmoid to decoder.4 / .5 / .6 / logits (set-major rows d B + b):
+// the samples its tile owns, each exactly once.  A struct of its own: the default instances' arguments stay.
+struct Tail3DumpArgs : Tail3Args {
+  float* dbg[4];
+  int dbg_ls[4];
+  long dbg_ws[4];
+};
 
 struct Tile3 {
   int d, win, t0;
@@ -132,8 +142,9 @@ __device__ __forceinline__ void t3_finish(const f32x4 acc, const float (&bias)[4
   for (int r = 0; r < 4; ++r) v[r] = in ? fmaxf(acc[r] + bias[r], 0.f) : 0.f;
 }
 
-template <int TW_>
-__global__ __launch_bounds__(T3_NTH) void eqt_tail3_kernel(const Tail3Args a) {
+template <int TW_, bool DUMP = false>
+__global__ __launch_bounds__(T3_NTH) void eqt_tail3_kernel(const std::conditional_t<DUMP, Tail3DumpArgs, Tail3Args> a) {
+  static_assert(!DUMP || TW_ == 1200, "DUMP instances exist for the 1200-sample tiling only");
   using K = T3<TW_>;
   using Q5 = typename K::Q5;
   using Q6 = typename K::Q6;
@@ -158,6 +169,16 @@ __global__ __launch_bounds__(T3_NTH) void eqt_tail3_kernel(const Tail3Args a) {
   Tile3 id = tile3_id<TW>(tile, a);
   unsigned long long* clk = (a.clk && tid == 0 && (int)blockIdx.x < a.B) ? a.clk + (long)blockIdx.x * 32 : nullptr;
   int n_done = 0;
+  // DUMP: channels co .. co + 3 (dbg_ls apart) at sample s of debug tensor i, row id.win, when the tile owns s: [lo, lo + len)
+  auto dump = [&](const int i, const int co, const int s, const int lo, const int len, const float (&v)[4]) {
+    if constexpr (DUMP) {
+      if ((unsigned)(s - lo) < (unsigned)len) {
+        float* p = a.dbg[i] + (long)id.win * a.dbg_ws[i] + HALO + (long)co * a.dbg_ls[i] + s;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) p[(long)r * a.dbg_ls[i]] = v[r];
+      }
+    }
+  };
 #define T3_STAMP(k) \
   if (clk && n_done < 4) clk[n_done * 6 + (k)] = __builtin_readcyclecounter();
   if (clk) clk[30] = __builtin_amdgcn_s_memrealtime();
@@ -235,6 +256,7 @@ __global__ __launch_bounds__(T3_NTH) void eqt_tail3_kernel(const Tail3Args a) {
         float v[4];
         t3_finish(acc, bias4, (unsigned)(t - lo) < 1500u, v);
         b3c_store4<16, NC5>(IN5, t, g, v);
+        if constexpr (DUMP) dump(0, 4 * g, t0 / 4 - 6 + t, t0 / 4, TW / 4, v);
       };
       if (older) b3c_mac_tiles<32, NC4, 5, NB4O>(b3c_lane_ptr<32, NC4, 5>(IN4, colb, lane), a4, finish);
       else b3c_mac_tiles<32, NC4, 5, NB4Y>(b3c_lane_ptr<32, NC4, 5>(IN4, colb, lane), a4, finish);
@@ -252,6 +274,7 @@ __global__ __launch_bounds__(T3_NTH) void eqt_tail3_kernel(const Tail3Args a) {
         float v[4];
         t3_finish(acc, bias5, (unsigned)(t - lo) < 3000u, v);
         if (!K::GUARD5 || t < NC6) b3c_store4<16, NC6>(IN6, t, g, v);  // (tilings whose stage 5 computes columns beyond the stage-6 image: nobody's input)
+        if constexpr (DUMP) dump(1, 4 * g, t0 / 2 - 6 + t, t0 / 2, TW / 2, v);
       };
       if (K::ZERO6) {  // columns [2 C5, NC6) of the stage-6 input image: 16-byte units (column, 8 channels) of every chunk plane
         constexpr int ZC = NC6 - 2 * C5, UNITS = 3 * 2 * ZC;
@@ -277,6 +300,7 @@ __global__ __launch_bounds__(T3_NTH) void eqt_tail3_kernel(const Tail3Args a) {
         const int t = 2 * (colb + j * 16 + n) + ph;
         float v[4];
         t3_finish(acc, bias6, (unsigned)(t - lo) < (unsigned)T_OUT, v);
+        if constexpr (DUMP) dump(2, 4 * (g & 1), t0 - 6 + t, t0, TW, v);
         if (B3_EXP & 16) {
           asm volatile("" ::"v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]));
           return;
@@ -333,6 +357,11 @@ __global__ __launch_bounds__(T3_NTH) void eqt_tail3_kernel(const Tail3Args a) {
       const int blk = 16 * w + n;
       if (16 * blk + 4 * g < TW && t0 + 16 * blk + 4 * g < T_OUT) {  // (a tile's last block may be half used; the last tile of a row may reach past it)
         const int b = id.win - id.d * a.B;
+        if constexpr (DUMP) {
+          float* p = a.dbg[3] + (long)id.win * a.dbg_ws[3] + HALO + t0 + 16 * blk + 4 * g;
+#pragma unroll
+          for (int k = 0; k < 4; ++k) p[k] = acc[k];
+        }
         float4 r;
         // sigmoid as v_exp + v_rcp (3e-7 absolute; the library expf and the IEEE division are ~18 instructions per value on a
         // path that is bound by issued instructions)
@@ -405,8 +434,17 @@ int plan_eqt_fuse_tail_b3(Net& net) {
   }
   const int x3 = c4->src1;
   net.need(x3, HALO - 5 + T_OUT / 8 + T3<1256>::PARK_COLS);  // the last tile of a row may read past it: zero margin
-  net.tensor_sets[c4->dst] = 0;  // stages 4 and 5 are never materialised by this plan
-  net.tensor_sets[c5->dst] = 0;
+  // stages 4 and 5 are never materialised by this plan; plan_flags[1] & 4 keeps them, and adds stage 6's output and the heads'
+  // logits, for the DUMP instance
+  const bool dumps = (net.cfg.plan_flags[1] & 4) != 0;
+  int dbg[4] = {c4->dst, c5->dst, -1, -1};
+  if (dumps) {
+    dbg[2] = net.add_tensor("decoder.6", 8, T_OUT, 3);
+    dbg[3] = net.add_tensor("logits", 1, T_OUT, 3);
+  } else {
+    net.tensor_sets[c4->dst] = 0;
+    net.tensor_sets[c5->dst] = 0;
+  }
   HostBlob* p4 = net.add_blob(b3_operand(*c4, true));
   HostBlob* p5 = net.add_blob(b3_operand(*c5, true));
   HostBlob* p6 = net.add_blob(b3_operand(*c6, true));
@@ -464,7 +502,7 @@ int plan_eqt_fuse_tail_b3(Net& net) {
     a.B = B;
     // the outputs the caller keeps (annotate / classify: [blind_l, T - blind_r); model(x): the whole row), in the tiling that
     // needs fewer tiles; plan_flags[7] bit 10 computes the whole row whatever the blinding (A/B, tests)
-    const Tail3Tiling tl = tail3_tiling(n.cfg, n.out_lo, n.out_hi);
+    const Tail3Tiling tl = tail3_tiling(n.cfg, dumps ? 0 : n.out_lo, dumps ? 0 : n.out_hi);  // (dumps: the whole row, 1200-sample tiles)
     const bool wide = tl.wide;
     a.t_lo = tl.t_lo;
     a.tiles_per_row = tl.tiles_per_row;
@@ -473,7 +511,17 @@ int plan_eqt_fuse_tail_b3(Net& net) {
                 ? reinterpret_cast<unsigned long long*>(n.debug_clock->d) + (size_t)n.max_batch * 32 + 64 * 8
                 : nullptr;
     const int grid = a.n_tiles < 256 ? a.n_tiles : 256;
-    if (wide)
+    if (dumps) {
+      Tail3DumpArgs d{};
+      static_cast<Tail3Args&>(d) = a;
+      for (int i = 0; i < 4; ++i) {
+        const Tensor& t = n.tensors[dbg[i]];
+        d.dbg[i] = t.p;
+        d.dbg_ls[i] = t.ls;
+        d.dbg_ws[i] = (long)t.win_stride();
+      }
+      hipLaunchKernelGGL((eqt_tail3_kernel<1200, true>), dim3(grid), dim3(T3_NTH), T3<1200>::LDS_BYTES, s, d);
+    } else if (wide)
       hipLaunchKernelGGL(eqt_tail3_kernel<1256>, dim3(grid), dim3(T3_NTH), T3<1256>::LDS_BYTES, s, a);
     else
       hipLaunchKernelGGL(eqt_tail3_kernel<1200>, dim3(grid), dim3(T3_NTH), T3<1200>::LDS_BYTES, s, a);
@@ -481,6 +529,7 @@ int plan_eqt_fuse_tail_b3(Net& net) {
   };
   net.extra_kernels.push_back({reinterpret_cast<const void*>(&eqt_tail3_kernel<1200>), (size_t)T3<1200>::LDS_BYTES});
   net.extra_kernels.push_back({reinterpret_cast<const void*>(&eqt_tail3_kernel<1256>), (size_t)T3<1256>::LDS_BYTES});
+  if (dumps) net.extra_kernels.push_back({reinterpret_cast<const void*>(&eqt_tail3_kernel<1200, true>), (size_t)T3<1200>::LDS_BYTES});
   st.issued_for_range = [](const Net& n, int lo, int hi, double* w) {
     w[0] = 0.0, w[1] = tail3_tiling(n.cfg, lo, hi).issued_bf16, w[2] = 0.0;
   };
