@@ -61,8 +61,10 @@ typedef struct {
                                       EQTransformer: the DUMP instances of the five default conv kernels write every conv
                                       layer's output (encoder.0-5, res.{i}.mid / .conv2 / .out, decoder.0-6 and the heads'
                                       logits, the decoders' set-major) to the debug tensors; the decoder tail computes whole
-                                      rows in 1200-sample tiles (tests; rejected with [0], [3] or any [7] bit but bit10 set,
-                                      or [6] = 2);
+                                      rows in 1200-sample tiles; the DUMP instance of eqt_mid4 writes every stage of the
+                                      BiLSTM blocks, the transformers and the pick branches (bilstm.{i}.h / .c, transformer
+                                      .p / .att / .y1 / .ff1 / .ff2, pick_lstms.{k}.h / .c, pick_attentions.{k}.p) (tests;
+                                      rejected with [0], [2], [3] or any [7] bit but bit10 set, or [6] = 2);
                                  [2]: PhaseNet: (1 = hand-pipelined K loop in the MFMA layers: removed in round 6, rejected);
                                       EQTransformer: 1 = the three
                                       BiLSTM blocks, two transformer blocks and the pick branches as six launches instead

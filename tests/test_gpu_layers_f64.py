@@ -14,7 +14,8 @@ import torch
 from oracle import pipeline as OP
 from oracle.models import load_pretrained
 from tests.gpu_util import debug_tensors
-from tests.layer_f64 import C_ELEM, K_RMS, check_layer, eqt_layers, eqt_mid_chain, phasenet_layers, rel_rms, report
+from tests.layer_f64 import (C_ELEM, K_RMS, attention_form_plain, attention_weights, check_layer, eqt_layers, eqt_mid_chain,
+                              eqt_mid_stages, mid_bad, phasenet_layers, rel_rms, report)
 from tests.test_gpu_parity_wide import _as_array, _scaled_state
 from volpick_amd import EQTransformer, PhaseNet, _lib
 from volpick_amd.synthetic import synthetic_windows
@@ -176,9 +177,9 @@ def _eqt_dumps(model, B):
     return t
 
 
-def _eqt_check(oracle, xn, weights, rows=None, state=None, label=""):
-    """The shipped plan and the DUMP plan on xn; the DUMP plan runs a different batch of the same size first, so that a sample
-    its dumps skip holds a stale value.  rows: windows checked in float64 (None = all)."""
+def _eqt_run(xn, weights, state=None):
+    """(probabilities of the shipped plan, of the DUMP plan, the dumps, the halo check) on xn; the DUMP plan runs a different
+    batch of the same size first, so that a sample its dumps skip holds a stale value"""
     B = xn.shape[0]
     other = torch.flip(xn, dims=(0, 2)).contiguous()
     outs = []
@@ -198,8 +199,14 @@ def _eqt_check(oracle, xn, weights, rows=None, state=None, label=""):
                 halos = _halo_words(m)
         finally:
             m._release()
-    y = outs[0]
-    assert np.array_equal(y, outs[1], equal_nan=True), f"{label}: the DUMP plan's probabilities differ from the shipped plan's"
+    return outs[0], outs[1], t, halos
+
+
+def _eqt_check(oracle, xn, weights, rows=None, state=None, label=""):
+    """The shipped plan and the DUMP plan on xn (_eqt_run).  rows: windows checked in float64 (None = all)."""
+    B = xn.shape[0]
+    y, yd, t, halos = _eqt_run(xn, weights, state)
+    assert np.array_equal(y, yd, equal_nan=True), f"{label}: the DUMP plan's probabilities differ from the shipped plan's"
     assert halos[0] == 0, f"{label}: the DUMP plan wrote into the zero margin of {halos[1]}"
     assert torch.equal(t["res.6.out"], t["res.xa"]), f"{label}: the dumped block-6 output is not the ResCNN kernel's output"
     # the dumped logits are the probabilities' own (sigmoid as v_exp + v_rcp in the kernel: 3e-7)
@@ -253,3 +260,113 @@ def test_eqt_activations_far_from_unity(scale):
     state = {k: (v.numpy() if torch.is_tensor(v) else v) for k, v in _scaled_state("eqtransformer", sd, scale).items()}
     xn = OP.batch_pre(oracle, torch.from_numpy(synthetic_windows(3, 6000, seed=4500)))
     _eqt_check(big, xn, "volpick", state=state, label=f"eqt activations x {scale:g}")
+
+
+# ---- eqt_mid4 stage by stage (its DUMP instance), every window ------------------------------------------------------------
+def _mid_check(oracle, xn, weights, state=None, label=""):
+    """Every stage of every window of eqt_mid4 against float64 on the kernel's own input to it (tests/layer_f64.eqt_mid_stages).
+    Returns the dumps."""
+    B = xn.shape[0]
+    y, yd, t, halos = _eqt_run(xn, weights, state)
+    assert np.array_equal(y, yd, equal_nan=True), f"{label}: the DUMP plan's probabilities differ from the shipped plan's"
+    assert halos[0] == 0, f"{label}: the DUMP plan wrote into the zero margin of {halos[1]}"
+    # links: the stage inputs the float64 check starts from are what the kernel read (res.xa: the ResCNN kernel's output; the
+    # block and transformer outputs: what eqt_mid4 wrote where the next stage reads it), and what the decoders read is the
+    # dumped stage outputs -- decoder.in set 0 is transformer_d's LN2 output, sets 1 and 2 the pick branches' a.x
+    assert torch.equal(t["res.6.out"], t["res.xa"]), label
+    assert torch.equal(t["transformer_d"], t["decoder0.in"]), f"{label}: decoder.in set 0 is not transformer_d's dumped output"
+    for k in range(2):
+        assert t[f"pick_attentions.{k}.p"].shape == (B, 47, 47) and t[f"decoder{k + 1}.in"].shape == (B, 16, 47), label
+    rows = eqt_mid_stages(oracle, t)
+    print(f"\n[{label}] B={B}, every window\n" + report(rows))
+    bad = mid_bad(rows)
+    assert not bad, f"{label}: eqt_mid4 stages beyond the float64 bars (rms ratio <= {K_RMS}, elementwise <= {C_ELEM}): {bad}"
+    return t
+
+
+def _edited(weights, edits):
+    """(oracle, state for the model) with the weights named in edits multiplied: {oracle parameter name: factor}"""
+    oracle = copy.deepcopy(load_pretrained("eqtransformer", weights))
+    params = dict(oracle.named_parameters())
+    sd = EQTransformer.from_pretrained(weights).state_dict()
+    with torch.no_grad():
+        for n, f in edits.items():
+            params[n].mul_(f)
+            sd[n] = sd[n] * np.float32(f)
+    return oracle, {k: (v.numpy() if torch.is_tensor(v) else v) for k, v in sd.items()}
+
+
+@pytest.mark.parametrize("weights", ["volpick", "volpick_95train"])
+@pytest.mark.parametrize("B", [1, 4, 5])
+def test_eqt_mid_stages_match_float64(weights, B):
+    """B = 5 leaves the last four-window workgroup with one window (its team computes it, the clamped ones repeat it)"""
+    oracle = load_pretrained("eqtransformer", weights)
+    xn = OP.batch_pre(oracle, torch.from_numpy(synthetic_windows(B, 6000, seed=990 + B)))
+    _mid_check(oracle, xn, weights, label=f"eqt_mid4 {weights}")
+
+
+@pytest.mark.slow
+@pytest.mark.parametrize("weights", ["volpick", "volpick_95train"])
+def test_eqt_mid_stages_match_float64_257(weights):
+    oracle = load_pretrained("eqtransformer", weights)
+    xn = OP.batch_pre(oracle, torch.from_numpy(synthetic_windows(257, 6000, seed=997)))
+    _mid_check(oracle, xn, weights, label=f"eqt_mid4 {weights}")
+
+
+PLAIN = ("transformer_d.attention.Wx", "transformer_d.attention.Wt", "pick_attentions.1.Wx", "pick_attentions.1.Wt")
+
+
+def test_eqt_mid_stages_plain_tanh_form():
+    """test_gpu_eqt.test_attention_beyond_the_exp_product_guard's weights (projections x 40 in transformer_d and the S branch):
+    every window past the |q|, |k| <= 30 guard, the plain tanh(q + k) form, which the probabilities alone checked before"""
+    oracle, state = _edited("volpick", {n: 40.0 for n in PLAIN})
+    xn = OP.batch_pre(oracle, torch.from_numpy(synthetic_windows(4, 6000, seed=991)))
+    t = _mid_check(oracle, xn, "volpick", state, label="eqt_mid4 plain tanh")
+    assert attention_form_plain(oracle.transformer_d.attention, t["transformer_d0"]).all()
+    assert attention_form_plain(oracle.pick_attentions[1], t["pick_lstms.1.h"]).all()
+    assert not attention_form_plain(oracle.transformer_d0.attention, t["bilstm.2"]).any()
+
+
+def test_eqt_mid_stages_mixed_forms_in_one_workgroup():
+    """transformer_d0's projections scaled until some windows of a four-window workgroup take the plain form and others the exp
+    product (tests/test_gpu_round4.py's construction); which form each window took follows from float64 q and k"""
+    B = 16
+    x = synthetic_windows(B, 6000, seed=4242)
+    x[1::4] *= 0.02  # quiet windows between loud ones: a spread of activation sizes at the attention input
+    oracle = load_pretrained("eqtransformer", "volpick")
+    xn = OP.batch_pre(oracle, torch.from_numpy(x))
+    with torch.no_grad():
+        xin = oracle.bi_lstm_stack(oracle.res_cnn_stack(oracle.encoder(xn)))
+    att = oracle.transformer_d0.attention
+    top = lambda w: torch.matmul(xin.permute(0, 2, 1), w.detach()).abs().amax(dim=(1, 2))
+    scale = float(30.0 / torch.median(torch.maximum(top(att.Wt), top(att.Wx))))
+    big, state = _edited("volpick", {"transformer_d0.attention.Wt": scale, "transformer_d0.attention.Wx": scale})
+    t = _mid_check(big, xn, "volpick", state, label=f"eqt_mid4 mixed forms (x {scale:.2f})")
+    plain = attention_form_plain(big.transformer_d0.attention, t["bilstm.2"]).reshape(-1, 4)
+    assert (plain.any(dim=1) & ~plain.all(dim=1)).sum() >= 1, plain
+
+
+@pytest.mark.parametrize("factor", [16.0, 1.0 / 16])
+def test_eqt_mid_stages_saturated_and_near_zero_gates(factor):
+    """the LSTM input weights of BiLSTM block 0 and of both pick LSTMs x 16 (gates saturated) and / 16 (near their midpoints)"""
+    names = ["bi_lstm_stack.members.0.lstm.weight_ih_l0", "bi_lstm_stack.members.0.lstm.weight_ih_l0_reverse",
+             "pick_lstms.0.weight_ih_l0", "pick_lstms.1.weight_ih_l0"]
+    oracle, state = _edited("volpick", {n: factor for n in names})
+    xn = OP.batch_pre(oracle, torch.from_numpy(synthetic_windows(4, 6000, seed=992)))
+    _mid_check(oracle, xn, "volpick", state, label=f"eqt_mid4 LSTM input weights x {factor:g}")
+
+
+def test_eqt_mid_stages_eps_dominated_pick_rows():
+    """the P branch's Wa x 200: its band scores sit far below their rows' maxima, eps dominates the denominators (some weights
+    underflow fp32: tests/layer_f64.P_FLOOR), edge rows t = 0 and 46 included"""
+    oracle, state = _edited("volpick", {"pick_attentions.0.Wa": 200.0})
+    xn = OP.batch_pre(oracle, torch.from_numpy(synthetic_windows(4, 6000, seed=993)))
+    t = _mid_check(oracle, xn, "volpick", state, label="eqt_mid4 eps-dominated pick rows")
+    att = oracle.pick_attentions[0]
+    with torch.no_grad():
+        _, e, _, _ = attention_weights(att, t["pick_lstms.0.h"], torch.float64)
+        ex = torch.exp(e - e.max(dim=-1, keepdim=True).values)
+    band = [(0, slice(0, 2)), (46, slice(45, 47))]
+    sums = {i: ex[:, i, sl].sum(dim=-1) for i, sl in band}
+    assert all(bool((s < att.eps).any()) for s in sums.values()), sums
+    assert float((ex[:, 1:46].diagonal(offset=1, dim1=1, dim2=2) < att.eps).double().mean()) > 0.5

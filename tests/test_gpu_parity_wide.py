@@ -270,7 +270,7 @@ def test_removed_plan_selectors_are_rejected(name, flags):
 
 
 # EQTransformer's layer dumps (plan_flags[1] & 4) exist for the default conv kernels only: every selector that swaps one out is refused
-EQT_DUMP_REFUSED = [(1, 4), (0, 4, 0, 1), (0, 4, 0, 0, 0, 0, 2)] + \
+EQT_DUMP_REFUSED = [(1, 4), (0, 4, 0, 1), (0, 4, 0, 0, 0, 0, 2), (0, 4, 1), (0, 4, 2), (0, 4, 3)] + \
                    [(0, 4, 0, 0, 0, 0, 0, 1 << b) for b in (0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 11, 13)]
 
 

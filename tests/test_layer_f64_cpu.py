@@ -7,13 +7,15 @@ What is measured first is the bare conv (no BatchNorm, no ReLU, unfolded weights
 neighbour of what the GPU test compares (post-BatchNorm / ReLU outputs of layers whose kernels fold BatchNorm into the weights):
 the margin shows the metric's sensitivity to the fault, not the GPU test's exact numbers.  EQTransformer's layers are then
 measured through the very descriptors the GPU test uses (tests/layer_f64.eqt_layers).  This runs no kernel: it covers the bars."""
+import copy
+
 import pytest
 import torch
 
 from oracle import pipeline as OP
 from oracle.models import load_pretrained
-from tests.layer_f64 import (C_ELEM, EPS24, K_RMS, attention_rows, bf16_drop_lo, elem_scale, eqt_acts, eqt_layers, layer_forward,
-                              rel_rms)
+from tests.layer_f64 import (C_ELEM, EPS24, K_RMS, MID_FAULTS, attention_rows, bf16_drop_lo, elem_scale, eqt_acts, eqt_layers,
+                              eqt_mid_acts, eqt_mid_chain, eqt_mid_stages, layer_forward, mid_bad, rel_rms)
 from volpick_amd.synthetic import synthetic_windows
 
 MARGIN = 1.75  # the weakest case, EQTransformer pick_convs.0 with its weights' lo piece dropped, sits at 1.8 x K_RMS
@@ -85,6 +87,53 @@ def test_dropped_lo_piece_fails_the_eqt_layer_bars():
                     weak.append((name, what, round(rr, 2), round(ee, 2)))
     print("\n" + "\n".join(lines))
     assert not weak, f"a dropped lo piece passes the EQTransformer layer bars (rms ratio, elementwise ratio): {weak}"
+
+
+def _res_xa(net, B, seed):
+    """the fp32 oracle's ResCNN output (eqt_mid4's input res.xa) for B synthetic windows"""
+    seen = {}
+    hook = net.bi_lstm_stack.register_forward_pre_hook(lambda mod, inp: seen.__setitem__("xa", inp[0].detach()))
+    with torch.no_grad():
+        net(OP.batch_pre(net, torch.from_numpy(synthetic_windows(B, net.in_samples, seed=seed))))
+    hook.remove()
+    return seen["xa"]
+
+
+# LayerNorm's variance in one pass (E[z^2] - mean^2) is not caught, because at these inputs it is no fault: its error is
+# (1 + mean^2 / var) ulps of the variance, and the transformers' LN inputs have |mean| below their deviation (LOG.md section 22)
+MID_UNCAUGHT = ("ln_one_pass",)
+MID_LOCAL = "step_rcp"  # one step of one direction, 2^-18 relative: inside today's chain bar K_MID, beyond the stage bars
+
+
+def test_mid_faults_fail_the_stage_bars():
+    """eqt_mid4's stages (tests/layer_f64.eqt_mid_stages) on the fp32 oracle's own values pass their bars; each planted fault of
+    MID_FAULTS fails them by MARGIN, and the localized MID_LOCAL passes the chain check of test_gpu_layers_f64 (K_MID) while it
+    fails the stage bars -- what the stage-by-stage check adds."""
+    from tests.test_gpu_layers_f64 import K_MID
+
+    net = load_pretrained("eqtransformer", "volpick")
+    xa = _res_xa(net, 3, seed=3)
+    rows = eqt_mid_stages(net, eqt_mid_acts(net, xa))
+    assert not mid_bad(rows), mid_bad(rows)
+    o64 = copy.deepcopy(net).double()
+    ref, y32 = eqt_mid_chain(o64, xa.double()), eqt_mid_chain(net, xa)
+    chain = lambda t: max(rel_rms(t[f"decoder{d}.in"], ref[d]) / rel_rms(y32[d], ref[d]) for d in range(3))
+    lines, weak = [], []
+    for fault in MID_FAULTS:
+        t = eqt_mid_acts(net, xa, fault)
+        rows = eqt_mid_stages(net, t)
+        worst = max(rows, key=lambda r: max(r["rms_ratio"] / K_RMS, r["elem_ratio"] / C_ELEM) if r["finite"] else float("inf"))
+        m = max(worst["rms_ratio"] / K_RMS, worst["elem_ratio"] / C_ELEM) if worst["finite"] else float("inf")
+        ch = chain(t)
+        lines.append(f"{fault:12s} worst stage {worst['name']:22s} {m:9.2f} x its bar   chain {ch:9.2f} x torch fp32")
+        if fault in MID_UNCAUGHT:
+            continue
+        if not m > MARGIN:
+            weak.append((fault, worst["name"], round(m, 2)))
+        if fault == MID_LOCAL:
+            assert ch <= K_MID, f"{fault}: the chain bar sees it already ({ch:.2f}): it shows nothing the stage bars add"
+    print("\n" + "\n".join(lines))
+    assert not weak, f"planted faults within {MARGIN} x the stage bars: {weak}"
 
 
 def test_row_blocked_attention_is_the_oracle_module_bit_for_bit():

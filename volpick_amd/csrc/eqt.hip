@@ -143,11 +143,12 @@ AttnWeights resolve(const AttnWeights& w) { return AttnWeights{dptr(w.Wt), dptr(
 }  // namespace
 
 int plan_eqt(Net& net, const ParamView& pv) {
-  // plan_flags[1] & 4: the DUMP instances of the five fused conv kernels (plan_eqt_fuse_*), which exist for their default forms only
-  if ((net.cfg.plan_flags[1] & 4) && (net.cfg.plan_flags[0] != 0 || net.cfg.plan_flags[3] != 0 || net.cfg.plan_flags[6] == 2 ||
-                                      (net.cfg.plan_flags[7] & ~1024) != 0)) {
-    set_error("EQTransformer plan_flags[1] & 4 dumps the default conv kernels only (plan_flags[0], [3], [7] other than bit 10 unset, "
-              "[6] != 2)");
+  // plan_flags[1] & 4: the DUMP instances of the five fused conv kernels (plan_eqt_fuse_*) and of eqt_mid4_kernel, which exist for
+  // their default forms only
+  if ((net.cfg.plan_flags[1] & 4) && (net.cfg.plan_flags[0] != 0 || net.cfg.plan_flags[2] != 0 || net.cfg.plan_flags[3] != 0 ||
+                                      net.cfg.plan_flags[6] == 2 || (net.cfg.plan_flags[7] & ~1024) != 0)) {
+    set_error("EQTransformer plan_flags[1] & 4 dumps the default conv kernels only, and the default middle kernel (plan_flags[0], "
+              "[2], [3], [7] other than bit 10 unset, [6] != 2)");
     return VP_ERR_UNSUPPORTED;
   }
   const float eps = net.cfg.bn_eps;
@@ -382,6 +383,25 @@ int plan_eqt(Net& net, const ParamView& pv) {
       // eight 47-step recurrences (64 gate rows x 16 units) and the four 47 x 47 x 32 score loops (two packed FMAs per pair)
       fused.set_issued((24.0 * 16 + 24 + 2 * (24.0 * 4 + 24) + 2 * (48.0 + 36 + 96 + 96) + 96 + 2 * (48.0 + 36)) * 2048.0, 0.0,
                        8 * 47 * 2.0 * 64 * 16 + 4 * 47.0 * 47 * 32 * 4);
+      // plan_flags[1] & 4 (plan_eqt refused the other middle forms): the DUMP instance of eqt_mid4_kernel and the tensors it
+      // writes, in the order of MD_* (eqt_kernels.h)
+      std::vector<int> mdbg;
+      if (net.cfg.plan_flags[1] & 4) {
+        for (const char* what : {".h", ".c"})
+          for (int i = 0; i < 3; ++i) mdbg.push_back(net.add_tensor("bilstm." + std::to_string(i) + what, 32, EQT_T));
+        static const std::pair<const char*, int> tr_dumps[5] = {{".p", EQT_T}, {".att", 16}, {".y1", 16}, {".ff1", 128}, {".ff2", 16}};
+        for (const char* tr : tr_names)
+          for (const auto& td : tr_dumps) mdbg.push_back(net.add_tensor(std::string(tr) + td.first, td.second, EQT_T));
+        for (int k = 0; k < 2; ++k) {
+          mdbg.push_back(net.add_tensor("pick_lstms." + std::to_string(k) + ".h", 16, EQT_T));
+          mdbg.push_back(net.add_tensor("pick_lstms." + std::to_string(k) + ".c", 16, EQT_T));
+          mdbg.push_back(net.add_tensor("pick_attentions." + std::to_string(k) + ".p", EQT_T, EQT_T));
+        }
+        if ((int)mdbg.size() != MD_N) {
+          set_error("eqt_mid4 dumps: %zu tensors for %d slots", mdbg.size(), (int)MD_N);
+          return VP_ERR_INVALID;
+        }
+      }
       fused.run = [=](Net& n, int B, hipStream_t s_) -> int {
         MidArgs m{};
         for (int i = 0; i < 3; ++i) m.lstm[i] = mk_lstm[i](n);
@@ -390,6 +410,17 @@ int plan_eqt(Net& net, const ParamView& pv) {
         m.clk = n.debug_clock ? reinterpret_cast<unsigned long long*>(n.debug_clock->d) : nullptr;  // slots [B][8] (tools/mid_clock.py)
         m.B = B;
         if (n.cfg.plan_flags[2] == 2 || n.cfg.plan_flags[2] == 3) return launch_eqt_mid(m, B, s_, n.cfg.plan_flags[2] == 2);
+        if (!mdbg.empty()) {
+          MidDumpArgs d{};
+          static_cast<MidArgs&>(d) = m;
+          for (int i = 0; i < MD_N; ++i) {
+            const Tensor& t = n.tensors[mdbg[i]];
+            d.dbg[i] = t.p;
+            d.dbg_ls[i] = t.ls;
+            d.dbg_ws[i] = (long)t.win_stride();
+          }
+          return launch_eqt_mid4_dump(d, B, s_);
+        }
         return launch_eqt_mid4(m, B, s_);
       };
       net.steps.erase(net.steps.begin() + mid_first, net.steps.end());

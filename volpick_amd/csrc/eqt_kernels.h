@@ -89,6 +89,31 @@ int launch_eqt_mid(const MidArgs& a, int B, hipStream_t s, bool one_window_per_w
 // default since round 6: teams of four waves, FOUR windows per 1024-thread workgroup (64 CUs for a batch of 256), eqt_mid4.hip;
 // bit-identical to the forms above
 int launch_eqt_mid4(const MidArgs& a, int B, hipStream_t s);
+// The DUMP instance of eqt_mid4_kernel (plan_flags[1] & 4, tests/test_gpu_layers_f64.py) also writes the fp32 values every stage
+// computed into haloed [C][47] debug tensors, index MD_* below (the order of the tensors plan_eqt adds for it).  A struct of its
+// own: the kernel requests sizeof(its argument struct) of kernel arguments up front, so a longer MidArgs would change the
+// default instances.
+enum : int {
+  MD_BI_H = 0,   // bilstm.{i}.h [32][47], i = 0..2: the recurrence outputs, forward units 0-15, backward 16-31
+  MD_BI_C = 3,   // bilstm.{i}.c [32][47]: the cell states
+  MD_TR = 6,     // transformer i (0: transformer_d0, 1: transformer_d): MD_TR + 5 i + MD_TR_*
+  MD_PICK = 16,  // pick branch k: MD_PICK + 3 k + MD_PK_*
+  MD_N = 22
+};
+enum : int {  // .p [47][47] attention weights, .att [16][47] a.x before the residual, .y1 [16][47] LN1's output,
+  MD_TR_P,    // .ff1 [128][47] ReLU(Linear1), .ff2 [16][47] Linear2 (both K halves) before the residual
+  MD_TR_ATT,
+  MD_TR_Y1,
+  MD_TR_FF1,
+  MD_TR_FF2
+};
+enum : int { MD_PK_H, MD_PK_C, MD_PK_P };  // pick_lstms.{k}.h, .c [16][47], pick_attentions.{k}.p [47][47]
+struct MidDumpArgs : MidArgs {
+  float* dbg[MD_N];
+  int dbg_ls[MD_N];
+  long dbg_ws[MD_N];
+};
+int launch_eqt_mid4_dump(const MidDumpArgs& a, int B, hipStream_t s);
 
 int launch_bilstm(const BiLstmArgs& a, int cin, int B, hipStream_t s);
 int launch_transformer(const TransformerArgs& a, int B, hipStream_t s);

@@ -37,6 +37,18 @@ static_assert((M4_POOL * 4) % 16 == 0 && M4_WPB * (M4_POOL + 16 * 48) * 4 <= 160
 
 __device__ __forceinline__ int m4_wave() { return __builtin_amdgcn_readfirstlane(MID_TID >> 6); }
 
+// DUMP instance (MidDumpArgs): row c of debug tensor i for window b (sample 0 at index 0)
+__device__ __forceinline__ float* md_row(const MidDumpArgs& d, const int i, const int b, const int c) {
+  return d.dbg[i] + (long)b * d.dbg_ws[i] + HALO + (long)c * d.dbg_ls[i];
+}
+// DUMP instance: rows [0, C) x columns [0, T) of an LDS image of row stride S, by the window's team
+__device__ void md_copy(const MidDumpArgs& d, const int i, const int b, const float* src, const int C, const int S) {
+  for (int idx = MID_TID; idx < C * T; idx += M4_NTH) {
+    const int c = idx / T, t = idx - c * T;
+    md_row(d, i, b, c)[t] = src[c * S + t];
+  }
+}
+
 template <int CIN>
 struct Bi4Frags {
   ProjFrag<CIN> f[2];    // wave = gate block; [direction]
@@ -54,9 +66,10 @@ __device__ __forceinline__ void bi4_load(Bi4Frags<CIN>& g, const BiLstmArgs& a) 
   load4(g.bcv, a.bc + 4 * (lane >> 4));
 }
 
-template <int CIN, class Prefetch>
+// DUMP: block BLK's recurrence outputs and cell states (d: the MidDumpArgs of the DUMP instance, unused otherwise)
+template <int CIN, bool DUMP, int BLK, class Args, class Prefetch>
 __device__ void mid4_bilstm(const BiLstmArgs& a, Bi4Frags<CIN>& g, const int b, float* P, float* cur, const bool from_memory,
-                            Prefetch&& prefetch, unsigned long long* sub) {
+                            Prefetch&& prefetch, unsigned long long* sub, const Args& d) {
   const int tid = MID_TID, lane = tid & 63, wave = m4_wave();
   float* gx = P;                // [2][T * GXS]
   float* hc = P + 2 * T * GXS;  // [32][48] recurrence outputs ...
@@ -97,10 +110,15 @@ __device__ void mid4_bilstm(const BiLstmArgs& a, Bi4Frags<CIN>& g, const int b, 
     const float sc = lstm_gate_scale(lane & 3);
 #pragma unroll
     for (int j = 0; j < EQT_H / 2; ++j) g.whh[j] *= sc;
-    lstm_recur<GXS, true>(gx + wave * T * GXS, g.whh, wave == 1, hc + wave * 16 * 48, 48);
+    if constexpr (DUMP)
+      lstm_recur<GXS, true, true>(gx + wave * T * GXS, g.whh, wave == 1, hc + wave * 16 * 48, 48,
+                                  md_row(d, MD_BI_C + BLK, b, 16 * wave), d.dbg_ls[MD_BI_C + BLK]);
+    else
+      lstm_recur<GXS, true>(gx + wave * T * GXS, g.whh, wave == 1, hc + wave * 16 * 48, 48);
   }
   __syncthreads();
   M4_SUB(10)
+  if constexpr (DUMP) md_copy(d, MD_BI_H + BLK, b, hc, 32, 48);  // hc is only read from here on
   if (wave >= 1) {  // Conv1d(32,16,1) + BatchNorm, folded
     float* dst = a.dst + (long)b * a.ws_dst;
     const int n0 = 16 * (wave - 1), t = n0 + (lane & 15);
@@ -202,9 +220,11 @@ __device__ __forceinline__ void tr4_load_late(Tr4Frags& g, const TransformerArgs
   load4(g.b2v, a.bb2 + 4 * (lane >> 4));  // the second K half ignores it at use
 }
 
-template <class Prefetch>
+// DUMP: transformer TR's attention weights, a.x, LN1's output and both feed-forward layers (d as in mid4_bilstm)
+template <bool DUMP, int TR, class Args, class Prefetch>
 __device__ void mid4_transformer(const TransformerArgs& a, Tr4Frags& g, const int b, float* P, float* cur, Prefetch&& prefetch,
-                                 unsigned long long* sub) {
+                                 unsigned long long* sub, const Args& d) {
+  constexpr int D0 = MD_TR + 5 * TR;
   const int tid = MID_TID, lane = tid & 63, wave = m4_wave();
   float(*q)[KP] = reinterpret_cast<float(*)[KP]>(P);
   float(*k)[KP] = q + T;
@@ -226,11 +246,22 @@ __device__ void mid4_transformer(const TransformerArgs& a, Tr4Frags& g, const in
         float z[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) z[r] = cur[(c0 + r) * 48 + col] + acc[r];
+        if constexpr (DUMP) {
+          if (col < T) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) md_row(d, D0 + MD_TR_ATT, b, c0 + r)[col] = acc[r];
+          }
+        }
         layer_norm_mfma<0>(z, g.ln_par, a.ln_eps);
 #pragma unroll
         for (int r = 0; r < 4; ++r) y1T[(c0 + r) * 48 + col] = z[r];  // all 48 columns: column 47 is padding
       },
       sub ? sub + 20 : nullptr);
+  if constexpr (DUMP) {  // the hidden layer below is written over e: out first, then a barrier
+    md_copy(d, D0 + MD_TR_P, b, e, T, AES);
+    md_copy(d, D0 + MD_TR_Y1, b, y1T, 16, 48);
+    __syncthreads();
+  }
   const float ln_par = g.ln_par;
   M4_SUB(13)
 #pragma unroll
@@ -246,6 +277,7 @@ __device__ void mid4_transformer(const TransformerArgs& a, Tr4Frags& g, const in
   }
   __syncthreads();
   M4_SUB(14)
+  if constexpr (DUMP) md_copy(d, D0 + MD_TR_FF1, b, h1T, 128, 48);  // h1T is only read from here on
   // Linear(128,16) in two K halves, as the eight-wave team sums them: bias + first half (waves 0, 1), plus the second half
   // (waves 2, 3, handed over through LDS)
   const int half = wave >> 1, nt0 = (wave & 1) ? 2 : 0, ntn = (wave & 1) ? 1 : 2;
@@ -271,6 +303,12 @@ __device__ void mid4_transformer(const TransformerArgs& a, Tr4Frags& g, const in
         float z[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) z[r] = y1T[(c0 + r) * 48 + col] + (acc2[j][r] + rT[(c0 + r) * 48 + col]);
+        if constexpr (DUMP) {
+          if (col < T) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) md_row(d, D0 + MD_TR_FF2, b, c0 + r)[col] = acc2[j][r] + rT[(c0 + r) * 48 + col];
+          }
+        }
         layer_norm_mfma<32>(z, ln_par, a.ln_eps);
         if (col < T) {
           float* dst = a.dst + (long)b * a.ws_dst + HALO + col;
@@ -303,7 +341,10 @@ __device__ __forceinline__ void pick4_load(Pick4Frags& g, const PickBranchArgs& 
                // score loop this runs under has no registers to spare
 }
 
-__device__ void mid4_pick(const PickBranchArgs& a, Pick4Frags& g, const int b, float* P, const float* cur, unsigned long long* sub) {
+// DUMP: both branches' LSTM outputs, cell states and attention weights (d as in mid4_bilstm)
+template <bool DUMP, class Args>
+__device__ void mid4_pick(const PickBranchArgs& a, Pick4Frags& g, const int b, float* P, const float* cur, unsigned long long* sub,
+                          const Args& d) {
   const int tid = MID_TID, wave = m4_wave();
   float* gx = P;                 // [2][T * GXS] input projections of the P and the S branch ...
   float(*q)[KP] = reinterpret_cast<float(*)[KP]>(P);  // ... and, once the recurrences have read them, q / k / e
@@ -334,10 +375,18 @@ __device__ void mid4_pick(const PickBranchArgs& a, Pick4Frags& g, const int b, f
     const float sc = lstm_gate_scale(tid & 3);
 #pragma unroll
     for (int j = 0; j < EQT_H / 2; ++j) g.whh[j] *= sc;
-    lstm_recur<GXS, true>(gx + wave * T * GXS, g.whh, false, hl + wave * 16 * 48, 48);
+    if constexpr (DUMP)
+      lstm_recur<GXS, true, true>(gx + wave * T * GXS, g.whh, false, hl + wave * 16 * 48, 48,
+                                  md_row(d, MD_PICK + 3 * wave + MD_PK_C, b, 0), d.dbg_ls[MD_PICK + 3 * wave + MD_PK_C]);
+    else
+      lstm_recur<GXS, true>(gx + wave * T * GXS, g.whh, false, hl + wave * 16 * 48, 48);
   }
   __syncthreads();  // gx is dead from here
   M4_SUB(19)
+  if constexpr (DUMP) {  // hl is only read from here on
+    md_copy(d, MD_PICK + MD_PK_H, b, hl, 16, 48);
+    md_copy(d, MD_PICK + 3 + MD_PK_H, b, hl + 16 * 48, 16, 48);
+  }
 #pragma unroll
   for (int br = 0; br < 2; ++br) {
     mid4_attention(g.af[br], g.wa_lane[br], hl + br * 16 * 48, q, k, e, a.attn_eps, a.width, NoPrefetch(),
@@ -349,6 +398,8 @@ __device__ void mid4_pick(const PickBranchArgs& a, Pick4Frags& g, const int b, f
                      }
                    },
                    sub && br ? sub + 26 : nullptr);
+    // e stays until the next branch's score loop, two barriers on
+    if constexpr (DUMP) md_copy(d, MD_PICK + 3 * br + MD_PK_P, b, e, T, AES);
     float* up = a.up + (long)((1 + br) * a.B + b) * a.ws_up + HALO;
     for (int idx = tid; idx < EQT_H * 48; idx += M4_NTH) {
       const int c = idx / 48, t = idx - c * 48;
@@ -360,7 +411,12 @@ __device__ void mid4_pick(const PickBranchArgs& a, Pick4Frags& g, const int b, f
 
 // The four teams execute the same barriers in the same order (same code, same trip counts); the last workgroup of a batch that
 // is not a multiple of four computes its last window more than once (identical stores).
-__global__ __launch_bounds__(M4_WPB* M4_NTH) void eqt_mid4_kernel(const MidArgs a) {
+// DUMP (tests only, plan_flags[1] & 4): the same kernel writing every stage's fp32 values to MidDumpArgs::dbg as well, from the
+// LDS images the next stage reads (copies behind the barriers that close them; the attention weights of a transformer before
+// its hidden layer is written over them, behind one more barrier), from registers (a.x, the second linear layer) and from
+// the recurrences (cell states)
+template <bool DUMP = false>
+__global__ __launch_bounds__(M4_WPB* M4_NTH) void eqt_mid4_kernel(const std::conditional_t<DUMP, MidDumpArgs, MidArgs> a) {
   __shared__ __attribute__((aligned(16))) float P_all[M4_WPB * M4_POOL];
   __shared__ float cur_all[M4_WPB * 16 * 48];
   const int team = __builtin_amdgcn_readfirstlane(MID_TEAM);
@@ -375,7 +431,7 @@ __global__ __launch_bounds__(M4_WPB* M4_NTH) void eqt_mid4_kernel(const MidArgs 
     const uptr_t ka = (uptr_t)__builtin_amdgcn_kernarg_segment_ptr();
     unsigned acc = 0;
 #pragma unroll
-    for (unsigned i = 0; i < (sizeof(MidArgs) + 63) / 64; ++i) acc |= ka[16 * i];
+    for (unsigned i = 0; i < (sizeof(a) + 63) / 64; ++i) acc |= ka[16 * i];
     asm volatile("" ::"s"(acc));
   }
 #define M4_STAMP()                                                                          \
@@ -387,17 +443,17 @@ __global__ __launch_bounds__(M4_WPB* M4_NTH) void eqt_mid4_kernel(const MidArgs 
   Bi4Frags<EQT_H> g1, g2;
   Tr4Frags t0, t1;
   Pick4Frags pf;
-  mid4_bilstm<64>(a.lstm[0], g0, b, P, cur, true, [&] { bi4_load<EQT_H>(g1, a.lstm[1]); }, sub);
+  mid4_bilstm<64, DUMP, 0>(a.lstm[0], g0, b, P, cur, true, [&] { bi4_load<EQT_H>(g1, a.lstm[1]); }, sub, a);
   M4_STAMP()
-  mid4_bilstm<EQT_H>(a.lstm[1], g1, b, P, cur, false, [&] { bi4_load<EQT_H>(g2, a.lstm[2]); }, nullptr);
+  mid4_bilstm<EQT_H, DUMP, 1>(a.lstm[1], g1, b, P, cur, false, [&] { bi4_load<EQT_H>(g2, a.lstm[2]); }, nullptr, a);
   M4_STAMP()
-  mid4_bilstm<EQT_H>(a.lstm[2], g2, b, P, cur, false, [&] { tr4_load_early(t0, a.tr[0]); }, nullptr);
+  mid4_bilstm<EQT_H, DUMP, 2>(a.lstm[2], g2, b, P, cur, false, [&] { tr4_load_early(t0, a.tr[0]); }, nullptr, a);
   M4_STAMP()
-  mid4_transformer(a.tr[0], t0, b, P, cur, [&] { tr4_load_early(t1, a.tr[1]); }, nullptr);
+  mid4_transformer<DUMP, 0>(a.tr[0], t0, b, P, cur, [&] { tr4_load_early(t1, a.tr[1]); }, nullptr, a);
   M4_STAMP()
-  mid4_transformer(a.tr[1], t1, b, P, cur, [&] { pick4_load(pf, a.pick); }, sub);
+  mid4_transformer<DUMP, 1>(a.tr[1], t1, b, P, cur, [&] { pick4_load(pf, a.pick); }, sub, a);
   M4_STAMP()
-  mid4_pick(a.pick, pf, b, P, cur, sub);
+  mid4_pick<DUMP>(a.pick, pf, b, P, cur, sub, a);
   M4_STAMP()
 #undef M4_STAMP
 }
@@ -405,7 +461,12 @@ __global__ __launch_bounds__(M4_WPB* M4_NTH) void eqt_mid4_kernel(const MidArgs 
 }  // namespace
 
 int launch_eqt_mid4(const MidArgs& a, int B, hipStream_t s) {
-  hipLaunchKernelGGL(eqt_mid4_kernel, dim3((B + M4_WPB - 1) / M4_WPB), dim3(M4_WPB * M4_NTH), 0, s, a);
+  hipLaunchKernelGGL(eqt_mid4_kernel<false>, dim3((B + M4_WPB - 1) / M4_WPB), dim3(M4_WPB * M4_NTH), 0, s, a);
+  return 0;
+}
+
+int launch_eqt_mid4_dump(const MidDumpArgs& a, int B, hipStream_t s) {
+  hipLaunchKernelGGL(eqt_mid4_kernel<true>, dim3((B + M4_WPB - 1) / M4_WPB), dim3(M4_WPB * M4_NTH), 0, s, a);
   return 0;
 }
 

@@ -95,8 +95,11 @@ __device__ __forceinline__ float lstm_gate_scale(const int gate) { return gate =
 // GS: row stride of gx (64, or 65 where the projection writes it with lane = time step).
 // SCALED: gx and whh already carry lstm_gate_scale (eqt_mid_kernel); the gate combination then runs as four fused DPP
 // instructions (v_mul_f32_dpp / v_fmac_f32_dpp read the quad's i and f gates in place).
-template <int GS = 64, bool SCALED = false>
-__device__ void lstm_recur(const float* gx, const f32x2 (&whh)[EQT_H / 2], const bool reverse, float* hout, const int hs) {
+// DUMP_C (the DUMP instance of eqt_mid4_kernel only): the cell state c_t of each unit goes to cout[unit * cs + t] as well,
+// from the quad's lane 0, the lane that stores h.
+template <int GS = 64, bool SCALED = false, bool DUMP_C = false>
+__device__ void lstm_recur(const float* gx, const f32x2 (&whh)[EQT_H / 2], const bool reverse, float* hout, const int hs,
+                           float* cout = nullptr, const int cs = 0) {
   const int lane = MID_TID & 63;
   const bool is_g = (lane & 3) == 2;
   float h = 0.f, c = 0.f;
@@ -142,6 +145,9 @@ __device__ void lstm_recur(const float* gx, const f32x2 (&whh)[EQT_H / 2], const
       h = og * tanh_fast(c);
     }
     if ((lane & 3) == 0) hout[(lane >> 2) * hs + t] = h;
+    if constexpr (DUMP_C) {
+      if ((lane & 3) == 0) cout[(lane >> 2) * cs + t] = c;
+    }
   }
 }
 
