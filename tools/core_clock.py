@@ -54,7 +54,7 @@ if n_steps == 1:  # whole-network kernel: slot 1 - slot 0 is the level-0 down ph
     if (sub[:, 1:4] > 0).all():
         print("load x in detail (wave 0's stamps): window read + partial reductions %d  barrier + 3-lane finish + barrier %d  "
               "normalise + store x image %d  closing barrier %d" % tuple(np.median(np.diff(sub, axis=1), axis=0)))
-    if (clk[:, 25] == 0).all():  # U3T form: stamps 23 (start), 24 (operands there, ring zeroed), 28 (last tile stored)
+    if (clk[:, 25] == 0).all():  # default form (level 0 time-tiled): stamps 23 (start), 24 (operands there, ring zeroed), 28 (last tile stored)
         print("level-0 up phase (tiled, bf16 matrix cores) median cycles: prepare %d  thirteen phases of 256 samples %d"
               % (np.median(clk[:, 24].astype(np.int64) - clk[:, 23].astype(np.int64)), np.median(clk[:, 28].astype(np.int64) - clk[:, 24].astype(np.int64))))
     else:

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-phase cycles of the tiled level-0 down path of pn_window_kernel.  Needs a library built with -DD0T_PROBE
-(cd volpick_amd/csrc && touch phasenet_fused.hip && make HIPCC="/opt/rocm/bin/hipcc -DD0T_PROBE"): slots 2 .. 14 then hold the phase ends."""
+(cd volpick_amd/csrc && touch phasenet_window.hip && make HIPCC="/opt/rocm/bin/hipcc -DD0T_PROBE"): slots 2 .. 14 then hold the phase ends."""
 import ctypes as C, os, sys
 from pathlib import Path
 import numpy as np

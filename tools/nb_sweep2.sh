@@ -2,7 +2,7 @@
 # three 16/32-channel "same" layers): fewer n-tiles per item = more waves streaming weights concurrently.
 set -e
 cd $GRAFT_REPO_ROOT
-F=volpick_amd/csrc/phasenet_fused.hip
+F=volpick_amd/csrc/phasenet_arena.h  # the core layers' LdsLayer shapes
 run() { # name u0same u1same d3same d2same
   sed -e "s/using C_u0same = LdsLayer<64, 64, 64, 1, 7, 1, -3, 0, [0-9]*, 1>;/using C_u0same = LdsLayer<64, 64, 64, 1, 7, 1, -3, 0, $2, 1>;/" \
       -e "s/using C_u1same = LdsLayer<32, 32, 32, 1, 7, 1, -3, 0, [0-9]*, 1>;/using C_u1same = LdsLayer<32, 32, 32, 1, 7, 1, -3, 0, $3, 1>;/" \

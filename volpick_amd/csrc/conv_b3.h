@@ -79,19 +79,6 @@ struct B3Store {
   }
 };
 
-// Output side: an fp32 image [channel][S], sample t at column B + t (the layers behind the bf16 chain)
-template <int S, int B>
-struct F32QuadStore {
-  float* img;
-  int L;
-  __device__ __forceinline__ void quad(const int co, const int t, const float (&v)[4]) const {
-    if ((unsigned)t < (unsigned)L) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) img[(co + r) * S + B + t] = v[r];
-    }
-  }
-};
-
 // lds_epilogue hook (conv_lds.h) for an fp32-MFMA layer whose OUTPUT feeds the bf16 chain (P = 1)
 template <int C>
 struct B3BlockStore : B3Store<C> {
@@ -267,12 +254,6 @@ __device__ __forceinline__ void conv_b3_part_impl(const B3Image<32> im, const ui
   }
 }
 
-template <class L, int KSTEP, int NB>
-__device__ __forceinline__ void conv_b3_part(const B3Image<32> im, const uint4* __restrict__ af3, const int mt, const int colb,
-                                             const int lane, f32x4 (&acc)[NB]) {
-  uint4 q[4][3];
-  conv_b3_part_impl<L, KSTEP, NB, false>(im, af3, mt, colb, lane, acc, q);
-}
 template <class L, int KSTEP>
 __device__ __forceinline__ void conv_b3_part_request(const uint4* __restrict__ af3, const int mt, const int lane, uint4 (&q)[4][3]) {
   constexpr int KS = (L::CIN1 + L::CIN2) / 32, STEPS = L::TAPS * KS, PF = 3;
@@ -287,48 +268,6 @@ __device__ __forceinline__ void conv_b3_part_requested(const B3Image<32> im, con
                                                        const int lane, f32x4 (&acc)[NB], uint4 (&q)[4][3]) {
   conv_b3_part_impl<L, KSTEP, NB, true>(im, af3, mt, colb, lane, acc, q);
 }
-
-// 4 x 4 transpose between a lane's four registers and the four 16-lane rows of the wavefront: afterwards v[k] of row g holds what
-// v[g] of row k held (v_permlane32_swap: upper half of the first operand <-> lower half of the second; v_permlane16_swap: odd
-// rows of the first <-> even rows of the second).
-__device__ __forceinline__ void b3_transpose_rows(float (&v)[4]) {
-  const auto p02 = __builtin_amdgcn_permlane32_swap(__float_as_uint(v[0]), __float_as_uint(v[2]), false, false);
-  const auto p13 = __builtin_amdgcn_permlane32_swap(__float_as_uint(v[1]), __float_as_uint(v[3]), false, false);
-  const auto q01 = __builtin_amdgcn_permlane16_swap(p02[0], p13[0], false, false);
-  const auto q23 = __builtin_amdgcn_permlane16_swap(p02[1], p13[1], false, false);
-  v[0] = __uint_as_float(q01[0]);
-  v[1] = __uint_as_float(q01[1]);
-  v[2] = __uint_as_float(q23[0]);
-  v[3] = __uint_as_float(q23[1]);
-}
-
-// lds_epilogue hook (conv_lds.h) of a FOUR-PHASE fp32-MFMA layer (transposed conv, rows (channel, phase)) whose output feeds
-// the bf16 chain: a lane's four values are four consecutive samples of ONE channel (channel 4 mt + row g of the lane); the
-// transpose above turns them into the m-tile's four channels at ONE sample (phase g), which leave as one 8-byte store per piece.
-// Only samples [0, L) are written: zero the other columns first (B3Store::zero_rest with the written range).
-template <int C>
-struct B3PhaseStore {
-  static constexpr bool custom_block_epilogue = true;
-  bf16_t* img;
-  int ps, c0, L;
-  template <class LY>
-  __device__ __forceinline__ void block_epilogue(const f32x4 (&acc)[LY::NB], const float (&biasv)[4], const int mt, const int colb,
-                                                 const int g, const int n) const {
-    static_assert(LY::P == 4, "four phases per channel");
-#pragma unroll
-    for (int j = 0; j < LY::NB; ++j) {
-      float v[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        v[r] = acc[j][r] + biasv[r];  // biasv: the lane's channel, the same for its four phases
-        if (LY::RELU) v[r] = fmaxf(v[r], 0.f);
-      }
-      b3_transpose_rows(v);  // v[k] = channel 4 mt + k at phase g
-      const int t = 4 * (colb + j * 16 + n) + g + LY::OUT_OFF;
-      if ((unsigned)t < (unsigned)L) b3_store4(img, ps, C + 8, t + c0, 4 * mt, v);
-    }
-  }
-};
 
 // an fp32 image [32 channels][S], sample t at column B + t, -> the three-piece image (samples [t_lo, t_hi): whatever the fp32
 // image holds there, its zero margins included)
@@ -557,30 +496,6 @@ __device__ __forceinline__ void b3c_mac_tiles_acc(const bf16_t* p, const uint4 (
   }
 }
 
-// B3PhaseStore for a chunk-plane image (C = 16: two chunks of eight channels)
-template <int C, int NC>
-struct B3PhaseStoreC {
-  static constexpr bool custom_block_epilogue = true;
-  bf16_t* img;
-  int c0, L;
-  template <class LY>
-  __device__ __forceinline__ void block_epilogue(const f32x4 (&acc)[LY::NB], const float (&biasv)[4], const int mt, const int colb,
-                                                 const int g, const int n) const {
-    static_assert(LY::P == 4, "four phases per channel");
-#pragma unroll
-    for (int j = 0; j < LY::NB; ++j) {
-      float v[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        v[r] = acc[j][r] + biasv[r];
-        if (LY::RELU) v[r] = fmaxf(v[r], 0.f);
-      }
-      b3_transpose_rows(v);  // v[k] = channel 4 mt + k at phase g
-      const int t = 4 * (colb + j * 16 + n) + g + LY::OUT_OFF;
-      if ((unsigned)t < (unsigned)L) b3c_store4<C, NC>(img, t + c0, mt, v);
-    }
-  }
-};
 // lds_epilogue hooks (conv_lds.h) of fp32-MFMA layers whose output feeds a bf16 layer with 8 or 16 input channels: chunk-plane
 // image, sample t at column t + c0; every computed column inside the image is written (zeros outside [0, L)).
 // P = 1: a lane's four rows are four consecutive channels.

@@ -53,6 +53,8 @@ constexpr int kDenseOut = -2;
 // The A operand of a conv layer regrouped for 16-byte loads (conv_lds_q4): [mt][step][64] -> [mt][step / 4][64][4],
 // step = channel block * taps + tap; needs (channel blocks * taps) % 4 == 0.
 std::vector<float> regroup_afrag4(const ConvLayer& L);
+// w as three bfloat16 pieces, each the round-to-nearest-even of what the ones before it left: hi + (mid + lo) == w in fp32
+void bf16_split3(float w, uint16_t* hi, uint16_t* mid, uint16_t* lo);
 // three-piece bf16 operands of every weight set of a layer (conv_b3.h) / the fp32 operand with phase-major rows (net.hip)
 std::vector<float> b3_operand(const ConvLayer& L, bool mperm);
 std::vector<float> regroup_afrag4_phase_major(const ConvLayer& L);
@@ -128,7 +130,7 @@ struct Net {
 };
 
 int plan_phasenet(Net& net, const ParamView& pv);
-int plan_phasenet_fused(Net& net, const ParamView& pv, int debug_flags);  // swaps the 18 layer steps for 3 fused launches; bit0: dump LDS intermediates, bit1: clock stamps, bit2: the one-launch kernel's DUMP instance
+int plan_phasenet_fused(Net& net, const ParamView& pv, int debug_flags);  // swaps the 18 layer steps for one launch (pn_window_kernel) or, for the reference plans, three; bit0: dump LDS intermediates, bit1: clock stamps, bit2: the one-launch kernel's DUMP instance
 int plan_eqt(Net& net, const ParamView& pv);
 int plan_eqt_fuse_res(Net& net);  // swaps the 14 ResCNN conv steps for one fused launch
 int plan_eqt_fuse_tail_b3(Net& net);  // the same on the bf16 matrix cores, exact three-piece operands (eqt_tail_b3.hip)

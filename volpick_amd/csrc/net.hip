@@ -65,15 +65,7 @@ std::vector<float> regroup_afrag4(const ConvLayer& L) {
 // fp32 MFMA-order fragments [set][mt][cb][tap][64] (pack_afrag) -> three-piece bf16 operands
 // [set][mt'][tap * KS + step][piece][64][8] (conv_b3.h): an fp32 weight is exactly hi + mid + lo in bfloat16.
 // mperm: GEMM rows regrouped (channel, phase) -> (phase, channel).  Two bf16 per float slot of the blob.
-std::vector<float> b3_operand(const ConvLayer& L, bool mperm) {
-  const int cinp = L.g.cinp(), taps = L.g.taps, M = L.g.M(), P = L.g.P, cout = L.g.cout, CB = cinp / 4, MT = M / 16;
-  // K of one instruction = 32: cinp >= 32: 32 channels of one tap, steps (tap, channel step); cinp = 16 / 8: all channels of
-  // 2 / 4 consecutive taps (taps beyond the filter carry zero weights), a lane's eight values = eight channels of one tap
-  // cinp = 4 (PhaseNet's inc, three input channels padded to four): all channels of EIGHT consecutive taps per step, a lane's
-  // eight values = four channels of two taps (lane group g: taps 2 g, 2 g + 1) in the order its two 8-byte reads deliver them:
-  // (tap a: ch 0, 1), (tap b: ch 0, 1), (tap a: ch 2, 3), (tap b: ch 2, 3)
-  const int KS = cinp >= 32 ? cinp / 32 : 1, TPK = cinp >= 32 ? 1 : 32 / cinp, LPT = cinp >= 32 ? 4 : (cinp >= 8 ? cinp / 8 : 1);  // lanes groups per tap
-  const int steps = cinp >= 32 ? taps * KS : (taps + TPK - 1) / TPK;
+void bf16_split3(float w, uint16_t* hi, uint16_t* mid, uint16_t* lo) {
   auto rne = [](float x) -> uint16_t {
     uint32_t u;
     memcpy(&u, &x, 4);
@@ -86,6 +78,21 @@ std::vector<float> b3_operand(const ConvLayer& L, bool mperm) {
     memcpy(&f, &u, 4);
     return f;
   };
+  *hi = rne(w);
+  const float r1 = w - widen(*hi);
+  *mid = rne(r1);
+  *lo = rne(r1 - widen(*mid));
+}
+
+std::vector<float> b3_operand(const ConvLayer& L, bool mperm) {
+  const int cinp = L.g.cinp(), taps = L.g.taps, M = L.g.M(), P = L.g.P, cout = L.g.cout, CB = cinp / 4, MT = M / 16;
+  // K of one instruction = 32: cinp >= 32: 32 channels of one tap, steps (tap, channel step); cinp = 16 / 8: all channels of
+  // 2 / 4 consecutive taps (taps beyond the filter carry zero weights), a lane's eight values = eight channels of one tap
+  // cinp = 4 (PhaseNet's inc, three input channels padded to four): all channels of EIGHT consecutive taps per step, a lane's
+  // eight values = four channels of two taps (lane group g: taps 2 g, 2 g + 1) in the order its two 8-byte reads deliver them:
+  // (tap a: ch 0, 1), (tap b: ch 0, 1), (tap a: ch 2, 3), (tap b: ch 2, 3)
+  const int KS = cinp >= 32 ? cinp / 32 : 1, TPK = cinp >= 32 ? 1 : 32 / cinp, LPT = cinp >= 32 ? 4 : (cinp >= 8 ? cinp / 8 : 1);  // lanes groups per tap
+  const int steps = cinp >= 32 ? taps * KS : (taps + TPK - 1) / TPK;
   const size_t set_in = (size_t)M * cinp * taps, set_out = (size_t)MT * steps * 3 * 64 * 8;
   std::vector<uint16_t> o(set_out * L.n_sets);
   for (int set = 0; set < L.n_sets; ++set) {
@@ -100,14 +107,8 @@ std::vector<float> b3_operand(const ConvLayer& L, bool mperm) {
             const int tap = cinp >= 32 ? st / KS : cinp == 4 ? st * TPK + 2 * g + ((i >> 1) & 1) : st * TPK + g / LPT;
             const int ci = cinp >= 32 ? (st % KS) * 32 + 8 * g + i : cinp == 4 ? (i & 1) + 2 * (i >> 2) : 8 * (g % LPT) + i;
             const float w = tap < taps ? af[(((size_t)(m / 16) * CB + ci / 4) * taps + tap) * 64 + (ci % 4) * 16 + (m % 16)] : 0.f;
-            const uint16_t h = rne(w);
-            const float r1 = w - widen(h);
-            const uint16_t md = rne(r1);
-            const uint16_t lo = rne(r1 - widen(md));
             const size_t base = ((((size_t)mt * steps + st) * 3) * 64 + l) * 8 + i;
-            os[base] = h;
-            os[base + 64 * 8] = md;
-            os[base + 2 * 64 * 8] = lo;
+            bf16_split3(w, &os[base], &os[base + 64 * 8], &os[base + 2 * 64 * 8]);
           }
   }
   std::vector<float> f(o.size() / 2);
