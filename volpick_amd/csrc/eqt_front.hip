@@ -206,7 +206,7 @@ __device__ __forceinline__ void front_window_stats(const PreArgs& p, const float
             m[h][c] = fmaxf(m[h][c], fabsf(d));
             if (d != d) m[h][c] = d;  // propagate NaN like torch.max
           } else {
-            m[h][c] += d * d;
+            m[h][c] = fmaf(d, d, m[h][c]);  // as gather_normalize_kernel: not left to the compiler's contraction
           }
         }
       }

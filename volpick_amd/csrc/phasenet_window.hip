@@ -348,7 +348,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_num_vgpr(60))) void pn_
           const int t = tid + k * NTH;
           if (t < T0) {
             const float d = v[c][k] - mean[c];
-            m[c] += d * d;
+            m[c] = fmaf(d, d, m[c]);  // as gather_normalize_kernel: not left to the compiler's contraction
           }
         }
       __syncthreads();

@@ -101,7 +101,7 @@ __global__ __launch_bounds__(1024) void gather_normalize_kernel(const PreArgs a)
         const int t = tid + k * NTH;
         if (t < T) {
           const float d = v[c][k] - mean[c];
-          m[c] += d * d;
+          m[c] = fmaf(d, d, m[c]);  // written out: the twins (pn_window_kernel, eqt_front_kernel) must round the same way
         }
       }
     __syncthreads();
