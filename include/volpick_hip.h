@@ -366,6 +366,38 @@ int vp_mseed_decode_bench(int device_id, const uint8_t* buf_dev, size_t nbytes, 
 int vp_mseed_release_scratch(int device_id, size_t* bytes_freed);
 
 /* ---------------------------------------------------------------------------------------------
+ * Sampling-rate conversion by an integer factor, on the device: what SeisBench's annotate() does to a trace whose rate
+ * is an integer multiple of the model's -- trace.filter("lowpass", freq = new Nyquist, zerophase = True), then
+ * trace.decimate(factor, no_filter = True) -- and volpick_amd/resample.py restates on the host with scipy:
+ *
+ *     f = sosfilt(sos, x);  g = sosfilt(sos, f[::-1])[::-1];  y = g[::factor]
+ *
+ * both passes from zero state, edge transients at both ends included.  in_dev: n samples in device memory, int32,
+ * float32 or float64 (in_kind).  sos: HOST array of n_sections rows b0 b1 b2 a0 a1 a2 (scipy's layout, a0 == 1) in
+ * double; 1 <= n_sections <= 4.  out_dev: out_len = ceil(n / factor) float32 samples in device memory.  State and the
+ * intermediate f are float64 (f lives in a per-device scratch of 8 bytes per input sample); the only rounding to
+ * float32 is the final store.  A NaN or Inf anywhere in the input makes every output sample NaN, as the whole-trace
+ * recursion does (scipy keeps Inf only for an Inf within a few samples of the trace's end; here that is NaN too).
+ *
+ * The trace is filtered in pieces that start a warm-up ahead of themselves from zero state; the warm-up W is taken from
+ * the largest pole radius r of `sos` so that r^W <= 2^-40.  VP_ERR_INVALID: factor < 2, n < 1, n_sections out of range,
+ * out_len != ceil(n / factor), a0 != 1, an unstable or non-finite section.  VP_ERR_UNSUPPORTED: W exceeds the 1024
+ * samples the kernel's tile has room for (4-corner Butterworth at 1 / factor of Nyquist: factor <= 40 fits).
+ * Runs on the device's null stream and returns after the work is done, as vp_mseed_decode does; a caller whose input
+ * was produced on a non-blocking stream synchronises that stream first.  Calls on one device are serialised.
+ *
+ * The scratch is kept per device, grow-only, between calls; vp_decimate_release_scratch frees it (bytes_freed may be
+ * NULL) -- vp_mseed_release_scratch does not touch it.  vp_decimate_lowpass_bench: mean time in ms (HIP events on a
+ * stream of its own, three untimed repetitions first) of `iters` repetitions of both passes (ms_total) and of the
+ * forward pass alone (ms_forward, may be NULL): bench only. */
+enum { VP_SAMPLES_FLOAT64 = 2 };
+int vp_decimate_lowpass(int device_id, const void* in_dev, int in_kind, int64_t n, const double* sos, int n_sections,
+                        int factor, float* out_dev, int64_t out_len);
+int vp_decimate_release_scratch(int device_id, size_t* bytes_freed);
+int vp_decimate_lowpass_bench(int device_id, const void* in_dev, int in_kind, int64_t n, const double* sos, int n_sections,
+                              int factor, float* out_dev, int64_t out_len, int iters, float* ms_total, float* ms_forward);
+
+/* ---------------------------------------------------------------------------------------------
  * PhaseNet training step (BASELINE config 5): what one
  * PhaseNetLit.training_step + Adam optimizer.step of the reference computes
  * (the reference's volpick/model/models.py:34-51 vector_cross_entropy, :160-164 training_step,

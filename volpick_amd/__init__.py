@@ -9,7 +9,7 @@ Drop-in for the ``seisbench.models`` picker API volpick users call:
 """
 from .models import EQTransformer, PhaseNet, WaveformModel  # noqa: F401
 from .picks import ClassifyOutput, Detection, DetectionList, Pick, PickList  # noqa: F401
-from .stream import Stream, Trace, UTCDateTime, pinned_array  # noqa: F401
+from .stream import Stream, Trace, UTCDateTime, pinned_array, to_device  # noqa: F401
 from ._lib import VolpickHipError  # noqa: F401
 from .io import read  # noqa: F401
 

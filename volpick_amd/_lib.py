@@ -90,7 +90,7 @@ class VpMseedRecord(C.Structure):
     ]
 
 
-VP_SAMPLES_INT32, VP_SAMPLES_FLOAT32 = 0, 1
+VP_SAMPLES_INT32, VP_SAMPLES_FLOAT32, VP_SAMPLES_FLOAT64 = 0, 1, 2
 
 
 class VolpickHipError(RuntimeError):
@@ -203,6 +203,15 @@ SIGNATURES = {
         C.c_int,
         [C.c_int, C.c_void_p, C.c_size_t, C.POINTER(VpMseedRecord), _I64P, C.c_int64, C.c_int, C.c_void_p, C.c_int64,
          C.c_int, _FP],
+    ),
+    "vp_decimate_lowpass": (
+        C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int64, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_void_p, C.c_int64],
+    ),
+    "vp_decimate_release_scratch": (C.c_int, [C.c_int, C.POINTER(C.c_size_t)]),
+    "vp_decimate_lowpass_bench": (
+        C.c_int,
+        [C.c_int, C.c_void_p, C.c_int, C.c_int64, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int,
+         _FP, _FP],
     ),
     "vp_train_create": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(_H)]),
     "vp_train_create_dtype": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(_H)]),

@@ -1,0 +1,332 @@
+// Integer-factor decimation behind a zero-phase low-pass, on the device: what volpick_amd/resample.py computes on the
+// host with scipy for traces whose rate is an integer multiple of the model's (SeisBench's annotate():
+// trace.filter("lowpass", zerophase=True) + trace.decimate(no_filter=True)):
+//
+//     f = sosfilt(sos, x);  g = sosfilt(sos, f[::-1])[::-1];  y = g[::k]
+//
+// Two launches of one kernel template.  The forward pass reads x (int32 / float32 / float64) and writes f as float64
+// into a scratch array; the backward pass reads f in reversed order and writes float32 at the kept samples only.
+// Coefficients, state and f are float64: the reference filters in float64, and counts with a large offset lose
+// several bits in an fp32 recursion (tests/test_decimate_f64_cpu.py).
+//
+// Parallel over the trace by warm-up ("Decimation"): a pass is cut into pieces of DC samples, one per
+// thread; a thread starts `warm` samples ahead of its piece from zero state, `warm` chosen on the host from the
+// largest pole radius r of the sections so that r^warm <= 2^-40.  A thread whose piece lies less than `warm` samples
+// behind the start of the pass starts AT the start, from the true zero state: that reproduces the edge transients.
+//
+// Memory access: a workgroup of DT threads stages the DT * DC samples of its pieces and the DHALO samples ahead of
+// them through LDS as float64 with coalesced loads; each thread then recurses over LDS.  Piece p of the image
+// starts at double (DC + 1) p: lane l of a wave reads byte address 8 (DC + 1) l + const, dword (2 DC + 2) l = 2 l
+// (mod 64) for DC = 32, so the 32 lanes of a ds_read_b64 group cover the 64 banks once -- no conflicts, where the
+// unpadded image (stride 256 B) would put every lane on the same two banks.  Results go back into the image (a
+// thread's own piece, after a barrier: its neighbours' warm-up has read the inputs there) and out with coalesced
+// stores.
+#include <cmath>
+#include <mutex>
+
+#include "vp_common.h"
+
+namespace vp {
+namespace {
+
+constexpr int DT = 256;             // threads per workgroup
+constexpr int DC = 32;              // samples per thread
+constexpr int DTILE = DT * DC;      // samples per workgroup
+constexpr int DHALO = 1024;         // room for the warm-up ahead of a tile (a multiple of DC)
+constexpr int DMAXS = 4;            // second-order sections the kernel is instantiated for
+constexpr int DLDS = (DHALO + DTILE) / DC * (DC + 1);  // doubles
+constexpr size_t DLDS_BYTES = (size_t)DLDS * sizeof(double);
+
+struct SosArg {
+  double c[DMAXS][5];  // b0 b1 b2 a1 a2 (a0 == 1)
+};
+
+__device__ __forceinline__ int phys(const int q) { return q + (q >> 5); }
+static_assert(DC == 32 && DHALO % DC == 0, "phys() is written for pieces of 32");
+
+// One pass.  Position m counts samples in the order the pass visits them: element m of the pass is in[m] (forward) or
+// in[n - 1 - m] (REV).  Forward: f_out[m] for every m.  REV: y_out[j] = (float) result at element j * factor of the
+// ORIGINAL order, for every j < ceil(n / factor); if *flag is set, NaN instead.
+template <typename InT, int NS, bool REV>
+__global__ __launch_bounds__(DT) void decimate_pass_kernel(const InT* __restrict__ in, const long long n, const SosArg sos,
+                                                           const int warm, double* __restrict__ f_out,
+                                                           float* __restrict__ y_out, const int factor,
+                                                           int* __restrict__ flag) {
+  extern __shared__ double dec_tile[];
+  const int t = threadIdx.x;
+  const long long m0 = (long long)blockIdx.x * DTILE;  // first element of the tile; m0 < n by the grid size
+  // kept outputs of this tile (REV): original indices [g_lo, g_hi] hold elements [m0, m0 + DTILE) of the pass
+  long long j_lo = 0, j_hi = -1;
+  if (REV) {
+    const long long g_hi = n - 1 - m0;
+    const long long g_lo = n - m0 - DTILE > 0 ? n - m0 - DTILE : 0;
+    j_lo = (g_lo + factor - 1) / factor;
+    j_hi = g_hi / factor;
+    if (*flag) {  // a non-finite input sample: the whole-trace filter answers NaN everywhere (uniform branch)
+      for (long long j = j_lo + t; j <= j_hi; j += DT) y_out[j] = __builtin_nanf("");
+      return;
+    }
+  }
+  // ---- stage elements [m0 - back, m0 + DTILE) as float64: image index q <-> element m0 - DHALO + q
+  const int back = m0 < warm ? (int)m0 : warm;
+  bool bad = false;
+  for (int q = DHALO - back + t; q < DHALO + DTILE; q += DT) {
+    const long long m = m0 - DHALO + q;
+    double v = 0.0;
+    if (m < n) v = static_cast<double>(in[REV ? n - 1 - m : m]);
+    if (!REV) bad |= !(fabs(v) <= 1.7976931348623157e308);
+    dec_tile[phys(q)] = v;
+  }
+  if (!REV && bad) *flag = 1;  // plain vector store; every writer writes the same word
+  __syncthreads();
+  // ---- this thread's piece: warm-up from zero state, then DC results kept in registers
+  const int q0 = DHALO + t * DC;
+  const long long ms = m0 + (long long)t * DC;
+  const int w = ms < warm ? (int)ms : warm;
+  double s1[NS], s2[NS];
+#pragma unroll
+  for (int s = 0; s < NS; ++s) s1[s] = s2[s] = 0.0;
+  auto step = [&](double v) {
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {  // direct form II transposed, the recurrence of scipy's sosfilt
+      const double y = sos.c[s][0] * v + s1[s];
+      s1[s] = sos.c[s][1] * v - sos.c[s][3] * y + s2[s];
+      s2[s] = sos.c[s][2] * v - sos.c[s][4] * y;
+      v = y;
+    }
+    return v;
+  };
+  double r[DC];
+  if (ms < n) {
+#pragma unroll 8
+    for (int q = q0 - w; q < q0; ++q) (void)step(dec_tile[phys(q)]);
+    const int p0 = phys(q0);  // q0 is a multiple of DC: the piece is contiguous in the image
+#pragma unroll
+    for (int i = 0; i < DC; ++i) r[i] = step(dec_tile[p0 + i]);
+  }
+  __syncthreads();  // every warm-up has read its inputs
+  if (ms < n) {
+    const int p0 = phys(q0);
+#pragma unroll
+    for (int i = 0; i < DC; ++i) dec_tile[p0 + i] = r[i];
+  }
+  __syncthreads();
+  if (!REV) {
+    for (int q = DHALO + t; q < DHALO + DTILE; q += DT) {
+      const long long m = m0 - DHALO + q;
+      if (m < n) f_out[m] = dec_tile[phys(q)];
+    }
+  } else {
+    for (long long j = j_lo + t; j <= j_hi; j += DT) {
+      const long long m = n - 1 - j * factor;  // in [m0, m0 + DTILE) and < n by the choice of j_lo, j_hi
+      y_out[j] = static_cast<float>(dec_tile[phys(DHALO + (int)(m - m0))]);
+    }
+  }
+}
+
+template <typename InT, bool REV>
+const void* pass_kernel(int ns) {
+  switch (ns) {
+    case 1: return (const void*)decimate_pass_kernel<InT, 1, REV>;
+    case 2: return (const void*)decimate_pass_kernel<InT, 2, REV>;
+    case 3: return (const void*)decimate_pass_kernel<InT, 3, REV>;
+    default: return (const void*)decimate_pass_kernel<InT, 4, REV>;
+  }
+}
+
+const void* forward_kernel(int in_kind, int ns) {
+  if (in_kind == VP_SAMPLES_INT32) return pass_kernel<int, false>(ns);
+  if (in_kind == VP_SAMPLES_FLOAT32) return pass_kernel<float, false>(ns);
+  return pass_kernel<double, false>(ns);
+}
+
+// Per device, grow-only, reused from call to call: f (8 bytes per input sample) and the flag word.
+struct DecimateScratch {
+  std::mutex mu;
+  void* p = nullptr;
+  size_t cap = 0;
+  int grow(size_t bytes, void** out) {
+    if (bytes > cap) {
+      if (p) (void)hipFree(p);
+      p = nullptr;
+      cap = 0;
+      const size_t want = bytes + bytes / 8 + 4096;
+      if (hipMalloc(&p, want) != hipSuccess) {
+        (void)hipGetLastError();
+        p = nullptr;
+        set_error("vp_decimate_lowpass: cannot allocate %zu bytes of device scratch", want);
+        return VP_ERR_NOMEM;
+      }
+      cap = want;
+    }
+    *out = p;
+    return VP_OK;
+  }
+};
+DecimateScratch& decimate_scratch(int device) {
+  static DecimateScratch pool[64];
+  return pool[(unsigned)device % 64];
+}
+
+// Samples after which the response to a wrong starting state has decayed by 2^-40: from the largest pole radius.
+int warmup_length(const double* sos, int ns, double* r_out) {
+  double r = 0.0;
+  for (int s = 0; s < ns; ++s) {
+    const double a1 = sos[6 * s + 4], a2 = sos[6 * s + 5];
+    const double disc = a1 * a1 - 4.0 * a2;
+    double rs;
+    if (disc < 0.0) {
+      rs = std::sqrt(a2);  // complex pair: |z|^2 = a2
+    } else {
+      const double q = std::sqrt(disc);
+      rs = std::fmax(std::fabs(-a1 + q), std::fabs(-a1 - q)) * 0.5;
+    }
+    r = std::fmax(r, rs);
+  }
+  *r_out = r;
+  if (!(r < 1.0)) return -1;
+  if (r < 1e-12) return 2 * ns;
+  return (int)std::ceil(40.0 * std::log(2.0) / -std::log(r)) + 2 * ns;
+}
+
+struct Plan {
+  SosArg arg;
+  int warm;
+  const void *fwd, *bwd;
+};
+
+int make_plan(const char* who, const void* in_dev, int in_kind, int64_t n, const double* sos, int n_sections, int factor,
+              const float* out_dev, int64_t out_len, Plan* plan) {
+  VP_REQUIRE(in_dev && sos && out_dev, "%s: null argument", who);
+  VP_REQUIRE(in_kind == VP_SAMPLES_INT32 || in_kind == VP_SAMPLES_FLOAT32 || in_kind == VP_SAMPLES_FLOAT64,
+             "%s: in_kind %d is none of VP_SAMPLES_INT32 / FLOAT32 / FLOAT64", who, in_kind);
+  VP_REQUIRE(n >= 1, "%s: n = %lld, need at least one sample", who, (long long)n);
+  VP_REQUIRE(factor >= 2, "%s: factor = %d, need >= 2", who, factor);
+  VP_REQUIRE(n_sections >= 1 && n_sections <= DMAXS, "%s: n_sections = %d, the kernel is built for 1..%d", who, n_sections,
+             DMAXS);
+  VP_REQUIRE(out_len == (n + factor - 1) / factor, "%s: out_len = %lld, ceil(n / factor) = %lld", who, (long long)out_len,
+             (long long)((n + factor - 1) / factor));
+  for (int s = 0; s < n_sections; ++s) {
+    for (int i = 0; i < 6; ++i) VP_REQUIRE(std::isfinite(sos[6 * s + i]), "%s: section %d has a non-finite coefficient", who, s);
+    VP_REQUIRE(sos[6 * s + 3] == 1.0, "%s: section %d has a0 = %g, need 1 (scipy's sos layout)", who, s, sos[6 * s + 3]);
+    plan->arg.c[s][0] = sos[6 * s + 0];
+    plan->arg.c[s][1] = sos[6 * s + 1];
+    plan->arg.c[s][2] = sos[6 * s + 2];
+    plan->arg.c[s][3] = sos[6 * s + 4];
+    plan->arg.c[s][4] = sos[6 * s + 5];
+  }
+  for (int s = n_sections; s < DMAXS; ++s)
+    for (int i = 0; i < 5; ++i) plan->arg.c[s][i] = 0.0;
+  double r = 0.0;
+  plan->warm = warmup_length(sos, n_sections, &r);
+  VP_REQUIRE(plan->warm >= 0, "%s: the filter is not stable (largest pole radius %g)", who, r);
+  if (plan->warm > DHALO) {
+    set_error("%s: largest pole radius %g needs a warm-up of %d samples, the tile has room for %d", who, r, plan->warm, DHALO);
+    return VP_ERR_UNSUPPORTED;
+  }
+  plan->fwd = forward_kernel(in_kind, n_sections);
+  plan->bwd = pass_kernel<double, true>(n_sections);
+  return VP_OK;
+}
+
+int prepare_kernels(const Plan& plan) {
+  VP_HIP(hipFuncSetAttribute(plan.fwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DLDS_BYTES));
+  VP_HIP(hipFuncSetAttribute(plan.bwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DLDS_BYTES));
+  return VP_OK;
+}
+
+// every instantiation takes the same argument list (the input pointer's type aside)
+hipError_t launch_pass(const void* kernel, const Plan& plan, const void* in, long long n, double* f_out, float* y_out,
+                       int factor, int* flag, hipStream_t s) {
+  SosArg arg = plan.arg;
+  int warm = plan.warm;
+  void* args[] = {&in, &n, &arg, &warm, &f_out, &y_out, &factor, &flag};
+  return hipLaunchKernel(kernel, dim3((unsigned)((n + DTILE - 1) / DTILE)), dim3(DT), args, DLDS_BYTES, s);
+}
+
+hipError_t launch_passes(const Plan& plan, const void* in_dev, long long n, int factor, double* f, int* flag, float* out,
+                         hipStream_t s) {
+  const hipError_t e = launch_pass(plan.fwd, plan, in_dev, n, f, nullptr, factor, flag, s);
+  return e != hipSuccess ? e : launch_pass(plan.bwd, plan, f, n, nullptr, out, factor, flag, s);
+}
+
+}  // namespace
+}  // namespace vp
+
+using namespace vp;
+
+extern "C" int vp_decimate_lowpass(int device_id, const void* in_dev, int in_kind, int64_t n, const double* sos,
+                                   int n_sections, int factor, float* out_dev, int64_t out_len) {
+  Plan plan;
+  if (const int rc = make_plan("vp_decimate_lowpass", in_dev, in_kind, n, sos, n_sections, factor, out_dev, out_len, &plan))
+    return rc;
+  VP_REQUIRE(device_id >= 0, "vp_decimate_lowpass: device index");
+  VP_HIP(hipSetDevice(device_id));
+  if (const int rc = prepare_kernels(plan)) return rc;
+  hipStream_t s = nullptr;  // the null stream, one synchronisation at the end: as vp_mseed_decode
+  DecimateScratch& sc = decimate_scratch(device_id);
+  std::lock_guard<std::mutex> lock(sc.mu);
+  void* p = nullptr;
+  if (const int rc = sc.grow(64 + (size_t)n * sizeof(double), &p)) return rc;
+  int* flag = (int*)p;
+  double* f = (double*)((char*)p + 64);
+  VP_HIP(hipMemsetAsync(flag, 0, sizeof(int), s));
+  VP_HIP(launch_passes(plan, in_dev, (long long)n, factor, f, flag, out_dev, s));
+  VP_HIP(hipStreamSynchronize(s));
+  return VP_OK;
+}
+
+extern "C" int vp_decimate_release_scratch(int device_id, size_t* bytes_freed) {
+  VP_REQUIRE(device_id >= 0, "vp_decimate_release_scratch: device index");
+  DecimateScratch& sc = decimate_scratch(device_id);
+  std::lock_guard<std::mutex> lock(sc.mu);  // behind any call in flight on this device
+  VP_HIP(hipSetDevice(device_id));
+  if (sc.p) (void)hipFree(sc.p);
+  if (bytes_freed) *bytes_freed = sc.cap;
+  sc.p = nullptr;
+  sc.cap = 0;
+  return VP_OK;
+}
+
+extern "C" int vp_decimate_lowpass_bench(int device_id, const void* in_dev, int in_kind, int64_t n, const double* sos,
+                                         int n_sections, int factor, float* out_dev, int64_t out_len, int iters,
+                                         float* ms_total, float* ms_forward) {
+  VP_REQUIRE(ms_total && iters > 0, "vp_decimate_lowpass_bench: bad argument");
+  Plan plan;
+  if (const int rc = make_plan("vp_decimate_lowpass_bench", in_dev, in_kind, n, sos, n_sections, factor, out_dev, out_len,
+                               &plan))
+    return rc;
+  VP_REQUIRE(device_id >= 0, "vp_decimate_lowpass_bench: device index");
+  VP_HIP(hipSetDevice(device_id));
+  if (const int rc = prepare_kernels(plan)) return rc;
+  DecimateScratch& sc = decimate_scratch(device_id);
+  std::lock_guard<std::mutex> lock(sc.mu);
+  void* p = nullptr;
+  if (const int rc = sc.grow(64 + (size_t)n * sizeof(double), &p)) return rc;
+  int* flag = (int*)p;
+  double* f = (double*)((char*)p + 64);
+  hipStream_t s;
+  VP_HIP(hipStreamCreate(&s));
+  hipEvent_t e0, e1;
+  VP_HIP(hipEventCreate(&e0));
+  VP_HIP(hipEventCreate(&e1));
+  VP_HIP(hipMemsetAsync(flag, 0, sizeof(int), s));
+  float t_all = 0.f, t_fwd = 0.f;
+  for (int i = 0; i < 3; ++i) VP_HIP(launch_passes(plan, in_dev, (long long)n, factor, f, flag, out_dev, s));
+  VP_HIP(hipEventRecord(e0, s));
+  for (int i = 0; i < iters; ++i) VP_HIP(launch_passes(plan, in_dev, (long long)n, factor, f, flag, out_dev, s));
+  VP_HIP(hipEventRecord(e1, s));
+  VP_HIP(hipEventSynchronize(e1));
+  VP_HIP(hipEventElapsedTime(&t_all, e0, e1));
+  VP_HIP(hipEventRecord(e0, s));
+  for (int i = 0; i < iters; ++i) VP_HIP(launch_pass(plan.fwd, plan, in_dev, (long long)n, f, nullptr, factor, flag, s));
+  VP_HIP(hipEventRecord(e1, s));
+  VP_HIP(hipEventSynchronize(e1));
+  VP_HIP(hipEventElapsedTime(&t_fwd, e0, e1));
+  *ms_total = t_all / iters;
+  if (ms_forward) *ms_forward = t_fwd / iters;
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  (void)hipStreamDestroy(s);
+  return VP_OK;
+}

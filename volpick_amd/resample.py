@@ -20,8 +20,10 @@ import warnings
 import numpy as np
 
 
-def lowpass_zerophase(data, freq, df, corners=4):
-    from scipy.signal import iirfilter, sosfilt, zpk2sos
+def lowpass_sos(freq, df, corners=4):
+    """Second-order sections (scipy's ``sos`` layout, float64) of ObsPy's Butterworth low-pass with corner ``freq`` at
+    sampling rate ``df``: the one source of filter coefficients of the host path and the device path."""
+    from scipy.signal import iirfilter, zpk2sos
 
     fe = 0.5 * df
     f = freq / fe
@@ -29,7 +31,13 @@ def lowpass_zerophase(data, freq, df, corners=4):
         f = 1.0
         warnings.warn("Selected corner frequency is above Nyquist. Setting Nyquist as high corner.")
     z, p, k = iirfilter(corners, f, btype="lowpass", ftype="butter", output="zpk")
-    sos = zpk2sos(z, p, k)
+    return zpk2sos(z, p, k)
+
+
+def lowpass_zerophase(data, freq, df, corners=4):
+    from scipy.signal import sosfilt
+
+    sos = lowpass_sos(freq, df, corners)
     firstpass = sosfilt(sos, data)
     return sosfilt(sos, firstpass[::-1])[::-1]
 
@@ -79,12 +87,79 @@ def resample_array(data, rate_in, rate_out):
     return resample_fourier(data, rate_in, rate_out)
 
 
+_IN_KINDS = {"torch.int32": 0, "torch.float32": 1, "torch.float64": 2}  # VP_SAMPLES_INT32 / FLOAT32 / FLOAT64
+
+
+def decimate_device(x, rate_in, rate_out):
+    """The integer-ratio branch of :func:`resample_array` on the GPU (``vp_decimate_lowpass``): ``x`` is a 1-D CUDA tensor
+    of int32, float32 or float64 samples at ``rate_in``, an integer multiple (>= 2) of ``rate_out``; returns a float32 CUDA
+    tensor of ``ceil(len(x) / k)`` samples.  Same coefficients as the host path (:func:`lowpass_sos`), float64 state and
+    intermediate, one rounding to float32 at the end.  Raises ``VolpickHipError`` where the library refuses (a factor whose
+    warm-up does not fit the kernel's tile): there is no silent host fallback inside this function."""
+    import ctypes as C
+
+    import torch
+
+    from . import _lib
+
+    rate_in, rate_out = float(rate_in), float(rate_out)
+    if not (rate_in % rate_out == 0 and rate_in > rate_out):
+        raise ValueError(f"decimate_device: {rate_in} Hz is not an integer multiple (>= 2) of {rate_out} Hz")
+    if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 1 and str(x.dtype) in _IN_KINDS):
+        raise TypeError("decimate_device: need a 1-D CUDA tensor of int32, float32 or float64 samples")
+    k = int(rate_in / rate_out)
+    x = x.contiguous()
+    n = int(x.shape[0])
+    out = torch.empty((n + k - 1) // k, dtype=torch.float32, device=x.device)
+    if n == 0:
+        return out
+    sos = np.ascontiguousarray(lowpass_sos(rate_out * 0.5, rate_in), dtype=np.float64)
+    torch.cuda.current_stream(x.device).synchronize()  # the library works on the null stream: x is complete before it starts
+    _lib.check(_lib.load().vp_decimate_lowpass(
+        x.device.index, C.c_void_p(x.data_ptr()), _IN_KINDS[str(x.dtype)], n, sos.ctypes.data_as(C.POINTER(C.c_double)),
+        len(sos), k, C.c_void_p(out.data_ptr()), out.shape[0]), "vp_decimate_lowpass")
+    return out
+
+
+def release_decimate_scratch(device=0):
+    """Free the float64 scratch `decimate_device` keeps per device between calls; returns the bytes freed."""
+    import ctypes as C
+
+    from . import _lib
+
+    freed = C.c_size_t(0)
+    _lib.check(_lib.load().vp_decimate_release_scratch(int(device), C.byref(freed)), "vp_decimate_release_scratch")
+    return int(freed.value)
+
+
 def resample_trace(tr, rate_out, copy=True):
     """A trace at ``rate_out``: the trace itself if it already is, a resampled copy (or, with ``copy=False``, the trace
-    resampled in place, as upstream does) otherwise.  Works on ``volpick_amd.Trace`` and on ObsPy traces."""
+    resampled in place, as upstream does) otherwise.  Works on ``volpick_amd.Trace`` and on ObsPy traces.
+
+    A device-backed ``volpick_amd.Trace`` whose rate is an integer multiple of ``rate_out`` is decimated on the GPU
+    (:func:`decimate_device`) and stays there: no host copy of it is made.  Every other case -- host traces, non-integer
+    ratios, upsampling -- takes the host path."""
     rate_in = float(tr.stats.sampling_rate)
     if abs(rate_in - rate_out) <= 1e-6:
         return tr
+    dev = getattr(tr, "_dev", None)
+    if dev is not None and rate_in % float(rate_out) == 0 and rate_in > rate_out and str(dev.dtype) in _IN_KINDS:
+        from ._lib import VolpickHipError
+        from .stream import Trace
+
+        try:
+            y = decimate_device(dev, rate_in, rate_out)
+        except VolpickHipError as e:  # a factor beyond the kernel's tile: said aloud, then the host path below
+            warnings.warn(f"{tr.id}: decimation on the device refused ({e}); resampling on the host")
+        else:
+            if copy:
+                hdr = tr.stats.copy()
+                hdr["sampling_rate"] = rate_out
+                return Trace(header=hdr, device_data=y)
+            tr._dev, tr._data = y, None
+            tr.stats["npts"] = int(y.shape[0])
+            tr.stats.sampling_rate = rate_out
+            return tr
     out = tr.copy() if copy else tr
     out.data = resample_array(out.data, rate_in, rate_out)
     out.stats.sampling_rate = rate_out

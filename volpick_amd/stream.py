@@ -297,6 +297,34 @@ class Stream:
     __repr__ = __str__
 
 
+def to_device(stream, device=0):
+    """A new Stream whose traces are device-backed: every trace's samples uploaded to ``cuda:device`` in their own dtype (int32,
+    float32, float64; anything else as float32), headers copied.  ``classify`` / ``annotate`` then assemble, and where the
+    rate is an integer multiple of the model's decimate, on the GPU.  Traces that already live on that device are shared,
+    not copied; masked traces are refused (split the stream at its gaps first)."""
+    import torch
+
+    dev = torch.device("cuda", int(device))
+    out = Stream()
+    for tr in stream:
+        d = getattr(tr, "_dev", None)
+        if d is None or d.device != dev:
+            if d is not None:
+                d = d.to(dev)
+            else:
+                a = tr.data
+                if np.ma.isMaskedArray(a):
+                    raise NotImplementedError("masked traces cannot be moved to the device; split the stream at its gaps first")
+                a = np.ascontiguousarray(a)
+                if a.dtype not in (np.dtype(np.int32), np.dtype(np.float32), np.dtype(np.float64)):
+                    a = a.astype(np.float32)
+                d = torch.from_numpy(a).to(dev)
+        hdr = Stats({k: v for k, v in dict(tr.stats).items() if k not in ("npts", "delta", "endtime")})
+        hdr["starttime"] = UTCDateTime(tr.stats.starttime)
+        out.append(Trace(header=hdr, device_data=d))
+    return out
+
+
 def deepcopy_stream(stream):
     return stream.copy() if hasattr(stream, "copy") else _copy.deepcopy(stream)
 
