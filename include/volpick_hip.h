@@ -398,6 +398,40 @@ int vp_decimate_lowpass_bench(int device_id, const void* in_dev, int in_kind, in
                               int factor, float* out_dev, int64_t out_len, int iters, float* ms_total, float* ms_forward);
 
 /* ---------------------------------------------------------------------------------------------
+ * Sampling-rate conversion by a non-integer ratio, on the device: what SeisBench's annotate() does to every other trace
+ * -- trace.resample(model_rate, no_filter = True), ObsPy's Fourier method with a Hann window -- and
+ * volpick_amd/resample.py:resample_fourier restates on the host with scipy:
+ *
+ *     X = rfft(x) * ifftshift(hann(n))[:n/2+1];  Y = interp(d_large_f * m, df * k, X);  y = irfft(Y) * num / n
+ *
+ * in_dev: n samples in device memory, int32, float32 or float64 (in_kind).  num, df and d_large_f are what the host
+ * function forms, passed in so that both sides use the same float64 values: num = int(n / (rate_in / rate_out)),
+ * df = 1.0 / (n * (1.0 / rate_in)), d_large_f = 1.0 / num * rate_out.  out_dev: out_len == num float32 samples in device
+ * memory.  Both transforms are Bluestein chirp-z convolutions over power-of-two complex float64 FFTs of M >= 2 L - 1
+ * points (L = n, then L = num), so n and num may be anything (primes included); the chirp phase is reduced in 64-bit
+ * integers; the only rounding to float32 is the final store.  float32 input is widened and transformed in float64 (the
+ * host path transforms float32 input in single precision, so it is the less accurate of the two).  A NaN or Inf anywhere
+ * in the input makes every output sample NaN, as the host transform does.
+ *
+ * VP_ERR_INVALID: a null pointer, an unknown in_kind, n < 1, num < 1, out_len != num, a rate or frequency step that is
+ * not finite and positive.  VP_ERR_UNSUPPORTED: max(n, num) needs an FFT beyond 2^27 points (2 max(n, num) - 1 > 2^27;
+ * a 250 Hz component-day takes 2^26).  VP_ERR_NOMEM: the scratch cannot be allocated.  No partial result in any case.
+ * Runs on the device's null stream and returns after the work is done, as vp_decimate_lowpass does.  Calls on one device
+ * are serialised.
+ *
+ * The scratch (two FFT buffers of 16 M bytes, the half spectrum, a twiddle table) is kept per device, grow-only, between
+ * calls; vp_resample_release_scratch frees it (bytes_freed may be NULL) -- the other release calls do not touch it.
+ * vp_resample_fourier_bench: mean time in ms (HIP events on a stream of its own, three untimed repetitions first) of
+ * `iters` repetitions of the whole conversion (ms_total) and of the forward transform alone (ms_forward, may be NULL):
+ * bench only. */
+int vp_resample_fourier(int device_id, const void* in_dev, int in_kind, int64_t n, double rate_in, double rate_out,
+                        int64_t num, double df, double d_large_f, float* out_dev, int64_t out_len);
+int vp_resample_release_scratch(int device_id, size_t* bytes_freed);
+int vp_resample_fourier_bench(int device_id, const void* in_dev, int in_kind, int64_t n, double rate_in, double rate_out,
+                              int64_t num, double df, double d_large_f, float* out_dev, int64_t out_len, int iters,
+                              float* ms_total, float* ms_forward);
+
+/* ---------------------------------------------------------------------------------------------
  * PhaseNet training step (BASELINE config 5): what one
  * PhaseNetLit.training_step + Adam optimizer.step of the reference computes
  * (the reference's volpick/model/models.py:34-51 vector_cross_entropy, :160-164 training_step,

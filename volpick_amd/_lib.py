@@ -213,6 +213,17 @@ SIGNATURES = {
         [C.c_int, C.c_void_p, C.c_int, C.c_int64, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int,
          _FP, _FP],
     ),
+    "vp_resample_fourier": (
+        C.c_int,
+        [C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_double, C.c_double, C.c_int64, C.c_double, C.c_double, C.c_void_p,
+         C.c_int64],
+    ),
+    "vp_resample_release_scratch": (C.c_int, [C.c_int, C.POINTER(C.c_size_t)]),
+    "vp_resample_fourier_bench": (
+        C.c_int,
+        [C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_double, C.c_double, C.c_int64, C.c_double, C.c_double, C.c_void_p,
+         C.c_int64, C.c_int, _FP, _FP],
+    ),
     "vp_train_create": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(_H)]),
     "vp_train_create_dtype": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(_H)]),
     "vp_train_dtype": (C.c_int, [_H]),

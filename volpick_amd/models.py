@@ -874,8 +874,9 @@ def _group_stream(stream, component_order, sampling_rate, copy, in_samples):
     from .resample import resample_trace
 
     # traces at the model's rate are never modified, so ``copy`` needs no deep copy for them; the others are
-    # resampled as SeisBench's annotate() does (on copies, or in place with copy=False)
-    traces = [resample_trace(tr, float(sampling_rate), copy) for tr in stream]
+    # resampled as SeisBench's annotate() does (on copies, or in place with copy=False); device-backed ones on the device,
+    # whichever branch of the rule they take
+    traces = [resample_trace(tr, float(sampling_rate), copy, fourier_on_device=True) for tr in stream]
     if len(traces) == 0:
         return
     groups = {}

@@ -132,25 +132,90 @@ def release_decimate_scratch(device=0):
     return int(freed.value)
 
 
-def resample_trace(tr, rate_out, copy=True):
+def fourier_args(n, rate_in, rate_out):
+    """``num``, ``df`` and ``d_large_f`` with exactly the expressions of :func:`resample_fourier`: the device path is handed
+    the host path's float64 values, not a restatement of them."""
+    factor = rate_in / float(rate_out)
+    num = int(n / factor)
+    df = 1.0 / (n * (1.0 / rate_in))
+    d_large_f = 1.0 / num * rate_out if num >= 1 else float("nan")
+    return num, df, d_large_f
+
+
+def fourier_device(x, rate_in, rate_out):
+    """The other branch of :func:`resample_array` on the GPU (``vp_resample_fourier``), :func:`decimate_device`'s twin: ``x``
+    is a 1-D CUDA tensor of int32, float32 or float64 samples at ``rate_in``, no integer multiple of ``rate_out``; returns a
+    float32 CUDA tensor of ``int(len(x) / (rate_in / rate_out))`` samples.  :func:`resample_fourier` in float64 on the device
+    (Bluestein chirp-z transforms, so any length costs the same), one rounding to float32 at the end.
+
+    float32 samples are widened and transformed in float64.  The host path transforms float32 input in single precision
+    (scipy.fftpack keeps the dtype), so for such traces the device answer is the more accurate of the two and the host one
+    differs from it by single-precision rounding noise.
+
+    Raises ``ValueError`` for equal rates, an integer ratio (the other branch) and a trace too short to give one output
+    sample; ``VolpickHipError`` where the library refuses (a trace beyond its largest transform, no memory for the scratch):
+    there is no silent host fallback inside this function."""
+    import ctypes as C
+
+    import torch
+
+    from . import _lib
+
+    rate_in, rate_out = float(rate_in), float(rate_out)
+    if rate_in == rate_out:
+        raise ValueError(f"fourier_device: the trace already is at {rate_out} Hz")
+    if rate_in % rate_out == 0:
+        raise ValueError(f"fourier_device: {rate_in} Hz is an integer multiple of {rate_out} Hz: that is decimate_device's branch")
+    if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 1 and str(x.dtype) in _IN_KINDS):
+        raise TypeError("fourier_device: need a 1-D CUDA tensor of int32, float32 or float64 samples")
+    x = x.contiguous()
+    n = int(x.shape[0])
+    num, df, d_large_f = fourier_args(n, rate_in, rate_out) if n else (0, 0.0, 0.0)
+    if num < 1:
+        raise ValueError(f"fourier_device: {n} samples at {rate_in} Hz give no sample at {rate_out} Hz")
+    out = torch.empty(num, dtype=torch.float32, device=x.device)
+    torch.cuda.current_stream(x.device).synchronize()  # the library works on the null stream: x is complete before it starts
+    _lib.check(_lib.load().vp_resample_fourier(
+        x.device.index, C.c_void_p(x.data_ptr()), _IN_KINDS[str(x.dtype)], n, rate_in, rate_out, num, df, d_large_f,
+        C.c_void_p(out.data_ptr()), num), "vp_resample_fourier")
+    return out
+
+
+def release_fourier_scratch(device=0):
+    """Free the FFT buffers `fourier_device` keeps per device between calls; returns the bytes freed."""
+    import ctypes as C
+
+    from . import _lib
+
+    freed = C.c_size_t(0)
+    _lib.check(_lib.load().vp_resample_release_scratch(int(device), C.byref(freed)), "vp_resample_release_scratch")
+    return int(freed.value)
+
+
+def resample_trace(tr, rate_out, copy=True, fourier_on_device=False):
     """A trace at ``rate_out``: the trace itself if it already is, a resampled copy (or, with ``copy=False``, the trace
     resampled in place, as upstream does) otherwise.  Works on ``volpick_amd.Trace`` and on ObsPy traces.
 
     A device-backed ``volpick_amd.Trace`` whose rate is an integer multiple of ``rate_out`` is decimated on the GPU
-    (:func:`decimate_device`) and stays there: no host copy of it is made.  Every other case -- host traces, non-integer
-    ratios, upsampling -- takes the host path."""
+    (:func:`decimate_device`) and stays there: no host copy of it is made.  With ``fourier_on_device=True`` (what
+    ``annotate`` / ``classify`` pass) a device-backed trace at any other rate is resampled there too
+    (:func:`fourier_device`; for float32 samples that is the float64 answer, where the host path computes in single
+    precision).  Every other case -- host traces, and device-backed ones on the Fourier branch by default -- takes the host
+    path."""
     rate_in = float(tr.stats.sampling_rate)
     if abs(rate_in - rate_out) <= 1e-6:
         return tr
     dev = getattr(tr, "_dev", None)
-    if dev is not None and rate_in % float(rate_out) == 0 and rate_in > rate_out and str(dev.dtype) in _IN_KINDS:
+    integer_ratio = rate_in % float(rate_out) == 0 and rate_in > rate_out
+    if dev is not None and (integer_ratio or fourier_on_device) and str(dev.dtype) in _IN_KINDS:
         from ._lib import VolpickHipError
         from .stream import Trace
 
         try:
-            y = decimate_device(dev, rate_in, rate_out)
-        except VolpickHipError as e:  # a factor beyond the kernel's tile: said aloud, then the host path below
-            warnings.warn(f"{tr.id}: decimation on the device refused ({e}); resampling on the host")
+            y = decimate_device(dev, rate_in, rate_out) if integer_ratio else fourier_device(dev, rate_in, float(rate_out))
+        except VolpickHipError as e:  # a factor beyond the kernel's tile, a trace beyond the largest FFT: said aloud, then the host path below
+            what = "decimation" if integer_ratio else "Fourier resampling"
+            warnings.warn(f"{tr.id}: {what} on the device refused ({e}); resampling on the host")
         else:
             if copy:
                 hdr = tr.stats.copy()

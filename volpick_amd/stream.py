@@ -300,7 +300,7 @@ class Stream:
 def to_device(stream, device=0):
     """A new Stream whose traces are device-backed: every trace's samples uploaded to ``cuda:device`` in their own dtype (int32,
     float32, float64; anything else as float32), headers copied.  ``classify`` / ``annotate`` then assemble, and where the
-    rate is an integer multiple of the model's decimate, on the GPU.  Traces that already live on that device are shared,
+    rate differs from the model's decimate or Fourier-resample, on the GPU.  Traces that already live on that device are shared,
     not copied; masked traces are refused (split the stream at its gaps first)."""
     import torch
 
