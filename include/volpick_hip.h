@@ -577,6 +577,52 @@ int vp_train_step_bank_aug(vp_trainer* t, vp_bank* bank, const vp_aug_row* rows,
                            const int* label_rows, float lr, int update, double* loss);
 
 /* ---------------------------------------------------------------------------------------------
+ * Frequency index and signal-to-noise ratio of picks and bank traces, on the device: the trace_frequency_index,
+ * trace_snr_db and trace_mean_snr_db columns the reference stores with every trace it writes (volpick/data/utils.py
+ * freqency_index, calculate_snr; volpick/data/convert.py:222-270).  One vp_attr_row per pick or trace, planned on the
+ * host (volpick_amd/attributes.py, plan_rows) from lengths and onsets alone; the rule is restated in
+ * tests/attributes_f64.py.  Per row, in float64:
+ *
+ *   frequency index of component c: X = DFT of x[c][fi_start : fi_start + fi_n] times the symmetric Hann window, at bins
+ *     [lo_first, lo_first + lo_count) and [hi_first, hi_first + hi_count) only; log10(mean |X| high / mean |X| low).
+ *     NaN where a band is empty (a count of 0), where fi_n = 0 (no reference sample), where the window holds a NaN, and
+ *     for a component whose sum |diff| over the WHOLE trace is <= 1e-9 (a dead channel).  The row's index is the mean of
+ *     the components that are not NaN, NaN if none.
+ *   percentile of a window of m samples (noise, signal): the values of rank `lo` and `up` of |x| (0-based, ascending),
+ *     a + (b - a) g, or b - (b - a) (1 - g) where g >= 0.5 -- numpy's linear method, bit for bit where the host plans
+ *     h = (m - 1) 0.95, lo = floor(h), up = min(lo + 1, m - 1), g = h - lo.  NaN if the window holds a NaN or m = 0.
+ *   snr_db of a component: 20 log10(signal / noise), NaN where either percentile is <= 1e-8 (np.isclose(v, 0)); their
+ *     mean over the components that are not NaN, NaN if none.
+ *   VP_ATTR_DEMEAN: before all of the above, each component has its mean over the span from the row's earliest window
+ *     start to its latest window end subtracted (raw counts carry an offset).
+ *
+ * out: n_rows x 14 float64, device or host memory (the call finds out): fi[3], fi_trace, noise_p95[3], signal_p95[3],
+ * snr_db[3], snr_mean.  Deterministic: no atomics, every sum in a fixed order.  vp_attributes reads one (3, n_samples)
+ * fp32 array on the device (every row's trace is 0); vp_bank_attributes reads the bank's traces (a row's `trace` indexes
+ * the bank).  Both run the same kernel on `stream` (hipStream_t, NULL = legacy default stream) and return after the work
+ * is done; `rows` is host memory.  Calls on one device are serialised.
+ *
+ * Every row is checked on the host first (VP_ERR_INVALID, nothing launched, out untouched): trace in range, windows
+ * inside the trace and of at most 2048 samples, bins below fi_n / 2, 0 <= lo <= up <= lo + 1 < m, 0 <= g <= 1, unknown
+ * flags.  VP_ERR_NOMEM: the scratch (staged rows, per-trace sums) cannot be allocated. */
+#define VP_ATTR_DEMEAN 1
+#define VP_ATTR_MAX_WINDOW 2048
+#define VP_ATTR_OUT 14
+typedef struct {
+  int32_t trace;
+  int32_t flags;                                /* VP_ATTR_DEMEAN */
+  int64_t fi_start, noise_start, signal_start;  /* first sample of each window */
+  int32_t fi_n, noise_n, signal_n;              /* their lengths; 0 = absent */
+  int32_t lo_first, lo_count, hi_first, hi_count;
+  int32_t noise_lo, noise_up, signal_lo, signal_up;
+  int32_t reserved;                             /* 0 */
+  double noise_g, signal_g;
+} vp_attr_row;
+int vp_attributes(int device_id, const float* data, int64_t n_samples, const vp_attr_row* rows, int n_rows, double* out,
+                  void* stream);
+int vp_bank_attributes(vp_bank* bank, const vp_attr_row* rows, int n_rows, double* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Multi-GPU bring-up.  The reference is single-GPU; windows are independent given the
  * weights, so the one exchange is the start-up broadcast of the flat weight blob from the root rank: a single
  * ncclBroadcast over RCCL (xGMI inside a node), after which vp_create(..., VP_MEM_DEVICE, ...) builds the plan from the

@@ -12,5 +12,6 @@ from .picks import ClassifyOutput, Detection, DetectionList, Pick, PickList  # n
 from .stream import Stream, Trace, UTCDateTime, pinned_array, to_device  # noqa: F401
 from ._lib import VolpickHipError  # noqa: F401
 from .io import read  # noqa: F401
+from .attributes import bank_attributes, pick_attributes, plan_rows  # noqa: F401
 
 __version__ = "0.1.0"

@@ -92,6 +92,32 @@ class VpMseedRecord(C.Structure):
 
 VP_SAMPLES_INT32, VP_SAMPLES_FLOAT32, VP_SAMPLES_FLOAT64 = 0, 1, 2
 
+VP_ATTR_DEMEAN, VP_ATTR_MAX_WINDOW, VP_ATTR_OUT = 1, 2048, 14
+
+
+class VpAttrRow(C.Structure):
+    _fields_ = [
+        ("trace", C.c_int32),
+        ("flags", C.c_int32),
+        ("fi_start", C.c_int64),
+        ("noise_start", C.c_int64),
+        ("signal_start", C.c_int64),
+        ("fi_n", C.c_int32),
+        ("noise_n", C.c_int32),
+        ("signal_n", C.c_int32),
+        ("lo_first", C.c_int32),
+        ("lo_count", C.c_int32),
+        ("hi_first", C.c_int32),
+        ("hi_count", C.c_int32),
+        ("noise_lo", C.c_int32),
+        ("noise_up", C.c_int32),
+        ("signal_lo", C.c_int32),
+        ("signal_up", C.c_int32),
+        ("reserved", C.c_int32),
+        ("noise_g", C.c_double),
+        ("signal_g", C.c_double),
+    ]
+
 
 class VolpickHipError(RuntimeError):
     pass
@@ -260,6 +286,8 @@ SIGNATURES = {
         C.c_int,
         [_H, _H, C.c_void_p, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_int), C.c_float, C.c_int, C.POINTER(C.c_double)],
     ),
+    "vp_attributes": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.POINTER(VpAttrRow), C.c_int, C.c_void_p, C.c_void_p]),
+    "vp_bank_attributes": (C.c_int, [_H, C.POINTER(VpAttrRow), C.c_int, C.c_void_p, C.c_void_p]),
     "vp_last_error": (C.c_char_p, []),
     "vp_version": (C.c_char_p, []),
 }
