@@ -79,9 +79,13 @@ def test_device_trigger_scan_exact_on_random_traces(pn):
 
 
 def test_device_trigger_scan_edge_cases(pn):
-    """Runs against the 2048-sample chunk grid of trigger_scan_kernel and the 64-sample walk-back."""
-    CH = 2048
-    base = np.full(5 * CH + 300, 0.05, np.float32)
+    """Runs against the chunk grid of trigger_scan_kernel (tests/trigger_cases.py: CH = 1024 samples per workgroup; every
+    case at a seam is laid at 2 * CH = 2048, a seam too, and at CH) and against its walk-back: four 64-sample blocks, TRIP =
+    256 samples, per trip.  The families that aim at the run-end list, the trips and the strided argmax one by one are in
+    tests/test_gpu_triggers.py."""
+    from tests.trigger_cases import CH as CHUNK, WALK_LENGTHS
+
+    base = np.full(5 * 2 * CHUNK + 300, 0.05, np.float32)
 
     def case(edit, thr=0.5, off=None):
         x = base.copy()
@@ -96,38 +100,41 @@ def test_device_trigger_scan_edge_cases(pn):
     def put(x, a, b, v=0.9):
         x[a:b + 1] = v
 
-    case(lambda x: put(x, CH - 8, CH + 12))                    # straddles one chunk boundary
-    case(lambda x: put(x, CH - 1, CH))                         # two samples, one on each side
-    case(lambda x: put(x, CH - 5, CH - 1))                     # ends exactly on the last sample of a chunk
-    case(lambda x: put(x, CH, CH + 5))                         # starts exactly on the first sample of a chunk
-    case(lambda x: put(x, 1000, 3 * CH + 77))                  # spans several chunks (walk-back over > 6000 samples)
+    for CH in (2 * CHUNK, CHUNK):
+        case(lambda x: put(x, CH - 8, CH + 12))                    # straddles one chunk boundary
+        case(lambda x: put(x, CH - 1, CH))                         # two samples, one on each side
+        case(lambda x: put(x, CH - 5, CH - 1))                     # ends exactly on the last sample of a chunk
+        case(lambda x: put(x, CH, CH + 5))                         # starts exactly on the first sample of a chunk
+        case(lambda x: put(x, 1000, 3 * CH + 77))                  # spans several chunks (walk-back over > 6000 samples at 2048)
+        case(lambda x: (put(x, CH - 70, CH + 70), x.__setitem__(CH, np.nan)))          # NaN inside a run splits it
+        case(lambda x: (put(x, CH - 64, CH - 1), put(x, CH + 1, CH + 64)))             # 64-sample runs around a gap of one
     case(lambda x: (put(x, 0, 10), put(x, len(x) - 30, len(x) - 1)))  # run at sample 0; run open at the last sample
     case(lambda x: put(x, 0, len(x) - 1))                      # the whole trace is one run
-    case(lambda x: (put(x, CH - 70, CH + 70), x.__setitem__(CH, np.nan)))          # NaN inside a run splits it
     case(lambda x: (put(x, 100, 200), x.__setitem__(slice(300, 400), np.nan), put(x, 500, 600)))  # NaN between runs
-    case(lambda x: (put(x, CH - 64, CH - 1), put(x, CH + 1, CH + 64)))             # 64-sample runs around a gap of one
-    for k in (62, 63, 64, 65, 127, 128, 129):                                      # walk-back block edges
+    assert set(WALK_LENGTHS) >= {62, 63, 64, 65, 127, 128, 129}
+    for k in WALK_LENGTHS:                                         # walk-back block and trip edges
         case(lambda x, k=k: put(x, 3000, 3000 + k - 1))
 
     # thr_off = thr / 2 re-arming: two bumps > thr_on joined by samples in (thr_off, thr_on] are ONE trigger whose
     # onset is the first bump; separated by a sample <= thr_off they are two
-    def bumps(x):
-        put(x, CH - 40, CH - 30, 0.9)
-        put(x, CH - 29, CH + 20, 0.3)   # > 0.25, <= 0.5
-        put(x, CH + 21, CH + 30, 0.95)
-        put(x, 4000, 4010, 0.9)
-        x[4011] = 0.2                   # <= thr_off: closes
-        put(x, 4012, 4020, 0.8)
-    w = case(bumps, thr=0.5, off=0.25)
-    assert (w[0][0], w[0][1], w[0][2]) == (CH - 40, CH + 30, CH + 21) and len(w) == 3
+    for CH in (2 * CHUNK, CHUNK):
+        def bumps(x):
+            put(x, CH - 40, CH - 30, 0.9)
+            put(x, CH - 29, CH + 20, 0.3)   # > 0.25, <= 0.5
+            put(x, CH + 21, CH + 30, 0.95)
+            put(x, 4000, 4010, 0.9)
+            x[4011] = 0.2                   # <= thr_off: closes
+            put(x, 4012, 4020, 0.8)
+        w = case(bumps, thr=0.5, off=0.25)
+        assert (w[0][0], w[0][1], w[0][2]) == (CH - 40, CH + 30, CH + 21) and len(w) == 3
 
-    # a run above thr_off that never exceeds thr_on is no trigger; a plateau's peak is its FIRST sample
-    def plateau(x):
-        put(x, 100, 300, 0.4)
-        put(x, CH - 20, CH + 20, 0.7)
-        put(x, CH - 3, CH + 3, 0.8)
-    w = case(plateau, thr=0.5, off=0.25)
-    assert len(w) == 1 and w[0][2] == CH - 3
+        # a run above thr_off that never exceeds thr_on is no trigger; a plateau's peak is its FIRST sample
+        def plateau(x):
+            put(x, 100, 300, 0.4)
+            put(x, CH - 20, CH + 20, 0.7)
+            put(x, CH - 3, CH + 3, 0.8)
+        w = case(plateau, thr=0.5, off=0.25)
+        assert len(w) == 1 and w[0][2] == CH - 3
 
 
 def test_device_trigger_scan_cap_and_long_trace(pn):

@@ -295,10 +295,11 @@ int launch_stack(const StackArgs& a, hipStream_t stream) {
 // instead of holding its CUs for itself at the boundary between two launches
 constexpr int SCAN_CHUNK = 1024;  // samples per workgroup
 
-// One launch: every workgroup lists the run ENDS inside its 2048-sample chunk in LDS (phase 1,
-// one thread per 8 samples), then its four wavefronts walk those runs backwards through memory
-// (phase 2) -- a run may start in an earlier chunk, only its end decides who owns it.
-// I = int when every row is shorter than 2^31 - 2048 samples (launch_pick): 32-bit positions keep the kernel within 32 registers
+// One launch: every workgroup lists the run ENDS inside its SCAN_CHUNK = 1024-sample chunk in LDS (phase 1,
+// 256 threads with 4 samples each at stride 256), then its four wavefronts walk those runs backwards through memory,
+// 256 samples per trip (phase 2) -- a run may start in an earlier chunk, only its end decides who owns it.
+// I = int when every row is at most SCAN_INT_MAX = 2^31 - 1 - 4096 samples long (launch_pick): 32-bit positions keep the kernel within
+// 32 registers
 template <class I>
 __device__ __forceinline__ void trigger_scan_body(const PickArgs& a) {
   __shared__ int n_ends;
