@@ -52,7 +52,8 @@ typedef struct {
   float layernorm_eps;        /* EQT LayerNormalization eps */
   float norm_eps;             /* x / (amp + norm_eps) */
   int32_t taper_samples;      /* EQT half-cosine taper length (0 for PhaseNet) */
-  int32_t plan_flags[8];      /* plan selectors (debug plans, A/B timing; all 0 = the default plan):
+  int32_t plan_flags[8];      /* plan selectors (debug plans, A/B timing; all 0 = the default plan; the library's names for
+                                 every index, value and bit: volpick_amd/csrc/plan_flags.h):
                                  [0]: 1 = PhaseNet layer-by-layer plan instead of the fused kernels (debug / A-B);
                                  [1]: bit0 = fused kernels also dump their LDS intermediates to the debug tensors
                                       (selects the three-launch plan), bit1 = per-layer clock stamps,

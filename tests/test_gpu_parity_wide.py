@@ -14,6 +14,7 @@ import torch
 import volpick_amd as va
 from oracle import pipeline as OP
 from oracle.models import load_pretrained
+from tests.plan_selectors import PLAN_SELECTORS
 from volpick_amd.synthetic import synthetic_stream_array, synthetic_windows
 
 pytestmark = pytest.mark.gpu
@@ -240,14 +241,8 @@ def test_regression_bar_full_batch(default_pair):
     assert float(np.abs(got - want).mean()) < 2e-7, err
 
 
-# ---- (e) every documented plan selector (include/volpick_hip.h: vp_config.plan_flags) still produces oracle-grade outputs --------
-PLAN_SELECTORS = {
-    "phasenet": [(1,), (0, 1), (0, 0, 0, 1), (0, 0, 0, 0, 1), (0, 0, 0, 0, 0, 1), (0, 0, 0, 0, 0, 2),
-                 (0, 0, 0, 0, 0, 3), (0, 0, 0, 0, 0, 8), (0, 0, 0, 0, 0, 0, 1), (0, 4)],
-    "eqtransformer": [(1,), (0, 0, 1), (0, 0, 2), (0, 0, 3), (0, 0, 0, 0, 1), (0, 0, 0, 0, 0, 0, 2)] +
-                     [(0, 0, 0, 0, 0, 0, 0, 1 << b) for b in range(12)] + [(0, 0, 0, 0, 0, 0, 0, 0x1F0), (0, 0, 0, 0, 0, 0, 0, 0xF)] +
-                     [(0, 4), (0, 4, 0, 0, 0, 0, 0, 1024)],
-}
+# ---- (e) every documented plan selector (include/volpick_hip.h: vp_config.plan_flags) still produces oracle-grade outputs:
+# PLAN_SELECTORS (tests/plan_selectors.py) --------
 
 
 # A/B forms that round 6 removed: the library says so instead of running something else

@@ -159,8 +159,8 @@ int run_batch(vp_handle* h, const vp::PreArgs& pa, int nb) {
   // (one-launch plans only: a plan of several launches gains from the contexts' launches interleaving; and only launches
   // that fill the chip -- one workgroup per window, 256 CUs: the few-window launches of a classify() over many short
   // blocks overlap freely across contexts, as before the gate)
-  const ForwardTurn turn(h, net.model_kind == VP_MODEL_PHASENET && net.steps.size() == 1 && net.cfg.plan_flags[3] != 64 &&
-                                nb >= FORWARD_GATE_MIN_WINDOWS);
+  const ForwardTurn turn(h, net.model_kind == VP_MODEL_PHASENET && net.steps.size() == 1 &&
+                                vp::pf::get(net.cfg, vp::pf::TILES) != vp::pf::TILES_PN_NO_GATE && nb >= FORWARD_GATE_MIN_WINDOWS);
   if (net.fused_pre && pa.preprocess) {
     net.pre = &pa;
     const int rc = net.run(nb, h->stream);
@@ -1221,10 +1221,9 @@ int vp_debug_conv_clock(vp_handle* h, unsigned long long* out, int max_layers) {
   VP_REQUIRE(h && out && h->net.debug_clock && h->net.debug_clock->d, "no clock stamps (create with plan_flags[1] & 2)");
   VP_HIP(hipSetDevice(h->device));
   VP_HIP(hipStreamSynchronize(h->stream));
-  const int n = std::min<int>(max_layers, 64);
-  const unsigned long long* src =
-      reinterpret_cast<const unsigned long long*>(h->net.debug_clock->d) + (size_t)h->net.max_batch * 32;
-  VP_HIP(hipMemcpy(out, src, (size_t)n * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  const int n = std::min<int>(max_layers, (int)vp::ClockRegions::kConvRows);
+  const unsigned long long* src = vp::clock_words(h->net, vp::ClockRegions(h->net.max_batch).conv);
+  VP_HIP(hipMemcpy(out, src, (size_t)n * vp::ClockRegions::kPerConv * sizeof(unsigned long long), hipMemcpyDeviceToHost));
   return (int)h->net.convs.size();
 }
 
@@ -1242,8 +1241,7 @@ int vp_debug_tail_clock(vp_handle* h, int B, unsigned long long* out32) {
   VP_REQUIRE(h->net.model_kind == VP_MODEL_EQTRANSFORMER && B > 0 && B <= h->net.max_batch, "EQTransformer handles only");
   VP_HIP(hipSetDevice(h->device));
   VP_HIP(hipStreamSynchronize(h->stream));
-  const unsigned long long* src =
-      reinterpret_cast<const unsigned long long*>(h->net.debug_clock->d) + (size_t)h->net.max_batch * 32 + 64 * 8;
+  const unsigned long long* src = vp::clock_words(h->net, vp::ClockRegions(h->net.max_batch).tail);
   VP_HIP(hipMemcpy(out32, src, (size_t)B * 32 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
   return VP_OK;
 }

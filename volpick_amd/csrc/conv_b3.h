@@ -1,5 +1,5 @@
 // Convolutions on the bf16 matrix cores with EXACT operands (the PhaseNet core's five deepest layers; the EQTransformer
-// ResCNN kernel in eqt_fused.hip is the same idea written out by hand).
+// ResCNN kernel in eqt_res.hip is the same idea written out by hand).
 //
 // An fp32 number is exactly the sum of three bfloat16 pieces (hi = rne(x), mid = rne(x - hi), lo = x - hi - mid: 8 + 8 + 8
 // significant bits), bf16 x bf16 products are exact in fp32, and v_mfma_f32_16x16x32_bf16 runs at 16x the rate of the

@@ -145,8 +145,9 @@ AttnWeights resolve(const AttnWeights& w) { return AttnWeights{dptr(w.Wt), dptr(
 int plan_eqt(Net& net, const ParamView& pv) {
   // plan_flags[1] & 4: the DUMP instances of the five fused conv kernels (plan_eqt_fuse_*) and of eqt_mid4_kernel, which exist for
   // their default forms only
-  if ((net.cfg.plan_flags[1] & 4) && (net.cfg.plan_flags[0] != 0 || net.cfg.plan_flags[2] != 0 || net.cfg.plan_flags[3] != 0 ||
-                                      net.cfg.plan_flags[6] == 2 || (net.cfg.plan_flags[7] & ~1024) != 0)) {
+  const vp_config& cfg = net.cfg;
+  if (pf::layer_dumps(cfg) && (pf::get(cfg, pf::LAYERS) != 0 || pf::get(cfg, pf::MID) != 0 || pf::get(cfg, pf::TILES) != 0 ||
+                               pf::get(cfg, pf::PRE) == pf::PRE_EQT_FRONT || pf::eqt_dumps_refuse(cfg))) {
     set_error("EQTransformer plan_flags[1] & 4 dumps the default conv kernels only, and the default middle kernel (plan_flags[0], "
               "[2], [3], [7] other than bit 10 unset, [6] != 2)");
     return VP_ERR_UNSUPPORTED;
@@ -253,14 +254,8 @@ int plan_eqt(Net& net, const ParamView& pv) {
     const int src_t = lstm_in;
     auto mk = [=](Net& n) -> BiLstmArgs {
       BiLstmArgs a{};
-      const Tensor& s0 = n.tensors[src_t];
-      const Tensor& d0 = n.tensors[out];
-      a.src = s0.p;
-      a.ls_src = s0.ls;
-      a.ws_src = (long)s0.win_stride();
-      a.dst = d0.p;
-      a.ls_dst = d0.ls;
-      a.ws_dst = (long)d0.win_stride();
+      bind(a.src, a.ls_src, a.ws_src, n.tensors[src_t]);
+      bind(a.dst, a.ls_dst, a.ws_dst, n.tensors[out]);
       a.fwd = resolve(fw);
       a.bwd = resolve(bw);
       a.wc = wcb->d;
@@ -301,20 +296,9 @@ int plan_eqt(Net& net, const ParamView& pv) {
     const float attn_eps = net.cfg.attention_eps, ln_eps = net.cfg.layernorm_eps;
     auto mk = [=](Net& n) -> TransformerArgs {
       TransformerArgs a{};
-      const Tensor& s0 = n.tensors[src_t];
-      const Tensor& d0 = n.tensors[out];
-      a.src = s0.p;
-      a.ls_src = s0.ls;
-      a.ws_src = (long)s0.win_stride();
-      a.dst = d0.p;
-      a.ls_dst = d0.ls;
-      a.ws_dst = (long)d0.win_stride();
-      if (last) {
-        const Tensor& u = n.tensors[dec_in];
-        a.up = u.p;
-        a.ls_up = u.ls;
-        a.ws_up = (long)u.win_stride();
-      }
+      bind(a.src, a.ls_src, a.ws_src, n.tensors[src_t]);
+      bind(a.dst, a.ls_dst, a.ws_dst, n.tensors[out]);
+      if (last) bind(a.up, a.ls_up, a.ws_up, n.tensors[dec_in]);
       a.att = resolve(aw);
       a.g1 = ln->d;
       a.b1 = ln->d + 16;
@@ -350,14 +334,8 @@ int plan_eqt(Net& net, const ParamView& pv) {
     const float attn_eps = net.cfg.attention_eps;
     auto mk_pick = [=](Net& n, int B) -> PickBranchArgs {
       PickBranchArgs a{};
-      const Tensor& s0 = n.tensors[src_t];
-      const Tensor& u = n.tensors[dec_in];
-      a.src = s0.p;
-      a.ls_src = s0.ls;
-      a.ws_src = (long)s0.win_stride();
-      a.up = u.p;
-      a.ls_up = u.ls;
-      a.ws_up = (long)u.win_stride();
+      bind(a.src, a.ls_src, a.ws_src, n.tensors[src_t]);
+      bind(a.up, a.ls_up, a.ws_up, n.tensors[dec_in]);
       a.B = B;
       for (int br = 0; br < 2; ++br) {
         a.lstm[br] = resolve(lw[br]);
@@ -373,7 +351,8 @@ int plan_eqt(Net& net, const ParamView& pv) {
     // plan_flags[2] = 1 keeps the six separate launches (A/B timing); default: one launch for the whole latency-bound chain,
     // four windows per workgroup in teams of four waves (eqt_mid4.hip); plan_flags[2] = 3: two windows per workgroup in teams
     // of eight waves (the default of rounds 3-5); plan_flags[2] = 2: one window per workgroup (the form of rounds 1-2)
-    if (net.cfg.plan_flags[2] != 1 && mid_first >= 0 && (int)net.steps.size() == mid_first + 6) {
+    const int mid_form = pf::get(cfg, pf::MID);
+    if (mid_form != pf::MID_SIX_LAUNCHES && mid_first >= 0 && (int)net.steps.size() == mid_first + 6) {
       Step fused;
       fused.name = "fused.mid (3 BiLSTM + 2 transformer blocks + pick branches)";
       fused.flops_per_window = mid_flops;
@@ -386,7 +365,7 @@ int plan_eqt(Net& net, const ParamView& pv) {
       // plan_flags[1] & 4 (plan_eqt refused the other middle forms): the DUMP instance of eqt_mid4_kernel and the tensors it
       // writes, in the order of MD_* (eqt_kernels.h)
       std::vector<int> mdbg;
-      if (net.cfg.plan_flags[1] & 4) {
+      if (pf::layer_dumps(cfg)) {
         for (const char* what : {".h", ".c"})
           for (int i = 0; i < 3; ++i) mdbg.push_back(net.add_tensor("bilstm." + std::to_string(i) + what, 32, EQT_T));
         static const std::pair<const char*, int> tr_dumps[5] = {{".p", EQT_T}, {".att", 16}, {".y1", 16}, {".ff1", 128}, {".ff2", 16}};
@@ -407,18 +386,13 @@ int plan_eqt(Net& net, const ParamView& pv) {
         for (int i = 0; i < 3; ++i) m.lstm[i] = mk_lstm[i](n);
         for (int i = 0; i < 2; ++i) m.tr[i] = mk_tr[i](n);
         m.pick = mk_pick(n, B);
-        m.clk = n.debug_clock ? reinterpret_cast<unsigned long long*>(n.debug_clock->d) : nullptr;  // slots [B][8] (tools/mid_clock.py)
+        m.clk = clock_words(n, ClockRegions(n.max_batch).mid);  // slots [B][8] (tools/mid_clock.py)
         m.B = B;
-        if (n.cfg.plan_flags[2] == 2 || n.cfg.plan_flags[2] == 3) return launch_eqt_mid(m, B, s_, n.cfg.plan_flags[2] == 2);
+        if (mid_form == pf::MID_ONE_WINDOW || mid_form == pf::MID_TWO_WINDOWS) return launch_eqt_mid(m, B, s_, mid_form == pf::MID_ONE_WINDOW);
         if (!mdbg.empty()) {
           MidDumpArgs d{};
           static_cast<MidArgs&>(d) = m;
-          for (int i = 0; i < MD_N; ++i) {
-            const Tensor& t = n.tensors[mdbg[i]];
-            d.dbg[i] = t.p;
-            d.dbg_ls[i] = t.ls;
-            d.dbg_ws[i] = (long)t.win_stride();
-          }
+          bind_dbg(d.dbg, d.dbg_ls, d.dbg_ws, n, mdbg.data());
           return launch_eqt_mid4_dump(d, B, s_);
         }
         return launch_eqt_mid4(m, B, s_);
@@ -436,7 +410,7 @@ int plan_eqt(Net& net, const ParamView& pv) {
   const int dk[7] = {3, 5, 5, 7, 7, 9, 11};
   const char* dec_prefix[3] = {"decoder_d", "pick_decoders.0", "pick_decoders.1"};
   int dsrc = dec_in;
-  const bool alt = net.cfg.plan_flags[3] == 1;
+  const bool alt = pf::get(cfg, pf::TILES) == pf::TILES_ALT;
   for (int i = 0; i < 7; ++i) {
     const bool polyphase = true;
     const int dst_len = dout[i];
@@ -498,13 +472,8 @@ int plan_eqt(Net& net, const ParamView& pv) {
       const int src_t = dsrc, dst_t = dst;
       st.run = [=](Net& n, int B, hipStream_t s_) -> int {
         EdgeArgs a{};
-        const Tensor &tx = n.tensors[src_t], &ty = n.tensors[dst_t];
-        a.x = tx.p;
-        a.ls_x = tx.ls;
-        a.ws_x = (long)tx.win_stride();
-        a.y = ty.p;
-        a.ls_y = ty.ls;
-        a.ws_y = (long)ty.win_stride();
+        bind(a.x, a.ls_x, a.ws_x, n.tensors[src_t]);
+        bind(a.y, a.ls_y, a.ws_y, n.tensors[dst_t]);
         a.e = hw->d;
         a.b = hb->d;
         a.win_per_set = B;
@@ -533,32 +502,31 @@ int plan_eqt(Net& net, const ParamView& pv) {
 
   net.flops_per_window = 0;
   for (auto& s : net.steps) net.flops_per_window += s.flops_per_window;
-  if (net.cfg.plan_flags[1] & 2)  // debug clock stamps of every conv launch (tools/conv_clock.py)
-    // [max_batch][32] eqt_mid_kernel | [64][8] conv launches | [max_batch][32] eqt_tail_kernel  (64-bit words)
-    net.debug_clock = net.add_blob(std::vector<float>(((size_t)net.max_batch * 64 + 64 * 8) * 2, 0.f));
+  if (pf::clock_stamps(cfg))  // debug clock stamps of the middle kernel, every conv launch and the tail (ClockRegions; tools/conv_clock.py)
+    net.debug_clock = net.add_blob(std::vector<float>(ClockRegions(net.max_batch).words * 2, 0.f));
   // plan_flags[0] = 1 keeps the 14 ResCNN conv launches (layer-by-layer debug / A-B plan)
-  if (net.cfg.plan_flags[0] != 1) {
+  if (pf::get(cfg, pf::LAYERS) != pf::ON) {
     int rc = plan_eqt_fuse_res(net);
     if (rc != VP_OK) return rc;
   }
   // plan_flags[7] bit 0 keeps decoder.4 / .5 / .6+heads as three launches (layer tests, A/B timing)
-  if (!(net.cfg.plan_flags[7] & 1) && !alt) {
-    int rc = (net.cfg.plan_flags[7] & 64) ? plan_eqt_fuse_tail(net) : plan_eqt_fuse_tail_b3(net);  // bit 6: the fp32-MFMA kernel
+  if (!pf::eqt(cfg, pf::EQT_TAIL_LAYERS) && !alt) {
+    int rc = pf::eqt(cfg, pf::EQT_TAIL_FP32) ? plan_eqt_fuse_tail(net) : plan_eqt_fuse_tail_b3(net);  // bit 6: the fp32-MFMA kernel
     if (rc != VP_OK) return rc;
   }
   // bit 2 keeps encoder.0 .. .2 as three launches
-  if (!(net.cfg.plan_flags[7] & 4)) {
-    int rc = plan_eqt_fuse_front(net, !(net.cfg.plan_flags[7] & 256));  // bit 8: stages 1 and 2 on the fp32 MFMA too
+  if (!pf::eqt(cfg, pf::EQT_FRONT_LAYERS)) {
+    int rc = plan_eqt_fuse_front(net, !pf::eqt(cfg, pf::EQT_FRONT_FP32));  // bit 8: stages 1 and 2 on the fp32 MFMA too
     if (rc != VP_OK) return rc;
   }
   // bit 3 keeps encoder.3 .. .6 as four launches
-  if (!(net.cfg.plan_flags[7] & 8)) {
-    int rc = (net.cfg.plan_flags[7] & 128) ? plan_eqt_fuse_enc36(net) : plan_eqt_fuse_enc36_b3(net);  // bit 7: the fp32-MFMA kernel
+  if (!pf::eqt(cfg, pf::EQT_ENC36_LAYERS)) {
+    int rc = pf::eqt(cfg, pf::EQT_ENC36_FP32) ? plan_eqt_fuse_enc36(net) : plan_eqt_fuse_enc36_b3(net);  // bit 7: the fp32-MFMA kernel
     if (rc != VP_OK) return rc;
   }
   // bit 1 keeps decoder.0 .. .3 (+ the stage-2 edge fix) as five launches
-  if (!(net.cfg.plan_flags[7] & 2)) {
-    int rc = plan_eqt_fuse_dec03(net, !(net.cfg.plan_flags[7] & 32));  // bit 5: every stage on the fp32 MFMA
+  if (!pf::eqt(cfg, pf::EQT_DEC03_LAYERS)) {
+    int rc = plan_eqt_fuse_dec03(net, !pf::eqt(cfg, pf::EQT_DEC03_FP32));  // bit 5: every stage on the fp32 MFMA
     if (rc != VP_OK) return rc;
   }
   return VP_OK;

@@ -507,24 +507,14 @@ __global__ __launch_bounds__(D03_NTH) void eqt_dec03_kernel(const std::condition
 
 // Replaces the steps "decoder.0", "decoder.1", "decoder.2", "decoder.2.edge", "decoder.3" of the plan by one fused step.
 int plan_eqt_fuse_dec03(Net& net, bool b3) {
-  int first = -1;
-  for (size_t i = 0; i < net.steps.size(); ++i)
-    if (net.steps[i].name == "decoder.0") first = (int)i;
-  if (first < 0 || first + 5 > (int)net.steps.size() || net.steps[first + 3].name != "decoder.2.edge" ||
-      net.steps[first + 4].name != "decoder.3") {
-    set_error("fused decoder stages 0-3: layer plan not found");
-    return VP_ERR_INVALID;
-  }
-  ConvLayer* c[4] = {nullptr, nullptr, nullptr, nullptr};
-  for (auto& l : net.convs)
-    for (int i = 0; i < 4; ++i)
-      if (l->name == "decoder." + std::to_string(i)) c[i] = l.get();
+  const char* label = "fused decoder stages 0-3";
+  FuseSite site;
+  if (int rc = find_fuse_site(net, label, "decoder.0", 5, "decoder.3", false, &site, "decoder.2.edge")) return rc;
+  ConvLayer* c[4];
+  const int missing = find_convs(net, {"decoder.0", "decoder.1", "decoder.2", "decoder.3"}, c);
   HostBlob* ew = net.named.count("decoder.2.edge.w") ? net.named["decoder.2.edge.w"] : nullptr;
   HostBlob* eb = net.named.count("decoder.2.edge.b") ? net.named["decoder.2.edge.b"] : nullptr;
-  if (!c[0] || !c[1] || !c[2] || !c[3] || !ew || !eb || c[0]->n_sets != 3) {
-    set_error("fused decoder stages 0-3: conv layers missing");
-    return VP_ERR_INVALID;
-  }
+  if (missing >= 0 || !ew || !eb || c[0]->n_sets != 3) return fuse_fail(label, "conv layers missing");
   HostBlob* q[4];
   for (int i = 0; i < 4; ++i) q[i] = c[i]->afrag_q4 ? c[i]->afrag_q4 : net.add_blob(regroup_afrag4(*c[i]));
   HostBlob* p3[3] = {nullptr, nullptr, nullptr};
@@ -534,17 +524,17 @@ int plan_eqt_fuse_dec03(Net& net, bool b3) {
   }
   const int x_in = c[0]->src1, y_out = c[3]->dst;
   // stages 0-2 live in LDS under this plan; plan_flags[1] & 4 keeps them (3 sets) for the DUMP instance
-  const bool dumps = (net.cfg.plan_flags[1] & 4) != 0;
+  const int dbg[3] = {c[0]->dst, c[1]->dst, c[2]->dst};
+  const bool dumps = pf::layer_dumps(net.cfg);
   if (dumps && !b3) {
     set_error("fused decoder stages 0-3: dumps exist for the bf16-piece form only");
     return VP_ERR_UNSUPPORTED;
   }
   if (!dumps)
-    for (int i = 0; i < 3; ++i) net.tensor_sets[c[i]->dst] = 0;
+    for (int i = 0; i < 3; ++i) net.tensor_sets[dbg[i]] = 0;
   Step st;
   st.name = "fused.dec03 (decoder.0-3, one row per workgroup)";
-  st.flops_per_window = 0;
-  for (int i = 0; i < 5; ++i) st.flops_per_window += net.steps[first + i].flops_per_window;
+  st.flops_per_window = site.flops_per_window;
   // issued MFMA work per row: 8 m-tiles x 3 n-tiles x 12 K-steps, 8 x 6 x 48, 4 x 12 x 48, 4 x 24 x 40 (2048 FLOP each)
   // (B3: stages 1-3 as six-MFMA groups over K = 32: an eighth of the fp32 K-steps; the two edge samples of stage 2: VALU, not counted)
   if (b3)
@@ -553,13 +543,8 @@ int plan_eqt_fuse_dec03(Net& net, bool b3) {
     st.set_issued(3.0 * (8.0 * 3 * 12 + 8.0 * 6 * 48 + 4.0 * 12 * 48 + 4.0 * 24 * 40) * 2048.0, 0.0, 0.0);
   st.run = [=](Net& n, int B, hipStream_t s) -> int {
     Dec03Args a{};
-    const Tensor &tx = n.tensors[x_in], &ty = n.tensors[y_out];
-    a.x = tx.p;
-    a.ls_x = tx.ls;
-    a.ws_x = (long)tx.win_stride();
-    a.y = ty.p;
-    a.ls_y = ty.ls;
-    a.ws_y = (long)ty.win_stride();
+    bind(a.x, a.ls_x, a.ws_x, n.tensors[x_in]);
+    bind(a.y, a.ls_y, a.ws_y, n.tensors[y_out]);
     for (int i = 0; i < 4; ++i) {
       a.af[i] = q[i]->d;
       a.bs[i] = c[i]->bias.d;
@@ -569,8 +554,8 @@ int plan_eqt_fuse_dec03(Net& net, bool b3) {
     a.edge_b = eb->d;
     a.B = B;
     a.n_rows = 3 * B;
-    a.even_split = (n.cfg.plan_flags[7] >> 11) & 1;
-    a.clk = (n.debug_clock && n.debug_clock->d) ? reinterpret_cast<unsigned long long*>(n.debug_clock->d) + (size_t)n.max_batch * 32 : nullptr;
+    a.even_split = pf::eqt(n.cfg, pf::EQT_DEC03_EVEN);
+    a.clk = clock_words(n, ClockRegions(n.max_batch).conv);
     const int grid = a.n_rows < 256 ? a.n_rows : 256;
     if (b3) {
       for (int i = 0; i < 3; ++i) {
@@ -580,12 +565,7 @@ int plan_eqt_fuse_dec03(Net& net, bool b3) {
       if (dumps) {
         Dec03DumpArgs dd{};
         static_cast<Dec03Args&>(dd) = a;
-        for (int i = 0; i < 3; ++i) {
-          const Tensor& t = n.tensors[c[i]->dst];
-          dd.dbg[i] = t.p;
-          dd.dbg_ls[i] = t.ls;
-          dd.dbg_ws[i] = (long)t.win_stride();
-        }
+        bind_dbg(dd.dbg, dd.dbg_ls, dd.dbg_ws, n, dbg);
         hipLaunchKernelGGL((eqt_dec03_kernel<true, true>), dim3(grid), dim3(D03_NTH), B3_LDS_BYTES, s, dd);
       } else {
         hipLaunchKernelGGL(eqt_dec03_kernel<true>, dim3(grid), dim3(D03_NTH), B3_LDS_BYTES, s, a);
@@ -601,8 +581,7 @@ int plan_eqt_fuse_dec03(Net& net, bool b3) {
     net.extra_kernels.push_back({reinterpret_cast<const void*>(&eqt_dec03_kernel<false>), D03_LDS_FLOATS * sizeof(float)});
   if (dumps)
     net.extra_kernels.push_back({reinterpret_cast<const void*>(&eqt_dec03_kernel<true, true>), (size_t)B3_LDS_BYTES});
-  net.steps.erase(net.steps.begin() + first, net.steps.begin() + first + 5);
-  net.steps.insert(net.steps.begin() + first, std::move(st));
+  replace_steps(net, site, std::move(st));
   return VP_OK;
 }
 

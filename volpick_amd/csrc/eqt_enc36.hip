@@ -183,21 +183,12 @@ __global__ __launch_bounds__(E36_NTH) void eqt_enc36_kernel(const Enc36Args a) {
 
 // Replaces the steps "encoder.3" .. "encoder.6" of the plan by one fused step.
 int plan_eqt_fuse_enc36(Net& net) {
-  int first = -1;
-  for (size_t i = 0; i < net.steps.size(); ++i)
-    if (net.steps[i].name == "encoder.3") first = (int)i;
-  if (first < 0 || first + 4 > (int)net.steps.size() || net.steps[first + 3].name != "encoder.6") {
-    set_error("fused encoder stages 3-6: layer plan not found");
-    return VP_ERR_INVALID;
-  }
-  ConvLayer* c[4] = {nullptr, nullptr, nullptr, nullptr};
-  for (auto& l : net.convs)
-    for (int i = 0; i < 4; ++i)
-      if (l->name == "encoder." + std::to_string(i + 3)) c[i] = l.get();
-  if (!c[0] || !c[1] || !c[2] || !c[3] || c[3]->dst2 < 0) {
-    set_error("fused encoder stages 3-6: conv layers missing");
-    return VP_ERR_INVALID;
-  }
+  const char* label = "fused encoder stages 3-6";
+  FuseSite site;
+  if (int rc = find_fuse_site(net, label, "encoder.3", 4, "encoder.6", false, &site)) return rc;
+  ConvLayer* c[4];
+  if (find_convs(net, {"encoder.3", "encoder.4", "encoder.5", "encoder.6"}, c) >= 0 || c[3]->dst2 < 0)
+    return fuse_fail(label, "conv layers missing");
   HostBlob* q[4];
   for (int i = 0; i < 4; ++i) q[i] = c[i]->afrag_q4 ? c[i]->afrag_q4 : net.add_blob(regroup_afrag4(*c[i]));
   const int x_in = c[0]->src1, y_out = c[3]->dst, act_out = c[3]->dst2;
@@ -205,22 +196,14 @@ int plan_eqt_fuse_enc36(Net& net) {
   for (int i = 0; i < 3; ++i) net.tensor_sets[c[i]->dst] = 0;  // encoder.3 - .5 live in LDS under this plan
   Step st;
   st.name = "fused.enc36 (encoder.3-6, one window per workgroup)";
-  st.flops_per_window = 0;
-  for (int i = 0; i < 4; ++i) st.flops_per_window += net.steps[first + i].flops_per_window;
+  st.flops_per_window = site.flops_per_window;
   // issued MFMA work: 2 m-tiles x 48 n-tiles x 28 K-steps, 2 x 24 x 40, 4 x 12 x 40, 4 x 6 x 48 (2048 FLOP each)
   st.set_issued((2.0 * 48 * 28 + 2.0 * 24 * 40 + 4.0 * 12 * 40 + 4.0 * 6 * 48) * 2048.0, 0.0, 0.0);
   st.run = [=](Net& n, int B, hipStream_t s) -> int {
     Enc36Args a{};
-    const Tensor &tx = n.tensors[x_in], &ty = n.tensors[y_out], &ta = n.tensors[act_out];
-    a.x = tx.p;
-    a.ls_x = tx.ls;
-    a.ws_x = (long)tx.win_stride();
-    a.y = ty.p;
-    a.ls_y = ty.ls;
-    a.ws_y = (long)ty.win_stride();
-    a.act = ta.p;
-    a.ls_a = ta.ls;
-    a.ws_a = (long)ta.win_stride();
+    bind(a.x, a.ls_x, a.ws_x, n.tensors[x_in]);
+    bind(a.y, a.ls_y, a.ws_y, n.tensors[y_out]);
+    bind(a.act, a.ls_a, a.ws_a, n.tensors[act_out]);
     for (int i = 0; i < 4; ++i) {
       a.af[i] = q[i]->d;
       a.bs[i] = c[i]->bias.d;
@@ -233,8 +216,7 @@ int plan_eqt_fuse_enc36(Net& net) {
     return 0;
   };
   net.extra_kernels.push_back({reinterpret_cast<const void*>(&eqt_enc36_kernel), E36_LDS_FLOATS * sizeof(float)});
-  net.steps.erase(net.steps.begin() + first, net.steps.begin() + first + 4);
-  net.steps.insert(net.steps.begin() + first, std::move(st));
+  replace_steps(net, site, std::move(st));
   return VP_OK;
 }
 

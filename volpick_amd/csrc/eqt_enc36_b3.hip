@@ -247,53 +247,35 @@ __global__ __launch_bounds__(E3_NTH) void eqt_enc36_b3_kernel(const std::conditi
 
 // Replaces the steps "encoder.3" .. "encoder.6" of the plan by one fused step (bf16-piece form).
 int plan_eqt_fuse_enc36_b3(Net& net) {
-  int first = -1;
-  for (size_t i = 0; i < net.steps.size(); ++i)
-    if (net.steps[i].name == "encoder.3") first = (int)i;
-  if (first < 0 || first + 4 > (int)net.steps.size() || net.steps[first + 3].name != "encoder.6") {
-    set_error("fused encoder stages 3-6: layer plan not found");
-    return VP_ERR_INVALID;
-  }
-  ConvLayer* c[4] = {nullptr, nullptr, nullptr, nullptr};
-  for (auto& l : net.convs)
-    for (int i = 0; i < 4; ++i)
-      if (l->name == "encoder." + std::to_string(i + 3)) c[i] = l.get();
+  const char* label = "fused encoder stages 3-6";
+  FuseSite site;
+  if (int rc = find_fuse_site(net, label, "encoder.3", 4, "encoder.6", false, &site)) return rc;
+  ConvLayer* c[4];
+  if (find_convs(net, {"encoder.3", "encoder.4", "encoder.5", "encoder.6"}, c) >= 0 || c[3]->dst2 < 0)
+    return fuse_fail(label, "conv layers missing");
   const int cin[4] = {16, 32, 32, 64}, taps[4] = {7, 5, 5, 3}, mrows[4] = {32, 32, 64, 64};
-  if (!c[0] || !c[1] || !c[2] || !c[3] || c[3]->dst2 < 0) {
-    set_error("fused encoder stages 3-6: conv layers missing");
-    return VP_ERR_INVALID;
-  }
   for (int i = 0; i < 4; ++i)
-    if (c[i]->g.cinp() != cin[i] || c[i]->g.taps != taps[i] || c[i]->g.M() != mrows[i] || c[i]->g.P != 1) {
-      set_error("fused encoder stages 3-6: unexpected layer shape");
-      return VP_ERR_INVALID;
-    }
+    if (c[i]->g.cinp() != cin[i] || c[i]->g.taps != taps[i] || c[i]->g.M() != mrows[i] || c[i]->g.P != 1)
+      return fuse_fail(label, "unexpected layer shape");
   HostBlob* p3[4];
   for (int i = 0; i < 4; ++i) p3[i] = net.add_blob(b3_operand(*c[i], false));
   const int x_in = c[0]->src1, y_out = c[3]->dst, act_out = c[3]->dst2;
+  const int dbg[3] = {c[0]->dst, c[1]->dst, c[2]->dst};
   net.need(x_in, HALO - K3 + NC3);  // the image row is fetched whole: zero margin up to there
   // encoder.3 - .5 live in LDS under this plan; plan_flags[1] & 4 keeps them for the DUMP instance
-  const bool dumps = (net.cfg.plan_flags[1] & 4) != 0;
+  const bool dumps = pf::layer_dumps(net.cfg);
   if (!dumps)
-    for (int i = 0; i < 3; ++i) net.tensor_sets[c[i]->dst] = 0;
+    for (int i = 0; i < 3; ++i) net.tensor_sets[dbg[i]] = 0;
   Step st;
   st.name = "fused.enc36 (encoder.3-6, one window per workgroup)";
-  st.flops_per_window = 0;
-  for (int i = 0; i < 4; ++i) st.flops_per_window += net.steps[first + i].flops_per_window;
+  st.flops_per_window = site.flops_per_window;
   // matrix work issued, as fp32-equivalent FLOP: one group of six bf16 MFMAs = one 16 x 16 x 32 fp32-accurate product
   st.set_issued(0.0, (2.0 * 48 * 4 + 2.0 * 24 * 5 + 4.0 * 12 * 5 + 4.0 * 6 * 6) * 6 * 16384.0, 0.0);  // 1008 groups = 6048 MFMAs
   st.run = [=](Net& n, int B, hipStream_t s) -> int {
     Enc36B3Args a{};
-    const Tensor &tx = n.tensors[x_in], &ty = n.tensors[y_out], &ta = n.tensors[act_out];
-    a.x = tx.p;
-    a.ls_x = tx.ls;
-    a.ws_x = (long)tx.win_stride();
-    a.y = ty.p;
-    a.ls_y = ty.ls;
-    a.ws_y = (long)ty.win_stride();
-    a.act = ta.p;
-    a.ls_a = ta.ls;
-    a.ws_a = (long)ta.win_stride();
+    bind(a.x, a.ls_x, a.ws_x, n.tensors[x_in]);
+    bind(a.y, a.ls_y, a.ws_y, n.tensors[y_out]);
+    bind(a.act, a.ls_a, a.ws_a, n.tensors[act_out]);
     for (int i = 0; i < 4; ++i) {
       a.af3[i] = reinterpret_cast<const uint4*>(p3[i]->d);
       a.bs[i] = c[i]->bias.d;
@@ -305,12 +287,7 @@ int plan_eqt_fuse_enc36_b3(Net& net) {
     if (dumps) {
       Enc36B3DumpArgs d{};
       static_cast<Enc36B3Args&>(d) = a;
-      for (int i = 0; i < 3; ++i) {
-        const Tensor& t = n.tensors[c[i]->dst];
-        d.dbg[i] = t.p;
-        d.dbg_ls[i] = t.ls;
-        d.dbg_ws[i] = (long)t.win_stride();
-      }
+      bind_dbg(d.dbg, d.dbg_ls, d.dbg_ws, n, dbg);
       hipLaunchKernelGGL(eqt_enc36_b3_kernel<true>, dim3(grid), dim3(E3_NTH), E3_LDS_BYTES, s, d);
     } else {
       hipLaunchKernelGGL(eqt_enc36_b3_kernel<false>, dim3(grid), dim3(E3_NTH), E3_LDS_BYTES, s, a);
@@ -319,8 +296,7 @@ int plan_eqt_fuse_enc36_b3(Net& net) {
   };
   net.extra_kernels.push_back({reinterpret_cast<const void*>(&eqt_enc36_b3_kernel<false>), (size_t)E3_LDS_BYTES});
   if (dumps) net.extra_kernels.push_back({reinterpret_cast<const void*>(&eqt_enc36_b3_kernel<true>), (size_t)E3_LDS_BYTES});
-  net.steps.erase(net.steps.begin() + first, net.steps.begin() + first + 4);
-  net.steps.insert(net.steps.begin() + first, std::move(st));
+  replace_steps(net, site, std::move(st));
   return VP_OK;
 }
 

@@ -528,44 +528,32 @@ __global__ __launch_bounds__(FR_NTH) void eqt_front_kernel(const std::conditiona
 
 // Replaces the steps "encoder.0", "encoder.1", "encoder.2" of the plan by one fused step.
 int plan_eqt_fuse_front(Net& net, bool b3) {
-  int first = -1;
-  for (size_t i = 0; i < net.steps.size(); ++i)
-    if (net.steps[i].name == "encoder.0") first = (int)i;
-  if (first < 0 || first + 3 > (int)net.steps.size() || net.steps[first + 2].name != "encoder.2") {
-    set_error("fused encoder front: layer plan not found");
-    return VP_ERR_INVALID;
-  }
-  ConvLayer* c[3] = {nullptr, nullptr, nullptr};
-  for (auto& l : net.convs)
-    for (int i = 0; i < 3; ++i)
-      if (l->name == "encoder." + std::to_string(i)) c[i] = l.get();
-  if (!c[0] || !c[1] || !c[2]) {
-    set_error("fused encoder front: conv layers missing");
-    return VP_ERR_INVALID;
-  }
+  const char* label = "fused encoder front";
+  FuseSite site;
+  if (int rc = find_fuse_site(net, label, "encoder.0", 3, "encoder.2", false, &site)) return rc;
+  ConvLayer* c[3];
+  if (find_convs(net, {"encoder.0", "encoder.1", "encoder.2"}, c) >= 0) return fuse_fail(label, "conv layers missing");
   HostBlob* p3[2] = {nullptr, nullptr};
   if (b3) {
-    if (c[1]->g.cinp() != 8 || c[1]->g.taps != 9 || c[1]->g.M() != 16 || c[2]->g.cinp() != 16 || c[2]->g.taps != 7 || c[2]->g.M() != 16) {
-      set_error("fused encoder front: unexpected layer shape");
-      return VP_ERR_INVALID;
-    }
+    if (c[1]->g.cinp() != 8 || c[1]->g.taps != 9 || c[1]->g.M() != 16 || c[2]->g.cinp() != 16 || c[2]->g.taps != 7 || c[2]->g.M() != 16)
+      return fuse_fail(label, "unexpected layer shape");
     for (int i = 0; i < 2; ++i) p3[i] = net.add_blob(b3_operand(*c[1 + i], false));
   }
   const int x_in = c[0]->src1, y_out = c[2]->dst;
   // encoder.0 / .1 live in LDS under this plan; plan_flags[1] & 4 keeps them for the DUMP instance
-  const bool dumps = (net.cfg.plan_flags[1] & 4) != 0;
-  if (dumps && (!b3 || net.cfg.plan_flags[6] == 2)) {
+  const int dbg[2] = {c[0]->dst, c[1]->dst};
+  const bool dumps = pf::layer_dumps(net.cfg), cuts_windows = pf::get(net.cfg, pf::PRE) == pf::PRE_EQT_FRONT;
+  if (dumps && (!b3 || cuts_windows)) {
     set_error("fused encoder front: dumps exist for the bf16-piece form reading the input tensor only");
     return VP_ERR_UNSUPPORTED;
   }
   if (!dumps) {
-    net.tensor_sets[c[0]->dst] = 0;
-    net.tensor_sets[c[1]->dst] = 0;
+    net.tensor_sets[dbg[0]] = 0;
+    net.tensor_sets[dbg[1]] = 0;
   }
   Step st;
   st.name = "fused.front (encoder.0-2, time-tiled)";
-  st.flops_per_window = 0;
-  for (int i = 0; i < 3; ++i) st.flops_per_window += net.steps[first + i].flops_per_window;
+  st.flops_per_window = site.flops_per_window;
   // per tile: stage 0 64 n-tiles x 12 K-steps of fp32 MFMAs; stages 1 / 2 64 x 18 and 32 x 28 fp32 MFMAs, or (bf16 pieces) 64 n-tiles x
   // 3 K-steps and 32 x 4 K-steps of six-MFMA groups
   if (b3)
@@ -574,13 +562,8 @@ int plan_eqt_fuse_front(Net& net, bool b3) {
     st.set_issued(FR_TILES * (64.0 * 12 + 64.0 * 18 + 32.0 * 28) * 2048.0, 0.0, 0.0);
   st.run = [=](Net& n, int B, hipStream_t s) -> int {
     FrontArgs a{};
-    const Tensor &tx = n.tensors[x_in], &ty = n.tensors[y_out];
-    a.x = tx.p;
-    a.ls_x = tx.ls;
-    a.ws_x = (long)tx.win_stride();
-    a.y = ty.p;
-    a.ls_y = ty.ls;
-    a.ws_y = (long)ty.win_stride();
+    bind(a.x, a.ls_x, a.ws_x, n.tensors[x_in]);
+    bind(a.y, a.ls_y, a.ws_y, n.tensors[y_out]);
     for (int i = 0; i < 3; ++i) {
       a.af[i] = c[i]->afrag.d;
       a.bs[i] = c[i]->bias.d;
@@ -601,12 +584,7 @@ int plan_eqt_fuse_front(Net& net, bool b3) {
         }
         FrontDumpArgs d{};
         static_cast<FrontArgs&>(d) = a;
-        for (int i = 0; i < 2; ++i) {
-          const Tensor& t = n.tensors[c[i]->dst];
-          d.dbg[i] = t.p;
-          d.dbg_ls[i] = t.ls;
-          d.dbg_ws[i] = (long)t.win_stride();
-        }
+        bind_dbg(d.dbg, d.dbg_ls, d.dbg_ws, n, dbg);
         hipLaunchKernelGGL((eqt_front_kernel<true, false, true>), dim3(grid), dim3(FR_NTH), FB_LDS_BYTES, s, d);
       } else if (a.has_pre)
         hipLaunchKernelGGL((eqt_front_kernel<true, true>), dim3(grid), dim3(FR_NTH), FB_LDS_BYTES, s, a);
@@ -628,15 +606,14 @@ int plan_eqt_fuse_front(Net& net, bool b3) {
     net.extra_kernels.push_back({reinterpret_cast<const void*>(&eqt_front_kernel<false, true>), FR_LDS_FLOATS * sizeof(float)});
     net.extra_kernels.push_back({reinterpret_cast<const void*>(&eqt_front_kernel<false, false>), FR_LDS_FLOATS * sizeof(float)});
   }
-  net.steps.erase(net.steps.begin() + first, net.steps.begin() + first + 3);
-  net.steps.insert(net.steps.begin() + first, std::move(st));
+  replace_steps(net, site, std::move(st));
   // plan_flags[6] = 2: the kernel cuts its windows out of the raw stream and normalises them itself (no gather_normalize launch,
   // no input tensor: -13 us of small kernels and 37 MB per step).  NOT the default: the statistics of a window (one pass over
   // its 72 KB, two barriers) and the 13 divisions per thread and tile stand in front of the first MFMA of every workgroup and
   // cost the kernel 8.6 us (34.3 -> 42.9), while the small launches they replace mostly hide in the tails of the big
   // kernels: 728 k against 736 k windows/s end to end (profiles/r03_eqt_front_cuts_its_windows_ab.txt).  Kept for that A/B
   // and for the bitwise test of the in-kernel arithmetic.
-  net.fused_pre = first == 0 && net.cfg.plan_flags[6] == 2;
+  net.fused_pre = site.first == 0 && cuts_windows;
   return VP_OK;
 }
 

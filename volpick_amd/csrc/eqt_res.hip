@@ -737,70 +737,26 @@ __global__ __launch_bounds__(512) void eqt_res3t_kernel(const std::conditional_t
 // (eqt_res3k_kernel -- eight waves per window, K split over wave pairs with a partial-sum exchange through LDS; round 2's default,
 // 31.5 us on 256 CUs against 44.5 us on 128 -- was removed in round 6: plan_flags[7] bit 12 is rejected.)
 
-// fp32 MFMA-order fragments [mt][cb][tap][64] (pack_afrag) -> three-piece bf16 operand [mt][tap * 2 + half][piece][64][8]
-std::vector<float> res3_operand(const ConvLayer& L, int taps) {
-  constexpr int CB = 16;
-  auto rne = [](float x) -> uint16_t {
-    uint32_t u;
-    memcpy(&u, &x, 4);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-  };
-  auto widen = [](uint16_t h) -> float {
-    const uint32_t u = (uint32_t)h << 16;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-  };
-  std::vector<uint16_t> o((size_t)4 * taps * 2 * 3 * 64 * 8);
-  const std::vector<float>& af = L.afrag.h;
-  for (int mt = 0; mt < 4; ++mt)
-    for (int tap = 0; tap < taps; ++tap)
-      for (int half = 0; half < 2; ++half)
-        for (int l = 0; l < 64; ++l)
-          for (int i = 0; i < 8; ++i) {
-            const int ci = half * 32 + 8 * (l >> 4) + i, m = l & 15;
-            const float w = af[(((size_t)mt * CB + ci / 4) * taps + tap) * 64 + (ci % 4) * 16 + m];
-            const uint16_t h = rne(w);
-            const float r1 = w - widen(h);
-            const uint16_t md = rne(r1);
-            const uint16_t lo = rne(r1 - widen(md));
-            const size_t base = ((((size_t)mt * taps * 2 + tap * 2 + half) * 3) * 64 + l) * 8 + i;
-            o[base] = h;
-            o[base + 64 * 8] = md;
-            o[base + 2 * 64 * 8] = lo;
-          }
-  std::vector<float> f(o.size() / 2);
-  memcpy(f.data(), o.data(), o.size() * 2);
-  return f;
-}
-
 }  // namespace
 
 // Replaces the steps "res0.conv1" .. "res6.conv2" of the layer plan by one fused step.
 int plan_eqt_fuse_res(Net& net) {
-  if (net.cfg.plan_flags[7] & 4096) {
+  if (pf::eqt(net.cfg, pf::EQT_RES_KSPLIT)) {
     set_error("EQTransformer plan_flags[7] bit 12 (ResCNN kernel with K split over wave pairs): removed in round 6");
     return VP_ERR_UNSUPPORTED;
   }
-  int first = -1;
-  for (size_t i = 0; i < net.steps.size(); ++i)
-    if (net.steps[i].name == "res0.conv1") first = (int)i;
-  if (first < 0 || first + 14 > (int)net.steps.size() || net.steps[first + 13].name != "res6.conv2") {
-    set_error("fused ResCNN: layer plan not found");
+  FuseSite site;
+  if (int rc = find_fuse_site(net, "fused ResCNN", "res0.conv1", 14, "res6.conv2", false, &site)) return rc;
+  std::vector<std::string> names;
+  for (int i = 0; i < 7; ++i)
+    for (const char* conv : {".conv1", ".conv2"}) names.push_back("res" + std::to_string(i) + conv);
+  ConvLayer* c[14];
+  if (const int missing = find_convs(net, names, c); missing >= 0) {
+    set_error("fused ResCNN: conv layer %d missing", missing / 2);
     return VP_ERR_INVALID;
   }
   std::vector<ConvLayer*> c1(7), c2(7);
-  for (auto& c : net.convs)
-    for (int i = 0; i < 7; ++i) {
-      if (c->name == "res" + std::to_string(i) + ".conv1") c1[i] = c.get();
-      if (c->name == "res" + std::to_string(i) + ".conv2") c2[i] = c.get();
-    }
-  for (int i = 0; i < 7; ++i)
-    if (!c1[i] || !c2[i]) {
-      set_error("fused ResCNN: conv layer %d missing", i);
-      return VP_ERR_INVALID;
-    }
+  for (int i = 0; i < 7; ++i) c1[i] = c[2 * i], c2[i] = c[2 * i + 1];
   const int x0 = c2[0]->res, act0 = c1[0]->src1, out = c2[6]->dst;
   // every workgroup streams the 690 KB of weights out of L2: as 16-byte loads per lane (conv_lds_q4, micro_stream.hip)
   std::vector<HostBlob*> q1(7), q2(7);
@@ -810,23 +766,22 @@ int plan_eqt_fuse_res(Net& net) {
   }
   // default: the 14 convs on the bf16 matrix cores with exact three-piece operands (eqt_res3_kernel); plan_flags[7] bit 4
   // keeps the fp32-MFMA kernel (A/B timing; the two agree to fp32 rounding, not bitwise)
-  const bool bf3 = !(net.cfg.plan_flags[7] & 16);
+  const bool bf3 = !pf::eqt(net.cfg, pf::EQT_RES_FP32);
   std::vector<HostBlob*> b1(7, nullptr), b2(7, nullptr);
   if (bf3)
     for (int i = 0; i < 7; ++i) {
-      b1[i] = net.add_blob(res3_operand(*c1[i], c1[i]->g.taps));
-      b2[i] = net.add_blob(res3_operand(*c2[i], c2[i]->g.taps));
+      b1[i] = net.add_blob(res3_operand(c1[i]->afrag.h, c1[i]->g.taps));
+      b2[i] = net.add_blob(res3_operand(c2[i]->afrag.h, c2[i]->g.taps));
     }
   // plan_flags[1] & 4 (plan_eqt checked that the plan is the default one): the DUMP instance and the tensors it writes
-  const bool dumps = (net.cfg.plan_flags[1] & 4) != 0;
+  const bool dumps = pf::layer_dumps(net.cfg);
   std::vector<int> dbg;
   if (dumps)
     for (int i = 0; i < 7; ++i)
       for (const char* what : {".mid", ".conv2", ".out"}) dbg.push_back(net.add_tensor("res." + std::to_string(i) + what, 64, EQT_T));
   Step st;
   st.name = "fused.rescnn (7 residual blocks)";
-  st.flops_per_window = 0;
-  for (int i = 0; i < 14; ++i) st.flops_per_window += net.steps[first + i].flops_per_window;
+  st.flops_per_window = site.flops_per_window;
   {  // 4 m-tiles x 3 n-tiles per conv; K = 64 channels x taps: 16 x taps fp32 K-steps, or 2 x taps six-MFMA groups
     double taps = 0;
     for (int i = 0; i < 7; ++i) taps += c1[i]->g.taps + c2[i]->g.taps;
@@ -835,34 +790,31 @@ int plan_eqt_fuse_res(Net& net) {
     else
       st.set_issued(12.0 * 16 * taps * 2048.0, 0.0, 0.0);
   }
+  // what ResArgs and Res3Args have in common, field for field
+  auto bind_common = [=](auto& a, const Net& n) {
+    bind(a.x0, a.ls_x, a.ws_x, n.tensors[x0]);
+    bind(a.act0, a.ls_a, a.ws_a, n.tensors[act0]);
+    bind(a.out, a.ls_out, a.ws_out, n.tensors[out]);
+    for (int i = 0; i < 7; ++i) {
+      a.bs1[i] = c1[i]->bias.d;
+      a.bs2[i] = c2[i]->bias.d;
+      a.s_next[i] = c2[i]->e1.d;
+      a.b_next[i] = c2[i]->e2.d;
+    }
+  };
   if (bf3) {
     st.run = [=](Net& n, int B, hipStream_t s) -> int {
       Res3Args a{};
-      const Tensor &tx = n.tensors[x0], &ta = n.tensors[act0], &to = n.tensors[out];
-      a.x0 = tx.p;
-      a.act0 = ta.p;
-      a.ls_x = tx.ls;
-      a.ws_x = (long)tx.win_stride();
-      a.ls_a = ta.ls;
-      a.ws_a = (long)ta.win_stride();
-      a.out = to.p;
-      a.ls_out = to.ls;
-      a.ws_out = (long)to.win_stride();
+      bind_common(a, n);
       for (int i = 0; i < 7; ++i) {
         a.af1[i] = reinterpret_cast<const uint4*>(b1[i]->d);
-        a.bs1[i] = c1[i]->bias.d;
         a.af2[i] = reinterpret_cast<const uint4*>(b2[i]->d);
-        a.bs2[i] = c2[i]->bias.d;
-        a.s_next[i] = c2[i]->e1.d;
-        a.b_next[i] = c2[i]->e2.d;
       }
       a.af_bytes_k3 = 4L * 3 * 2 * 3 * 64 * 16;
       a.af_bytes_k2 = 4L * 2 * 2 * 3 * 64 * 16;
-      a.warm = n.cfg.plan_flags[4] != 1;
+      a.warm = pf::warm(n.cfg);
       a.n_windows = B;
-      a.clk = (n.debug_clock && n.debug_clock->d)  // the conv launches' region: unused under the fused plan
-                  ? reinterpret_cast<unsigned long long*>(n.debug_clock->d) + (size_t)n.max_batch * 32
-                  : nullptr;
+      a.clk = clock_words(n, ClockRegions(n.max_batch).conv);  // the conv launches' region: unused under the fused plan
       if (dumps) {
         Res3DumpArgs d{};
         static_cast<Res3Args&>(d) = a;
@@ -877,40 +829,27 @@ int plan_eqt_fuse_res(Net& net) {
           d.dbg[i] = t.p;
         }
         hipLaunchKernelGGL(eqt_res3t_kernel<true>, dim3((B + 2) / 3), dim3(512), 0, s, d);
-      } else if (n.cfg.plan_flags[7] & 512)  // bit 9: four waves per window, one window per workgroup
+      } else if (pf::eqt(n.cfg, pf::EQT_RES_ONE_WINDOW))  // bit 9: four waves per window, one window per workgroup
         hipLaunchKernelGGL(eqt_res3_kernel<1>, dim3(B), dim3(256), 0, s, a);
-      else if (n.cfg.plan_flags[7] & 8192)  // bit 13: four waves per window, two windows per workgroup (rounds 5-6: 45 us on 128 CUs)
+      else if (pf::eqt(n.cfg, pf::EQT_RES_TWO_WINDOWS))  // bit 13: four waves per window, two windows per workgroup (rounds 5-6: 45 us on 128 CUs)
         hipLaunchKernelGGL(eqt_res3_kernel<2>, dim3((B + 1) / 2), dim3(512), 0, s, a);
       else  // eight waves per THREE windows
         hipLaunchKernelGGL(eqt_res3t_kernel<false>, dim3((B + 2) / 3), dim3(512), 0, s, a);
       return 0;
     };
-  } else
-  st.run = [=](Net& n, int B, hipStream_t s) -> int {
-    ResArgs a{};
-    const Tensor &tx = n.tensors[x0], &ta = n.tensors[act0], &to = n.tensors[out];
-    a.x0 = tx.p;
-    a.act0 = ta.p;
-    a.ls_x = tx.ls;
-    a.ws_x = (long)tx.win_stride();
-    a.ls_a = ta.ls;
-    a.ws_a = (long)ta.win_stride();
-    a.out = to.p;
-    a.ls_out = to.ls;
-    a.ws_out = (long)to.win_stride();
-    for (int i = 0; i < 7; ++i) {
-      a.af1[i] = q1[i]->d;
-      a.bs1[i] = c1[i]->bias.d;
-      a.af2[i] = q2[i]->d;
-      a.bs2[i] = c2[i]->bias.d;
-      a.s_next[i] = c2[i]->e1.d;
-      a.b_next[i] = c2[i]->e2.d;
-    }
-    hipLaunchKernelGGL(eqt_res_kernel, dim3(B), dim3(256), 0, s, a);
-    return 0;
-  };
-  net.steps.erase(net.steps.begin() + first, net.steps.begin() + first + 14);
-  net.steps.insert(net.steps.begin() + first, std::move(st));
+  } else {
+    st.run = [=](Net& n, int B, hipStream_t s) -> int {
+      ResArgs a{};
+      bind_common(a, n);
+      for (int i = 0; i < 7; ++i) {
+        a.af1[i] = q1[i]->d;
+        a.af2[i] = q2[i]->d;
+      }
+      hipLaunchKernelGGL(eqt_res_kernel, dim3(B), dim3(256), 0, s, a);
+      return 0;
+    };
+  }
+  replace_steps(net, site, std::move(st));
   return VP_OK;
 }
 

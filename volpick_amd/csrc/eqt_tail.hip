@@ -302,23 +302,12 @@ __global__ __launch_bounds__(TAIL_NTH) void eqt_tail_kernel(const TailArgs a) {
 
 // Replaces the steps "decoder.4", "decoder.5", "decoder.6+heads" of the plan by one fused step.
 int plan_eqt_fuse_tail(Net& net) {
-  int first = -1;
-  for (size_t i = 0; i < net.steps.size(); ++i)
-    if (net.steps[i].name == "decoder.4") first = (int)i;
-  if (first < 0 || first + 3 != (int)net.steps.size() || net.steps[first + 2].name != "decoder.6+heads") {
-    set_error("fused decoder tail: layer plan not found");
-    return VP_ERR_INVALID;
-  }
-  ConvLayer *c4 = nullptr, *c5 = nullptr, *c6 = nullptr;
-  for (auto& c : net.convs) {
-    if (c->name == "decoder.4") c4 = c.get();
-    if (c->name == "decoder.5") c5 = c.get();
-    if (c->name == "decoder.6") c6 = c.get();
-  }
-  if (!c4 || !c5 || !c6 || c4->n_sets != 3) {
-    set_error("fused decoder tail: conv layers missing");
-    return VP_ERR_INVALID;
-  }
+  const char* label = "fused decoder tail";
+  FuseSite site;
+  if (int rc = find_fuse_site(net, label, "decoder.4", 3, "decoder.6+heads", true, &site)) return rc;
+  ConvLayer* c[3];
+  if (find_convs(net, {"decoder.4", "decoder.5", "decoder.6"}, c) >= 0 || c[0]->n_sets != 3) return fuse_fail(label, "conv layers missing");
+  ConvLayer *c4 = c[0], *c5 = c[1], *c6 = c[2];
   const int x3 = c4->src1;
   net.need(x3, HALO - 7 + (TILES_PER_ROW - 1) * TW / 8 + S4);  // the last tile reads past the row: zero margin
   // stages 4 and 5 are never materialised by this plan: their tensors take no memory
@@ -343,18 +332,14 @@ int plan_eqt_fuse_tail(Net& net) {
   HostBlob* head_a = net.add_blob(std::move(ha));
   Step st;
   st.name = "fused.tail (decoder.4-6 + heads, time-tiled)";
-  st.flops_per_window = 0;
-  for (int i = 0; i < 3; ++i) st.flops_per_window += net.steps[first + i].flops_per_window;
+  st.flops_per_window = site.flops_per_window;
   {  // issued MFMA work per tile: 2 m-tiles x 16 n-tiles x 40 K-steps, 2 x 32 x 20, 1 x 64 x 28, heads 8 x 56 (2048 FLOP each)
     const double mfma = 2.0 * (C4 / 16) * 40 + 2.0 * (C5 / 16) * 20 + 1.0 * (C6 / 16) * 28 + 8.0 * HEAD_KS;
     st.set_issued(3.0 * TILES_PER_ROW * mfma * 2048.0, 0.0, 0.0);
   }
   st.run = [=](Net& n, int B, hipStream_t s) -> int {
     TailArgs a{};
-    const Tensor& t3 = n.tensors[x3];
-    a.x3 = t3.p;
-    a.ls3 = t3.ls;
-    a.ws3 = (long)t3.win_stride();
+    bind(a.x3, a.ls3, a.ws3, n.tensors[x3]);
     a.y = n.y;
     a.af4 = q4->d, a.af5 = q5->d, a.af6 = q6->d;
     a.bs4 = c4->bias.d, a.bs5 = c5->bias.d, a.bs6 = c6->bias.d;
@@ -365,16 +350,13 @@ int plan_eqt_fuse_tail(Net& net) {
     a.head_b = c6->e1.d;
     a.B = B;
     a.n_tiles = 3 * B * TILES_PER_ROW;
-    a.clk = (n.debug_clock && n.debug_clock->d)
-                ? reinterpret_cast<unsigned long long*>(n.debug_clock->d) + (size_t)n.max_batch * 32 + 64 * 8
-                : nullptr;
+    a.clk = clock_words(n, ClockRegions(n.max_batch).tail);
     const int grid = a.n_tiles < 256 ? a.n_tiles : 256;
     hipLaunchKernelGGL(eqt_tail_kernel, dim3(grid), dim3(TAIL_NTH), TAIL_LDS_FLOATS * sizeof(float), s, a);
     return 0;
   };
   net.extra_kernels.push_back({reinterpret_cast<const void*>(&eqt_tail_kernel), TAIL_LDS_FLOATS * sizeof(float)});
-  net.steps.erase(net.steps.begin() + first, net.steps.end());
-  net.steps.push_back(std::move(st));
+  replace_steps(net, site, std::move(st));
   return VP_OK;
 }
 

@@ -399,7 +399,7 @@ struct Tail3Tiling {
   double issued_bf16;
 };
 Tail3Tiling tail3_tiling(const vp_config& cfg, int out_lo, int out_hi) {
-  const bool whole = (cfg.plan_flags[7] & 1024) || out_hi <= 0;
+  const bool whole = pf::eqt_tail_whole_row(cfg) || out_hi <= 0;
   const int t_lo = whole ? 0 : (out_lo / 16) * 16, t_hi = whole ? T_OUT : out_hi;
   const int tiles_a = (t_hi - t_lo + 1199) / 1200, tiles_b = (t_hi - t_lo + 1255) / 1256;
   Tail3Tiling t;
@@ -414,29 +414,19 @@ Tail3Tiling tail3_tiling(const vp_config& cfg, int out_lo, int out_hi) {
 
 // Replaces the steps "decoder.4", "decoder.5", "decoder.6+heads" of the plan by one fused step (bf16-piece form).
 int plan_eqt_fuse_tail_b3(Net& net) {
-  int first = -1;
-  for (size_t i = 0; i < net.steps.size(); ++i)
-    if (net.steps[i].name == "decoder.4") first = (int)i;
-  if (first < 0 || first + 3 != (int)net.steps.size() || net.steps[first + 2].name != "decoder.6+heads") {
-    set_error("fused decoder tail: layer plan not found");
-    return VP_ERR_INVALID;
-  }
-  ConvLayer *c4 = nullptr, *c5 = nullptr, *c6 = nullptr;
-  for (auto& c : net.convs) {
-    if (c->name == "decoder.4") c4 = c.get();
-    if (c->name == "decoder.5") c5 = c.get();
-    if (c->name == "decoder.6") c6 = c.get();
-  }
-  if (!c4 || !c5 || !c6 || c4->n_sets != 3 || c4->g.cinp() != 32 || c5->g.cinp() != 16 || c6->g.cinp() != 16 || c4->g.taps != 5 ||
-      c5->g.taps != 5 || c6->g.taps != 7 || c6->g.M() != 16) {
-    set_error("fused decoder tail: conv layers missing");
-    return VP_ERR_INVALID;
-  }
+  const char* label = "fused decoder tail";
+  FuseSite site;
+  if (int rc = find_fuse_site(net, label, "decoder.4", 3, "decoder.6+heads", true, &site)) return rc;
+  ConvLayer* c[3];
+  if (find_convs(net, {"decoder.4", "decoder.5", "decoder.6"}, c) >= 0 || c[0]->n_sets != 3 || c[0]->g.cinp() != 32 ||
+      c[1]->g.cinp() != 16 || c[2]->g.cinp() != 16 || c[0]->g.taps != 5 || c[1]->g.taps != 5 || c[2]->g.taps != 7 || c[2]->g.M() != 16)
+    return fuse_fail(label, "conv layers missing");
+  ConvLayer *c4 = c[0], *c5 = c[1], *c6 = c[2];
   const int x3 = c4->src1;
   net.need(x3, HALO - 5 + T_OUT / 8 + T3<1256>::PARK_COLS);  // the last tile of a row may read past it: zero margin
   // stages 4 and 5 are never materialised by this plan; plan_flags[1] & 4 keeps them, and adds stage 6's output and the heads'
   // logits, for the DUMP instance
-  const bool dumps = (net.cfg.plan_flags[1] & 4) != 0;
+  const bool dumps = pf::layer_dumps(net.cfg);
   int dbg[4] = {c4->dst, c5->dst, -1, -1};
   if (dumps) {
     dbg[2] = net.add_tensor("decoder.6", 8, T_OUT, 3);
@@ -449,45 +439,13 @@ int plan_eqt_fuse_tail_b3(Net& net) {
   HostBlob* p5 = net.add_blob(b3_operand(*c5, true));
   HostBlob* p6 = net.add_blob(b3_operand(*c6, true));
   // head table: [decoder][piece][entry e][8 channels] bf16, entry e <-> k = e - 15: w[ci][k] for 0 <= k <= 10, else zero
-  std::vector<uint16_t> ht((size_t)3 * 3 * HT_N * 8, 0);
-  auto rne = [](float x) -> uint16_t {
-    uint32_t u;
-    memcpy(&u, &x, 4);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-  };
-  auto widen = [](uint16_t h) -> float {
-    const uint32_t u = (uint32_t)h << 16;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-  };
-  for (int d = 0; d < 3; ++d)
-    for (int k = 0; k <= 10; ++k)
-      for (int ci = 0; ci < 8; ++ci) {
-        const float wv = c6->e0.h[(size_t)d * 88 + ci * 11 + k];
-        const uint16_t h = rne(wv);
-        const float r1 = wv - widen(h);
-        const uint16_t md = rne(r1);
-        const uint16_t lo = rne(r1 - widen(md));
-        const size_t e = ((size_t)d * 3 * HT_N + (k + 15)) * 8 + ci;
-        ht[e] = h;
-        ht[e + (size_t)HT_N * 8] = md;
-        ht[e + (size_t)2 * HT_N * 8] = lo;
-      }
-  std::vector<float> htf(ht.size() / 2);
-  memcpy(htf.data(), ht.data(), ht.size() * 2);
-  HostBlob* head_t = net.add_blob(std::move(htf));
+  HostBlob* head_t = net.add_blob(head_table3(c6->e0.h, HT_N, 15));
   Step st;
   st.name = "fused.tail (decoder.4-6 + heads, time-tiled)";
-  st.flops_per_window = 0;
-  for (int i = 0; i < 3; ++i) st.flops_per_window += net.steps[first + i].flops_per_window;
+  st.flops_per_window = site.flops_per_window;
   st.run = [=](Net& n, int B, hipStream_t s) -> int {
     Tail3Args a{};
-    const Tensor& t3 = n.tensors[x3];
-    a.x3 = t3.p;
-    a.ls3 = t3.ls;
-    a.ws3 = (long)t3.win_stride();
+    bind(a.x3, a.ls3, a.ws3, n.tensors[x3]);
     a.y = n.y;
     a.af4 = reinterpret_cast<const uint4*>(p4->d);
     a.af5 = reinterpret_cast<const uint4*>(p5->d);
@@ -507,19 +465,12 @@ int plan_eqt_fuse_tail_b3(Net& net) {
     a.t_lo = tl.t_lo;
     a.tiles_per_row = tl.tiles_per_row;
     a.n_tiles = 3 * B * a.tiles_per_row;
-    a.clk = (n.debug_clock && n.debug_clock->d)
-                ? reinterpret_cast<unsigned long long*>(n.debug_clock->d) + (size_t)n.max_batch * 32 + 64 * 8
-                : nullptr;
+    a.clk = clock_words(n, ClockRegions(n.max_batch).tail);
     const int grid = a.n_tiles < 256 ? a.n_tiles : 256;
     if (dumps) {
       Tail3DumpArgs d{};
       static_cast<Tail3Args&>(d) = a;
-      for (int i = 0; i < 4; ++i) {
-        const Tensor& t = n.tensors[dbg[i]];
-        d.dbg[i] = t.p;
-        d.dbg_ls[i] = t.ls;
-        d.dbg_ws[i] = (long)t.win_stride();
-      }
+      bind_dbg(d.dbg, d.dbg_ls, d.dbg_ws, n, dbg);
       hipLaunchKernelGGL((eqt_tail3_kernel<1200, true>), dim3(grid), dim3(T3_NTH), T3<1200>::LDS_BYTES, s, d);
     } else if (wide)
       hipLaunchKernelGGL(eqt_tail3_kernel<1256>, dim3(grid), dim3(T3_NTH), T3<1256>::LDS_BYTES, s, a);
@@ -534,8 +485,7 @@ int plan_eqt_fuse_tail_b3(Net& net) {
     w[0] = 0.0, w[1] = tail3_tiling(n.cfg, lo, hi).issued_bf16, w[2] = 0.0;
   };
   st.set_issued(0.0, tail3_tiling(net.cfg, 0, 0).issued_bf16, 0.0);  // the whole row
-  net.steps.erase(net.steps.begin() + first, net.steps.begin() + first + 3);
-  net.steps.push_back(std::move(st));
+  replace_steps(net, site, std::move(st));
   net.poison_in_plan = true;  // no poison_kernel launch behind this plan
   return VP_OK;
 }

@@ -4,7 +4,9 @@
 #include <functional>
 #include <memory>
 
+#include "bf16_pack.h"
 #include "conv_mfma.h"
+#include "plan_flags.h"
 #include "prepost.h"
 
 namespace vp {
@@ -53,9 +55,8 @@ constexpr int kDenseOut = -2;
 // The A operand of a conv layer regrouped for 16-byte loads (conv_lds_q4): [mt][step][64] -> [mt][step / 4][64][4],
 // step = channel block * taps + tap; needs (channel blocks * taps) % 4 == 0.
 std::vector<float> regroup_afrag4(const ConvLayer& L);
-// w as three bfloat16 pieces, each the round-to-nearest-even of what the ones before it left: hi + (mid + lo) == w in fp32
-void bf16_split3(float w, uint16_t* hi, uint16_t* mid, uint16_t* lo);
-// three-piece bf16 operands of every weight set of a layer (conv_b3.h) / the fp32 operand with phase-major rows (net.hip)
+// three-piece bf16 operands (bf16_split3, bf16_pack.h) of every weight set of a layer (conv_b3.h) / the fp32 operand with
+// phase-major rows (net.hip)
 std::vector<float> b3_operand(const ConvLayer& L, bool mperm);
 std::vector<float> regroup_afrag4_phase_major(const ConvLayer& L);
 
@@ -79,7 +80,7 @@ struct Net {
   double flops_per_window = 0;
   int warm_launches = 1;  // launches of the fused PhaseNet kernels that still pre-touch the weights (first launch of a plan:
                           // cold L2); in steady state the weights are L2-resident and the touch only delays 8 workgroups
-  HostBlob* debug_clock = nullptr;  // fused PhaseNet core: per-layer shader-clock stamps (debug plan flag)
+  HostBlob* debug_clock = nullptr;  // fused PhaseNet core: per-layer shader-clock stamps (debug plan flag); layout: ClockRegions
   HostBlob* win_flags = nullptr;    // [max_batch]: 1 where annotate_batch_pre met a non-finite window (its predictions become NaN, as the reference's)
   bool fused_pre = false;           // the plan's first launch can gather + normalise its windows itself (pn_window_kernel, eqt_front_kernel)
   int out_lo = 0, out_hi = 0;       // set by the caller around run(): the output samples [out_lo, out_hi) of every window that it keeps
@@ -132,14 +133,54 @@ struct Net {
 int plan_phasenet(Net& net, const ParamView& pv);
 int plan_phasenet_fused(Net& net, const ParamView& pv, int debug_flags);  // swaps the 18 layer steps for one launch (pn_window_kernel) or, for the reference plans, three; bit0: dump LDS intermediates, bit1: clock stamps, bit2: the one-launch kernel's DUMP instance
 int plan_eqt(Net& net, const ParamView& pv);
-int plan_eqt_fuse_res(Net& net);  // swaps the 14 ResCNN conv steps for one fused launch
-int plan_eqt_fuse_tail_b3(Net& net);  // the same on the bf16 matrix cores, exact three-piece operands (eqt_tail_b3.hip)
-int plan_eqt_fuse_tail(Net& net);  // swaps decoder.4 / .5 / .6+heads for one time-tiled fused launch (eqt_tail.hip)
-int plan_eqt_fuse_front(Net& net, bool b3);  // swaps encoder.0 / .1 / .2 for one time-tiled fused launch (eqt_front.hip)
-int plan_eqt_fuse_enc36_b3(Net& net);  // the same on the bf16 matrix cores, exact three-piece operands (eqt_enc36_b3.hip)
-int plan_eqt_fuse_enc36(Net& net);  // swaps encoder.3 .. .6 for one launch per window (eqt_enc36.hip)
-int plan_eqt_fuse_dec03(Net& net, bool b3);  // swaps decoder.0 / .1 / .2 / .2.edge / .3 for one launch per (decoder, window) row (eqt_dec03.hip)
+// The fused launches of EQTransformer, each swapped in for a run of consecutive steps of the layer plan (fuse-site helpers below).
+// A kernel on the fp32 MFMA is bit-identical to the launches it replaces; its bf16-piece twin (exact three-piece operands on the
+// bf16 matrix cores, the default) agrees with it to fp32 rounding.
+int plan_eqt_fuse_res(Net& net);              // the 14 ResCNN conv steps -> one launch, fp32 or bf16 pieces (eqt_res.hip)
+int plan_eqt_fuse_front(Net& net, bool b3);   // encoder.0 / .1 / .2 -> one time-tiled launch; b3: stages 1 and 2 on bf16 pieces (eqt_front.hip)
+int plan_eqt_fuse_enc36(Net& net);            // encoder.3 .. .6 -> one launch per window, fp32 MFMA (eqt_enc36.hip)
+int plan_eqt_fuse_enc36_b3(Net& net);         // the same steps on bf16 pieces (eqt_enc36_b3.hip)
+int plan_eqt_fuse_dec03(Net& net, bool b3);   // decoder.0 / .1 / .2 / .2.edge / .3 -> one launch per (decoder, window) row; b3: stages 1-3 on bf16 pieces (eqt_dec03.hip)
+int plan_eqt_fuse_tail(Net& net);             // decoder.4 / .5 / .6+heads -> one time-tiled launch, fp32 MFMA (eqt_tail.hip)
+int plan_eqt_fuse_tail_b3(Net& net);          // the same steps on bf16 pieces (eqt_tail_b3.hip)
 
+// ---- fuse-site helpers: what every plan_eqt_fuse_* does before and after the part that is its own ----
+struct FuseSite {
+  int first = -1, count = 0;    // net.steps[first, first + count)
+  double flops_per_window = 0;  // of those steps, summed in plan order
+};
+// The `count` consecutive steps from the one named `first` to the one named `last`; ends_plan: nothing may follow them;
+// before_last: the name the step in front of the last one must have (decoder.2.edge).  Failure: "<label>: layer plan not found".
+int find_fuse_site(const Net& net, const char* label, const char* first, int count, const char* last, bool ends_plan, FuseSite* site,
+                   const char* before_last = nullptr);
+// The conv layers of these names into out[], in the order given; returns the index of the first one missing, -1 if none is.
+int find_convs(const Net& net, const std::vector<std::string>& names, ConvLayer** out);
+int fuse_fail(const char* label, const char* what);  // set_error("<label>: <what>"), returns VP_ERR_INVALID
+// Puts st where the site's steps were.
+void replace_steps(Net& net, const FuseSite& site, Step st);
+
+// ---- binding a tensor to the (pointer, row stride, window stride) fields of a kernel's argument struct ----
+inline void bind(const float*& p, int& ls, long& ws, const Tensor& t) { p = t.p, ls = t.ls, ws = (long)t.win_stride(); }
+inline void bind(float*& p, int& ls, long& ws, const Tensor& t) { p = t.p, ls = t.ls, ws = (long)t.win_stride(); }
+// ... and the tensors ids[0 .. N) to the dbg / dbg_ls / dbg_ws block of a DUMP instance's arguments
+template <int N>
+inline void bind_dbg(float* (&p)[N], int (&ls)[N], long (&ws)[N], const Net& n, const int* ids) {
+  for (int i = 0; i < N; ++i) bind(p[i], ls[i], ws[i], n.tensors[ids[i]]);
+}
+
+// Net::debug_clock (plan_flags[1] & 2), in 64-bit words: [max_batch][32] EQTransformer's middle kernel / PhaseNet's fused core |
+// [64][8] conv launches of either model's layer plan, one row per ConvLayer (add_conv_step; a fused ResCNN / decoder 0-3 kernel
+// stamps into the rows of the launches it replaced) | [max_batch][32] EQTransformer's tail (PhaseNet allocates the first two only)
+struct ClockRegions {
+  static constexpr size_t kPerWindow = 32, kConvRows = 64, kPerConv = 8;
+  size_t mid, conv, tail, words;
+  explicit ClockRegions(int max_batch)
+      : mid(0), conv((size_t)max_batch * kPerWindow), tail(conv + kConvRows * kPerConv), words(tail + (size_t)max_batch * kPerWindow) {}
+};
+// where a region starts on the device; nullptr without clock stamps
+inline unsigned long long* clock_words(const Net& n, size_t offset) {
+  return (n.debug_clock && n.debug_clock->d) ? reinterpret_cast<unsigned long long*>(n.debug_clock->d) + offset : nullptr;
+}
 
 // BatchNorm (eval) folded into the preceding conv: scale = gamma / sqrt(var + eps),
 // shift = beta - mean * scale (+ conv bias * scale).

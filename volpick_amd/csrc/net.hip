@@ -63,27 +63,8 @@ std::vector<float> regroup_afrag4(const ConvLayer& L) {
 }
 
 // fp32 MFMA-order fragments [set][mt][cb][tap][64] (pack_afrag) -> three-piece bf16 operands
-// [set][mt'][tap * KS + step][piece][64][8] (conv_b3.h): an fp32 weight is exactly hi + mid + lo in bfloat16.
+// [set][mt'][tap * KS + step][piece][64][8] (conv_b3.h): an fp32 weight is exactly hi + mid + lo in bfloat16 (bf16_split3).
 // mperm: GEMM rows regrouped (channel, phase) -> (phase, channel).  Two bf16 per float slot of the blob.
-void bf16_split3(float w, uint16_t* hi, uint16_t* mid, uint16_t* lo) {
-  auto rne = [](float x) -> uint16_t {
-    uint32_t u;
-    memcpy(&u, &x, 4);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-  };
-  auto widen = [](uint16_t h) -> float {
-    const uint32_t u = (uint32_t)h << 16;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-  };
-  *hi = rne(w);
-  const float r1 = w - widen(*hi);
-  *mid = rne(r1);
-  *lo = rne(r1 - widen(*mid));
-}
-
 std::vector<float> b3_operand(const ConvLayer& L, bool mperm) {
   const int cinp = L.g.cinp(), taps = L.g.taps, M = L.g.M(), P = L.g.P, cout = L.g.cout, CB = cinp / 4, MT = M / 16;
   // K of one instruction = 32: cinp >= 32: 32 channels of one tap, steps (tap, channel step); cinp = 16 / 8: all channels of
@@ -165,39 +146,61 @@ HostBlob* Net::add_blob(std::vector<float> v) {
   return extra.back().get();
 }
 
+int find_fuse_site(const Net& net, const char* label, const char* first, int count, const char* last, bool ends_plan, FuseSite* site,
+                   const char* before_last) {
+  const int n = (int)net.steps.size();
+  int at = -1;
+  for (int i = 0; i < n; ++i)
+    if (net.steps[i].name == first) at = i;
+  if (at < 0 || (ends_plan ? at + count != n : at + count > n) || net.steps[at + count - 1].name != last ||
+      (before_last && net.steps[at + count - 2].name != before_last))
+    return fuse_fail(label, "layer plan not found");
+  site->first = at;
+  site->count = count;
+  site->flops_per_window = 0;
+  for (int i = 0; i < count; ++i) site->flops_per_window += net.steps[at + i].flops_per_window;
+  return VP_OK;
+}
+
+int find_convs(const Net& net, const std::vector<std::string>& names, ConvLayer** out) {
+  int i = 0, missing = -1;
+  for (const std::string& name : names) {
+    out[i] = nullptr;
+    for (auto& c : net.convs)
+      if (c->name == name) out[i] = c.get();
+    if (!out[i] && missing < 0) missing = i;
+    ++i;
+  }
+  return missing;
+}
+
+int fuse_fail(const char* label, const char* what) {
+  set_error("%s: %s", label, what);
+  return VP_ERR_INVALID;
+}
+
+void replace_steps(Net& net, const FuseSite& site, Step st) {
+  net.steps.erase(net.steps.begin() + site.first, net.steps.begin() + site.first + site.count);
+  net.steps.insert(net.steps.begin() + site.first, std::move(st));
+}
+
 void Net::add_conv_step(ConvLayer* L) {
   Step s;
   s.name = L->name;
   s.run = [L](Net& net, int B, hipStream_t stream) -> int {
     ConvArgs a{};
-    const Tensor& s1 = net.tensors[L->src1];
-    a.src1 = s1.p;
-    a.ls1 = s1.ls;
-    a.ws1 = (long)s1.win_stride();
-    if (L->src2 >= 0) {
-      const Tensor& s2 = net.tensors[L->src2];
-      a.src2 = s2.p;
-      a.ls2 = s2.ls;
-      a.ws2 = (long)s2.win_stride();
-    }
+    bind(a.src1, a.ls1, a.ws1, net.tensors[L->src1]);
+    if (L->src2 >= 0) bind(a.src2, a.ls2, a.ws2, net.tensors[L->src2]);
     if (L->dst == kDenseOut) {
       a.dst = net.y;
       a.lsd = net.in_samples;
       a.wsd = (long)net.n_out * net.in_samples;
       a.dst_halo = 0;
     } else {
-      const Tensor& d = net.tensors[L->dst];
-      a.dst = d.p;
-      a.lsd = d.ls;
-      a.wsd = (long)d.win_stride();
+      bind(a.dst, a.lsd, a.wsd, net.tensors[L->dst]);
       a.dst_halo = HALO;
     }
-    if (L->dst2 >= 0) {
-      const Tensor& d2 = net.tensors[L->dst2];
-      a.dst2 = d2.p;
-      a.lsd2 = d2.ls;
-      a.wsd2 = (long)d2.win_stride();
-    }
+    if (L->dst2 >= 0) bind(a.dst2, a.lsd2, a.wsd2, net.tensors[L->dst2]);
     a.afrag = L->afrag_q4 ? L->afrag_q4->d : L->afrag.d;
     a.bias = L->bias.d;
     a.afrag_set_stride = (long)(L->afrag.h.size() / L->n_sets);
@@ -206,11 +209,8 @@ void Net::add_conv_step(ConvLayer* L) {
     a.n_windows = B * L->n_sets;
     a.l_out = L->l_out;
     a.l_dst = L->l_dst;
-    a.e0 = (L->res >= 0) ? net.tensors[L->res].p : L->e0.d;
-    if (L->res >= 0) {
-      a.ls_res = net.tensors[L->res].ls;
-      a.ws_res = (long)net.tensors[L->res].win_stride();
-    }
+    a.e0 = L->e0.d;
+    if (L->res >= 0) bind(a.e0, a.ls_res, a.ws_res, net.tensors[L->res]);
     a.e1 = L->e1.d;
     a.e2 = L->e2.d;
     a.e_set_stride = L->e1.h.empty() ? 0 : (long)(L->e1.h.size() / L->n_sets);
@@ -220,7 +220,7 @@ void Net::add_conv_step(ConvLayer* L) {
         if (c.get() == L) break;
         ++li;
       }
-      a.clk = reinterpret_cast<unsigned long long*>(net.debug_clock->d) + (size_t)net.max_batch * 32 + (size_t)li * 8;
+      a.clk = clock_words(net, ClockRegions(net.max_batch).conv + (size_t)li * ClockRegions::kPerConv);
     }
     return L->launch(a, L->cols, stream);
   };

@@ -125,7 +125,7 @@ Step core_step(Net& net, const PnPlan& p) {
     for (int i = 0; i < 12; ++i)
       if (p.debug_dumps && dbg_ids[i] >= 0) bind(n.tensors[dbg_ids[i]], &a.dbg[i], &a.dbg_ls[i], &a.dbg_ws[i]);
     a.clk = clk ? reinterpret_cast<unsigned long long*>(clk->d) : nullptr;
-    a.warm = n.cfg.plan_flags[4] != 1;
+    a.warm = pf::warm(n.cfg);
     pn_launch_core(a, B, s);
     return 0;
   };
@@ -249,7 +249,7 @@ Step window_step(Net& net, const PnPlan& p, PnForm form, const std::vector<int>&
       a.c.bs[i] = n.convs[3 + i]->bias.d;
     }
     a.c.clk = clk ? reinterpret_cast<unsigned long long*>(clk->d) : nullptr;
-    a.c.warm = n.cfg.plan_flags[4] != 1 && n.warm_launches > 0;
+    a.c.warm = pf::warm(n.cfg) && n.warm_launches > 0;
     if (n.warm_launches > 0) --n.warm_launches;
     bind(n.tensors[p.x], &a.x, &a.ls_x, &a.ws_x);
     bind(n.tensors[p.skip0], &a.skip0, &a.ls_s, &a.ws_s);
@@ -281,32 +281,32 @@ Step window_step(Net& net, const PnPlan& p, PnForm form, const std::vector<int>&
 
 int plan_phasenet_fused(Net& net, const ParamView& pv, int debug_flags) {
   PnPlan p{};
-  p.debug_dumps = (debug_flags & 1) != 0;
-  p.debug_clock = (debug_flags & 2) != 0;
+  p.debug_dumps = (debug_flags & pf::DBG_LDS_DUMPS) != 0;
+  p.debug_clock = (debug_flags & pf::DBG_CLOCK) != 0;
   // bit 2: the one-launch kernel's DUMP instance writes every layer's output (and the head's logits) to the debug tensors
-  const bool win_dumps = (debug_flags & 4) != 0;
-  const int f5 = net.cfg.plan_flags[5];
-  if (win_dumps && (p.debug_dumps || f5 != 0 || net.cfg.plan_flags[6] != 0)) {
+  const bool win_dumps = (debug_flags & pf::DBG_LAYER_DUMPS) != 0;
+  const int f5 = pf::get(net.cfg, pf::PN_FORM);
+  if (win_dumps && (p.debug_dumps || f5 != pf::PN_DEFAULT || pf::get(net.cfg, pf::PRE) != 0)) {
     set_error("PhaseNet plan_flags[1] & 4 dumps the default one-launch form only (plan_flags[1] & 1, plan_flags[5], plan_flags[6] unset)");
     return VP_ERR_UNSUPPORTED;
   }
   // Removed in round 6: the hand-pipelined K loop and the intermediate forms of pn_window_kernel between its references
-  if (net.cfg.plan_flags[2] == 1 || f5 == 4 || f5 == 5 || f5 == 6 || f5 == 7 || f5 == 9) {
+  if (pf::get(net.cfg, pf::MID) == pf::MID_PN_REMOVED || pf::pn_form_removed(f5)) {
     set_error("PhaseNet plan_flags[2] = %d / plan_flags[5] = %d: this A/B form was removed in round 6 (kept: plan_flags[5] = 0, 1, 2, 3, 8)",
-              net.cfg.plan_flags[2], f5);
+              pf::get(net.cfg, pf::MID), f5);
     return VP_ERR_UNSUPPORTED;
   }
-  if (net.cfg.plan_flags[3] == 2) {
+  if (pf::get(net.cfg, pf::TILES) == pf::TILES_PN_REMOVED) {
     set_error("PhaseNet plan_flags[3] = 2 (persistent level-0 down kernel): removed in round 6");
     return VP_ERR_UNSUPPORTED;
   }
   // plan_flags[5] = 1: the three-launch plan with the MFMA forms of the two level-0 kernels (bit-identical to the layer plan),
   // 2: with their VALU forms; otherwise the whole network in one launch, in one of three forms.  The debug dumps of
   // plan_flags[1] & 1 exist in the three-launch plans only.
-  p.valu = f5 != 1;
-  p.persistent = net.cfg.plan_flags[3] != 1;  // plan_flags[3] = 1: one workgroup per tile for up3 too (A/B timing)
-  const bool whole = p.valu && f5 != 2 && !p.debug_dumps;
-  const PnForm form = f5 == 3 ? PnForm::Fp32Core : f5 == 8 ? PnForm::Level0Valu : PnForm::Default;
+  p.valu = f5 != pf::PN_TILED_MFMA;
+  p.persistent = pf::get(net.cfg, pf::TILES) != pf::TILES_ALT;  // plan_flags[3] = 1: one workgroup per tile for up3 too (A/B timing)
+  const bool whole = p.valu && f5 != pf::PN_TILED_VALU && !p.debug_dumps;
+  const PnForm form = f5 == pf::PN_FP32_CORE ? PnForm::Fp32Core : f5 == pf::PN_LEVEL0_VALU ? PnForm::Level0Valu : PnForm::Default;
   if (p.valu) {
     const float eps = net.cfg.bn_eps;
     struct {
@@ -366,7 +366,7 @@ int plan_phasenet_fused(Net& net, const ParamView& pv, int debug_flags) {
   if (whole) {
     steps.clear();
     steps.push_back(window_step(net, p, form, wd_ids));
-    net.fused_pre = net.cfg.plan_flags[6] != 1;  // plan_flags[6] = 1: gather_normalize_kernel fills the input tensor as in the other plans
+    net.fused_pre = pf::get(net.cfg, pf::PRE) != pf::PRE_PN_GATHER;  // plan_flags[6] = 1: gather_normalize_kernel fills the input tensor as in the other plans
     net.fused_pre_poisons = true;                // ... and then writes the NaN predictions of a non-finite window itself
     pn_register_window(net, win_dumps);
   }
