@@ -153,6 +153,13 @@ static_assert(D0T_TILES * D0T_TS >= W0_S - 4 + 8 && D0T_RING >= 2 * D0T_TS + 11 
 // (rows (phase, channel), K = 8 taps x 16 channels = four K-steps) on tile j - 1, eight samples behind, and finish it in
 // registers: the two lanes that hold a sample's eight channels exchange their halves of the 1 x 1 conv (v_permlane16_swap),
 // softmax, store.  No fp32 level-0 row exists in the up path any more.
+// The schedule inside a phase: a producer's MFMAs issue right behind the barrier from fragments of up2.same's (static) image
+// that it fetched a phase ahead; the next fragments, the split and ring store of the skip quad (fetched from memory TWO tiles
+// ahead) and the next skip fetch follow, the transposed conv's own epilogue and ring store come last.  A consumer requests the
+// first K-step's fragments of tile j - 1, runs the epilogue of tile j - 2 (1 x 1 conv, swap, softmax, stores: it writes y only)
+// while they are in flight, then its MFMAs; only the four BN + ReLU sums cross the barrier, and one drain epilogue behind the
+// loop finishes the last tile.  Each role runs its own copy of the loop (thirteen barriers in each), so that neither holds the
+// other's carried registers.  Same products, same sums, same order: y is bit for bit what the undeferred schedule stored.
 constexpr int U3T_TS = 256, U3T_RING = 528, U3T_NCU = 768;
 using U3T_QU = B3Chunk<16, U3T_NCU>;                      // up2.same's output: sample t at column t + 1
 constexpr int U3T_PLN = U3T_RING / 2, U3T_MIR = 4;  // entries of a parity plane; its first four entries are repeated behind it, so
@@ -189,8 +196,8 @@ constexpr bool U3T_PROBE_BUILD = false;
 // barrier that closes its layer, or in the epilogue of a time-tiled level-0 layer, and adds nothing to the other instances.
 template <PnForm F, bool DUMP = false>
 // amdgpu_num_vgpr counts the VGPR half of the unified file on gfx90a+ (LLVM doubles it): 60 -> at most 120 registers per lane, so that
-// four forward waves leave each SIMD the 32 registers the post-processing kernels need to run beside them (prepost.hip; a dozen
-// one-off spills per window in the D0T form, none inside a loop)
+// four forward waves leave each SIMD the 32 registers the post-processing kernels need to run beside them (prepost.hip; the D0T
+// form fits without scratch, its DUMP instance, tests only, spills 24 bytes per lane)
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_num_vgpr(60))) void pn_window_kernel(const WindowArgs a) {
   constexpr bool B3 = F != PnForm::Fp32Core;  // the core layers (all but the strided convs) on bf16 pieces
   constexpr bool D0T = F == PnForm::Default;  // level 0, down and up, time-tiled on the bf16 matrix cores
@@ -927,10 +934,10 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_num_vgpr(60))) void pn_
   [[maybe_unused]] float u3_w1[3][4], u3_b1[3], u3_sk[4] = {0.f, 0.f, 0.f, 0.f};
   [[maybe_unused]] const int u3_pl = tid - 512, u3_skq = u3_pl & 1, u3_sks = u3_pl >> 1;  // producer lane: skip channel quad, sample within the tile
   [[maybe_unused]] const float* const u3_src = a.skip0 + (long)win * a.ws_s + HALO + (long)(4 * u3_skq) * a.ls_s;
-  [[maybe_unused]] auto u3_fetch_skip = [&](const int j, const bool edge) {  // samples 256 j - 2 + u3_sks of channels 4 u3_skq ..
+  [[maybe_unused]] auto u3_fetch_skip = [&](float (&d)[4], const int j, const bool edge) {  // samples 256 j - 2 + u3_sks of channels 4 u3_skq ..
     const int ts = U3T_TS * j - 2 + u3_sks;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) u3_sk[r] = (!edge || (unsigned)ts < (unsigned)T0) ? u3_src[(long)r * a.ls_s + ts] : 0.f;
+    for (int r = 0; r < 4; ++r) d[r] = (!edge || (unsigned)ts < (unsigned)T0) ? u3_src[(long)r * a.ls_s + ts] : 0.f;
   };
   [[maybe_unused]] auto u3_load_operands = [&]() {
     const int q = (lane >> 4) & 1;
@@ -939,7 +946,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_num_vgpr(60))) void pn_
       for (int pc = 0; pc < 3; ++pc) u3_aw[pc] = a.af3_u3t[(long)(wave & 1) * (3 * 64) + pc * 64 + lane];
 #pragma unroll
       for (int r = 0; r < 4; ++r) u3_bv[r] = a.bs_u3t[4 * q + r];
-      u3_fetch_skip(0, true);
+      u3_fetch_skip(u3_sk, 0, true);
     } else {
       b3_load_a<16, 8>(a.af3_u3s, 0, lane, u3_aw);
 #pragma unroll
@@ -1081,7 +1088,9 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_num_vgpr(60))) void pn_
     auto& sk = u3_sk;
     const int sk_q = u3_skq, sk_s = u3_sks;
     if (tid < 96) {  // ring columns 512 .. 527 <-> samples -16 .. -1 of both chunks: zeros
-      const int cp = tid >> 4, c = U3T_RING - 16 + (tid & 15);  // cp = piece * 2 + chunk
+      int tz = tid;
+      asm volatile("" : "+v"(tz));  // (opaque: otherwise 4 tid and tid & 1 of the kernel's first lines are kept for this, in scratch)
+      const int cp = tz >> 4, c = U3T_RING - 16 + (tz & 15);  // cp = piece * 2 + chunk
       *reinterpret_cast<uint4*>(RU + (cp >> 1) * U3T_PS + (cp & 1) * U3T_CH + ring_at(c)) = make_uint4(0u, 0u, 0u, 0u);
     }
     __syncthreads();
@@ -1098,93 +1107,129 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_num_vgpr(60))) void pn_
     int cc = U3T_RING - 11 + 32 * wv + 2 * n + ph;
     cc = cc >= U3T_RING ? cc - U3T_RING : cc;
     float* const yrow = a.y + (long)win * 3 * T0;
+    // consumer: a tile's epilogue from its four BN + ReLU sums h (this lane's channel quad of sample t): Conv1d(8, 3, 1) -- the
+    // other four channels come from the lane 16 further (the other channel quad) -- softmax, store.  It writes y only.
+    auto u3_finish = [&](const int jt, const float (&h)[4]) {
+      float z[3];
 #pragma unroll
-    for (int j = 0; j <= U3T_TILES; ++j) {
-      if (producer) {
-        if (j < U3T_TILES) {
-          uint4 b[3];
+      for (int k = 0; k < 3; ++k) {
+        float zz = 0.f;
 #pragma unroll
-          for (int pc = 0; pc < 3; ++pc) b[pc] = *reinterpret_cast<const uint4*>(up + pc * U3T_QU::PS);
-          f32x4 acc = bv;
-          U3T_MFMA(acc, aw[2], b[0]);
-          U3T_MFMA(acc, aw[1], b[1]);
-          U3T_MFMA(acc, aw[0], b[2]);
-          U3T_MFMA(acc, aw[1], b[0]);
-          U3T_MFMA(acc, aw[0], b[1]);
-          U3T_MFMA(acc, aw[0], b[0]);
-          // the skip quad fetched a phase ago -> pieces, chunk 0
-          ring_store(RU, cs, sk_q, sk);
-          if (j + 1 < U3T_TILES) u3_fetch_skip(j + 1, U3T_TS * (j + 2) > T0);
-          float o[4];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) o[r] = fmaxf(acc[r], 0.f);
-          if (j == 0 || U3T_TS * (j + 1) > T0) {  // (uniform) the tiles that meet the ends of the signal
-            const int s = U3T_TS * j + mphase - 2 + 4 * (16 * (wv >> 1) + n);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) o[r] = (unsigned)s < (unsigned)T0 ? o[r] : 0.f;
-          }
-          if constexpr (DUMP) {
-            const int s = U3T_TS * j + mphase - 2 + 4 * (16 * (wv >> 1) + n);
-            if ((unsigned)s < (unsigned)T0) {
-#pragma unroll
-              for (int r = 0; r < 4; ++r) win_dump_row(a, WD_U3T, win, 4 * quad + r)[s] = o[r];
-            }
-          }
-          ring_store(RU + U3T_CH, ct, quad, o);
-          ct += U3T_TS, cs += U3T_TS;
-          ct = ct >= U3T_RING ? ct - U3T_RING : ct;
-          cs = cs >= U3T_RING ? cs - U3T_RING : cs;
-          up += (U3T_TS / 4) * 8;
-        }
-      } else if (j > 0) {
-        f32x4 sa = {0.f, 0.f, 0.f, 0.f}, sb = bv;
-        const bf16_t* const rp0 = RU + quad * U3T_CH + ring_at(cc);  // K-step st: two columns = one plane entry further (mirrored: no wrap)
-#pragma unroll
-        for (int st = 0; st < 4; ++st) {
-          uint4 b[3];
-          const bf16_t* rp = rp0 + st * 8;
-#pragma unroll
-          for (int pc = 0; pc < 3; ++pc) b[pc] = *reinterpret_cast<const uint4*>(rp + pc * U3T_PS);
-          U3T_MFMA(sa, aw[st * 3 + 2], b[0]);
-          U3T_MFMA(sb, aw[st * 3 + 1], b[0]);
-          U3T_MFMA(sa, aw[st * 3 + 1], b[1]);
-          U3T_MFMA(sb, aw[st * 3 + 0], b[1]);
-          U3T_MFMA(sa, aw[st * 3 + 0], b[2]);
-          U3T_MFMA(sb, aw[st * 3 + 0], b[0]);
-        }
-        // BN + ReLU -> Conv1d(8, 3, 1): this lane's four channels, the other four from the lane 16 further (the other channel quad)
-        float z[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          float zz = 0.f;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) zz = fmaf(w1[k][r], fmaxf(sa[r] + sb[r], 0.f), zz);
-          const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(zz), __float_as_uint(zz), false, false);
-          z[k] = (__uint_as_float(sw[0]) + __uint_as_float(sw[1])) + b1[k];  // rows (0, 1) and (2, 3): the pair's sum in both
-        }
-        if constexpr (DUMP) {
-          const int t = U3T_TS * (j - 1) - 8 + 32 * wv + 2 * n + ph;
-          if ((unsigned)t < (unsigned)T0) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) win_dump_row(a, WD_U3SAME, win, 4 * quad + r)[t] = fmaxf(sa[r] + sb[r], 0.f);
-            if (quad == 0) {
-#pragma unroll
-              for (int k = 0; k < 3; ++k) win_dump_row(a, WD_LOGITS, win, k)[t] = z[k];
-            }
-          }
-        }
-        const float mx = fmaxf(z[0], fmaxf(z[1], z[2]));
-        const float e0 = __expf(z[0] - mx), e1 = __expf(z[1] - mx), e2 = __expf(z[2] - mx);
-        const float inv = __builtin_amdgcn_rcpf(e0 + e1 + e2);  // (1 ulp; the IEEE division is ten instructions on this issue-bound path)
-        float y0 = e0 * inv, y1 = e1 * inv, y2 = e2 * inv;
-        if (poisoned) y0 = y1 = y2 = __builtin_nanf("");
-        const int t = U3T_TS * (j - 1) - 8 + 32 * wv + 2 * n + ph;
-        if (quad == 0 && (unsigned)t < (unsigned)T0) yrow[t] = y0, yrow[T0 + t] = y1, yrow[2 * T0 + t] = y2;
-        cc += U3T_TS;
-        cc = cc >= U3T_RING ? cc - U3T_RING : cc;
+        for (int r = 0; r < 4; ++r) zz = fmaf(w1[k][r], h[r], zz);
+        const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(zz), __float_as_uint(zz), false, false);
+        z[k] = (__uint_as_float(sw[0]) + __uint_as_float(sw[1])) + b1[k];  // rows (0, 1) and (2, 3): the pair's sum in both
       }
-      lds_barrier();
-      U3T_PHASE_STAMP(j)
+      const int t = U3T_TS * jt - 8 + 32 * wv + 2 * n + ph;
+      if constexpr (DUMP) {
+        if ((unsigned)t < (unsigned)T0) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) win_dump_row(a, WD_U3SAME, win, 4 * quad + r)[t] = h[r];
+          if (quad == 0) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) win_dump_row(a, WD_LOGITS, win, k)[t] = z[k];
+          }
+        }
+      }
+      const float mx = fmaxf(z[0], fmaxf(z[1], z[2]));
+      const float e0 = __expf(z[0] - mx), e1 = __expf(z[1] - mx), e2 = __expf(z[2] - mx);
+      const float inv = __builtin_amdgcn_rcpf(e0 + e1 + e2);  // (1 ulp; the IEEE division is ten instructions on this issue-bound path)
+      float y0 = e0 * inv, y1 = e1 * inv, y2 = e2 * inv;
+      if (poisoned) y0 = y1 = y2 = __builtin_nanf("");
+      if (quad == 0 && (unsigned)t < (unsigned)T0) yrow[t] = y0, yrow[T0 + t] = y1, yrow[2 * T0 + t] = y2;
+    };
+    float u3_h[4] = {0.f, 0.f, 0.f, 0.f};  // consumer: the sums of the tile whose epilogue is still owed
+    // producer: up2.same's image is complete and static, so tile j + 1's fragments are fetched during phase j; the skip quads are
+    // fetched TWO tiles ahead, even tiles into sk, odd ones into sk2 (one phase does not cover their trip to L2 once the MFMAs
+    // no longer wait for a fragment read in front of them)
+    uint4 u3_pb[3];
+    float u3_sk2[4] = {0.f, 0.f, 0.f, 0.f};
+    if (producer) {
+      u3_fetch_skip(u3_sk2, 1, false);
+#pragma unroll
+      for (int pc = 0; pc < 3; ++pc) u3_pb[pc] = *reinterpret_cast<const uint4*>(up + pc * U3T_QU::PS);
+    }
+    auto u3_produce = [&](const int j) {  // tile j: MFMAs first, then everything that does not depend on them, then their epilogue
+      f32x4 acc = bv;
+      U3T_MFMA(acc, aw[2], u3_pb[0]);
+      U3T_MFMA(acc, aw[1], u3_pb[1]);
+      U3T_MFMA(acc, aw[0], u3_pb[2]);
+      U3T_MFMA(acc, aw[1], u3_pb[0]);
+      U3T_MFMA(acc, aw[0], u3_pb[1]);
+      U3T_MFMA(acc, aw[0], u3_pb[0]);
+      up += (U3T_TS / 4) * 8;
+      if (j + 1 < U3T_TILES) {
+#pragma unroll
+        for (int pc = 0; pc < 3; ++pc) u3_pb[pc] = *reinterpret_cast<const uint4*>(up + pc * U3T_QU::PS);
+      }
+      // the skip quad fetched two phases ago -> pieces, chunk 0
+      float(&skj)[4] = (j & 1) ? u3_sk2 : sk;
+      ring_store(RU, cs, sk_q, skj);
+      if (j + 2 < U3T_TILES) u3_fetch_skip(skj, j + 2, U3T_TS * (j + 3) > T0);
+      float o[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) o[r] = fmaxf(acc[r], 0.f);
+      if (j == 0 || U3T_TS * (j + 1) > T0) {  // (uniform) the tiles that meet the ends of the signal
+        const int s = U3T_TS * j + mphase - 2 + 4 * (16 * (wv >> 1) + n);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) o[r] = (unsigned)s < (unsigned)T0 ? o[r] : 0.f;
+      }
+      if constexpr (DUMP) {
+        const int s = U3T_TS * j + mphase - 2 + 4 * (16 * (wv >> 1) + n);
+        if ((unsigned)s < (unsigned)T0) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) win_dump_row(a, WD_U3T, win, 4 * quad + r)[s] = o[r];
+        }
+      }
+      ring_store(RU + U3T_CH, ct, quad, o);
+      ct += U3T_TS, cs += U3T_TS;
+      ct = ct >= U3T_RING ? ct - U3T_RING : ct;
+      cs = cs >= U3T_RING ? cs - U3T_RING : cs;
+    };
+    // consumer, phase j: the first K-step's fragments of tile j - 1 are requested, tile j - 2's epilogue runs while they are in
+    // flight, the MFMAs follow (the other K-steps' reads among them).  (Requesting two or more K-steps ahead of the epilogue
+    // spills at 120 registers.)
+    auto u3_consume = [&](const int j) {
+      const bf16_t* const rp0 = RU + quad * U3T_CH + ring_at(cc);  // K-step st: two columns = one plane entry further (mirrored: no wrap)
+      uint4 b[4][3];
+#pragma unroll
+      for (int pc = 0; pc < 3; ++pc) b[0][pc] = *reinterpret_cast<const uint4*>(rp0 + pc * U3T_PS);
+      if (j > 1) u3_finish(j - 2, u3_h);
+      f32x4 sa = {0.f, 0.f, 0.f, 0.f}, sb = bv;
+#pragma unroll
+      for (int st = 0; st < 4; ++st) {
+        if (st > 0) {
+#pragma unroll
+          for (int pc = 0; pc < 3; ++pc) b[st][pc] = *reinterpret_cast<const uint4*>(rp0 + st * 8 + pc * U3T_PS);
+        }
+        U3T_MFMA(sa, aw[st * 3 + 2], b[st][0]);
+        U3T_MFMA(sb, aw[st * 3 + 1], b[st][0]);
+        U3T_MFMA(sa, aw[st * 3 + 1], b[st][1]);
+        U3T_MFMA(sb, aw[st * 3 + 0], b[st][1]);
+        U3T_MFMA(sa, aw[st * 3 + 0], b[st][2]);
+        U3T_MFMA(sb, aw[st * 3 + 0], b[st][0]);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) u3_h[r] = fmaxf(sa[r] + sb[r], 0.f);  // BN + ReLU: all that crosses the barrier
+      cc += U3T_TS;
+      cc = cc >= U3T_RING ? cc - U3T_RING : cc;
+    };
+    // One loop per role, the same thirteen barriers in each (the branch is wave-uniform): what a role carries from phase to
+    // phase -- the producers' fetched fragments and skip quads, the consumers' owed sums and 1 x 1 head -- then costs the other
+    // role no registers.  One loop with both roles in its body spills 41 registers with these prefetches.
+    if (producer) {
+#pragma unroll
+      for (int j = 0; j <= U3T_TILES; ++j) {
+        if (j < U3T_TILES) u3_produce(j);
+        lds_barrier();
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j <= U3T_TILES; ++j) {
+        if (j > 0) u3_consume(j);
+        lds_barrier();
+        U3T_PHASE_STAMP(j)
+      }
+      u3_finish(U3T_TILES - 1, u3_h);  // the last tile's epilogue
     }
 #undef U3T_MFMA
     WIN_STAMP(28)
