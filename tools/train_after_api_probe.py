@@ -27,8 +27,6 @@ if mode != "none":
             r[:] = s
     if mode != "pinned_only":
         m = va.PhaseNet.from_pretrained("volpick").cuda()
-        if len(sys.argv) > 2 and sys.argv[2] == "no_ahead":
-            m._upload_ahead = lambda groups, args: groups
         st = va.Stream([va.Trace(rows[i], dict(network="XX", station=f"S{k}", location="", channel=f"HH{c}", starttime=t0,
                                                sampling_rate=100.0)) for k in range(1 if (len(sys.argv) > 2 and sys.argv[2] == "one_station") else 6) for i, c in enumerate("ZNE")])
         for _ in range(2):

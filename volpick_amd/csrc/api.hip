@@ -2,14 +2,42 @@
 #include <algorithm>
 #include <cmath>
 #include <mutex>
-#include <numeric>
 
+#include "api_host.h"
 #include "net.h"
 #include "prepost.h"
 
 namespace vp {
 const char* last_error();
 }
+
+namespace {
+
+// Grow-only device buffer of `cap` elements, with MIRROR a mapped pinned host block `host` of the same size beside it.
+// Growing drops the contents; zero_new clears a new device block (synchronously).
+template <class T, bool MIRROR = false>
+struct DevBuf {
+  T *p = nullptr, *host = nullptr;
+  size_t cap = 0;
+  int reserve(size_t need, bool zero_new = false) {
+    if (need <= cap) return VP_OK;
+    release();
+    VP_HIP(hipMalloc((void**)&p, need * sizeof(T)));
+    if (zero_new) VP_HIP(hipMemset(p, 0, need * sizeof(T)));
+    if (MIRROR) VP_HIP(hipHostMalloc((void**)&host, need * sizeof(T), hipHostMallocMapped));
+    cap = need;
+    return VP_OK;
+  }
+  void release() {
+    if (p) (void)hipFree(p);
+    if (host) (void)hipHostFree(host);
+    p = host = nullptr;
+    cap = 0;
+  }
+};
+using MirroredBuf = DevBuf<char, true>;  // a trigger result block (vp::ScanLayout) and what the publish kernel copies it to
+
+}  // namespace
 
 struct vp_handle {
   int device = 0;
@@ -25,22 +53,14 @@ struct vp_handle {
   int last_pre_windows = 0;
   int last_out_lo = 0, last_out_hi = 0;  // ... and the kept output range of that batch (Net::out_lo / out_hi)
   // growable device scratch
-  float* d_in = nullptr;    // staged host input (stream or windows)
-  size_t d_in_cap = 0;
-  float* d_pred = nullptr;  // [n_windows][n_out][T] predictions of one annotate call
-  size_t d_pred_cap = 0;
-  float* d_out = nullptr;   // stacked output when the caller's buffer is on the host
-  size_t d_out_cap = 0;
+  DevBuf<float> d_in;    // staged host input (stream or windows)
+  DevBuf<float> d_pred;  // [n_windows][n_out][T] predictions of one annotate call
+  DevBuf<float> d_out;   // stacked output when the caller's buffer is on the host
   // vp_classify_multi: tables (window table, block table, scan rows) and the result block
-  char* d_tab = nullptr;
-  size_t d_tab_cap = 0;
-  char* m_pick_d = nullptr;
-  char* m_pick_h = nullptr;
-  size_t m_pick_bytes = 0;
-  struct Slot {             // one in-flight vp_classify_submit
-    char* d_pick = nullptr;  // trigger results: counters + per-spec on/off/peak/value arrays
-    char* h_pick = nullptr;  // pinned host mirror, filled by ONE async copy per submit
-    size_t pick_bytes = 0;
+  DevBuf<char> d_tab;
+  MirroredBuf m_pick;
+  struct Slot {          // one in-flight vp_classify_submit
+    MirroredBuf pick;    // trigger results; the host mirror is filled by ONE async copy per submit
     hipEvent_t done = nullptr;
     bool busy = false;
     int n_specs = 0, cap = 0;
@@ -50,27 +70,46 @@ struct vp_handle {
 
 namespace {
 
-int grow(float** p, size_t* cap, size_t need) {
-  if (need <= *cap) return VP_OK;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  VP_HIP(hipMalloc(p, need * sizeof(float)));
-  *cap = need;
+// ---- argument checks shared by the entry points ----
+int check_specs(const vp_trigger_spec* specs, int n_specs, int n_out, int min_specs) {
+  VP_REQUIRE(n_specs >= min_specs && n_specs <= 16 && (n_specs == 0 || specs), "bad trigger specs");
+  for (int i = 0; i < n_specs; ++i) {
+    VP_REQUIRE(specs[i].row >= 0 && specs[i].row < n_out, "spec %d: row %d out of range", i, specs[i].row);
+    VP_REQUIRE(specs[i].thr_off <= specs[i].thr_on, "spec %d: thr_off must not exceed thr_on", i);
+  }
   return VP_OK;
 }
 
-int64_t count_windows(int64_t N, int T, int overlap, int64_t* n_regular, int* has_tail) {
-  if (N < T) {
-    *n_regular = 0;
-    *has_tail = 0;
-    return 0;
-  }
-  const int64_t step = T - overlap;
-  *n_regular = (N - T) / step + 1;
-  *has_tail = ((*n_regular - 1) * step + T < N) ? 1 : 0;
-  return *n_regular + *has_tail;
+int check_windowing(int T, int overlap, int blind_l, int blind_r, int stacking) {
+  VP_REQUIRE(overlap >= 0 && overlap < T, "overlap %d must be in [0, %d)", overlap, T);
+  VP_REQUIRE(blind_l >= 0 && blind_r >= 0 && blind_l + blind_r < T, "blinding (%d, %d) leaves no samples", blind_l,
+             blind_r);
+  VP_REQUIRE(stacking == VP_STACK_AVG || stacking == VP_STACK_MAX, "unknown stacking %d", stacking);
+  return VP_OK;
 }
+
+int free_slot(const vp_handle* h, int* slot) {
+  int i = 0;
+  while (i < VP_MAX_INFLIGHT && h->slot[i].busy) ++i;
+  VP_REQUIRE(i < VP_MAX_INFLIGHT, "all %d in-flight slots are busy", VP_MAX_INFLIGHT);
+  *slot = i;
+  return VP_OK;
+}
+
+// Until the scope ends the last layer writes to `y` (null: where it writes anyway) and the plan is told that the caller
+// keeps only the samples [out_lo, out_hi) of every window ((0, 0), the state outside any scope: all of them).
+struct OutputRedirect {
+  vp::Net& net;
+  float* const y_saved;
+  OutputRedirect(vp::Net& n, float* y, int out_lo = 0, int out_hi = 0) : net(n), y_saved(n.y) {
+    if (y) net.y = y;
+    net.out_lo = out_lo, net.out_hi = out_hi;
+  }
+  ~OutputRedirect() {
+    net.y = y_saved;
+    net.out_lo = net.out_hi = 0;
+  }
+};
 
 vp::PreArgs pre_args(const vp_handle* h, const float* src, int dense, long N, long step, long first, int preprocess) {
   const vp::Net& net = h->net;
@@ -276,15 +315,13 @@ int vp_destroy(vp_handle* h) {
   for (auto& e : h->ev)
     if (e) (void)hipEventDestroy(e);
   if (h->stream) (void)hipStreamDestroy(h->stream);
-  if (h->d_in) (void)hipFree(h->d_in);
-  if (h->d_pred) (void)hipFree(h->d_pred);
-  if (h->d_out) (void)hipFree(h->d_out);
-  if (h->d_tab) (void)hipFree(h->d_tab);
-  if (h->m_pick_d) (void)hipFree(h->m_pick_d);
-  if (h->m_pick_h) (void)hipHostFree(h->m_pick_h);
+  h->d_in.release();
+  h->d_pred.release();
+  h->d_out.release();
+  h->d_tab.release();
+  h->m_pick.release();
   for (auto& sl : h->slot) {
-    if (sl.d_pick) (void)hipFree(sl.d_pick);
-    if (sl.h_pick) (void)hipHostFree(sl.h_pick);
+    sl.pick.release();
     if (sl.done) (void)hipEventDestroy(sl.done);
   }
   h->net.release();
@@ -309,20 +346,19 @@ int vp_forward(vp_handle* h, const float* x, int x_mem, int B, int preprocess, f
   vp::Net& net = h->net;
   const int T = net.in_samples;
   const size_t in_w = (size_t)3 * T, out_w = (size_t)net.n_out * T;
-  float* y_saved = net.y;
   VP_HIP(hipEventRecord(h->ev[0], h->stream));
   for (int b0 = 0; b0 < B; b0 += net.max_batch) {
     const int nb = std::min(net.max_batch, B - b0);
     const float* src = x + (size_t)b0 * in_w;
     if (x_mem == VP_MEM_HOST) {
-      int rc = grow(&h->d_in, &h->d_in_cap, (size_t)net.max_batch * in_w);
+      int rc = h->d_in.reserve((size_t)net.max_batch * in_w);
       if (rc != VP_OK) return rc;
-      VP_HIP(hipMemcpyAsync(h->d_in, src, nb * in_w * sizeof(float), hipMemcpyHostToDevice, h->stream));
-      src = h->d_in;
+      VP_HIP(hipMemcpyAsync(h->d_in.p, src, nb * in_w * sizeof(float), hipMemcpyHostToDevice, h->stream));
+      src = h->d_in.p;
     }
-    if (y_mem == VP_MEM_DEVICE) net.y = y + (size_t)b0 * out_w;  // last layer writes straight into y
+    // a device-resident y is written by the last layer itself; otherwise net.y stays and is copied out below
+    const OutputRedirect to_y(net, y_mem == VP_MEM_DEVICE ? y + (size_t)b0 * out_w : nullptr);
     int rc = run_batch(h, pre_args(h, src, 1, 0, 0, 0, preprocess), nb);
-    net.y = y_saved;
     if (rc != VP_OK) return rc;
     if (y_mem == VP_MEM_HOST) {
       VP_HIP(hipMemcpyAsync(y + (size_t)b0 * out_w, net.y, nb * out_w * sizeof(float), hipMemcpyDeviceToHost,
@@ -343,12 +379,9 @@ int64_t vp_window_starts(int64_t N, int in_samples, int overlap, int64_t* starts
     vp::set_error("overlap %d must be in [0, in_samples=%d)", overlap, in_samples);
     return VP_ERR_INVALID;
   }
-  int64_t n_reg;
-  int tail;
-  const int64_t n = count_windows(N, in_samples, overlap, &n_reg, &tail);
-  const int64_t step = in_samples - overlap;
-  for (int64_t i = 0; i < n && i < cap; ++i) starts[i] = (i < n_reg) ? i * step : N - in_samples;
-  return n;
+  const vp::WindowPlan wp(N, in_samples, overlap, 0, 0);
+  for (int64_t i = 0; i < wp.n_windows() && i < cap; ++i) starts[i] = wp.start(i);
+  return wp.n_windows();
 }
 
 // Shared body of vp_annotate / vp_classify: everything up to the stacked (n_out, N) rows in
@@ -359,59 +392,46 @@ static int annotate_device(vp_handle* h, const float* stream, int stream_mem, in
   vp::Net& net = h->net;
   const int T = net.in_samples;
   VP_REQUIRE(N > 0, "N must be positive");
-  VP_REQUIRE(overlap >= 0 && overlap < T, "overlap %d must be in [0, %d)", overlap, T);
-  VP_REQUIRE(blind_l >= 0 && blind_r >= 0 && blind_l + blind_r < T, "blinding (%d, %d) leaves no samples", blind_l,
-             blind_r);
-  VP_REQUIRE(stacking == VP_STACK_AVG || stacking == VP_STACK_MAX, "unknown stacking %d", stacking);
+  int rc = check_windowing(T, overlap, blind_l, blind_r, stacking);
+  if (rc != VP_OK) return rc;
   if (batch <= 0 || batch > net.max_batch) batch = net.max_batch;
 
-  int64_t n_reg;
-  int tail;
-  const int64_t nwin = count_windows(N, T, overlap, &n_reg, &tail);
+  const vp::WindowPlan wp(N, T, overlap, blind_l, blind_r);
+  const int64_t nwin = wp.n_windows();
   if (n_windows) *n_windows = nwin;
-  const long step = T - overlap;
-  // valid (un-blinded) output range: union of [s_i + blind_l, s_i + T - blind_r)
-  int64_t fv = -1, lv = -1;
-  if (nwin > 0) {
-    fv = blind_l;
-    lv = (tail ? N - T : (n_reg - 1) * step) + T - blind_r - 1;
-  }
-  if (first_valid) *first_valid = fv;
-  if (last_valid) *last_valid = lv;
+  if (first_valid) *first_valid = wp.first_valid;
+  if (last_valid) *last_valid = wp.last_valid;
 
   if (h->timing) VP_HIP(hipEventRecord(h->ev[0], h->stream));
   const float* d_stream = stream;
   if (stream_mem == VP_MEM_HOST) {
-    int rc = grow(&h->d_in, &h->d_in_cap, std::max((size_t)3 * N, (size_t)net.max_batch * 3 * T));
+    rc = h->d_in.reserve(std::max((size_t)3 * N, (size_t)net.max_batch * 3 * T));
     if (rc != VP_OK) return rc;
-    VP_HIP(hipMemcpyAsync(h->d_in, stream, (size_t)3 * N * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    d_stream = h->d_in;
+    VP_HIP(hipMemcpyAsync(h->d_in.p, stream, (size_t)3 * N * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    d_stream = h->d_in.p;
   }
   if (nwin > 0) {
     const size_t out_w = (size_t)net.n_out * T;
-    int rc = grow(&h->d_pred, &h->d_pred_cap, (size_t)nwin * out_w);
+    rc = h->d_pred.reserve((size_t)nwin * out_w);
     if (rc != VP_OK) return rc;
-    float* y_saved = net.y;
     for (int64_t w0 = 0; w0 < nwin; w0 += batch) {
       const int nb = (int)std::min<int64_t>(batch, nwin - w0);
-      net.y = h->d_pred + (size_t)w0 * out_w;
-      net.out_lo = blind_l, net.out_hi = T - blind_r;  // what stacking will read of every window
-      rc = run_batch(h, pre_args(h, d_stream, 0, N, step, w0, 1), nb);
-      net.out_lo = net.out_hi = 0;
-      net.y = y_saved;
+      // the range is what stacking will read of every window
+      const OutputRedirect to_pred(net, h->d_pred.p + (size_t)w0 * out_w, blind_l, T - blind_r);
+      rc = run_batch(h, pre_args(h, d_stream, 0, N, wp.step, w0, 1), nb);
       if (rc != VP_OK) return rc;
     }
   }
   if (h->timing) VP_HIP(hipEventRecord(h->ev[1], h->stream));
   vp::StackArgs sa{};
-  sa.pred = h->d_pred;
+  sa.pred = h->d_pred.p;
   sa.out = d_out;
   sa.N = N;
   sa.T = T;
   sa.n_out = net.n_out;
-  sa.step = step;
-  sa.n_regular = n_reg;
-  sa.has_tail = tail;
+  sa.step = wp.step;
+  sa.n_regular = wp.n_regular;
+  sa.has_tail = wp.has_tail;
   sa.blind_l = blind_l;
   sa.blind_r = blind_r;
   sa.mode = stacking;
@@ -440,9 +460,9 @@ int vp_annotate(vp_handle* h, const float* stream, int stream_mem, int64_t N, in
   VP_HIP(hipSetDevice(h->device));
   float* d_out = out;
   if (out_mem == VP_MEM_HOST) {
-    int rc = grow(&h->d_out, &h->d_out_cap, (size_t)h->net.n_out * std::max<int64_t>(N, 1));
+    int rc = h->d_out.reserve((size_t)h->net.n_out * std::max<int64_t>(N, 1));
     if (rc != VP_OK) return rc;
-    d_out = h->d_out;
+    d_out = h->d_out.p;
   }
   int rc = annotate_device(h, stream, stream_mem, N, overlap, blind_l, blind_r, stacking, batch, d_out, first_valid,
                            last_valid, n_windows);
@@ -456,54 +476,21 @@ int vp_annotate(vp_handle* h, const float* stream, int stream_mem, int64_t N, in
 }
 
 // ---- trigger scan of one or more device rows; ONE device->host copy, one synchronisation ----
-struct ScanLayout {
-  size_t header, per_spec, total;
-  int cap;
-};
-static ScanLayout scan_layout(int n_specs, int cap) {
-  ScanLayout L;
-  L.cap = std::max(cap, 1);
-  L.header = ((size_t)n_specs * 2 * sizeof(int) + 255) / 256 * 256;
-  L.per_spec = (size_t)L.cap * (3 * sizeof(int64_t) + sizeof(float));
-  L.per_spec = (L.per_spec + 255) / 256 * 256;
-  L.total = L.header + L.per_spec * n_specs;
-  return L;
-}
-
-// Enqueue the trigger scan of `n_specs` device rows into slot `sl` (no host synchronisation).
-static int scan_submit(vp_handle* h, vp_handle::Slot& sl, const float* const* rows, const int64_t* lens,
-                       const float* thr_on, const float* thr_off, int n_specs, int cap) {
-  const ScanLayout L = scan_layout(n_specs, cap);
-  if (L.total > sl.pick_bytes) {
-    if (sl.d_pick) (void)hipFree(sl.d_pick);
-    if (sl.h_pick) (void)hipHostFree(sl.h_pick);
-    sl.d_pick = sl.h_pick = nullptr;
-    sl.pick_bytes = 0;
-    VP_HIP(hipMalloc((void**)&sl.d_pick, L.total));
-    VP_HIP(hipMemset(sl.d_pick, 0, L.total));  // counters start at zero; publish_kernel re-arms them
-    VP_HIP(hipHostMalloc((void**)&sl.h_pick, L.total, hipHostMallocMapped));
-    sl.pick_bytes = L.total;
-  }
+// Enqueue the trigger scan of rows `specs[i].row` (N samples each) of the device array `rows_dev` into slot `sl`
+// (no host synchronisation).
+static int scan_submit(vp_handle* h, vp_handle::Slot& sl, const float* rows_dev, int64_t N, const vp_trigger_spec* specs,
+                       int n_specs, int cap) {
+  const vp::ScanLayout L(n_specs, cap);
+  int rc = sl.pick.reserve(L.total, true);  // counters start at zero; publish_kernel re-arms them
+  if (rc != VP_OK) return rc;
   if (h->timing) VP_HIP(hipEventRecord(h->ev[3], h->stream));
   for (int i0 = 0; i0 < n_specs; i0 += vp::kMaxPickRows) {
     vp::PickBatch batch{};
-    for (int i = i0; i < n_specs && i < i0 + vp::kMaxPickRows; ++i) {
-      char* base = sl.d_pick + L.header + L.per_spec * i;
-      vp::PickArgs& a = batch.a[batch.n++];
-      a.trace = rows[i];
-      a.n = lens[i] > 0 ? lens[i] : 0;
-      a.thr_on = thr_on[i];
-      a.thr_off = thr_off[i];
-      a.count = (int*)sl.d_pick + 2 * i;
-      a.on = (int64_t*)base;
-      a.off = a.on + L.cap;
-      a.peak = a.off + L.cap;
-      a.value = (float*)(a.peak + L.cap);
-      a.cap = cap;
-    }
+    for (int i = i0; i < n_specs && i < i0 + vp::kMaxPickRows; ++i)
+      batch.a[batch.n++] = L.args(sl.pick.p, i, rows_dev + (size_t)specs[i].row * N, N, specs[i].thr_on, specs[i].thr_off, cap);
     vp::launch_pick(batch, h->stream);
   }
-  vp::launch_publish(sl.d_pick, sl.h_pick, n_specs, cap, (long)L.header, (long)L.per_spec, h->stream);
+  vp::launch_publish(sl.pick.p, sl.pick.host, n_specs, cap, (long)L.header, (long)L.per_spec, h->stream);
   if (h->timing) VP_HIP(hipEventRecord(h->ev[4], h->stream));
   sl.n_specs = n_specs;
   sl.cap = cap;
@@ -513,29 +500,10 @@ static int scan_submit(vp_handle* h, vp_handle::Slot& sl, const float* const* ro
 // After the slot's `done` event: sort each spec's triggers by onset and hand them out.
 static int scan_collect(const vp_handle::Slot& sl, int64_t* on, int64_t* off, int64_t* peak, float* value,
                         int32_t* spec_of, int cap, int* n_found) {
-  const ScanLayout L = scan_layout(sl.n_specs, sl.cap);
-  int total = 0, written = 0;
-  for (int i = 0; i < sl.n_specs; ++i) {
-    const int found = ((const int*)sl.h_pick)[2 * i];
-    total += found;
-    const int m = std::min(found, sl.cap);
-    const char* base = sl.h_pick + L.header + L.per_spec * i;
-    const int64_t* t_on = (const int64_t*)base;
-    const int64_t* t_off = t_on + L.cap;
-    const int64_t* t_pk = t_off + L.cap;
-    const float* t_v = (const float*)(t_pk + L.cap);
-    std::vector<int> order(m);
-    std::iota(order.begin(), order.end(), 0);
-    std::sort(order.begin(), order.end(), [&](int x, int y) { return t_on[x] < t_on[y]; });
-    for (int k = 0; k < m && written < cap; ++k, ++written) {
-      on[written] = t_on[order[k]];
-      off[written] = t_off[order[k]];
-      peak[written] = t_pk[order[k]];
-      value[written] = t_v[order[k]];
-      if (spec_of) spec_of[written] = i;
-    }
-  }
-  *n_found = total;
+  *n_found = vp::collect_rows(vp::ScanLayout(sl.n_specs, sl.cap), sl.pick.host, sl.n_specs, sl.cap, on, off, peak, value, cap, 0,
+                              [&](int i, int r) {
+                                if (spec_of) spec_of[i] = r;
+                              });
   return VP_OK;
 }
 
@@ -545,41 +513,28 @@ int vp_classify_submit(vp_handle* h, int slot, const float* stream, int stream_m
   VP_REQUIRE(h && stream, "null argument");
   VP_REQUIRE(slot >= 0 && slot < VP_MAX_INFLIGHT, "slot %d outside [0, %d)", slot, VP_MAX_INFLIGHT);
   VP_REQUIRE(!h->slot[slot].busy, "slot %d has an uncollected submit", slot);
-  VP_REQUIRE(n_specs >= 0 && n_specs <= 16 && (n_specs == 0 || specs), "bad trigger specs");
   VP_REQUIRE(cap >= 0, "negative cap");
-  VP_HIP(hipSetDevice(h->device));
   const int n_out = h->net.n_out;
-  for (int i = 0; i < n_specs; ++i) {
-    VP_REQUIRE(specs[i].row >= 0 && specs[i].row < n_out, "spec %d: row %d out of range", i, specs[i].row);
-    VP_REQUIRE(specs[i].thr_off <= specs[i].thr_on, "spec %d: thr_off must not exceed thr_on", i);
-  }
+  int rc = check_specs(specs, n_specs, n_out, 0);
+  if (rc != VP_OK) return rc;
+  VP_HIP(hipSetDevice(h->device));
   vp_handle::Slot& sl = h->slot[slot];
   float* d_out = (out && out_mem == VP_MEM_DEVICE) ? out : nullptr;
   if (!d_out) {
     const size_t need = (size_t)n_out * std::max<int64_t>(N, 1);
-    if (need > h->d_out_cap) VP_HIP(hipStreamSynchronize(h->stream));  // in-flight work may still read the old buffer
-    int rc = grow(&h->d_out, &h->d_out_cap, need);
+    if (need > h->d_out.cap) VP_HIP(hipStreamSynchronize(h->stream));  // in-flight work may still read the old buffer
+    rc = h->d_out.reserve(need);
     if (rc != VP_OK) return rc;
-    d_out = h->d_out;
+    d_out = h->d_out.p;
   }
-  int rc = annotate_device(h, stream, stream_mem, N, overlap, blind_l, blind_r, stacking, batch, d_out, &sl.fv, &sl.lv,
-                           &sl.nwin);
+  rc = annotate_device(h, stream, stream_mem, N, overlap, blind_l, blind_r, stacking, batch, d_out, &sl.fv, &sl.lv, &sl.nwin);
   if (rc != VP_OK) return rc;
   if (out && out_mem == VP_MEM_HOST) {
     VP_HIP(hipMemcpyAsync(out, d_out, (size_t)n_out * N * sizeof(float), hipMemcpyDeviceToHost, h->stream));
   }
-  const float* rows[16];
-  int64_t lens[16];
-  float t_on[16], t_off[16];
-  for (int i = 0; i < n_specs; ++i) {
-    rows[i] = d_out + (size_t)specs[i].row * N;  // NaN outside [fv, lv] never triggers
-    lens[i] = N;
-    t_on[i] = specs[i].thr_on;
-    t_off[i] = specs[i].thr_off;
-  }
   sl.n_specs = 0;
   if (n_specs > 0) {
-    rc = scan_submit(h, sl, rows, lens, t_on, t_off, n_specs, cap);
+    rc = scan_submit(h, sl, d_out, N, specs, n_specs, cap);  // NaN outside [fv, lv] never triggers
     if (rc != VP_OK) return rc;
   }
   VP_HIP(hipEventRecord(sl.done, h->stream));
@@ -613,15 +568,11 @@ int vp_classify(vp_handle* h, const float* stream, int stream_mem, int64_t N, in
                 int64_t* off, int64_t* peak, float* value, int32_t* spec_of, int cap, int* n_found) {
   VP_REQUIRE(h && stream && n_found, "null argument");
   VP_REQUIRE(cap >= 0 && (cap == 0 || (on && off && peak && value)), "null output arrays");
-  int slot = -1;
-  for (int i = 0; i < VP_MAX_INFLIGHT; ++i)
-    if (!h->slot[i].busy) {
-      slot = i;
-      break;
-    }
-  VP_REQUIRE(slot >= 0, "all %d in-flight slots are busy", VP_MAX_INFLIGHT);
-  int rc = vp_classify_submit(h, slot, stream, stream_mem, N, overlap, blind_l, blind_r, stacking, batch, specs,
-                              n_specs, out, out_mem, cap);
+  int slot;
+  int rc = free_slot(h, &slot);
+  if (rc != VP_OK) return rc;
+  rc = vp_classify_submit(h, slot, stream, stream_mem, N, overlap, blind_l, blind_r, stacking, batch, specs, n_specs, out,
+                          out_mem, cap);
   if (rc != VP_OK) return rc;
   rc = vp_classify_collect(h, slot, first_valid, last_valid, n_windows, on, off, peak, value, spec_of, cap, n_found);
   if (rc != VP_OK) return rc;
@@ -635,29 +586,15 @@ int vp_classify(vp_handle* h, const float* stream, int stream_mem, int64_t N, in
 int vp_pick_rows(vp_handle* h, const float* rows_dev, int64_t N, const vp_trigger_spec* specs, int n_specs, int64_t* on,
                  int64_t* off, int64_t* peak, float* value, int32_t* spec_of, int cap, int* n_found) {
   VP_REQUIRE(h && rows_dev && n_found && N > 0, "null / empty argument");
-  VP_REQUIRE(n_specs > 0 && n_specs <= 16 && specs, "bad trigger specs");
+  int rc = check_specs(specs, n_specs, h->net.n_out, 1);
+  if (rc != VP_OK) return rc;
   VP_REQUIRE(cap >= 0 && (cap == 0 || (on && off && peak && value)), "null output arrays");
   VP_HIP(hipSetDevice(h->device));
-  int slot = -1;
-  for (int i = 0; i < VP_MAX_INFLIGHT; ++i)
-    if (!h->slot[i].busy) {
-      slot = i;
-      break;
-    }
-  VP_REQUIRE(slot >= 0, "all %d in-flight slots are busy", VP_MAX_INFLIGHT);
-  const float* rows[16];
-  int64_t lens[16];
-  float t_on[16], t_off[16];
-  for (int i = 0; i < n_specs; ++i) {
-    VP_REQUIRE(specs[i].row >= 0 && specs[i].row < h->net.n_out, "spec %d: row %d out of range", i, specs[i].row);
-    VP_REQUIRE(specs[i].thr_off <= specs[i].thr_on, "spec %d: thr_off must not exceed thr_on", i);
-    rows[i] = rows_dev + (size_t)specs[i].row * N;
-    lens[i] = N;
-    t_on[i] = specs[i].thr_on;
-    t_off[i] = specs[i].thr_off;
-  }
+  int slot;
+  rc = free_slot(h, &slot);
+  if (rc != VP_OK) return rc;
   vp_handle::Slot& sl = h->slot[slot];
-  int rc = scan_submit(h, sl, rows, lens, t_on, t_off, n_specs, cap);
+  rc = scan_submit(h, sl, rows_dev, N, specs, n_specs, cap);
   if (rc != VP_OK) return rc;
   VP_HIP(hipStreamSynchronize(h->stream));
   return scan_collect(sl, on, off, peak, value, spec_of, cap, n_found);
@@ -673,19 +610,13 @@ int vp_classify_multi(vp_handle* h, const float* streams, int stream_mem, const 
                       int32_t* spec_of, int32_t* block_of, int cap_per_row, int cap, int* n_found) {
   VP_REQUIRE(h && streams && offsets && lengths && n_found, "null argument");
   VP_REQUIRE(K > 0 && K <= 65535, "block count %d out of range", K);
-  VP_REQUIRE(n_specs >= 0 && n_specs <= 16 && (n_specs == 0 || specs), "bad trigger specs");
   VP_REQUIRE(cap >= 0 && cap_per_row > 0 && (cap == 0 || (on && off && peak && value)), "bad result capacity");
   vp::Net& net = h->net;
   const int T = net.in_samples, n_out = net.n_out;
   VP_REQUIRE(n_out == 3, "vp_classify_multi expects three output rows per block");
-  VP_REQUIRE(overlap >= 0 && overlap < T, "overlap %d must be in [0, %d)", overlap, T);
-  VP_REQUIRE(blind_l >= 0 && blind_r >= 0 && blind_l + blind_r < T, "blinding (%d, %d) leaves no samples", blind_l,
-             blind_r);
-  VP_REQUIRE(stacking == VP_STACK_AVG || stacking == VP_STACK_MAX, "unknown stacking %d", stacking);
-  for (int i = 0; i < n_specs; ++i) {
-    VP_REQUIRE(specs[i].row >= 0 && specs[i].row < n_out, "spec %d: row %d out of range", i, specs[i].row);
-    VP_REQUIRE(specs[i].thr_off <= specs[i].thr_on, "spec %d: thr_off must not exceed thr_on", i);
-  }
+  int rc = check_windowing(T, overlap, blind_l, blind_r, stacking);
+  if (rc == VP_OK) rc = check_specs(specs, n_specs, n_out, 0);
+  if (rc != VP_OK) return rc;
   for (int i = 0; i < VP_MAX_INFLIGHT; ++i) VP_REQUIRE(!h->slot[i].busy, "uncollected vp_classify_submit on this handle");
   if (batch <= 0 || batch > net.max_batch) batch = net.max_batch;
   VP_HIP(hipSetDevice(h->device));
@@ -698,25 +629,23 @@ int vp_classify_multi(vp_handle* h, const float* streams, int stream_mem, const 
   for (int k = 0; k < K; ++k) {
     const int64_t N = lengths[k];
     VP_REQUIRE(N > 0 && offsets[k] >= 0, "block %d: bad offset / length", k);
-    int64_t n_reg;
-    int tail;
-    const int64_t nw = count_windows(N, T, overlap, &n_reg, &tail);
+    const vp::WindowPlan wp(N, T, overlap, blind_l, blind_r);
     vp::StackBlock& b = blocks[k];
     b.off = offsets[k];
     b.N = N;
-    b.n_regular = n_reg;
-    b.has_tail = tail;
+    b.n_regular = wp.n_regular;
+    b.has_tail = wp.has_tail;
     b.w0 = (long)(wtab.size() / 3);
     b.cum = total;
     b.pad = 0;
-    for (int64_t i = 0; i < nw; ++i) {
+    for (int64_t i = 0; i < wp.n_windows(); ++i) {
       wtab.push_back(offsets[k]);
       wtab.push_back(N);
-      wtab.push_back(i < n_reg ? i * step : N - T);
+      wtab.push_back(wp.start(i));
     }
-    if (n_windows) n_windows[k] = nw;
-    if (first_valid) first_valid[k] = nw > 0 ? blind_l : -1;
-    if (last_valid) last_valid[k] = nw > 0 ? (tail ? N - T : (n_reg - 1) * step) + T - blind_r - 1 : -1;
+    if (n_windows) n_windows[k] = wp.n_windows();
+    if (first_valid) first_valid[k] = wp.first_valid;
+    if (last_valid) last_valid[k] = wp.last_valid;
     total += N;
     span = std::max<int64_t>(span, offsets[k] + 3 * N);
     n_max = std::max(n_max, N);
@@ -727,58 +656,34 @@ int vp_classify_multi(vp_handle* h, const float* streams, int stream_mem, const 
   // ---- device buffers ------------------------------------------------------------------------
   const float* d_streams = streams;
   if (stream_mem == VP_MEM_HOST) {
-    int rc = grow(&h->d_in, &h->d_in_cap, std::max((size_t)span, (size_t)net.max_batch * 3 * T));
+    rc = h->d_in.reserve(std::max((size_t)span, (size_t)net.max_batch * 3 * T));
     if (rc != VP_OK) return rc;
-    VP_HIP(hipMemcpyAsync(h->d_in, streams, (size_t)span * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    d_streams = h->d_in;
+    VP_HIP(hipMemcpyAsync(h->d_in.p, streams, (size_t)span * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    d_streams = h->d_in.p;
   }
   float* d_out = (out && out_mem == VP_MEM_DEVICE) ? out : nullptr;
   if (!d_out) {
-    int rc = grow(&h->d_out, &h->d_out_cap, (size_t)span);
+    rc = h->d_out.reserve((size_t)span);
     if (rc != VP_OK) return rc;
-    d_out = h->d_out;
+    d_out = h->d_out.p;
   }
   const size_t wt_bytes = (wtab.size() * sizeof(long) + 255) / 256 * 256;
   const size_t bt_bytes = ((size_t)K * sizeof(vp::StackBlock) + 255) / 256 * 256;
   const size_t rt_bytes = ((size_t)std::max(R, 1) * sizeof(vp::PickArgs) + 255) / 256 * 256;
-  if (wt_bytes + bt_bytes + rt_bytes > h->d_tab_cap) {
-    if (h->d_tab) (void)hipFree(h->d_tab);
-    h->d_tab = nullptr;
-    h->d_tab_cap = 0;
-    VP_HIP(hipMalloc((void**)&h->d_tab, wt_bytes + bt_bytes + rt_bytes));
-    h->d_tab_cap = wt_bytes + bt_bytes + rt_bytes;
-  }
-  long* d_wtab = reinterpret_cast<long*>(h->d_tab);
-  vp::StackBlock* d_blocks = reinterpret_cast<vp::StackBlock*>(h->d_tab + wt_bytes);
-  vp::PickArgs* d_rows = reinterpret_cast<vp::PickArgs*>(h->d_tab + wt_bytes + bt_bytes);
-  const ScanLayout L = scan_layout(std::max(R, 1), cap_per_row);
-  if (L.total > h->m_pick_bytes) {
-    if (h->m_pick_d) (void)hipFree(h->m_pick_d);
-    if (h->m_pick_h) (void)hipHostFree(h->m_pick_h);
-    h->m_pick_d = h->m_pick_h = nullptr;
-    h->m_pick_bytes = 0;
-    VP_HIP(hipMalloc((void**)&h->m_pick_d, L.total));
-    VP_HIP(hipHostMalloc((void**)&h->m_pick_h, L.total, hipHostMallocMapped));
-    h->m_pick_bytes = L.total;
-  }
-  VP_HIP(hipMemsetAsync(h->m_pick_d, 0, L.header, h->stream));  // counters
+  rc = h->d_tab.reserve(wt_bytes + bt_bytes + rt_bytes);
+  if (rc != VP_OK) return rc;
+  long* d_wtab = reinterpret_cast<long*>(h->d_tab.p);
+  vp::StackBlock* d_blocks = reinterpret_cast<vp::StackBlock*>(h->d_tab.p + wt_bytes);
+  vp::PickArgs* d_rows = reinterpret_cast<vp::PickArgs*>(h->d_tab.p + wt_bytes + bt_bytes);
+  const vp::ScanLayout L(std::max(R, 1), cap_per_row);
+  rc = h->m_pick.reserve(L.total, false);
+  if (rc != VP_OK) return rc;
+  VP_HIP(hipMemsetAsync(h->m_pick.p, 0, L.header, h->stream));  // counters
   std::vector<vp::PickArgs> rows(R);
   for (int k = 0; k < K; ++k)
-    for (int i = 0; i < n_specs; ++i) {
-      const int r = k * n_specs + i;
-      char* base = h->m_pick_d + L.header + L.per_spec * r;
-      vp::PickArgs& a = rows[r];
-      a.trace = d_out + offsets[k] + (size_t)specs[i].row * lengths[k];
-      a.n = lengths[k];
-      a.thr_on = specs[i].thr_on;
-      a.thr_off = specs[i].thr_off;
-      a.count = (int*)h->m_pick_d + 2 * r;
-      a.on = (int64_t*)base;
-      a.off = a.on + L.cap;
-      a.peak = a.off + L.cap;
-      a.value = (float*)(a.peak + L.cap);
-      a.cap = cap_per_row;
-    }
+    for (int i = 0; i < n_specs; ++i)
+      rows[k * n_specs + i] = L.args(h->m_pick.p, k * n_specs + i, d_out + offsets[k] + (size_t)specs[i].row * lengths[k],
+                                     lengths[k], specs[i].thr_on, specs[i].thr_off, cap_per_row);
   if (W > 0) VP_HIP(hipMemcpyAsync(d_wtab, wtab.data(), wtab.size() * sizeof(long), hipMemcpyHostToDevice, h->stream));
   VP_HIP(hipMemcpyAsync(d_blocks, blocks.data(), (size_t)K * sizeof(vp::StackBlock), hipMemcpyHostToDevice, h->stream));
   if (R > 0) VP_HIP(hipMemcpyAsync(d_rows, rows.data(), (size_t)R * sizeof(vp::PickArgs), hipMemcpyHostToDevice, h->stream));
@@ -787,21 +692,19 @@ int vp_classify_multi(vp_handle* h, const float* streams, int stream_mem, const 
   // ---- forward over all windows, stack, scan ------------------------------------------------
   if (W > 0) {
     const size_t out_w = (size_t)n_out * T;
-    int rc = grow(&h->d_pred, &h->d_pred_cap, (size_t)W * out_w);
+    rc = h->d_pred.reserve((size_t)W * out_w);
     if (rc != VP_OK) return rc;
-    float* y_saved = net.y;
     for (int64_t w0 = 0; w0 < W; w0 += batch) {
       const int nb = (int)std::min<int64_t>(batch, W - w0);
       vp::PreArgs pa = pre_args(h, d_streams, 0, 0, step, w0, 1);
       pa.table = d_wtab;
-      net.y = h->d_pred + (size_t)w0 * out_w;
+      const OutputRedirect to_pred(net, h->d_pred.p + (size_t)w0 * out_w);
       rc = run_batch(h, pa, nb);
-      net.y = y_saved;
       if (rc != VP_OK) return rc;
     }
   }
   vp::StackMultiArgs sa{};
-  sa.pred = h->d_pred;
+  sa.pred = h->d_pred.p;
   sa.out = d_out;
   sa.blocks = d_blocks;
   sa.n_blocks = K;
@@ -817,36 +720,17 @@ int vp_classify_multi(vp_handle* h, const float* streams, int stream_mem, const 
     VP_HIP(hipMemcpyAsync(out, d_out, (size_t)span * sizeof(float), hipMemcpyDeviceToHost, h->stream));
   if (R > 0) {
     vp::launch_pick_table(d_rows, R, n_max, h->stream);
-    vp::launch_publish_table(h->m_pick_d, h->m_pick_h, R, cap_per_row, (long)L.header, (long)L.per_spec, h->stream);
+    vp::launch_publish_table(h->m_pick.p, h->m_pick.host, R, cap_per_row, (long)L.header, (long)L.per_spec, h->stream);
   }
   VP_HIP(hipStreamSynchronize(h->stream));
 
   // ---- results: per (block, spec) sorted by onset; a row that overflowed its cap_per_row is reported whole
   // in *n_found (found > written tells the caller to retry with more room) ---------------------------------
-  int total_found = 0, written = 0;
-  for (int r = 0; r < R; ++r) {
-    const int found = ((const int*)h->m_pick_h)[2 * r];
-    total_found += found;
-    const int m = std::min(found, cap_per_row);
-    const char* base = h->m_pick_h + L.header + L.per_spec * r;
-    const int64_t* t_on = (const int64_t*)base;
-    const int64_t* t_off = t_on + L.cap;
-    const int64_t* t_pk = t_off + L.cap;
-    const float* t_v = (const float*)(t_pk + L.cap);
-    std::vector<int> order(m);
-    std::iota(order.begin(), order.end(), 0);
-    std::sort(order.begin(), order.end(), [&](int x, int y) { return t_on[x] < t_on[y]; });
-    for (int k = 0; k < m && written < cap; ++k, ++written) {
-      on[written] = t_on[order[k]];
-      off[written] = t_off[order[k]];
-      peak[written] = t_pk[order[k]];
-      value[written] = t_v[order[k]];
-      if (spec_of) spec_of[written] = r % n_specs;
-      if (block_of) block_of[written] = r / n_specs;
-    }
-    if (found > cap_per_row) total_found = std::max(total_found, cap + 1);  // forces the retry path
-  }
-  *n_found = total_found;
+  *n_found = vp::collect_rows(L, h->m_pick.host, R, cap_per_row, on, off, peak, value, cap, cap + 1 /* forces the retry path */,
+                              [&](int i, int r) {
+                                if (spec_of) spec_of[i] = r % n_specs;
+                                if (block_of) block_of[i] = r / n_specs;
+                              });
   return VP_OK;
 }
 
@@ -873,17 +757,12 @@ int vp_pick(vp_handle* h, const float* trace, int trace_mem, int64_t n, float th
     return vp::pick_host(trace, n, thr_on, thr_off, on, off, peak, value, cap, n_found);
   }
   VP_HIP(hipSetDevice(h->device));
-  const float* rows[1] = {trace};
-  const int64_t lens[1] = {n};
-  int slot = -1;
-  for (int i = 0; i < VP_MAX_INFLIGHT; ++i)
-    if (!h->slot[i].busy) {
-      slot = i;
-      break;
-    }
-  VP_REQUIRE(slot >= 0, "all %d in-flight slots are busy", VP_MAX_INFLIGHT);
+  const vp_trigger_spec spec{0, thr_on, thr_off};  // the trace is row 0 of itself
+  int slot;
+  int rc = free_slot(h, &slot);
+  if (rc != VP_OK) return rc;
   vp_handle::Slot& sl = h->slot[slot];
-  int rc = scan_submit(h, sl, rows, lens, &thr_on, &thr_off, 1, cap);
+  rc = scan_submit(h, sl, trace, n, &spec, 1, cap);
   if (rc != VP_OK) return rc;
   VP_HIP(hipStreamSynchronize(h->stream));
   if (h->timing) (void)hipEventElapsedTime(&h->stage_ms[3], h->ev[3], h->ev[4]);
@@ -894,7 +773,7 @@ int vp_pick(vp_handle* h, const float* trace, int trace_mem, int64_t n, float th
   const int all = *n_found;
   std::vector<int64_t> t_on(all), t_off(all), t_pk(all);
   std::vector<float> t_v(all);
-  rc = scan_submit(h, sl, rows, lens, &thr_on, &thr_off, 1, all);
+  rc = scan_submit(h, sl, trace, n, &spec, 1, all);
   if (rc != VP_OK) return rc;
   VP_HIP(hipStreamSynchronize(h->stream));
   int again = 0;
@@ -921,9 +800,9 @@ int vp_pick_windows(vp_handle* h, const float* prob, int prob_mem, int B, int n_
   const size_t n_prob = (size_t)B * n_rows * T;
   // scratch layout (floats): [prob copy if host][lo B][hi B][count B][peak B*K][value B*K]
   const size_t need = (prob_mem == VP_MEM_HOST ? n_prob : 0) + (size_t)B * 3 + (size_t)B * K * 2 + 64;
-  int rc = grow(&h->d_in, &h->d_in_cap, std::max(need, (size_t)h->net.max_batch * 3 * T));
+  int rc = h->d_in.reserve(std::max(need, (size_t)h->net.max_batch * 3 * T));
   if (rc != VP_OK) return rc;
-  float* p = h->d_in;
+  float* p = h->d_in.p;
   const float* d_prob = prob;
   if (prob_mem == VP_MEM_HOST) {
     VP_HIP(hipMemcpyAsync(p, prob, n_prob * sizeof(float), hipMemcpyHostToDevice, h->stream));
@@ -1067,6 +946,20 @@ struct ProfilePre {
   }
 };
 
+// One launch of the plan: once to warm, then `iters` times back to back between two events on the handle's stream.
+static int time_step(vp_handle* h, int B, int iters, int index, float* ms) {
+  vp::Net& net = h->net;
+  int rc = net.steps[index].run(net, B, h->stream);  // warm
+  if (rc != 0) return rc;
+  VP_HIP(hipEventRecord(h->ev[0], h->stream));
+  for (int i = 0; i < iters; ++i) net.steps[index].run(net, B, h->stream);
+  VP_HIP(hipEventRecord(h->ev[1], h->stream));
+  VP_HIP(hipStreamSynchronize(h->stream));
+  VP_HIP(hipEventElapsedTime(ms, h->ev[0], h->ev[1]));
+  *ms /= iters;
+  return VP_OK;
+}
+
 // Runs every launch of the forward pass `iters` times on B windows (whatever the input
 // tensor currently holds) and reports the mean duration of each launch in milliseconds,
 // measured with HIP events on the handle's stream.
@@ -1078,15 +971,8 @@ int vp_profile_steps(vp_handle* h, int B, int iters, float* step_ms, int cap) {
   ProfilePre pre_scope(h, B);
   const int n = (int)net.steps.size();
   for (int s = 0; s < n && s < cap; ++s) {
-    int rc = net.steps[s].run(net, B, h->stream);  // warm
-    if (rc != 0) return rc;
-    VP_HIP(hipEventRecord(h->ev[0], h->stream));
-    for (int i = 0; i < iters; ++i) net.steps[s].run(net, B, h->stream);
-    VP_HIP(hipEventRecord(h->ev[1], h->stream));
-    VP_HIP(hipStreamSynchronize(h->stream));
-    float ms = 0.f;
-    VP_HIP(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-    step_ms[s] = ms / iters;
+    int rc = time_step(h, B, iters, s, &step_ms[s]);
+    if (rc != VP_OK) return rc;
   }
   return VP_OK;
 }
@@ -1100,15 +986,7 @@ int vp_profile_one_step(vp_handle* h, int B, int iters, int index, float* ms) {
   VP_REQUIRE(index >= 0 && index < (int)net.steps.size(), "step index %d outside [0, %d)", index, (int)net.steps.size());
   VP_HIP(hipSetDevice(h->device));
   ProfilePre pre_scope(h, B);
-  int rc = net.steps[index].run(net, B, h->stream);  // warm
-  if (rc != 0) return rc;
-  VP_HIP(hipEventRecord(h->ev[0], h->stream));
-  for (int i = 0; i < iters; ++i) net.steps[index].run(net, B, h->stream);
-  VP_HIP(hipEventRecord(h->ev[1], h->stream));
-  VP_HIP(hipStreamSynchronize(h->stream));
-  VP_HIP(hipEventElapsedTime(ms, h->ev[0], h->ev[1]));
-  *ms /= iters;
-  return VP_OK;
+  return time_step(h, B, iters, index, ms);
 }
 
 // Mean duration of ONE step measured where it runs in practice: the whole step list executes in order

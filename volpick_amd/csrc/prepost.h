@@ -1,5 +1,6 @@
 // Argument blocks of the HBM-bound pre/post kernels (prepost.hip).
 #pragma once
+#include "pick_args.h"  // PickArgs
 #include "vp_common.h"
 
 namespace vp {
@@ -131,15 +132,6 @@ struct StackMultiArgs {
 };
 int launch_stack_multi(const StackMultiArgs& a, hipStream_t stream);
 
-struct PickArgs {
-  const float* trace;
-  long n;
-  float thr_on, thr_off;
-  int64_t *on, *off, *peak;
-  float* value;
-  int cap;
-  int* count;
-};
 constexpr int kMaxPickRows = 4;
 struct PickBatch {
   PickArgs a[kMaxPickRows];
