@@ -433,6 +433,56 @@ int vp_resample_fourier_bench(int device_id, const void* in_dev, int in_kind, in
                               float* ms_total, float* ms_forward);
 
 /* ---------------------------------------------------------------------------------------------
+ * Filtering and detrending on the device: ObsPy's trace.filter(...) and trace.detrend(...), which
+ * volpick_amd/signal.py restates on the host with scipy.
+ *
+ *     y = sosfilt(sos, x)                              zerophase == 0
+ *     y = sosfilt(sos, sosfilt(sos, x)[::-1])[::-1]    zerophase != 0
+ *
+ * from zero state, edge transients included.  in_dev: n samples in device memory, int32, float32 or float64 (in_kind).
+ * sos: HOST array of n_sections rows b0 b1 b2 a0 a1 a2 (scipy's layout, a0 == 1) in double; 1 <= n_sections <= 4, which
+ * covers ObsPy's 4-corner low-pass and high-pass (2 sections) and band-pass and band-stop (4); a first-order section
+ * (b2 == a2 == 0) is fine.  out_dev: n float32 samples in device memory; it must not overlap in_dev.  Coefficients,
+ * state and the intermediate of the zero-phase form are float64; the only rounding to float32 is the final store, so
+ * |y - scipy's float64 answer| <= 2^-24 |y| plus float64 noise (tests: 2^-22 max|x| on every sample).
+ *
+ * Scheme: the filter state z (2 doubles per section) is linear in itself, z <- A z + B x per sample, so a run of L samples
+ * from state z0 ends in A^L z0 + (its end from zero state).  A pass is cut into tiles of 8192 samples and pieces of 32;
+ * the host squares A into the table A^(32 2^k), k = 0..15, and three launches carry the state EXACTLY across every seam:
+ * per tile, a scan of the pieces' zero-state ends to the tile's; one workgroup that scans the tiles' ends, 256 at a time,
+ * to every tile's true start state; per tile, the scan again from that state and every piece run from its true start.
+ * No pole radius is too close to 1 for it (unlike the warm-up of vp_decimate_lowpass).  Order between tiles comes from
+ * the launch boundaries alone; no atomics: the same call gives the same bits twice.
+ *
+ * Non-finite input behaves as the whole-trace recursion does: one pass is right ahead of the first NaN and NaN from it on
+ * (an Inf turns into NaN within the samples the recursion itself needs); a zero-phase call is NaN everywhere.
+ *
+ * VP_ERR_INVALID, out_dev untouched: a null pointer, an unknown in_kind, n < 0, n_sections outside 1..4, a0 != 1, a
+ * non-finite coefficient, a section with a pole of radius >= 1, out_dev overlapping in_dev.  n == 0 does nothing.
+ * VP_ERR_NOMEM: the scratch cannot be allocated.  Runs on the device's null stream and returns after the work is done, as
+ * vp_decimate_lowpass does; calls on one device are serialised.
+ *
+ * The scratch (the table, 128 bytes per tile, 8 bytes per sample for a zero-phase call; a detrend's partial sums) is kept
+ * per device, grow-only, between calls; vp_sos_filter_release_scratch frees it (bytes_freed may be NULL) -- the other
+ * release calls do not touch it.  vp_sos_filter_bench: mean time in ms (HIP events on a stream of its own, three untimed
+ * repetitions first) of `iters` repetitions of the whole filter (ms_total) and of one pass's carry launch alone
+ * (ms_carry, may be NULL): bench only.
+ *
+ * vp_detrend: out = x minus its mean (VP_DETREND_DEMEAN, ObsPy's "demean" / "constant"), minus its least-squares line
+ * (VP_DETREND_LINEAR, scipy.signal.detrend) or minus the line through its first and last sample
+ * (VP_DETREND_SIMPLE: x[i] - (x[0] + i (x[n-1] - x[0]) / (n - 1)), ObsPy's default).  The sums are float64 in a fixed order
+ * (per-workgroup partials, then one workgroup), the index centred on (n - 1) / 2 for the line; out_dev is float32 and must
+ * not overlap in_dev.  VP_ERR_INVALID: as above, an unknown type, a line through fewer than two samples.  n == 0 with
+ * VP_DETREND_DEMEAN does nothing. */
+int vp_sos_filter(int device_id, const void* in_dev, int in_kind, int64_t n, const double* sos, int n_sections,
+                  int zerophase, float* out_dev);
+int vp_sos_filter_release_scratch(int device_id, size_t* bytes_freed);
+int vp_sos_filter_bench(int device_id, const void* in_dev, int in_kind, int64_t n, const double* sos, int n_sections,
+                        int zerophase, float* out_dev, int iters, float* ms_total, float* ms_carry);
+enum { VP_DETREND_DEMEAN = 0, VP_DETREND_LINEAR = 1, VP_DETREND_SIMPLE = 2 };
+int vp_detrend(int device_id, const void* in_dev, int in_kind, int64_t n, int type, float* out_dev);
+
+/* ---------------------------------------------------------------------------------------------
  * PhaseNet training step (BASELINE config 5): what one
  * PhaseNetLit.training_step + Adam optimizer.step of the reference computes
  * (the reference's volpick/model/models.py:34-51 vector_cross_entropy, :160-164 training_step,

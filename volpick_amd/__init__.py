@@ -13,5 +13,6 @@ from .stream import Stream, Trace, UTCDateTime, pinned_array, to_device  # noqa:
 from ._lib import VolpickHipError  # noqa: F401
 from .io import read  # noqa: F401
 from .attributes import bank_attributes, pick_attributes, plan_rows  # noqa: F401
+from .signal import butter_sos, detrend_array, detrend_device, filter_array, sos_filter_device  # noqa: F401
 
 __version__ = "0.1.0"

@@ -92,6 +92,8 @@ class VpMseedRecord(C.Structure):
 
 VP_SAMPLES_INT32, VP_SAMPLES_FLOAT32, VP_SAMPLES_FLOAT64 = 0, 1, 2
 
+VP_DETREND_DEMEAN, VP_DETREND_LINEAR, VP_DETREND_SIMPLE = 0, 1, 2
+
 VP_ATTR_DEMEAN, VP_ATTR_MAX_WINDOW, VP_ATTR_OUT = 1, 2048, 14
 
 
@@ -250,6 +252,13 @@ SIGNATURES = {
         [C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_double, C.c_double, C.c_int64, C.c_double, C.c_double, C.c_void_p,
          C.c_int64, C.c_int, _FP, _FP],
     ),
+    "vp_sos_filter": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int64, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_void_p]),
+    "vp_sos_filter_release_scratch": (C.c_int, [C.c_int, C.POINTER(C.c_size_t)]),
+    "vp_sos_filter_bench": (
+        C.c_int,
+        [C.c_int, C.c_void_p, C.c_int, C.c_int64, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_void_p, C.c_int, _FP, _FP],
+    ),
+    "vp_detrend": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p]),
     "vp_train_create": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(_H)]),
     "vp_train_create_dtype": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(_H)]),
     "vp_train_dtype": (C.c_int, [_H]),

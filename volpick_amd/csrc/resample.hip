@@ -24,25 +24,15 @@
 #include <cmath>
 #include <mutex>
 
-#include "vp_common.h"
+#include "sos_tile.h"  // DT, DC, DTILE, DMAXS, SosArg, phys(): shared with sosfilt.hip
 
 namespace vp {
 namespace {
 
-constexpr int DT = 256;             // threads per workgroup
-constexpr int DC = 32;              // samples per thread
-constexpr int DTILE = DT * DC;      // samples per workgroup
 constexpr int DHALO = 1024;         // room for the warm-up ahead of a tile (a multiple of DC)
-constexpr int DMAXS = 4;            // second-order sections the kernel is instantiated for
 constexpr int DLDS = (DHALO + DTILE) / DC * (DC + 1);  // doubles
 constexpr size_t DLDS_BYTES = (size_t)DLDS * sizeof(double);
-
-struct SosArg {
-  double c[DMAXS][5];  // b0 b1 b2 a1 a2 (a0 == 1)
-};
-
-__device__ __forceinline__ int phys(const int q) { return q + (q >> 5); }
-static_assert(DC == 32 && DHALO % DC == 0, "phys() is written for pieces of 32");
+static_assert(DHALO % DC == 0, "the halo is a whole number of pieces");
 
 // One pass.  Position m counts samples in the order the pass visits them: element m of the pass is in[m] (forward) or
 // in[n - 1 - m] (REV).  Forward: f_out[m] for every m.  REV: y_out[j] = (float) result at element j * factor of the
@@ -170,19 +160,7 @@ DecimateScratch& decimate_scratch(int device) {
 
 // Samples after which the response to a wrong starting state has decayed by 2^-40: from the largest pole radius.
 int warmup_length(const double* sos, int ns, double* r_out) {
-  double r = 0.0;
-  for (int s = 0; s < ns; ++s) {
-    const double a1 = sos[6 * s + 4], a2 = sos[6 * s + 5];
-    const double disc = a1 * a1 - 4.0 * a2;
-    double rs;
-    if (disc < 0.0) {
-      rs = std::sqrt(a2);  // complex pair: |z|^2 = a2
-    } else {
-      const double q = std::sqrt(disc);
-      rs = std::fmax(std::fabs(-a1 + q), std::fabs(-a1 - q)) * 0.5;
-    }
-    r = std::fmax(r, rs);
-  }
+  const double r = sos_pole_radius(sos, ns);
   *r_out = r;
   if (!(r < 1.0)) return -1;
   if (r < 1e-12) return 2 * ns;

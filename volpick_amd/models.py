@@ -99,9 +99,12 @@ class WaveformModel:
     _known_args = {"batch_size", "overlap", "stacking", "blinding", "parallelism", "copy", "strict",
                    "flexible_horizontal_components", "stride"}
 
-    def __init__(self, component_order="ZNE", norm="peak", **kwargs):
+    def __init__(self, component_order="ZNE", norm="peak", filter_args=None, filter_kwargs=None, **kwargs):
         self.component_order = component_order
         self.norm = norm
+        # SeisBench: ``trace.filter(*filter_args, **filter_kwargs)`` on every trace inside annotate() / classify()
+        self.filter_args = tuple(filter_args) if filter_args is not None else None
+        self.filter_kwargs = dict(filter_kwargs) if filter_kwargs is not None else None
         self.default_args = {}
         self.weights_docstring = None
         self._weights_metadata = None
@@ -207,7 +210,17 @@ class WaveformModel:
         return out
 
     def get_model_args(self):
-        return {"component_order": self.component_order, "norm": self.norm}
+        args = {"component_order": self.component_order, "norm": self.norm}
+        if self.filter_args is not None or self.filter_kwargs is not None:  # absent from the JSON of a model without a filter
+            args["filter_args"] = list(self.filter_args) if self.filter_args is not None else None
+            args["filter_kwargs"] = self.filter_kwargs
+        return args
+
+    def _stream_filter(self):
+        """(args, kwargs) of the filter annotate() / classify() apply to every trace, or None."""
+        if self.filter_args is None and self.filter_kwargs is None:
+            return None
+        return self.filter_args or (), self.filter_kwargs or {}
 
     def save(self, path, weights_docstring="", version_str=None):
         """Write ``<path>.json[.vN]`` + ``<path>.pt[.vN]`` in the SeisBench model-zoo format
@@ -651,7 +664,7 @@ class WaveformModel:
         """Sliding-window probability traces, one per label, named ``<Model>_<label>``."""
         args = self._argdict(kwargs)
         out = Stream()
-        for grp in _group_stream(stream, self.component_order, self.sampling_rate, copy, self.in_samples):
+        for grp in _group_stream(stream, self.component_order, self.sampling_rate, copy, self.in_samples, self._stream_filter()):
             long_block = self._is_long(grp["data"].shape[1], args)
             dev_out, fv, lv, nw = (self._annotate_segments if long_block else self._annotate_block)(grp["data"], args)
             if nw == 0 or fv < 0:
@@ -719,7 +732,7 @@ class WaveformModel:
                 if tm is not None:
                     tm["emit_records_ms"] = tm.get("emit_records_ms", 0.0) + (time.perf_counter() - t2) * 1e3
 
-        for grp in _group_stream(stream, self.component_order, sr, copy, self.in_samples):
+        for grp in _group_stream(stream, self.component_order, sr, copy, self.in_samples, self._stream_filter()):
             if self._is_long(grp["data"].shape[1], args):  # a day-long block: its segments occupy all contexts
                 for g0, job in pending:
                     emit(g0, self._collect_block(job, args, specs, True)[0])
@@ -863,16 +876,39 @@ class _Rows:
 
 
 # --------------------------------------------------------------------------- stream handling
-def _group_stream(stream, component_order, sampling_rate, copy, in_samples):
+# SeisBench's annotate() runs annotate_stream_pre -- the model's filter -- ahead of its resampling: every trace is filtered at
+# its OWN rate, then brought to the model's.
+FILTER_BEFORE_RESAMPLE = True
+
+
+def _prepare_trace(tr, sampling_rate, copy, stream_filter):
+    """One trace of the caller's stream as the grouping takes it: filtered (if the model has a filter) and at the model's rate.
+    With ``copy`` the caller's trace is never modified; without, it is processed in place, as upstream does."""
+    from .resample import resample_trace
+
+    def filt(t, may_modify):
+        if stream_filter is None:
+            return t
+        from .signal import filtered_copy
+
+        args, kwargs = stream_filter
+        return t.filter(*args, **kwargs) if may_modify else filtered_copy(t, *args, **kwargs)
+
+    if FILTER_BEFORE_RESAMPLE:
+        out = filt(tr, not copy)
+        return resample_trace(out, sampling_rate, copy and out is tr, fourier_on_device=True)
+    out = resample_trace(tr, sampling_rate, copy, fourier_on_device=True)
+    return filt(out, not copy or out is not tr)
+
+
+def _group_stream(stream, component_order, sampling_rate, copy, in_samples, stream_filter=None):
     """Yield one dict per contiguous block of one instrument: data (3,N) float32 in
     ``component_order`` (missing components / gaps inside a block zero-filled), start time and
     ids.  In-repo twin of the array assembly: volpick/data/convert.py:26-70."""
-    from .resample import resample_trace
-
     # traces at the model's rate are never modified, so ``copy`` needs no deep copy for them; the others are
     # resampled as SeisBench's annotate() does (on copies, or in place with copy=False); device-backed ones on the device,
     # whichever branch of the rule they take
-    traces = [resample_trace(tr, float(sampling_rate), copy, fourier_on_device=True) for tr in stream]
+    traces = [_prepare_trace(tr, float(sampling_rate), copy, stream_filter) for tr in stream]
     if len(traces) == 0:
         return
     groups = {}

@@ -197,6 +197,21 @@ class Trace:
     def copy(self):
         return Trace(self.data.copy(), self.stats.copy())
 
+    def filter(self, type, **options):
+        """ObsPy's ``Trace.filter``: ``lowpass`` / ``highpass`` (``freq``), ``bandpass`` / ``bandstop`` (``freqmin``,
+        ``freqmax``); ``corners=4``, ``zerophase=False``.  In place, returns ``self``.  A device-backed trace is filtered on the
+        device (float64 state, float32 samples) and stays there; a host trace becomes float64, as in ObsPy."""
+        from .signal import filter_trace
+
+        return filter_trace(self, type, **options)
+
+    def detrend(self, type="simple"):
+        """ObsPy's ``Trace.detrend`` for ``simple``, ``linear``, ``demean`` / ``constant``.  In place, returns ``self``; device-backed
+        traces on the device, as :meth:`filter`."""
+        from .signal import detrend_trace
+
+        return detrend_trace(self, type)
+
     def __len__(self):
         return int(self.stats["npts"])
 
@@ -235,6 +250,16 @@ class Stream:
 
     def copy(self):
         return Stream([t.copy() for t in self.traces])
+
+    def filter(self, type, **options):
+        for tr in self.traces:
+            tr.filter(type, **options)
+        return self
+
+    def detrend(self, type="simple"):
+        for tr in self.traces:
+            tr.detrend(type)
+        return self
 
     def sort(self, keys=("network", "station", "location", "channel", "starttime")):
         self.traces.sort(key=lambda t: tuple(str(t.stats[k]) if k != "starttime" else t.stats[k]._us for k in keys))
