@@ -28,9 +28,9 @@
 // largest window / bin count: 29 KB at the defaults (five workgroups per CU), 80 KB + magnitudes at the cap of 2048.
 #include <algorithm>
 #include <cmath>
-#include <mutex>
 
 #include "batchgen.h"
+#include "device_scratch.h"
 
 namespace vp {
 namespace {
@@ -261,30 +261,8 @@ __global__ __launch_bounds__(AT) void attributes_kernel(const AttrArgs a) {
 
 // Per device, grow-only, reused from call to call: the staged rows, the dead-component sums and, for a host `out`, the
 // result.
-struct AttrScratch {
-  std::mutex mu;
-  void* p = nullptr;
-  size_t cap = 0;
-  int grow(size_t bytes, void** out) {
-    if (bytes > cap) {
-      if (p) (void)hipFree(p);
-      p = nullptr;
-      cap = 0;
-      const size_t want = bytes + bytes / 8 + 4096;
-      if (hipMalloc(&p, want) != hipSuccess) {
-        (void)hipGetLastError();
-        p = nullptr;
-        set_error("vp_attributes: cannot allocate %zu bytes of device scratch", want);
-        return VP_ERR_NOMEM;
-      }
-      cap = want;
-    }
-    *out = p;
-    return VP_OK;
-  }
-};
-AttrScratch& attr_scratch(int device) {
-  static AttrScratch pool[64];
+DeviceScratch<1>& attr_scratch(int device) {
+  static DeviceScratch<1> pool[64];
   return pool[(unsigned)device % 64];
 }
 
@@ -367,15 +345,16 @@ int run_attributes(const char* who, int device, const float* data, const long lo
   const size_t lds = ((size_t)5 * nmax + (size_t)3 * nbmax) * sizeof(double);
   VP_HIP(hipFuncSetAttribute((const void*)attributes_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
 
-  AttrScratch& sc = attr_scratch(device);
+  DeviceScratch<1>& sc = attr_scratch(device);
   std::lock_guard<std::mutex> lock(sc.mu);
   const size_t b_rows = align256((size_t)n_rows * sizeof(vp_attr_row)), b_ru = align256((size_t)n_rows * sizeof(int));
   const size_t b_un = align256((size_t)n_units * sizeof(int));
   const size_t b_part = align256((size_t)n_units * 3 * chunks * sizeof(double));
   const size_t b_flat = align256((size_t)n_units * 3 * sizeof(double));
   const size_t b_out = out_on_device ? 0 : align256((size_t)n_rows * ATTR_OUT * sizeof(double));
+  const size_t bytes = b_rows + b_ru + b_un + b_part + b_flat + b_out;
   void* p = nullptr;
-  if (const int rc = sc.grow(b_rows + b_ru + b_un + b_part + b_flat + b_out, &p)) return rc;
+  if (const int rc = sc.b[0].grow(who, bytes, bytes / 8 + 4096, &p)) return rc;
   char* q = (char*)p;
   vp_attr_row* rows_dev = (vp_attr_row*)q;
   int* ru_dev = (int*)(q += b_rows);

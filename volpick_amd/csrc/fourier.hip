@@ -24,9 +24,9 @@
 // pass (nb = 1) pads the image by one element in eight: the first radix-4 stage stores at a lane stride of 64 bytes,
 // which unpadded is a 4-way conflict on the 8 x 8-lane groups of ds_write_b128.
 #include <cmath>
-#include <mutex>
 
-#include "vp_common.h"
+#include "device_scratch.h"
+#include "sos_host.h"  // check_sample_kind
 
 namespace vp {
 namespace {
@@ -352,13 +352,8 @@ hipError_t launch_transform(const FftPlan& f, int first_lm, int final_sm, cd* bu
 }
 
 // Per device, grow-only, reused from call to call: flag word, twiddle table, half spectrum, the two FFT buffers.
-struct ResampleScratch {
-  std::mutex mu;
-  void* p = nullptr;
-  size_t cap = 0;
-};
-ResampleScratch& resample_scratch(int device) {
-  static ResampleScratch pool[64];
+DeviceScratch<1>& resample_scratch(int device) {
+  static DeviceScratch<1> pool[64];
   return pool[(unsigned)device % 64];
 }
 
@@ -371,8 +366,7 @@ struct Job {
 int make_job(const char* who, const void* in_dev, int in_kind, int64_t n, double rate_in, double rate_out, int64_t num,
              double df, double d_large_f, float* out_dev, int64_t out_len, Job* job) {
   VP_REQUIRE(in_dev && out_dev, "%s: null argument", who);
-  VP_REQUIRE(in_kind == VP_SAMPLES_INT32 || in_kind == VP_SAMPLES_FLOAT32 || in_kind == VP_SAMPLES_FLOAT64,
-             "%s: in_kind %d is none of VP_SAMPLES_INT32 / FLOAT32 / FLOAT64", who, in_kind);
+  if (const int rc = check_sample_kind(who, in_kind)) return rc;
   VP_REQUIRE(n >= 1, "%s: n = %lld, need at least one sample", who, (long long)n);
   VP_REQUIRE(num >= 1, "%s: num = %lld, need at least one output sample", who, (long long)num);
   VP_REQUIRE(out_len == num, "%s: out_len = %lld, num = %lld", who, (long long)out_len, (long long)num);
@@ -403,21 +397,6 @@ int make_job(const char* who, const void* in_dev, int in_kind, int64_t n, double
   c.df = df;
   c.dlf = d_large_f;
   c.L = 0, c.sgn = 0, c.logM = 0, c.B = nullptr, c.X = nullptr, c.flag = nullptr;
-  return VP_OK;
-}
-
-int grow(const char* who, ResampleScratch& sc, size_t bytes) {
-  if (bytes <= sc.cap) return VP_OK;
-  if (sc.p) (void)hipFree(sc.p);
-  sc.p = nullptr;
-  sc.cap = 0;
-  if (hipMalloc(&sc.p, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    sc.p = nullptr;
-    set_error("%s: cannot allocate %zu bytes of device scratch", who, bytes);
-    return VP_ERR_NOMEM;
-  }
-  sc.cap = bytes;
   return VP_OK;
 }
 
@@ -463,26 +442,19 @@ extern "C" int vp_resample_fourier(int device_id, const void* in_dev, int in_kin
   VP_HIP(hipSetDevice(device_id));
   if (const int rc = prepare_kernels()) return rc;
   hipStream_t s = nullptr;  // the null stream, one synchronisation at the end: as vp_decimate_lowpass
-  ResampleScratch& sc = resample_scratch(device_id);
+  DeviceScratch<1>& sc = resample_scratch(device_id);
   std::lock_guard<std::mutex> lock(sc.mu);
-  if (const int rc = grow(who, sc, job.bytes)) return rc;
+  void* p = nullptr;
+  if (const int rc = sc.b[0].grow(who, job.bytes, 0, &p)) return rc;  // exact: 2 GiB after a 250 Hz component-day
   cd *wt, *a, *b;
-  bind(job, sc.p, &wt, &a, &b);
+  bind(job, p, &wt, &a, &b);
   VP_HIP(launch_all(job, wt, a, b, s));
   VP_HIP(hipStreamSynchronize(s));
   return VP_OK;
 }
 
 extern "C" int vp_resample_release_scratch(int device_id, size_t* bytes_freed) {
-  VP_REQUIRE(device_id >= 0, "vp_resample_release_scratch: device index");
-  ResampleScratch& sc = resample_scratch(device_id);
-  std::lock_guard<std::mutex> lock(sc.mu);  // behind any call in flight on this device
-  VP_HIP(hipSetDevice(device_id));
-  if (sc.p) (void)hipFree(sc.p);
-  if (bytes_freed) *bytes_freed = sc.cap;
-  sc.p = nullptr;
-  sc.cap = 0;
-  return VP_OK;
+  return release_scratch("vp_resample_release_scratch", resample_scratch(device_id), device_id, bytes_freed);
 }
 
 extern "C" int vp_resample_fourier_bench(int device_id, const void* in_dev, int in_kind, int64_t n, double rate_in,
@@ -495,32 +467,20 @@ extern "C" int vp_resample_fourier_bench(int device_id, const void* in_dev, int 
   VP_REQUIRE(device_id >= 0, "vp_resample_fourier_bench: device index");
   VP_HIP(hipSetDevice(device_id));
   if (const int rc = prepare_kernels()) return rc;
-  ResampleScratch& sc = resample_scratch(device_id);
+  DeviceScratch<1>& sc = resample_scratch(device_id);
   std::lock_guard<std::mutex> lock(sc.mu);
-  if (const int rc = grow(who, sc, job.bytes)) return rc;
+  void* p = nullptr;
+  if (const int rc = sc.b[0].grow(who, job.bytes, 0, &p)) return rc;  // exact: 2 GiB after a 250 Hz component-day
   cd *wt, *a, *b;
-  bind(job, sc.p, &wt, &a, &b);
-  hipStream_t s;
-  VP_HIP(hipStreamCreate(&s));
-  hipEvent_t e0, e1;
-  VP_HIP(hipEventCreate(&e0));
-  VP_HIP(hipEventCreate(&e1));
+  bind(job, p, &wt, &a, &b);
+  BenchTimer t;
+  VP_HIP(t.init());
+  const auto all = [&] { return launch_all(job, wt, a, b, t.s); };
   float t_all = 0.f, t_fwd = 0.f;
-  for (int i = 0; i < 3; ++i) VP_HIP(launch_all(job, wt, a, b, s));
-  VP_HIP(hipEventRecord(e0, s));
-  for (int i = 0; i < iters; ++i) VP_HIP(launch_all(job, wt, a, b, s));
-  VP_HIP(hipEventRecord(e1, s));
-  VP_HIP(hipEventSynchronize(e1));
-  VP_HIP(hipEventElapsedTime(&t_all, e0, e1));
-  VP_HIP(hipEventRecord(e0, s));
-  for (int i = 0; i < iters; ++i) VP_HIP(launch_forward(job, wt, a, b, s));
-  VP_HIP(hipEventRecord(e1, s));
-  VP_HIP(hipEventSynchronize(e1));
-  VP_HIP(hipEventElapsedTime(&t_fwd, e0, e1));
-  *ms_total = t_all / iters;
-  if (ms_forward) *ms_forward = t_fwd / iters;
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  (void)hipStreamDestroy(s);
+  VP_HIP(t.run(3, all));
+  VP_HIP(t.time(iters, all, &t_all));
+  VP_HIP(t.time(iters, [&] { return launch_forward(job, wt, a, b, t.s); }, &t_fwd));
+  *ms_total = t_all;
+  if (ms_forward) *ms_forward = t_fwd;
   return VP_OK;
 }

@@ -8,9 +8,7 @@
 // at a time, and the two serial steps -- where each word's differences start (1..7 per word)
 // and the running sum -- are two DPP prefix scans over the lanes; the <= 7 differences of a
 // word are integrated in registers and stored straight to their place in the output.
-#include <mutex>
-
-#include "vp_common.h"
+#include "device_scratch.h"
 
 namespace vp {
 namespace {
@@ -381,41 +379,15 @@ void launch_decode(const uint8_t* buf, long long nbytes, const DevRec* recs, lon
 // Device scratch of vp_mseed_decode, per device, grow-only, reused from call to call: the file image, the sample array (host
 // destinations), the record table and the status words.  (hipMalloc + hipFree of 35 + 104 MB around every station-day cost
 // more than the decode itself; a call holds the device's lock from its first use of the scratch to its last.)
-struct MseedScratch {
-  std::mutex mu;
-  void* p[4] = {nullptr, nullptr, nullptr, nullptr};
-  size_t cap[4] = {0, 0, 0, 0};
-  int grow(int slot, size_t bytes, void** out) {
-    if (bytes > cap[slot]) {
-      if (p[slot]) (void)hipFree(p[slot]);
-      p[slot] = nullptr;
-      cap[slot] = 0;
-      const size_t want = bytes + bytes / 4 + 4096;
-      if (hipMalloc(&p[slot], want) != hipSuccess) {
-        (void)hipGetLastError();  // the failure is reported here: do not leave HIP's sticky last error for an unrelated later check
-        p[slot] = nullptr;
-        set_error("vp_mseed_decode: cannot allocate %zu bytes of device scratch", want);
-        return VP_ERR_HIP;
-      }
-      cap[slot] = want;
-    }
-    *out = p[slot];
-    return VP_OK;
-  }
-  size_t release() {  // caller holds mu
-    size_t freed = 0;
-    for (int i = 0; i < 4; ++i) {
-      if (p[i]) (void)hipFree(p[i]);
-      freed += cap[i];
-      p[i] = nullptr;
-      cap[i] = 0;
-    }
-    return freed;
-  }
-};
+enum { SLOT_FILE, SLOT_SAMPLES, SLOT_RECORDS, SLOT_STATUS, MSEED_SLOTS };
+typedef DeviceScratch<MSEED_SLOTS> MseedScratch;
 MseedScratch& mseed_scratch(int device) {
   static MseedScratch pool[64];
   return pool[(unsigned)device % 64];
+}
+int grow_slot(MseedScratch& sc, int slot, size_t bytes, void** out) {
+  const int rc = sc.b[slot].grow("vp_mseed_decode", bytes, bytes / 4 + 4096, out);
+  return rc == VP_OK ? VP_OK : VP_ERR_HIP;  // the code this entry point has answered since before VP_ERR_NOMEM
 }
 
 }  // namespace
@@ -424,13 +396,7 @@ MseedScratch& mseed_scratch(int device) {
 using namespace vp;
 
 extern "C" int vp_mseed_release_scratch(int device_id, size_t* bytes_freed) {
-  VP_REQUIRE(device_id >= 0, "vp_mseed_release_scratch: device index");
-  MseedScratch& sc = mseed_scratch(device_id);
-  std::lock_guard<std::mutex> lock(sc.mu);  // behind any decode call in flight on this device
-  VP_HIP(hipSetDevice(device_id));
-  const size_t freed = sc.release();
-  if (bytes_freed) *bytes_freed = freed;
-  return VP_OK;
+  return release_scratch("vp_mseed_release_scratch", mseed_scratch(device_id), device_id, bytes_freed);
 }
 
 extern "C" int vp_mseed_scan(const uint8_t* buf, size_t nbytes, vp_mseed_record* recs, int64_t cap,
@@ -531,7 +497,7 @@ extern "C" int vp_mseed_decode(int device_id, const uint8_t* buf, int buf_mem, s
   void *dbuf = nullptr, *dout = nullptr, *drec = nullptr, *dstat = nullptr;
   const uint8_t* bufp = buf;
   if (buf_mem == VP_MEM_HOST) {
-    if (const int rc2 = sc.grow(0, nbytes ? nbytes : 4, &dbuf)) return rc2;
+    if (const int rc2 = grow_slot(sc, SLOT_FILE, nbytes ? nbytes : 4, &dbuf)) return rc2;
     VP_HIP(hipMemcpyAsync(dbuf, buf, nbytes, hipMemcpyHostToDevice, s));
     bufp = (const uint8_t*)dbuf;
   }
@@ -539,16 +505,16 @@ extern "C" int vp_mseed_decode(int device_id, const uint8_t* buf, int buf_mem, s
   void* outp = out;
   const size_t out_bytes = (size_t)out_len * 4;
   if (out_mem == VP_MEM_HOST) {
-    if (const int rc2 = sc.grow(1, out_bytes ? out_bytes : 4, &dout)) return rc2;
+    if (const int rc2 = grow_slot(sc, SLOT_SAMPLES, out_bytes ? out_bytes : 4, &dout)) return rc2;
     outp = dout;
     if (!zero_fill) VP_HIP(hipMemcpyAsync(outp, out, out_bytes, hipMemcpyHostToDevice, s));
   }
   if (zero_fill) VP_HIP(hipMemsetAsync(outp, 0, out_bytes, s));
   if (!dev.empty()) {
-    if (const int rc2 = sc.grow(2, dev.size() * sizeof(DevRec), &drec)) return rc2;
+    if (const int rc2 = grow_slot(sc, SLOT_RECORDS, dev.size() * sizeof(DevRec), &drec)) return rc2;
     VP_HIP(hipMemcpyAsync(drec, dev.data(), dev.size() * sizeof(DevRec), hipMemcpyHostToDevice, s));
     if (status) {
-      if (const int rc2 = sc.grow(3, dev.size() * sizeof(int), &dstat)) return rc2;
+      if (const int rc2 = grow_slot(sc, SLOT_STATUS, dev.size() * sizeof(int), &dstat)) return rc2;
       VP_HIP(hipMemsetAsync(dstat, 0, dev.size() * sizeof(int), s));
     }
     launch_decode(bufp, (long long)nbytes, (const DevRec*)drec, (long long)dev.size(), out_kind, outp, out_len, (int*)dstat, s);
@@ -582,23 +548,13 @@ extern "C" int vp_mseed_decode_bench(int device_id, const uint8_t* buf_dev, size
   } drec;
   VP_HIP(hipMalloc(&drec.p, dev.size() * sizeof(DevRec)));
   VP_HIP(hipMemcpy(drec.p, dev.data(), dev.size() * sizeof(DevRec), hipMemcpyHostToDevice));
-  hipStream_t s;
-  VP_HIP(hipStreamCreate(&s));
-  hipEvent_t e0, e1;
-  VP_HIP(hipEventCreate(&e0));
-  VP_HIP(hipEventCreate(&e1));
-  for (int i = 0; i < 3; ++i)
-    launch_decode(buf_dev, (long long)nbytes, (const DevRec*)drec.p, (long long)dev.size(), out_kind, out_dev, out_len, nullptr, s);
-  VP_HIP(hipEventRecord(e0, s));
-  for (int i = 0; i < iters; ++i)
-    launch_decode(buf_dev, (long long)nbytes, (const DevRec*)drec.p, (long long)dev.size(), out_kind, out_dev, out_len, nullptr, s);
-  VP_HIP(hipEventRecord(e1, s));
-  VP_HIP(hipEventSynchronize(e1));
-  float t = 0.f;
-  VP_HIP(hipEventElapsedTime(&t, e0, e1));
-  *ms = t / iters;
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  (void)hipStreamDestroy(s);
+  BenchTimer t;
+  VP_HIP(t.init());
+  const auto decode = [&] {
+    launch_decode(buf_dev, (long long)nbytes, (const DevRec*)drec.p, (long long)dev.size(), out_kind, out_dev, out_len, nullptr, t.s);
+    return hipSuccess;
+  };
+  VP_HIP(t.run(3, decode));
+  VP_HIP(t.time(iters, decode, ms));
   return VP_OK;
 }

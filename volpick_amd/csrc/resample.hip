@@ -21,10 +21,8 @@
 // unpadded image (stride 256 B) would put every lane on the same two banks.  Results go back into the image (a
 // thread's own piece, after a barrier: its neighbours' warm-up has read the inputs there) and out with coalesced
 // stores.
-#include <cmath>
-#include <mutex>
-
-#include "sos_tile.h"  // DT, DC, DTILE, DMAXS, SosArg, phys(): shared with sosfilt.hip
+#include "device_scratch.h"
+#include "sos_tile.h"  // DT, DC, DTILE, SosArg, phys(): shared with sosfilt.hip
 
 namespace vp {
 namespace {
@@ -76,6 +74,8 @@ __global__ __launch_bounds__(DT) void decimate_pass_kernel(const InT* __restrict
   double s1[NS], s2[NS];
 #pragma unroll
   for (int s = 0; s < NS; ++s) s1[s] = s2[s] = 0.0;
+  // sos_step<NS> of sos_tile.h, kept as a local lambda: with the shared function the compiler schedules twelve of the
+  // instantiations differently (LOG.md, section 33)
   auto step = [&](double v) {
 #pragma unroll
     for (int s = 0; s < NS; ++s) {  // direct form II transposed, the recurrence of scipy's sosfilt
@@ -131,40 +131,19 @@ const void* forward_kernel(int in_kind, int ns) {
 }
 
 // Per device, grow-only, reused from call to call: f (8 bytes per input sample) and the flag word.
-struct DecimateScratch {
-  std::mutex mu;
-  void* p = nullptr;
-  size_t cap = 0;
-  int grow(size_t bytes, void** out) {
-    if (bytes > cap) {
-      if (p) (void)hipFree(p);
-      p = nullptr;
-      cap = 0;
-      const size_t want = bytes + bytes / 8 + 4096;
-      if (hipMalloc(&p, want) != hipSuccess) {
-        (void)hipGetLastError();
-        p = nullptr;
-        set_error("vp_decimate_lowpass: cannot allocate %zu bytes of device scratch", want);
-        return VP_ERR_NOMEM;
-      }
-      cap = want;
-    }
-    *out = p;
-    return VP_OK;
-  }
-};
-DecimateScratch& decimate_scratch(int device) {
-  static DecimateScratch pool[64];
+DeviceScratch<1>& decimate_scratch(int device) {
+  static DeviceScratch<1> pool[64];
   return pool[(unsigned)device % 64];
 }
 
-// Samples after which the response to a wrong starting state has decayed by 2^-40: from the largest pole radius.
-int warmup_length(const double* sos, int ns, double* r_out) {
-  const double r = sos_pole_radius(sos, ns);
-  *r_out = r;
-  if (!(r < 1.0)) return -1;
-  if (r < 1e-12) return 2 * ns;
-  return (int)std::ceil(40.0 * std::log(2.0) / -std::log(r)) + 2 * ns;
+// the flag word and f of a call of n samples
+int grow_scratch(const char* who, DeviceScratch<1>& sc, int64_t n, int** flag, double** f) {
+  const size_t bytes = 64 + (size_t)n * sizeof(double);
+  void* p = nullptr;
+  if (const int rc = sc.b[0].grow(who, bytes, bytes / 8 + 4096, &p)) return rc;
+  *flag = (int*)p;
+  *f = (double*)((char*)p + 64);
+  return VP_OK;
 }
 
 struct Plan {
@@ -176,27 +155,14 @@ struct Plan {
 int make_plan(const char* who, const void* in_dev, int in_kind, int64_t n, const double* sos, int n_sections, int factor,
               const float* out_dev, int64_t out_len, Plan* plan) {
   VP_REQUIRE(in_dev && sos && out_dev, "%s: null argument", who);
-  VP_REQUIRE(in_kind == VP_SAMPLES_INT32 || in_kind == VP_SAMPLES_FLOAT32 || in_kind == VP_SAMPLES_FLOAT64,
-             "%s: in_kind %d is none of VP_SAMPLES_INT32 / FLOAT32 / FLOAT64", who, in_kind);
+  if (const int rc = check_sample_kind(who, in_kind)) return rc;
   VP_REQUIRE(n >= 1, "%s: n = %lld, need at least one sample", who, (long long)n);
   VP_REQUIRE(factor >= 2, "%s: factor = %d, need >= 2", who, factor);
-  VP_REQUIRE(n_sections >= 1 && n_sections <= DMAXS, "%s: n_sections = %d, the kernel is built for 1..%d", who, n_sections,
-             DMAXS);
   VP_REQUIRE(out_len == (n + factor - 1) / factor, "%s: out_len = %lld, ceil(n / factor) = %lld", who, (long long)out_len,
              (long long)((n + factor - 1) / factor));
-  for (int s = 0; s < n_sections; ++s) {
-    for (int i = 0; i < 6; ++i) VP_REQUIRE(std::isfinite(sos[6 * s + i]), "%s: section %d has a non-finite coefficient", who, s);
-    VP_REQUIRE(sos[6 * s + 3] == 1.0, "%s: section %d has a0 = %g, need 1 (scipy's sos layout)", who, s, sos[6 * s + 3]);
-    plan->arg.c[s][0] = sos[6 * s + 0];
-    plan->arg.c[s][1] = sos[6 * s + 1];
-    plan->arg.c[s][2] = sos[6 * s + 2];
-    plan->arg.c[s][3] = sos[6 * s + 4];
-    plan->arg.c[s][4] = sos[6 * s + 5];
-  }
-  for (int s = n_sections; s < DMAXS; ++s)
-    for (int i = 0; i < 5; ++i) plan->arg.c[s][i] = 0.0;
   double r = 0.0;
-  plan->warm = warmup_length(sos, n_sections, &r);
+  if (const int rc = load_sos(who, sos, n_sections, &plan->arg, &r)) return rc;
+  plan->warm = warmup_length(sos, n_sections, &r);  // the same radius again, and what it asks for
   VP_REQUIRE(plan->warm >= 0, "%s: the filter is not stable (largest pole radius %g)", who, r);
   if (plan->warm > DHALO) {
     set_error("%s: largest pole radius %g needs a warm-up of %d samples, the tile has room for %d", who, r, plan->warm, DHALO);
@@ -242,12 +208,11 @@ extern "C" int vp_decimate_lowpass(int device_id, const void* in_dev, int in_kin
   VP_HIP(hipSetDevice(device_id));
   if (const int rc = prepare_kernels(plan)) return rc;
   hipStream_t s = nullptr;  // the null stream, one synchronisation at the end: as vp_mseed_decode
-  DecimateScratch& sc = decimate_scratch(device_id);
+  DeviceScratch<1>& sc = decimate_scratch(device_id);
   std::lock_guard<std::mutex> lock(sc.mu);
-  void* p = nullptr;
-  if (const int rc = sc.grow(64 + (size_t)n * sizeof(double), &p)) return rc;
-  int* flag = (int*)p;
-  double* f = (double*)((char*)p + 64);
+  int* flag;
+  double* f;
+  if (const int rc = grow_scratch("vp_decimate_lowpass", sc, n, &flag, &f)) return rc;
   VP_HIP(hipMemsetAsync(flag, 0, sizeof(int), s));
   VP_HIP(launch_passes(plan, in_dev, (long long)n, factor, f, flag, out_dev, s));
   VP_HIP(hipStreamSynchronize(s));
@@ -255,15 +220,7 @@ extern "C" int vp_decimate_lowpass(int device_id, const void* in_dev, int in_kin
 }
 
 extern "C" int vp_decimate_release_scratch(int device_id, size_t* bytes_freed) {
-  VP_REQUIRE(device_id >= 0, "vp_decimate_release_scratch: device index");
-  DecimateScratch& sc = decimate_scratch(device_id);
-  std::lock_guard<std::mutex> lock(sc.mu);  // behind any call in flight on this device
-  VP_HIP(hipSetDevice(device_id));
-  if (sc.p) (void)hipFree(sc.p);
-  if (bytes_freed) *bytes_freed = sc.cap;
-  sc.p = nullptr;
-  sc.cap = 0;
-  return VP_OK;
+  return release_scratch("vp_decimate_release_scratch", decimate_scratch(device_id), device_id, bytes_freed);
 }
 
 extern "C" int vp_decimate_lowpass_bench(int device_id, const void* in_dev, int in_kind, int64_t n, const double* sos,
@@ -277,34 +234,21 @@ extern "C" int vp_decimate_lowpass_bench(int device_id, const void* in_dev, int 
   VP_REQUIRE(device_id >= 0, "vp_decimate_lowpass_bench: device index");
   VP_HIP(hipSetDevice(device_id));
   if (const int rc = prepare_kernels(plan)) return rc;
-  DecimateScratch& sc = decimate_scratch(device_id);
+  DeviceScratch<1>& sc = decimate_scratch(device_id);
   std::lock_guard<std::mutex> lock(sc.mu);
-  void* p = nullptr;
-  if (const int rc = sc.grow(64 + (size_t)n * sizeof(double), &p)) return rc;
-  int* flag = (int*)p;
-  double* f = (double*)((char*)p + 64);
-  hipStream_t s;
-  VP_HIP(hipStreamCreate(&s));
-  hipEvent_t e0, e1;
-  VP_HIP(hipEventCreate(&e0));
-  VP_HIP(hipEventCreate(&e1));
-  VP_HIP(hipMemsetAsync(flag, 0, sizeof(int), s));
+  int* flag;
+  double* f;
+  if (const int rc = grow_scratch("vp_decimate_lowpass_bench", sc, n, &flag, &f)) return rc;
+  BenchTimer t;
+  VP_HIP(t.init());
+  VP_HIP(hipMemsetAsync(flag, 0, sizeof(int), t.s));
+  const auto both = [&] { return launch_passes(plan, in_dev, (long long)n, factor, f, flag, out_dev, t.s); };
+  const auto forward = [&] { return launch_pass(plan.fwd, plan, in_dev, (long long)n, f, nullptr, factor, flag, t.s); };
   float t_all = 0.f, t_fwd = 0.f;
-  for (int i = 0; i < 3; ++i) VP_HIP(launch_passes(plan, in_dev, (long long)n, factor, f, flag, out_dev, s));
-  VP_HIP(hipEventRecord(e0, s));
-  for (int i = 0; i < iters; ++i) VP_HIP(launch_passes(plan, in_dev, (long long)n, factor, f, flag, out_dev, s));
-  VP_HIP(hipEventRecord(e1, s));
-  VP_HIP(hipEventSynchronize(e1));
-  VP_HIP(hipEventElapsedTime(&t_all, e0, e1));
-  VP_HIP(hipEventRecord(e0, s));
-  for (int i = 0; i < iters; ++i) VP_HIP(launch_pass(plan.fwd, plan, in_dev, (long long)n, f, nullptr, factor, flag, s));
-  VP_HIP(hipEventRecord(e1, s));
-  VP_HIP(hipEventSynchronize(e1));
-  VP_HIP(hipEventElapsedTime(&t_fwd, e0, e1));
-  *ms_total = t_all / iters;
-  if (ms_forward) *ms_forward = t_fwd / iters;
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  (void)hipStreamDestroy(s);
+  VP_HIP(t.run(3, both));
+  VP_HIP(t.time(iters, both, &t_all));
+  VP_HIP(t.time(iters, forward, &t_fwd));
+  *ms_total = t_all;
+  if (ms_forward) *ms_forward = t_fwd;
   return VP_OK;
 }

@@ -1,9 +1,8 @@
 // What the two recursive-filter kernels share (resample.hip: decimation by warm-up; sosfilt.hip: general filters by an
 // exact carry): the cut of a pass into tiles and pieces, the padded LDS image of a tile, the section coefficients as a
-// kernel argument, one sample's recurrence and the host's pole radius.
+// kernel argument (sos_host.h, with the host's checks) and one sample's recurrence.
 #pragma once
-#include <cmath>
-
+#include "sos_host.h"  // DMAXS, SosArg
 #include "vp_common.h"
 
 namespace vp {
@@ -11,11 +10,6 @@ namespace vp {
 constexpr int DT = 256;         // threads per workgroup
 constexpr int DC = 32;          // samples per thread (one piece)
 constexpr int DTILE = DT * DC;  // samples per workgroup (one tile)
-constexpr int DMAXS = 4;        // second-order sections the kernels are instantiated for
-
-struct SosArg {
-  double c[DMAXS][5];  // b0 b1 b2 a1 a2 (a0 == 1)
-};
 
 // Piece p of a tile image starts at double (DC + 1) p: lane l of a wave reads dword (2 DC + 2) l = 2 l (mod 64), so the
 // 32 lanes of a ds_read_b64 group cover the 64 banks once.
@@ -33,24 +27,6 @@ __device__ __forceinline__ double sos_step(const SosArg& sos, double (&s1)[NS], 
     v = y;
   }
   return v;
-}
-
-// Largest pole radius of `ns` sections in scipy's six-column layout.
-inline double sos_pole_radius(const double* sos, int ns) {
-  double r = 0.0;
-  for (int s = 0; s < ns; ++s) {
-    const double a1 = sos[6 * s + 4], a2 = sos[6 * s + 5];
-    const double disc = a1 * a1 - 4.0 * a2;
-    double rs;
-    if (disc < 0.0) {
-      rs = std::sqrt(a2);  // complex pair: |z|^2 = a2
-    } else {
-      const double q = std::sqrt(disc);
-      rs = std::fmax(std::fabs(-a1 + q), std::fabs(-a1 - q)) * 0.5;
-    }
-    r = std::fmax(r, rs);
-  }
-  return r;
 }
 
 }  // namespace vp

@@ -29,8 +29,7 @@
 // (0 * NaN is NaN), so everything behind it in the order of the pass is NaN, and in a zero-phase call everything.
 //
 // Detrending: float64 sums in a fixed order (per-workgroup partials, then one workgroup), then one subtracting pass.
-#include <mutex>
-
+#include "device_scratch.h"
 #include "sos_matrices.h"
 #include "sos_tile.h"
 
@@ -343,34 +342,13 @@ hipError_t launch_detrend(const InT* in, long long n, int type, double* part, do
 
 // Per device, grow-only, reused from call to call: the matrix table, E and Z, the float64 intermediate of a zero-phase
 // call; a detrend's partial sums.
-struct SosScratch {
-  std::mutex mu;
-  void* p = nullptr;
-  size_t cap = 0;
-  int grow(const char* who, size_t bytes, void** out) {
-    if (bytes > cap) {
-      if (p) (void)hipFree(p);
-      p = nullptr;
-      cap = 0;
-      const size_t want = bytes + bytes / 8 + 4096;
-      if (hipMalloc(&p, want) != hipSuccess) {
-        (void)hipGetLastError();
-        p = nullptr;
-        set_error("%s: cannot allocate %zu bytes of device scratch", who, want);
-        return VP_ERR_NOMEM;
-      }
-      cap = want;
-    }
-    *out = p;
-    return VP_OK;
-  }
-};
-SosScratch& sos_scratch(int device) {
-  static SosScratch pool[64];
+DeviceScratch<1>& sos_scratch(int device) {
+  static DeviceScratch<1> pool[64];
   return pool[(unsigned)device % 64];
 }
-
-size_t elem_bytes(int kind) { return kind == VP_SAMPLES_FLOAT64 ? 8 : 4; }
+int grow_scratch(const char* who, DeviceScratch<1>& sc, size_t bytes, void** out) {
+  return sc.b[0].grow(who, bytes, bytes / 8 + 4096, out);
+}
 
 bool overlap(const void* a, size_t na, const void* b, size_t nb) {
   const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
@@ -387,25 +365,12 @@ struct Plan {
 
 int make_plan(const char* who, const void* in_dev, int in_kind, int64_t n, const double* sos, int n_sections,
               const float* out_dev, Plan* plan) {
-  VP_REQUIRE(in_kind == VP_SAMPLES_INT32 || in_kind == VP_SAMPLES_FLOAT32 || in_kind == VP_SAMPLES_FLOAT64,
-             "%s: in_kind %d is none of VP_SAMPLES_INT32 / FLOAT32 / FLOAT64", who, in_kind);
+  if (const int rc = check_sample_kind(who, in_kind)) return rc;
   VP_REQUIRE(n >= 0, "%s: n = %lld is negative", who, (long long)n);
   VP_REQUIRE(sos, "%s: null argument", who);
   VP_REQUIRE(n == 0 || (in_dev && out_dev), "%s: null argument", who);
-  VP_REQUIRE(n_sections >= 1 && n_sections <= DMAXS, "%s: n_sections = %d, the kernel is built for 1..%d", who, n_sections,
-             DMAXS);
-  for (int s = 0; s < n_sections; ++s) {
-    for (int i = 0; i < 6; ++i) VP_REQUIRE(std::isfinite(sos[6 * s + i]), "%s: section %d has a non-finite coefficient", who, s);
-    VP_REQUIRE(sos[6 * s + 3] == 1.0, "%s: section %d has a0 = %g, need 1 (scipy's sos layout)", who, s, sos[6 * s + 3]);
-    plan->arg.c[s][0] = sos[6 * s + 0];
-    plan->arg.c[s][1] = sos[6 * s + 1];
-    plan->arg.c[s][2] = sos[6 * s + 2];
-    plan->arg.c[s][3] = sos[6 * s + 4];
-    plan->arg.c[s][4] = sos[6 * s + 5];
-  }
-  for (int s = n_sections; s < DMAXS; ++s)
-    for (int i = 0; i < 5; ++i) plan->arg.c[s][i] = 0.0;
-  const double r = sos_pole_radius(sos, n_sections);
+  double r = 0.0;
+  if (const int rc = load_sos(who, sos, n_sections, &plan->arg, &r)) return rc;
   VP_REQUIRE(r < 1.0, "%s: the filter is not stable (largest pole radius %g)", who, r);
   VP_REQUIRE(n == 0 || !overlap(in_dev, (size_t)n * elem_bytes(in_kind), out_dev, (size_t)n * sizeof(float)),
              "%s: out_dev overlaps in_dev", who);
@@ -497,10 +462,10 @@ extern "C" int vp_sos_filter(int device_id, const void* in_dev, int in_kind, int
   VP_HIP(hipSetDevice(device_id));
   if (const int rc = prepare_kernels(plan, zerophase != 0)) return rc;
   hipStream_t s = nullptr;  // the null stream, one synchronisation at the end: as vp_decimate_lowpass
-  SosScratch& sc = sos_scratch(device_id);
+  DeviceScratch<1>& sc = sos_scratch(device_id);
   std::lock_guard<std::mutex> lock(sc.mu);
   void* p = nullptr;
-  if (const int rc = sc.grow("vp_sos_filter", Layout::bytes(n, zerophase != 0), &p)) return rc;
+  if (const int rc = grow_scratch("vp_sos_filter", sc, Layout::bytes(n, zerophase != 0), &p)) return rc;
   const Layout L(p, n);
   VP_HIP(upload_tables(plan, L, s));
   VP_HIP(launch_filter(plan, L, in_dev, (long long)n, zerophase != 0, out_dev, s));
@@ -509,15 +474,7 @@ extern "C" int vp_sos_filter(int device_id, const void* in_dev, int in_kind, int
 }
 
 extern "C" int vp_sos_filter_release_scratch(int device_id, size_t* bytes_freed) {
-  VP_REQUIRE(device_id >= 0, "vp_sos_filter_release_scratch: device index");
-  SosScratch& sc = sos_scratch(device_id);
-  std::lock_guard<std::mutex> lock(sc.mu);  // behind any call in flight on this device
-  VP_HIP(hipSetDevice(device_id));
-  if (sc.p) (void)hipFree(sc.p);
-  if (bytes_freed) *bytes_freed = sc.cap;
-  sc.p = nullptr;
-  sc.cap = 0;
-  return VP_OK;
+  return release_scratch("vp_sos_filter_release_scratch", sos_scratch(device_id), device_id, bytes_freed);
 }
 
 extern "C" int vp_sos_filter_bench(int device_id, const void* in_dev, int in_kind, int64_t n, const double* sos,
@@ -529,43 +486,28 @@ extern "C" int vp_sos_filter_bench(int device_id, const void* in_dev, int in_kin
   VP_REQUIRE(device_id >= 0, "vp_sos_filter_bench: device index");
   VP_HIP(hipSetDevice(device_id));
   if (const int rc = prepare_kernels(plan, zerophase != 0)) return rc;
-  SosScratch& sc = sos_scratch(device_id);
+  DeviceScratch<1>& sc = sos_scratch(device_id);
   std::lock_guard<std::mutex> lock(sc.mu);
   void* p = nullptr;
-  if (const int rc = sc.grow("vp_sos_filter_bench", Layout::bytes(n, zerophase != 0), &p)) return rc;
+  if (const int rc = grow_scratch("vp_sos_filter_bench", sc, Layout::bytes(n, zerophase != 0), &p)) return rc;
   const Layout L(p, n);
-  hipStream_t s;
-  VP_HIP(hipStreamCreate(&s));
-  hipEvent_t e0, e1;
-  VP_HIP(hipEventCreate(&e0));
-  VP_HIP(hipEventCreate(&e1));
-  VP_HIP(upload_tables(plan, L, s));
-  float t_all = 0.f, t_carry = 0.f;
+  BenchTimer t;
+  VP_HIP(t.init());
+  VP_HIP(upload_tables(plan, L, t.s));
   const long long ne = (n + DTILE - 1) / DTILE - 1;
-  for (int i = 0; i < 3; ++i) VP_HIP(launch_filter(plan, L, in_dev, (long long)n, zerophase != 0, out_dev, s));
-  VP_HIP(hipEventRecord(e0, s));
-  for (int i = 0; i < iters; ++i) VP_HIP(launch_filter(plan, L, in_dev, (long long)n, zerophase != 0, out_dev, s));
-  VP_HIP(hipEventRecord(e1, s));
-  VP_HIP(hipEventSynchronize(e1));
-  VP_HIP(hipEventElapsedTime(&t_all, e0, e1));
-  if (ne > 0) {  // one pass's carry launch alone, over the E the last pass left
-    VP_HIP(hipEventRecord(e0, s));
-    for (int i = 0; i < iters; ++i) VP_HIP(launch_carry(plan, L, ne, s));
-    VP_HIP(hipEventRecord(e1, s));
-    VP_HIP(hipEventSynchronize(e1));
-    VP_HIP(hipEventElapsedTime(&t_carry, e0, e1));
-  }
-  *ms_total = t_all / iters;
-  if (ms_carry) *ms_carry = t_carry / iters;
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  (void)hipStreamDestroy(s);
+  const auto filter = [&] { return launch_filter(plan, L, in_dev, (long long)n, zerophase != 0, out_dev, t.s); };
+  float t_all = 0.f, t_carry = 0.f;
+  VP_HIP(t.run(3, filter));
+  VP_HIP(t.time(iters, filter, &t_all));
+  if (ne > 0)  // one pass's carry launch alone, over the E the last pass left
+    VP_HIP(t.time(iters, [&] { return launch_carry(plan, L, ne, t.s); }, &t_carry));
+  *ms_total = t_all;
+  if (ms_carry) *ms_carry = t_carry;
   return VP_OK;
 }
 
 extern "C" int vp_detrend(int device_id, const void* in_dev, int in_kind, int64_t n, int type, float* out_dev) {
-  VP_REQUIRE(in_kind == VP_SAMPLES_INT32 || in_kind == VP_SAMPLES_FLOAT32 || in_kind == VP_SAMPLES_FLOAT64,
-             "vp_detrend: in_kind %d is none of VP_SAMPLES_INT32 / FLOAT32 / FLOAT64", in_kind);
+  if (const int rc = check_sample_kind("vp_detrend", in_kind)) return rc;
   VP_REQUIRE(type == VP_DETREND_DEMEAN || type == VP_DETREND_LINEAR || type == VP_DETREND_SIMPLE,
              "vp_detrend: type %d is none of VP_DETREND_DEMEAN / LINEAR / SIMPLE", type);
   VP_REQUIRE(n >= 0, "vp_detrend: n = %lld is negative", (long long)n);
@@ -577,11 +519,11 @@ extern "C" int vp_detrend(int device_id, const void* in_dev, int in_kind, int64_
              "vp_detrend: out_dev overlaps in_dev");
   VP_HIP(hipSetDevice(device_id));
   hipStream_t s = nullptr;
-  SosScratch& sc = sos_scratch(device_id);
+  DeviceScratch<1>& sc = sos_scratch(device_id);
   std::lock_guard<std::mutex> lock(sc.mu);
   void* p = nullptr;
   const size_t nb = (size_t)((n + DTILE - 1) / DTILE);
-  if (const int rc = sc.grow("vp_detrend", sizeof(double) * (2 + 2 * nb), &p)) return rc;
+  if (const int rc = grow_scratch("vp_detrend", sc, sizeof(double) * (2 + 2 * nb), &p)) return rc;
   double* prm = (double*)p;
   double* part = prm + 2;
   if (in_kind == VP_SAMPLES_INT32)

@@ -10,7 +10,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/volpick_hip.h"
+#include "vp_error.h"  // set_error, VP_REQUIRE, volpick_hip.h
 
 namespace vp {
 
@@ -21,8 +21,6 @@ constexpr int HALO = 8;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-void set_error(const char* fmt, ...);
-
 #define VP_HIP(call)                                                                         \
   do {                                                                                       \
     hipError_t e_ = (call);                                                                  \
@@ -30,14 +28,6 @@ void set_error(const char* fmt, ...);
       vp::set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
       return VP_ERR_HIP;                                                                     \
     }                                                                                        \
-  } while (0)
-
-#define VP_REQUIRE(cond, ...)     \
-  do {                            \
-    if (!(cond)) {                \
-      vp::set_error(__VA_ARGS__); \
-      return VP_ERR_INVALID;      \
-    }                             \
   } while (0)
 
 struct ParamDesc {

@@ -22,6 +22,7 @@ from datetime import datetime, timedelta, timezone
 import numpy as np
 
 from . import _lib
+from ._device import release_scratch
 from .stream import Stream, Trace, UTCDateTime
 
 _REC_DTYPE = np.dtype(
@@ -171,9 +172,7 @@ def read_mseed(source, device=0, dtype=None, device_resident=False):
 
 def release_decode_scratch(device=0):
     """Free the device scratch `read_mseed` keeps per device between calls (vp_mseed_release_scratch); returns the bytes freed."""
-    freed = C.c_size_t(0)
-    _lib.check(_lib.load().vp_mseed_release_scratch(int(device), C.byref(freed)), "vp_mseed_release_scratch")
-    return int(freed.value)
+    return release_scratch("vp_mseed_release_scratch", device)
 
 
 def read_sac(source):

@@ -15,9 +15,13 @@ ObsPy's building blocks, restated with the scipy calls ObsPy itself makes:
 """
 from __future__ import annotations
 
+import ctypes as C
 import warnings
 
 import numpy as np
+
+from . import _lib
+from ._device import SAMPLE_KINDS, device_samples, release_scratch, try_on_device
 
 
 def lowpass_sos(freq, df, corners=4):
@@ -87,28 +91,19 @@ def resample_array(data, rate_in, rate_out):
     return resample_fourier(data, rate_in, rate_out)
 
 
-_IN_KINDS = {"torch.int32": 0, "torch.float32": 1, "torch.float64": 2}  # VP_SAMPLES_INT32 / FLOAT32 / FLOAT64
-
-
 def decimate_device(x, rate_in, rate_out):
     """The integer-ratio branch of :func:`resample_array` on the GPU (``vp_decimate_lowpass``): ``x`` is a 1-D CUDA tensor
     of int32, float32 or float64 samples at ``rate_in``, an integer multiple (>= 2) of ``rate_out``; returns a float32 CUDA
     tensor of ``ceil(len(x) / k)`` samples.  Same coefficients as the host path (:func:`lowpass_sos`), float64 state and
     intermediate, one rounding to float32 at the end.  Raises ``VolpickHipError`` where the library refuses (a factor whose
     warm-up does not fit the kernel's tile): there is no silent host fallback inside this function."""
-    import ctypes as C
-
     import torch
-
-    from . import _lib
 
     rate_in, rate_out = float(rate_in), float(rate_out)
     if not (rate_in % rate_out == 0 and rate_in > rate_out):
         raise ValueError(f"decimate_device: {rate_in} Hz is not an integer multiple (>= 2) of {rate_out} Hz")
-    if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 1 and str(x.dtype) in _IN_KINDS):
-        raise TypeError("decimate_device: need a 1-D CUDA tensor of int32, float32 or float64 samples")
+    x = device_samples(x, "decimate_device")
     k = int(rate_in / rate_out)
-    x = x.contiguous()
     n = int(x.shape[0])
     out = torch.empty((n + k - 1) // k, dtype=torch.float32, device=x.device)
     if n == 0:
@@ -116,20 +111,14 @@ def decimate_device(x, rate_in, rate_out):
     sos = np.ascontiguousarray(lowpass_sos(rate_out * 0.5, rate_in), dtype=np.float64)
     torch.cuda.current_stream(x.device).synchronize()  # the library works on the null stream: x is complete before it starts
     _lib.check(_lib.load().vp_decimate_lowpass(
-        x.device.index, C.c_void_p(x.data_ptr()), _IN_KINDS[str(x.dtype)], n, sos.ctypes.data_as(C.POINTER(C.c_double)),
+        x.device.index, C.c_void_p(x.data_ptr()), SAMPLE_KINDS[str(x.dtype)], n, sos.ctypes.data_as(C.POINTER(C.c_double)),
         len(sos), k, C.c_void_p(out.data_ptr()), out.shape[0]), "vp_decimate_lowpass")
     return out
 
 
 def release_decimate_scratch(device=0):
     """Free the float64 scratch `decimate_device` keeps per device between calls; returns the bytes freed."""
-    import ctypes as C
-
-    from . import _lib
-
-    freed = C.c_size_t(0)
-    _lib.check(_lib.load().vp_decimate_release_scratch(int(device), C.byref(freed)), "vp_decimate_release_scratch")
-    return int(freed.value)
+    return release_scratch("vp_decimate_release_scratch", device)
 
 
 def fourier_args(n, rate_in, rate_out):
@@ -155,20 +144,14 @@ def fourier_device(x, rate_in, rate_out):
     Raises ``ValueError`` for equal rates, an integer ratio (the other branch) and a trace too short to give one output
     sample; ``VolpickHipError`` where the library refuses (a trace beyond its largest transform, no memory for the scratch):
     there is no silent host fallback inside this function."""
-    import ctypes as C
-
     import torch
-
-    from . import _lib
 
     rate_in, rate_out = float(rate_in), float(rate_out)
     if rate_in == rate_out:
         raise ValueError(f"fourier_device: the trace already is at {rate_out} Hz")
     if rate_in % rate_out == 0:
         raise ValueError(f"fourier_device: {rate_in} Hz is an integer multiple of {rate_out} Hz: that is decimate_device's branch")
-    if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 1 and str(x.dtype) in _IN_KINDS):
-        raise TypeError("fourier_device: need a 1-D CUDA tensor of int32, float32 or float64 samples")
-    x = x.contiguous()
+    x = device_samples(x, "fourier_device")
     n = int(x.shape[0])
     num, df, d_large_f = fourier_args(n, rate_in, rate_out) if n else (0, 0.0, 0.0)
     if num < 1:
@@ -176,20 +159,14 @@ def fourier_device(x, rate_in, rate_out):
     out = torch.empty(num, dtype=torch.float32, device=x.device)
     torch.cuda.current_stream(x.device).synchronize()  # the library works on the null stream: x is complete before it starts
     _lib.check(_lib.load().vp_resample_fourier(
-        x.device.index, C.c_void_p(x.data_ptr()), _IN_KINDS[str(x.dtype)], n, rate_in, rate_out, num, df, d_large_f,
+        x.device.index, C.c_void_p(x.data_ptr()), SAMPLE_KINDS[str(x.dtype)], n, rate_in, rate_out, num, df, d_large_f,
         C.c_void_p(out.data_ptr()), num), "vp_resample_fourier")
     return out
 
 
 def release_fourier_scratch(device=0):
     """Free the FFT buffers `fourier_device` keeps per device between calls; returns the bytes freed."""
-    import ctypes as C
-
-    from . import _lib
-
-    freed = C.c_size_t(0)
-    _lib.check(_lib.load().vp_resample_release_scratch(int(device), C.byref(freed)), "vp_resample_release_scratch")
-    return int(freed.value)
+    return release_scratch("vp_resample_release_scratch", device)
 
 
 def resample_trace(tr, rate_out, copy=True, fourier_on_device=False):
@@ -207,16 +184,15 @@ def resample_trace(tr, rate_out, copy=True, fourier_on_device=False):
         return tr
     dev = getattr(tr, "_dev", None)
     integer_ratio = rate_in % float(rate_out) == 0 and rate_in > rate_out
-    if dev is not None and (integer_ratio or fourier_on_device) and str(dev.dtype) in _IN_KINDS:
-        from ._lib import VolpickHipError
+    if dev is not None and (integer_ratio or fourier_on_device) and str(dev.dtype) in SAMPLE_KINDS:
         from .stream import Trace
 
-        try:
-            y = decimate_device(dev, rate_in, rate_out) if integer_ratio else fourier_device(dev, rate_in, float(rate_out))
-        except VolpickHipError as e:  # a factor beyond the kernel's tile, a trace beyond the largest FFT: said aloud, then the host path below
-            what = "decimation" if integer_ratio else "Fourier resampling"
-            warnings.warn(f"{tr.id}: {what} on the device refused ({e}); resampling on the host")
+        # refused: a factor beyond the kernel's tile, a trace beyond the largest FFT: said aloud, then the host path below
+        if integer_ratio:
+            y = try_on_device(tr.id, "decimation", lambda: decimate_device(dev, rate_in, rate_out), "resampling")
         else:
+            y = try_on_device(tr.id, "Fourier resampling", lambda: fourier_device(dev, rate_in, float(rate_out)), "resampling")
+        if y is not None:
             if copy:
                 hdr = tr.stats.copy()
                 hdr["sampling_rate"] = rate_out

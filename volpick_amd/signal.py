@@ -10,14 +10,18 @@ source of coefficients of both.
 """
 from __future__ import annotations
 
+import ctypes as C
 import warnings
 
 import numpy as np
 
-from .resample import _IN_KINDS, lowpass_sos
+from . import _lib
+from ._device import SAMPLE_KINDS, device_samples, release_scratch, try_on_device
+from .resample import lowpass_sos
 
 FILTER_TYPES = ("lowpass", "highpass", "bandpass", "bandstop")
-DETREND_TYPES = {"demean": 0, "constant": 0, "linear": 1, "simple": 2}  # VP_DETREND_*
+DETREND_TYPES = {"demean": _lib.VP_DETREND_DEMEAN, "constant": _lib.VP_DETREND_DEMEAN, "linear": _lib.VP_DETREND_LINEAR,
+                 "simple": _lib.VP_DETREND_SIMPLE}
 
 
 def butter_sos(type, df, corners=4, freq=None, freqmin=None, freqmax=None):
@@ -90,27 +94,15 @@ def detrend_array(data, type="simple"):
     return detrend(x, type="linear" if type == "linear" else "constant")
 
 
-def _device_samples(x, who):
-    import torch
-
-    if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 1 and str(x.dtype) in _IN_KINDS):
-        raise TypeError(f"{who}: need a 1-D CUDA tensor of int32, float32 or float64 samples")
-    return x.contiguous()
-
-
 def sos_filter_device(x, sos, zerophase=False):
     """``sosfilt(sos, x)`` (with ``zerophase``: forward, then backward) on the GPU (``vp_sos_filter``): ``x`` is a 1-D CUDA
     tensor of int32, float32 or float64 samples, ``sos`` up to 4 sections in scipy's layout; returns a new float32 CUDA tensor
     of the same length.  float64 coefficients, state and intermediate, one rounding to float32 at the end.  Raises
     ``VolpickHipError`` where the library refuses (more than 4 sections, an unstable section, ``a0 != 1``): there is no silent
     host fallback inside this function."""
-    import ctypes as C
-
     import torch
 
-    from . import _lib
-
-    x = _device_samples(x, "sos_filter_device")
+    x = device_samples(x, "sos_filter_device")
     n = int(x.shape[0])
     out = torch.empty(n, dtype=torch.float32, device=x.device)
     sos = np.ascontiguousarray(np.atleast_2d(np.asarray(sos, dtype=np.float64)))
@@ -118,7 +110,7 @@ def sos_filter_device(x, sos, zerophase=False):
         raise ValueError("sos_filter_device: sos must have six columns (scipy's sos layout)")
     torch.cuda.current_stream(x.device).synchronize()  # the library works on the null stream: x is complete before it starts
     _lib.check(_lib.load().vp_sos_filter(
-        x.device.index, C.c_void_p(x.data_ptr()), _IN_KINDS[str(x.dtype)], n, sos.ctypes.data_as(C.POINTER(C.c_double)),
+        x.device.index, C.c_void_p(x.data_ptr()), SAMPLE_KINDS[str(x.dtype)], n, sos.ctypes.data_as(C.POINTER(C.c_double)),
         len(sos), int(bool(zerophase)), C.c_void_p(out.data_ptr())), "vp_sos_filter")
     return out
 
@@ -127,46 +119,31 @@ def detrend_device(x, type="simple"):
     """:func:`detrend_array` on the GPU (``vp_detrend``): ``x`` is a 1-D CUDA tensor of int32, float32 or float64 samples;
     returns a new float32 CUDA tensor.  Sums in float64 in a fixed order.  Raises ``VolpickHipError`` where the library
     refuses (a line through fewer than two samples): no silent host fallback."""
-    import ctypes as C
-
     import torch
-
-    from . import _lib
 
     if type not in DETREND_TYPES:
         raise ValueError(f"detrend type {type!r} is not one of {sorted(DETREND_TYPES)}")
-    x = _device_samples(x, "detrend_device")
+    x = device_samples(x, "detrend_device")
     n = int(x.shape[0])
     out = torch.empty(n, dtype=torch.float32, device=x.device)
     torch.cuda.current_stream(x.device).synchronize()
-    _lib.check(_lib.load().vp_detrend(x.device.index, C.c_void_p(x.data_ptr()), _IN_KINDS[str(x.dtype)], n,
+    _lib.check(_lib.load().vp_detrend(x.device.index, C.c_void_p(x.data_ptr()), SAMPLE_KINDS[str(x.dtype)], n,
                                       DETREND_TYPES[type], C.c_void_p(out.data_ptr())), "vp_detrend")
     return out
 
 
 def release_filter_scratch(device=0):
     """Free the scratch `sos_filter_device` and `detrend_device` keep per device between calls; returns the bytes freed."""
-    import ctypes as C
-
-    from . import _lib
-
-    freed = C.c_size_t(0)
-    _lib.check(_lib.load().vp_sos_filter_release_scratch(int(device), C.byref(freed)), "vp_sos_filter_release_scratch")
-    return int(freed.value)
+    return release_scratch("vp_sos_filter_release_scratch", device)
 
 
 def _on_device(tr, what, run, host):
     """``tr`` processed in place: on the device if it lives there (``run``: device tensor -> float32 device tensor), on the host
     otherwise or where the library refuses (``host``: ndarray -> float64 ndarray)."""
     dev = getattr(tr, "_dev", None)
-    if dev is not None and str(dev.dtype) in _IN_KINDS:
-        from ._lib import VolpickHipError
-
-        try:
-            y = run(dev)
-        except VolpickHipError as e:
-            warnings.warn(f"{tr.id}: {what} on the device refused ({e}); {what} on the host")
-        else:
+    if dev is not None and str(dev.dtype) in SAMPLE_KINDS:
+        y = try_on_device(tr.id, what, lambda: run(dev), what)
+        if y is not None:
             tr._dev, tr._data = y, None
             return tr
     tr.data = host(tr.data)
