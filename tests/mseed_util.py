@@ -24,3 +24,12 @@ def three_component(n, rng, start_us=T0, rate=100.0, net="XX", sta="VOLC", loc="
 
 def file_bytes(traces, **kw):
     return OM.write_mseed(traces, **kw)
+
+
+def mixed_file_bytes(seed=71, n=20000):
+    """One buffer of miniSEED 2 records (512 bytes, Steim-2) followed by miniSEED 3 records (Steim-2, with extra headers): what
+    the threading tests scan from several threads at once."""
+    rng = np.random.default_rng(seed)
+    v2 = file_bytes(three_component(n, rng), with_b1001=True)
+    v3 = OM.write_mseed3(three_component(n, rng, sta="VOL3"), max_payload=640, extra_headers=b'{"a":1}')
+    return v2 + v3
