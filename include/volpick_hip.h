@@ -674,6 +674,46 @@ int vp_attributes(int device_id, const float* data, int64_t n_samples, const vp_
 int vp_bank_attributes(vp_bank* bank, const vp_attr_row* rows, int n_rows, double* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Spectrograms on the device: the numbers of the reference's spectrogram() (volpick/data/utils.py:1251-1440) up to the point
+ * where it starts to draw, i.e. matplotlib.mlab.specgram(data - data.mean(), Fs, NFFT, pad_to, noverlap) without bin 0, then
+ * sqrt or 10 log10.  The host plans nfft, pad and hop from the sampling rate (volpick_amd/spectrogram.py, plan); the rule is
+ * restated in tests/spectrogram_f64.py.  Per series, in float64:
+ *
+ *   x = data - mean(data), the mean over the WHOLE series (all n samples, whatever the frame range);
+ *   frame j = x[j hop : j hop + nfft] times np.hanning(nfft), zero-padded to pad;  X = its DFT;
+ *   P[k] = |X[k]|^2 / samp_rate / sum(w^2) for k = 1 .. pad / 2, doubled for every k but pad / 2;
+ *   out = sqrt(P) (dbscale == 0) or 10 log10(P) (dbscale == 1), rounded once to float32.
+ *
+ * in_dev: n_series series of n samples each, series i at in_dev + i * series_stride samples, int32, float32 or float64
+ * (in_kind): a (3, N) block or an (M, 3, L) tensor in one launch.  A series has (n - (nfft - hop)) / hop frames; the call
+ * writes frames [first_frame, first_frame + n_frames) into out_dev, (n_series, pad / 2, n_frames) float32 in device memory,
+ * frequency-major as the reference's specgram[f, t] (no flipud).  A frame range equals the same columns of the full result
+ * bit for bit, so a day can be produced in pieces.  A NaN or Inf anywhere in a series makes that series' whole output NaN
+ * (the reference's mean is non-finite then); a frame of exact zeros gives 0, or -inf with dbscale.  Deterministic: no
+ * atomics, every sum in a fixed order.  For float32 input the reference's mean accumulates in float32; this one does not.
+ *
+ * Every argument is checked on the host before any launch; a refusal leaves out_dev untouched.  VP_ERR_INVALID: a null
+ * pointer, an unknown in_kind, n_series < 1, n < nfft, hop < 1 or hop > nfft, nfft or pad not a power of two or pad < nfft,
+ * a frame range outside [0, (n - (nfft - hop)) / hop], series_stride < n, a samp_rate that is not finite and positive,
+ * dbscale other than 0 or 1.  VP_ERR_UNSUPPORTED: beyond nfft 32..512, pad / nfft <= 16, pad <= 4096, 65535 series of 2^40
+ * samples.  VP_ERR_NOMEM: the scratch cannot be allocated.  n_frames == 0 is a valid call that writes nothing.
+ *
+ * Runs on `stream` (hipStream_t, NULL = legacy default stream) and returns after the work is done.  Calls on one device are
+ * serialised.  A workgroup owns min(VP_SPECTROGRAM_TILE_FRAMES, 4096 / nfft) consecutive frames.  The scratch (the series'
+ * means, the mean pass's partial sums, the window and root tables) is kept per device, grow-only, between calls;
+ * vp_spectrogram_release_scratch frees it (bytes_freed may be NULL) -- the other release calls do not touch it.
+ * vp_spectrogram_bench: mean time in ms (HIP events on a stream of its own, two untimed repetitions first) of `iters`
+ * repetitions of the whole call (ms_total) and of the frame kernel alone (ms_frames, may be NULL): bench only. */
+#define VP_SPECTROGRAM_TILE_FRAMES 32
+int vp_spectrogram(int device_id, const void* in_dev, int in_kind, int n_series, int64_t series_stride, int64_t n,
+                   double samp_rate, int nfft, int pad, int hop, int dbscale, int64_t first_frame, int64_t n_frames,
+                   float* out_dev, void* stream);
+int vp_spectrogram_release_scratch(int device_id, size_t* bytes_freed);
+int vp_spectrogram_bench(int device_id, const void* in_dev, int in_kind, int n_series, int64_t series_stride, int64_t n,
+                         double samp_rate, int nfft, int pad, int hop, int dbscale, int64_t first_frame, int64_t n_frames,
+                         float* out_dev, int iters, float* ms_total, float* ms_frames);
+
+/* ---------------------------------------------------------------------------------------------
  * Multi-GPU bring-up.  The reference is single-GPU; windows are independent given the
  * weights, so the one exchange is the start-up broadcast of the flat weight blob from the root rank: a single
  * ncclBroadcast over RCCL (xGMI inside a node), after which vp_create(..., VP_MEM_DEVICE, ...) builds the plan from the

@@ -6,6 +6,11 @@ Drop-in for the ``seisbench.models`` picker API volpick users call:
     picker = sbm.EQTransformer.from_pretrained("volpick")
     picks = picker.classify(stream, batch_size=256, overlap=5500, blinding=(500, 500),
                             stacking="avg", P_threshold=0.2, S_threshold=0.2).picks
+
+``volpick_amd.spectrogram`` is the module of the reference's ``spectrogram()`` as numbers on the GPU:
+``volpick_amd.spectrogram.spectrogram(x, samp_rate, ...)`` for a CUDA tensor ``(..., N)``, ``Trace.spectrogram()`` /
+``Stream.spectrogram()`` for traces (device-backed ones stay on the device), ``volpick_amd.spectrogram.plan`` for the host
+plan, ``release_spectrogram_scratch`` for the scratch the kernel keeps.
 """
 from .models import EQTransformer, PhaseNet, WaveformModel  # noqa: F401
 from .picks import ClassifyOutput, Detection, DetectionList, Pick, PickList  # noqa: F401
@@ -14,5 +19,7 @@ from ._lib import VolpickHipError  # noqa: F401
 from .io import read  # noqa: F401
 from .attributes import bank_attributes, pick_attributes, plan_rows  # noqa: F401
 from .signal import butter_sos, detrend_array, detrend_device, filter_array, sos_filter_device  # noqa: F401
+from . import spectrogram  # noqa: F401
+from .spectrogram import Spectrogram, release_spectrogram_scratch  # noqa: F401
 
 __version__ = "0.1.0"

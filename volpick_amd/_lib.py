@@ -96,6 +96,8 @@ VP_DETREND_DEMEAN, VP_DETREND_LINEAR, VP_DETREND_SIMPLE = 0, 1, 2
 
 VP_ATTR_DEMEAN, VP_ATTR_MAX_WINDOW, VP_ATTR_OUT = 1, 2048, 14
 
+VP_SPECTROGRAM_TILE_FRAMES = 32
+
 
 class VpAttrRow(C.Structure):
     _fields_ = [
@@ -297,6 +299,17 @@ SIGNATURES = {
     ),
     "vp_attributes": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.POINTER(VpAttrRow), C.c_int, C.c_void_p, C.c_void_p]),
     "vp_bank_attributes": (C.c_int, [_H, C.POINTER(VpAttrRow), C.c_int, C.c_void_p, C.c_void_p]),
+    "vp_spectrogram": (
+        C.c_int,
+        [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64,
+         C.c_int64, C.c_void_p, C.c_void_p],
+    ),
+    "vp_spectrogram_release_scratch": (C.c_int, [C.c_int, C.POINTER(C.c_size_t)]),
+    "vp_spectrogram_bench": (
+        C.c_int,
+        [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64,
+         C.c_int64, C.c_void_p, C.c_int, _FP, _FP],
+    ),
     "vp_last_error": (C.c_char_p, []),
     "vp_version": (C.c_char_p, []),
 }

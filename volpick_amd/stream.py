@@ -212,6 +212,16 @@ class Trace:
 
         return detrend_trace(self, type)
 
+    def spectrogram(self, **kw):
+        """The numbers of a spectrogram, on the GPU: ObsPy's method of this name draws; this one returns what it would draw --
+        a ``volpick_amd.spectrogram.Spectrogram`` ``(data, freq, time)``, ``data`` a float32 CUDA tensor ``(n_freq, n_frames)``
+        as the reference's ``specgram[f, t]``.  Keywords: ``per_lap=0.9, wlen=None, dbscale=False, mult=8.0, frames=None`` (see
+        ``volpick_amd.spectrogram.spectrogram``).  A device-backed trace is read where it lies and stays there; a host trace is
+        uploaded and goes through the same kernel (no host fallback); a masked trace is refused."""
+        from .spectrogram import trace_spectrogram
+
+        return trace_spectrogram(self, **kw)
+
     def __len__(self):
         return int(self.stats["npts"])
 
@@ -260,6 +270,10 @@ class Stream:
         for tr in self.traces:
             tr.detrend(type)
         return self
+
+    def spectrogram(self, **kw):
+        """``[tr.spectrogram(**kw) for tr in self]``: one result per trace (ObsPy's method draws; this one returns numbers)."""
+        return [tr.spectrogram(**kw) for tr in self.traces]
 
     def sort(self, keys=("network", "station", "location", "channel", "starttime")):
         self.traces.sort(key=lambda t: tuple(str(t.stats[k]) if k != "starttime" else t.stats[k]._us for k in keys))
