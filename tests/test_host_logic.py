@@ -318,3 +318,76 @@ def test_records_from_columns_sort_like_the_records_and_are_built_on_first_touch
     assert list(copy.copy(va.PickList(sorted(want_p)[:4]))) == sorted(want_p)[:4] and len(copy.copy(va.PickList())) == 0
     empty_p, empty_d = _records_from_columns([], [], [], labels, 100.0)
     assert len(empty_p) == 0 and list(empty_d) == []
+
+
+# ------------------------------------------------------------ the single copies of the picker's host path (LOG section 36)
+def test_trigger_tuples_and_columns_round_trip():
+    from volpick_amd.models import _trigger_columns, _trigger_tuples
+
+    dtypes = [np.int32, np.int64, np.int64, np.int64, np.float32]
+    for empty in (_trigger_columns(), _trigger_columns([]), _trigger_columns(())):
+        assert [c.dtype for c in empty] == dtypes and all(c.shape == (0,) for c in empty)
+        assert _trigger_tuples(empty) == []
+    v = np.array([0x3F7FFFFF, 0x00000001, 0x3DCCCCCD], np.uint32).view(np.float32)  # just under 1, a denormal, float32(0.1)
+    trig = [(2, 2**40 + 1, 2**40 + 9, 2**40 + 5, float(v[0])), (0, 0, 0, 0, float(v[1])), (1, 7, 9, 8, float(v[2]))]
+    for n in (1, 3):
+        cols = _trigger_columns(trig[:n])
+        assert [c.dtype for c in cols] == dtypes and all(c.shape == (n,) for c in cols)
+        assert cols[4].view(np.uint32).tolist() == v[:n].view(np.uint32).tolist()  # the value's bits survive
+        assert cols[1][0] == 2**40 + 1  # an index beyond int32 stays int64
+        back = _trigger_tuples(cols)
+        assert back == trig[:n] and all(type(x) is int for t in back for x in t[:4]) and all(type(t[4]) is float for t in back)
+        assert _trigger_columns(cols) is cols  # columns pass through
+        again = _trigger_columns(back)
+        assert all(np.array_equal(a, b) and a.dtype == b.dtype for a, b in zip(again, cols))
+
+
+@pytest.mark.parametrize("max_batch", [8, 256])
+@pytest.mark.parametrize("batch_size", [0, 1, 256, 10**6])
+@pytest.mark.parametrize("stacking", ["avg", "max"])
+def test_call_args_are_the_inline_expressions(stacking, batch_size, max_batch):
+    eq = va.EQTransformer.from_pretrained("volpick")
+    eq._max_batch = max_batch
+    args = eq._argdict(dict(overlap=5500, blinding=(400, 600), stacking=stacking, batch_size=batch_size))
+    # what every caller spelled out before there was one helper
+    want_stacking = _lib.VP_STACK_AVG if args["stacking"] == "avg" else _lib.VP_STACK_MAX
+    want_batch = max(1, min(int(args["batch_size"]), eq._max_batch))
+    got = eq._call_args(args)
+    assert got == (5500, 400, 600, want_stacking, want_batch) and all(type(v) is int for v in got)
+    assert want_stacking == {"avg": 0, "max": 1}[stacking] and want_batch == {0: 1, 1: 1, 256: min(256, max_batch), 10**6: max_batch}[batch_size]
+    # _is_long reads the same clamp: at least two full batches for each of the four contexts
+    step, n_windows = 500, 2 * want_batch * eq.n_contexts
+    assert eq._is_long(6000 + step * (n_windows - 1), args) and not eq._is_long(6000 + step * (n_windows - 1) - 1, args)
+
+
+def test_rows_slice_is_the_slice_of_the_stacked_block_and_stacks_nothing():
+    from volpick_amd.models import _Rows
+
+    rng = np.random.default_rng(36)
+    masked = np.ma.masked_array(rng.normal(size=1000).astype(np.float32), mask=rng.random(1000) < 0.1)
+    parts = [rng.normal(size=1000).astype(np.float32), rng.integers(-2**20, 2**20, 1000).astype(np.int32), rng.normal(size=1000),
+             masked.filled(0)]  # (_group_stream fills a masked row with 0 before it builds the _Rows)
+    rows = _Rows(parts)
+    stacked = np.asarray(rows)
+    assert stacked.shape == (4, 1000) == rows.shape and stacked.dtype == np.float32
+    assert (stacked[3][masked.mask] == 0).all() and np.array_equal(stacked[3][~masked.mask], masked.compressed())
+    for lo, hi in ((0, 1000), (3, 997), (500, 501), (None, None), (None, 10), (990, None)):
+        cut = rows.slice(lo, hi)
+        assert isinstance(cut, _Rows) and cut.shape == stacked[:, lo:hi].shape
+        assert np.array_equal(np.asarray(cut), stacked[:, lo:hi]) and np.array_equal(rows[:, lo:hi], stacked[:, lo:hi])
+        for p, q in zip(cut.parts, parts):  # views of the caller's rows, in their own dtypes
+            assert p.base is q and p.dtype == q.dtype and np.shares_memory(p, q)
+
+
+def test_group_stream_yields_the_same_keys_on_both_paths():
+    t0 = va.UTCDateTime("2005-05-31T21:04:52.110000Z")
+    mk = lambda ch, start, n: va.Trace(np.ones(n, np.float32), dict(network="XX", station="AAA", location="00", channel=ch,  # noqa: E731
+                                                                    starttime=start, sampling_rate=100.0))
+    keys = {"data", "starttime", "trace_id", "network", "station", "location"}
+    full = list(_group_stream(va.Stream([mk("HHZ", t0, 4000), mk("HHN", t0, 4000), mk("HHE", t0, 4000)]), "ZNE", 100.0, True, 3001))
+    ragged = list(_group_stream(va.Stream([mk("HHZ", t0, 4000), mk("HHN", t0 + 1.0, 3500)]), "ZNE", 100.0, True, 3001))
+    assert len(full) == len(ragged) == 1
+    assert type(full[0]["data"]).__name__ == "_Rows" and isinstance(ragged[0]["data"], np.ndarray)  # one stack / the zero fill
+    for g in full + ragged:
+        assert set(g) == keys and list(g) == ["data", "starttime", "trace_id", "network", "station", "location"]
+        assert (g["trace_id"], g["network"], g["station"], g["location"], g["starttime"]) == ("XX.AAA.00", "XX", "AAA", "00", t0)

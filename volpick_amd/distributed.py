@@ -11,6 +11,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from .models import _records_from_columns, _trigger_columns
+
 
 def shard_range(n_items: int, rank: int, world_size: int):
     """Contiguous [lo, hi) share of ``n_items`` for ``rank``; sizes differ by at most one."""
@@ -238,10 +240,7 @@ def annotate_stream_sharded(model, data, group=None, annotate_fn=None, **kwargs)
     on_gpu = annotate_fn is None
     if on_gpu:
         dev = torch.device("cuda", model._device_index if model._device_index is not None else torch.cuda.current_device())
-
-        def annotate_fn(block):
-            fn = model._annotate_segments if model._is_long(block.shape[1], args) else model._annotate_block
-            return fn(block, args)[0]
+        annotate_fn = lambda block: model._annotate_data(block, args)[0]  # noqa: E731
     else:
         dev = torch.device("cpu")
     width = max(sg["keep_hi"] - sg["keep_lo"] for sg in segs)
@@ -325,17 +324,6 @@ def _head_run_end(pick_fn, rows, spec, lo, hi):
 _EXCHANGE_CAP = 16  # trigger rows per rank that travel WITH the header (classify_stream_sharded): enough for a quiet segment
 
 
-def _trigger_columns(found):
-    """[(spec, on, off, peak, value)] or the five arrays -> the five arrays (int32, int64 x 3, float32)."""
-    if isinstance(found, tuple):
-        return found
-    if not found:
-        return (np.empty(0, np.int32), np.empty(0, np.int64), np.empty(0, np.int64), np.empty(0, np.int64), np.empty(0, np.float32))
-    z = list(zip(*found))
-    return (np.asarray(z[0], np.int32), np.asarray(z[1], np.int64), np.asarray(z[2], np.int64), np.asarray(z[3], np.int64),
-            np.asarray(z[4], np.float32))
-
-
 def stitch_trigger_columns(parts, n_specs):
     """``stitch_triggers`` on columns.  ``parts`` (in segment order): (keep_lo, keep_hi, head_end[n_specs], columns) with the
     columns in stream sample indices.  Only the triggers that touch a cut -- the one that ends on a part's last owned sample
@@ -383,7 +371,6 @@ def classify_stream_sharded(model, data, starttime, trace_id, group=None, annota
     import torch
     import torch.distributed as dist
 
-    from .models import _records_from_columns
     from .picks import ClassifyOutput
     from .segments import plan_segments
 
@@ -398,13 +385,11 @@ def classify_stream_sharded(model, data, starttime, trace_id, group=None, annota
         n, load = int(data.shape[1]), (lambda lo, hi: data[:, lo:hi])
     segs = plan_segments(n, model.in_samples, args["overlap"], args["blinding"], world)
     if annotate_fn is None:
-        def annotate_fn(block):
-            fn = model._annotate_segments if model._is_long(block.shape[1], args) else model._annotate_block
-            return fn(block, args)[0]
+        annotate_fn = lambda block: model._annotate_data(block, args)[0]  # noqa: E731
     if pick_fn is None:
         def pick_fn(rows, sp):
             return model._pick_rows(rows, sp, columns=True)
-    cols = _trigger_columns([])
+    cols = _trigger_columns()
     head, keep = [-1] * n_specs, (-1, -1)
     t_gpu = t_scan = 0.0
     if rank < len(segs):  # a short stream has fewer segments than ranks: the surplus ranks own nothing
