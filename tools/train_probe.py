@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Where does the wall time of a training step go?  tr.step() (torch event + stream wait per step) against the bare
-vp_train_step call on the same device pointers, and the host time of the call alone (enqueue only)."""
+vp_train_step call on the same device pointers, and the host time of the call alone (enqueue only).
+usage: train_probe.py [bf16|fp32]"""
 import ctypes as C
 import sys
 import time
@@ -16,7 +17,7 @@ from volpick_amd.train import PhaseNetTrainer  # noqa: E402
 B = 512
 x, y = make_batch(B)
 xd, yd = torch.from_numpy(x).cuda(), torch.from_numpy(y).cuda()
-tr = PhaseNetTrainer(PhaseNet.from_pretrained("volpick"), max_batch=B, dtype="bf16")
+tr = PhaseNetTrainer(PhaseNet.from_pretrained("volpick"), max_batch=B, dtype=sys.argv[1] if len(sys.argv) > 1 else "bf16")
 lib = _lib.load()
 
 

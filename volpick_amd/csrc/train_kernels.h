@@ -442,12 +442,12 @@ __global__ __launch_bounds__(256) void head_fwd_bwd_kernel(const HeadArgs2 h) {
                                         ((double)shv[2][threadIdx.x] + (double)shv[3][threadIdx.x]);
 }
 
-// The same head with NS consecutive samples per thread (NS = 2: even-aligned pairs, 4-byte accesses of bf16 rows; NS = 4:
-// quads, 8-byte accesses -- half the blocks, half the 28-value block reductions per sample: 36 -> 27 us per step).
+// The same head on bf16 rows with NS = 4 consecutive samples per thread, 8-byte accesses (against even-aligned pairs: half
+// the blocks, half the 28-value block reductions per sample: 36 -> 27 us per step).
 // grid (ceil(T / (256 NS)), B), 256 threads.
 template <class T, int NS = 2>
 __global__ __launch_bounds__(256) void head_fwd_bwd_pair_kernel(const HeadArgs2 h) {
-  static_assert(NS == 2 || (NS == 4 && sizeof(T) == 2), "pairs, or quads of bf16");
+  static_assert(NS == 4 && sizeof(T) == 2, "quads of bf16 (the template head is the name profiles know the kernel by)");
   const int b = blockIdx.y, t0 = NS * (blockIdx.x * 256 + threadIdx.x);
   float w[3][8], bb[3];
 #pragma unroll
@@ -463,12 +463,8 @@ __global__ __launch_bounds__(256) void head_fwd_bwd_pair_kernel(const HeadArgs2 
     float x[8][NS], ga[8][NS];
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-      if constexpr (NS == 2) {
-        Elem<T>::load2(h.a.row<T>(b, k) + t0, reinterpret_cast<float(&)[2]>(x[k]));
-      } else {
-        const uint2 r = *reinterpret_cast<const uint2*>(h.a.row<T>(b, k) + t0);
-        x[k][0] = bf16_lo(r.x), x[k][1] = bf16_hi(r.x), x[k][2] = bf16_lo(r.y), x[k][3] = bf16_hi(r.y);
-      }
+      const uint2 r = *reinterpret_cast<const uint2*>(h.a.row<T>(b, k) + t0);
+      x[k][0] = bf16_lo(r.x), x[k][1] = bf16_hi(r.x), x[k][2] = bf16_lo(r.y), x[k][3] = bf16_hi(r.y);
     }
     const float scale = 1.f / ((float)h.B * (float)h.T);
 #pragma unroll
@@ -513,13 +509,8 @@ __global__ __launch_bounds__(256) void head_fwd_bwd_pair_kernel(const HeadArgs2 
       }
     }
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      if constexpr (NS == 2) {
-        Elem<T>::store2(h.ga.row<T>(b, k) + t0, ga[k][0], ga[k][1]);
-      } else {
-        *reinterpret_cast<uint2*>(h.ga.row<T>(b, k) + t0) = make_uint2(pack_bf16x2(ga[k][0], ga[k][1]), pack_bf16x2(ga[k][2], ga[k][3]));
-      }
-    }
+    for (int k = 0; k < 8; ++k)
+      *reinterpret_cast<uint2*>(h.ga.row<T>(b, k) + t0) = make_uint2(pack_bf16x2(ga[k][0], ga[k][1]), pack_bf16x2(ga[k][2], ga[k][3]));
   }
   __shared__ float shv[4][28];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -738,6 +729,8 @@ struct WgradCfg {
   // (the LDS budget of wgrad_kernel is asserted there: wgrad_bf16_kernel has images of its own, WgradB)
 };
 
+// (T and the PAIRS branch -- bf16 rows fetched as pairs -- are instantiated by nothing: bf16 rows have wgrad_bf16_kernel.  They stay:
+// with them cut out the compiler gave all 18 fp32 instantiations another instruction stream, and the kernels are measured as they are.)
 template <class C, class T = float>
 __global__ __launch_bounds__(64 * C::NWAVE) void wgrad_kernel(const WgradArgs a) {
   // bf16 rows are fetched as even-aligned PAIRS (4-byte loads) and widened while they are parked in LDS: a hi window
@@ -1142,13 +1135,7 @@ __global__ __launch_bounds__(64 * WgradB<C>::NWAVE) void wgrad_bf16_kernel(const
 
 template <class C>
 int launch_wgrad_bf16(const WgradArgs& a, int grid, hipStream_t s) {
-  static bool attr = false;
-  constexpr size_t lds = (size_t)WgradB<C>::LDS_ELEMS * 2;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_bf16_kernel<C, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_bf16_kernel<C, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr = true;
-  }
+  constexpr size_t lds = (size_t)WgradB<C>::LDS_ELEMS * 2;  // (the owner of the launches raises the kernels' dynamic LDS limit to it)
   if (a.off & 1) {
     hipLaunchKernelGGL((wgrad_bf16_kernel<C, 1>), dim3(grid), dim3(64 * WgradB<C>::NWAVE), lds, s, a);
   } else {
@@ -1157,9 +1144,9 @@ int launch_wgrad_bf16(const WgradArgs& a, int grid, hipStream_t s) {
   return 0;
 }
 
-template <class C, class T = float>
+template <class C>
 int launch_wgrad(const WgradArgs& a, int grid, hipStream_t s) {
-  hipLaunchKernelGGL((wgrad_kernel<C, T>), dim3(grid), dim3(64 * C::NWAVE), 0, s, a);
+  hipLaunchKernelGGL((wgrad_kernel<C, float>), dim3(grid), dim3(64 * C::NWAVE), 0, s, a);
   return 0;
 }
 

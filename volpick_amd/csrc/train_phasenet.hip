@@ -10,6 +10,11 @@
 // inference packers); weight gradients on wgrad_kernel; everything else in train_kernels.h.
 // ConvTranspose outputs are kept at full length (4 L + 3): BatchNorm sees the samples the U-Net
 // crops away, and they receive gradient through the batch statistics.
+//
+// This file, top to bottom: the table of the 18 layers (LayerTable: one row per layer, its three Cfg types), the plan
+// built from it (build_plan: everything else follows from a row's kind and level), the Trainer and its device memory
+// (DevArray, upload), the step as a sequence of phases (forward_backward) with the weight gradients' side queue
+// (WgradQueue), and the C entry points.
 #include <hip/hip_ext.h>
 
 #include <memory>
@@ -24,75 +29,72 @@ namespace {
 
 constexpr int T0 = 3001, T1 = 751, T2 = 188, T3 = 47, T4 = 12;
 constexpr int NLAYER = 18;
-static int wg_rows_cap(int out_n);  // rows of partial weight-gradient results a launch may write (defined below)
+constexpr int LEN[5] = {T0, T1, T2, T3, T4};  // samples, channels of a level
+constexpr int CH[5] = {8, 16, 32, 64, 128};
+constexpr int PADL[4] = {3, 2, 1, 2};          // left padding of the stride-4 conv that leaves a level
 
-//                    CIN1 CIN2 COUT P TAPS SN IN_OFF OUT_OFF WM WN NW RELU EPI
-// (BF = 1: rows stored as bf16, conv_mfma.h)
-// forward (no activation: BatchNorm needs the raw output)
-template <int BF> using F_inc = ConvCfg<3, 0, 8, 2, 8, 2, -3, 0, 1, 4, 8, 0, EPI_STORE, 0, 0, BF>;
-template <int BF> using F_d0s = ConvCfg<8, 0, 8, 2, 8, 2, -3, 0, 1, 4, 8, 0, EPI_STORE, 0, 0, BF>;
-template <int BF> using F_d0d = ConvCfg<8, 0, 8, 2, 11, 8, -3, 0, 1, 4, 2, 0, EPI_STORE, 0, 0, BF>;
-template <int BF> using F_d1s = ConvCfg<8, 0, 16, 1, 7, 1, -3, 0, 1, 4, 4, 0, EPI_STORE, 0, 0, BF>;
-template <int BF> using F_d1d = ConvCfg<16, 0, 16, 1, 7, 4, -2, 0, 1, 4, 1, 0, EPI_STORE, 0, 0, BF>;
-template <int BF> using F_d2s = ConvCfg<16, 0, 32, 1, 7, 1, -3, 0, 2, 2, 3, 0, EPI_STORE, 0, 0, BF>;
-template <int BF> using F_d2d = ConvCfg<32, 0, 32, 1, 7, 4, -1, 0, 2, 2, 1, 0, EPI_STORE, 0, 0, BF>;
-template <int BF> using F_d3s = ConvCfg<32, 0, 64, 1, 7, 1, -3, 0, 4, 1, 3, 0, EPI_STORE, 0, 0, BF>;
-template <int BF> using F_d3d = ConvCfg<64, 0, 64, 1, 7, 4, -2, 0, 4, 1, 1, 0, EPI_STORE, 0, 0, BF>;
-template <int BF> using F_d4s = ConvCfg<64, 0, 128, 1, 7, 1, -3, 0, 4, 1, 1, 0, EPI_STORE, 0, 0, BF>;
-template <int BF> using F_u0T = ConvCfg<128, 0, 64, 4, 2, 1, -1, 0, 4, 1, 1, 0, EPI_STORE, 0, 0, BF>;
-template <int BF> using F_u0s = ConvCfg<64, 64, 64, 1, 7, 1, -3, 0, 4, 1, 3, 0, EPI_STORE, 0, 0, BF>;
-template <int BF> using F_u1T = ConvCfg<64, 0, 32, 4, 2, 1, -1, 0, 4, 1, 3, 0, EPI_STORE, 0, 0, BF>;
-template <int BF> using F_u1s = ConvCfg<32, 32, 32, 1, 7, 1, -3, 0, 2, 2, 3, 0, EPI_STORE, 0, 0, BF>;
-template <int BF> using F_u2T = ConvCfg<32, 0, 16, 4, 2, 1, -1, 0, 4, 1, 4, 0, EPI_STORE, 0, 0, BF>;
-template <int BF> using F_u2s = ConvCfg<16, 16, 16, 1, 7, 1, -3, 0, 1, 4, 4, 0, EPI_STORE, 0, 0, BF>;
-template <int BF> using F_u3T = ConvCfg<16, 0, 8, 4, 2, 1, -1, 0, 2, 2, 4, 0, EPI_STORE, 0, 0, BF>;
-template <int BF> using F_u3s = ConvCfg<8, 8, 8, 2, 8, 2, -3, 0, 1, 4, 8, 0, EPI_STORE, 0, 0, BF>;
-// input gradients: conv(k7, same) -> conv with the flipped, transposed kernel
-template <int BF> using G_d0s = ConvCfg<8, 0, 8, 2, 8, 2, -3, 0, 1, 4, 8, 0, EPI_STORE, 0, 0, BF>;
-template <int BF> using G_d1s = ConvCfg<16, 0, 8, 2, 8, 2, -3, 0, 1, 4, 2, 0, EPI_STORE, 0, 0, BF>;
-template <int BF> using G_d2s = ConvCfg<32, 0, 16, 1, 7, 1, -3, 0, 1, 4, 3, 0, EPI_STORE, 0, 0, BF>;
-template <int BF> using G_d3s = ConvCfg<64, 0, 32, 1, 7, 1, -3, 0, 2, 2, 2, 0, EPI_STORE, 0, 0, BF>;
-template <int BF> using G_d4s = ConvCfg<128, 0, 64, 1, 7, 1, -3, 0, 4, 1, 1, 0, EPI_STORE, 0, 0, BF>;
-template <int BF> using G_u0s = ConvCfg<64, 0, 128, 1, 7, 1, -3, 0, 4, 1, 3, 0, EPI_STORE, 0, 0, BF>;
-template <int BF> using G_u1s = ConvCfg<32, 0, 64, 1, 7, 1, -3, 0, 2, 2, 3, 0, EPI_STORE, 0, 0, BF>;
-template <int BF> using G_u2s = ConvCfg<16, 0, 32, 1, 7, 1, -3, 0, 2, 2, 4, 0, EPI_STORE, 0, 0, BF>;
-template <int BF> using G_u3s = ConvCfg<8, 0, 16, 1, 7, 1, -3, 0, 1, 4, 8, 0, EPI_STORE, 0, 0, BF>;
-// conv(k7, s4, left pad p) -> ConvTranspose(k7, s4) of the same kernel, output shifted by -p
-template <int BF> using G_d0d = ConvCfg<8, 0, 8, 4, 2, 1, -1, -3, 2, 2, 4, 0, EPI_STORE, 0, 0, BF>;
-template <int BF> using G_d1d = ConvCfg<16, 0, 16, 4, 2, 1, -1, -2, 4, 1, 4, 0, EPI_STORE, 0, 0, BF>;
-template <int BF> using G_d2d = ConvCfg<32, 0, 32, 4, 2, 1, -1, -1, 4, 1, 3, 0, EPI_STORE, 0, 0, BF>;
-template <int BF> using G_d3d = ConvCfg<64, 0, 64, 4, 2, 1, -1, -2, 4, 1, 1, 0, EPI_STORE, 0, 0, BF>;
-// ConvTranspose(k7, s4) -> conv(k7, s4, no pad) of the same kernel over the full-length gradient
-template <int BF> using G_u0T = ConvCfg<64, 0, 128, 1, 7, 4, 0, 0, 4, 1, 1, 0, EPI_STORE, 0, 0, BF>;
-template <int BF> using G_u1T = ConvCfg<32, 0, 64, 1, 7, 4, 0, 0, 4, 1, 3, 0, EPI_STORE, 0, 0, BF>;
-template <int BF> using G_u2T = ConvCfg<16, 0, 32, 1, 7, 4, 0, 0, 2, 2, 3, 0, EPI_STORE, 0, 0, BF>;
-template <int BF> using G_u3T = ConvCfg<8, 0, 16, 1, 7, 4, 0, 0, 1, 4, 4, 0, EPI_STORE, 0, 0, BF>;
+// ---- the layers ------------------------------------------------------------------------------------------------------
+// A layer is a kind and a level.  SAME / DOWN: the stride-1 and the stride-4 conv of down_branch.<level>; CONVT / UP_SAME:
+// the ConvTranspose up to <level> and the conv over concat(skip, up) there, up_branch.<3 - level>.
+enum Kind { INC, SAME, DOWN, CONVT, UP_SAME };
+// forward order: 0 inc, 1+2i down{i}.same, 2+2i down{i}.down (i<4), 9 down4.same, 10+2j up{j}.convT, 11+2j up{j}.same
+constexpr int layer_index(Kind k, int lv) {
+  return k == INC ? 0 : k == SAME ? (lv < 4 ? 1 + 2 * lv : 9) : k == DOWN ? 2 + 2 * lv : (k == CONVT ? 10 : 11) + 2 * (3 - lv);
+}
+constexpr int layer_cout(Kind k, int lv) { return k == INC ? 8 : CH[lv]; }
+constexpr int layer_cin(Kind k, int lv) {
+  return k == INC ? 3 : k == SAME ? (lv ? CH[lv - 1] : 8) : k == DOWN ? CH[lv] : k == CONVT ? CH[lv + 1] : 2 * CH[lv];
+}
+
+// One row of the table: where the layer stands and the Cfg types of its forward (F), input-gradient (G, void for the
+// first layer) and weight-gradient (W) launches.  bind_layer checks every Cfg figure that kind and level decide.
+template <int LI_, Kind KIND_, int LV_, class F_, class G_, class W_>
+struct LayerCfg {
+  static constexpr int LI = LI_, LV = LV_;
+  static constexpr Kind KIND = KIND_;
+  using F = F_;
+  using G = G_;
+  using W = W_;
+};
+template <class... R>
+struct LayerList {};
+
+//                    CIN1 CIN2 COUT P TAPS SN IN_OFF OUT_OFF WM WN NW    (BF = 1: rows stored as bf16, conv_mfma.h)
+// (no activation: BatchNorm needs the raw output)
+template <int BF, int... V>
+using TC = ConvCfg<V..., 0, EPI_STORE, 0, 0, BF>;
+//                     LO HI1 HI2 K S NWAVE TT [WB windows per item]
 // (level-0 stride-1 layers, bf16 rows: 512-sample chunks -- half the barriers per byte; same-box 1.394 -> 1.384 ms per step)
 constexpr int W0TT = 512;
-//                     LO HI1 HI2 K S NWAVE TT [WB windows per item]
-template <int BF> using W_inc = WgradCfg<8, 3, 0, 7, 1, 8, BF ? W0TT : 256>;
-template <int BF> using W_d0s = WgradCfg<8, 8, 0, 7, 1, 8, BF ? W0TT : 256>;
-using W_d0d = WgradCfg<8, 8, 0, 7, 4, 8, 256>;
-using W_d1s = WgradCfg<16, 8, 0, 7, 1, 8, 256>;
-using W_d1d = WgradCfg<16, 16, 0, 7, 4, 8, 96>;
-using W_d2s = WgradCfg<32, 16, 0, 7, 1, 8, 192>;
-using W_d2d = WgradCfg<32, 32, 0, 7, 4, 4, 48>;
-using W_d3s = WgradCfg<64, 32, 0, 7, 1, 8, 48>;
-using W_d3d = WgradCfg<64, 64, 0, 7, 4, 16, 12, 2>;
-using W_d4s = WgradCfg<128, 64, 0, 7, 1, 16, 12, 4>;
-using W_u0T = WgradCfg<128, 64, 0, 7, 4, 16, 12, 2>;
-using W_u0s = WgradCfg<64, 64, 64, 7, 1, 16, 48>;
-using W_u1T = WgradCfg<64, 32, 0, 7, 4, 8, 48>;
-using W_u1s = WgradCfg<32, 32, 32, 7, 1, 8, 96>;
-using W_u2T = WgradCfg<32, 16, 0, 7, 4, 8, 96>;
-using W_u2s = WgradCfg<16, 16, 16, 7, 1, 8, 256>;
-using W_u3T = WgradCfg<16, 8, 0, 7, 4, 8, 256>;
-template <int BF> using W_u3s = WgradCfg<8, 8, 8, 7, 1, 8, BF ? W0TT : 256>;
 
+// Input gradients: conv(k7, same) -> conv with the flipped, transposed kernel; conv(k7, s4, left pad p) ->
+// ConvTranspose(k7, s4) of the same kernel, output shifted by -p; ConvTranspose(k7, s4) -> conv(k7, s4, no pad) of the
+// same kernel over the full-length gradient.
 // (No layer keeps the fp32 form for its matrix time any more: with two K-steps of fragments in flight up0.same and its input
 // gradient -- 57 k weights per 48-column tile, six bytes each as pieces instead of four -- were 1-7 us slower on the bf16
-// pipe; with six in flight they are even.  The trait stays for the next such case.)
-template <class Cfg> constexpr bool b16_loses = false;
+// pipe; with six in flight they are even.)
+// clang-format off
+template <int BF>
+using LayerTable = LayerList<
+    LayerCfg<0, INC, 0,       TC<BF, 3, 0, 8, 2, 8, 2, -3, 0, 1, 4, 8>,      void,                                          WgradCfg<8, 3, 0, 7, 1, 8, BF ? W0TT : 256>>,
+    LayerCfg<1, SAME, 0,      TC<BF, 8, 0, 8, 2, 8, 2, -3, 0, 1, 4, 8>,      TC<BF, 8, 0, 8, 2, 8, 2, -3, 0, 1, 4, 8>,      WgradCfg<8, 8, 0, 7, 1, 8, BF ? W0TT : 256>>,
+    LayerCfg<2, DOWN, 0,      TC<BF, 8, 0, 8, 2, 11, 8, -3, 0, 1, 4, 2>,     TC<BF, 8, 0, 8, 4, 2, 1, -1, -3, 2, 2, 4>,     WgradCfg<8, 8, 0, 7, 4, 8, 256>>,
+    LayerCfg<3, SAME, 1,      TC<BF, 8, 0, 16, 1, 7, 1, -3, 0, 1, 4, 4>,     TC<BF, 16, 0, 8, 2, 8, 2, -3, 0, 1, 4, 2>,     WgradCfg<16, 8, 0, 7, 1, 8, 256>>,
+    LayerCfg<4, DOWN, 1,      TC<BF, 16, 0, 16, 1, 7, 4, -2, 0, 1, 4, 1>,    TC<BF, 16, 0, 16, 4, 2, 1, -1, -2, 4, 1, 4>,   WgradCfg<16, 16, 0, 7, 4, 8, 96>>,
+    LayerCfg<5, SAME, 2,      TC<BF, 16, 0, 32, 1, 7, 1, -3, 0, 2, 2, 3>,    TC<BF, 32, 0, 16, 1, 7, 1, -3, 0, 1, 4, 3>,    WgradCfg<32, 16, 0, 7, 1, 8, 192>>,
+    LayerCfg<6, DOWN, 2,      TC<BF, 32, 0, 32, 1, 7, 4, -1, 0, 2, 2, 1>,    TC<BF, 32, 0, 32, 4, 2, 1, -1, -1, 4, 1, 3>,   WgradCfg<32, 32, 0, 7, 4, 4, 48>>,
+    LayerCfg<7, SAME, 3,      TC<BF, 32, 0, 64, 1, 7, 1, -3, 0, 4, 1, 3>,    TC<BF, 64, 0, 32, 1, 7, 1, -3, 0, 2, 2, 2>,    WgradCfg<64, 32, 0, 7, 1, 8, 48>>,
+    LayerCfg<8, DOWN, 3,      TC<BF, 64, 0, 64, 1, 7, 4, -2, 0, 4, 1, 1>,    TC<BF, 64, 0, 64, 4, 2, 1, -1, -2, 4, 1, 1>,   WgradCfg<64, 64, 0, 7, 4, 16, 12, 2>>,
+    LayerCfg<9, SAME, 4,      TC<BF, 64, 0, 128, 1, 7, 1, -3, 0, 4, 1, 1>,   TC<BF, 128, 0, 64, 1, 7, 1, -3, 0, 4, 1, 1>,   WgradCfg<128, 64, 0, 7, 1, 16, 12, 4>>,
+    LayerCfg<10, CONVT, 3,    TC<BF, 128, 0, 64, 4, 2, 1, -1, 0, 4, 1, 1>,   TC<BF, 64, 0, 128, 1, 7, 4, 0, 0, 4, 1, 1>,    WgradCfg<128, 64, 0, 7, 4, 16, 12, 2>>,
+    LayerCfg<11, UP_SAME, 3,  TC<BF, 64, 64, 64, 1, 7, 1, -3, 0, 4, 1, 3>,   TC<BF, 64, 0, 128, 1, 7, 1, -3, 0, 4, 1, 3>,   WgradCfg<64, 64, 64, 7, 1, 16, 48>>,
+    LayerCfg<12, CONVT, 2,    TC<BF, 64, 0, 32, 4, 2, 1, -1, 0, 4, 1, 3>,    TC<BF, 32, 0, 64, 1, 7, 4, 0, 0, 4, 1, 3>,     WgradCfg<64, 32, 0, 7, 4, 8, 48>>,
+    LayerCfg<13, UP_SAME, 2,  TC<BF, 32, 32, 32, 1, 7, 1, -3, 0, 2, 2, 3>,   TC<BF, 32, 0, 64, 1, 7, 1, -3, 0, 2, 2, 3>,    WgradCfg<32, 32, 32, 7, 1, 8, 96>>,
+    LayerCfg<14, CONVT, 1,    TC<BF, 32, 0, 16, 4, 2, 1, -1, 0, 4, 1, 4>,    TC<BF, 16, 0, 32, 1, 7, 4, 0, 0, 2, 2, 3>,     WgradCfg<32, 16, 0, 7, 4, 8, 96>>,
+    LayerCfg<15, UP_SAME, 1,  TC<BF, 16, 16, 16, 1, 7, 1, -3, 0, 1, 4, 4>,   TC<BF, 16, 0, 32, 1, 7, 1, -3, 0, 2, 2, 4>,    WgradCfg<16, 16, 16, 7, 1, 8, 256>>,
+    LayerCfg<16, CONVT, 0,    TC<BF, 16, 0, 8, 4, 2, 1, -1, 0, 2, 2, 4>,     TC<BF, 8, 0, 16, 1, 7, 4, 0, 0, 1, 4, 4>,      WgradCfg<16, 8, 0, 7, 4, 8, 256>>,
+    LayerCfg<17, UP_SAME, 0,  TC<BF, 8, 8, 8, 2, 8, 2, -3, 0, 1, 4, 8>,      TC<BF, 8, 0, 16, 1, 7, 1, -3, 0, 1, 4, 8>,     WgradCfg<8, 8, 8, 7, 1, 8, BF ? W0TT : 256>>>;
+// clang-format on
 
 struct ConvOp {
   bool used = false;
@@ -112,6 +114,8 @@ struct ConvOp {
 
 struct WgradOp {
   int (*launch)(const WgradArgs&, int, hipStream_t) = nullptr;
+  const void* kernel[2] = {nullptr, nullptr};  // wgrad_bf16_kernel for an even / odd tap offset, and its dynamic LDS
+  size_t lds_bytes = 0;
   int lo = -1, hi1 = -1, hi2 = -1;
   int Ln = 0, off = 0, TT = 0, WB = 1, out_n = 0;
   long grad_off = 0;
@@ -127,6 +131,8 @@ struct BnOp {
 };
 
 struct Layer {
+  Kind kind = INC;
+  int lv = 0;
   std::string name;
   ConvOp fwd, dgrad;
   BnOp bn;
@@ -134,18 +140,13 @@ struct Layer {
 };
 
 template <class Cfg>
-void set_conv(ConvOp* op, int src1, int src2, int dst, int cols, int l_out) {
+void set_conv(ConvOp* op) {
   op->used = true;
   op->g = Cfg::geom();
   op->launch = &launch_conv<Cfg>;
   op->kernel = reinterpret_cast<const void*>(&conv_mfma_kernel<Cfg>);
   op->lds_bytes = Cfg::LDS_FLOATS * sizeof(float);
-  op->src1 = src1;
-  op->src2 = src2;
-  op->dst = dst;
-  op->cols = cols;
-  op->l_out = l_out;
-  if constexpr (Cfg::BF16 && (Cfg::TAPS >= 7 || (Cfg::TAPS == 2 && Cfg::CB % 4 == 0)) && !b16_loses<Cfg>) {
+  if constexpr (Cfg::BF16 && (Cfg::TAPS >= 7 || (Cfg::TAPS == 2 && Cfg::CB % 4 == 0))) {
     op->launch_b16 = &launch_conv_b16<Cfg>;
     op->a3_n = ConvB16<Cfg>::A_UINT4;
     op->tn = Cfg::TN;
@@ -153,25 +154,61 @@ void set_conv(ConvOp* op, int src1, int src2, int dst, int cols, int l_out) {
   }
 }
 
-template <class Cfg, class T>
-void set_wgrad(WgradOp* op, int lo, int hi1, int hi2, int Ln, int off) {
+template <class Cfg, int BF>
+void set_wgrad(WgradOp* op) {
   // bf16 rows: exact products on the bf16 matrix cores (wgrad_bf16_kernel).  (Round 4 kept the four deepest layers -- >= 4096
   // channel pairs, <= 48 samples per row -- on the fp32-MFMA kernel: with 256 partial rows per tensor their cost was the
   // 115-230 KB every workgroup writes.  With the rows capped by bytes (wg_rows_cap: 64 workgroups for 57 k weights) the fp32
   // form is bound by its matrix time on those few CUs: up0.same 99-118 us against 51 here; the step itself does not move.)
-  if constexpr (sizeof(T) == 2) {
+  if constexpr (BF != 0) {
     op->launch = &launch_wgrad_bf16<Cfg>;
+    op->kernel[0] = reinterpret_cast<const void*>(&wgrad_bf16_kernel<Cfg, 0>);
+    op->kernel[1] = reinterpret_cast<const void*>(&wgrad_bf16_kernel<Cfg, 1>);
+    op->lds_bytes = (size_t)WgradB<Cfg>::LDS_ELEMS * 2;
   } else {
-    op->launch = &launch_wgrad<Cfg, T>;
+    op->launch = &launch_wgrad<Cfg>;
   }
-  op->lo = lo;
-  op->hi1 = hi1;
-  op->hi2 = hi2;
-  op->Ln = Ln;
-  op->off = off;
   op->TT = Cfg::TT;
   op->WB = Cfg::WB;
   op->out_n = Cfg::OUT;
+}
+
+// The launchers of a row, and the check that its Cfg types are those of a layer of this kind at this level: channels,
+// stride (SN = stride x P phases; a ConvTranspose as four phases of two taps) and, for the stride-4 conv, the padding.
+template <class R, int BF>
+void bind_layer(Layer* Ls) {
+  using F = typename R::F;
+  using G = typename R::G;
+  using W = typename R::W;
+  constexpr Kind K = R::KIND;
+  constexpr int LV = R::LV, COUT = layer_cout(K, LV), CIN = layer_cin(K, LV), STRIDE = K == DOWN ? 4 : 1;
+  static_assert(R::LI == layer_index(K, LV), "the row's index is not that of its kind and level");
+  static_assert(F::COUT == COUT && F::CIN == CIN && (K != UP_SAME || F::CIN1 == COUT), "forward conv: channels");
+  static_assert(K == CONVT ? F::P == 4 && F::TAPS == 2 && F::SN == 1 : F::SN == STRIDE * F::P, "forward conv: stride");
+  Layer& L = Ls[R::LI];
+  L.kind = K;
+  L.lv = LV;
+  set_conv<F>(&L.fwd);
+  if constexpr (K != INC) {
+    static_assert(G::CIN == COUT && G::COUT == CIN && G::CIN2 == 0, "input gradient: channels");
+    static_assert(K == DOWN    ? G::P == 4 && G::TAPS == 2 && G::SN == 1 && G::OUT_OFF == -PADL[LV < 4 ? LV : 0]
+                  : K == CONVT ? G::P == 1 && G::SN == 4
+                               : G::SN == G::P,
+                  "input gradient: stride");
+    set_conv<G>(&L.dgrad);
+  } else {
+    static_assert(std::is_void<G>::value, "the first layer has no input gradient");
+  }
+  // ConvTranspose: lo = layer input, hi = gz
+  static_assert(W::K == 7 && W::LO == (K == CONVT ? CIN : COUT) && W::HI == (K == CONVT ? COUT : CIN) && W::S == (K == CONVT ? 4 : STRIDE) &&
+                    (K == UP_SAME ? W::HI1 == COUT : W::HI2 == 0),
+                "weight gradient: channels, stride");
+  set_wgrad<W, BF>(&L.wg);
+}
+template <int BF, class... R>
+void bind_layers(LayerList<R...>, Layer* Ls) {
+  static_assert(sizeof...(R) == NLAYER && ((1u << R::LI) | ...) == (1u << NLAYER) - 1, "one row per layer");
+  (bind_layer<R, BF>(Ls), ...);
 }
 
 // dense (B, C, T) -> haloed rows
@@ -190,40 +227,79 @@ __global__ __launch_bounds__(256) void load_rows_bf16_kernel(const float* __rest
   }
 }
 
-}  // namespace
+// What differs between fp32 and bf16 rows outside the convs, chosen once with the plan (the convs' and weight gradients'
+// launchers come with the table's BF).  The BatchNorm passes come per crop of the ConvTranspose layers: 0, 1 or 2 samples.
+using BnKernel = void (*)(BnArgs);
+struct RowKernels {
+  void (*load_rows)(const float*, Rows, int, int) = nullptr;
+  int load_span = 0;  // samples per workgroup
+  BnKernel bn_stats = nullptr, bn_apply[3] = {}, bn_bwd_partial[3] = {}, bn_bwd_apply[3] = {};
+  void (*head)(HeadArgs2) = nullptr;
+  int head_span = 0;
+  void (*channel_sum)(Rows, int, int, int, double*) = nullptr;
+};
+template <class T>
+RowKernels row_kernels() {
+  RowKernels k;
+  if constexpr (sizeof(T) == 2) {
+    k.load_rows = load_rows_bf16_kernel, k.load_span = 512;
+    k.head = head_fwd_bwd_pair_kernel<bf16_t, 4>, k.head_span = 1024;
+  } else {
+    k.load_rows = load_rows_kernel, k.load_span = 256;
+    k.head = head_fwd_bwd_kernel, k.head_span = 256;
+  }
+  k.bn_stats = bnv_stats_partial_kernel<T>;
+  k.bn_apply[0] = bnv_apply_kernel<T, 0>, k.bn_apply[1] = bnv_apply_kernel<T, 1>, k.bn_apply[2] = bnv_apply_kernel<T, 2>;
+  k.bn_bwd_partial[0] = bnv_bwd_partial_kernel<T, 0>, k.bn_bwd_partial[1] = bnv_bwd_partial_kernel<T, 1>, k.bn_bwd_partial[2] = bnv_bwd_partial_kernel<T, 2>;
+  k.bn_bwd_apply[0] = bnv_bwd_apply_kernel<T, 0>, k.bn_bwd_apply[1] = bnv_bwd_apply_kernel<T, 1>, k.bn_bwd_apply[2] = bnv_bwd_apply_kernel<T, 2>;
+  k.channel_sum = channel_sum_partial_v_kernel<T>;
+  return k;
+}
 
-thread_local int g_launches = 0;  // kernel launches of the step being enqueued (vp_train_launch_count)
-#define TRL(...)                      \
-  do {                                \
-    ++g_launches;                     \
-    hipLaunchKernelGGL(__VA_ARGS__);  \
-  } while (0)
+// A device array that belongs to its holder: allocated (and zeroed where something reads it before a kernel has written it)
+// in one statement, freed with the holder.  (DevBuf of api.hip is the other thing: it regrows, may carry a pinned host
+// mirror, and is released by hand.)
+template <class T>
+struct DevArray {
+  T* p = nullptr;
+  DevArray() = default;
+  DevArray(const DevArray&) = delete;
+  DevArray& operator=(const DevArray&) = delete;
+  ~DevArray() {
+    if (p) (void)hipFree(p);
+  }
+  hipError_t alloc(size_t n, bool zero = false) {
+    const hipError_t e = hipMalloc((void**)&p, n * sizeof(T));
+    return e == hipSuccess && zero ? hipMemset(p, 0, n * sizeof(T)) : e;
+  }
+  operator T*() const { return p; }
+};
+
+}  // namespace
 
 struct Trainer {
   int device = 0, max_batch = 0;
-  int launches_last_step = 0;
+  int launches = 0;   // kernel launches of the step enqueued last (vp_train_launch_count)
   bool bf16 = false;  // activation / gradient rows stored as bfloat16 (weights, gradients, statistics, Adam: fp32)
   int esize = 4;      // bytes per row element
+  RowKernels rk;
   hipStream_t stream = nullptr;
   // The weight gradients run on a stream of their own: wgrad of layer L needs gz of L and the activations below it, nothing
   // downstream needs its result before the fold at the end of the step, and the backward chain (BatchNorm backward -> input
   // gradient -> next layer's BatchNorm backward) is a string of short launches that leave most of the chip idle in the deep
   // layers.  Events order the two: ev_gz[L] (gz of L complete) -> wgrad of L; ev_wg (all weight gradients) -> fold + Adam.
   hipStream_t stream_wg = nullptr;
-  hipEvent_t ev_gz[32] = {}, ev_wg = nullptr, ev_wg1 = nullptr;  // ev_wg1: every weight gradient but the first layer's
+  hipEvent_t ev_gz[NLAYER] = {}, ev_wg = nullptr, ev_wg1 = nullptr;  // ev_wg1: every weight gradient but the first layer's
   std::vector<Tensor> tensors;
   std::vector<Layer> layers;
   std::map<std::string, long> poff;  // parameter name -> offset in the flat blob
   std::map<std::string, size_t> psize;
   size_t n_params = 0;
   // device memory
-  float* arena = nullptr;   // activation / gradient tensors
-  float* w = nullptr;       // weights (flat blob, canonical order)
-  float* grad = nullptr;
-  float* adam_m = nullptr;
-  float* adam_v = nullptr;
-  float* mask = nullptr;
-  float* ema = nullptr;     // EMA of the weights (allocated by vp_train_set_ema)
+  DevArray<char> arena;  // activation / gradient tensors
+  DevArray<float> w;     // weights (flat blob, canonical order)
+  DevArray<float> grad, adam_m, adam_v, mask;
+  DevArray<float> ema;   // EMA of the weights (allocated by vp_train_set_ema)
   // behind the last reader of a step's x / y (the head kernel), a ring over the steps in flight:
   // vp_train_wait_inputs_consumed (the latest), vp_train_inputs_consumed_upto (which steps are past it)
   static constexpr int EV_RING = 8;
@@ -231,26 +307,23 @@ struct Trainer {
   long long ev_inputs_seq[EV_RING] = {-1, -1, -1, -1, -1, -1, -1, -1};
   long long seq = 0;  // steps enqueued so far
   float ema_decay = 0.f;
-  int* frag_idx = nullptr;
-  float* frag = nullptr;
+  DevArray<int> frag_idx;
+  DevArray<float> frag;
   size_t frag_n = 0;
-  float* zeros = nullptr;   // 256 zero floats (bias of bias-free convs)
-  float* stats = nullptr;
-  double* bn_partial = nullptr;
-  unsigned* bn_counter = nullptr;
-  float* conv_stat = nullptr;  // BatchNorm sums a forward bf16-MFMA conv leaves per workgroup (one layer at a time)
-  uint4* frag3 = nullptr;  // three-piece A operands of the bf16-MFMA convs, cut from `frag` every step
+  DevArray<float> zeros;  // 256 zero floats (bias of bias-free convs)
+  DevArray<float> stats;
+  DevArray<double> bn_partial;
+  DevArray<float> conv_stat;  // BatchNorm sums a forward bf16-MFMA conv leaves per workgroup (one layer at a time)
+  DevArray<uint4> frag3;      // three-piece A operands of the bf16-MFMA convs, cut from `frag` every step
   ConvB16PackJobs b16_jobs{};
   int b16_blocks = 0;
-  float* wg_partial = nullptr;
-  size_t wg_partial_floats = 0;
-  double* head_partial = nullptr;
-  double* head_sums = nullptr;  // [28] + loss at [28]
-  double* head_stage = nullptr; // [64][28]
-  float* x_dev = nullptr;       // staging for host inputs, and where vp_train_step_bank generates its batch
-  float* y_dev = nullptr;
-  RowRing plan_rows;            // vp_train_step_bank(_aug)'s rows: slot seq % EV_RING, free again at ev_inputs of that slot
-  float* p_dev = nullptr;       // predictions of the last step
+  DevArray<float> wg_partial;
+  DevArray<double> head_partial;
+  DevArray<double> head_sums;   // [28] + loss at [28]
+  DevArray<double> head_stage;  // [64][28]
+  DevArray<float> x_dev, y_dev;  // staging for host inputs, and where vp_train_step_bank generates its batch
+  RowRing plan_rows;             // vp_train_step_bank(_aug)'s rows: slot seq % EV_RING, free again at ev_inputs of that slot
+  DevArray<float> p_dev;         // predictions of the last step
   long step = 0;
   float beta1 = 0.9f, beta2 = 0.999f, adam_eps = 1e-8f, bn_eps = 1e-3f, bn_momentum = 0.1f, loss_eps = 1e-5f;
   int t_x = -1, t_ga_last = -1;
@@ -273,11 +346,7 @@ struct Trainer {
     const Tensor& t = tensors[id];  // (t.p is a byte address in disguise when the rows are bf16)
     return Rows{reinterpret_cast<float*>(reinterpret_cast<char*>(t.p) + (long)ch * t.ls * esize), t.ls, (long)t.win_stride()};
   }
-  ~Trainer() {
-    for (void* p : {(void*)arena, (void*)w, (void*)grad, (void*)adam_m, (void*)adam_v, (void*)mask, (void*)ema, (void*)frag_idx,
-                    (void*)frag, (void*)zeros, (void*)stats, (void*)bn_partial, (void*)bn_counter, (void*)frag3, (void*)conv_stat, (void*)wg_partial, (void*)head_partial,
-                    (void*)head_sums, (void*)head_stage, (void*)x_dev, (void*)y_dev, (void*)p_dev})
-      if (p) (void)hipFree(p);
+  ~Trainer() {  // (the device arrays free themselves)
     if (stream) (void)hipStreamDestroy(stream);
     if (stream_wg) (void)hipStreamDestroy(stream_wg);
     for (hipEvent_t e : ev_gz)
@@ -290,6 +359,13 @@ struct Trainer {
 };
 
 namespace {
+
+// a launch of the step: counted for vp_train_launch_count
+#define TRL(...)                     \
+  do {                               \
+    ++tr.launches;                   \
+    hipLaunchKernelGGL(__VA_ARGS__); \
+  } while (0)
 
 // index map of one conv's packed fragments: pack "weights" whose values are their own flat index + 1
 std::vector<int> to_index(const std::vector<float>& packed) {
@@ -317,9 +393,8 @@ void append_frag(Trainer& tr, ConvOp* op, const std::vector<float>& amat) {
   tr.frag_idx_host.insert(tr.frag_idx_host.end(), idx.begin(), idx.end());
 }
 
-template <int BF>
+// Everything of the plan that is not a Cfg type, from each layer's kind and level.
 int build_plan(Trainer& tr) {
-  using ET = typename std::conditional<BF != 0, bf16_t, float>::type;
   const ParamDesc* table;
   const int np = param_table(VP_MODEL_PHASENET, &table);
   long off = 0;
@@ -329,170 +404,114 @@ int build_plan(Trainer& tr) {
     off += (long)table[i].size;
   }
   tr.n_params = (size_t)off;
-  const int len[5] = {T0, T1, T2, T3, T4};
-  const int ch[5] = {8, 16, 32, 64, 128};
-  const int padl[4] = {3, 2, 1, 2};
   tr.layers.resize(NLAYER);
-  // layer order: 0 inc, 1+2i down{i}.same, 2+2i down{i}.down (i<4), 9 down4.same, 10+2j up{j}.convT, 11+2j up{j}.same
-  auto P = [&](const std::string& n) { return tr.poff.at(n); };
-  auto mk_bn = [&](Layer& L, const std::string& bn, int C, int Lz, int La, int crop) {
-    L.bn.C = C;
-    L.bn.Lz = Lz;
-    L.bn.La = La;
-    L.bn.crop = crop;
-    L.bn.gamma_off = P(bn + ".weight");
-    L.bn.beta_off = P(bn + ".bias");
-    L.bn.rm_off = P(bn + ".running_mean");
-    L.bn.rv_off = P(bn + ".running_var");
-    L.bn.z = tr.add_tensor(L.name + ".z", C, Lz);
-    L.bn.a = tr.add_tensor(L.name + ".a", C, La);
-    L.bn.gz = tr.add_tensor(L.name + ".gz", C, Lz);
-  };
-  tr.t_x = tr.add_tensor("x", 3, T0);
   Layer* Ls = tr.layers.data();
-  Ls[0].name = "inc";
-  mk_bn(Ls[0], "in_bn", 8, T0, T0, 0);
-  for (int i = 0; i < 5; ++i) {
-    Layer& S = Ls[i < 4 ? 1 + 2 * i : 9];
-    S.name = "down" + std::to_string(i) + ".same";
-    mk_bn(S, "down_branch." + std::to_string(i) + ".1", ch[i], len[i], len[i], 0);
-    if (i < 4) {
-      Layer& D = Ls[2 + 2 * i];
-      D.name = "down" + std::to_string(i) + ".down";
-      mk_bn(D, "down_branch." + std::to_string(i) + ".3", ch[i], len[i + 1], len[i + 1], 0);
+  if (tr.bf16) {  // the one place the row type is asked for
+    bind_layers<1>(LayerTable<1>{}, Ls);
+    tr.rk = row_kernels<bf16_t>();
+  } else {
+    bind_layers<0>(LayerTable<0>{}, Ls);
+    tr.rk = row_kernels<float>();
+  }
+  auto P = [&](const std::string& n) { return tr.poff.at(n); };
+
+  // ---- names, BatchNorm, the tensors z, a, gz ---------------------------------------------
+  std::string conv_name[NLAYER];  // the conv's parameters: inc, down_branch.<i>.0 / .2, up_branch.<j>.0 / .2 (its BatchNorm: .1 / .3)
+  tr.t_x = tr.add_tensor("x", 3, T0);
+  for (int li = 0; li < NLAYER; ++li) {
+    Layer& L = Ls[li];
+    const int lv = L.lv;
+    const bool up = L.kind == CONVT || L.kind == UP_SAME, second = L.kind == DOWN || L.kind == UP_SAME;
+    const std::string n = std::to_string(up ? 3 - lv : lv), branch = std::string(up ? "up" : "down") + "_branch." + n;
+    L.name = L.kind == INC ? "inc" : (up ? "up" : "down") + n + (L.kind == DOWN ? ".down" : L.kind == CONVT ? ".convT" : ".same");
+    conv_name[li] = L.kind == INC ? "inc" : branch + (second ? ".2" : ".0");
+    const std::string bn = L.kind == INC ? "in_bn" : branch + (second ? ".3" : ".1");
+    BnOp& b = L.bn;
+    b.C = layer_cout(L.kind, lv);
+    b.La = LEN[L.kind == DOWN ? lv + 1 : lv];                   // what the next layer reads
+    b.Lz = L.kind == CONVT ? 4 * LEN[lv + 1] + 3 : b.La;          // (a ConvTranspose output stays at full length)
+    b.crop = L.kind == CONVT ? 1 + ((b.Lz - 3) - b.La) / 2 : 0;  // x[:, :, 1:-2] then the centre crop to the skip length
+    b.gamma_off = P(bn + ".weight");
+    b.beta_off = P(bn + ".bias");
+    b.rm_off = P(bn + ".running_mean");
+    b.rv_off = P(bn + ".running_var");
+    b.z = tr.add_tensor(L.name + ".z", b.C, b.Lz);
+    b.a = tr.add_tensor(L.name + ".a", b.C, b.La);
+    b.gz = tr.add_tensor(L.name + ".gz", b.C, b.Lz);
+  }
+  // ---- gradient-of-activation tensors -------------------------------------------------------
+  int gcat[4], gskip[4];  // by level
+  for (int lv = 3; lv >= 0; --lv) {
+    gcat[lv] = tr.add_tensor("up" + std::to_string(3 - lv) + ".gcat", 2 * CH[lv], LEN[lv]);  // d(concat(skip, up)) of the up path's conv at lv
+    gskip[lv] = tr.add_tensor("down" + std::to_string(lv) + ".gskip", CH[lv], LEN[lv]);      // from down{lv}.down
+  }
+  for (Layer& L : tr.layers) {
+    BnOp& b = L.bn;
+    if (L.kind == SAME && L.lv < 4) {  // skips: from the up path (first half of gcat) + from the strided conv below
+      b.ga1 = gcat[L.lv];
+      b.ga2 = gskip[L.lv];
+    } else if (L.kind == CONVT) {  // convT outputs: second half of gcat
+      b.ga1 = gcat[L.lv];
+      b.ga1_ch = CH[L.lv];
+    } else {  // a single producer: the input gradient of the next layer, or the head for the last
+      b.ga1 = tr.add_tensor(L.name + ".ga", b.C, b.La);
     }
   }
-  for (int j = 0; j < 4; ++j) {
-    const int lv = 3 - j;  // output level
-    Layer& U = Ls[10 + 2 * j];
-    U.name = "up" + std::to_string(j) + ".convT";
-    const int lfull = 4 * len[lv + 1] + 3;
-    const int crop = 1 + ((lfull - 3) - len[lv]) / 2;  // x[:, :, 1:-2] then the centre crop to the skip length
-    mk_bn(U, "up_branch." + std::to_string(j) + ".1", ch[lv], lfull, len[lv], crop);
-    Layer& S = Ls[11 + 2 * j];
-    S.name = "up" + std::to_string(j) + ".same";
-    mk_bn(S, "up_branch." + std::to_string(j) + ".3", ch[lv], len[lv], len[lv], 0);
-  }
-  // gradient-of-activation tensors
-  int ga[NLAYER];       // plain ga tensors (single producer)
-  int gcat[4], gskip[4];
-  for (int i = 0; i < NLAYER; ++i) ga[i] = -1;
-  for (int j = 0; j < 4; ++j) {
-    const int lv = 3 - j;
-    gcat[j] = tr.add_tensor("up" + std::to_string(j) + ".gcat", 2 * ch[lv], len[lv]);   // d(concat(skip, up)) of up{j}.same
-    gskip[lv] = tr.add_tensor("down" + std::to_string(lv) + ".gskip", ch[lv], len[lv]);  // from down{lv}.down
-  }
-  auto mk_ga = [&](int li) {
-    ga[li] = tr.add_tensor(Ls[li].name + ".ga", Ls[li].bn.C, Ls[li].bn.La);
-    Ls[li].bn.ga1 = ga[li];
-  };
-  mk_ga(0);                                    // inc        <- dgrad of down0.same
-  for (int i = 0; i < 4; ++i) mk_ga(2 + 2 * i);  // down{i}.down <- dgrad of down{i+1}.same
-  mk_ga(9);                                    // down4.same <- dgrad of up0.convT
-  for (int j = 0; j < 4; ++j) mk_ga(11 + 2 * j);  // up{j}.same <- dgrad of up{j+1}.convT, or the head for j = 3
-  tr.t_ga_last = ga[17];
-  for (int i = 0; i < 4; ++i) {  // skips: from the up path (first half of gcat) + from the strided conv below
-    BnOp& b = Ls[1 + 2 * i].bn;
-    b.ga1 = gcat[3 - i];
-    b.ga1_ch = 0;
-    b.ga2 = gskip[i];
-  }
-  for (int j = 0; j < 4; ++j) {  // convT outputs: second half of gcat
-    BnOp& b = Ls[10 + 2 * j].bn;
-    b.ga1 = gcat[j];
-    b.ga1_ch = ch[3 - j];
-  }
+  tr.t_ga_last = Ls[NLAYER - 1].bn.ga1;
 
-  // ---- convolutions: forward, input gradient, weight gradient ------------------------------
-  auto W = [&](const std::string& n) { return index_weights(P(n), tr.psize.at(n)); };
-#define FWD_CONV(LI, CFG, WNAME, COUT, CIN, STRIDE, SRC1, SRC2, COLS)                                        \
-  set_conv<CFG<BF>>(&Ls[LI].fwd, SRC1, SRC2, Ls[LI].bn.z, COLS, Ls[LI].bn.Lz);                                    \
-  append_frag(tr, &Ls[LI].fwd, amat_conv(W(WNAME).data(), COUT, CIN, 7, STRIDE, CFG<BF>::P, CFG<BF>::CINP, nullptr));
-#define FWD_CONVT(LI, CFG, WNAME, CIN, COUT, SRC, LIN)                                                       \
-  set_conv<CFG<BF>>(&Ls[LI].fwd, SRC, -1, Ls[LI].bn.z, (LIN) + 1, Ls[LI].bn.Lz);                                  \
-  append_frag(tr, &Ls[LI].fwd, amat_convT_k7s4(W(WNAME).data(), CIN, COUT, CFG<BF>::CINP, nullptr));
-  // dgrad of a stride-1 conv W[COUT][CIN][7]: conv of gz (COUT channels) with the flipped transpose -> CIN channels
-#define BWD_SAME(LI, CFG, WNAME, COUT, CIN, DST, LDST)                                                       \
-  set_conv<CFG<BF>>(&Ls[LI].dgrad, Ls[LI].bn.gz, -1, DST, ((LDST) + CFG<BF>::P - 1) / CFG<BF>::P, LDST);                  \
-  append_frag(tr, &Ls[LI].dgrad,                                                                             \
-              amat_conv(flip_transpose(W(WNAME), COUT, CIN, 7).data(), CIN, COUT, 7, 1, CFG<BF>::P, CFG<BF>::CINP, nullptr));
-  // dgrad of a stride-4 conv W[C][C][7] with left pad PADL: transposed conv of gz, output index shifted by -PADL
-#define BWD_DOWN(LI, CFG, WNAME, C, DST, LDST, PADL)                                                         \
-  set_conv<CFG<BF>>(&Ls[LI].dgrad, Ls[LI].bn.gz, -1, DST, ((LDST)-1 + (PADL)) / 4 + 1, LDST);                     \
-  append_frag(tr, &Ls[LI].dgrad, amat_convT_k7s4(W(WNAME).data(), C, C, CFG<BF>::CINP, nullptr));
-  // dgrad of ConvTranspose Wt[CIN][COUT][7]: stride-4 conv of the full-length gz (COUT channels) -> CIN channels
-#define BWD_UPT(LI, CFG, WNAME, CIN, COUT, DST, LIN)                                                         \
-  set_conv<CFG<BF>>(&Ls[LI].dgrad, Ls[LI].bn.gz, -1, DST, LIN, LIN);                                              \
-  append_frag(tr, &Ls[LI].dgrad, amat_conv(W(WNAME).data(), CIN, COUT, 7, 4, 1, CFG<BF>::CINP, nullptr));
-
-  const int x = tr.t_x;
-  auto A = [&](int li) { return Ls[li].bn.a; };
-  FWD_CONV(0, F_inc, "inc.weight", 8, 3, 1, x, -1, (T0 + 1) / 2)
-  Ls[0].fwd.bias_off = P("inc.bias");
-  FWD_CONV(1, F_d0s, "down_branch.0.0.weight", 8, 8, 1, A(0), -1, (T0 + 1) / 2)
-  FWD_CONV(2, F_d0d, "down_branch.0.2.weight", 8, 8, 4, A(1), -1, (T1 + 1) / 2)
-  FWD_CONV(3, F_d1s, "down_branch.1.0.weight", 16, 8, 1, A(2), -1, T1)
-  FWD_CONV(4, F_d1d, "down_branch.1.2.weight", 16, 16, 4, A(3), -1, T2)
-  FWD_CONV(5, F_d2s, "down_branch.2.0.weight", 32, 16, 1, A(4), -1, T2)
-  FWD_CONV(6, F_d2d, "down_branch.2.2.weight", 32, 32, 4, A(5), -1, T3)
-  FWD_CONV(7, F_d3s, "down_branch.3.0.weight", 64, 32, 1, A(6), -1, T3)
-  FWD_CONV(8, F_d3d, "down_branch.3.2.weight", 64, 64, 4, A(7), -1, T4)
-  FWD_CONV(9, F_d4s, "down_branch.4.0.weight", 128, 64, 1, A(8), -1, T4)
-  FWD_CONVT(10, F_u0T, "up_branch.0.0.weight", 128, 64, A(9), T4)
-  FWD_CONV(11, F_u0s, "up_branch.0.2.weight", 64, 128, 1, A(7), A(10), T3)
-  FWD_CONVT(12, F_u1T, "up_branch.1.0.weight", 64, 32, A(11), T3)
-  FWD_CONV(13, F_u1s, "up_branch.1.2.weight", 32, 64, 1, A(5), A(12), T2)
-  FWD_CONVT(14, F_u2T, "up_branch.2.0.weight", 32, 16, A(13), T2)
-  FWD_CONV(15, F_u2s, "up_branch.2.2.weight", 16, 32, 1, A(3), A(14), T1)
-  FWD_CONVT(16, F_u3T, "up_branch.3.0.weight", 16, 8, A(15), T1)
-  FWD_CONV(17, F_u3s, "up_branch.3.2.weight", 8, 16, 1, A(1), A(16), (T0 + 1) / 2)
-
-  BWD_SAME(1, G_d0s, "down_branch.0.0.weight", 8, 8, ga[0], T0)
-  BWD_SAME(3, G_d1s, "down_branch.1.0.weight", 16, 8, ga[2], T1)
-  BWD_SAME(5, G_d2s, "down_branch.2.0.weight", 32, 16, ga[4], T2)
-  BWD_SAME(7, G_d3s, "down_branch.3.0.weight", 64, 32, ga[6], T3)
-  BWD_SAME(9, G_d4s, "down_branch.4.0.weight", 128, 64, ga[8], T4)
-  BWD_SAME(11, G_u0s, "up_branch.0.2.weight", 64, 128, gcat[0], T3)
-  BWD_SAME(13, G_u1s, "up_branch.1.2.weight", 32, 64, gcat[1], T2)
-  BWD_SAME(15, G_u2s, "up_branch.2.2.weight", 16, 32, gcat[2], T1)
-  BWD_SAME(17, G_u3s, "up_branch.3.2.weight", 8, 16, gcat[3], T0)
-  BWD_DOWN(2, G_d0d, "down_branch.0.2.weight", 8, gskip[0], T0, padl[0])
-  BWD_DOWN(4, G_d1d, "down_branch.1.2.weight", 16, gskip[1], T1, padl[1])
-  BWD_DOWN(6, G_d2d, "down_branch.2.2.weight", 32, gskip[2], T2, padl[2])
-  BWD_DOWN(8, G_d3d, "down_branch.3.2.weight", 64, gskip[3], T3, padl[3])
-  BWD_UPT(10, G_u0T, "up_branch.0.0.weight", 128, 64, ga[9], T4)
-  BWD_UPT(12, G_u1T, "up_branch.1.0.weight", 64, 32, ga[11], T3)
-  BWD_UPT(14, G_u2T, "up_branch.2.0.weight", 32, 16, ga[13], T2)
-  BWD_UPT(16, G_u3T, "up_branch.3.0.weight", 16, 8, ga[15], T1)
-#undef FWD_CONV
-#undef FWD_CONVT
-#undef BWD_SAME
-#undef BWD_DOWN
-#undef BWD_UPT
-
-  auto GZ = [&](int li) { return Ls[li].bn.gz; };
-#define WG(LI, CFG, WNAME, LO, HI1, HI2, LN, OFF)            \
-  set_wgrad<CFG, ET>(&Ls[LI].wg, LO, HI1, HI2, LN, OFF);          \
-  Ls[LI].wg.grad_off = P(WNAME);
-  WG(0, W_inc<BF>, "inc.weight", GZ(0), x, -1, T0, -3)
-  WG(1, W_d0s<BF>, "down_branch.0.0.weight", GZ(1), A(0), -1, T0, -3)
-  WG(2, W_d0d, "down_branch.0.2.weight", GZ(2), A(1), -1, T1, -padl[0])
-  WG(3, W_d1s, "down_branch.1.0.weight", GZ(3), A(2), -1, T1, -3)
-  WG(4, W_d1d, "down_branch.1.2.weight", GZ(4), A(3), -1, T2, -padl[1])
-  WG(5, W_d2s, "down_branch.2.0.weight", GZ(5), A(4), -1, T2, -3)
-  WG(6, W_d2d, "down_branch.2.2.weight", GZ(6), A(5), -1, T3, -padl[2])
-  WG(7, W_d3s, "down_branch.3.0.weight", GZ(7), A(6), -1, T3, -3)
-  WG(8, W_d3d, "down_branch.3.2.weight", GZ(8), A(7), -1, T4, -padl[3])
-  WG(9, W_d4s, "down_branch.4.0.weight", GZ(9), A(8), -1, T4, -3)
-  WG(10, W_u0T, "up_branch.0.0.weight", A(9), GZ(10), -1, T4, 0)   // ConvTranspose: lo = layer input, hi = gz
-  WG(11, W_u0s, "up_branch.0.2.weight", GZ(11), A(7), A(10), T3, -3)
-  WG(12, W_u1T, "up_branch.1.0.weight", A(11), GZ(12), -1, T3, 0)
-  WG(13, W_u1s, "up_branch.1.2.weight", GZ(13), A(5), A(12), T2, -3)
-  WG(14, W_u2T, "up_branch.2.0.weight", A(13), GZ(14), -1, T2, 0)
-  WG(15, W_u2s, "up_branch.2.2.weight", GZ(15), A(3), A(14), T1, -3)
-  WG(16, W_u3T, "up_branch.3.0.weight", A(15), GZ(16), -1, T1, 0)
-  WG(17, W_u3s<BF>, "up_branch.3.2.weight", GZ(17), A(1), A(16), T0, -3)
-#undef WG
+  // ---- convolutions: forward, weight gradient, input gradient -------------------------------
+  auto W = [&](int li) { return index_weights(P(conv_name[li] + ".weight"), tr.psize.at(conv_name[li] + ".weight")); };
+  auto cols_of = [](const ConvOp& op) { return (op.l_out + op.g.P - 1) / op.g.P; };
+  for (int li = 0; li < NLAYER; ++li) {
+    Layer& L = Ls[li];
+    const Kind k = L.kind;
+    const int lv = L.lv, cin = layer_cin(k, lv), cout = layer_cout(k, lv);
+    const int below = li ? Ls[li - 1].bn.a : tr.t_x;
+    ConvOp& f = L.fwd;
+    f.src1 = k == UP_SAME ? Ls[layer_index(SAME, lv)].bn.a : below;  // concat(skip, up)
+    f.src2 = k == UP_SAME ? below : -1;
+    f.dst = L.bn.z;
+    f.l_out = L.bn.Lz;
+    f.cols = cols_of(f);
+    append_frag(tr, &f, k == CONVT ? amat_convT_k7s4(W(li).data(), cin, cout, f.g.cinp(), nullptr)
+                                   : amat_conv(W(li).data(), cout, cin, 7, k == DOWN ? 4 : 1, f.g.P, f.g.cinp(), nullptr));
+    if (k == INC) f.bias_off = P("inc.bias");
+    WgradOp& g = L.wg;
+    g.grad_off = P(conv_name[li] + ".weight");
+    if (k == CONVT) {  // ConvTranspose: lo = layer input, hi = gz
+      g.lo = f.src1, g.hi1 = L.bn.gz, g.Ln = LEN[lv + 1], g.off = 0;
+    } else {
+      g.lo = L.bn.gz, g.hi1 = f.src1, g.hi2 = f.src2, g.Ln = L.bn.Lz, g.off = k == DOWN ? -PADL[lv] : -3;
+    }
+  }
+  // (fragments in the order they have always had: stride-1, stride-4, ConvTranspose)
+  for (Kind pass : {SAME, DOWN, CONVT})
+    for (int li = 1; li < NLAYER; ++li) {
+      Layer& L = Ls[li];
+      const Kind k = L.kind;
+      if ((k == UP_SAME ? SAME : k) != pass) continue;
+      const int lv = L.lv, cin = layer_cin(k, lv), cout = layer_cout(k, lv);
+      ConvOp& d = L.dgrad;
+      d.src1 = L.bn.gz;
+      if (k == DOWN) {
+        // dgrad of a stride-4 conv W[C][C][7] with left pad PADL: transposed conv of gz, output index shifted by -PADL
+        d.dst = gskip[lv];
+        d.l_out = LEN[lv];
+        d.cols = (d.l_out - 1 + PADL[lv]) / 4 + 1;
+        append_frag(tr, &d, amat_convT_k7s4(W(li).data(), cout, cout, d.g.cinp(), nullptr));
+      } else if (k == CONVT) {
+        // dgrad of ConvTranspose Wt[CIN][COUT][7]: stride-4 conv of the full-length gz (COUT channels) -> CIN channels
+        d.dst = Ls[li - 1].bn.ga1;
+        d.l_out = d.cols = LEN[lv + 1];
+        append_frag(tr, &d, amat_conv(W(li).data(), cin, cout, 7, 4, 1, d.g.cinp(), nullptr));
+      } else {
+        // dgrad of a stride-1 conv W[COUT][CIN][7]: conv of gz (COUT channels) with the flipped transpose -> CIN channels
+        d.dst = k == UP_SAME ? gcat[lv] : Ls[li - 1].bn.ga1;
+        d.l_out = LEN[lv];
+        d.cols = cols_of(d);
+        append_frag(tr, &d, amat_conv(flip_transpose(W(li), cout, cin, 7).data(), cin, cout, 7, 1, d.g.P, d.g.cinp(), nullptr));
+      }
+    }
 
   for (Layer& L : tr.layers)
     for (ConvOp* op : {&L.fwd, &L.dgrad})
@@ -508,14 +527,16 @@ int build_plan(Trainer& tr) {
   return VP_OK;
 }
 
-#define TR_HIP(call)                                                                              \
-  do {                                                                                            \
-    hipError_t e_ = (call);                                                                       \
-    if (e_ != hipSuccess) {                                                                       \
-      set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__);       \
-      return VP_ERR_HIP;                                                                          \
-    }                                                                                             \
-  } while (0)
+// Partial results of a weight gradient: one row of out_n floats per workgroup, folded by sum_rows_multi_kernel.  With 256
+// rows for every tensor of > 10 k weights the rows were 267 MB per step -- written by the weight-gradient launches, read
+// again by the fold (68 us, on the step's critical path) -- for 1.1 MB of gradients: the rows are capped by their bytes.
+int wg_rows_cap(int out_n) {
+  constexpr long budget = 1L << 22;  // same-box sweep: 1.64 ms per step unbounded, 1.60 at 8 M floats, 1.57 at 4-6 M, 1.60 at 2-3 M
+                                     // (below that the deep layers' launches have too few workgroups and end behind the main chain)
+  int cap = out_n > 10000 ? 256 : 512;
+  while (cap > 32 && (long)cap * out_n > budget) cap >>= 1;
+  return cap;
+}
 
 int upload(Trainer& tr, const float* weights) {
   const int B = tr.max_batch;
@@ -528,16 +549,11 @@ int upload(Trainer& tr, const float* weights) {
     total += (size_t)t.C * t.ls * B;
     total = (total + 63) / 64 * 64;
   }
-  TR_HIP(hipMalloc(&tr.arena, total * tr.esize));
-  TR_HIP(hipMemset(tr.arena, 0, total * tr.esize));  // (a zero of either type)
-  for (size_t i = 0; i < tr.tensors.size(); ++i)
-    tr.tensors[i].p = reinterpret_cast<float*>(reinterpret_cast<char*>(tr.arena) + toff[i] * tr.esize);
+  VP_HIP(tr.arena.alloc(total * tr.esize, true));  // (a zero of either type)
+  for (size_t i = 0; i < tr.tensors.size(); ++i) tr.tensors[i].p = reinterpret_cast<float*>(tr.arena.p + toff[i] * tr.esize);
   const size_t np = tr.n_params;
-  for (float** p : {&tr.w, &tr.grad, &tr.adam_m, &tr.adam_v, &tr.mask}) {
-    TR_HIP(hipMalloc(p, np * sizeof(float)));
-    TR_HIP(hipMemset(*p, 0, np * sizeof(float)));
-  }
-  TR_HIP(hipMemcpy(tr.w, weights, np * sizeof(float), hipMemcpyHostToDevice));
+  for (DevArray<float>* a : {&tr.w, &tr.grad, &tr.adam_m, &tr.adam_v, &tr.mask}) VP_HIP(a->alloc(np, true));
+  VP_HIP(hipMemcpy(tr.w, weights, np * sizeof(float), hipMemcpyHostToDevice));
   std::vector<float> mask(np, 1.f);
   for (auto& kv : tr.poff) {
     const std::string& n = kv.first;
@@ -545,11 +561,11 @@ int upload(Trainer& tr, const float* weights) {
     if (running)
       for (size_t i = 0; i < tr.psize[n]; ++i) mask[kv.second + i] = 0.f;
   }
-  TR_HIP(hipMemcpy(tr.mask, mask.data(), np * sizeof(float), hipMemcpyHostToDevice));
+  VP_HIP(hipMemcpy(tr.mask, mask.data(), np * sizeof(float), hipMemcpyHostToDevice));
   tr.frag_n = tr.frag_idx_host.size();
-  TR_HIP(hipMalloc(&tr.frag_idx, tr.frag_n * sizeof(int)));
-  TR_HIP(hipMemcpy(tr.frag_idx, tr.frag_idx_host.data(), tr.frag_n * sizeof(int), hipMemcpyHostToDevice));
-  TR_HIP(hipMalloc(&tr.frag, tr.frag_n * sizeof(float)));
+  VP_HIP(tr.frag_idx.alloc(tr.frag_n));
+  VP_HIP(hipMemcpy(tr.frag_idx, tr.frag_idx_host.data(), tr.frag_n * sizeof(int), hipMemcpyHostToDevice));
+  VP_HIP(tr.frag.alloc(tr.frag_n));
   {  // the bf16-MFMA convs' operands
     size_t n3 = 0;
     for (Layer& L : tr.layers)
@@ -565,8 +581,8 @@ int upload(Trainer& tr, const float* weights) {
           const size_t need = (size_t)L.fwd.cout * ((L.fwd.cols + L.fwd.tn - 1) / L.fwd.tn) * tr.max_batch * 2;
           if (need > ns2) ns2 = need;
         }
-      if (ns2) TR_HIP(hipMalloc(&tr.conv_stat, ns2 * sizeof(float)));
-      TR_HIP(hipMalloc(&tr.frag3, n3 * sizeof(uint4)));
+      if (ns2) VP_HIP(tr.conv_stat.alloc(ns2));
+      VP_HIP(tr.frag3.alloc(n3));
       for (Layer& L : tr.layers)
         for (ConvOp* op : {&L.fwd, &L.dgrad})
           if (op->used && op->launch_b16) {
@@ -585,63 +601,67 @@ int upload(Trainer& tr, const float* weights) {
           }
     }
   }
-  TR_HIP(hipMalloc(&tr.zeros, 256 * sizeof(float)));
-  TR_HIP(hipMemset(tr.zeros, 0, 256 * sizeof(float)));
+  VP_HIP(tr.zeros.alloc(256, true));
   size_t ns = 0;
   for (Layer& L : tr.layers) ns += 4 * (size_t)L.bn.C;
-  TR_HIP(hipMalloc(&tr.stats, ns * sizeof(float)));
-  TR_HIP(hipMemset(tr.stats, 0, ns * sizeof(float)));
-  TR_HIP(hipMalloc(&tr.bn_partial, (size_t)128 * 256 * 2 * sizeof(double)));
-  TR_HIP(hipMalloc(&tr.bn_counter, 128 * sizeof(unsigned)));
-  TR_HIP(hipMemset(tr.bn_counter, 0, 128 * sizeof(unsigned)));
+  VP_HIP(tr.stats.alloc(ns, true));
+  VP_HIP(tr.bn_partial.alloc((size_t)128 * 256 * 2));
   size_t wtot = 0;
   for (Layer& L : tr.layers) {
     L.wg.partial_off = wtot;
     wtot += (size_t)wg_rows_cap(L.wg.out_n) * (size_t)L.wg.out_n;  // what the launches can reach (512 rows each was 550 MB)
   }
-  tr.wg_partial_floats = wtot;
-  TR_HIP(hipMalloc(&tr.wg_partial, wtot * sizeof(float)));
-  const size_t hb = (size_t)((T0 + 255) / 256) * B;
-  TR_HIP(hipMalloc(&tr.head_partial, hb * 28 * sizeof(double)));
-  TR_HIP(hipMalloc(&tr.head_sums, 32 * sizeof(double)));
-  TR_HIP(hipMemset(tr.head_sums, 0, 32 * sizeof(double)));
-  TR_HIP(hipMalloc(&tr.head_stage, 64 * 28 * sizeof(double)));
-  const size_t dense = (size_t)B * 3 * T0;
-  TR_HIP(hipMalloc(&tr.x_dev, dense * sizeof(float)));
-  TR_HIP(hipMalloc(&tr.y_dev, dense * sizeof(float)));
-  TR_HIP(hipMalloc(&tr.p_dev, dense * sizeof(float)));
-  for (Layer& L : tr.layers)
+  VP_HIP(tr.wg_partial.alloc(wtot));
+  VP_HIP(tr.head_partial.alloc((size_t)((T0 + 255) / 256) * B * 28));
+  VP_HIP(tr.head_sums.alloc(32, true));
+  VP_HIP(tr.head_stage.alloc(64 * 28));
+  for (DevArray<float>* a : {&tr.x_dev, &tr.y_dev, &tr.p_dev}) VP_HIP(a->alloc((size_t)B * 3 * T0));
+  for (Layer& L : tr.layers) {  // dynamic LDS beyond the default, for this trainer's device
     for (ConvOp* op : {&L.fwd, &L.dgrad})
       if (op->used && op->lds_bytes > 48 * 1024)
-        TR_HIP(hipFuncSetAttribute(op->kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)op->lds_bytes));
+        VP_HIP(hipFuncSetAttribute(op->kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)op->lds_bytes));
+    for (const void* k : L.wg.kernel)
+      if (k) VP_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.wg.lds_bytes));
+  }
   // Non-blocking: a blocking stream synchronises implicitly with the legacy default stream, so every event a binder
   // records there for the step's inputs (volpick_amd/train.py: torch's current stream) serialised the step against its
   // predecessor on the device -- 2.75 instead of 1.72 ms per 512-window step (tools/train_probe.py).  The uploads above ran
   // on the default stream: they are complete before the first step can be enqueued.
-  TR_HIP(hipDeviceSynchronize());
+  VP_HIP(hipDeviceSynchronize());
   // The weight gradients' stream gets the LOWEST priority, the main chain the default one: streams of different priority
   // never share a hardware queue (two default-priority streams created after other streams of the process had been
   // destroyed did: the step ran 1.96 instead of 1.56 ms, its two chains serialised -- tools/train_after_forward_probe.py),
   // and where both have workgroups waiting the chain the step's length hangs on goes first.
   {
     int pr_least = 0, pr_greatest = 0;
-    TR_HIP(hipDeviceGetStreamPriorityRange(&pr_least, &pr_greatest));
-    TR_HIP(hipStreamCreateWithFlags(&tr.stream, hipStreamNonBlocking));
-    TR_HIP(hipStreamCreateWithPriority(&tr.stream_wg, hipStreamNonBlocking, pr_least));  // (main chain at the highest: the same)
+    VP_HIP(hipDeviceGetStreamPriorityRange(&pr_least, &pr_greatest));
+    VP_HIP(hipStreamCreateWithFlags(&tr.stream, hipStreamNonBlocking));
+    VP_HIP(hipStreamCreateWithPriority(&tr.stream_wg, hipStreamNonBlocking, pr_least));  // (main chain at the highest: the same)
   }
   // consumed by another stream of this device only: a device-scope release at the event is enough (the default release
   // to the system writes the L2 back: ~5 us in front of the stream's next launch, once per layer)
   const unsigned ev_dev = hipEventDisableTiming | hipEventReleaseToDevice;
-  for (int i = 0; i < NLAYER; ++i) TR_HIP(hipEventCreateWithFlags(&tr.ev_gz[i], ev_dev));
-  TR_HIP(hipEventCreateWithFlags(&tr.ev_wg, ev_dev));
-  TR_HIP(hipEventCreateWithFlags(&tr.ev_wg1, ev_dev));
-  for (hipEvent_t& e : tr.ev_inputs) TR_HIP(hipEventCreateWithFlags(&e, ev_dev));
+  for (hipEvent_t& e : tr.ev_gz) VP_HIP(hipEventCreateWithFlags(&e, ev_dev));
+  VP_HIP(hipEventCreateWithFlags(&tr.ev_wg, ev_dev));
+  VP_HIP(hipEventCreateWithFlags(&tr.ev_wg1, ev_dev));
+  for (hipEvent_t& e : tr.ev_inputs) VP_HIP(hipEventCreateWithFlags(&e, ev_dev));
   return VP_OK;
+}
+
+// The A/B switches of the bf16-MFMA convs, read once per process: VP_CONV_B16=0 = the fp32-MFMA convs, VP_CONV_STAT=0 =
+// separate statistics launches.
+struct ConvSwitches {
+  bool b16, stat;
+};
+const ConvSwitches& conv_switches() {
+  static const auto on = [](const char* name) { return !getenv(name) || atoi(getenv(name)) != 0; };
+  static const ConvSwitches s{on("VP_CONV_B16"), on("VP_CONV_STAT")};
+  return s;
 }
 
 // Returns the number of per-workgroup BatchNorm sums the launch left in tr.conv_stat (want_stat, bf16-MFMA form), else 0.
 int run_conv(Trainer& tr, const ConvOp& op, int B, bool want_stat = false) {
-  ++g_launches;
+  ++tr.launches;
   ConvArgs a{};
   const Tensor& s1 = tr.tensors[op.src1];
   a.src1 = s1.p;
@@ -659,16 +679,14 @@ int run_conv(Trainer& tr, const ConvOp& op, int B, bool want_stat = false) {
   a.wsd = (long)d.win_stride();
   a.dst_halo = HALO;
   a.afrag = tr.frag + op.frag_off;
-  a.bias = op.bias_off >= 0 ? tr.w + op.bias_off : tr.zeros;
+  a.bias = op.bias_off >= 0 ? tr.w + op.bias_off : tr.zeros.p;
   a.win_per_set = B;
   a.n_windows = B;
   a.l_out = op.l_out;
   a.l_dst = op.l_out;
-  static const bool b16 = [] { const char* e = getenv("VP_CONV_B16"); return !e || atoi(e) != 0; }();
-  static const bool estat = [] { const char* e = getenv("VP_CONV_STAT"); return !e || atoi(e) != 0; }();
-  if (op.launch_b16 && tr.frag3 && b16) {
-    const bool st = want_stat && estat && tr.conv_stat;
-    op.launch_b16(a, tr.frag3 + op.a3_off, st ? tr.conv_stat : nullptr, op.cols, tr.stream);
+  if (op.launch_b16 && tr.frag3 && conv_switches().b16) {
+    const bool st = want_stat && conv_switches().stat && tr.conv_stat;
+    op.launch_b16(a, tr.frag3 + op.a3_off, st ? tr.conv_stat.p : nullptr, op.cols, tr.stream);
     return st ? ((op.cols + op.tn - 1) / op.tn) * B : 0;
   }
   op.launch(a, op.cols, tr.stream);
@@ -708,226 +726,203 @@ BnArgs bn_args(Trainer& tr, const BnOp& b, int B) {
   return a;
 }
 
-// BatchNorm passes: the crop of the ConvTranspose layers (0, 1 or 2 samples) selects the instantiation
-#define BN_CROP_LAUNCH(KERNEL, GRID, NTH)                                              \
-  do {                                                                                 \
-    if (a.crop == 0) {                                                                 \
-      TRL((KERNEL<T, 0>), GRID, dim3(NTH), 0, s, a);                     \
-    } else if (a.crop == 1) {                                                          \
-      TRL((KERNEL<T, 1>), GRID, dim3(NTH), 0, s, a);                     \
-    } else {                                                                           \
-      TRL((KERNEL<T, 2>), GRID, dim3(NTH), 0, s, a);                     \
-    }                                                                                  \
-  } while (0)
-// the same with an event bound to the launch's own completion (hipExtLaunchKernel's stop event): what another stream
-// waits for is this kernel's end, without the marker packet a hipEventRecord puts into the queue (6-8 us in front of the
-// next launch of this stream, eighteen times per step)
-#define BN_CROP_LAUNCH_EV(KERNEL, GRID, NTH, EV)                                                         \
-  do {                                                                                                   \
-    ++g_launches;                                                                                        \
-    if (a.crop == 0) {                                                                                   \
-      hipExtLaunchKernelGGL((KERNEL<T, 0>), GRID, dim3(NTH), 0, s, nullptr, EV, 0, a);                   \
-    } else if (a.crop == 1) {                                                                            \
-      hipExtLaunchKernelGGL((KERNEL<T, 1>), GRID, dim3(NTH), 0, s, nullptr, EV, 0, a);                   \
-    } else {                                                                                             \
-      hipExtLaunchKernelGGL((KERNEL<T, 2>), GRID, dim3(NTH), 0, s, nullptr, EV, 0, a);                   \
-    }                                                                                                    \
-  } while (0)
-template <class T>
-void bn_forward_v(const BnArgs& a, hipStream_t s) {
+// A BatchNorm pass: the crop of the ConvTranspose layers (0, 1 or 2 samples) selects the instantiation.  With `done` (which
+// may point to a null event) the launch is hipExtLaunchKernel's, the event bound to the launch's own completion (its stop
+// event): what another stream waits for is this kernel's end, without the marker packet a hipEventRecord puts into the
+// queue (6-8 us in front of the next launch of this stream, eighteen times per step).
+void launch_bn(Trainer& tr, const BnKernel (&by_crop)[3], const BnArgs& a, const hipEvent_t* done = nullptr) {
+  const BnKernel kernel = by_crop[a.crop < 2 ? a.crop : 2];
   const dim3 grid(a.C, a.GB);
-  if (!a.fpart) TRL(bnv_stats_partial_kernel<T>, grid, dim3(256), 0, s, a);  // (else the conv launch left the sums)
-  BN_CROP_LAUNCH(bnv_apply_kernel, grid, 256);
-}
-template <class T>
-void bn_backward_v(const BnArgs& a, hipStream_t s, hipEvent_t gz_done) {
-  const dim3 grid(a.C, a.GB);
-  BN_CROP_LAUNCH(bnv_bwd_partial_kernel, grid, 256);
-  BN_CROP_LAUNCH_EV(bnv_bwd_apply_kernel, grid, 256, gz_done);
-}
-#undef BN_CROP_LAUNCH
-#undef BN_CROP_LAUNCH_EV
-
-// Partial results of a weight gradient: one row of out_n floats per workgroup, folded by sum_rows_multi_kernel.  With 256
-// rows for every tensor of > 10 k weights the rows were 267 MB per step -- written by the weight-gradient launches, read
-// again by the fold (68 us, on the step's critical path) -- for 1.1 MB of gradients: the rows are capped by their bytes.
-static int wg_rows_cap(int out_n) {
-  constexpr long budget = 1L << 22;  // same-box sweep: 1.64 ms per step unbounded, 1.60 at 8 M floats, 1.57 at 4-6 M, 1.60 at 2-3 M
-                                     // (below that the deep layers' launches have too few workgroups and end behind the main chain)
-  int cap = out_n > 10000 ? 256 : 512;
-  while (cap > 32 && (long)cap * out_n > budget) cap >>= 1;
-  return cap;
-}
-
-int forward_backward(Trainer& tr, const float* x_dev, const float* y_dev, int B, bool update, float lr) {
-  hipStream_t s = tr.stream;
-  g_launches = 0;
-  TRL(gather_pack_kernel, dim3((unsigned)((tr.frag_n + 255) / 256)), dim3(256), 0, s, tr.frag_idx, tr.w,
-                     tr.frag, (long)tr.frag_n);
-  if (tr.b16_blocks) TRL(conv_b16_pack_kernel, dim3(tr.b16_blocks), dim3(256), 0, s, tr.b16_jobs);
-  if (tr.bf16) {
-    TRL(load_rows_bf16_kernel, dim3((T0 + 511) / 512, 3, B), dim3(256), 0, s, x_dev, tr.rows(tr.t_x), 3, T0);
+  if (done) {
+    ++tr.launches;
+    hipExtLaunchKernelGGL(kernel, grid, dim3(256), 0, tr.stream, nullptr, *done, 0, a);
   } else {
-    TRL(load_rows_kernel, dim3((T0 + 255) / 256, 3, B), dim3(256), 0, s, x_dev, tr.rows(tr.t_x), 3, T0);
+    TRL(kernel, grid, dim3(256), 0, tr.stream, a);
   }
-  for (Layer& L : tr.layers) {
-    const int n_stat = run_conv(tr, L.fwd, B, true);
-    BnArgs a = bn_args(tr, L.bn, B);
-    a.fpart = n_stat ? tr.conv_stat : nullptr;
-    a.n_fpart = n_stat;
-    if (tr.bf16) {
-      bn_forward_v<bf16_t>(a, s);
-    } else {
-      bn_forward_v<float>(a, s);
-    }
-  }
-  {
-    HeadArgs2 h{};
-    h.a = tr.rows(tr.layers[17].bn.a);
-    h.ga = tr.rows(tr.t_ga_last);
-    h.y = y_dev;
-    h.p = tr.p_dev;
-    h.w = tr.w + tr.poff.at("out.weight");
-    h.b = tr.w + tr.poff.at("out.bias");
-    h.partial = tr.head_partial;
-    h.B = B;
-    h.T = T0;
-    h.eps = tr.loss_eps;
-    int gx = (T0 + 255) / 256;
-    const int slot = (int)(tr.seq % Trainer::EV_RING);
-    hipEvent_t ev_in = tr.ev_inputs[slot];
-    tr.ev_inputs_seq[slot] = tr.seq++;
-    if (tr.bf16) {
-      gx = (T0 + 1023) / 1024;
-      ++g_launches;
-      hipExtLaunchKernelGGL((head_fwd_bwd_pair_kernel<bf16_t, 4>), dim3(gx, B), dim3(256), 0, s, nullptr, ev_in, 0, h);
-    } else {
-      ++g_launches;
-      hipExtLaunchKernelGGL(head_fwd_bwd_kernel, dim3(gx, B), dim3(256), 0, s, nullptr, ev_in, 0, h);
-    }
-    // load_rows above read x, this launch read y: nothing behind its end (ev_inputs) touches the caller's buffers
-    // two stages: 64 row groups, then the 64 group sums
-    TRL((sum_rows_kernel<double, double>), dim3(1, 64), dim3(256), 0, s, tr.head_partial, gx * B, 28,
-                       tr.head_stage);
-    TRL((sum_rows_kernel<double, double>), dim3(1, 1), dim3(256), 0, s, tr.head_stage, 64, 28,
-                       tr.head_sums);
-    TRL(head_final_kernel, dim3(1), dim3(32), 0, s, tr.head_sums, tr.head_sums + 28,
-                       tr.grad + tr.poff.at("out.bias"), tr.grad + tr.poff.at("out.weight"));
-  }
+}
+
+// ---- the weight gradients' side queue --------------------------------------------------------------------------------
+// fills the job of folding `rows` partial rows of a layer's weight gradient; returns the workgroups it takes
+int fill_sum_job(SumJob& jb, Trainer& tr, const WgradOp& w, const float* partial, int rows, int first_block) {
+  jb.partial = partial;
+  jb.out = tr.grad + w.grad_off;
+  jb.rows = rows;
+  jb.n = w.out_n;
+  jb.first_block = first_block;
+  jb.cq = sum_job_cq(rows);
+  return (w.out_n + 4 * jb.cq - 1) / (4 * jb.cq);
+}
+
+// The backward pass hands every layer's weight gradient to add(); flush() sends what is held to the other stream behind an
+// event of the main chain.
+struct WgradQueue {
   // The partial rows of the weight gradients are folded by sum_rows_multi_kernel: those of the layers >= FOLD_EARLY each
   // right behind its weight gradient on that stream (where the stream still waits for the main chain between its
   // launches), the rest in one launch at the end of the step, in front of Adam, alone on the chip.
   // (same-box sweep of FOLD_EARLY: none 1.414 ms per step, 13: 1.389, 11: 1.405, 9: 1.411, 7: 1.418, 5: 1.436 -- the folds of
   // the deep layers' 15 MB rows take more from the main chain beside them than they save at the end)
-  constexpr int FOLD_EARLY = 13;
-  SumJobs jobs{}, jobs_last{};
-  int sum_blocks_main = 0, sum_blocks_last = 0;
+  static constexpr int FOLD_EARLY = 13;
   // Layers whose gz gets an event for the weight-gradient stream; the layers between hand their launch to the next event.
   // An event costs the main chain ~5 us (the launch behind a kernel with a completion signal starts that much later):
   // every other layer above level 0, every layer of the last four (their weight gradients are the step's tail).
-  constexpr unsigned ev_mask = 0x2aaaf;
-  // ev_wg1 is recorded at li == 1 on the premise that layer 1's launch has just been flushed, li == 0 flushes the rest, and the
+  static constexpr unsigned ev_mask = 0x2aaaf;
+  // ev_wg1 is recorded behind layer 1's launch on the premise that it is the last of its flush, li == 0 flushes the rest, and the
   // first layer handled (NLAYER - 1) opens the chain: a retuned mask must keep those three bits
   static_assert((ev_mask & 3u) == 3u && ((ev_mask >> (NLAYER - 1)) & 1u), "ev_mask: layers 0, 1 and NLAYER - 1 carry an event");
-  struct { const WgradOp* w; WgradArgs g; int grid, li; } held[NLAYER];
-  int n_held = 0;
   static_assert(NLAYER <= MAX_SUM_JOBS, "one sum job per layer");
+  static bool has_event(int li) { return (ev_mask >> li) & 1; }
+
+  Trainer& tr;
+  const int B;
+  struct {
+    const WgradOp* w;
+    WgradArgs g;
+    int grid, li;
+  } held[NLAYER];
+  int n_held = 0;
+  SumJobs jobs{}, jobs_last{};  // the folds left for the end of the step: layers 1 .. FOLD_EARLY - 1 | layer 0
+  int blocks = 0, blocks_last = 0;
+
+  void add(int li) {
+    const WgradOp& w = tr.layers[li].wg;
+    WgradArgs g{};
+    g.lo = tr.rows(w.lo);
+    g.hi1 = tr.rows(w.hi1);
+    g.lim_hi1 = tr.tensors[w.hi1].ls - HALO;
+    if (w.hi2 >= 0) {
+      g.hi2 = tr.rows(w.hi2);
+      g.lim_hi2 = tr.tensors[w.hi2].ls - HALO;
+    }
+    g.Ln = w.Ln;
+    g.off = w.off;
+    g.B = B;
+    g.chunks = (w.Ln + w.TT - 1) / w.TT;
+    g.partial = tr.wg_partial + w.partial_off;
+    const int items = ((B + w.WB - 1) / w.WB) * g.chunks;
+    const int cap = wg_rows_cap(w.out_n);  // one partial result per workgroup: fewer, longer-lived workgroups for the big weight tensors
+    const int grid = items < cap ? items : cap;
+    held[n_held++] = {&w, g, grid, li};
+    if (li < FOLD_EARLY) {
+      SumJobs& set = li == 0 ? jobs_last : jobs;
+      int& nb = li == 0 ? blocks_last : blocks;
+      nb += fill_sum_job(set.job[set.count], tr, w, g.partial, grid, nb);
+      ++set.count;
+    }
+  }
+  void flush(hipEvent_t gz_done) {
+    (void)hipStreamWaitEvent(tr.stream_wg, gz_done, 0);
+    for (int k = 0; k < n_held; ++k) {
+      const WgradOp& w = *held[k].w;
+      ++tr.launches;
+      w.launch(held[k].g, held[k].grid, tr.stream_wg);
+      if (held[k].li >= FOLD_EARLY) {
+        SumJobs one{};
+        one.count = 1;
+        const int nb = fill_sum_job(one.job[0], tr, w, held[k].g.partial, held[k].grid, 0);
+        ++tr.launches;
+        hipLaunchKernelGGL(sum_rows_multi_kernel, dim3(nb), dim3(256), 0, tr.stream_wg, one);
+      }
+      if (held[k].li == 1) (void)hipEventRecord(tr.ev_wg1, tr.stream_wg);  // (layer 1 carries an event: its launch is out)
+    }
+    n_held = 0;
+  }
+};
+
+// ---- the step, phase by phase ----------------------------------------------------------------------------------------
+void pack_weights(Trainer& tr) {
+  TRL(gather_pack_kernel, dim3((unsigned)((tr.frag_n + 255) / 256)), dim3(256), 0, tr.stream, tr.frag_idx, tr.w, tr.frag,
+      (long)tr.frag_n);
+  if (tr.b16_blocks) TRL(conv_b16_pack_kernel, dim3(tr.b16_blocks), dim3(256), 0, tr.stream, tr.b16_jobs);
+}
+
+void load_input(Trainer& tr, const float* x_dev, int B) {
+  TRL(tr.rk.load_rows, dim3((T0 + tr.rk.load_span - 1) / tr.rk.load_span, 3, B), dim3(256), 0, tr.stream, x_dev, tr.rows(tr.t_x), 3, T0);
+}
+
+void forward_layers(Trainer& tr, int B) {
+  for (Layer& L : tr.layers) {
+    const int n_stat = run_conv(tr, L.fwd, B, true);
+    BnArgs a = bn_args(tr, L.bn, B);
+    a.fpart = n_stat ? tr.conv_stat.p : nullptr;
+    a.n_fpart = n_stat;
+    if (!a.fpart) TRL(tr.rk.bn_stats, dim3(a.C, a.GB), dim3(256), 0, tr.stream, a);  // (else the conv launch left the sums)
+    launch_bn(tr, tr.rk.bn_apply, a);
+  }
+}
+
+void head_and_loss(Trainer& tr, const float* y_dev, int B) {
+  hipStream_t s = tr.stream;
+  HeadArgs2 h{};
+  h.a = tr.rows(tr.layers[NLAYER - 1].bn.a);
+  h.ga = tr.rows(tr.t_ga_last);
+  h.y = y_dev;
+  h.p = tr.p_dev;
+  h.w = tr.w + tr.poff.at("out.weight");
+  h.b = tr.w + tr.poff.at("out.bias");
+  h.partial = tr.head_partial;
+  h.B = B;
+  h.T = T0;
+  h.eps = tr.loss_eps;
+  const int gx = (T0 + tr.rk.head_span - 1) / tr.rk.head_span;
+  const int slot = (int)(tr.seq % Trainer::EV_RING);
+  hipEvent_t ev_in = tr.ev_inputs[slot];
+  tr.ev_inputs_seq[slot] = tr.seq++;
+  // load_rows read x, this launch reads y: nothing behind its end (ev_inputs) touches the caller's buffers
+  ++tr.launches;
+  hipExtLaunchKernelGGL(tr.rk.head, dim3(gx, B), dim3(256), 0, s, nullptr, ev_in, 0, h);
+  // two stages: 64 row groups, then the 64 group sums
+  TRL((sum_rows_kernel<double, double>), dim3(1, 64), dim3(256), 0, s, tr.head_partial, gx * B, 28, tr.head_stage);
+  TRL((sum_rows_kernel<double, double>), dim3(1, 1), dim3(256), 0, s, tr.head_stage, 64, 28, tr.head_sums);
+  TRL(head_final_kernel, dim3(1), dim3(32), 0, s, tr.head_sums, tr.head_sums + 28, tr.grad + tr.poff.at("out.bias"),
+      tr.grad + tr.poff.at("out.weight"));
+}
+
+void backward_layers(Trainer& tr, WgradQueue& wq, int B) {
+  hipStream_t s = tr.stream;
   for (int li = NLAYER - 1; li >= 0; --li) {
     Layer& L = tr.layers[li];
     const BnArgs a = bn_args(tr, L.bn, B);
-    if (tr.bf16) {
-      bn_backward_v<bf16_t>(a, s, ((ev_mask >> li) & 1) ? tr.ev_gz[li] : nullptr);  // the event: gz of this layer is complete
-    } else {
-      bn_backward_v<float>(a, s, ((ev_mask >> li) & 1) ? tr.ev_gz[li] : nullptr);
-    }
-    {
-      const WgradOp& w = L.wg;
-      WgradArgs g{};
-      g.lo = tr.rows(w.lo);
-      g.hi1 = tr.rows(w.hi1);
-      g.lim_hi1 = tr.tensors[w.hi1].ls - HALO;
-      if (w.hi2 >= 0) {
-        g.hi2 = tr.rows(w.hi2);
-        g.lim_hi2 = tr.tensors[w.hi2].ls - HALO;
-      }
-      g.Ln = w.Ln;
-      g.off = w.off;
-      g.B = B;
-      g.chunks = (w.Ln + w.TT - 1) / w.TT;
-      g.partial = tr.wg_partial + w.partial_off;
-      const int items = ((B + w.WB - 1) / w.WB) * g.chunks;
-      const int cap = wg_rows_cap(w.out_n);  // one partial result per workgroup: fewer, longer-lived workgroups for the big weight tensors
-      const int grid = items < cap ? items : cap;
-      ++g_launches;
-      held[n_held].w = &w;
-      held[n_held].g = g;
-      held[n_held].li = li;
-      held[n_held++].grid = grid;
-      if ((ev_mask >> li) & 1) {
-        (void)hipStreamWaitEvent(tr.stream_wg, tr.ev_gz[li], 0);
-        for (int k = 0; k < n_held; ++k) {
-          const WgradOp& hw = *held[k].w;
-          hw.launch(held[k].g, held[k].grid, tr.stream_wg);
-          if (held[k].li >= FOLD_EARLY) {
-            SumJobs one{};
-            one.count = 1;
-            SumJob& ej = one.job[0];
-            ej.partial = held[k].g.partial;
-            ej.out = tr.grad + hw.grad_off;
-            ej.rows = held[k].grid;
-            ej.n = hw.out_n;
-            ej.first_block = 0;
-            ej.cq = sum_job_cq(held[k].grid);
-            ++g_launches;
-            hipLaunchKernelGGL(sum_rows_multi_kernel, dim3((hw.out_n + 4 * ej.cq - 1) / (4 * ej.cq)), dim3(256), 0, tr.stream_wg, one);
-          }
-        }
-        n_held = 0;
-      }
-      if (li == 1) (void)hipEventRecord(tr.ev_wg1, tr.stream_wg);  // (layer 1 carries an event: its launch is out)
-      if (li < FOLD_EARLY) {
-        SumJobs& jset = li == 0 ? jobs_last : jobs;
-        int& sum_blocks = li == 0 ? sum_blocks_last : sum_blocks_main;
-        SumJob& jb = jset.job[jset.count++];
-        jb.partial = g.partial;
-        jb.out = tr.grad + w.grad_off;
-        jb.rows = grid;
-        jb.n = w.out_n;
-        jb.first_block = sum_blocks;
-        jb.cq = sum_job_cq(grid);
-        sum_blocks += (w.out_n + 4 * jb.cq - 1) / (4 * jb.cq);
-      }
-    }
+    const hipEvent_t gz_done = WgradQueue::has_event(li) ? tr.ev_gz[li] : nullptr;  // the event: gz of this layer is complete
+    launch_bn(tr, tr.rk.bn_bwd_partial, a);
+    launch_bn(tr, tr.rk.bn_bwd_apply, a, &gz_done);
+    wq.add(li);
+    if (gz_done) wq.flush(gz_done);
     if (li == 0) {  // conv bias of `inc`: sum of gz per channel (zero up to rounding: BatchNorm removes the mean)
       const int GB = B < 64 ? B : 64;
-      if (tr.bf16) {
-        TRL(channel_sum_partial_v_kernel<bf16_t>, dim3(8, GB), dim3(256), 0, s, tr.rows(L.bn.gz), B, T0, GB,
-                           tr.bn_partial);
-      } else {
-        TRL(channel_sum_partial_v_kernel<float>, dim3(8, GB), dim3(256), 0, s, tr.rows(L.bn.gz), B, T0, GB,
-                           tr.bn_partial);
-      }
-      TRL((sum_rows_kernel<double, float>), dim3(1, 1), dim3(256), 0, s, tr.bn_partial, GB, 8,
-                         tr.grad + tr.poff.at("inc.bias"));
+      TRL(tr.rk.channel_sum, dim3(8, GB), dim3(256), 0, s, tr.rows(L.bn.gz), B, T0, GB, tr.bn_partial);
+      TRL((sum_rows_kernel<double, float>), dim3(1, 1), dim3(256), 0, s, tr.bn_partial, GB, 8, tr.grad + tr.poff.at("inc.bias"));
     }
     if (L.dgrad.used) run_conv(tr, L.dgrad, B);
   }
+}
+
+void fold_and_update(Trainer& tr, const WgradQueue& wq, bool update, float lr) {
+  hipStream_t s = tr.stream;
   // the fold of everything but the first layer's rows runs beside that layer's weight gradient, the step's last launch on
   // the other stream; its own few rows behind it
   (void)hipStreamWaitEvent(s, tr.ev_wg1, 0);
-  TRL(sum_rows_multi_kernel, dim3(sum_blocks_main), dim3(256), 0, s, jobs);
+  TRL(sum_rows_multi_kernel, dim3(wq.blocks), dim3(256), 0, s, wq.jobs);
   (void)hipEventRecord(tr.ev_wg, tr.stream_wg);
   (void)hipStreamWaitEvent(s, tr.ev_wg, 0);  // every weight gradient's partial rows are written
-  TRL(sum_rows_multi_kernel, dim3(sum_blocks_last), dim3(256), 0, s, jobs_last);
+  TRL(sum_rows_multi_kernel, dim3(wq.blocks_last), dim3(256), 0, s, wq.jobs_last);
   if (update) {
     tr.step += 1;
     const float bc1 = 1.f - powf(tr.beta1, (float)tr.step);
     const float bc2 = 1.f - powf(tr.beta2, (float)tr.step);
-    TRL(adam_kernel, dim3((unsigned)((tr.n_params + 255) / 256)), dim3(256), 0, s, tr.w, tr.grad,
-                       tr.adam_m, tr.adam_v, tr.mask, tr.ema, (int)tr.n_params, lr, tr.beta1, tr.beta2, tr.adam_eps, bc1,
-                       sqrtf(bc2), tr.ema_decay);
+    TRL(adam_kernel, dim3((unsigned)((tr.n_params + 255) / 256)), dim3(256), 0, s, tr.w, tr.grad, tr.adam_m, tr.adam_v, tr.mask,
+        tr.ema, (int)tr.n_params, lr, tr.beta1, tr.beta2, tr.adam_eps, bc1, sqrtf(bc2), tr.ema_decay);
   }
-  tr.launches_last_step = g_launches;
+}
+
+int forward_backward(Trainer& tr, const float* x_dev, const float* y_dev, int B, bool update, float lr) {
+  tr.launches = 0;
+  pack_weights(tr);
+  load_input(tr, x_dev, B);
+  forward_layers(tr, B);
+  head_and_loss(tr, y_dev, B);
+  WgradQueue wq{tr, B};
+  backward_layers(tr, wq, B);
+  fold_and_update(tr, wq, update, lr);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     set_error("training step: kernel launch failed: %s", hipGetErrorString(e));
@@ -1003,7 +998,7 @@ int vp_train_create_dtype(int device_id, int model_kind, const float* weights, s
   tr->max_batch = max_batch;
   tr->bf16 = dtype == VP_TRAIN_BF16;
   tr->esize = tr->bf16 ? 2 : 4;
-  int rc = tr->bf16 ? build_plan<1>(*tr) : build_plan<0>(*tr);
+  int rc = build_plan(*tr);
   if (rc != VP_OK) return rc;
   VP_REQUIRE(n_floats == tr->n_params, "vp_train_create: expected %zu weights, got %zu", tr->n_params, n_floats);
   VP_HIP(hipSetDevice(device_id));
@@ -1034,7 +1029,7 @@ int vp_train_set_ema(vp_trainer* h, float decay) {
   Trainer& tr = *reinterpret_cast<Trainer*>(h);
   VP_HIP(hipSetDevice(tr.device));
   VP_HIP(hipStreamSynchronize(tr.stream));
-  if (!tr.ema) VP_HIP(hipMalloc(&tr.ema, tr.n_params * sizeof(float)));
+  if (!tr.ema) VP_HIP(tr.ema.alloc(tr.n_params));
   // starts at the current weights; on the trainer's (non-blocking) stream, so that the next step's Adam / EMA update is
   // ordered behind the copy (a null-stream device-to-device copy may return before it has run)
   VP_HIP(hipMemcpyAsync(tr.ema, tr.w, tr.n_params * sizeof(float), hipMemcpyDeviceToDevice, tr.stream));
@@ -1112,7 +1107,7 @@ int vp_train_read(vp_trainer* h, int which, float* out, size_t n_floats) {
   Trainer& tr = *reinterpret_cast<Trainer*>(h);
   VP_REQUIRE(n_floats == tr.n_params && which >= 0 && which <= 4, "vp_train_read: bad size or selector");
   VP_REQUIRE(which != 4 || tr.ema, "vp_train_read: EMA is off (vp_train_set_ema)");
-  const float* src = which == 0 ? tr.w : which == 1 ? tr.grad : which == 2 ? tr.adam_m : which == 3 ? tr.adam_v : tr.ema;
+  const float* src = *(which == 0 ? &tr.w : which == 1 ? &tr.grad : which == 2 ? &tr.adam_m : which == 3 ? &tr.adam_v : &tr.ema);
   VP_HIP(hipSetDevice(tr.device));
   VP_HIP(hipStreamSynchronize(tr.stream));
   VP_HIP(hipMemcpy(out, src, n_floats * sizeof(float), hipMemcpyDeviceToHost));
@@ -1175,7 +1170,7 @@ int vp_train_tensor_read(vp_trainer* h, int index, int B, float* out) {
                      (size_t)B * t.C, hipMemcpyDeviceToHost));
   return VP_OK;
 }
-int vp_train_launch_count(const vp_trainer* h) { return h ? reinterpret_cast<const Trainer*>(h)->launches_last_step : 0; }
+int vp_train_launch_count(const vp_trainer* h) { return h ? reinterpret_cast<const Trainer*>(h)->launches : 0; }
 
 void* vp_train_stream(const vp_trainer* h) { return h ? reinterpret_cast<const Trainer*>(h)->stream : nullptr; }
 
