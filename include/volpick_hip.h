@@ -628,6 +628,50 @@ int vp_train_step_bank_aug(vp_trainer* t, vp_bank* bank, const vp_aug_row* rows,
                            const int* label_rows, float lr, int update, double* loss);
 
 /* ---------------------------------------------------------------------------------------------
+ * Validation loss on the device: the reference's vector_cross_entropy (volpick/model/models.py:34-51) of predictions
+ * that never leave the GPU, in float64, and the validation half of its training loop (validation_step, :171-174) on
+ * batches generated from a waveform bank.
+ *
+ * vp_vce_loss reads p and y, dense (B, C, T) fp32 on device `device_id`, and writes on `stream` (hipStream_t, NULL =
+ * legacy default stream), without waiting for it:
+ *   per_window_dev[b] = -(1/T) sum_c sum_t y[b][c][t] * log((double)p[b][c][t] + eps)     (B doubles, may be NULL)
+ *   batch_dev[0]      = (1/B) sum_b per_window_dev[b]                                      (1 double, may be NULL)
+ * Every operation is a float64 one (eps is a double: 1e-5, not (double)1e-5f).  The order of every sum is fixed and there
+ * are no atomics: the same arrays at the same addresses give the same bits (the order depends on the addresses mod 16 only).
+ * NaN and Inf propagate as IEEE arithmetic takes them -- that window's value and the batch loss become NaN -- and are no
+ * error.  With per_window_dev NULL the batch loss is the same number, computed by one workgroup: slow, for callers with
+ * nowhere to put B doubles.  Checked on the host before any launch (VP_ERR_INVALID, outputs untouched): B >= 1,
+ * 1 <= C <= 8, T >= 1, eps > 0, p and y not NULL.
+ *
+ * A validation pass on a PhaseNet handle; an EQTransformer handle gets VP_ERR_UNSUPPORTED, its loss has other labels:
+ *   vp_validate_begin(h)        opens a pass: no batches yet.
+ *   vp_validate_bank(h, ...)    enqueues one batch on the handle's stream and returns: rows cut, normalised and labelled as
+ *                               vp_bank_make_batch does (T = vp_in_samples(h)) into scratch of the handle; the forward pass
+ *                               on it as vp_forward(preprocess = 0) runs it, in chunks of max_batch windows; the loss of all
+ *                               B windows (the batch value is their mean, not a mean of chunk means), appended with the B
+ *                               window values to device arrays of the handle.  pred_out_dev, when not NULL, receives the
+ *                               (B, 3, T) predictions (device memory no other stream is using).  Any B >= 1.  Rows and
+ *                               arguments are checked as for vp_bank_make_batch, and eps > 0, before anything is enqueued.
+ *   vp_validate_bank_aug        the same on vp_aug_row rows (vp_bank_make_batch_aug).
+ *   vp_validate_end(h, ...)     waits for the stream -- the pass's only host wait in the steady state -- and copies out up
+ *                               to `cap` batch losses and `cap_windows` window values, in the order enqueued; *n_batches and
+ *                               *n_windows are how many the pass holds.  Closes the pass.
+ * The host does wait inside a pass when a batch is larger than any before it on this handle, or a result array grows
+ * (both reallocate), and when eight batches are in flight: a slot of the row staging ring is reused only behind the event
+ * of the launch that read it.  `rows` may be reused as soon as the call returns.  The bank must live on the handle's
+ * device and stay alive until vp_validate_end.  One thread at a time per handle, as for every call on a vp_handle; the
+ * results of a pass do not depend on what ran before it (bit for bit). */
+int vp_vce_loss(int device_id, const float* p_dev, const float* y_dev, int B, int C, int T, double eps,
+                double* per_window_dev, double* batch_dev, void* stream);
+int vp_validate_begin(vp_handle* h);
+int vp_validate_bank(vp_handle* h, vp_bank* bank, const vp_plan_row* rows, int B, float sigma, int norm,
+                     const int* label_rows, double eps, float* pred_out_dev);
+int vp_validate_bank_aug(vp_handle* h, vp_bank* bank, const vp_aug_row* rows, int B, float sigma, int norm,
+                         const int* label_rows, double eps, float* pred_out_dev);
+int vp_validate_end(vp_handle* h, double* batch_losses, long long cap, long long* n_batches, double* per_window,
+                    long long cap_windows, long long* n_windows);
+
+/* ---------------------------------------------------------------------------------------------
  * Frequency index and signal-to-noise ratio of picks and bank traces, on the device: the trace_frequency_index,
  * trace_snr_db and trace_mean_snr_db columns the reference stores with every trace it writes (volpick/data/utils.py
  * freqency_index, calculate_snr; volpick/data/convert.py:222-270).  One vp_attr_row per pick or trace, planned on the

@@ -1,0 +1,135 @@
+#!/usr/bin/env python3
+"""What one validation batch costs beside one training step (LOG.md), on a synthetic bank.
+
+At B = 512 and B = 64, medians after warm-up:
+  host    ms per batch of ``PhaseNetLit.validation_step(bank.make_batch(rows))``: forward on the GPU, predictions and
+          labels copied back, float64 numpy loss on one host thread (each batch ends with the host holding its loss);
+  device  ms per batch of ``validate_batches``: passes of N batches between one vp_validate_begin and vp_validate_end
+          (pass time / N), and the latency of a pass of one batch;
+  stages  of the device batch, each alone between HIP events: generation, forward, loss kernel;
+  export  ms of one ``PhaseNetTrainer.export()`` and of the handle rebuild (``model.cuda()``) that follows it;
+  step    ms of one ``step_bank`` as ``fit_bank`` runs it (the loss read back every step) and with the steps queued.
+usage: validate_timing.py [--batches 20] [--passes 7]"""
+import argparse
+import ctypes as C
+import json
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
+import torch  # noqa: E402
+
+from volpick_amd import PhaseNet, _lib  # noqa: E402
+from volpick_amd import generate as G  # noqa: E402
+from volpick_amd.synthetic import synthetic_stream_array  # noqa: E402
+from volpick_amd.train import PhaseNetLit, validate_batches, vector_cross_entropy  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--batches", type=int, default=20, help="batches per device pass, and host batches / steps timed")
+ap.add_argument("--passes", type=int, default=7)
+ap.add_argument("--traces", type=int, default=128)
+args = ap.parse_args()
+N = max(20, args.batches)
+
+
+def wall_ms(fn, n, warm=3):
+    """Median wall time of fn() in ms over n calls after `warm` calls; the GPU is idle at the start of each."""
+    out = []
+    for i in range(warm + n):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        if i >= warm:
+            out.append(1e3 * (time.perf_counter() - t0))
+    return float(np.median(out))
+
+
+def event_ms(fn, n, warm=3):
+    """Median time of what fn() enqueues on torch's current stream, between two events."""
+    out = []
+    for i in range(warm + n):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        if i >= warm:
+            out.append(a.elapsed_time(b))
+    return float(np.median(out))
+
+
+rng = np.random.default_rng(0)
+xs, ps, ss = [], [], []
+for i in range(args.traces):
+    x, p, s = synthetic_stream_array(9000, seed=1000 + i, n_events=1)
+    xs.append(x * rng.uniform(0.1, 100.0))
+    ps.append(float(p[0]))
+    ss.append(float(s[0]))
+bank = G.WaveformBank(np.stack(xs).astype(np.float32), {"P": ps, "S": ss})
+lib = _lib.load()
+result = {}
+for B in (512, 64):
+    lit = PhaseNetLit(lr=1e-3, model=PhaseNet.from_pretrained("volpick"), max_batch=B)
+    tr = lit._ensure()
+    planner = G.WindowPlanner(bank, B, seed=B)
+    plans = [planner.plan(rng.integers(0, args.traces, B)) for _ in range(N)]
+    model = lit._exported_model()
+    r = result[f"B{B}"] = {}
+
+    it = iter(plans * 4)
+    r["host_ms_per_batch"] = wall_ms(lambda: lit.validation_step(bank.make_batch(next(it), model, lit.sigma)), N)
+    r["device_ms_per_batch_in_a_pass"] = wall_ms(lambda: validate_batches(model, bank, plans, lit.sigma), args.passes, warm=2) / N
+    it = iter(plans * 4)
+    r["device_ms_single_batch_pass"] = wall_ms(lambda: validate_batches(model, bank, [next(it)], lit.sigma), N)
+
+    # the stages of a device batch, each alone
+    it = iter(plans * 4)
+    made = bank.make_batch(plans[0], model, lit.sigma)
+    r["stage_generate_ms"] = event_ms(lambda: bank.make_batch(next(it), model, lit.sigma), N)
+    r["stage_forward_ms"] = wall_ms(lambda: model(made["X"]), N)  # (vp_forward waits for its stream itself)
+    pred = model(made["X"])
+    pw = torch.empty(B, dtype=torch.float64, device="cuda")
+    bt = torch.empty(1, dtype=torch.float64, device="cuda")
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    r["stage_loss_kernel_ms"] = event_ms(
+        lambda: _lib.check(lib.vp_vce_loss(0, C.c_void_p(pred.data_ptr()), C.c_void_p(made["y"].data_ptr()), B, 3, 3001, 1e-5,
+                                           C.c_void_p(pw.data_ptr()), C.c_void_p(bt.data_ptr()), stream)), N)
+    # the host path's own parts
+    p_host, y_host = pred.cpu().numpy(), made["y"].cpu().numpy()
+    r["host_copy_back_ms"] = wall_ms(lambda: (pred.cpu(), made["y"].cpu()), N)
+    t0 = time.perf_counter()
+    for _ in range(5):
+        vector_cross_entropy(p_host.astype(np.float64), y_host.astype(np.float64))
+    r["host_numpy_loss_ms"] = 1e3 * (time.perf_counter() - t0) / 5
+
+    for prec in ("32", "bf16-mixed"):
+        lt = lit if prec == "32" else PhaseNetLit(lr=1e-3, model=PhaseNet.from_pretrained("volpick"), max_batch=B, precision=prec)
+        t = lt._ensure()
+        it = iter(plans * 4)
+        key = "fp32" if prec == "32" else "bf16"
+        r[f"train_step_ms_{key}"] = wall_ms(lambda: t.step_bank(bank, next(it), 1e-3, lt.sigma), N)
+
+        def queued():
+            for rows in plans:
+                t.step_bank(bank, rows, 1e-3, lt.sigma, want_loss=False)
+            t.synchronize()
+
+        r[f"train_step_ms_{key}_queued"] = wall_ms(queued, 3, warm=1) / N
+
+    r["export_ms"] = wall_ms(lambda: tr.export(), 5, warm=1)
+
+    def export_and_rebuild():
+        tr.export()
+        lit.model.cuda(0)
+
+    r["export_and_handle_rebuild_ms"] = wall_ms(export_and_rebuild, 5, warm=1)
+    print(f"B = {B}")
+    for k, v in r.items():
+        print(f"  {k:34s} {v:9.3f} ms")
+    r["device_batch_below_train_step"] = bool(r["device_ms_per_batch_in_a_pass"] < r["train_step_ms_fp32"])
+bank.close()
+print(json.dumps({"validate_timing": result}))

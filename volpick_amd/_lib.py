@@ -297,6 +297,20 @@ SIGNATURES = {
         C.c_int,
         [_H, _H, C.c_void_p, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_int), C.c_float, C.c_int, C.POINTER(C.c_double)],
     ),
+    "vp_vce_loss": (
+        C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
+    "vp_validate_begin": (C.c_int, [_H]),
+    "vp_validate_bank": (
+        C.c_int, [_H, _H, C.c_void_p, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_int), C.c_double, C.c_void_p],
+    ),
+    "vp_validate_bank_aug": (
+        C.c_int, [_H, _H, C.c_void_p, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_int), C.c_double, C.c_void_p],
+    ),
+    "vp_validate_end": (
+        C.c_int, [_H, C.POINTER(C.c_double), C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(C.c_double), C.c_longlong,
+                  C.POINTER(C.c_longlong)],
+    ),
     "vp_attributes": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.POINTER(VpAttrRow), C.c_int, C.c_void_p, C.c_void_p]),
     "vp_bank_attributes": (C.c_int, [_H, C.POINTER(VpAttrRow), C.c_int, C.c_void_p, C.c_void_p]),
     "vp_spectrogram": (

@@ -2,10 +2,13 @@
 #include <algorithm>
 #include <cmath>
 #include <mutex>
+#include <type_traits>
 
 #include "api_host.h"
+#include "batchgen.h"
 #include "net.h"
 #include "prepost.h"
+#include "valloss.h"
 
 namespace vp {
 const char* last_error();
@@ -37,6 +40,28 @@ struct DevBuf {
 };
 using MirroredBuf = DevBuf<char, true>;  // a trigger result block (vp::ScanLayout) and what the publish kernel copies it to
 
+// One validation pass (vp_validate_begin ... vp_validate_end): the scratch one batch is generated into and predicted in,
+// the staging of its plan rows, and the losses of every batch of the pass, all on the device until the pass ends.
+struct ValidationPass {
+  bool open = false;
+  DevBuf<float> x, y, pred;          // (B, 3, T) each: the batch of the latest vp_validate_bank
+  vp::RowRing rows;                  // slot launches % N, free again behind ev[slot]
+  hipEvent_t ev[vp::RowRing::N] = {};  // behind the last kernel of the launch that read ring slot i
+  bool ev_used[vp::RowRing::N] = {};
+  long long launches = 0;            // over the handle's life: the ring outlives a pass
+  DevBuf<double> batch, window;      // the pass's results: n_batches and n_windows values
+  long long n_batches = 0, n_windows = 0;
+  void release() {
+    for (DevBuf<float>* b : {&x, &y, &pred}) b->release();
+    batch.release();
+    window.release();
+    for (hipEvent_t& e : ev) {
+      if (e) (void)hipEventDestroy(e);
+      e = nullptr;
+    }
+  }
+};
+
 }  // namespace
 
 struct vp_handle {
@@ -66,6 +91,7 @@ struct vp_handle {
     int n_specs = 0, cap = 0;
     int64_t fv = -1, lv = -1, nwin = 0;
   } slot[VP_MAX_INFLIGHT];
+  ValidationPass val;
 };
 
 namespace {
@@ -320,6 +346,7 @@ int vp_destroy(vp_handle* h) {
   h->d_out.release();
   h->d_tab.release();
   h->m_pick.release();
+  h->val.release();
   for (auto& sl : h->slot) {
     sl.pick.release();
     if (sl.done) (void)hipEventDestroy(sl.done);
@@ -371,6 +398,137 @@ int vp_forward(vp_handle* h, const float* x, int x_mem, int B, int preprocess, f
   VP_HIP(hipEventElapsedTime(&h->total_ms, h->ev[0], h->ev[1]));
   h->stage_ms[0] = h->stage_ms[2] = h->stage_ms[3] = 0.f;
   h->stage_ms[1] = h->total_ms;
+  return VP_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// Room for `need` values in a results array of a validation pass, its first `used` values kept.  Growing waits for the
+// stream: the launches in flight write into the old block.
+int grow_results(DevBuf<double>& b, size_t used, size_t need, hipStream_t s) {
+  if (need <= b.cap) return VP_OK;
+  VP_HIP(hipStreamSynchronize(s));
+  DevBuf<double> old = b;
+  b = DevBuf<double>();
+  const int rc = b.reserve(std::max(need, 2 * old.cap));
+  hipError_t e = hipSuccess;
+  if (rc == VP_OK && used) e = hipMemcpy(b.p, old.p, used * sizeof(double), hipMemcpyDeviceToDevice);
+  old.release();
+  if (rc != VP_OK) return rc;
+  VP_HIP(e);
+  return VP_OK;
+}
+
+// vp_validate_bank(_aug): generate, forward in chunks of max_batch, loss of all B windows, results appended.
+template <class Row>
+int validate_batch(vp_handle* h, vp_bank* bank, const Row* rows, int B, float sigma, int norm, const int* label_rows, double eps,
+                   float* pred_out_dev, const char* who) {
+  constexpr bool AUG = std::is_same<Row, vp_aug_row>::value;
+  VP_REQUIRE(h && bank, "%s: null argument", who);
+  if (h->net.model_kind != VP_MODEL_PHASENET) {
+    vp::set_error("%s: only a PhaseNet handle has a validation loss", who);
+    return VP_ERR_UNSUPPORTED;
+  }
+  ValidationPass& v = h->val;
+  VP_REQUIRE(v.open, "%s: no pass is open (vp_validate_begin)", who);
+  const vp::Bank& bk = *reinterpret_cast<const vp::Bank*>(bank);
+  VP_REQUIRE(bk.device == h->device, "%s: bank on device %d, handle on device %d", who, bk.device, h->device);
+  VP_REQUIRE(eps > 0.0, "%s: eps = %g must be > 0", who, eps);
+  vp::Net& net = h->net;
+  const int T = net.in_samples;
+  int rc;
+  if constexpr (AUG) {
+    rc = vp::bank_check_aug(bk, rows, B, T, sigma, norm, label_rows);
+  } else {
+    rc = vp::bank_check(bk, rows, B, T, sigma, norm, label_rows);
+  }
+  if (rc != VP_OK) return rc;
+  VP_HIP(hipSetDevice(h->device));
+
+  // ---- room for the batch, its rows and its results: nothing is enqueued before all of it stands -------------------------
+  const size_t w = (size_t)3 * T, bytes = (size_t)B * sizeof(Row);
+  if (!v.ev[0])
+    for (hipEvent_t& e : v.ev) VP_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  if ((size_t)B * w > v.x.cap || bytes > v.rows.cap) {
+    VP_HIP(hipStreamSynchronize(h->stream));  // launches in flight read the old blocks; every ring slot is idle afterwards
+    for (DevBuf<float>* b : {&v.x, &v.y, &v.pred})
+      if ((rc = b->reserve((size_t)B * w)) != VP_OK) return rc;
+    if ((rc = v.rows.reserve(std::max(bytes, (size_t)net.max_batch * sizeof(vp_aug_row)))) != VP_OK) return rc;
+  }
+  if ((rc = grow_results(v.batch, (size_t)v.n_batches, (size_t)v.n_batches + 1, h->stream)) != VP_OK) return rc;
+  if ((rc = grow_results(v.window, (size_t)v.n_windows, (size_t)v.n_windows + B, h->stream)) != VP_OK) return rc;
+  const int slot = (int)(v.launches % vp::RowRing::N);
+  if (v.ev_used[slot]) VP_HIP(hipEventSynchronize(v.ev[slot]));  // (eight launches back: long complete in the steady state)
+
+  // ---- generate -> forward -> loss ----------------------------------------------------------------------------------------
+  const Row* rd = static_cast<const Row*>(v.rows.stage(slot, rows, bytes, h->stream));
+  if (!rd) return VP_ERR_HIP;
+  if constexpr (AUG) {
+    rc = vp::bank_launch_aug(bk, rd, B, T, sigma, norm, label_rows, v.x.p, v.y.p, h->stream);
+  } else {
+    rc = vp::bank_launch(bk, rd, B, T, sigma, norm, label_rows, v.x.p, v.y.p, h->stream);
+  }
+  if (rc != VP_OK) return rc;
+  for (int b0 = 0; b0 < B; b0 += net.max_batch) {
+    const int nb = std::min(net.max_batch, B - b0);
+    const OutputRedirect to_pred(net, v.pred.p + (size_t)b0 * w);
+    if ((rc = run_batch(h, pre_args(h, v.x.p + (size_t)b0 * w, 1, 0, 0, 0, 0), nb)) != VP_OK) return rc;
+  }
+  rc = vp::vce_launch(v.pred.p, v.y.p, B, 3, T, eps, v.window.p + v.n_windows, v.batch.p + v.n_batches, h->stream);
+  if (rc != VP_OK) return rc;
+  VP_HIP(hipEventRecord(v.ev[slot], h->stream));
+  v.ev_used[slot] = true;
+  ++v.launches;
+  if (pred_out_dev)
+    VP_HIP(hipMemcpyAsync(pred_out_dev, v.pred.p, (size_t)B * w * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+  ++v.n_batches;
+  v.n_windows += B;
+  return VP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vp_validate_begin(vp_handle* h) {
+  VP_REQUIRE(h != nullptr, "vp_validate_begin: null handle");
+  if (h->net.model_kind != VP_MODEL_PHASENET) {
+    vp::set_error("vp_validate_begin: only a PhaseNet handle has a validation loss");
+    return VP_ERR_UNSUPPORTED;
+  }
+  static_assert(sizeof(vp_aug_row) >= sizeof(vp_plan_row), "the row ring is sized for the larger row");
+  h->val.open = true;
+  h->val.n_batches = h->val.n_windows = 0;  // (launches of an abandoned pass run ahead of this one's on the same stream)
+  return VP_OK;
+}
+
+int vp_validate_bank(vp_handle* h, vp_bank* bank, const vp_plan_row* rows, int B, float sigma, int norm,
+                     const int* label_rows, double eps, float* pred_out_dev) {
+  return validate_batch(h, bank, rows, B, sigma, norm, label_rows, eps, pred_out_dev, "vp_validate_bank");
+}
+
+int vp_validate_bank_aug(vp_handle* h, vp_bank* bank, const vp_aug_row* rows, int B, float sigma, int norm,
+                         const int* label_rows, double eps, float* pred_out_dev) {
+  return validate_batch(h, bank, rows, B, sigma, norm, label_rows, eps, pred_out_dev, "vp_validate_bank_aug");
+}
+
+int vp_validate_end(vp_handle* h, double* batch_losses, long long cap, long long* n_batches, double* per_window,
+                    long long cap_windows, long long* n_windows) {
+  VP_REQUIRE(h != nullptr, "vp_validate_end: null handle");
+  ValidationPass& v = h->val;
+  VP_REQUIRE(v.open, "vp_validate_end: no pass is open (vp_validate_begin)");
+  VP_REQUIRE(cap >= 0 && cap_windows >= 0 && (cap == 0 || batch_losses) && (cap_windows == 0 || per_window),
+             "vp_validate_end: null output arrays");
+  VP_HIP(hipSetDevice(h->device));
+  const long long nb = std::min(cap, v.n_batches), nw = std::min(cap_windows, v.n_windows);
+  if (nb > 0) VP_HIP(hipMemcpyAsync(batch_losses, v.batch.p, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (nw > 0) VP_HIP(hipMemcpyAsync(per_window, v.window.p, (size_t)nw * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  VP_HIP(hipStreamSynchronize(h->stream));
+  if (n_batches) *n_batches = v.n_batches;
+  if (n_windows) *n_windows = v.n_windows;
+  v.open = false;
   return VP_OK;
 }
 

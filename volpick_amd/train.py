@@ -12,9 +12,14 @@ Batches come either finished, as ``(x, y)`` tensors (``PhaseNetTrainer.step``, `
 generated on the GPU from a device-resident :class:`~volpick_amd.generate.WaveformBank`: window cut, demean and
 normalise and Gaussian labels -- the core of the reference's augmentation block 1, its random choices planned on the
 host by :class:`~volpick_amd.generate.WindowPlanner` (``PhaseNetTrainer.step_bank``, ``PhaseNetLit.fit_bank``).
-volpick's stacking augmentations, logging and checkpointing (Lightning) are not part of this package.  Forward
-(training-mode BatchNorm), loss, backward and Adam all run in ``libvolpick_hip.so`` (``vp_train_*``); there is no CPU
-fallback.
+Logging and checkpoint files (Lightning) are not part of this package.  Forward (training-mode BatchNorm), loss, backward and
+Adam all run in ``libvolpick_hip.so`` (``vp_train_*``); there is no CPU fallback.
+
+The validation half of the loop runs there too: ``validate_batches`` / ``PhaseNetLit.validate_bank`` generate each validation
+batch from a bank, run the inference forward and reduce ``vector_cross_entropy`` in float64 on the GPU
+(``vp_validate_begin`` / ``_bank`` / ``_end``), and ``fit_bank`` feeds that loss to what the released config trains with
+(``configure_optimizers``, :187-219, and the callbacks of the reference's train.py:137-179): ``ReduceLROnPlateau`` (torch's
+arithmetic, restated here without torch), the weights of the lowest validation loss, and the early stop.
 """
 from __future__ import annotations
 
@@ -257,6 +262,103 @@ def _torch():
     return torch
 
 
+class ReduceLROnPlateau:
+    """The arithmetic of ``torch.optim.lr_scheduler.ReduceLROnPlateau(mode="min")`` on one learning rate, without torch:
+    ``step(metric, lr)`` returns the learning rate that follows ``lr``.  ``is_better`` (relative or absolute threshold
+    against the best metric so far), the count of bad epochs, the cooldown in which bad epochs are ignored, the reduction
+    ``max(lr * factor, min_lr)`` once the count exceeds ``patience``, and the rule that a reduction of at most ``eps`` is
+    skipped (the count and the cooldown restart all the same) are torch's, statement for statement."""
+
+    def __init__(self, factor=0.1, patience=10, min_lr=0.0, threshold=1e-4, threshold_mode="rel", cooldown=0, eps=1e-8):
+        if factor >= 1.0:
+            raise ValueError("Factor should be < 1.0.")
+        if threshold_mode not in ("rel", "abs"):
+            raise ValueError(f"threshold mode {threshold_mode} is unknown!")
+        self.factor, self.patience, self.min_lr = factor, patience, min_lr
+        self.threshold, self.threshold_mode, self.cooldown, self.eps = threshold, threshold_mode, cooldown, eps
+        self.best = float("inf")
+        self.num_bad_epochs = 0
+        self.cooldown_counter = 0
+        self.last_epoch = 0
+
+    def is_better(self, a, best):
+        if self.threshold_mode == "rel":
+            return a < best * (1.0 - self.threshold)
+        return a < best - self.threshold
+
+    @property
+    def in_cooldown(self):
+        return self.cooldown_counter > 0
+
+    def step(self, metric, lr):
+        current = float(metric)
+        self.last_epoch += 1
+        if self.is_better(current, self.best):
+            self.best = current
+            self.num_bad_epochs = 0
+        else:
+            self.num_bad_epochs += 1
+        if self.in_cooldown:
+            self.cooldown_counter -= 1
+            self.num_bad_epochs = 0  # bad epochs in the cooldown do not count
+        if self.num_bad_epochs > self.patience:
+            old_lr = float(lr)
+            new_lr = max(old_lr * self.factor, self.min_lr)
+            if old_lr - new_lr > self.eps:
+                lr = new_lr
+            self.cooldown_counter = self.cooldown
+            self.num_bad_epochs = 0
+        return lr
+
+
+LR_SCHEDULERS = {"ReduceLROnPlateau": ReduceLROnPlateau}
+VALIDATION_MODES = ("host", "device")
+
+
+def validate_batches(model, bank, batches, sigma, eps=1e-5, predictions=False):
+    """One validation pass on the GPU (``vp_validate_begin`` ... ``vp_validate_end``): every element of ``batches`` (plan
+    rows or augmented rows, any number per batch) is cut from ``bank``, run through ``model``'s inference path and scored
+    with ``vector_cross_entropy`` in float64 on the device; the host waits once, at the end.  Returns
+    ``(batch_losses, window_losses)``: a float64 array with one loss per batch and one with one per window, in order;
+    with ``predictions=True`` also the list of the batches' (B, 3, T) predictions (CUDA tensors)."""
+    from .generate import AUG_ROW, as_aug_rows, as_rows, label_rows, _norm
+
+    lib = _lib.load()
+    if model._device_index is None:
+        model.cuda(bank.device)
+    h = model._ensure_handle()
+    lrows = label_rows(model.labels).ctypes.data_as(C.POINTER(C.c_int))
+    preds, n_windows, n_batches = [], 0, 0
+    if predictions:
+        torch = _torch()
+        dev = torch.device("cuda", model._device_index)
+    _lib.check(lib.vp_validate_begin(h), "vp_validate_begin")
+    try:
+        for rows in batches:
+            aug = getattr(rows, "dtype", None) == AUG_ROW
+            rows = as_aug_rows(rows) if aug else as_rows(rows)
+            name = "vp_validate_bank_aug" if aug else "vp_validate_bank"
+            out = None
+            if predictions:
+                out = torch.empty((len(rows), 3, model.in_samples), dtype=torch.float32, device=dev)
+                torch.cuda.current_stream(dev).synchronize()  # whatever used this memory last on torch's stream is done
+                preds.append(out)
+            _lib.check(getattr(lib, name)(h, bank.handle, rows.ctypes.data_as(C.c_void_p), len(rows), float(sigma),
+                                          _norm(model.norm), lrows, float(eps), C.c_void_p(out.data_ptr()) if predictions else None),
+                       name)
+            n_batches += 1
+            n_windows += len(rows)
+    finally:
+        batch = np.empty(n_batches, np.float64)
+        window = np.empty(n_windows, np.float64)
+        nb, nw = C.c_longlong(), C.c_longlong()
+        rc = lib.vp_validate_end(h, batch.ctypes.data_as(C.POINTER(C.c_double)), n_batches, C.byref(nb),
+                                 window.ctypes.data_as(C.POINTER(C.c_double)), n_windows, C.byref(nw))
+    _lib.check(rc, "vp_validate_end")
+    assert (nb.value, nw.value) == (n_batches, n_windows)
+    return (batch, window, preds) if predictions else (batch, window)
+
+
 class PhaseNetLit:
     """The arithmetic of the reference's ``PhaseNetLit`` (models.py:108-185): Adam at ``lr`` with the
     500-step linear warm-up of ``optimizer_step``.  ``training_step(batch)`` takes
@@ -297,12 +399,9 @@ class PhaseNetLit:
         tr = self._ensure()
         return tr.step(batch["X"], batch["y"], self.learning_rate(tr.global_step), update=True)
 
-    def validation_step(self, batch, batch_idx=None):
-        """Loss in eval mode (running statistics), as Lightning's validation loop computes it: the current weights
-        go through the inference path (``vp_forward``).  The device plan is rebuilt only when an optimiser step
-        has happened since the last validation batch.  With EMA enabled (``enable_ema``) the EMA weights are the
-        ones validated, as the reference's EMA callback does with ``validate_original_weights=False``
-        (volpick/model/ema.py)."""
+    def _exported_model(self):
+        """``self.model`` on the GPU with the trainer's current weights (the EMA weights when EMA is on), exported only
+        when something has changed since the last export."""
         tr = self._ensure()
         # what the exported model depends on: the weights (global_step), the BatchNorm running statistics (every
         # step(), update or not, moves them) and which weights are validated (EMA on / off)
@@ -314,13 +413,39 @@ class PhaseNetLit:
             model = self.model
         if model._device_index is None:
             model.cuda(self._device)
+        return model
+
+    def validation_step(self, batch, batch_idx=None):
+        """Loss in eval mode (running statistics), as Lightning's validation loop computes it: the current weights
+        go through the inference path (``vp_forward``).  The device plan is rebuilt only when an optimiser step
+        has happened since the last validation batch.  With EMA enabled (``enable_ema``) the EMA weights are the
+        ones validated, as the reference's EMA callback does with ``validate_original_weights=False``
+        (volpick/model/ema.py)."""
+        model = self._exported_model()
         p = model(batch["X"])
         p = p.cpu().numpy() if hasattr(p, "cpu") else np.asarray(p)
         y = batch["y"]
         y = y.cpu().numpy() if hasattr(y, "cpu") else np.asarray(y)
         return vector_cross_entropy(p.astype(np.float64), y.astype(np.float64))
 
-    def fit_bank(self, bank, steps, batch_size=512, seed=0, val_bank=None, augment=None):
+    def validate_bank(self, val_bank, planner_or_rows, per_window=False):
+        """The validation loss of every batch of ``planner_or_rows`` -- a planner (its ``validation()`` batches), one array of
+        rows (one batch) or an iterable of such arrays -- on the GPU from end to end: the current weights (the EMA weights when EMA is on) are
+        exported as ``validation_step`` exports them, then one ``validate_batches`` pass generates, predicts and scores the
+        batches with a single host wait.  Returns the list of batch losses; with ``per_window=True``
+        ``(batch_losses, window_losses)``, the latter one float64 array over all windows in order."""
+        model = self._exported_model()
+        if hasattr(planner_or_rows, "validation"):
+            batches = planner_or_rows.validation()
+        elif getattr(getattr(planner_or_rows, "dtype", None), "names", None):  # one array of rows: one batch
+            batches = [planner_or_rows]
+        else:
+            batches = planner_or_rows
+        batch, window = validate_batches(model, val_bank, batches, self.sigma)
+        return (batch.tolist(), window) if per_window else batch.tolist()
+
+    def fit_bank(self, bank, steps, batch_size=512, seed=0, val_bank=None, augment=None, validation="host",
+                 lr_scheduler=None, lr_scheduler_args=None, keep_best=False, early_stop_patience=None):
         """``steps`` optimiser steps on batches generated on the GPU from ``bank`` (a ``WaveformBank``): epochs of
         ``WindowPlanner(bank, batch_size, seed=seed)`` (a new permutation each, last partial batch dropped), learning
         rate ``learning_rate(step)``, labels of width ``self.sigma``.  Returns the per-step losses and, with ``val_bank``,
@@ -329,9 +454,35 @@ class PhaseNetLit:
 
         ``augment`` (a ``generate.Augmentation``) adds the reference's stacking block, gap and second Normalize to the
         training and the validation batches (``AugmentedPlanner`` with its subsets of ``bank`` / ``val_bank``); ``None``
-        plans block 1 alone."""
+        plans block 1 alone.
+
+        ``validation="device"`` computes the same validation loss -- the unweighted mean of the batch losses -- with
+        ``validate_bank``: batches, predictions and losses stay on the GPU.
+
+        What the validation loss drives (the reference's ``configure_optimizers`` and ``train.py`` callbacks; all need
+        ``val_bank``):
+
+        * ``lr_scheduler="ReduceLROnPlateau"`` with ``lr_scheduler_args`` (``factor``, ``patience``, ``min_lr``, ...): stepped
+          with the validation loss after every validation (Lightning's ``interval="epoch"``, monitor ``val_loss``).  The
+          optimiser then has ONE learning rate that both the warm-up and the scheduler write: after optimiser step
+          ``k < WARMUP_STEPS`` the warm-up sets it to ``lr * (k + 1) / WARMUP_STEPS``, overwriting a reduction made
+          meanwhile; from step ``WARMUP_STEPS`` on only the scheduler changes it, by ``max(current * factor, min_lr)``.
+          The scheduler's state lasts for this call.
+        * ``keep_best=True`` keeps in ``self.best_state`` a host copy of the validated weights (``weights()``, the EMA
+          weights when EMA is on) of the strictly lowest validation loss so far (``ModelCheckpoint(mode="min")``).
+        * ``early_stop_patience=n`` ends the fit after ``n`` validations in a row without a new minimum.
+
+        ``self.history`` records the call: ``val_loss`` per validation, ``lr`` in force after each of them, ``best`` =
+        (validation index, global step, loss) of the minimum or ``None``, and ``stopped_early``."""
         from .generate import WindowPlanner
 
+        if validation not in VALIDATION_MODES:
+            raise ValueError(f"validation must be one of {VALIDATION_MODES}, got {validation!r}")
+        if lr_scheduler is not None and lr_scheduler not in LR_SCHEDULERS:
+            raise ValueError(f"lr_scheduler must be None or one of {sorted(LR_SCHEDULERS)}, got {lr_scheduler!r}")
+        if val_bank is None and (lr_scheduler is not None or keep_best or early_stop_patience is not None):
+            raise ValueError("lr_scheduler, keep_best and early_stop_patience follow the validation loss: they need val_bank")
+        scheduler = LR_SCHEDULERS[lr_scheduler](**(lr_scheduler_args or {})) if lr_scheduler is not None else None
         tr = self._ensure()
         in_samples = self.model.in_samples
         if augment is None:
@@ -347,14 +498,37 @@ class PhaseNetLit:
             val_planner = augment.planner(val_bank, batch_size, seed + 1, in_samples=in_samples, sigma=self.sigma,
                                           validation=True)
         losses, val_losses = [], []
+        self.history = history = {"val_loss": val_losses, "lr": [], "best": None, "stopped_early": False}
+        self.best_state = None
+        # the optimiser's learning rate, a state only where a scheduler writes it too
+        lr_now = self.learning_rate(tr.global_step)
+        since_best = 0
 
         def validate():
-            vl = [self.validation_step(val_bank.make_batch(rows, self.model, self.sigma)) for rows in val_planner.validation()]
+            nonlocal lr_now, since_best
+            if validation == "device":
+                vl = self.validate_bank(val_bank, val_planner)
+            else:
+                vl = [self.validation_step(val_bank.make_batch(rows, self.model, self.sigma)) for rows in val_planner.validation()]
             val_losses.append(float(np.mean(vl)))
+            if scheduler is not None:
+                lr_now = scheduler.step(val_losses[-1], lr_now)
+            history["lr"].append(lr_now if scheduler is not None else self.learning_rate(tr.global_step))
+            since_best += 1
+            if val_losses[-1] < (float("inf") if history["best"] is None else history["best"][2]):  # (never a NaN)
+                history["best"] = (len(val_losses) - 1, tr.global_step, val_losses[-1])
+                since_best = 0
+                if keep_best:
+                    self.best_state = tr.ema_weights() if self._ema else tr.weights()
+            if early_stop_patience is not None and since_best >= early_stop_patience:
+                history["stopped_early"] = True
 
-        while len(losses) < steps:
+        while len(losses) < steps and not history["stopped_early"]:
             for rows in planner.epoch():
-                losses.append(tr.step_bank(bank, rows, self.learning_rate(tr.global_step), self.sigma))
+                k = tr.global_step
+                losses.append(tr.step_bank(bank, rows, self.learning_rate(k) if scheduler is None else lr_now, self.sigma))
+                if scheduler is not None and k < self.WARMUP_STEPS:
+                    lr_now = self.lr * (k + 1) / float(self.WARMUP_STEPS)
                 if len(losses) == steps:
                     break
             else:
@@ -362,7 +536,8 @@ class PhaseNetLit:
                     validate()
         if val_planner is None:
             return losses
-        validate()
+        if not history["stopped_early"]:
+            validate()
         return losses, val_losses
 
     def enable_ema(self, decay=0.999):
