@@ -672,6 +672,59 @@ int vp_validate_end(vp_handle* h, double* batch_losses, long long cap, long long
                     long long cap_windows, long long* n_windows);
 
 /* ---------------------------------------------------------------------------------------------
+ * Pick-benchmark tasks 1-3: the per-window scores of the reference's predict_step (volpick/model/models.py:454-480 for
+ * PhaseNet, :881-906 for EQTransformer; driven by volpick/model/eval_taks123.py:20-166), reduced on the device.
+ *
+ * For window b and its border [lo[b], hi[b]) (lo = hi = NULL: [0, T), T = vp_in_samples(h)) one vp_predict_record:
+ *   det     VP_DET_ONE_MINUS_NOISE (PhaseNet; det_row is the noise row): max_t of the fp32 difference 1 - noise[t];
+ *           VP_DET_ROW (EQTransformer; det_row is the detection trace): max_t det[t];
+ *   p_max, s_max   the maxima of rows p_row and s_row inside the border;
+ *   p_arg, s_arg   their positions relative to lo[b].
+ * Maximum and argmax are torch's on the CPU: the lowest index among equal maxima; a NaN is above every number and the
+ * first NaN wins, so a NaN in a row makes that row's maximum NaN.  The maximum is the value AT that index: -0 and +0 compare
+ * equal, so a maximum of zero carries the sign of the first zero (torch's vectorised max may return either zero; nothing
+ * else differs from it, bit for bit).  No atomics: the same input gives the same bits.
+ * score_p_or_s of the reference is p_max / s_max; the library does not divide.  The caller forms the quotient on the host
+ * in float32 (correctly rounded, x / 0 = inf, 0 / 0 = NaN), as volpick_amd/evaluate.py does.
+ *
+ * vp_predict_windows reduces prob, (B, n_rows, T) fp32 in host or device memory (prob_mem), into out[0 .. B) (host) and
+ * returns when that is done: the loop of predict_step.  Checked on the host before any launch (VP_ERR_INVALID, `out`
+ * untouched): null h / prob / out, lo without hi or hi without lo, B < 1, n_rows outside [3, 64], a row outside
+ * [0, n_rows) or two rows equal, an unknown det_mode, a border with lo < 0, hi > T or hi <= lo (torch raises on the empty
+ * slice; an empty border is an error here, never a zero).
+ *
+ * A pass over a waveform bank, for PhaseNet and EQTransformer handles alike, shaped like vp_validate_*:
+ *   vp_predict_begin(h)        opens a pass: no windows yet.
+ *   vp_predict_bank(h, ...)    enqueues one batch on the handle's stream and returns: the B rows cut, demeaned and
+ *                              normalised exactly as vp_bank_make_batch does with `norm` (a kernel of its own that leaves
+ *                              the label work out) into scratch of the handle; the forward pass on it as
+ *                              vp_forward(preprocess = 0) runs it, in chunks of max_batch windows; the reduction above
+ *                              on rows det_row / p_row / s_row of the three outputs, with the handle's own rule
+ *                              (PhaseNet: VP_DET_ONE_MINUS_NOISE, det_row the noise row; EQTransformer: VP_DET_ROW,
+ *                              rows 0 / 1 / 2); the B records appended to a device array of the handle.  pred_out_dev,
+ *                              when not NULL, receives
+ *                              the (B, 3, T) probabilities the records were reduced from (device memory no other stream
+ *                              is using).  Any B >= 1.  Rows are checked as for vp_bank_make_batch and borders as above
+ *                              before anything is enqueued.
+ *   vp_predict_end(h, ...)     waits for the stream -- the pass's only host wait in the steady state -- and copies out up
+ *                              to `cap` records in the order enqueued; *n_windows is how many the pass holds.  Closes it.
+ * The host waits inside a pass where vp_validate_bank does (a larger batch than before, a growing result array, eight
+ * batches in flight).  `rows`, `lo` and `hi` may be reused as soon as the call returns.  The bank must live on the handle's
+ * device and stay alive until vp_predict_end.  One thread at a time per handle; the results of a pass do not depend on
+ * what ran before it (bit for bit).  A validation pass and a prediction pass of one handle may be open together. */
+enum { VP_DET_ONE_MINUS_NOISE = 0, VP_DET_ROW = 1 };
+typedef struct {
+  float det, p_max, s_max;
+  int32_t p_arg, s_arg;
+} vp_predict_record;
+int vp_predict_windows(vp_handle* h, const float* prob, int prob_mem, int B, int n_rows, int det_row, int p_row, int s_row,
+                       int det_mode, const int32_t* lo, const int32_t* hi, vp_predict_record* out);
+int vp_predict_begin(vp_handle* h);
+int vp_predict_bank(vp_handle* h, vp_bank* bank, const vp_plan_row* rows, const int32_t* lo, const int32_t* hi, int B,
+                    int norm, int det_row, int p_row, int s_row, float* pred_out_dev);
+int vp_predict_end(vp_handle* h, vp_predict_record* out, long long cap, long long* n_windows);
+
+/* ---------------------------------------------------------------------------------------------
  * Frequency index and signal-to-noise ratio of picks and bank traces, on the device: the trace_frequency_index,
  * trace_snr_db and trace_mean_snr_db columns the reference stores with every trace it writes (volpick/data/utils.py
  * freqency_index, calculate_snr; volpick/data/convert.py:222-270).  One vp_attr_row per pick or trace, planned on the

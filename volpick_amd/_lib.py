@@ -49,6 +49,11 @@ class VpPlanRow(C.Structure):
 
 
 VP_AUG_NONE, VP_AUG_BANK, VP_AUG_SELF = 0, 1, 2
+VP_DET_ONE_MINUS_NOISE, VP_DET_ROW = 0, 1
+
+
+class VpPredictRecord(C.Structure):
+    _fields_ = [("det", C.c_float), ("p_max", C.c_float), ("s_max", C.c_float), ("p_arg", C.c_int32), ("s_arg", C.c_int32)]
 
 
 class VpAugEvent(C.Structure):
@@ -311,6 +316,15 @@ SIGNATURES = {
         C.c_int, [_H, C.POINTER(C.c_double), C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(C.c_double), C.c_longlong,
                   C.POINTER(C.c_longlong)],
     ),
+    "vp_predict_windows": (
+        C.c_int,
+        [_H, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
+    "vp_predict_begin": (C.c_int, [_H]),
+    "vp_predict_bank": (
+        C.c_int, [_H, _H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p],
+    ),
+    "vp_predict_end": (C.c_int, [_H, C.c_void_p, C.c_longlong, C.POINTER(C.c_longlong)]),
     "vp_attributes": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.POINTER(VpAttrRow), C.c_int, C.c_void_p, C.c_void_p]),
     "vp_bank_attributes": (C.c_int, [_H, C.POINTER(VpAttrRow), C.c_int, C.c_void_p, C.c_void_p]),
     "vp_spectrogram": (

@@ -7,6 +7,7 @@
 #include "api_host.h"
 #include "batchgen.h"
 #include "net.h"
+#include "predict.h"
 #include "prepost.h"
 #include "valloss.h"
 
@@ -62,6 +63,28 @@ struct ValidationPass {
   }
 };
 
+// One prediction pass (vp_predict_begin ... vp_predict_end): the same for the windows, the probabilities and the records.
+// A ring slot holds the batch's plan rows, then its B lower and B upper borders.
+struct PredictPass {
+  bool open = false;
+  DevBuf<float> x, pred;  // (B, 3, T) each: the batch of the latest vp_predict_bank
+  vp::RowRing rows;
+  hipEvent_t ev[vp::RowRing::N] = {};
+  bool ev_used[vp::RowRing::N] = {};
+  long long launches = 0;
+  DevBuf<vp_predict_record> rec;  // the pass's results: n_windows records
+  long long n_windows = 0;
+  void release() {
+    x.release();
+    pred.release();
+    rec.release();
+    for (hipEvent_t& e : ev) {
+      if (e) (void)hipEventDestroy(e);
+      e = nullptr;
+    }
+  }
+};
+
 }  // namespace
 
 struct vp_handle {
@@ -92,6 +115,7 @@ struct vp_handle {
     int64_t fv = -1, lv = -1, nwin = 0;
   } slot[VP_MAX_INFLIGHT];
   ValidationPass val;
+  PredictPass prd;
 };
 
 namespace {
@@ -347,6 +371,7 @@ int vp_destroy(vp_handle* h) {
   h->d_tab.release();
   h->m_pick.release();
   h->val.release();
+  h->prd.release();
   for (auto& sl : h->slot) {
     sl.pick.release();
     if (sl.done) (void)hipEventDestroy(sl.done);
@@ -405,16 +430,17 @@ int vp_forward(vp_handle* h, const float* x, int x_mem, int B, int preprocess, f
 
 namespace {
 
-// Room for `need` values in a results array of a validation pass, its first `used` values kept.  Growing waits for the
-// stream: the launches in flight write into the old block.
-int grow_results(DevBuf<double>& b, size_t used, size_t need, hipStream_t s) {
+// Room for `need` values in a results array of a validation or prediction pass, its first `used` values kept.  Growing
+// waits for the stream: the launches in flight write into the old block.
+template <class T>
+int grow_results(DevBuf<T>& b, size_t used, size_t need, hipStream_t s) {
   if (need <= b.cap) return VP_OK;
   VP_HIP(hipStreamSynchronize(s));
-  DevBuf<double> old = b;
-  b = DevBuf<double>();
+  DevBuf<T> old = b;
+  b = DevBuf<T>();
   const int rc = b.reserve(std::max(need, 2 * old.cap));
   hipError_t e = hipSuccess;
-  if (rc == VP_OK && used) e = hipMemcpy(b.p, old.p, used * sizeof(double), hipMemcpyDeviceToDevice);
+  if (rc == VP_OK && used) e = hipMemcpy(b.p, old.p, used * sizeof(T), hipMemcpyDeviceToDevice);
   old.release();
   if (rc != VP_OK) return rc;
   VP_HIP(e);
@@ -527,6 +553,134 @@ int vp_validate_end(vp_handle* h, double* batch_losses, long long cap, long long
   if (nw > 0) VP_HIP(hipMemcpyAsync(per_window, v.window.p, (size_t)nw * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   VP_HIP(hipStreamSynchronize(h->stream));
   if (n_batches) *n_batches = v.n_batches;
+  if (n_windows) *n_windows = v.n_windows;
+  v.open = false;
+  return VP_OK;
+}
+
+// The counterpart of the loop in the reference's predict_step (volpick/model/models.py:454-480, :881-906).
+int vp_predict_windows(vp_handle* h, const float* prob, int prob_mem, int B, int n_rows, int det_row, int p_row, int s_row,
+                       int det_mode, const int32_t* lo, const int32_t* hi, vp_predict_record* out) {
+  VP_REQUIRE(h && prob && out, "vp_predict_windows: null argument");
+  VP_REQUIRE(prob_mem == VP_MEM_HOST || prob_mem == VP_MEM_DEVICE, "vp_predict_windows: prob_mem %d", prob_mem);
+  VP_REQUIRE(((uintptr_t)prob & 3) == 0, "vp_predict_windows: prob must be 4-byte aligned");
+  const int T = h->net.in_samples;
+  int rc = vp::predict_check(B, n_rows, T, det_row, p_row, s_row, det_mode, lo, hi, "vp_predict_windows");
+  if (rc != VP_OK) return rc;
+  VP_HIP(hipSetDevice(h->device));
+  const size_t n_prob = (size_t)B * n_rows * T;
+  // scratch layout (floats): [prob copy if host][lo B][hi B][records B], every piece a multiple of 4 bytes
+  constexpr size_t rec_floats = sizeof(vp_predict_record) / sizeof(float);
+  static_assert(sizeof(vp_predict_record) % sizeof(float) == 0 && alignof(vp_predict_record) <= alignof(float), "record layout");
+  const size_t need = (prob_mem == VP_MEM_HOST ? n_prob : 0) + (size_t)B * (2 + rec_floats);
+  if ((rc = h->d_in.reserve(std::max(need, (size_t)h->net.max_batch * 3 * T))) != VP_OK) return rc;
+  float* p = h->d_in.p;
+  vp::PredictArgs a{};
+  a.prob = prob;
+  if (prob_mem == VP_MEM_HOST) {
+    VP_HIP(hipMemcpyAsync(p, prob, n_prob * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    a.prob = p;
+    p += n_prob;
+  }
+  int* d_lo = reinterpret_cast<int*>(p);
+  int* d_hi = d_lo + B;
+  a.out = reinterpret_cast<vp_predict_record*>(d_hi + B);
+  if (lo) {
+    VP_HIP(hipMemcpyAsync(d_lo, lo, B * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    VP_HIP(hipMemcpyAsync(d_hi, hi, B * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    a.lo = d_lo, a.hi = d_hi;
+  }
+  a.B = B, a.n_rows = n_rows, a.T = T;
+  a.det_row = det_row, a.p_row = p_row, a.s_row = s_row, a.det_mode = det_mode;
+  if ((rc = vp::predict_launch(a, h->stream)) != VP_OK) return rc;
+  VP_HIP(hipMemcpyAsync(out, a.out, (size_t)B * sizeof(vp_predict_record), hipMemcpyDeviceToHost, h->stream));
+  VP_HIP(hipStreamSynchronize(h->stream));
+  return VP_OK;
+}
+
+int vp_predict_begin(vp_handle* h) {
+  VP_REQUIRE(h != nullptr, "vp_predict_begin: null handle");
+  h->prd.open = true;
+  h->prd.n_windows = 0;  // (launches of an abandoned pass run ahead of this one's on the same stream)
+  return VP_OK;
+}
+
+// generate -> forward in chunks of max_batch -> the records of all B windows, appended.
+int vp_predict_bank(vp_handle* h, vp_bank* bank, const vp_plan_row* rows, const int32_t* lo, const int32_t* hi, int B,
+                    int norm, int det_row, int p_row, int s_row, float* pred_out_dev) {
+  VP_REQUIRE(h && bank, "vp_predict_bank: null argument");
+  PredictPass& v = h->prd;
+  VP_REQUIRE(v.open, "vp_predict_bank: no pass is open (vp_predict_begin)");
+  const vp::Bank& bk = *reinterpret_cast<const vp::Bank*>(bank);
+  VP_REQUIRE(bk.device == h->device, "vp_predict_bank: bank on device %d, handle on device %d", bk.device, h->device);
+  vp::Net& net = h->net;
+  const int T = net.in_samples;
+  const int det_mode = net.model_kind == VP_MODEL_PHASENET ? VP_DET_ONE_MINUS_NOISE : VP_DET_ROW;
+  int rc = vp::bank_check_windows(bk, rows, B, T, norm);
+  if (rc == VP_OK) rc = vp::predict_check(B, net.n_out, T, det_row, p_row, s_row, det_mode, lo, hi, "vp_predict_bank");
+  if (rc != VP_OK) return rc;
+  VP_HIP(hipSetDevice(h->device));
+
+  // ---- room for the batch, its rows and borders and its records: nothing is enqueued before all of it stands ---------------
+  const size_t w = (size_t)net.n_out * T, row_bytes = (size_t)B * sizeof(vp_plan_row);
+  const size_t bytes = row_bytes + (lo ? (size_t)2 * B * sizeof(int32_t) : 0);
+  static_assert(sizeof(vp_plan_row) % alignof(int32_t) == 0, "the borders follow the rows in a ring slot");
+  if (!v.ev[0])
+    for (hipEvent_t& e : v.ev) VP_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  if ((size_t)B * w > v.x.cap || bytes > v.rows.cap) {
+    VP_HIP(hipStreamSynchronize(h->stream));  // launches in flight read the old blocks; every ring slot is idle afterwards
+    for (DevBuf<float>* b : {&v.x, &v.pred})
+      if ((rc = b->reserve((size_t)B * w)) != VP_OK) return rc;
+    if ((rc = v.rows.reserve(std::max(bytes, (size_t)net.max_batch * (sizeof(vp_plan_row) + 2 * sizeof(int32_t))))) != VP_OK)
+      return rc;
+  }
+  if ((rc = grow_results(v.rec, (size_t)v.n_windows, (size_t)v.n_windows + B, h->stream)) != VP_OK) return rc;
+  const int slot = (int)(v.launches % vp::RowRing::N);
+  if (v.ev_used[slot]) VP_HIP(hipEventSynchronize(v.ev[slot]));  // (eight launches back: long complete in the steady state)
+
+  // ---- generate -> forward -> reduce ---------------------------------------------------------------------------------------
+  char* hs = static_cast<char*>(v.rows.host[slot]);
+  char* ds = static_cast<char*>(v.rows.dev[slot]);
+  memcpy(hs, rows, row_bytes);
+  if (lo) {
+    memcpy(hs + row_bytes, lo, (size_t)B * sizeof(int32_t));
+    memcpy(hs + row_bytes + (size_t)B * sizeof(int32_t), hi, (size_t)B * sizeof(int32_t));
+  }
+  VP_HIP(hipMemcpyAsync(ds, hs, bytes, hipMemcpyHostToDevice, h->stream));
+  if ((rc = vp::bank_launch_windows(bk, reinterpret_cast<const vp_plan_row*>(ds), B, T, norm, v.x.p, h->stream)) != VP_OK) return rc;
+  for (int b0 = 0; b0 < B; b0 += net.max_batch) {
+    const int nb = std::min(net.max_batch, B - b0);
+    const OutputRedirect to_pred(net, v.pred.p + (size_t)b0 * w);
+    if ((rc = run_batch(h, pre_args(h, v.x.p + (size_t)b0 * w, 1, 0, 0, 0, 0), nb)) != VP_OK) return rc;
+  }
+  vp::PredictArgs a{};
+  a.prob = v.pred.p;
+  a.B = B, a.n_rows = net.n_out, a.T = T;
+  a.det_row = det_row, a.p_row = p_row, a.s_row = s_row, a.det_mode = det_mode;
+  if (lo) {
+    a.lo = reinterpret_cast<const int*>(ds + row_bytes);
+    a.hi = a.lo + B;
+  }
+  a.out = v.rec.p + v.n_windows;
+  if ((rc = vp::predict_launch(a, h->stream)) != VP_OK) return rc;
+  VP_HIP(hipEventRecord(v.ev[slot], h->stream));
+  v.ev_used[slot] = true;
+  ++v.launches;
+  if (pred_out_dev)
+    VP_HIP(hipMemcpyAsync(pred_out_dev, v.pred.p, (size_t)B * w * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+  v.n_windows += B;
+  return VP_OK;
+}
+
+int vp_predict_end(vp_handle* h, vp_predict_record* out, long long cap, long long* n_windows) {
+  VP_REQUIRE(h != nullptr, "vp_predict_end: null handle");
+  PredictPass& v = h->prd;
+  VP_REQUIRE(v.open, "vp_predict_end: no pass is open (vp_predict_begin)");
+  VP_REQUIRE(cap >= 0 && (cap == 0 || out), "vp_predict_end: null output array");
+  VP_HIP(hipSetDevice(h->device));
+  const long long nw = std::min(cap, v.n_windows);
+  if (nw > 0) VP_HIP(hipMemcpyAsync(out, v.rec.p, (size_t)nw * sizeof(vp_predict_record), hipMemcpyDeviceToHost, h->stream));
+  VP_HIP(hipStreamSynchronize(h->stream));
   if (n_windows) *n_windows = v.n_windows;
   v.open = false;
   return VP_OK;

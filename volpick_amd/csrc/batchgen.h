@@ -41,6 +41,9 @@ int bank_check(const Bank& bk, const vp_plan_row* rows, int B, int T, float sigm
 // x, y: (B, 3, T) fp32 on the bank's device.  Arguments already checked by bank_check.
 int bank_launch(const Bank& bk, const vp_plan_row* rows_dev, int B, int T, float sigma, int norm, const int* label_rows,
                 float* x, float* y, hipStream_t s);
+// x alone -- the rows cut, demeaned and normalised exactly as bank_launch does, no labels (vp_predict_bank).
+int bank_check_windows(const Bank& bk, const vp_plan_row* rows, int B, int T, int norm);
+int bank_launch_windows(const Bank& bk, const vp_plan_row* rows_dev, int B, int T, int norm, float* x, hipStream_t s);
 // The same for augmented rows (vp_bank_make_batch_aug): bank_check's arguments plus every field of every vp_aug_row.
 int bank_check_aug(const Bank& bk, const vp_aug_row* rows, int B, int T, float sigma, int norm, const int* label_rows);
 int bank_launch_aug(const Bank& bk, const vp_aug_row* rows_dev, int B, int T, float sigma, int norm, const int* label_rows,

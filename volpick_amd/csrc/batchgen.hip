@@ -164,12 +164,9 @@ __device__ __forceinline__ void phase_labels(const double o[4], const bool has[4
     }
 }
 
-__global__ __launch_bounds__(GEN_NTH) void bank_batch_kernel(const GenArgs a) {
-  __shared__ GenShared sh;
-  const int w = blockIdx.x, tid = threadIdx.x;
+// Window w of the batch: row r cut, demeaned and normalised into a.x.
+__device__ __forceinline__ void write_window(const GenArgs& a, const vp_plan_row& r, int w, int tid, GenShared& sh) {
   const int T = a.T;
-  const vp_plan_row r = a.rows[w];
-
   float v[3][GEN_MAXE];
   gather_window(a, r, tid, v);
   double mean[3], den[3];
@@ -183,6 +180,20 @@ __global__ __launch_bounds__(GEN_NTH) void bank_batch_kernel(const GenArgs a) {
       if (t < T) xw[(long long)c * T + t] = (float)(((double)v[c][k] - mean[c]) / den[c]);
     }
   }
+}
+
+// x alone, for callers that need no labels (vp_predict_bank): a.y, a.onset, a.sigma and the label rows are not read.
+__global__ __launch_bounds__(GEN_NTH) void bank_window_kernel(const GenArgs a) {
+  __shared__ GenShared sh;
+  write_window(a, a.rows[blockIdx.x], blockIdx.x, threadIdx.x, sh);
+}
+
+__global__ __launch_bounds__(GEN_NTH) void bank_batch_kernel(const GenArgs a) {
+  __shared__ GenShared sh;
+  const int w = blockIdx.x, tid = threadIdx.x;
+  const int T = a.T;
+  const vp_plan_row r = a.rows[w];
+  write_window(a, r, w, tid, sh);
 
   double o[4];
   bool has[4];
@@ -469,6 +480,18 @@ int bank_check(const Bank& bk, const vp_plan_row* rows, int B, int T, float sigm
   return VP_OK;
 }
 
+int bank_check_windows(const Bank& bk, const vp_plan_row* rows, int B, int T, int norm) {
+  VP_REQUIRE(rows, "bank windows: null rows");
+  VP_REQUIRE(B >= 1, "bank windows: B = %d", B);
+  VP_REQUIRE(T >= 1 && T <= GEN_MAX_T, "bank windows: T = %d outside [1, %d]", T, GEN_MAX_T);
+  VP_REQUIRE(norm == VP_NORM_PEAK || norm == VP_NORM_STD, "bank windows: norm %d is neither VP_NORM_PEAK nor VP_NORM_STD", norm);
+  for (int b = 0; b < B; ++b) {
+    const int rc = row_check(bk, rows[b], b, "row");
+    if (rc != VP_OK) return rc;
+  }
+  return VP_OK;
+}
+
 namespace {
 
 int launch(void (*kernel)(GenArgs), const char* name, const Bank& bk, const vp_plan_row* rows_dev, const vp_aug_row* aug_dev,
@@ -502,6 +525,11 @@ int launch(void (*kernel)(GenArgs), const char* name, const Bank& bk, const vp_p
 int bank_launch(const Bank& bk, const vp_plan_row* rows_dev, int B, int T, float sigma, int norm, const int* label_rows,
                 float* x, float* y, hipStream_t s) {
   return launch(bank_batch_kernel, "bank_batch_kernel", bk, rows_dev, nullptr, B, T, sigma, norm, label_rows, x, y, s);
+}
+
+int bank_launch_windows(const Bank& bk, const vp_plan_row* rows_dev, int B, int T, int norm, float* x, hipStream_t s) {
+  const int unused_label_rows[3] = {0, 1, 2};
+  return launch(bank_window_kernel, "bank_window_kernel", bk, rows_dev, nullptr, B, T, 1.f, norm, unused_label_rows, x, nullptr, s);
 }
 
 int bank_check_aug(const Bank& bk, const vp_aug_row* rows, int B, int T, float sigma, int norm, const int* label_rows) {

@@ -34,7 +34,9 @@ constant here:
 * ``SELECTION_FIRST`` -- which onset ``WindowAroundSample(selection="first")`` centres on;
 * ``GAUSSIAN_NOISE_SCALE`` -- what ``GaussianNoise`` scales its draw by;
 * ``GAP_DRAW`` and ``GAP_NOISE_ROW`` -- how ``AddGap`` draws its gap and which label row it sets to 1 there;
-* ``EVENT_END_INDEX`` -- how a non-integer first-event end becomes a sample index.
+* ``EVENT_END_INDEX`` -- how a non-integer first-event end becomes a sample index;
+* ``STEERED_CENTRE``, ``STEERED_CLAMP`` and ``STEERED_SHORT_TRACE`` -- where ``SteeredWindow(strategy="pad")`` puts the
+  window around its target (:class:`SteeredPlanner`, the evaluation windows of the pick-benchmark tasks 1-3).
 
 Out of scope: array rotation (``rotate_array`` defaults to False and no config sets it).
 """
@@ -58,6 +60,10 @@ GAP_NOISE_ROW = "model"     # AddGap: labels in the gap 0, the model's noise row
                             # default -1 is the last row, which is the noise row of volpick's PSN labels
 EVENT_END_INDEX = np.trunc  # the first-event end e as a sample index: int(e), toward zero; x[:, min(T, int(e)):] = 0 then
                             # follows numpy slicing, a negative index counting from the end
+STEERED_CENTRE = "floor"    # SteeredWindow: p0 = start - (windowlen - (end - start)) // 2 -- an odd remainder's extra sample
+                            # lies behind the target
+STEERED_CLAMP = True        # ... then p0 is moved into [0, L - windowlen]: a window inside the trace, not zeros beside it
+STEERED_SHORT_TRACE = "pad_end"  # a trace shorter than windowlen: p0 = 0, zeros behind the trace, borders as given
 
 # the reference's phase_dict (volpick/model/models.py:26-31): metadata column -> phase, two columns per phase
 PHASE_DICT = {
@@ -320,6 +326,56 @@ class WindowPlanner:
         n, B = len(self.lengths), self.batch_size
         for i in range(0, n, B):
             yield self.plan(np.arange(i, min(i + B, n)))
+
+
+class SteeredPlanner:
+    """``SteeredWindow(windowlen=in_samples, strategy="pad")`` as plan rows: the evaluation windows of the pick-benchmark
+    tasks 1-3 (the reference's ``get_eval_augmentations``, driven by the task targets' ``start_sample`` / ``end_sample``).
+
+    ``bank`` is anything with ``lengths`` (N,).  Per target ``(trace, start, end)`` with ``w = end - start``:
+    ``p0 = start - (in_samples - w) // 2``, moved into ``[0, L - in_samples]``; a trace shorter than the window is taken
+    from ``p0 = 0`` and zero-filled behind its end.  The row is ``(trace, start=p0, lo=0, hi=L)`` and the window border
+    ``(start - p0, end - p0)``: the target's samples, local to the window.  ``ValueError`` for a target longer than the
+    window, one that is empty or starts before the trace, and one whose end no window can hold (past the trace's end, or
+    past ``in_samples`` on a short trace)."""
+
+    def __init__(self, bank, in_samples):
+        self.lengths = np.asarray(bank.lengths, np.int64)
+        self.in_samples = int(in_samples)
+        if self.in_samples < 1:
+            raise ValueError("in_samples must be >= 1")
+
+    def plan(self, targets):
+        """``(rows, window_borders)``: a PLAN_ROW array and an (n, 2) int32 array, in the targets' order.  ``targets``: a
+        DataFrame or a dict of arrays with ``trace`` (bank index), ``start_sample`` and ``end_sample``."""
+        assert STEERED_CENTRE == "floor" and STEERED_CLAMP and STEERED_SHORT_TRACE == "pad_end"
+        trace = np.asarray(targets["trace"], np.int64)
+        start = np.asarray(targets["start_sample"])
+        end = np.asarray(targets["end_sample"])
+        if (start != np.floor(start)).any() or (end != np.floor(end)).any():
+            raise ValueError("start_sample / end_sample must be whole samples (resampled targets are out of scope)")
+        start, end = start.astype(np.int64), end.astype(np.int64)
+        if ((trace < 0) | (trace >= len(self.lengths))).any():
+            raise ValueError(f"target traces outside [0, {len(self.lengths)})")
+        T = self.in_samples
+        L = self.lengths[trace]
+        w = end - start
+        if (w > T).any():
+            i = int(np.flatnonzero(w > T)[0])
+            raise ValueError(f"target {i}: [{start[i]}, {end[i]}) is longer than the window of {T} samples")
+        if ((w < 1) | (start < 0)).any():
+            i = int(np.flatnonzero((w < 1) | (start < 0))[0])
+            raise ValueError(f"target {i}: [{start[i]}, {end[i]}) is empty or starts before the trace")
+        p0 = np.clip(start - (T - w) // 2, 0, np.maximum(L - T, 0))
+        if (end - p0 > T).any():
+            i = int(np.flatnonzero(end - p0 > T)[0])
+            raise ValueError(f"target {i}: [{start[i]}, {end[i]}) ends behind every window of trace {trace[i]} ({L[i]} samples)")
+        rows = np.zeros(len(trace), PLAN_ROW)
+        rows["trace"] = trace
+        rows["start"] = p0
+        rows["hi"] = L
+        borders = np.stack([start - p0, end - p0], axis=1).astype(np.int32)
+        return rows, borders
 
 
 def trace_subsets(metadata, column="source_type", noise_value="noise"):
