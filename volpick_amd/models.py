@@ -708,7 +708,8 @@ class _ClassifyRun:
     """One classify() call: the station blocks on their way through the device and the triggers back so far.  A block takes
     one of three routes, each an ``add_*`` (issue its work) and a ``drain_*`` (wait, scan, emit).  The ORDER in which they
     issue uploads, submits and collects is the optimisation (tests/test_gpu_classify_calls.py pins it).  The short routes
-    use submit slot 0 of the contexts the long route fills: each drains the long route first, the long route the host route.
+    use submit slot 0 of the contexts the long route fills: each drains the long route first, the long route the host route,
+    and a resident chunk the host route before it goes.
 
     Triggers stay COLUMNS (numpy) from the library's result arrays to the sorted record lists: times in integer
     microseconds, one stable lexsort by Pick / Detection order (start time, trace id, phase), and the records themselves
@@ -777,6 +778,8 @@ class _ClassifyRun:
 
     def drain_resident(self):
         m = self.model
+        if self.chunk:  # a chunk that fills up in mid-stream finds host blocks in flight on context 0, whose slots it needs
+            self.drain_host()
         if len(self.chunk) == 1:
             self._collect(self.chunk[0], m._submit_block(0, self.chunk[0]["data"], self.args, self.specs, 8192))
         elif self.chunk:

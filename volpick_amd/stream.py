@@ -166,7 +166,8 @@ class Trace:
             self._data = None
             n = int(device_data.shape[0])
         else:
-            self._data = np.asarray(data if data is not None else np.zeros(0, dtype=np.float32))
+            # (asanyarray: a masked array -- what a gappy merge leaves -- keeps its mask, as in an ObsPy trace)
+            self._data = np.asanyarray(data if data is not None else np.zeros(0, dtype=np.float32))
             n = len(self._data)
         self.stats = Stats(header)
         self.stats["npts"] = n
@@ -179,7 +180,7 @@ class Trace:
 
     @data.setter
     def data(self, value):
-        self._data = np.asarray(value)
+        self._data = np.asanyarray(value)
         self._dev = None
         self.stats["npts"] = len(self._data)
 
