@@ -725,6 +725,59 @@ int vp_predict_bank(vp_handle* h, vp_bank* bank, const vp_plan_row* rows, const 
 int vp_predict_end(vp_handle* h, vp_predict_record* out, long long cap, long long* n_windows);
 
 /* ---------------------------------------------------------------------------------------------
+ * Pick-benchmark task 0: the threshold sweep of the reference's eval_task0 (volpick/model/eval_taks0.py:370-825; its
+ * evaluate(), :20-200, runs the model once per threshold), every threshold from ONE set of probabilities on the device.
+ *
+ * For window b, its border [lo[b], hi[b]) (lo = hi = NULL: [0, T), T = vp_in_samples(h)), phase ph (0: row p_row, 1: row
+ * s_row) and threshold pair j of NT, with x = prob[b][row][lo[b] .. hi[b]):
+ *   count[(b * 2 + ph) * NT + j]             the triggers of ObsPy's trigger_onset(x, thr_on[j], thr_off[j]): one per run of
+ *                                            consecutive samples > thr_off[j] that holds a sample > thr_on[j].  A run is cut
+ *                                            at the border on both sides.  The count may exceed K.
+ *   peak[((b * 2 + ph) * NT + j) * K + i]    trigger i < min(count, K), in sample order: the argmax of the span [first
+ *                                            sample > thr_on[j] of the run, run end], relative to lo[b]; the lowest index
+ *                                            among equal maxima.  The first K triggers are kept; slots i >= count hold -1.
+ *   value[the same index]                    the maximum at peak; slots i >= count hold 0.  value may be NULL: nothing is
+ *                                            computed into or copied out of it (the reference never saves the scores).
+ * Thresholds are fp32 and every comparison is a strict fp32 `>`, vp_pick_windows' contract: a sample equal to a threshold
+ * is below it, and a NaN ends a run and is never a maximum.  The reference calls this with thr_off = thr_on / 2.
+ * thr_off[j] > thr_on[j] -- the corner vp_pick_host resolves the way ObsPy's loop happens to -- is REFUSED here.
+ * Slots are numbered by counts and an exclusive scan in sample order, without atomics: entries ascend and the same input
+ * gives the same bits.  One launch covers both phases and all NT thresholds and reads each border once.
+ *
+ * vp_sweep_windows sweeps prob, (B, n_rows, T) fp32 in host or device memory (prob_mem), into the host arrays count
+ * [B][2][NT], peak [B][2][NT][K] and value (the same shape, or NULL) and returns when that is done.  Checked on the host
+ * before anything is enqueued (VP_ERR_INVALID, the outputs untouched): null h / prob / thr_on / thr_off / count / peak, lo
+ * without hi or hi without lo, a border with lo < 0, hi > T or hi <= lo, B < 1, NT outside [1, 32], K outside [1, 64],
+ * n_rows outside [2, 64], a row outside [0, n_rows), p_row == s_row, a threshold that is not finite, thr_off[j] >
+ * thr_on[j], and T above VP_SWEEP_MAX_T, the border the kernel's LDS row holds.
+ *
+ * A pass over a waveform bank, shaped like vp_predict_*:
+ *   vp_sweep_begin(h, ...)    opens a pass with its NT threshold pairs, K and whether values are kept (keep_values != 0):
+ *                             fixed for the pass, so that its results have one stride.  Checked as above.
+ *   vp_sweep_bank(h, ...)     enqueues one batch on the handle's stream and returns: the B rows cut and normalised and
+ *                             the forward pass run in chunks of max_batch exactly as vp_predict_bank does, then ONE sweep
+ *                             launch on rows p_row / s_row; the results appended to device arrays of the handle.
+ *                             pred_out_dev, when not NULL, receives the (B, 3, T) probabilities that were swept.  Any
+ *                             B >= 1.  Rows are checked as for vp_bank_make_batch, the rest as above, before anything is
+ *                             enqueued; a refused batch leaves the pass as it was.
+ *   vp_sweep_end(h, ...)      waits for the stream -- the pass's only host wait in the steady state -- and copies out the
+ *                             results of up to cap_windows windows in the order enqueued: count [n][2][NT], peak
+ *                             [n][2][NT][K] and, when not NULL (the pass must have kept them), value.  *n_windows is how
+ *                             many the pass holds.  Closes it.
+ * The host waits inside a pass where vp_predict_bank does.  `rows`, `lo`, `hi` and the thresholds may be reused as soon as
+ * the call returns.  The bank must live on the handle's device and stay alive until vp_sweep_end.  One thread at a time per
+ * handle; the results of a pass do not depend on what ran before it (bit for bit).  A sweep pass may be open beside a
+ * prediction pass and a validation pass of the same handle: each has its own scratch and results. */
+#define VP_SWEEP_MAX_T 6400
+int vp_sweep_windows(vp_handle* h, const float* prob, int prob_mem, int B, int n_rows, int p_row, int s_row, const int32_t* lo,
+                     const int32_t* hi, const float* thr_on, const float* thr_off, int NT, int K, int32_t* count,
+                     int32_t* peak, float* value);
+int vp_sweep_begin(vp_handle* h, const float* thr_on, const float* thr_off, int NT, int K, int keep_values);
+int vp_sweep_bank(vp_handle* h, vp_bank* bank, const vp_plan_row* rows, const int32_t* lo, const int32_t* hi, int B, int norm,
+                  int p_row, int s_row, float* pred_out_dev);
+int vp_sweep_end(vp_handle* h, int32_t* count, int32_t* peak, float* value, long long cap_windows, long long* n_windows);
+
+/* ---------------------------------------------------------------------------------------------
  * Frequency index and signal-to-noise ratio of picks and bank traces, on the device: the trace_frequency_index,
  * trace_snr_db and trace_mean_snr_db columns the reference stores with every trace it writes (volpick/data/utils.py
  * freqency_index, calculate_snr; volpick/data/convert.py:222-270).  One vp_attr_row per pick or trace, planned on the

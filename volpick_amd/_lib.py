@@ -325,6 +325,14 @@ SIGNATURES = {
         C.c_int, [_H, _H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p],
     ),
     "vp_predict_end": (C.c_int, [_H, C.c_void_p, C.c_longlong, C.POINTER(C.c_longlong)]),
+    "vp_sweep_windows": (
+        C.c_int,
+        [_H, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+         C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
+    "vp_sweep_begin": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "vp_sweep_bank": (C.c_int, [_H, _H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "vp_sweep_end": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.POINTER(C.c_longlong)]),
     "vp_attributes": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.POINTER(VpAttrRow), C.c_int, C.c_void_p, C.c_void_p]),
     "vp_bank_attributes": (C.c_int, [_H, C.POINTER(VpAttrRow), C.c_int, C.c_void_p, C.c_void_p]),
     "vp_spectrogram": (

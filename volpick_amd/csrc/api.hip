@@ -9,6 +9,7 @@
 #include "net.h"
 #include "predict.h"
 #include "prepost.h"
+#include "sweep.h"
 #include "valloss.h"
 
 namespace vp {
@@ -63,25 +64,53 @@ struct ValidationPass {
   }
 };
 
-// One prediction pass (vp_predict_begin ... vp_predict_end): the same for the windows, the probabilities and the records.
-// A ring slot holds the batch's plan rows, then its B lower and B upper borders.
-struct PredictPass {
-  bool open = false;
-  DevBuf<float> x, pred;  // (B, 3, T) each: the batch of the latest vp_predict_bank
+// What a pass that cuts its windows from a bank keeps from batch to batch (window_batch below): the windows and the
+// probabilities of the latest batch, (B, 3, T) each, and the staging ring.  A ring slot holds the batch's plan rows, then
+// its B lower and B upper borders.
+struct WindowBatches {
+  DevBuf<float> x, pred;
   vp::RowRing rows;
   hipEvent_t ev[vp::RowRing::N] = {};
   bool ev_used[vp::RowRing::N] = {};
-  long long launches = 0;
-  DevBuf<vp_predict_record> rec;  // the pass's results: n_windows records
-  long long n_windows = 0;
+  long long launches = 0;  // over the handle's life: the ring outlives a pass
   void release() {
     x.release();
     pred.release();
-    rec.release();
     for (hipEvent_t& e : ev) {
       if (e) (void)hipEventDestroy(e);
       e = nullptr;
     }
+  }
+};
+
+// One prediction pass (vp_predict_begin ... vp_predict_end): its batches and its records.
+struct PredictPass {
+  bool open = false;
+  WindowBatches io;
+  DevBuf<vp_predict_record> rec;  // the pass's results: n_windows records
+  long long n_windows = 0;
+  void release() {
+    io.release();
+    rec.release();
+  }
+};
+
+// One sweep pass (vp_sweep_begin ... vp_sweep_end): its batches, the thresholds and K it was opened with, and per window
+// 2 NT counts and 2 NT K peaks (and values, when kept).
+struct SweepPass {
+  bool open = false;
+  WindowBatches io;
+  int NT = 0, K = 0;
+  bool keep_values = false;
+  float thr_on[vp::SW_MAX_NT] = {}, thr_off[vp::SW_MAX_NT] = {};
+  DevBuf<int32_t> count, peak;
+  DevBuf<float> value;
+  long long n_windows = 0;
+  void release() {
+    io.release();
+    count.release();
+    peak.release();
+    value.release();
   }
 };
 
@@ -116,6 +145,7 @@ struct vp_handle {
   } slot[VP_MAX_INFLIGHT];
   ValidationPass val;
   PredictPass prd;
+  SweepPass swp;
 };
 
 namespace {
@@ -372,6 +402,7 @@ int vp_destroy(vp_handle* h) {
   h->m_pick.release();
   h->val.release();
   h->prd.release();
+  h->swp.release();
   for (auto& sl : h->slot) {
     sl.pick.release();
     if (sl.done) (void)hipEventDestroy(sl.done);
@@ -514,6 +545,57 @@ int validate_batch(vp_handle* h, vp_bank* bank, const Row* rows, int B, float si
   return VP_OK;
 }
 
+// One batch of a pass over a bank (vp_predict_bank, vp_sweep_bank), arguments already checked: room for the batch, its
+// rows and borders and -- room_for_results() -- its results, nothing enqueued before all of it stands; then the rows
+// staged, the B windows cut and normalised, the forward pass in chunks of max_batch, and reduce(pred, lo_dev, hi_dev) on
+// the (B, 3, T) probabilities (the borders null when there are none).
+template <class Room, class Reduce>
+int window_batch(vp_handle* h, WindowBatches& v, const vp::Bank& bk, const vp_plan_row* rows, const int32_t* lo,
+                 const int32_t* hi, int B, int norm, float* pred_out_dev, Room room_for_results, Reduce reduce) {
+  vp::Net& net = h->net;
+  const int T = net.in_samples;
+  int rc;
+  const size_t w = (size_t)net.n_out * T, row_bytes = (size_t)B * sizeof(vp_plan_row);
+  const size_t bytes = row_bytes + (lo ? (size_t)2 * B * sizeof(int32_t) : 0);
+  static_assert(sizeof(vp_plan_row) % alignof(int32_t) == 0, "the borders follow the rows in a ring slot");
+  if (!v.ev[0])
+    for (hipEvent_t& e : v.ev) VP_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  if ((size_t)B * w > v.x.cap || bytes > v.rows.cap) {
+    VP_HIP(hipStreamSynchronize(h->stream));  // launches in flight read the old blocks; every ring slot is idle afterwards
+    for (DevBuf<float>* b : {&v.x, &v.pred})
+      if ((rc = b->reserve((size_t)B * w)) != VP_OK) return rc;
+    if ((rc = v.rows.reserve(std::max(bytes, (size_t)net.max_batch * (sizeof(vp_plan_row) + 2 * sizeof(int32_t))))) != VP_OK)
+      return rc;
+  }
+  if ((rc = room_for_results()) != VP_OK) return rc;
+  const int slot = (int)(v.launches % vp::RowRing::N);
+  if (v.ev_used[slot]) VP_HIP(hipEventSynchronize(v.ev[slot]));  // (eight launches back: long complete in the steady state)
+
+  // ---- generate -> forward -> reduce ---------------------------------------------------------------------------------------
+  char* hs = static_cast<char*>(v.rows.host[slot]);
+  char* ds = static_cast<char*>(v.rows.dev[slot]);
+  memcpy(hs, rows, row_bytes);
+  if (lo) {
+    memcpy(hs + row_bytes, lo, (size_t)B * sizeof(int32_t));
+    memcpy(hs + row_bytes + (size_t)B * sizeof(int32_t), hi, (size_t)B * sizeof(int32_t));
+  }
+  VP_HIP(hipMemcpyAsync(ds, hs, bytes, hipMemcpyHostToDevice, h->stream));
+  if ((rc = vp::bank_launch_windows(bk, reinterpret_cast<const vp_plan_row*>(ds), B, T, norm, v.x.p, h->stream)) != VP_OK) return rc;
+  for (int b0 = 0; b0 < B; b0 += net.max_batch) {
+    const int nb = std::min(net.max_batch, B - b0);
+    const OutputRedirect to_pred(net, v.pred.p + (size_t)b0 * w);
+    if ((rc = run_batch(h, pre_args(h, v.x.p + (size_t)b0 * w, 1, 0, 0, 0, 0), nb)) != VP_OK) return rc;
+  }
+  const int* d_lo = lo ? reinterpret_cast<const int*>(ds + row_bytes) : nullptr;
+  if ((rc = reduce(v.pred.p, d_lo, d_lo ? d_lo + B : nullptr)) != VP_OK) return rc;
+  VP_HIP(hipEventRecord(v.ev[slot], h->stream));
+  v.ev_used[slot] = true;
+  ++v.launches;
+  if (pred_out_dev)
+    VP_HIP(hipMemcpyAsync(pred_out_dev, v.pred.p, (size_t)B * w * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+  return VP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -621,53 +703,18 @@ int vp_predict_bank(vp_handle* h, vp_bank* bank, const vp_plan_row* rows, const 
   if (rc != VP_OK) return rc;
   VP_HIP(hipSetDevice(h->device));
 
-  // ---- room for the batch, its rows and borders and its records: nothing is enqueued before all of it stands ---------------
-  const size_t w = (size_t)net.n_out * T, row_bytes = (size_t)B * sizeof(vp_plan_row);
-  const size_t bytes = row_bytes + (lo ? (size_t)2 * B * sizeof(int32_t) : 0);
-  static_assert(sizeof(vp_plan_row) % alignof(int32_t) == 0, "the borders follow the rows in a ring slot");
-  if (!v.ev[0])
-    for (hipEvent_t& e : v.ev) VP_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  if ((size_t)B * w > v.x.cap || bytes > v.rows.cap) {
-    VP_HIP(hipStreamSynchronize(h->stream));  // launches in flight read the old blocks; every ring slot is idle afterwards
-    for (DevBuf<float>* b : {&v.x, &v.pred})
-      if ((rc = b->reserve((size_t)B * w)) != VP_OK) return rc;
-    if ((rc = v.rows.reserve(std::max(bytes, (size_t)net.max_batch * (sizeof(vp_plan_row) + 2 * sizeof(int32_t))))) != VP_OK)
-      return rc;
-  }
-  if ((rc = grow_results(v.rec, (size_t)v.n_windows, (size_t)v.n_windows + B, h->stream)) != VP_OK) return rc;
-  const int slot = (int)(v.launches % vp::RowRing::N);
-  if (v.ev_used[slot]) VP_HIP(hipEventSynchronize(v.ev[slot]));  // (eight launches back: long complete in the steady state)
-
-  // ---- generate -> forward -> reduce ---------------------------------------------------------------------------------------
-  char* hs = static_cast<char*>(v.rows.host[slot]);
-  char* ds = static_cast<char*>(v.rows.dev[slot]);
-  memcpy(hs, rows, row_bytes);
-  if (lo) {
-    memcpy(hs + row_bytes, lo, (size_t)B * sizeof(int32_t));
-    memcpy(hs + row_bytes + (size_t)B * sizeof(int32_t), hi, (size_t)B * sizeof(int32_t));
-  }
-  VP_HIP(hipMemcpyAsync(ds, hs, bytes, hipMemcpyHostToDevice, h->stream));
-  if ((rc = vp::bank_launch_windows(bk, reinterpret_cast<const vp_plan_row*>(ds), B, T, norm, v.x.p, h->stream)) != VP_OK) return rc;
-  for (int b0 = 0; b0 < B; b0 += net.max_batch) {
-    const int nb = std::min(net.max_batch, B - b0);
-    const OutputRedirect to_pred(net, v.pred.p + (size_t)b0 * w);
-    if ((rc = run_batch(h, pre_args(h, v.x.p + (size_t)b0 * w, 1, 0, 0, 0, 0), nb)) != VP_OK) return rc;
-  }
   vp::PredictArgs a{};
-  a.prob = v.pred.p;
   a.B = B, a.n_rows = net.n_out, a.T = T;
   a.det_row = det_row, a.p_row = p_row, a.s_row = s_row, a.det_mode = det_mode;
-  if (lo) {
-    a.lo = reinterpret_cast<const int*>(ds + row_bytes);
-    a.hi = a.lo + B;
-  }
-  a.out = v.rec.p + v.n_windows;
-  if ((rc = vp::predict_launch(a, h->stream)) != VP_OK) return rc;
-  VP_HIP(hipEventRecord(v.ev[slot], h->stream));
-  v.ev_used[slot] = true;
-  ++v.launches;
-  if (pred_out_dev)
-    VP_HIP(hipMemcpyAsync(pred_out_dev, v.pred.p, (size_t)B * w * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+  rc = window_batch(
+      h, v.io, bk, rows, lo, hi, B, norm, pred_out_dev,
+      [&] { return grow_results(v.rec, (size_t)v.n_windows, (size_t)v.n_windows + B, h->stream); },
+      [&](const float* pred, const int* d_lo, const int* d_hi) {
+        a.prob = pred, a.lo = d_lo, a.hi = d_hi;
+        a.out = v.rec.p + v.n_windows;
+        return vp::predict_launch(a, h->stream);
+      });
+  if (rc != VP_OK) return rc;
   v.n_windows += B;
   return VP_OK;
 }
@@ -680,6 +727,126 @@ int vp_predict_end(vp_handle* h, vp_predict_record* out, long long cap, long lon
   VP_HIP(hipSetDevice(h->device));
   const long long nw = std::min(cap, v.n_windows);
   if (nw > 0) VP_HIP(hipMemcpyAsync(out, v.rec.p, (size_t)nw * sizeof(vp_predict_record), hipMemcpyDeviceToHost, h->stream));
+  VP_HIP(hipStreamSynchronize(h->stream));
+  if (n_windows) *n_windows = v.n_windows;
+  v.open = false;
+  return VP_OK;
+}
+
+// ---- task 0: the threshold sweep (sweep.hip) -----------------------------------------------------------------------------
+static void sweep_args(vp::SweepArgs& a, int B, int n_rows, int T, int p_row, int s_row, const float* thr_on,
+                       const float* thr_off, int NT, int K) {
+  a.B = B, a.n_rows = n_rows, a.T = T, a.p_row = p_row, a.s_row = s_row, a.NT = NT, a.K = K;
+  memcpy(a.thr_on, thr_on, NT * sizeof(float));
+  memcpy(a.thr_off, thr_off, NT * sizeof(float));
+}
+
+int vp_sweep_windows(vp_handle* h, const float* prob, int prob_mem, int B, int n_rows, int p_row, int s_row, const int32_t* lo,
+                     const int32_t* hi, const float* thr_on, const float* thr_off, int NT, int K, int32_t* count,
+                     int32_t* peak, float* value) {
+  VP_REQUIRE(h && prob && thr_on && thr_off && count && peak, "vp_sweep_windows: null argument");
+  VP_REQUIRE(prob_mem == VP_MEM_HOST || prob_mem == VP_MEM_DEVICE, "vp_sweep_windows: prob_mem %d", prob_mem);
+  VP_REQUIRE(((uintptr_t)prob & 3) == 0, "vp_sweep_windows: prob must be 4-byte aligned");
+  const int T = h->net.in_samples;
+  int rc = vp::sweep_check(B, n_rows, T, p_row, s_row, lo, hi, thr_on, thr_off, NT, K, "vp_sweep_windows");
+  if (rc != VP_OK) return rc;
+  VP_HIP(hipSetDevice(h->device));
+  const size_t n_prob = (size_t)B * n_rows * T, n_cnt = (size_t)B * 2 * NT, n_pk = n_cnt * K;
+  // scratch layout (4-byte words): [prob copy if host][lo B][hi B][count][peak][value if asked for]
+  const size_t need = (prob_mem == VP_MEM_HOST ? n_prob : 0) + (size_t)2 * B + n_cnt + n_pk * (value ? 2 : 1);
+  if ((rc = h->d_in.reserve(std::max(need, (size_t)h->net.max_batch * 3 * T))) != VP_OK) return rc;
+  float* p = h->d_in.p;
+  vp::SweepArgs a{};
+  sweep_args(a, B, n_rows, T, p_row, s_row, thr_on, thr_off, NT, K);
+  a.prob = prob;
+  if (prob_mem == VP_MEM_HOST) {
+    VP_HIP(hipMemcpyAsync(p, prob, n_prob * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    a.prob = p;
+    p += n_prob;
+  }
+  int* d_lo = reinterpret_cast<int*>(p);
+  int* d_hi = d_lo + B;
+  a.count = d_hi + B;
+  a.peak = a.count + n_cnt;
+  a.value = value ? reinterpret_cast<float*>(a.peak + n_pk) : nullptr;
+  if (lo) {
+    VP_HIP(hipMemcpyAsync(d_lo, lo, B * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    VP_HIP(hipMemcpyAsync(d_hi, hi, B * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    a.lo = d_lo, a.hi = d_hi;
+  }
+  if ((rc = vp::sweep_launch(a, h->stream)) != VP_OK) return rc;
+  VP_HIP(hipMemcpyAsync(count, a.count, n_cnt * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  VP_HIP(hipMemcpyAsync(peak, a.peak, n_pk * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  if (value) VP_HIP(hipMemcpyAsync(value, a.value, n_pk * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  VP_HIP(hipStreamSynchronize(h->stream));
+  return VP_OK;
+}
+
+int vp_sweep_begin(vp_handle* h, const float* thr_on, const float* thr_off, int NT, int K, int keep_values) {
+  VP_REQUIRE(h && thr_on && thr_off, "vp_sweep_begin: null argument");
+  const vp::Net& net = h->net;
+  // (B, the rows and the borders are each batch's: 1, 0 / 1 and none stand in for them here)
+  const int rc = vp::sweep_check(1, net.n_out, net.in_samples, 0, 1, nullptr, nullptr, thr_on, thr_off, NT, K, "vp_sweep_begin");
+  if (rc != VP_OK) return rc;
+  SweepPass& v = h->swp;
+  v.NT = NT, v.K = K, v.keep_values = keep_values != 0;
+  memcpy(v.thr_on, thr_on, NT * sizeof(float));
+  memcpy(v.thr_off, thr_off, NT * sizeof(float));
+  v.open = true;
+  v.n_windows = 0;  // (launches of an abandoned pass run ahead of this one's on the same stream)
+  return VP_OK;
+}
+
+// generate -> forward in chunks of max_batch -> the picks of all B windows at every threshold, appended.
+int vp_sweep_bank(vp_handle* h, vp_bank* bank, const vp_plan_row* rows, const int32_t* lo, const int32_t* hi, int B, int norm,
+                  int p_row, int s_row, float* pred_out_dev) {
+  VP_REQUIRE(h && bank, "vp_sweep_bank: null argument");
+  SweepPass& v = h->swp;
+  VP_REQUIRE(v.open, "vp_sweep_bank: no pass is open (vp_sweep_begin)");
+  const vp::Bank& bk = *reinterpret_cast<const vp::Bank*>(bank);
+  VP_REQUIRE(bk.device == h->device, "vp_sweep_bank: bank on device %d, handle on device %d", bk.device, h->device);
+  vp::Net& net = h->net;
+  const int T = net.in_samples;
+  int rc = vp::bank_check_windows(bk, rows, B, T, norm);
+  if (rc == VP_OK) rc = vp::sweep_check(B, net.n_out, T, p_row, s_row, lo, hi, v.thr_on, v.thr_off, v.NT, v.K, "vp_sweep_bank");
+  if (rc != VP_OK) return rc;
+  VP_HIP(hipSetDevice(h->device));
+  const size_t per_cnt = (size_t)2 * v.NT, per_pk = per_cnt * v.K, nw = (size_t)v.n_windows;
+  vp::SweepArgs a{};
+  sweep_args(a, B, net.n_out, T, p_row, s_row, v.thr_on, v.thr_off, v.NT, v.K);
+  rc = window_batch(
+      h, v.io, bk, rows, lo, hi, B, norm, pred_out_dev,
+      [&] {
+        int r = grow_results(v.count, nw * per_cnt, (nw + B) * per_cnt, h->stream);
+        if (r == VP_OK) r = grow_results(v.peak, nw * per_pk, (nw + B) * per_pk, h->stream);
+        if (r == VP_OK && v.keep_values) r = grow_results(v.value, nw * per_pk, (nw + B) * per_pk, h->stream);
+        return r;
+      },
+      [&](const float* pred, const int* d_lo, const int* d_hi) {
+        a.prob = pred, a.lo = d_lo, a.hi = d_hi;
+        a.count = v.count.p + nw * per_cnt;
+        a.peak = v.peak.p + nw * per_pk;
+        a.value = v.keep_values ? v.value.p + nw * per_pk : nullptr;
+        return vp::sweep_launch(a, h->stream);
+      });
+  if (rc != VP_OK) return rc;
+  v.n_windows += B;
+  return VP_OK;
+}
+
+int vp_sweep_end(vp_handle* h, int32_t* count, int32_t* peak, float* value, long long cap_windows, long long* n_windows) {
+  VP_REQUIRE(h != nullptr, "vp_sweep_end: null handle");
+  SweepPass& v = h->swp;
+  VP_REQUIRE(v.open, "vp_sweep_end: no pass is open (vp_sweep_begin)");
+  VP_REQUIRE(cap_windows >= 0 && (cap_windows == 0 || (count && peak)), "vp_sweep_end: null output arrays");
+  VP_REQUIRE(!value || v.keep_values, "vp_sweep_end: the pass was opened without keep_values");
+  VP_HIP(hipSetDevice(h->device));
+  const size_t nw = (size_t)std::min(cap_windows, v.n_windows), per_cnt = (size_t)2 * v.NT, per_pk = per_cnt * v.K;
+  if (nw > 0) {
+    VP_HIP(hipMemcpyAsync(count, v.count.p, nw * per_cnt * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    VP_HIP(hipMemcpyAsync(peak, v.peak.p, nw * per_pk * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    if (value) VP_HIP(hipMemcpyAsync(value, v.value.p, nw * per_pk * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  }
   VP_HIP(hipStreamSynchronize(h->stream));
   if (n_windows) *n_windows = v.n_windows;
   v.open = false;

@@ -18,6 +18,9 @@ struct PredictArgs {
   vp_predict_record* out;  // [B] on the device
 };
 
+// The border rule of every per-window reduction (predict_check, sweep_check): lo and hi together or not at all, and every
+// HOST border inside [0, T] and not empty.
+int border_check(int B, int T, const int32_t* lo, const int32_t* hi, const char* who);
 // Checks the shape arguments and, where given, the HOST copies of the borders; VP_ERR_INVALID (with the message set) on
 // the first bad one.  Nothing the kernel indexes with is left unchecked.
 int predict_check(int B, int n_rows, int T, int det_row, int p_row, int s_row, int det_mode, const int32_t* lo,

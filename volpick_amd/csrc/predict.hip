@@ -108,6 +108,15 @@ __global__ __launch_bounds__(PW_NTH) void predict_windows_kernel(const PredictAr
 
 }  // namespace
 
+int border_check(int B, int T, const int32_t* lo, const int32_t* hi, const char* who) {
+  VP_REQUIRE((lo == nullptr) == (hi == nullptr), "%s: lo and hi come together or not at all", who);
+  if (lo)
+    for (int b = 0; b < B; ++b)
+      VP_REQUIRE(lo[b] >= 0 && hi[b] <= T && hi[b] > lo[b], "%s: window %d: border [%d, %d) is empty or outside [0, %d]", who,
+                 b, (int)lo[b], (int)hi[b], T);
+  return VP_OK;
+}
+
 int predict_check(int B, int n_rows, int T, int det_row, int p_row, int s_row, int det_mode, const int32_t* lo,
                   const int32_t* hi, const char* who) {
   VP_REQUIRE(B >= 1, "%s: B = %d", who, B);
@@ -117,12 +126,7 @@ int predict_check(int B, int n_rows, int T, int det_row, int p_row, int s_row, i
   VP_REQUIRE(det_row != p_row && det_row != s_row && p_row != s_row, "%s: rows (%d, %d, %d) are not distinct", who, det_row,
              p_row, s_row);
   VP_REQUIRE(det_mode == VP_DET_ONE_MINUS_NOISE || det_mode == VP_DET_ROW, "%s: unknown det_mode %d", who, det_mode);
-  VP_REQUIRE((lo == nullptr) == (hi == nullptr), "%s: lo and hi come together or not at all", who);
-  if (lo)
-    for (int b = 0; b < B; ++b)
-      VP_REQUIRE(lo[b] >= 0 && hi[b] <= T && hi[b] > lo[b], "%s: window %d: border [%d, %d) is empty or outside [0, %d]", who,
-                 b, (int)lo[b], (int)hi[b], T);
-  return VP_OK;
+  return border_check(B, T, lo, hi, who);
 }
 
 int predict_launch(const PredictArgs& a, hipStream_t s) {

@@ -4,7 +4,13 @@ Mirrors ``evaluate()`` of volpick/model/eval_taks0.py:20-200 for pre-cut, alread
 windows: forward pass, slice ``window_borders``, ``trigger_onset(prob, thr, thr / 2)`` and per
 trigger ``max`` / ``argmax`` (``get_picks_from_prob``, eval_taks0.py:46-56).  The per-sample
 Python loop of the reference (eval_taks0.py:96-142) runs as one kernel launch per phase
-(``vp_pick_windows``).  Dataset handling, TP/FP/FN counting and CSV bookkeeping stay out of scope.
+(``vp_pick_windows``).
+
+Task 0 itself (``eval_task0``, eval_taks0.py:370-825) runs from a :class:`~volpick_amd.generate.WaveformBank`: ``sweep_bank``
+makes one forward pass per window and takes the picks of every threshold from it in one launch per batch (``vp_sweep_begin``
+/ ``_bank`` / ``_end``; ``sweep_windows`` on pre-cut windows), and ``task0_truth``, ``task0_counts``, ``task0_residuals``,
+``task0_metrics``, ``task0_tnr`` and ``opt_prob_metrics`` restate the reference's ground truth, TP/FP/FN counting, residual
+statistics and tables in numpy.  Dataset handling and CSV bookkeeping stay out of scope.
 
 The pick-benchmark tasks 1-3 (volpick/model/eval_taks123.py) are here as well.  ``predict_windows`` is ``predict_step``
 of the reference's Lightning modules (models.py:454-480, :881-906) on pre-cut windows, ``eval_tasks123`` the pass of
@@ -330,3 +336,327 @@ def task23_metrics(dev, test):
                 stats[f"{name}_{phase}_modified_rmse_s"] = np.sqrt(np.mean(inside**2))
                 stats[f"{name}_{phase}_modified_mae_s"] = np.mean(np.abs(inside))
     return stats
+
+
+# ---- pick-benchmark task 0 ---------------------------------------------------------------------------------------------
+# The reference compares float32 probabilities with ``prob_thre`` inside ObsPy's trigger_onset.  With a Python float that is
+# a float32 comparison under every NumPy; with the ``np.float64`` elements of ``np.arange(0.1, 1.0, 0.1)`` it is float32
+# under NumPy 1's value-based casting and float64 under NumPy 2, and the reference pins no NumPy version.  The sweep rounds
+# every threshold to float32 and compares in float32, which is ``vp_pick_windows``' and ``evaluate_windows``' contract.
+SWEEP_COMPARE_DTYPE = np.float32
+SWEEP_OFF_FRACTION = 2  # thr_off = thr_on / 2 (eval_taks0.py:46-56)
+SWEEP_MAX_THRESHOLDS = 32
+SWEEP_MAX_PICKS = 64
+TASK0_SAMPLING_RATE = 100  # the reference hard-codes 100 Hz in its counts and residuals (eval_taks0.py:552, :573)
+
+
+def _sweep_rows(model):
+    if model.name == "PhaseNet":
+        return model.labels.index("P"), model.labels.index("S")
+    return 1, 2  # EQTransformer returns (detection, P, S)
+
+
+def _sweep_grid(thresholds):
+    """``thresholds``: a number, NT numbers, or ``[P_thresholds, S_thresholds]`` (two rows of NT).  Returns the float32 on
+    and off thresholds the kernel sweeps and, per phase, which of them are that phase's NT columns (None: all, in order)."""
+    thr = np.asarray(thresholds, np.float64)
+    if thr.ndim == 0:
+        thr = thr[None]
+    if thr.ndim == 2 and thr.shape[0] == 2:
+        grid = np.unique(thr.astype(SWEEP_COMPARE_DTYPE))
+        select = [np.searchsorted(grid, thr[ph].astype(SWEEP_COMPARE_DTYPE)) for ph in (0, 1)]
+    elif thr.ndim == 1 and thr.size:
+        grid, select = thr.astype(SWEEP_COMPARE_DTYPE), None
+    else:
+        raise ValueError("thresholds: a number, NT numbers or [P_thresholds, S_thresholds]")
+    if grid.size > SWEEP_MAX_THRESHOLDS:
+        raise ValueError(f"{grid.size} distinct thresholds; one sweep takes {SWEEP_MAX_THRESHOLDS}")
+    if not np.isfinite(grid).all():
+        raise ValueError("thresholds must be finite")
+    on = np.ascontiguousarray(grid)
+    return on, np.ascontiguousarray(on / SWEEP_COMPARE_DTYPE(SWEEP_OFF_FRACTION)), select
+
+
+def _sweep_result(count, peak, value, select, max_picks):
+    if select is not None:
+        pick = lambda a: np.stack([a[:, ph][:, select[ph]] for ph in (0, 1)], axis=1)
+        count, peak, value = pick(count), pick(peak), (None if value is None else pick(value))
+    if (count > max_picks).any():
+        raise RuntimeError(f"more than max_picks={max_picks} triggers in a window; raise max_picks")
+    return count, peak, value
+
+
+def sweep_windows(model, X, window_borders=None, thresholds=np.arange(0.1, 1.0, 0.1), batch_size=1024, max_picks=8,
+                  scores=False):
+    """The picks of ``evaluate_windows`` at every threshold of ``thresholds`` from ONE forward pass per window
+    (``vp_sweep_windows``).  X and window_borders as for ``evaluate_windows``; ``thresholds``: NT numbers, or
+    ``[P_thresholds, S_thresholds]`` as the reference's ``evaluate`` takes ``[p, s]``; ``thr_off = thr / 2``.
+
+    Returns ``(count, peak, value)``: count (n, 2, NT) int32, phase 0 = P and 1 = S; peak (n, 2, NT, max_picks) int32, the
+    pick samples local to the border start, ascending, -1 behind the count; value the float32 maxima (0 behind the count)
+    with ``scores=True``, else None.  ``RuntimeError`` when a window has more than ``max_picks`` triggers."""
+    torch = __import__("torch")
+    lib = _lib.load()
+    X = np.ascontiguousarray(X, dtype=np.float32)
+    n = X.shape[0]
+    lo, hi = _borders(window_borders, n)
+    on, off, select = _sweep_grid(thresholds)
+    NT, K = len(on), int(max_picks)
+    p_row, s_row = _sweep_rows(model)
+    count = np.zeros((n, 2, NT), np.int32)
+    peak = np.full((n, 2, NT, K), -1, np.int32)
+    value = np.zeros((n, 2, NT, K), np.float32) if scores else None
+    h = model._ensure_handle()
+    ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    for b0 in range(0, n, batch_size):
+        y = model._forward_raw(torch.from_numpy(X[b0 : b0 + batch_size]).to(model.device))  # (B, 3, T) on the device
+        B = y.shape[0]
+        _lib.check(lib.vp_sweep_windows(h, C.c_void_p(y.data_ptr()), _lib.VP_MEM_DEVICE, B, 3, p_row, s_row,
+                                        ptr(None if lo is None else lo[b0 : b0 + B]), ptr(None if hi is None else hi[b0 : b0 + B]),
+                                        ptr(on), ptr(off), NT, K, ptr(count[b0 : b0 + B]), ptr(peak[b0 : b0 + B]),
+                                        ptr(None if value is None else value[b0 : b0 + B])), "vp_sweep_windows")
+    return _sweep_result(count, peak, value, select, K)
+
+
+def sweep_bank(model, bank, rows, window_borders=None, thresholds=np.arange(0.1, 1.0, 0.1), batch_size=1024, max_picks=8,
+               scores=False, predictions=False):
+    """One sweep pass on the GPU (``vp_sweep_begin`` ... ``vp_sweep_end``): the plan ``rows`` are cut from ``bank`` and
+    normalised with ``model.norm``, predicted once and swept at every threshold in batches of ``batch_size``; the host waits
+    once, at the end.  Returns ``sweep_windows``' tuple; with ``predictions=True`` also the list of the batches' (B, 3, T)
+    probabilities (CUDA tensors)."""
+    from .generate import _norm, as_rows
+
+    lib = _lib.load()
+    rows = as_rows(rows)
+    n = len(rows)
+    lo, hi = _borders(window_borders, n)
+    on, off, select = _sweep_grid(thresholds)
+    NT, K = len(on), int(max_picks)
+    p_row, s_row = _sweep_rows(model)
+    if model._device_index is None:
+        model.cuda(bank.device)
+    h = model._ensure_handle()
+    preds = []
+    if predictions:
+        torch = __import__("torch")
+        dev = torch.device("cuda", model._device_index)
+    count = np.zeros((n, 2, NT), np.int32)
+    peak = np.full((n, 2, NT, K), -1, np.int32)
+    value = np.zeros((n, 2, NT, K), np.float32) if scores else None
+    ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    _lib.check(lib.vp_sweep_begin(h, ptr(on), ptr(off), NT, K, int(scores)), "vp_sweep_begin")
+    try:
+        for b0 in range(0, n, batch_size):
+            r = rows[b0 : b0 + batch_size]
+            B = len(r)
+            out = None
+            if predictions:
+                out = torch.empty((B, 3, model.in_samples), dtype=torch.float32, device=dev)
+                torch.cuda.current_stream(dev).synchronize()  # whatever used this memory last on torch's stream is done
+                preds.append(out)
+            _lib.check(lib.vp_sweep_bank(h, bank.handle, ptr(r), ptr(None if lo is None else lo[b0 : b0 + B]),
+                                         ptr(None if hi is None else hi[b0 : b0 + B]), B, _norm(model.norm), p_row, s_row,
+                                         C.c_void_p(out.data_ptr()) if predictions else None), "vp_sweep_bank")
+    finally:
+        nw = C.c_longlong()
+        rc = lib.vp_sweep_end(h, ptr(count), ptr(peak), ptr(value), n, C.byref(nw))
+    _lib.check(rc, "vp_sweep_end")
+    assert nw.value == n
+    return _sweep_result(count, peak, value, select, K) + ((preds,) if predictions else ())
+
+
+def task0_truth(bank, targets, p_truth=None, s_truth=None):
+    """``get_ground_truth`` (eval_taks0.py:203-239): per target the first P and the first S onset of its trace (``bank.onsets``;
+    ``p_truth`` / ``s_truth``, one value per target, take their place when given), in trace samples; NaN where the trace
+    has none or it lies outside the target's ``[start_sample, end_sample)``.  Returns ``(p, s)``, float64 arrays."""
+    trace = np.asarray(targets["trace"], np.int64)
+    start, end = np.asarray(targets["start_sample"]), np.asarray(targets["end_sample"])
+    out = []
+    for col, given in ((0, p_truth), (2, s_truth)):
+        t = np.asarray(bank.onsets, np.float64).reshape(-1, 4)[trace, col] if given is None else np.array(given, np.float64)
+        with np.errstate(invalid="ignore"):
+            inside = (t >= start) & (t < end)
+        out.append(np.where(inside, t, np.nan))
+    return out[0], out[1]
+
+
+def _picks(count, peak, start_sample):
+    """(n, NT) counts and (n, NT, K) local peaks of one phase -> the picks in trace samples and which slots hold one."""
+    count, peak = np.asarray(count), np.asarray(peak)
+    held = np.arange(peak.shape[-1]) < count[..., None]
+    return peak.astype(np.float64) + np.asarray(start_sample, np.float64)[:, None, None], held
+
+
+def task0_counts(truth, count, peak, start_sample, tp_thre=0.5, sampling_rate=TASK0_SAMPLING_RATE, method=0):
+    """``count_TP_FP_FN`` (eval_taks0.py:242-311) for one phase at every threshold: ``truth`` (n,) the onset per target or
+    NaN (``task0_truth``), ``count`` (n, NT) and ``peak`` (n, NT, K) that phase's part of a sweep; the picks are
+    ``peak + start_sample``.  A target without picks is a false negative if it has an onset.  With picks and no onset,
+    method 0 counts every pick as a false positive and method 1 one per target.  With both, the target is a true positive
+    when a pick lies within ``tp_thre`` seconds of the onset (``<=``); else it is a false negative (method 0) or a false
+    positive (method 1); method 0 also counts each pick beyond ``tp_thre`` as a false positive.
+    Returns ``(TP, FP, FN, tps, fps, fns)``: float64, the sums of shape (NT,) and the per-target arrays of shape (n, NT)."""
+    if method not in (0, 1):
+        raise ValueError("method must be 0 or 1")
+    truth = np.asarray(truth, np.float64)
+    picks, held = _picks(count, peak, start_sample)
+    has_truth = ~np.isnan(truth)[:, None]
+    has_picks = held.any(-1)
+    with np.errstate(invalid="ignore"):
+        near = held & (np.abs((picks - truth[:, None, None]) / sampling_rate) <= tp_thre)
+    hit = near.any(-1)
+    tps = (has_picks & has_truth & hit).astype(np.float64)
+    if method == 0:
+        fns = (has_truth & ~(has_picks & hit)).astype(np.float64)
+        fps = np.where(has_truth, (held & ~near).sum(-1), held.sum(-1)).astype(np.float64)
+    else:
+        fns = (has_truth & ~has_picks).astype(np.float64)
+        fps = (has_picks & ~(has_truth & hit)).astype(np.float64)
+    return tps.sum(0), fps.sum(0), fns.sum(0), tps, fps, fns
+
+
+def task0_residuals(truth, count, peak, start_sample, sampling_rate=TASK0_SAMPLING_RATE, method=0):
+    """``compute_residuals`` (eval_taks0.py:326-353) for one phase: per threshold the residuals ``(pick - onset) /
+    sampling_rate`` in seconds of the targets that have an onset and picks, in target order -- every pick (method 0), or per
+    target the pick closest to the onset, the earlier of two equally close (method 1).  Returns a list of NT float64 arrays."""
+    if method not in (0, 1):
+        raise ValueError("method must be 0 or 1")
+    truth = np.asarray(truth, np.float64)
+    picks, held = _picks(count, peak, start_sample)
+    held = held & ~np.isnan(truth)[:, None, None]
+    res = (picks - truth[:, None, None]) / sampling_rate
+    out = []
+    for j in range(held.shape[1]):
+        if method == 0:
+            out.append(res[:, j][held[:, j]])
+        else:
+            some = held[:, j].any(-1)
+            closest = np.argmin(np.where(held[:, j], np.abs(res[:, j]), np.inf), axis=-1)
+            out.append(res[np.arange(len(truth)), j, closest][some])
+    return out
+
+
+TASK0_RESIDUAL_KEYS = ("mean", "median", "std", "MAE", "MAD", "out", "modified_mean", "modified_median", "modified_std",
+                       "modified_RMSE", "modified_MAE", "modified_MAD", "modified_mean2", "modified_median2", "modified_std2",
+                       "modified_RMSE2", "modified_MAE2", "modified_MAD2")
+
+
+def _residual_stats(r):
+    """The eighteen residual statistics of eval_taks0.py:605-641, in TASK0_RESIDUAL_KEYS' order; None each without residuals.
+    "modified": residuals clipped to +-1 s; "modified...2": residuals beyond +-1 s (and at it) left out."""
+    if len(r) == 0:
+        return dict.fromkeys(TASK0_RESIDUAL_KEYS)
+    mad = lambda a: np.median(np.abs(a - np.median(a)))
+    clipped = np.clip(r, -1, 1)
+    inside = r[(r > -1) & (r < 1)]
+    values = (np.mean(r), np.median(r), np.std(r, ddof=1), np.mean(np.abs(r)), mad(r), ((r < -1) | (r > 1)).sum() / r.size,
+              np.mean(clipped), np.median(clipped), np.std(clipped, ddof=1), np.sqrt(np.mean(clipped**2)),
+              np.mean(np.abs(clipped)), mad(clipped),
+              np.mean(inside), np.median(inside), np.std(inside, ddof=1), np.sqrt(np.mean(inside**2)),
+              np.mean(np.abs(inside)), mad(inside))
+    return dict(zip(TASK0_RESIDUAL_KEYS, values))
+
+
+def task0_metrics(p_truth, s_truth, count, peak, start_sample, prob_thres, tp_thre=0.5, count_tp_method=0, no_p=False,
+                  no_s=False):
+    """The reference's metric table (eval_taks0.py:497-782) from one sweep: ``count`` (n, 2, NT) and ``peak`` (n, 2, NT, K)
+    as ``sweep_bank`` returns them, ``p_truth`` / ``s_truth`` from ``task0_truth``.  One dict per threshold with the
+    reference's keys in its order: ``prob_thre``, ``tp_thre``, then per phase ``TP FP FN precision recall F1score`` and the
+    eighteen residual statistics (None each when the phase has no residuals).  ``no_p`` / ``no_s`` leave that phase's keys
+    out (choosing the targets without that phase is the caller's part; ``eval_task0`` does it).  0 / 0 and the ``ddof=1``
+    deviation of one value are numpy's NaN with its RuntimeWarning, as in the reference."""
+    if no_p and no_s:
+        raise ValueError("no_p and no_s together leave nothing to score")
+    count, peak = np.asarray(count), np.asarray(peak)
+    if len(prob_thres) != count.shape[2]:
+        raise ValueError(f"{len(prob_thres)} thresholds for counts of {count.shape[2]}")
+    per_phase = {}
+    for ph, (name, truth, skip) in enumerate((("p", p_truth, no_p), ("s", s_truth, no_s))):
+        if not skip:
+            per_phase[name] = (task0_counts(truth, count[:, ph], peak[:, ph], start_sample, tp_thre, method=count_tp_method),
+                               task0_residuals(truth, count[:, ph], peak[:, ph], start_sample, method=count_tp_method))
+    rows = []
+    for j, thr in enumerate(prob_thres):
+        row = {"prob_thre": thr, "tp_thre": tp_thre}
+        for name, ((TP, FP, FN, _, _, _), residuals) in per_phase.items():
+            tp, fp, fn = TP[j], FP[j], FN[j]
+            precision, recall = tp / (tp + fp), tp / (tp + fn)
+            stats = {"TP": tp, "FP": fp, "FN": fn, "precision": precision, "recall": recall,
+                     "F1score": 2.0 * (precision * recall) / (precision + recall)}
+            stats.update(_residual_stats(residuals[j]))
+            row.update({f"{name}_{k}": v for k, v in stats.items()})
+        rows.append(row)
+    return rows
+
+
+def task0_tnr(p_truth, s_truth, count, prob_thres):
+    """The rows of ``eval_task0_true_negative_rate`` (eval_taks0.py:943-971) from one sweep: per threshold and phase, among
+    the targets WITHOUT an onset, TN those without picks, FP those with picks (one per target), and TN / (TN + FP) -- NaN
+    where the reference's integer division raises because no target is without an onset."""
+    count = np.asarray(count)
+    rows = []
+    for j, thr in enumerate(prob_thres):
+        row = {"prob_thre": thr}
+        for ph, (name, truth) in enumerate((("p", p_truth), ("s", s_truth))):
+            negative = np.isnan(np.asarray(truth, np.float64))
+            tn, fp = int((negative & (count[:, ph, j] == 0)).sum()), int((negative & (count[:, ph, j] > 0)).sum())
+            with np.errstate(invalid="ignore"):
+                row.update({f"{name}_TN": tn, f"{name}_FP": fp, f"{name}_true_negative_rate": np.float64(tn) / np.float64(tn + fp)})
+        rows.append(row)
+    return rows
+
+
+def opt_prob_metrics(dev_metrics, test_metrics):
+    """``opt_prob_metrics`` (eval_taks0.py:1139-1172) on two ``task0_metrics`` tables (lists of rows, or DataFrames) over the
+    same thresholds: per phase the row where the DEV F1 score is largest (``np.argmax``: the first such row, and a NaN
+    counts as largest, as it does there), and that row of both tables.  Keys in the reference's order without its
+    ``exp_name``: ``tp_thre``, ``p_opt_prob_thre``, ``s_opt_prob_thre``, ``test_p_*``, ``test_s_*``, ``dev_p_*``, ``dev_s_*``."""
+    def table(t):
+        if hasattr(t, "to_dict") and not isinstance(t, dict):
+            return t.to_dict("records")
+        return list(t)
+
+    dev, test = table(dev_metrics), table(test_metrics)
+    best = {}
+    for name in ("p", "s"):
+        f1 = np.array([np.nan if r[f"{name}_F1score"] is None else r[f"{name}_F1score"] for r in dev], np.float64)
+        best[name] = int(np.argmax(f1))
+    result = {"tp_thre": test[0]["tp_thre"], "p_opt_prob_thre": dev[best["p"]]["prob_thre"],
+              "s_opt_prob_thre": dev[best["s"]]["prob_thre"]}
+    for prefix, rows in (("test_", test), ("dev_", dev)):
+        for name in ("p", "s"):
+            result.update({prefix + k: v for k, v in rows[best[name]].items() if k[:2] == name + "_"})
+    return result
+
+
+def eval_task0(model, bank, targets, prob_thres=np.arange(0.1, 1.0, 0.1), tp_thre=0.5, count_tp_method=0, no_p=False,
+               no_s=False, batch_size=1024, max_picks=8):
+    """``eval_task0`` of the reference (eval_taks0.py:370-825) for one set of task targets in ONE pass -- one forward per
+    window, every threshold swept on the GPU: ``targets`` (a DataFrame or a dict of arrays) holds ``trace`` (the bank index),
+    ``start_sample`` and ``end_sample``.  ``no_p`` / ``no_s`` keep the targets whose trace has no P / no S onset and leave
+    that phase out of the table.  Returns ``(metrics, targets_out)``: the ``task0_metrics`` rows, and a copy of the (kept)
+    targets with ``p_pred_sample_thr{thr:.4f}`` / ``s_pred_sample_thr{thr:.4f}`` added per threshold, in that order: per
+    target one int64 array of picks in trace samples.  Files and directories are the caller's."""
+    from .generate import SteeredPlanner
+
+    if no_p and no_s:
+        raise ValueError("no_p and no_s together leave nothing to score")
+    onsets = np.asarray(bank.onsets, np.float64).reshape(-1, 4)[np.asarray(targets["trace"], np.int64)]
+    keep = np.ones(len(onsets), bool)
+    if no_p:
+        keep &= np.isnan(onsets[:, 0])
+    if no_s:
+        keep &= np.isnan(onsets[:, 2])
+    if isinstance(targets, dict):
+        out = {k: np.asarray(v)[keep] for k, v in targets.items()}
+    else:
+        out = targets[keep].copy()
+    rows, borders = SteeredPlanner(bank, model.in_samples).plan(out)
+    count, peak, _ = sweep_bank(model, bank, rows, borders, prob_thres, batch_size, max_picks)
+    start = np.asarray(out["start_sample"]).astype(np.int64)
+    p_truth, s_truth = task0_truth(bank, out)
+    metrics = task0_metrics(p_truth, s_truth, count, peak, start, prob_thres, tp_thre, count_tp_method, no_p, no_s)
+    for j, thr in enumerate(prob_thres):
+        for ph, name in enumerate("ps"):
+            out[f"{name}_pred_sample_thr{thr:.4f}"] = [peak[i, ph, j, : count[i, ph, j]].astype(np.int64) + start[i]
+                                                      for i in range(len(start))]
+    return metrics, out
