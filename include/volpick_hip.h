@@ -864,6 +864,68 @@ int vp_spectrogram_bench(int device_id, const void* in_dev, int in_kind, int n_s
                          float* out_dev, int iters, float* ms_total, float* ms_frames);
 
 /* ---------------------------------------------------------------------------------------------
+ * STA/LTA characteristic functions of device-resident series and the triggers cut from them: ObsPy's classic_sta_lta,
+ * recursive_sta_lta and trigger_onset (the reference's waveform check, volpick/data/utils.py:1064-1071), which
+ * volpick_amd/trigger.py restates on the host.  With sq = x * x and tiny the smallest normal double:
+ *
+ *     VP_STALTA_RECURSIVE   csta = 1 / nsta, clta = 1 / nlta, sta = 0, lta = tiny, cft[0] = 0; for i = 1 .. n - 1:
+ *                           sta = csta sq[i] + (1 - csta) sta, lta = clta sq[i] + (1 - clta) lta, cft[i] = sta / lta,
+ *                           replaced by 0 where i < nlta.  Sample 0 never enters the sums.
+ *     VP_STALTA_CLASSIC     STA[i], LTA[i]: the sum of sq over the nsta, nlta samples ending at i (samples ahead of the
+ *                           series count as 0) divided by nsta, nlta; STA[i] = 0 for i < nlta - 1; LTA below tiny is
+ *                           tiny; cft = STA / LTA.
+ *
+ * An all-zero series gives 0 everywhere (in the recursion also behind the sample where tiny (1 - clta)^i leaves the
+ * doubles: 0 / lta stays 0); nlta > n gives all zeros.  in_dev: n_series series of n samples, series_stride samples from
+ * one to the next (>= n), int32, float32 or float64 (in_kind).  out_dev: the same layout in float32 or float64 (out_kind:
+ * VP_SAMPLES_FLOAT32 / FLOAT64); it must not overlap in_dev.  Arithmetic is float64 throughout, the only other rounding is
+ * the store.  Every term is a square, so no sum here cancels: against the rule in extended precision the recursion is
+ * within (6 (i + 1) + 10) 2^-53 of the value at sample i and the classic type within (nsta + nlta + 8) 2^-53 (the tests'
+ * bars; float32 output adds 2^-24).
+ *
+ * Scheme: tiles of 8192 samples, pieces of 32.  Recursive: both states are linear in themselves, so they are carried
+ * exactly as vp_sos_filter carries its state, with the host's table (1 - c)^(32 2^k), k = 0..15: per tile a scan of the
+ * pieces' zero-state ends, one workgroup per series that scans the tiles' ends 256 at a time (lta's start value tiny is
+ * its initial state), per tile the scan again and every piece run from its true start.  Classic: a window sum is never a
+ * difference of running sums.  For each width w the series is cut into blocks of w samples; a window is the sum from its
+ * first sample to the right edge of that sample's block plus the sum from the left edge of the next block to its last
+ * sample.  Both are segmented scans (per tile, with the tiles' partial sums scanned by one workgroup per series, forward
+ * and backward); a window of w samples takes at most w - 1 additions.  Order between tiles comes from the launch
+ * boundaries alone; no atomics: the same call gives the same bits twice.
+ *
+ * Non-finite input: a NaN or an Inf is read as NaN.  Recursive: every sample >= max(first non-finite, nlta) is NaN, the head
+ * stays 0 (sample 0, which never enters the sums, is not read: a non-finite value there changes nothing).  Classic: every sample at or after the first non-finite one is NaN, those below nlta - 1 included, as the rule's
+ * whole-trace cumulative sum leaves them.  Samples ahead of the first non-finite one are right.  (ObsPy keeps an Inf as
+ * Inf for the few samples until Inf - Inf or Inf / Inf turns it into NaN; here those are NaN at once.)
+ *
+ * VP_ERR_INVALID, out_dev untouched: a null pointer, an unknown in_kind, out_kind or type, n < 0, n_series < 1,
+ * series_stride < n, nsta < 1, nsta > nlta, out_dev overlapping in_dev.  n == 0 does nothing.  VP_ERR_UNSUPPORTED, out_dev
+ * untouched: nlta > 65536 (131 s at 500 Hz).  VP_ERR_NOMEM: the scratch cannot be allocated.  Runs on the device's null
+ * stream and returns after the work is done, as vp_sos_filter does; calls on one device are serialised.
+ *
+ * The scratch (72 bytes per tile; 16 bytes per sample for the classic type) is kept per device, grow-only, between calls;
+ * vp_sta_lta_release_scratch frees it and vp_trigger_onset's (bytes_freed may be NULL) -- the other release calls do not
+ * touch it.  vp_sta_lta_bench: mean time in ms (HIP events on a stream of its own, three untimed repetitions first) of
+ * `iters` repetitions of the whole call: bench only.
+ *
+ * vp_trigger_onset: trigger_onset(cft, thr_on, thr_off) without max_len for thr_off <= thr_on on n_series float32 rows in
+ * device memory -- exactly the triggers of vp_pick, by the same scan kernel, without a vp_handle: a trigger opens at the
+ * first sample > thr_on and closes at the last sample of the run of samples > thr_off; NaN compares false; peak / value are
+ * the first maximum over [on, off].  Results as vp_classify_multi's: grouped by series (series_of, may be NULL), sorted by
+ * onset, at most cap_per_series per series and cap in all; *n_found > cap means call again with more room (a series
+ * that overflowed cap_per_series raises it above cap).  VP_ERR_INVALID: a null pointer, n < 0, n_series < 1,
+ * series_stride < n, thr_off > thr_on (vp_pick_host has the general rule), a negative cap. */
+enum { VP_STALTA_CLASSIC = 0, VP_STALTA_RECURSIVE = 1 };
+int vp_sta_lta(int device_id, const void* in_dev, int in_kind, int n_series, int64_t series_stride, int64_t n, int type,
+               int64_t nsta, int64_t nlta, void* out_dev, int out_kind);
+int vp_sta_lta_release_scratch(int device_id, size_t* bytes_freed);
+int vp_sta_lta_bench(int device_id, const void* in_dev, int in_kind, int n_series, int64_t series_stride, int64_t n, int type,
+                     int64_t nsta, int64_t nlta, void* out_dev, int out_kind, int iters, float* ms_total);
+int vp_trigger_onset(int device_id, const float* cft_dev, int n_series, int64_t series_stride, int64_t n, float thr_on,
+                     float thr_off, int64_t* on, int64_t* off, int64_t* peak, float* value, int32_t* series_of,
+                     int cap_per_series, int cap, int* n_found);
+
+/* ---------------------------------------------------------------------------------------------
  * Multi-GPU bring-up.  The reference is single-GPU; windows are independent given the
  * weights, so the one exchange is the start-up broadcast of the flat weight blob from the root rank: a single
  * ncclBroadcast over RCCL (xGMI inside a node), after which vp_create(..., VP_MEM_DEVICE, ...) builds the plan from the

@@ -23,5 +23,8 @@ from .evaluate import (eval_task0, opt_prob_metrics, sweep_bank, sweep_windows, 
                        task0_residuals, task0_tnr, task0_truth)
 from . import spectrogram  # noqa: F401
 from .spectrogram import Spectrogram, release_spectrogram_scratch  # noqa: F401
+from . import trigger  # noqa: F401
+from .trigger import (classic_sta_lta, recursive_sta_lta, release_trigger_scratch, sta_lta_triggers,  # noqa: F401
+                      trigger_onset)
 
 __version__ = "0.1.0"

@@ -103,6 +103,8 @@ VP_ATTR_DEMEAN, VP_ATTR_MAX_WINDOW, VP_ATTR_OUT = 1, 2048, 14
 
 VP_SPECTROGRAM_TILE_FRAMES = 32
 
+VP_STALTA_CLASSIC, VP_STALTA_RECURSIVE = 0, 1
+
 
 class VpAttrRow(C.Structure):
     _fields_ = [
@@ -345,6 +347,21 @@ SIGNATURES = {
         C.c_int,
         [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64,
          C.c_int64, C.c_void_p, C.c_int, _FP, _FP],
+    ),
+    "vp_sta_lta": (
+        C.c_int,
+        [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int],
+    ),
+    "vp_sta_lta_release_scratch": (C.c_int, [C.c_int, C.POINTER(C.c_size_t)]),
+    "vp_sta_lta_bench": (
+        C.c_int,
+        [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int,
+         C.c_int, _FP],
+    ),
+    "vp_trigger_onset": (
+        C.c_int,
+        [C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_float, C.c_float, _I64P, _I64P, _I64P, _FP,
+         C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_int)],
     ),
     "vp_last_error": (C.c_char_p, []),
     "vp_version": (C.c_char_p, []),

@@ -223,6 +223,15 @@ class Trace:
 
         return trace_spectrogram(self, **kw)
 
+    def trigger(self, type, sta, lta):
+        """ObsPy's ``Trace.trigger`` for ``classicstalta`` and ``recstalta``: the data becomes the STA/LTA characteristic
+        function, ``sta`` and ``lta`` in seconds (``int(seconds * sampling_rate)`` samples, clipped to ``[1, npts]``).  In
+        place, returns ``self``.  A device-backed trace is processed on the device (float64 arithmetic, float32 samples) and
+        stays there; a host trace becomes float64."""
+        from .trigger import trace_trigger
+
+        return trace_trigger(self, type, sta, lta)
+
     def __len__(self):
         return int(self.stats["npts"])
 
@@ -275,6 +284,11 @@ class Stream:
     def spectrogram(self, **kw):
         """``[tr.spectrogram(**kw) for tr in self]``: one result per trace (ObsPy's method draws; this one returns numbers)."""
         return [tr.spectrogram(**kw) for tr in self.traces]
+
+    def trigger(self, type, sta, lta):
+        for tr in self.traces:
+            tr.trigger(type, sta=sta, lta=lta)
+        return self
 
     def sort(self, keys=("network", "station", "location", "channel", "starttime")):
         self.traces.sort(key=lambda t: tuple(str(t.stats[k]) if k != "starttime" else t.stats[k]._us for k in keys))
