@@ -404,6 +404,11 @@ def check(rc: int, what: str = "volpick_hip"):
     return rc
 
 
+def ptr(a):
+    """A numpy array's data as a ``void *`` argument; None stays None (a null pointer)."""
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
 def last_error() -> str:
     """The calling thread's last error message of the library."""
     return load().vp_last_error().decode(errors="replace")

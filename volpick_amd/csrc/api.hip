@@ -1,152 +1,17 @@
-// C ABI of libvolpick_hip.so (include/volpick_hip.h).
+// C ABI of libvolpick_hip.so (include/volpick_hip.h): the stream path -- forward, annotate, classify, the trigger scans,
+// timing, introspection and debug.  The passes over a bank and the reducers of pre-cut windows are in passes.hip.
 #include <algorithm>
 #include <cmath>
 #include <mutex>
-#include <type_traits>
 
+#include "api_handle.h"
 #include "api_host.h"
-#include "batchgen.h"
-#include "net.h"
-#include "predict.h"
-#include "prepost.h"
-#include "sweep.h"
-#include "valloss.h"
 
 namespace vp {
 const char* last_error();
 }
-
-namespace {
-
-// Grow-only device buffer of `cap` elements, with MIRROR a mapped pinned host block `host` of the same size beside it.
-// Growing drops the contents; zero_new clears a new device block (synchronously).
-template <class T, bool MIRROR = false>
-struct DevBuf {
-  T *p = nullptr, *host = nullptr;
-  size_t cap = 0;
-  int reserve(size_t need, bool zero_new = false) {
-    if (need <= cap) return VP_OK;
-    release();
-    VP_HIP(hipMalloc((void**)&p, need * sizeof(T)));
-    if (zero_new) VP_HIP(hipMemset(p, 0, need * sizeof(T)));
-    if (MIRROR) VP_HIP(hipHostMalloc((void**)&host, need * sizeof(T), hipHostMallocMapped));
-    cap = need;
-    return VP_OK;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    if (host) (void)hipHostFree(host);
-    p = host = nullptr;
-    cap = 0;
-  }
-};
-using MirroredBuf = DevBuf<char, true>;  // a trigger result block (vp::ScanLayout) and what the publish kernel copies it to
-
-// One validation pass (vp_validate_begin ... vp_validate_end): the scratch one batch is generated into and predicted in,
-// the staging of its plan rows, and the losses of every batch of the pass, all on the device until the pass ends.
-struct ValidationPass {
-  bool open = false;
-  DevBuf<float> x, y, pred;          // (B, 3, T) each: the batch of the latest vp_validate_bank
-  vp::RowRing rows;                  // slot launches % N, free again behind ev[slot]
-  hipEvent_t ev[vp::RowRing::N] = {};  // behind the last kernel of the launch that read ring slot i
-  bool ev_used[vp::RowRing::N] = {};
-  long long launches = 0;            // over the handle's life: the ring outlives a pass
-  DevBuf<double> batch, window;      // the pass's results: n_batches and n_windows values
-  long long n_batches = 0, n_windows = 0;
-  void release() {
-    for (DevBuf<float>* b : {&x, &y, &pred}) b->release();
-    batch.release();
-    window.release();
-    for (hipEvent_t& e : ev) {
-      if (e) (void)hipEventDestroy(e);
-      e = nullptr;
-    }
-  }
-};
-
-// What a pass that cuts its windows from a bank keeps from batch to batch (window_batch below): the windows and the
-// probabilities of the latest batch, (B, 3, T) each, and the staging ring.  A ring slot holds the batch's plan rows, then
-// its B lower and B upper borders.
-struct WindowBatches {
-  DevBuf<float> x, pred;
-  vp::RowRing rows;
-  hipEvent_t ev[vp::RowRing::N] = {};
-  bool ev_used[vp::RowRing::N] = {};
-  long long launches = 0;  // over the handle's life: the ring outlives a pass
-  void release() {
-    x.release();
-    pred.release();
-    for (hipEvent_t& e : ev) {
-      if (e) (void)hipEventDestroy(e);
-      e = nullptr;
-    }
-  }
-};
-
-// One prediction pass (vp_predict_begin ... vp_predict_end): its batches and its records.
-struct PredictPass {
-  bool open = false;
-  WindowBatches io;
-  DevBuf<vp_predict_record> rec;  // the pass's results: n_windows records
-  long long n_windows = 0;
-  void release() {
-    io.release();
-    rec.release();
-  }
-};
-
-// One sweep pass (vp_sweep_begin ... vp_sweep_end): its batches, the thresholds and K it was opened with, and per window
-// 2 NT counts and 2 NT K peaks (and values, when kept).
-struct SweepPass {
-  bool open = false;
-  WindowBatches io;
-  int NT = 0, K = 0;
-  bool keep_values = false;
-  float thr_on[vp::SW_MAX_NT] = {}, thr_off[vp::SW_MAX_NT] = {};
-  DevBuf<int32_t> count, peak;
-  DevBuf<float> value;
-  long long n_windows = 0;
-  void release() {
-    io.release();
-    count.release();
-    peak.release();
-    value.release();
-  }
-};
-
-}  // namespace
-
-struct vp_handle {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  vp::Net net;
-  hipEvent_t ev[5] = {};
-  float total_ms = 0.f;
-  bool timing = false;  // stage events cost ~5 us of stream bubble each: off unless vp_set_timing(h, 1)
-  float stage_ms[4] = {0.f, 0.f, 0.f, 0.f};
-  // the window description of the latest preprocessing batch: the vp_profile_* calls replay it through plans whose first
-  // launch cuts its windows itself -- after checking that what it points to is still allocated (pre_is_replayable)
-  vp::PreArgs last_pre{};
-  int last_pre_windows = 0;
-  int last_out_lo = 0, last_out_hi = 0;  // ... and the kept output range of that batch (Net::out_lo / out_hi)
-  // growable device scratch
-  DevBuf<float> d_in;    // staged host input (stream or windows)
-  DevBuf<float> d_pred;  // [n_windows][n_out][T] predictions of one annotate call
-  DevBuf<float> d_out;   // stacked output when the caller's buffer is on the host
-  // vp_classify_multi: tables (window table, block table, scan rows) and the result block
-  DevBuf<char> d_tab;
-  MirroredBuf m_pick;
-  struct Slot {          // one in-flight vp_classify_submit
-    MirroredBuf pick;    // trigger results; the host mirror is filled by ONE async copy per submit
-    hipEvent_t done = nullptr;
-    bool busy = false;
-    int n_specs = 0, cap = 0;
-    int64_t fv = -1, lv = -1, nwin = 0;
-  } slot[VP_MAX_INFLIGHT];
-  ValidationPass val;
-  PredictPass prd;
-  SweepPass swp;
-};
+using vp::pre_args;
+using vp::run_batch;
 
 namespace {
 
@@ -174,46 +39,6 @@ int free_slot(const vp_handle* h, int* slot) {
   VP_REQUIRE(i < VP_MAX_INFLIGHT, "all %d in-flight slots are busy", VP_MAX_INFLIGHT);
   *slot = i;
   return VP_OK;
-}
-
-// Until the scope ends the last layer writes to `y` (null: where it writes anyway) and the plan is told that the caller
-// keeps only the samples [out_lo, out_hi) of every window ((0, 0), the state outside any scope: all of them).
-struct OutputRedirect {
-  vp::Net& net;
-  float* const y_saved;
-  OutputRedirect(vp::Net& n, float* y, int out_lo = 0, int out_hi = 0) : net(n), y_saved(n.y) {
-    if (y) net.y = y;
-    net.out_lo = out_lo, net.out_hi = out_hi;
-  }
-  ~OutputRedirect() {
-    net.y = y_saved;
-    net.out_lo = net.out_hi = 0;
-  }
-};
-
-vp::PreArgs pre_args(const vp_handle* h, const float* src, int dense, long N, long step, long first, int preprocess) {
-  const vp::Net& net = h->net;
-  const vp::Tensor& in = net.tensors[net.input];
-  vp::PreArgs a{};
-  a.src = src;
-  a.N = N;
-  a.dense = dense;
-  a.T = net.in_samples;
-  a.step = step;
-  a.first_window = first;
-  a.preprocess = preprocess;
-  a.norm = net.cfg.norm;
-  a.per_comp = (net.model_kind == VP_MODEL_PHASENET) ? 1 : net.cfg.norm_amp_per_comp;
-  // SeisBench EQTransformer.annotate_batch_pre: norm_amp_per_comp divides by the per-channel PEAK whatever `norm`
-  // says; `norm` only selects peak / std for the amplitude taken over all three channels.
-  if (net.model_kind == VP_MODEL_EQTRANSFORMER && net.cfg.norm_amp_per_comp) a.norm = VP_NORM_PEAK;
-  a.taper = net.cfg.taper_samples;
-  a.norm_eps = net.cfg.norm_eps;
-  a.dst = in.p;
-  a.lsd = in.ls;
-  a.wsd = (long)in.win_stride();
-  a.flags = net.win_flags ? net.win_flags->d : nullptr;
-  return a;
 }
 
 // ---- first come, first served between the device contexts of one GPU (PhaseNet) ----------------------------------------------
@@ -266,6 +91,35 @@ struct ForwardTurn {  // RAII around one forward launch of a gated plan
   }
 };
 
+}  // namespace
+
+namespace vp {
+
+PreArgs pre_args(const vp_handle* h, const float* src, int dense, long N, long step, long first, int preprocess) {
+  const vp::Net& net = h->net;
+  const vp::Tensor& in = net.tensors[net.input];
+  vp::PreArgs a{};
+  a.src = src;
+  a.N = N;
+  a.dense = dense;
+  a.T = net.in_samples;
+  a.step = step;
+  a.first_window = first;
+  a.preprocess = preprocess;
+  a.norm = net.cfg.norm;
+  a.per_comp = (net.model_kind == VP_MODEL_PHASENET) ? 1 : net.cfg.norm_amp_per_comp;
+  // SeisBench EQTransformer.annotate_batch_pre: norm_amp_per_comp divides by the per-channel PEAK whatever `norm`
+  // says; `norm` only selects peak / std for the amplitude taken over all three channels.
+  if (net.model_kind == VP_MODEL_EQTRANSFORMER && net.cfg.norm_amp_per_comp) a.norm = VP_NORM_PEAK;
+  a.taper = net.cfg.taper_samples;
+  a.norm_eps = net.cfg.norm_eps;
+  a.dst = in.p;
+  a.lsd = in.ls;
+  a.wsd = (long)in.win_stride();
+  a.flags = net.win_flags ? net.win_flags->d : nullptr;
+  return a;
+}
+
 // One batch through annotate_batch_pre + the forward pass.  Plans whose first launch gathers and normalises the
 // windows itself take the window description with them; otherwise gather_normalize fills the input tensor first.
 int run_batch(vp_handle* h, const vp::PreArgs& pa, int nb) {
@@ -295,7 +149,7 @@ int run_batch(vp_handle* h, const vp::PreArgs& pa, int nb) {
   return rc;
 }
 
-}  // namespace
+}  // namespace vp
 
 extern "C" {
 
@@ -400,9 +254,7 @@ int vp_destroy(vp_handle* h) {
   h->d_out.release();
   h->d_tab.release();
   h->m_pick.release();
-  h->val.release();
-  h->prd.release();
-  h->swp.release();
+  vp::passes_release(h->passes);
   for (auto& sl : h->slot) {
     sl.pick.release();
     if (sl.done) (void)hipEventDestroy(sl.done);
@@ -454,402 +306,6 @@ int vp_forward(vp_handle* h, const float* x, int x_mem, int B, int preprocess, f
   VP_HIP(hipEventElapsedTime(&h->total_ms, h->ev[0], h->ev[1]));
   h->stage_ms[0] = h->stage_ms[2] = h->stage_ms[3] = 0.f;
   h->stage_ms[1] = h->total_ms;
-  return VP_OK;
-}
-
-}  // extern "C"
-
-namespace {
-
-// Room for `need` values in a results array of a validation or prediction pass, its first `used` values kept.  Growing
-// waits for the stream: the launches in flight write into the old block.
-template <class T>
-int grow_results(DevBuf<T>& b, size_t used, size_t need, hipStream_t s) {
-  if (need <= b.cap) return VP_OK;
-  VP_HIP(hipStreamSynchronize(s));
-  DevBuf<T> old = b;
-  b = DevBuf<T>();
-  const int rc = b.reserve(std::max(need, 2 * old.cap));
-  hipError_t e = hipSuccess;
-  if (rc == VP_OK && used) e = hipMemcpy(b.p, old.p, used * sizeof(T), hipMemcpyDeviceToDevice);
-  old.release();
-  if (rc != VP_OK) return rc;
-  VP_HIP(e);
-  return VP_OK;
-}
-
-// vp_validate_bank(_aug): generate, forward in chunks of max_batch, loss of all B windows, results appended.
-template <class Row>
-int validate_batch(vp_handle* h, vp_bank* bank, const Row* rows, int B, float sigma, int norm, const int* label_rows, double eps,
-                   float* pred_out_dev, const char* who) {
-  constexpr bool AUG = std::is_same<Row, vp_aug_row>::value;
-  VP_REQUIRE(h && bank, "%s: null argument", who);
-  if (h->net.model_kind != VP_MODEL_PHASENET) {
-    vp::set_error("%s: only a PhaseNet handle has a validation loss", who);
-    return VP_ERR_UNSUPPORTED;
-  }
-  ValidationPass& v = h->val;
-  VP_REQUIRE(v.open, "%s: no pass is open (vp_validate_begin)", who);
-  const vp::Bank& bk = *reinterpret_cast<const vp::Bank*>(bank);
-  VP_REQUIRE(bk.device == h->device, "%s: bank on device %d, handle on device %d", who, bk.device, h->device);
-  VP_REQUIRE(eps > 0.0, "%s: eps = %g must be > 0", who, eps);
-  vp::Net& net = h->net;
-  const int T = net.in_samples;
-  int rc;
-  if constexpr (AUG) {
-    rc = vp::bank_check_aug(bk, rows, B, T, sigma, norm, label_rows);
-  } else {
-    rc = vp::bank_check(bk, rows, B, T, sigma, norm, label_rows);
-  }
-  if (rc != VP_OK) return rc;
-  VP_HIP(hipSetDevice(h->device));
-
-  // ---- room for the batch, its rows and its results: nothing is enqueued before all of it stands -------------------------
-  const size_t w = (size_t)3 * T, bytes = (size_t)B * sizeof(Row);
-  if (!v.ev[0])
-    for (hipEvent_t& e : v.ev) VP_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  if ((size_t)B * w > v.x.cap || bytes > v.rows.cap) {
-    VP_HIP(hipStreamSynchronize(h->stream));  // launches in flight read the old blocks; every ring slot is idle afterwards
-    for (DevBuf<float>* b : {&v.x, &v.y, &v.pred})
-      if ((rc = b->reserve((size_t)B * w)) != VP_OK) return rc;
-    if ((rc = v.rows.reserve(std::max(bytes, (size_t)net.max_batch * sizeof(vp_aug_row)))) != VP_OK) return rc;
-  }
-  if ((rc = grow_results(v.batch, (size_t)v.n_batches, (size_t)v.n_batches + 1, h->stream)) != VP_OK) return rc;
-  if ((rc = grow_results(v.window, (size_t)v.n_windows, (size_t)v.n_windows + B, h->stream)) != VP_OK) return rc;
-  const int slot = (int)(v.launches % vp::RowRing::N);
-  if (v.ev_used[slot]) VP_HIP(hipEventSynchronize(v.ev[slot]));  // (eight launches back: long complete in the steady state)
-
-  // ---- generate -> forward -> loss ----------------------------------------------------------------------------------------
-  const Row* rd = static_cast<const Row*>(v.rows.stage(slot, rows, bytes, h->stream));
-  if (!rd) return VP_ERR_HIP;
-  if constexpr (AUG) {
-    rc = vp::bank_launch_aug(bk, rd, B, T, sigma, norm, label_rows, v.x.p, v.y.p, h->stream);
-  } else {
-    rc = vp::bank_launch(bk, rd, B, T, sigma, norm, label_rows, v.x.p, v.y.p, h->stream);
-  }
-  if (rc != VP_OK) return rc;
-  for (int b0 = 0; b0 < B; b0 += net.max_batch) {
-    const int nb = std::min(net.max_batch, B - b0);
-    const OutputRedirect to_pred(net, v.pred.p + (size_t)b0 * w);
-    if ((rc = run_batch(h, pre_args(h, v.x.p + (size_t)b0 * w, 1, 0, 0, 0, 0), nb)) != VP_OK) return rc;
-  }
-  rc = vp::vce_launch(v.pred.p, v.y.p, B, 3, T, eps, v.window.p + v.n_windows, v.batch.p + v.n_batches, h->stream);
-  if (rc != VP_OK) return rc;
-  VP_HIP(hipEventRecord(v.ev[slot], h->stream));
-  v.ev_used[slot] = true;
-  ++v.launches;
-  if (pred_out_dev)
-    VP_HIP(hipMemcpyAsync(pred_out_dev, v.pred.p, (size_t)B * w * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-  ++v.n_batches;
-  v.n_windows += B;
-  return VP_OK;
-}
-
-// One batch of a pass over a bank (vp_predict_bank, vp_sweep_bank), arguments already checked: room for the batch, its
-// rows and borders and -- room_for_results() -- its results, nothing enqueued before all of it stands; then the rows
-// staged, the B windows cut and normalised, the forward pass in chunks of max_batch, and reduce(pred, lo_dev, hi_dev) on
-// the (B, 3, T) probabilities (the borders null when there are none).
-template <class Room, class Reduce>
-int window_batch(vp_handle* h, WindowBatches& v, const vp::Bank& bk, const vp_plan_row* rows, const int32_t* lo,
-                 const int32_t* hi, int B, int norm, float* pred_out_dev, Room room_for_results, Reduce reduce) {
-  vp::Net& net = h->net;
-  const int T = net.in_samples;
-  int rc;
-  const size_t w = (size_t)net.n_out * T, row_bytes = (size_t)B * sizeof(vp_plan_row);
-  const size_t bytes = row_bytes + (lo ? (size_t)2 * B * sizeof(int32_t) : 0);
-  static_assert(sizeof(vp_plan_row) % alignof(int32_t) == 0, "the borders follow the rows in a ring slot");
-  if (!v.ev[0])
-    for (hipEvent_t& e : v.ev) VP_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  if ((size_t)B * w > v.x.cap || bytes > v.rows.cap) {
-    VP_HIP(hipStreamSynchronize(h->stream));  // launches in flight read the old blocks; every ring slot is idle afterwards
-    for (DevBuf<float>* b : {&v.x, &v.pred})
-      if ((rc = b->reserve((size_t)B * w)) != VP_OK) return rc;
-    if ((rc = v.rows.reserve(std::max(bytes, (size_t)net.max_batch * (sizeof(vp_plan_row) + 2 * sizeof(int32_t))))) != VP_OK)
-      return rc;
-  }
-  if ((rc = room_for_results()) != VP_OK) return rc;
-  const int slot = (int)(v.launches % vp::RowRing::N);
-  if (v.ev_used[slot]) VP_HIP(hipEventSynchronize(v.ev[slot]));  // (eight launches back: long complete in the steady state)
-
-  // ---- generate -> forward -> reduce ---------------------------------------------------------------------------------------
-  char* hs = static_cast<char*>(v.rows.host[slot]);
-  char* ds = static_cast<char*>(v.rows.dev[slot]);
-  memcpy(hs, rows, row_bytes);
-  if (lo) {
-    memcpy(hs + row_bytes, lo, (size_t)B * sizeof(int32_t));
-    memcpy(hs + row_bytes + (size_t)B * sizeof(int32_t), hi, (size_t)B * sizeof(int32_t));
-  }
-  VP_HIP(hipMemcpyAsync(ds, hs, bytes, hipMemcpyHostToDevice, h->stream));
-  if ((rc = vp::bank_launch_windows(bk, reinterpret_cast<const vp_plan_row*>(ds), B, T, norm, v.x.p, h->stream)) != VP_OK) return rc;
-  for (int b0 = 0; b0 < B; b0 += net.max_batch) {
-    const int nb = std::min(net.max_batch, B - b0);
-    const OutputRedirect to_pred(net, v.pred.p + (size_t)b0 * w);
-    if ((rc = run_batch(h, pre_args(h, v.x.p + (size_t)b0 * w, 1, 0, 0, 0, 0), nb)) != VP_OK) return rc;
-  }
-  const int* d_lo = lo ? reinterpret_cast<const int*>(ds + row_bytes) : nullptr;
-  if ((rc = reduce(v.pred.p, d_lo, d_lo ? d_lo + B : nullptr)) != VP_OK) return rc;
-  VP_HIP(hipEventRecord(v.ev[slot], h->stream));
-  v.ev_used[slot] = true;
-  ++v.launches;
-  if (pred_out_dev)
-    VP_HIP(hipMemcpyAsync(pred_out_dev, v.pred.p, (size_t)B * w * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-  return VP_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int vp_validate_begin(vp_handle* h) {
-  VP_REQUIRE(h != nullptr, "vp_validate_begin: null handle");
-  if (h->net.model_kind != VP_MODEL_PHASENET) {
-    vp::set_error("vp_validate_begin: only a PhaseNet handle has a validation loss");
-    return VP_ERR_UNSUPPORTED;
-  }
-  static_assert(sizeof(vp_aug_row) >= sizeof(vp_plan_row), "the row ring is sized for the larger row");
-  h->val.open = true;
-  h->val.n_batches = h->val.n_windows = 0;  // (launches of an abandoned pass run ahead of this one's on the same stream)
-  return VP_OK;
-}
-
-int vp_validate_bank(vp_handle* h, vp_bank* bank, const vp_plan_row* rows, int B, float sigma, int norm,
-                     const int* label_rows, double eps, float* pred_out_dev) {
-  return validate_batch(h, bank, rows, B, sigma, norm, label_rows, eps, pred_out_dev, "vp_validate_bank");
-}
-
-int vp_validate_bank_aug(vp_handle* h, vp_bank* bank, const vp_aug_row* rows, int B, float sigma, int norm,
-                         const int* label_rows, double eps, float* pred_out_dev) {
-  return validate_batch(h, bank, rows, B, sigma, norm, label_rows, eps, pred_out_dev, "vp_validate_bank_aug");
-}
-
-int vp_validate_end(vp_handle* h, double* batch_losses, long long cap, long long* n_batches, double* per_window,
-                    long long cap_windows, long long* n_windows) {
-  VP_REQUIRE(h != nullptr, "vp_validate_end: null handle");
-  ValidationPass& v = h->val;
-  VP_REQUIRE(v.open, "vp_validate_end: no pass is open (vp_validate_begin)");
-  VP_REQUIRE(cap >= 0 && cap_windows >= 0 && (cap == 0 || batch_losses) && (cap_windows == 0 || per_window),
-             "vp_validate_end: null output arrays");
-  VP_HIP(hipSetDevice(h->device));
-  const long long nb = std::min(cap, v.n_batches), nw = std::min(cap_windows, v.n_windows);
-  if (nb > 0) VP_HIP(hipMemcpyAsync(batch_losses, v.batch.p, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (nw > 0) VP_HIP(hipMemcpyAsync(per_window, v.window.p, (size_t)nw * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  VP_HIP(hipStreamSynchronize(h->stream));
-  if (n_batches) *n_batches = v.n_batches;
-  if (n_windows) *n_windows = v.n_windows;
-  v.open = false;
-  return VP_OK;
-}
-
-// The counterpart of the loop in the reference's predict_step (volpick/model/models.py:454-480, :881-906).
-int vp_predict_windows(vp_handle* h, const float* prob, int prob_mem, int B, int n_rows, int det_row, int p_row, int s_row,
-                       int det_mode, const int32_t* lo, const int32_t* hi, vp_predict_record* out) {
-  VP_REQUIRE(h && prob && out, "vp_predict_windows: null argument");
-  VP_REQUIRE(prob_mem == VP_MEM_HOST || prob_mem == VP_MEM_DEVICE, "vp_predict_windows: prob_mem %d", prob_mem);
-  VP_REQUIRE(((uintptr_t)prob & 3) == 0, "vp_predict_windows: prob must be 4-byte aligned");
-  const int T = h->net.in_samples;
-  int rc = vp::predict_check(B, n_rows, T, det_row, p_row, s_row, det_mode, lo, hi, "vp_predict_windows");
-  if (rc != VP_OK) return rc;
-  VP_HIP(hipSetDevice(h->device));
-  const size_t n_prob = (size_t)B * n_rows * T;
-  // scratch layout (floats): [prob copy if host][lo B][hi B][records B], every piece a multiple of 4 bytes
-  constexpr size_t rec_floats = sizeof(vp_predict_record) / sizeof(float);
-  static_assert(sizeof(vp_predict_record) % sizeof(float) == 0 && alignof(vp_predict_record) <= alignof(float), "record layout");
-  const size_t need = (prob_mem == VP_MEM_HOST ? n_prob : 0) + (size_t)B * (2 + rec_floats);
-  if ((rc = h->d_in.reserve(std::max(need, (size_t)h->net.max_batch * 3 * T))) != VP_OK) return rc;
-  float* p = h->d_in.p;
-  vp::PredictArgs a{};
-  a.prob = prob;
-  if (prob_mem == VP_MEM_HOST) {
-    VP_HIP(hipMemcpyAsync(p, prob, n_prob * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    a.prob = p;
-    p += n_prob;
-  }
-  int* d_lo = reinterpret_cast<int*>(p);
-  int* d_hi = d_lo + B;
-  a.out = reinterpret_cast<vp_predict_record*>(d_hi + B);
-  if (lo) {
-    VP_HIP(hipMemcpyAsync(d_lo, lo, B * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    VP_HIP(hipMemcpyAsync(d_hi, hi, B * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    a.lo = d_lo, a.hi = d_hi;
-  }
-  a.B = B, a.n_rows = n_rows, a.T = T;
-  a.det_row = det_row, a.p_row = p_row, a.s_row = s_row, a.det_mode = det_mode;
-  if ((rc = vp::predict_launch(a, h->stream)) != VP_OK) return rc;
-  VP_HIP(hipMemcpyAsync(out, a.out, (size_t)B * sizeof(vp_predict_record), hipMemcpyDeviceToHost, h->stream));
-  VP_HIP(hipStreamSynchronize(h->stream));
-  return VP_OK;
-}
-
-int vp_predict_begin(vp_handle* h) {
-  VP_REQUIRE(h != nullptr, "vp_predict_begin: null handle");
-  h->prd.open = true;
-  h->prd.n_windows = 0;  // (launches of an abandoned pass run ahead of this one's on the same stream)
-  return VP_OK;
-}
-
-// generate -> forward in chunks of max_batch -> the records of all B windows, appended.
-int vp_predict_bank(vp_handle* h, vp_bank* bank, const vp_plan_row* rows, const int32_t* lo, const int32_t* hi, int B,
-                    int norm, int det_row, int p_row, int s_row, float* pred_out_dev) {
-  VP_REQUIRE(h && bank, "vp_predict_bank: null argument");
-  PredictPass& v = h->prd;
-  VP_REQUIRE(v.open, "vp_predict_bank: no pass is open (vp_predict_begin)");
-  const vp::Bank& bk = *reinterpret_cast<const vp::Bank*>(bank);
-  VP_REQUIRE(bk.device == h->device, "vp_predict_bank: bank on device %d, handle on device %d", bk.device, h->device);
-  vp::Net& net = h->net;
-  const int T = net.in_samples;
-  const int det_mode = net.model_kind == VP_MODEL_PHASENET ? VP_DET_ONE_MINUS_NOISE : VP_DET_ROW;
-  int rc = vp::bank_check_windows(bk, rows, B, T, norm);
-  if (rc == VP_OK) rc = vp::predict_check(B, net.n_out, T, det_row, p_row, s_row, det_mode, lo, hi, "vp_predict_bank");
-  if (rc != VP_OK) return rc;
-  VP_HIP(hipSetDevice(h->device));
-
-  vp::PredictArgs a{};
-  a.B = B, a.n_rows = net.n_out, a.T = T;
-  a.det_row = det_row, a.p_row = p_row, a.s_row = s_row, a.det_mode = det_mode;
-  rc = window_batch(
-      h, v.io, bk, rows, lo, hi, B, norm, pred_out_dev,
-      [&] { return grow_results(v.rec, (size_t)v.n_windows, (size_t)v.n_windows + B, h->stream); },
-      [&](const float* pred, const int* d_lo, const int* d_hi) {
-        a.prob = pred, a.lo = d_lo, a.hi = d_hi;
-        a.out = v.rec.p + v.n_windows;
-        return vp::predict_launch(a, h->stream);
-      });
-  if (rc != VP_OK) return rc;
-  v.n_windows += B;
-  return VP_OK;
-}
-
-int vp_predict_end(vp_handle* h, vp_predict_record* out, long long cap, long long* n_windows) {
-  VP_REQUIRE(h != nullptr, "vp_predict_end: null handle");
-  PredictPass& v = h->prd;
-  VP_REQUIRE(v.open, "vp_predict_end: no pass is open (vp_predict_begin)");
-  VP_REQUIRE(cap >= 0 && (cap == 0 || out), "vp_predict_end: null output array");
-  VP_HIP(hipSetDevice(h->device));
-  const long long nw = std::min(cap, v.n_windows);
-  if (nw > 0) VP_HIP(hipMemcpyAsync(out, v.rec.p, (size_t)nw * sizeof(vp_predict_record), hipMemcpyDeviceToHost, h->stream));
-  VP_HIP(hipStreamSynchronize(h->stream));
-  if (n_windows) *n_windows = v.n_windows;
-  v.open = false;
-  return VP_OK;
-}
-
-// ---- task 0: the threshold sweep (sweep.hip) -----------------------------------------------------------------------------
-static void sweep_args(vp::SweepArgs& a, int B, int n_rows, int T, int p_row, int s_row, const float* thr_on,
-                       const float* thr_off, int NT, int K) {
-  a.B = B, a.n_rows = n_rows, a.T = T, a.p_row = p_row, a.s_row = s_row, a.NT = NT, a.K = K;
-  memcpy(a.thr_on, thr_on, NT * sizeof(float));
-  memcpy(a.thr_off, thr_off, NT * sizeof(float));
-}
-
-int vp_sweep_windows(vp_handle* h, const float* prob, int prob_mem, int B, int n_rows, int p_row, int s_row, const int32_t* lo,
-                     const int32_t* hi, const float* thr_on, const float* thr_off, int NT, int K, int32_t* count,
-                     int32_t* peak, float* value) {
-  VP_REQUIRE(h && prob && thr_on && thr_off && count && peak, "vp_sweep_windows: null argument");
-  VP_REQUIRE(prob_mem == VP_MEM_HOST || prob_mem == VP_MEM_DEVICE, "vp_sweep_windows: prob_mem %d", prob_mem);
-  VP_REQUIRE(((uintptr_t)prob & 3) == 0, "vp_sweep_windows: prob must be 4-byte aligned");
-  const int T = h->net.in_samples;
-  int rc = vp::sweep_check(B, n_rows, T, p_row, s_row, lo, hi, thr_on, thr_off, NT, K, "vp_sweep_windows");
-  if (rc != VP_OK) return rc;
-  VP_HIP(hipSetDevice(h->device));
-  const size_t n_prob = (size_t)B * n_rows * T, n_cnt = (size_t)B * 2 * NT, n_pk = n_cnt * K;
-  // scratch layout (4-byte words): [prob copy if host][lo B][hi B][count][peak][value if asked for]
-  const size_t need = (prob_mem == VP_MEM_HOST ? n_prob : 0) + (size_t)2 * B + n_cnt + n_pk * (value ? 2 : 1);
-  if ((rc = h->d_in.reserve(std::max(need, (size_t)h->net.max_batch * 3 * T))) != VP_OK) return rc;
-  float* p = h->d_in.p;
-  vp::SweepArgs a{};
-  sweep_args(a, B, n_rows, T, p_row, s_row, thr_on, thr_off, NT, K);
-  a.prob = prob;
-  if (prob_mem == VP_MEM_HOST) {
-    VP_HIP(hipMemcpyAsync(p, prob, n_prob * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    a.prob = p;
-    p += n_prob;
-  }
-  int* d_lo = reinterpret_cast<int*>(p);
-  int* d_hi = d_lo + B;
-  a.count = d_hi + B;
-  a.peak = a.count + n_cnt;
-  a.value = value ? reinterpret_cast<float*>(a.peak + n_pk) : nullptr;
-  if (lo) {
-    VP_HIP(hipMemcpyAsync(d_lo, lo, B * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    VP_HIP(hipMemcpyAsync(d_hi, hi, B * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    a.lo = d_lo, a.hi = d_hi;
-  }
-  if ((rc = vp::sweep_launch(a, h->stream)) != VP_OK) return rc;
-  VP_HIP(hipMemcpyAsync(count, a.count, n_cnt * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-  VP_HIP(hipMemcpyAsync(peak, a.peak, n_pk * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-  if (value) VP_HIP(hipMemcpyAsync(value, a.value, n_pk * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-  VP_HIP(hipStreamSynchronize(h->stream));
-  return VP_OK;
-}
-
-int vp_sweep_begin(vp_handle* h, const float* thr_on, const float* thr_off, int NT, int K, int keep_values) {
-  VP_REQUIRE(h && thr_on && thr_off, "vp_sweep_begin: null argument");
-  const vp::Net& net = h->net;
-  // (B, the rows and the borders are each batch's: 1, 0 / 1 and none stand in for them here)
-  const int rc = vp::sweep_check(1, net.n_out, net.in_samples, 0, 1, nullptr, nullptr, thr_on, thr_off, NT, K, "vp_sweep_begin");
-  if (rc != VP_OK) return rc;
-  SweepPass& v = h->swp;
-  v.NT = NT, v.K = K, v.keep_values = keep_values != 0;
-  memcpy(v.thr_on, thr_on, NT * sizeof(float));
-  memcpy(v.thr_off, thr_off, NT * sizeof(float));
-  v.open = true;
-  v.n_windows = 0;  // (launches of an abandoned pass run ahead of this one's on the same stream)
-  return VP_OK;
-}
-
-// generate -> forward in chunks of max_batch -> the picks of all B windows at every threshold, appended.
-int vp_sweep_bank(vp_handle* h, vp_bank* bank, const vp_plan_row* rows, const int32_t* lo, const int32_t* hi, int B, int norm,
-                  int p_row, int s_row, float* pred_out_dev) {
-  VP_REQUIRE(h && bank, "vp_sweep_bank: null argument");
-  SweepPass& v = h->swp;
-  VP_REQUIRE(v.open, "vp_sweep_bank: no pass is open (vp_sweep_begin)");
-  const vp::Bank& bk = *reinterpret_cast<const vp::Bank*>(bank);
-  VP_REQUIRE(bk.device == h->device, "vp_sweep_bank: bank on device %d, handle on device %d", bk.device, h->device);
-  vp::Net& net = h->net;
-  const int T = net.in_samples;
-  int rc = vp::bank_check_windows(bk, rows, B, T, norm);
-  if (rc == VP_OK) rc = vp::sweep_check(B, net.n_out, T, p_row, s_row, lo, hi, v.thr_on, v.thr_off, v.NT, v.K, "vp_sweep_bank");
-  if (rc != VP_OK) return rc;
-  VP_HIP(hipSetDevice(h->device));
-  const size_t per_cnt = (size_t)2 * v.NT, per_pk = per_cnt * v.K, nw = (size_t)v.n_windows;
-  vp::SweepArgs a{};
-  sweep_args(a, B, net.n_out, T, p_row, s_row, v.thr_on, v.thr_off, v.NT, v.K);
-  rc = window_batch(
-      h, v.io, bk, rows, lo, hi, B, norm, pred_out_dev,
-      [&] {
-        int r = grow_results(v.count, nw * per_cnt, (nw + B) * per_cnt, h->stream);
-        if (r == VP_OK) r = grow_results(v.peak, nw * per_pk, (nw + B) * per_pk, h->stream);
-        if (r == VP_OK && v.keep_values) r = grow_results(v.value, nw * per_pk, (nw + B) * per_pk, h->stream);
-        return r;
-      },
-      [&](const float* pred, const int* d_lo, const int* d_hi) {
-        a.prob = pred, a.lo = d_lo, a.hi = d_hi;
-        a.count = v.count.p + nw * per_cnt;
-        a.peak = v.peak.p + nw * per_pk;
-        a.value = v.keep_values ? v.value.p + nw * per_pk : nullptr;
-        return vp::sweep_launch(a, h->stream);
-      });
-  if (rc != VP_OK) return rc;
-  v.n_windows += B;
-  return VP_OK;
-}
-
-int vp_sweep_end(vp_handle* h, int32_t* count, int32_t* peak, float* value, long long cap_windows, long long* n_windows) {
-  VP_REQUIRE(h != nullptr, "vp_sweep_end: null handle");
-  SweepPass& v = h->swp;
-  VP_REQUIRE(v.open, "vp_sweep_end: no pass is open (vp_sweep_begin)");
-  VP_REQUIRE(cap_windows >= 0 && (cap_windows == 0 || (count && peak)), "vp_sweep_end: null output arrays");
-  VP_REQUIRE(!value || v.keep_values, "vp_sweep_end: the pass was opened without keep_values");
-  VP_HIP(hipSetDevice(h->device));
-  const size_t nw = (size_t)std::min(cap_windows, v.n_windows), per_cnt = (size_t)2 * v.NT, per_pk = per_cnt * v.K;
-  if (nw > 0) {
-    VP_HIP(hipMemcpyAsync(count, v.count.p, nw * per_cnt * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    VP_HIP(hipMemcpyAsync(peak, v.peak.p, nw * per_pk * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    if (value) VP_HIP(hipMemcpyAsync(value, v.value.p, nw * per_pk * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-  }
-  VP_HIP(hipStreamSynchronize(h->stream));
-  if (n_windows) *n_windows = v.n_windows;
-  v.open = false;
   return VP_OK;
 }
 
@@ -1264,57 +720,6 @@ int vp_pick(vp_handle* h, const float* trace, int trace_mem, int64_t n, float th
     peak[i] = t_pk[i];
     value[i] = t_v[i];
   }
-  return VP_OK;
-}
-
-// Replaces the per-sample Python loop of the reference's evaluate() (eval_taks0.py:96-142).
-int vp_pick_windows(vp_handle* h, const float* prob, int prob_mem, int B, int n_rows, int row, const int32_t* lo,
-                    const int32_t* hi, float thr_on, float thr_off, int K, int32_t* count, int32_t* peak,
-                    float* value) {
-  VP_REQUIRE(h && prob && count && peak && value, "null argument");
-  VP_REQUIRE(B > 0 && K > 0 && n_rows > 0 && row >= 0 && row < n_rows, "bad shape arguments");
-  VP_REQUIRE(thr_off <= thr_on, "thr_off must not exceed thr_on");
-  VP_HIP(hipSetDevice(h->device));
-  const int T = h->net.in_samples;
-  const size_t n_prob = (size_t)B * n_rows * T;
-  // scratch layout (floats): [prob copy if host][lo B][hi B][count B][peak B*K][value B*K]
-  const size_t need = (prob_mem == VP_MEM_HOST ? n_prob : 0) + (size_t)B * 3 + (size_t)B * K * 2 + 64;
-  int rc = h->d_in.reserve(std::max(need, (size_t)h->net.max_batch * 3 * T));
-  if (rc != VP_OK) return rc;
-  float* p = h->d_in.p;
-  const float* d_prob = prob;
-  if (prob_mem == VP_MEM_HOST) {
-    VP_HIP(hipMemcpyAsync(p, prob, n_prob * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    d_prob = p;
-    p += n_prob;
-  }
-  int* d_lo = reinterpret_cast<int*>(p);
-  int* d_hi = d_lo + B;
-  int* d_count = d_hi + B;
-  int* d_peak = d_count + B;
-  float* d_value = reinterpret_cast<float*>(d_peak + (size_t)B * K);
-  if (lo) VP_HIP(hipMemcpyAsync(d_lo, lo, B * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  if (hi) VP_HIP(hipMemcpyAsync(d_hi, hi, B * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  vp::WindowPickArgs a{};
-  a.prob = d_prob;
-  a.B = B;
-  a.n_rows = n_rows;
-  a.T = T;
-  a.row = row;
-  a.lo = lo ? d_lo : nullptr;
-  a.hi = hi ? d_hi : nullptr;
-  a.thr_on = thr_on;
-  a.thr_off = thr_off;
-  a.K = K;
-  a.count = d_count;
-  a.peak = d_peak;
-  a.value = d_value;
-  VP_HIP(hipMemsetAsync(d_count, 0, B * sizeof(int), h->stream));
-  vp::launch_window_pick(a, h->stream);
-  VP_HIP(hipMemcpyAsync(count, d_count, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  VP_HIP(hipMemcpyAsync(peak, d_peak, (size_t)B * K * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  VP_HIP(hipMemcpyAsync(value, d_value, (size_t)B * K * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-  VP_HIP(hipStreamSynchronize(h->stream));
   return VP_OK;
 }
 

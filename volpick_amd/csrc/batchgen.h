@@ -1,6 +1,8 @@
 // Training-batch generation from a device-resident waveform bank (batchgen.hip): the pieces the trainer's
-// vp_train_step_bank (train_phasenet.hip) shares with vp_bank_make_batch.
+// vp_train_step_bank (train_phasenet.hip) and the passes over a bank (passes.hip) share with vp_bank_make_batch.
 #pragma once
+#include <initializer_list>
+
 #include "vp_common.h"
 
 namespace vp {
@@ -15,9 +17,36 @@ struct RowRing {
   size_t cap = 0;  // bytes per slot
   // Every slot is idle when this is called.  Grows the slots to hold `bytes`.
   int reserve(size_t bytes);
-  // rows -> host[slot] -> dev[slot] (async on s); returns dev[slot]
-  void* stage(int slot, const void* rows, size_t bytes, hipStream_t s);
+  struct Piece {
+    const void* p;
+    size_t bytes;
+  };
+  // The pieces, back to back -> host[slot] -> dev[slot] (one copy, async on s); returns dev[slot], null (with the error
+  // set) when the copy fails.
+  void* stage(int slot, std::initializer_list<Piece> pieces, hipStream_t s);
   ~RowRing();
+};
+
+// A RowRing that frees its own slots: use number u takes slot u % N, which is idle again behind the event that retire()
+// recorded when the slot was used last.  acquire -> stage -> the launches that read the slot -> retire; a use that fails
+// before retire() leaves the slot to the next one.  (The trainer frees the slots of its RowRing behind its step events,
+// which it keeps for other reasons: train_phasenet.hip.)
+struct StagingRing {
+  using Piece = RowRing::Piece;
+  // The next slot, idle and at least `bytes` large.  Slots that are too small are grown to max(bytes, at_least) once
+  // every used slot is idle.  Waits on the slots' events alone: right for any stream the uses were launched on.
+  int acquire(size_t bytes, size_t at_least = 0);
+  void* stage(std::initializer_list<Piece> pieces, hipStream_t s) { return ring.stage(slot(), pieces, s); }
+  // Behind the last launch on s that reads the slot.
+  int retire(hipStream_t s);
+  ~StagingRing();
+
+ private:
+  RowRing ring;
+  hipEvent_t ev[RowRing::N] = {};  // created by the first acquire()
+  bool ev_used[RowRing::N] = {};
+  long long uses = 0;
+  int slot() const { return (int)(uses % RowRing::N); }
 };
 
 struct Bank {
@@ -29,10 +58,7 @@ struct Bank {
   long long* len_dev = nullptr;   // [n_traces]
   double* onset_dev = nullptr;    // [n_traces][4]: P, P, S, S in trace samples, NaN = no pick
   std::vector<long long> len;     // host copy of the written traces' lengths (row validation)
-  RowRing ring;                   // vp_bank_make_batch's staging
-  hipEvent_t ev[RowRing::N] = {}; // behind the kernel that read ring slot i
-  bool ev_used[RowRing::N] = {};
-  long long batches = 0;
+  StagingRing ring;               // vp_bank_make_batch's staging
   ~Bank();
 };
 
@@ -45,8 +71,8 @@ int bank_launch(const Bank& bk, const vp_plan_row* rows_dev, int B, int T, float
 int bank_check_windows(const Bank& bk, const vp_plan_row* rows, int B, int T, int norm);
 int bank_launch_windows(const Bank& bk, const vp_plan_row* rows_dev, int B, int T, int norm, float* x, hipStream_t s);
 // The same for augmented rows (vp_bank_make_batch_aug): bank_check's arguments plus every field of every vp_aug_row.
-int bank_check_aug(const Bank& bk, const vp_aug_row* rows, int B, int T, float sigma, int norm, const int* label_rows);
-int bank_launch_aug(const Bank& bk, const vp_aug_row* rows_dev, int B, int T, float sigma, int norm, const int* label_rows,
-                    float* x, float* y, hipStream_t s);
+int bank_check(const Bank& bk, const vp_aug_row* rows, int B, int T, float sigma, int norm, const int* label_rows);
+int bank_launch(const Bank& bk, const vp_aug_row* rows_dev, int B, int T, float sigma, int norm, const int* label_rows,
+                float* x, float* y, hipStream_t s);
 
 }  // namespace vp

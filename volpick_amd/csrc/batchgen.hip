@@ -412,8 +412,12 @@ int RowRing::reserve(size_t bytes) {
   return VP_OK;
 }
 
-void* RowRing::stage(int slot, const void* rows, size_t bytes, hipStream_t s) {
-  memcpy(host[slot], rows, bytes);
+void* RowRing::stage(int slot, std::initializer_list<Piece> pieces, hipStream_t s) {
+  size_t bytes = 0;
+  for (const Piece& piece : pieces) {
+    if (piece.bytes) memcpy(static_cast<char*>(host[slot]) + bytes, piece.p, piece.bytes);
+    bytes += piece.bytes;
+  }
   if (hipMemcpyAsync(dev[slot], host[slot], bytes, hipMemcpyHostToDevice, s) != hipSuccess) {
     set_error("plan rows: hipMemcpyAsync failed");
     return nullptr;
@@ -428,11 +432,34 @@ RowRing::~RowRing() {
   }
 }
 
+int StagingRing::acquire(size_t bytes, size_t at_least) {
+  if (!ev[0])
+    for (hipEvent_t& e : ev) VP_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  if (bytes > ring.cap) {  // every slot idle before the ring is reallocated
+    for (int i = 0; i < RowRing::N; ++i)
+      if (ev_used[i]) VP_HIP(hipEventSynchronize(ev[i]));
+    return ring.reserve(std::max(bytes, at_least));
+  }
+  // the launches that read this slot last (and so the copy into it) have run: N uses back, long so in the steady state
+  if (ev_used[slot()]) VP_HIP(hipEventSynchronize(ev[slot()]));
+  return VP_OK;
+}
+
+int StagingRing::retire(hipStream_t s) {
+  VP_HIP(hipEventRecord(ev[slot()], s));
+  ev_used[slot()] = true;
+  ++uses;
+  return VP_OK;
+}
+
+StagingRing::~StagingRing() {
+  for (hipEvent_t e : ev)
+    if (e) (void)hipEventDestroy(e);
+}
+
 Bank::~Bank() {
   for (void* p : {(void*)data, (void*)off_dev, (void*)len_dev, (void*)onset_dev})
     if (p) (void)hipFree(p);
-  for (hipEvent_t e : ev)
-    if (e) (void)hipEventDestroy(e);
 }
 
 namespace {
@@ -532,7 +559,7 @@ int bank_launch_windows(const Bank& bk, const vp_plan_row* rows_dev, int B, int 
   return launch(bank_window_kernel, "bank_window_kernel", bk, rows_dev, nullptr, B, T, 1.f, norm, unused_label_rows, x, nullptr, s);
 }
 
-int bank_check_aug(const Bank& bk, const vp_aug_row* rows, int B, int T, float sigma, int norm, const int* label_rows) {
+int bank_check(const Bank& bk, const vp_aug_row* rows, int B, int T, float sigma, int norm, const int* label_rows) {
   VP_REQUIRE(rows, "bank batch: null rows");
   int rc = args_check(B, T, sigma, norm, label_rows);
   if (rc != VP_OK) return rc;
@@ -578,7 +605,7 @@ int bank_check_aug(const Bank& bk, const vp_aug_row* rows, int B, int T, float s
   return VP_OK;
 }
 
-int bank_launch_aug(const Bank& bk, const vp_aug_row* rows_dev, int B, int T, float sigma, int norm, const int* label_rows,
+int bank_launch(const Bank& bk, const vp_aug_row* rows_dev, int B, int T, float sigma, int norm, const int* label_rows,
                     float* x, float* y, hipStream_t s) {
   return launch(bank_aug_kernel, "bank_aug_kernel", bk, nullptr, rows_dev, B, T, sigma, norm, label_rows, x, y, s);
 }
@@ -589,47 +616,21 @@ using namespace vp;
 
 namespace {
 
-int check_rows(const Bank& bk, const vp_plan_row* rows, int B, int T, float sigma, int norm, const int* lr) {
-  return bank_check(bk, rows, B, T, sigma, norm, lr);
-}
-int check_rows(const Bank& bk, const vp_aug_row* rows, int B, int T, float sigma, int norm, const int* lr) {
-  return bank_check_aug(bk, rows, B, T, sigma, norm, lr);
-}
-int launch_rows(const Bank& bk, const vp_plan_row* rd, int B, int T, float sigma, int norm, const int* lr, float* x, float* y,
-                hipStream_t s) {
-  return bank_launch(bk, rd, B, T, sigma, norm, lr, x, y, s);
-}
-int launch_rows(const Bank& bk, const vp_aug_row* rd, int B, int T, float sigma, int norm, const int* lr, float* x, float* y,
-                hipStream_t s) {
-  return bank_launch_aug(bk, rd, B, T, sigma, norm, lr, x, y, s);
-}
-
 // vp_bank_make_batch(_aug): rows staged through the bank's ring, slot k reused once the kernel that last read it has run.
 template <class Row>
 int make_batch(Bank& bk, const Row* rows, int B, int T, float sigma, int norm, const int* label_rows, float* x, float* y,
                void* stream) {
-  const int rc = check_rows(bk, rows, B, T, sigma, norm, label_rows);
+  const int rc = bank_check(bk, rows, B, T, sigma, norm, label_rows);
   if (rc != VP_OK) return rc;
   VP_HIP(hipSetDevice(bk.device));
-  const int slot = (int)(bk.batches % RowRing::N);
   const size_t bytes = (size_t)B * sizeof(Row);
-  if (bytes > bk.ring.cap) {  // every slot idle before the ring is reallocated
-    for (int i = 0; i < RowRing::N; ++i)
-      if (bk.ev_used[i]) VP_HIP(hipEventSynchronize(bk.ev[i]));
-    const int r = bk.ring.reserve(bytes);
-    if (r != VP_OK) return r;
-  } else if (bk.ev_used[slot]) {
-    VP_HIP(hipEventSynchronize(bk.ev[slot]));  // the kernel that read this slot last (and so the copy into it) has run
-  }
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const Row* rd = static_cast<const Row*>(bk.ring.stage(slot, rows, bytes, s));
-  if (!rd) return VP_ERR_HIP;
-  const int r = launch_rows(bk, rd, B, T, sigma, norm, label_rows, x, y, s);
+  int r = bk.ring.acquire(bytes);
   if (r != VP_OK) return r;
-  VP_HIP(hipEventRecord(bk.ev[slot], s));
-  bk.ev_used[slot] = true;
-  ++bk.batches;
-  return VP_OK;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const Row* rd = static_cast<const Row*>(bk.ring.stage({{rows, bytes}}, s));
+  if (!rd) return VP_ERR_HIP;
+  if ((r = bank_launch(bk, rd, B, T, sigma, norm, label_rows, x, y, s)) != VP_OK) return r;
+  return bk.ring.retire(s);
 }
 
 }  // namespace
@@ -648,7 +649,6 @@ int vp_bank_create(int device_id, long long n_traces, long long n_floats_total, 
   VP_HIP(hipMalloc((void**)&bk->off_dev, (size_t)n_traces * sizeof(long long)));
   VP_HIP(hipMalloc((void**)&bk->len_dev, (size_t)n_traces * sizeof(long long)));
   VP_HIP(hipMalloc((void**)&bk->onset_dev, (size_t)n_traces * 4 * sizeof(double)));
-  for (hipEvent_t& e : bk->ev) VP_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   *out = reinterpret_cast<vp_bank*>(bk.release());
   return VP_OK;
 }

@@ -1,5 +1,5 @@
 // Per-window scores of the pick-benchmark tasks 1-3 from device-resident probabilities (predict.hip): what
-// vp_predict_windows and the vp_predict_bank pass (api.hip) launch.
+// vp_predict_windows and the vp_predict_bank pass (passes.hip) launch.
 //
 // score_p_or_s = p_max / s_max is NOT formed here: the record carries the two maxima and the host divides them in
 // float32 (numpy's correctly rounded quotient, x / 0 = inf and 0 / 0 = NaN included) -- volpick_amd/evaluate.py.

@@ -1,5 +1,5 @@
 // Pick-benchmark task 0: the picks of every threshold of a sweep from device-resident probabilities in one launch
-// (sweep.hip): what vp_sweep_windows and the vp_sweep_bank pass (api.hip) launch.
+// (sweep.hip): what vp_sweep_windows and the vp_sweep_bank pass (passes.hip) launch.
 #pragma once
 #include "vp_common.h"
 

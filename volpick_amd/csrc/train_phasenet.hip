@@ -257,7 +257,7 @@ RowKernels row_kernels() {
 }
 
 // A device array that belongs to its holder: allocated (and zeroed where something reads it before a kernel has written it)
-// in one statement, freed with the holder.  (DevBuf of api.hip is the other thing: it regrows, may carry a pinned host
+// in one statement, freed with the holder.  (DevBuf of api_handle.h is the other thing: it regrows, may carry a pinned host
 // mirror, and is released by hand.)
 template <class T>
 struct DevArray {
@@ -323,6 +323,7 @@ struct Trainer {
   DevArray<double> head_stage;  // [64][28]
   DevArray<float> x_dev, y_dev;  // staging for host inputs, and where vp_train_step_bank generates its batch
   RowRing plan_rows;             // vp_train_step_bank(_aug)'s rows: slot seq % EV_RING, free again at ev_inputs of that slot
+                                 // (the bare ring, not a StagingRing: the step events below exist anyway and free the slots too)
   DevArray<float> p_dev;         // predictions of the last step
   long step = 0;
   float beta1 = 0.9f, beta2 = 0.999f, adam_eps = 1e-8f, bn_eps = 1e-3f, bn_momentum = 0.1f, loss_eps = 1e-5f;
@@ -947,7 +948,7 @@ int step_bank(Trainer& tr, const Bank& bk, const vp_plan_row* rows, const vp_aug
   VP_REQUIRE(B >= 2 && B <= tr.max_batch, "vp_train_step_bank: batch %d outside [2, %d]", B, tr.max_batch);
   VP_REQUIRE(bk.device == tr.device, "vp_train_step_bank: bank on device %d, trainer on device %d", bk.device, tr.device);
   static_assert(RowRing::N == Trainer::EV_RING, "one plan-row slot per step event");
-  int rc = aug ? bank_check_aug(bk, aug, B, T0, sigma, norm, label_rows) : bank_check(bk, rows, B, T0, sigma, norm, label_rows);
+  int rc = aug ? bank_check(bk, aug, B, T0, sigma, norm, label_rows) : bank_check(bk, rows, B, T0, sigma, norm, label_rows);
   if (rc != VP_OK) return rc;
   VP_HIP(hipSetDevice(tr.device));
   if (!tr.plan_rows.cap) {  // once, for either kind of row: a regrowth would have to wait for every slot
@@ -958,10 +959,10 @@ int step_bank(Trainer& tr, const Bank& bk, const vp_plan_row* rows, const vp_aug
   // that read the slot's device copy, which ran after the copy that read the host slot
   const int slot = (int)(tr.seq % Trainer::EV_RING);
   if (tr.ev_inputs_seq[slot] >= 0) VP_HIP(hipEventSynchronize(tr.ev_inputs[slot]));
-  const void* rd = aug ? tr.plan_rows.stage(slot, aug, (size_t)B * sizeof(vp_aug_row), tr.stream)
-                       : tr.plan_rows.stage(slot, rows, (size_t)B * sizeof(vp_plan_row), tr.stream);
+  const void* rd = aug ? tr.plan_rows.stage(slot, {{aug, (size_t)B * sizeof(vp_aug_row)}}, tr.stream)
+                       : tr.plan_rows.stage(slot, {{rows, (size_t)B * sizeof(vp_plan_row)}}, tr.stream);
   if (!rd) return VP_ERR_HIP;
-  rc = aug ? bank_launch_aug(bk, static_cast<const vp_aug_row*>(rd), B, T0, sigma, norm, label_rows, tr.x_dev, tr.y_dev,
+  rc = aug ? bank_launch(bk, static_cast<const vp_aug_row*>(rd), B, T0, sigma, norm, label_rows, tr.x_dev, tr.y_dev,
                              tr.stream)
            : bank_launch(bk, static_cast<const vp_plan_row*>(rd), B, T0, sigma, norm, label_rows, tr.x_dev, tr.y_dev,
                          tr.stream);

@@ -1,5 +1,5 @@
 // Vector cross entropy of device-resident predictions in float64 (valloss.hip): what vp_vce_loss and the
-// vp_validate_bank entry points (api.hip) launch.
+// vp_validate_bank entry points (passes.hip) launch.
 #pragma once
 #include "vp_common.h"
 

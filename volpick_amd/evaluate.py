@@ -29,6 +29,78 @@ import numpy as np
 from . import _lib
 
 
+def _predict_rows(model):
+    """(det_row, p_row, s_row, det_mode) of the model's (B, 3, T) output."""
+    if model.name == "PhaseNet":
+        return model.labels.index("N"), model.labels.index("P"), model.labels.index("S"), _lib.VP_DET_ONE_MINUS_NOISE
+    return 0, 1, 2, _lib.VP_DET_ROW  # EQTransformer returns (detection, P, S)
+
+
+def _sweep_rows(model):
+    return _predict_rows(model)[1:3]
+
+
+def _borders(window_borders, n):
+    if window_borders is None:
+        return None, None
+    wb = np.asarray(window_borders, dtype=np.int32).reshape(n, 2)
+    return np.ascontiguousarray(wb[:, 0]), np.ascontiguousarray(wb[:, 1])
+
+
+def _border_ptrs(lo, hi, b0, B):
+    """Pointers to the borders of the windows [b0, b0 + B) for a C call; None each without borders."""
+    return (None, None) if lo is None else (_lib.ptr(lo[b0 : b0 + B]), _lib.ptr(hi[b0 : b0 + B]))
+
+
+def _forward_batches(model, X, window_borders, batch_size):
+    """X: (N, 3, T) windows through the model in batches of ``batch_size``.  Yields ``(b0, B, y, lo, hi)`` per batch: its
+    first window and size, its (B, 3, T) probabilities on the device, and the pointers to its borders (None without)."""
+    torch = __import__("torch")
+    lo, hi = _borders(window_borders, len(X))
+    for b0 in range(0, len(X), batch_size):
+        y = model._forward_raw(torch.from_numpy(X[b0 : b0 + batch_size]).to(model.device))
+        B = y.shape[0]
+        yield (b0, B, y) + _border_ptrs(lo, hi, b0, B)
+
+
+def prediction_tensor(model, B):
+    """A fresh (B, 3, T) float32 tensor on the model's device for a pass to write a batch's probabilities to.  The pass
+    writes on the handle's stream, so whatever used this memory last on torch's stream is waited for here."""
+    torch = __import__("torch")
+    dev = torch.device("cuda", model._device_index)
+    out = torch.empty((B, 3, model.in_samples), dtype=torch.float32, device=dev)
+    torch.cuda.current_stream(dev).synchronize()
+    return out
+
+
+def _bank_pass(model, bank, rows, window_borders, batch_size, predictions, name, begin, batch, end):
+    """One pass over a bank on the GPU, its three C calls (``name``_begin / _bank / _end) supplied by the caller, each
+    returning its code: ``begin(h)``; per ``batch_size`` of the plan ``rows`` (``as_rows``' array)
+    ``batch(h, rows, lo, hi, B, out)`` -- pointers, ``lo`` / ``hi`` None without borders, ``out`` a fresh prediction tensor
+    with ``predictions`` and else None; and in any case ``end(h, n, n_windows)``.  Returns the prediction tensors."""
+    n = len(rows)
+    lo, hi = _borders(window_borders, n)
+    if model._device_index is None:
+        model.cuda(bank.device)
+    h = model._ensure_handle()
+    preds = []
+    _lib.check(begin(h), name + "_begin")
+    try:
+        for b0 in range(0, n, batch_size):
+            r = rows[b0 : b0 + batch_size]
+            B = len(r)
+            if predictions:
+                preds.append(prediction_tensor(model, B))
+            out = C.c_void_p(preds[-1].data_ptr()) if predictions else None
+            _lib.check(batch(h, _lib.ptr(r), *_border_ptrs(lo, hi, b0, B), B, out), name + "_bank")
+    finally:
+        nw = C.c_longlong()
+        rc = end(h, n, C.byref(nw))
+    _lib.check(rc, name + "_end")
+    assert nw.value == n
+    return preds
+
+
 def evaluate_windows(model, X, window_borders=None, threshold=0.3, batch_size=1024, max_picks=64):
     """X: (N, 3, T) float32, normalised as the reference's generator does
     (``Normalize(demean_axis=-1, amp_norm_axis=-1, amp_norm_type=model.norm)``, eval_taks0.py:458-469).
@@ -39,55 +111,32 @@ def evaluate_windows(model, X, window_borders=None, threshold=0.3, batch_size=10
     (pick samples are local to the window border start, ascending), the first four entries of the
     reference's ``merged_predictions`` before the per-trace ``start_sample`` offset is added.
     """
-    torch = __import__("torch")
     lib = _lib.load()
     X = np.ascontiguousarray(X, dtype=np.float32)
-    n = X.shape[0]
-    p_thr, s_thr = (threshold if isinstance(threshold, (list, tuple)) else (threshold, threshold))
-    if model.name == "PhaseNet":
-        rows = {"P": model.labels.index("P"), "S": model.labels.index("S")}
-    else:  # EQTransformer returns (detection, P, S)
-        rows = {"P": 1, "S": 2}
-    lo = hi = None
-    if window_borders is not None:
-        wb = np.asarray(window_borders, dtype=np.int32).reshape(n, 2)
-        lo, hi = np.ascontiguousarray(wb[:, 0]), np.ascontiguousarray(wb[:, 1])
-    out = {ph: ([], []) for ph in rows}
+    thresholds = threshold if isinstance(threshold, (list, tuple)) else (threshold, threshold)
+    out = ([], []), ([], [])  # per phase: picks, scores
     h = model._ensure_handle()
-    for b0 in range(0, n, batch_size):
-        xb = torch.from_numpy(X[b0 : b0 + batch_size]).to(model.device)
-        y = model._forward_raw(xb)  # (B, 3, T) on the device
-        B = y.shape[0]
-        for ph, thr in (("P", p_thr), ("S", s_thr)):
+    for _, B, y, lo, hi in _forward_batches(model, X, window_borders, batch_size):
+        for (picks, scores), row, thr in zip(out, _sweep_rows(model), thresholds):
             count = np.zeros(B, np.int32)
             peak = np.zeros((B, max_picks), np.int32)
             value = np.zeros((B, max_picks), np.float32)
-            plo = lo[b0 : b0 + B].ctypes.data_as(C.c_void_p) if lo is not None else None
-            phi = hi[b0 : b0 + B].ctypes.data_as(C.c_void_p) if hi is not None else None
-            _lib.check(lib.vp_pick_windows(h, C.c_void_p(y.data_ptr()), _lib.VP_MEM_DEVICE, B, 3, rows[ph], plo, phi,
-                                           float(thr), float(thr) / 2.0, max_picks,
-                                           count.ctypes.data_as(C.c_void_p), peak.ctypes.data_as(C.c_void_p),
-                                           value.ctypes.data_as(C.c_void_p)), "vp_pick_windows")
+            _lib.check(lib.vp_pick_windows(h, C.c_void_p(y.data_ptr()), _lib.VP_MEM_DEVICE, B, 3, row, lo, hi, float(thr),
+                                           float(thr) / 2.0, max_picks, _lib.ptr(count), _lib.ptr(peak), _lib.ptr(value)),
+                       "vp_pick_windows")
             if (count > max_picks).any():
                 raise RuntimeError(f"more than max_picks={max_picks} triggers in a window; raise max_picks")
             for i in range(B):
                 k = count[i]
                 order = np.argsort(peak[i, :k], kind="stable")
-                out[ph][0].append(peak[i, :k][order].astype(np.int64))
-                out[ph][1].append(value[i, :k][order])
-    return [out["P"][0], out["P"][1], out["S"][0], out["S"][1]]
+                picks.append(peak[i, :k][order].astype(np.int64))
+                scores.append(value[i, :k][order])
+    return [out[0][0], out[0][1], out[1][0], out[1][1]]
 
 
 # ---- pick-benchmark tasks 1-3 ------------------------------------------------------------------------------------------
 RECORD = np.dtype([("det", np.float32), ("p_max", np.float32), ("s_max", np.float32), ("p_arg", np.int32), ("s_arg", np.int32)])
 assert RECORD.itemsize == C.sizeof(_lib.VpPredictRecord)
-
-
-def _predict_rows(model):
-    """(det_row, p_row, s_row, det_mode) of the model's (B, 3, T) output."""
-    if model.name == "PhaseNet":
-        return model.labels.index("N"), model.labels.index("P"), model.labels.index("S"), _lib.VP_DET_ONE_MINUS_NOISE
-    return 0, 1, 2, _lib.VP_DET_ROW  # EQTransformer returns (detection, P, S)
 
 
 def _scores(rec):
@@ -97,34 +146,19 @@ def _scores(rec):
     return rec["det"].copy(), p_or_s, rec["p_arg"].astype(np.int64), rec["s_arg"].astype(np.int64)
 
 
-def _borders(window_borders, n):
-    if window_borders is None:
-        return None, None
-    wb = np.asarray(window_borders, dtype=np.int32).reshape(n, 2)
-    return np.ascontiguousarray(wb[:, 0]), np.ascontiguousarray(wb[:, 1])
-
-
 def predict_windows(model, X, window_borders=None, batch_size=1024):
     """``predict_step`` of the reference on X: (N, 3, T) float32 windows, cut and normalised as its generator does.
     window_borders: (N, 2) int [start, end) local sample ranges, or None for whole windows.
 
     Returns ``(score_detection, score_p_or_s, p_sample, s_sample)``: float32, float32, int64, int64 arrays of N, the samples
     local to the border start.  PhaseNet: ``max(1 - noise)``; EQTransformer: the maximum of its detection trace."""
-    torch = __import__("torch")
     lib = _lib.load()
     X = np.ascontiguousarray(X, dtype=np.float32)
-    n = X.shape[0]
-    lo, hi = _borders(window_borders, n)
-    det_row, p_row, s_row, mode = _predict_rows(model)
-    rec = np.zeros(n, RECORD)
+    rec = np.zeros(len(X), RECORD)
     h = model._ensure_handle()
-    for b0 in range(0, n, batch_size):
-        y = model._forward_raw(torch.from_numpy(X[b0 : b0 + batch_size]).to(model.device))  # (B, 3, T) on the device
-        B = y.shape[0]
-        plo = lo[b0 : b0 + B].ctypes.data_as(C.c_void_p) if lo is not None else None
-        phi = hi[b0 : b0 + B].ctypes.data_as(C.c_void_p) if hi is not None else None
-        _lib.check(lib.vp_predict_windows(h, C.c_void_p(y.data_ptr()), _lib.VP_MEM_DEVICE, B, 3, det_row, p_row, s_row, mode,
-                                          plo, phi, rec[b0 : b0 + B].ctypes.data_as(C.c_void_p)), "vp_predict_windows")
+    for b0, B, y, lo, hi in _forward_batches(model, X, window_borders, batch_size):
+        _lib.check(lib.vp_predict_windows(h, C.c_void_p(y.data_ptr()), _lib.VP_MEM_DEVICE, B, 3, *_predict_rows(model), lo, hi,
+                                          _lib.ptr(rec[b0 : b0 + B])), "vp_predict_windows")
     return _scores(rec)
 
 
@@ -137,36 +171,11 @@ def predict_bank(model, bank, rows, window_borders=None, batch_size=1024, predic
 
     lib = _lib.load()
     rows = as_rows(rows)
-    n = len(rows)
-    lo, hi = _borders(window_borders, n)
-    det_row, p_row, s_row, _ = _predict_rows(model)
-    if model._device_index is None:
-        model.cuda(bank.device)
-    h = model._ensure_handle()
-    preds = []
-    if predictions:
-        torch = __import__("torch")
-        dev = torch.device("cuda", model._device_index)
-    rec = np.zeros(n, RECORD)
-    _lib.check(lib.vp_predict_begin(h), "vp_predict_begin")
-    try:
-        for b0 in range(0, n, batch_size):
-            r = rows[b0 : b0 + batch_size]
-            B = len(r)
-            out = None
-            if predictions:
-                out = torch.empty((B, 3, model.in_samples), dtype=torch.float32, device=dev)
-                torch.cuda.current_stream(dev).synchronize()  # whatever used this memory last on torch's stream is done
-                preds.append(out)
-            plo = lo[b0 : b0 + B].ctypes.data_as(C.c_void_p) if lo is not None else None
-            phi = hi[b0 : b0 + B].ctypes.data_as(C.c_void_p) if hi is not None else None
-            _lib.check(lib.vp_predict_bank(h, bank.handle, r.ctypes.data_as(C.c_void_p), plo, phi, B, _norm(model.norm), det_row,
-                                           p_row, s_row, C.c_void_p(out.data_ptr()) if predictions else None), "vp_predict_bank")
-    finally:
-        nw = C.c_longlong()
-        rc = lib.vp_predict_end(h, rec.ctypes.data_as(C.c_void_p), n, C.byref(nw))
-    _lib.check(rc, "vp_predict_end")
-    assert nw.value == n
+    norm, rows3 = _norm(model.norm), _predict_rows(model)[:3]
+    rec = np.zeros(len(rows), RECORD)
+    preds = _bank_pass(model, bank, rows, window_borders, batch_size, predictions, "vp_predict", lib.vp_predict_begin,
+                       lambda h, r, lo, hi, B, out: lib.vp_predict_bank(h, bank.handle, r, lo, hi, B, norm, *rows3, out),
+                       lambda h, n, nw: lib.vp_predict_end(h, _lib.ptr(rec), n, nw))
     return _scores(rec) + ((preds,) if predictions else ())
 
 
@@ -350,12 +359,6 @@ SWEEP_MAX_PICKS = 64
 TASK0_SAMPLING_RATE = 100  # the reference hard-codes 100 Hz in its counts and residuals (eval_taks0.py:552, :573)
 
 
-def _sweep_rows(model):
-    if model.name == "PhaseNet":
-        return model.labels.index("P"), model.labels.index("S")
-    return 1, 2  # EQTransformer returns (detection, P, S)
-
-
 def _sweep_grid(thresholds):
     """``thresholds``: a number, NT numbers, or ``[P_thresholds, S_thresholds]`` (two rows of NT).  Returns the float32 on
     and off thresholds the kernel sweeps and, per phase, which of them are that phase's NT columns (None: all, in order)."""
@@ -386,6 +389,11 @@ def _sweep_result(count, peak, value, select, max_picks):
     return count, peak, value
 
 
+def _sweep_arrays(n, NT, K, scores):
+    """The results of a sweep over n windows, as empty as the kernel leaves a window without picks."""
+    return np.zeros((n, 2, NT), np.int32), np.full((n, 2, NT, K), -1, np.int32), (np.zeros((n, 2, NT, K), np.float32) if scores else None)
+
+
 def sweep_windows(model, X, window_borders=None, thresholds=np.arange(0.1, 1.0, 0.1), batch_size=1024, max_picks=8,
                   scores=False):
     """The picks of ``evaluate_windows`` at every threshold of ``thresholds`` from ONE forward pass per window
@@ -395,24 +403,15 @@ def sweep_windows(model, X, window_borders=None, thresholds=np.arange(0.1, 1.0, 
     Returns ``(count, peak, value)``: count (n, 2, NT) int32, phase 0 = P and 1 = S; peak (n, 2, NT, max_picks) int32, the
     pick samples local to the border start, ascending, -1 behind the count; value the float32 maxima (0 behind the count)
     with ``scores=True``, else None.  ``RuntimeError`` when a window has more than ``max_picks`` triggers."""
-    torch = __import__("torch")
     lib = _lib.load()
+    ptr = _lib.ptr
     X = np.ascontiguousarray(X, dtype=np.float32)
-    n = X.shape[0]
-    lo, hi = _borders(window_borders, n)
     on, off, select = _sweep_grid(thresholds)
     NT, K = len(on), int(max_picks)
-    p_row, s_row = _sweep_rows(model)
-    count = np.zeros((n, 2, NT), np.int32)
-    peak = np.full((n, 2, NT, K), -1, np.int32)
-    value = np.zeros((n, 2, NT, K), np.float32) if scores else None
+    count, peak, value = _sweep_arrays(len(X), NT, K, scores)
     h = model._ensure_handle()
-    ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
-    for b0 in range(0, n, batch_size):
-        y = model._forward_raw(torch.from_numpy(X[b0 : b0 + batch_size]).to(model.device))  # (B, 3, T) on the device
-        B = y.shape[0]
-        _lib.check(lib.vp_sweep_windows(h, C.c_void_p(y.data_ptr()), _lib.VP_MEM_DEVICE, B, 3, p_row, s_row,
-                                        ptr(None if lo is None else lo[b0 : b0 + B]), ptr(None if hi is None else hi[b0 : b0 + B]),
+    for b0, B, y, lo, hi in _forward_batches(model, X, window_borders, batch_size):
+        _lib.check(lib.vp_sweep_windows(h, C.c_void_p(y.data_ptr()), _lib.VP_MEM_DEVICE, B, 3, *_sweep_rows(model), lo, hi,
                                         ptr(on), ptr(off), NT, K, ptr(count[b0 : b0 + B]), ptr(peak[b0 : b0 + B]),
                                         ptr(None if value is None else value[b0 : b0 + B])), "vp_sweep_windows")
     return _sweep_result(count, peak, value, select, K)
@@ -427,41 +426,16 @@ def sweep_bank(model, bank, rows, window_borders=None, thresholds=np.arange(0.1,
     from .generate import _norm, as_rows
 
     lib = _lib.load()
+    ptr = _lib.ptr
     rows = as_rows(rows)
-    n = len(rows)
-    lo, hi = _borders(window_borders, n)
     on, off, select = _sweep_grid(thresholds)
     NT, K = len(on), int(max_picks)
-    p_row, s_row = _sweep_rows(model)
-    if model._device_index is None:
-        model.cuda(bank.device)
-    h = model._ensure_handle()
-    preds = []
-    if predictions:
-        torch = __import__("torch")
-        dev = torch.device("cuda", model._device_index)
-    count = np.zeros((n, 2, NT), np.int32)
-    peak = np.full((n, 2, NT, K), -1, np.int32)
-    value = np.zeros((n, 2, NT, K), np.float32) if scores else None
-    ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
-    _lib.check(lib.vp_sweep_begin(h, ptr(on), ptr(off), NT, K, int(scores)), "vp_sweep_begin")
-    try:
-        for b0 in range(0, n, batch_size):
-            r = rows[b0 : b0 + batch_size]
-            B = len(r)
-            out = None
-            if predictions:
-                out = torch.empty((B, 3, model.in_samples), dtype=torch.float32, device=dev)
-                torch.cuda.current_stream(dev).synchronize()  # whatever used this memory last on torch's stream is done
-                preds.append(out)
-            _lib.check(lib.vp_sweep_bank(h, bank.handle, ptr(r), ptr(None if lo is None else lo[b0 : b0 + B]),
-                                         ptr(None if hi is None else hi[b0 : b0 + B]), B, _norm(model.norm), p_row, s_row,
-                                         C.c_void_p(out.data_ptr()) if predictions else None), "vp_sweep_bank")
-    finally:
-        nw = C.c_longlong()
-        rc = lib.vp_sweep_end(h, ptr(count), ptr(peak), ptr(value), n, C.byref(nw))
-    _lib.check(rc, "vp_sweep_end")
-    assert nw.value == n
+    norm, rows2 = _norm(model.norm), _sweep_rows(model)
+    count, peak, value = _sweep_arrays(len(rows), NT, K, scores)
+    preds = _bank_pass(model, bank, rows, window_borders, batch_size, predictions, "vp_sweep",
+                       lambda h: lib.vp_sweep_begin(h, ptr(on), ptr(off), NT, K, int(scores)),
+                       lambda h, r, lo, hi, B, out: lib.vp_sweep_bank(h, bank.handle, r, lo, hi, B, norm, *rows2, out),
+                       lambda h, n, nw: lib.vp_sweep_end(h, ptr(count), ptr(peak), ptr(value), n, nw))
     return _sweep_result(count, peak, value, select, K) + ((preds,) if predictions else ())
 
 

@@ -79,7 +79,7 @@ class PhaseNetTrainer:
         self.n_params = int(model._weights.size)
         self._h = C.c_void_p()
         w = np.ascontiguousarray(model._weights, dtype=np.float32)
-        _lib.check(self._lib.vp_train_create_dtype(int(device), _lib.VP_MODEL_PHASENET, w.ctypes.data_as(C.c_void_p), w.size,
+        _lib.check(self._lib.vp_train_create_dtype(int(device), _lib.VP_MODEL_PHASENET, _lib.ptr(w), w.size,
                                                    self.max_batch, self.DTYPES[str(dtype)], C.byref(self._h)), "vp_train_create")
         _lib.check(self._lib.vp_train_set_hyper(self._h, betas[0], betas[1], eps, bn_momentum, loss_eps))
         self.global_step = 0
@@ -104,7 +104,7 @@ class PhaseNetTrainer:
                 a = a.float().contiguous()
             return a, C.c_void_p(a.data_ptr()), (_lib.VP_MEM_DEVICE if a.is_cuda else _lib.VP_MEM_HOST)
         a = np.ascontiguousarray(a, dtype=np.float32)
-        return a, a.ctypes.data_as(C.c_void_p), _lib.VP_MEM_HOST
+        return a, _lib.ptr(a), _lib.VP_MEM_HOST
 
     def step(self, x, y, lr, update=True, want_loss=True, inputs_unchanged=False):
         """Forward + loss + backward (+ Adam when ``update``).  x, y: (B, 3, 3001).
@@ -174,7 +174,7 @@ class PhaseNetTrainer:
         lrows = label_rows(self.model.labels)
         self._drop_consumed()
         loss = C.c_double(float("nan"))
-        _lib.check(getattr(self._lib, name)(self._h, bank.handle, rows.ctypes.data_as(C.c_void_p), len(rows), float(sigma),
+        _lib.check(getattr(self._lib, name)(self._h, bank.handle, _lib.ptr(rows), len(rows), float(sigma),
                                             _norm(self.model.norm), lrows.ctypes.data_as(C.POINTER(C.c_int)), float(lr),
                                             int(bool(update)), C.byref(loss) if want_loss else None), name)
         # the bank stays referenced until the step's reads of it are complete (as the device inputs of `step`)
@@ -198,7 +198,7 @@ class PhaseNetTrainer:
 
     def _read(self, which):
         out = np.empty(self.n_params, dtype=np.float32)
-        _lib.check(self._lib.vp_train_read(self._h, which, out.ctypes.data_as(C.c_void_p), out.size), "vp_train_read")
+        _lib.check(self._lib.vp_train_read(self._h, which, _lib.ptr(out), out.size), "vp_train_read")
         return out
 
     def _named(self, blob):
@@ -229,7 +229,7 @@ class PhaseNetTrainer:
 
     def predictions(self, B):
         out = np.empty((B, 3, self.in_samples), dtype=np.float32)
-        _lib.check(self._lib.vp_train_predictions(self._h, out.ctypes.data_as(C.c_void_p), B))
+        _lib.check(self._lib.vp_train_predictions(self._h, _lib.ptr(out), B))
         return out
 
     def tensors(self, B):
@@ -239,7 +239,7 @@ class PhaseNetTrainer:
             name, c, l = C.c_char_p(), C.c_int(), C.c_int()
             _lib.check(lib.vp_train_tensor_info(self._h, i, C.byref(name), C.byref(c), C.byref(l)))
             a = np.empty((B, c.value, l.value), dtype=np.float32)
-            _lib.check(lib.vp_train_tensor_read(self._h, i, B, a.ctypes.data_as(C.c_void_p)))
+            _lib.check(lib.vp_train_tensor_read(self._h, i, B, _lib.ptr(a)))
             out[name.value.decode()] = a
         return out
 
@@ -321,6 +321,7 @@ def validate_batches(model, bank, batches, sigma, eps=1e-5, predictions=False):
     with ``vector_cross_entropy`` in float64 on the device; the host waits once, at the end.  Returns
     ``(batch_losses, window_losses)``: a float64 array with one loss per batch and one with one per window, in order;
     with ``predictions=True`` also the list of the batches' (B, 3, T) predictions (CUDA tensors)."""
+    from .evaluate import prediction_tensor
     from .generate import AUG_ROW, as_aug_rows, as_rows, label_rows, _norm
 
     lib = _lib.load()
@@ -329,23 +330,16 @@ def validate_batches(model, bank, batches, sigma, eps=1e-5, predictions=False):
     h = model._ensure_handle()
     lrows = label_rows(model.labels).ctypes.data_as(C.POINTER(C.c_int))
     preds, n_windows, n_batches = [], 0, 0
-    if predictions:
-        torch = _torch()
-        dev = torch.device("cuda", model._device_index)
     _lib.check(lib.vp_validate_begin(h), "vp_validate_begin")
     try:
         for rows in batches:
             aug = getattr(rows, "dtype", None) == AUG_ROW
             rows = as_aug_rows(rows) if aug else as_rows(rows)
             name = "vp_validate_bank_aug" if aug else "vp_validate_bank"
-            out = None
             if predictions:
-                out = torch.empty((len(rows), 3, model.in_samples), dtype=torch.float32, device=dev)
-                torch.cuda.current_stream(dev).synchronize()  # whatever used this memory last on torch's stream is done
-                preds.append(out)
-            _lib.check(getattr(lib, name)(h, bank.handle, rows.ctypes.data_as(C.c_void_p), len(rows), float(sigma),
-                                          _norm(model.norm), lrows, float(eps), C.c_void_p(out.data_ptr()) if predictions else None),
-                       name)
+                preds.append(prediction_tensor(model, len(rows)))
+            _lib.check(getattr(lib, name)(h, bank.handle, _lib.ptr(rows), len(rows), float(sigma), _norm(model.norm), lrows,
+                                          float(eps), C.c_void_p(preds[-1].data_ptr()) if predictions else None), name)
             n_batches += 1
             n_windows += len(rows)
     finally:
