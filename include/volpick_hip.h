@@ -572,6 +572,51 @@ int vp_bank_create(int device_id, long long n_traces, long long n_floats_total, 
 int vp_bank_write(vp_bank* bank, long long first_trace, long long n_traces, const float* data, int mem,
                   const int64_t* trace_lengths, const double* onsets);
 int vp_bank_destroy(vp_bank* bank);
+/* vp_bank_read copies trace `trace` (written, or assembled on any stream: the bank's device is synchronised first) out as
+ * its (3, length) fp32 array, to host or device memory (mem). */
+int vp_bank_read(vp_bank* bank, long long trace, float* out, int mem);
+/* vp_bank_assemble is vp_bank_write for traces that are still scattered over device-resident source arrays: it writes
+ * traces [first_trace, first_trace + n_traces) -- in order, as vp_bank_write; trace_lengths and onsets as there -- from a
+ * HOST table of pieces, in three launches on `stream` (hipStream_t, NULL = legacy default stream) for any number of
+ * traces.  It is what the reference's conversion step computes per event file with ObsPy and numpy (its
+ * volpick/data/convert.py:162 detrend("demean") and :26-70 stream_to_array), in float64:
+ *
+ *   a piece is one source trace's contribution to row (trace, component) of the bank.  src points at the first sample
+ *   (device memory; int32, float32 or float64: kind, a VP_SAMPLES_* value) of the range the piece's own mean is taken
+ *   over, mean_n samples: the source trace as it was when it was demeaned.  Of these, samples [keep_lo, keep_lo + keep_n)
+ *   -- what the trims and the row's end leave -- go to row samples [dst, dst + keep_n) as x - mean(src[0 .. mean_n)).
+ *   Pieces are grouped by row, rows ascending (trace, then component); within a row they stand in the order the
+ *   reference writes them, and a row sample that several pieces cover takes the LAST of them (no racing stores: every
+ *   row sample is written once, by the thread that has found its winner from the table).  Samples no piece covers
+ *   are 0, a row without pieces is all 0.  Then the row's mean over all its samples, zeros included, is subtracted, and
+ *   the result is rounded once to fp32:  bank = fp32((x - mean_piece) - mean_row).
+ *
+ * Sums are float64 in a fixed order that does not depend on the launch geometry: per piece and tile of
+ * VP_ASSEMBLE_TILE samples one workgroup's partial sums (of x over the mean range, and of x and 1 over the samples the
+ * piece wins), then one workgroup per row that adds its pieces' partials, forms the piece means and the row mean
+ * (sum over pieces of [sum of won x - won count * piece mean] / row length); no atomics.  The same call gives the same
+ * bits twice.  A source sample is read twice (sums, then the store), a bank sample written once.
+ *
+ * Everything is checked on the host first: first_trace is the number of traces written so far and the traces and their
+ * floats fit the bank; every trace length >= 1; per piece first_trace <= trace < first_trace + n_traces, component in
+ * 0..2, a known kind, a non-null src, mean_n >= 1, keep_n >= 1, 0 <= keep_lo and keep_lo + keep_n <= mean_n,
+ * 0 <= dst and dst + keep_n <= the trace's length, rows ascending.  VP_ERR_INVALID launches nothing and leaves the bank
+ * untouched.  `pieces` (n_pieces >= 0; may be NULL when 0), trace_lengths and onsets are host memory the caller may
+ * reuse on return; the sources must stay alive and unchanged until the launches have run.  The call does not wait for
+ * the device: the traces are there for work queued on `stream` behind it (another stream waits for `stream` first;
+ * vp_bank_read and vp_bank_destroy synchronise the device themselves). */
+#define VP_ASSEMBLE_TILE 4096
+typedef struct {
+  const void* src;
+  int64_t mean_n;
+  int64_t keep_lo, keep_n;
+  int64_t dst;
+  int32_t trace, component;
+  int32_t kind;
+  int32_t reserved; /* 0 */
+} vp_assemble_piece;
+int vp_bank_assemble(vp_bank* bank, long long first_trace, long long n_traces, const vp_assemble_piece* pieces,
+                     long long n_pieces, const int64_t* trace_lengths, const double* onsets, void* stream);
 int vp_bank_make_batch(vp_bank* bank, const vp_plan_row* rows, int B, int T, float sigma, int norm, const int* label_rows,
                        float* x, float* y, void* stream);
 int vp_train_step_bank(vp_trainer* t, vp_bank* bank, const vp_plan_row* rows, int B, float sigma, int norm,

@@ -16,7 +16,8 @@ from .models import EQTransformer, PhaseNet, WaveformModel  # noqa: F401
 from .picks import ClassifyOutput, Detection, DetectionList, Pick, PickList  # noqa: F401
 from .stream import Stream, Trace, UTCDateTime, pinned_array, to_device  # noqa: F401
 from ._lib import VolpickHipError  # noqa: F401
-from .io import read  # noqa: F401
+from .io import read, read_many  # noqa: F401
+from .convert import bank_from_mseed, bank_from_streams, plan_event  # noqa: F401
 from .attributes import bank_attributes, pick_attributes, plan_rows  # noqa: F401
 from .signal import butter_sos, detrend_array, detrend_device, filter_array, sos_filter_device  # noqa: F401
 from .evaluate import (eval_task0, opt_prob_metrics, sweep_bank, sweep_windows, task0_counts, task0_metrics,  # noqa: F401

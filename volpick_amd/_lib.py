@@ -48,6 +48,13 @@ class VpPlanRow(C.Structure):
     _fields_ = [("trace", C.c_int32), ("reserved", C.c_int32), ("start", C.c_int64), ("lo", C.c_int64), ("hi", C.c_int64)]
 
 
+class VpAssemblePiece(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("mean_n", C.c_int64), ("keep_lo", C.c_int64), ("keep_n", C.c_int64), ("dst", C.c_int64),
+                ("trace", C.c_int32), ("component", C.c_int32), ("kind", C.c_int32), ("reserved", C.c_int32)]
+
+
+VP_ASSEMBLE_TILE = 4096  # include/volpick_hip.h
+
 VP_AUG_NONE, VP_AUG_BANK, VP_AUG_SELF = 0, 1, 2
 VP_DET_ONE_MINUS_NOISE, VP_DET_ROW = 0, 1
 
@@ -290,6 +297,10 @@ SIGNATURES = {
     "vp_bank_create": (C.c_int, [C.c_int, C.c_longlong, C.c_longlong, C.POINTER(_H)]),
     "vp_bank_write": (C.c_int, [_H, C.c_longlong, C.c_longlong, C.c_void_p, C.c_int, _I64P, C.POINTER(C.c_double)]),
     "vp_bank_destroy": (C.c_int, [_H]),
+    "vp_bank_read": (C.c_int, [_H, C.c_longlong, C.c_void_p, C.c_int]),
+    "vp_bank_assemble": (
+        C.c_int, [_H, C.c_longlong, C.c_longlong, C.c_void_p, C.c_longlong, _I64P, C.POINTER(C.c_double), C.c_void_p],
+    ),
     "vp_bank_make_batch": (
         C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p],
     ),

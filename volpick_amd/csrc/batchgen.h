@@ -58,7 +58,9 @@ struct Bank {
   long long* len_dev = nullptr;   // [n_traces]
   double* onset_dev = nullptr;    // [n_traces][4]: P, P, S, S in trace samples, NaN = no pick
   std::vector<long long> len;     // host copy of the written traces' lengths (row validation)
+  std::vector<long long> off;     // ... and of their offsets (vp_bank_read)
   StagingRing ring;               // vp_bank_make_batch's staging
+  StagingRing assemble_ring;      // vp_bank_assemble's tables and partial sums (assemble.hip)
   ~Bank();
 };
 

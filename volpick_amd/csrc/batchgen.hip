@@ -679,8 +679,21 @@ int vp_bank_write(vp_bank* h, long long first_trace, long long n_traces, const f
   VP_HIP(hipMemcpy(bk.onset_dev + 4 * first_trace, onsets, (size_t)n_traces * 4 * sizeof(double), hipMemcpyHostToDevice));
   VP_HIP(hipDeviceSynchronize());  // batches enqueued on any stream afterwards see the data
   bk.len.insert(bk.len.end(), len.begin(), len.end());
+  bk.off.insert(bk.off.end(), off.begin(), off.end());
   bk.n_written += n_traces;
   bk.floats_written += floats;
+  return VP_OK;
+}
+
+int vp_bank_read(vp_bank* h, long long trace, float* out, int mem) {
+  VP_REQUIRE(h && out, "vp_bank_read: null argument");
+  VP_REQUIRE(mem == VP_MEM_HOST || mem == VP_MEM_DEVICE, "vp_bank_read: mem %d", mem);
+  Bank& bk = *reinterpret_cast<Bank*>(h);
+  VP_REQUIRE(trace >= 0 && trace < bk.n_written, "vp_bank_read: trace %lld outside [0, %lld)", trace, bk.n_written);
+  VP_HIP(hipSetDevice(bk.device));
+  VP_HIP(hipDeviceSynchronize());  // the trace is complete, whichever stream assembled it
+  VP_HIP(hipMemcpy(out, bk.data + bk.off[(size_t)trace], (size_t)(3 * bk.len[(size_t)trace]) * sizeof(float),
+                   mem == VP_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
   return VP_OK;
 }
 

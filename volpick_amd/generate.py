@@ -77,6 +77,12 @@ PLAN_ROW = np.dtype([("trace", np.int32), ("reserved", np.int32), ("start", np.i
                     align=True)
 assert PLAN_ROW.itemsize == C.sizeof(_lib.VpPlanRow)
 
+# include/volpick_hip.h vp_assemble_piece: one source trace's contribution to one (trace, component) row of a bank
+ASSEMBLE_PIECE = np.dtype([("src", np.uint64), ("mean_n", np.int64), ("keep_lo", np.int64), ("keep_n", np.int64),
+                           ("dst", np.int64), ("trace", np.int32), ("component", np.int32), ("kind", np.int32),
+                           ("reserved", np.int32)], align=True)
+assert ASSEMBLE_PIECE.itemsize == C.sizeof(_lib.VpAssemblePiece)
+
 AUG_NONE, AUG_BANK, AUG_SELF = _lib.VP_AUG_NONE, _lib.VP_AUG_BANK, _lib.VP_AUG_SELF
 AUG_EVENT = np.dtype([("row", PLAN_ROW), ("kind", np.int32), ("zero_before", np.int32), ("shift", np.int32),
                       ("scale", np.float32)], align=True)
@@ -191,6 +197,44 @@ class WaveformBank:
         ons = np.ascontiguousarray(self.onsets[first:first + count])
         _lib.check(self._lib.vp_bank_write(self._h, first, count, ptr, mem, lens.ctypes.data_as(C.POINTER(C.c_int64)),
                                            ons.ctypes.data_as(C.POINTER(C.c_double))), "vp_bank_write")
+
+    @classmethod
+    def from_pieces(cls, pieces, lengths, onsets, device=0, sources=()):
+        """A bank assembled on the device from source arrays that already live there (``vp_bank_assemble``, one call for
+        every trace): ``pieces`` is an :data:`ASSEMBLE_PIECE` array grouped by (trace, component), ``lengths`` the traces'
+        lengths, ``onsets`` as for the constructor.  Runs on torch's current stream and does not wait for it.  ``sources``
+        (the tensors the pieces point into) are kept alive with the bank."""
+        import torch
+
+        pieces = np.ascontiguousarray(pieces)
+        if pieces.dtype != ASSEMBLE_PIECE or pieces.ndim != 1:
+            raise TypeError("pieces: a 1-D array of generate.ASSEMBLE_PIECE")
+        self = cls.__new__(cls)
+        self._lib = _lib.load()
+        self._h = C.c_void_p()
+        self.lengths = np.ascontiguousarray(lengths, np.int64).reshape(-1)
+        n = self.n_traces = len(self.lengths)
+        if n == 0:
+            raise ValueError("an empty waveform bank")
+        self.onsets = _onset_table(onsets, n)
+        self.device = int(device)
+        self._sources = list(sources)
+        _lib.check(self._lib.vp_bank_create(self.device, n, int(3 * self.lengths.sum()), C.byref(self._h)), "vp_bank_create")
+        stream = torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream
+        _lib.check(self._lib.vp_bank_assemble(self._h, 0, n, pieces.ctypes.data_as(C.c_void_p), len(pieces),
+                                              self.lengths.ctypes.data_as(C.POINTER(C.c_int64)),
+                                              np.ascontiguousarray(self.onsets).ctypes.data_as(C.POINTER(C.c_double)),
+                                              C.c_void_p(stream)), "vp_bank_assemble")
+        return self
+
+    def trace(self, i):
+        """Trace ``i`` read back: its (3, L_i) float32 array on the host (``vp_bank_read``; waits for the device)."""
+        i = int(i)
+        if not 0 <= i < self.n_traces:
+            raise IndexError(f"trace {i} outside [0, {self.n_traces})")
+        out = np.empty((3, int(self.lengths[i])), np.float32)
+        _lib.check(self._lib.vp_bank_read(self._h, i, out.ctypes.data_as(C.c_void_p), _lib.VP_MEM_HOST), "vp_bank_read")
+        return out
 
     @classmethod
     def from_metadata(cls, waveforms, metadata, phase_dict=PHASE_DICT, device=0):

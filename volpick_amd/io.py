@@ -170,6 +170,114 @@ def read_mseed(source, device=0, dtype=None, device_resident=False):
     return st
 
 
+def many_tables(bufs):
+    """Host bookkeeping of :func:`read_many`: ``(table, seg, bounds, bases)``.  ``table`` holds every file's records as
+    :func:`_segments` orders them, file after file, with ``offset`` shifted by the file's position ``bases[k]`` in the
+    concatenated bytes; ``seg`` numbers the continuous segments, which never reach across a file boundary (each file is
+    scanned and chained on its own, and its segment numbers start behind the previous file's); file ``k`` owns the records
+    ``[bounds[k], bounds[k + 1])``."""
+    tables, segs, bounds, bases = [], [], [0], []
+    pos = next_seg = 0
+    for buf in bufs:
+        r, seg = _segments(scan_mseed(buf))
+        r = r.copy()
+        r["offset"] += pos
+        tables.append(r)
+        segs.append(seg + next_seg)
+        if len(seg):
+            next_seg += int(seg[-1]) + 1
+        bounds.append(bounds[-1] + len(r))
+        bases.append(pos)
+        pos += len(buf)
+    table = np.concatenate(tables) if tables else np.zeros(0, _REC_DTYPE)
+    seg = np.concatenate(segs) if segs else np.zeros(0, np.int64)
+    return table, seg, np.asarray(bounds, np.int64), np.asarray(bases, np.int64)
+
+
+def short_payload_error(table, status, bounds, bases):
+    """The ``ValueError`` :func:`read_mseed` raises for the first record (in table order) whose payload is shorter than its
+    header says, with the offset within the record's own file; ``None`` if there is none."""
+    bad = np.flatnonzero(status == 2)
+    if len(bad) == 0:
+        return None
+    k = int(np.searchsorted(bounds, bad[0], side="right")) - 1
+    return ValueError(f"miniSEED record at byte {int(table['offset'][bad[0]] - bases[k])}: payload holds fewer samples than "
+                      "its header says")
+
+
+def read_many(sources, device=0, dtype=None, device_resident=True):
+    """``[read(s, device_resident=...) for s in sources]`` for miniSEED sources, with one ``vp_mseed_decode`` per sample
+    kind for all of them: every file is scanned on the host, the bytes are concatenated, and one record table over the
+    whole buffer is decoded at once.  Each returned ``Stream`` equals what :func:`read_mseed` returns for that file --
+    same traces, order, headers and ``stats.mseed``, samples bit for bit, same error for a short payload -- and its traces
+    are views into the decode buffers all files share."""
+    bufs = [_as_bytes(s) for s in sources]
+    lib = _lib.load()
+    r, seg, bounds, bases = many_tables(bufs)
+    streams = [Stream() for _ in bufs]
+    if len(r) == 0:
+        return streams
+    buf = b"".join(bufs)
+    is_float = np.isin(r["encoding"], _FLOAT_ENCODINGS)
+    as_float = is_float | (dtype is not None and np.dtype(dtype) == np.float32)
+    recs_c = (_lib.VpMseedRecord * len(r)).from_buffer_copy(np.ascontiguousarray(r).tobytes())
+    buffers = {}
+    for kind, sel in ((_lib.VP_SAMPLES_INT32, ~as_float), (_lib.VP_SAMPLES_FLOAT32, as_float)):
+        if not sel.any():
+            continue
+        ns = np.where(sel, r["nsamples"], 0).astype(np.int64)
+        index = np.where(sel, np.cumsum(ns) - ns, -1).astype(np.int64)
+        n_out = int(ns.sum())
+        status = np.zeros(len(r), np.int32)
+        if device_resident:
+            import torch
+
+            out = torch.empty(n_out, dtype=torch.int32 if kind == _lib.VP_SAMPLES_INT32 else torch.float32,
+                              device=torch.device("cuda", device))
+            out_ptr, out_mem = C.c_void_p(out.data_ptr()), _lib.VP_MEM_DEVICE
+        else:
+            out = np.empty(n_out, dtype=np.int32 if kind == _lib.VP_SAMPLES_INT32 else np.float32)
+            out_ptr, out_mem = out.ctypes.data_as(C.c_void_p), _lib.VP_MEM_HOST
+        _lib.check(
+            lib.vp_mseed_decode(device, buf, _lib.VP_MEM_HOST, len(buf), recs_c,
+                                index.ctypes.data_as(C.POINTER(C.c_int64)), None, len(r), kind,
+                                out_ptr, out_mem, n_out, 0,
+                                status.ctypes.data_as(C.POINTER(C.c_int32))), "vp_mseed_decode")
+        err = short_payload_error(r, status, bounds, bases)
+        if err is not None:
+            raise err
+        buffers[kind] = (out, index, status)
+    first = np.flatnonzero(np.concatenate([[True], seg[1:] != seg[:-1]]))
+    last = np.concatenate([first[1:], [len(r)]])
+    file_of = np.searchsorted(bounds, first, side="right") - 1
+    for a, b, k in zip(first, last, file_of):
+        kind = _lib.VP_SAMPLES_FLOAT32 if as_float[a] else _lib.VP_SAMPLES_INT32
+        out, index, status = buffers[kind]
+        n = int(r["nsamples"][a:b].sum())
+        data = out[index[a]:index[a] + n]
+        if device_resident:
+            tr_args = dict(device_data=data)
+        else:
+            if dtype is not None and data.dtype != np.dtype(dtype):
+                data = data.astype(dtype)
+            elif int(r["encoding"][a]) == 0 and dtype is None:
+                data = data.astype(np.uint8).view("S1")
+            tr_args = dict(data=data)
+        tr = Trace(header=dict(network=r["network"][a].decode(), station=r["station"][a].decode(),
+                              location=r["location"][a].decode(), channel=r["channel"][a].decode(),
+                              starttime=UTCDateTime._from_us(int(r["start_us"][a])),
+                              sampling_rate=float(r["sample_rate"][a])), **tr_args)
+        q = int(r["quality"][a])
+        tr.stats["mseed"] = dict(dataquality=chr(q) if q < 256 else "", format_version=2 if q < 256 else 3,
+                                 publication_version=q & 255 if q >= 256 else None, number_of_records=int(b - a),
+                                 encoding=int(r["encoding"][a]), byteorder=">" if r["big_endian"][a] else "<",
+                                 record_length=int(r["reclen"][a]),
+                                 steim_integrity_errors=int((status[a:b] == 1).sum()))
+        tr.stats["_format"] = "MSEED"
+        streams[k].append(tr)
+    return streams
+
+
 def release_decode_scratch(device=0):
     """Free the device scratch `read_mseed` keeps per device between calls (vp_mseed_release_scratch); returns the bytes freed."""
     return release_scratch("vp_mseed_release_scratch", device)

@@ -119,6 +119,43 @@ class UTCDateTime:
         return f"UTCDateTime({str(self)!r})"
 
 
+# --- ObsPy's Trace.trim(starttime, endtime) with its defaults, restated (ObsPy is not available to pin it) ------------------
+TRIM_PAD = False              # pad=False: a time outside the trace cuts nothing, it never adds samples
+TRIM_NEAREST_SAMPLE = True    # nearest_sample=True: the cut lands on the sample nearest to the given time ...
+TRIM_ROUNDING = "half_away"   # ... by ObsPy's round_away: halves go away from zero (2.5 -> 3, -2.5 -> -3), not to even
+
+
+def round_half_away(x):
+    """The integer nearest to ``x``, halves away from zero (ObsPy's ``compatibility.round_away``)."""
+    assert TRIM_ROUNDING == "half_away"
+    x = float(x)
+    return int(math.floor(x + 0.5)) if x >= 0 else -int(math.floor(-x + 0.5))
+
+
+def trim_cut(starttime, npts, rate, t_start=None, t_end=None):
+    """``(first, count)``: the samples ``[first, first + count)`` of a trace of ``npts`` samples at ``rate`` Hz from
+    ``starttime`` that ``trim(t_start, t_end)`` keeps.  Left: ``delta = round_half_away((t_start - starttime) * rate)``, a
+    cut only when ``delta > 0``.  Right, on the trace the left cut has left: ``delta = round_half_away((t_end - its start)
+    * rate) - its npts + 1``, a cut only when ``delta < 0``.  An end before the start leaves nothing."""
+    assert TRIM_NEAREST_SAMPLE and not TRIM_PAD
+    starttime = UTCDateTime(starttime)
+    if t_start is not None and t_end is not None and UTCDateTime(t_start) > UTCDateTime(t_end):
+        return 0, 0
+    first, count = 0, int(npts)
+    if t_start is not None:
+        delta = round_half_away((UTCDateTime(t_start) - starttime) * rate)
+        if delta > 0:
+            first = min(delta, count)
+            count -= first
+            if count:
+                starttime = starttime + first / rate
+    if t_end is not None and count:
+        delta = round_half_away((UTCDateTime(t_end) - starttime) * rate) - count + 1
+        if delta < 0:
+            count = max(count + delta, 0)
+    return first, count
+
+
 class Stats(dict):
     """Trace header; attribute and item access, derived npts / delta / endtime."""
 
@@ -198,6 +235,25 @@ class Trace:
     def copy(self):
         return Trace(self.data.copy(), self.stats.copy())
 
+    def trim(self, starttime=None, endtime=None):
+        """ObsPy's ``Trace.trim(starttime, endtime)`` with its defaults ``pad=False, nearest_sample=True``, in place; returns
+        ``self``.  A restatement of ObsPy's rule (:func:`trim_cut` and the ``TRIM_*`` constants beside it), not ObsPy's code.
+        A device-backed trace is cut by slicing its tensor -- a view of the same storage, no copy, no host visit -- a host
+        trace by slicing its array."""
+        first, count = trim_cut(self.stats.starttime, self.stats.npts, self.stats.sampling_rate, starttime, endtime)
+        if first == 0 and count == self.stats.npts:
+            return self
+        if self._dev is not None:
+            self._dev = self._dev[first:first + count]
+            if self._data is not None:
+                self._data = self._data[first:first + count]
+        else:
+            self._data = self._data[first:first + count]
+        if first and count:
+            self.stats["starttime"] = self.stats.starttime + first / self.stats.sampling_rate
+        self.stats["npts"] = count
+        return self
+
     def filter(self, type, **options):
         """ObsPy's ``Trace.filter``: ``lowpass`` / ``highpass`` (``freq``), ``bandpass`` / ``bandstop`` (``freqmin``,
         ``freqmax``); ``corners=4``, ``zerophase=False``.  In place, returns ``self``.  A device-backed trace is filtered on the
@@ -270,6 +326,13 @@ class Stream:
 
     def copy(self):
         return Stream([t.copy() for t in self.traces])
+
+    def trim(self, starttime=None, endtime=None):
+        """``Trace.trim`` on every trace, in place; traces left empty are dropped, as ObsPy's ``Stream.trim`` does."""
+        for tr in self.traces:
+            tr.trim(starttime, endtime)
+        self.traces = [tr for tr in self.traces if tr.stats.npts]
+        return self
 
     def filter(self, type, **options):
         for tr in self.traces:
