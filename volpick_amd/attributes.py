@@ -27,6 +27,7 @@ import math
 import numpy as np
 
 from . import _lib
+from ._device import stream_handle
 
 ATTR_ROW = np.dtype([
     ("trace", np.int32), ("flags", np.int32),
@@ -137,12 +138,6 @@ def _columns(out):
     }
 
 
-def _current_stream(device):
-    import torch
-
-    return C.c_void_p(torch.cuda.current_stream(torch.device("cuda", device)).cuda_stream)
-
-
 def array_attributes(data, rows, raw=False):
     """``vp_attributes`` on one (3, N) float32 CUDA tensor: the columns of :func:`bank_attributes` for ``rows``
     (``raw=True``: the kernel's (n_rows, 14) float64 table -- fi[3], fi_trace, noise_p95[3], signal_p95[3], snr_db[3],
@@ -156,7 +151,7 @@ def array_attributes(data, rows, raw=False):
     out = np.full((len(rows), N_OUT), np.nan)
     dev = data.device.index
     _lib.check(_lib.load().vp_attributes(dev, C.c_void_p(data.data_ptr()), data.shape[1], rows.ctypes.data_as(C.POINTER(_lib.VpAttrRow)),
-                                         len(rows), out.ctypes.data_as(C.c_void_p), _current_stream(dev)), "vp_attributes")
+                                         len(rows), out.ctypes.data_as(C.c_void_p), stream_handle(dev)), "vp_attributes")
     return out if raw else _columns(out)
 
 
@@ -169,7 +164,7 @@ def bank_attributes(bank, sampling_rate=100, fi_window=(1.0, 6.0), low_band=(1, 
                      snr_window, demean=False)
     out = np.full((len(rows), N_OUT), np.nan)
     _lib.check(_lib.load().vp_bank_attributes(bank.handle, rows.ctypes.data_as(C.POINTER(_lib.VpAttrRow)), len(rows),
-                                              out.ctypes.data_as(C.c_void_p), _current_stream(bank.device)),
+                                              out.ctypes.data_as(C.c_void_p), stream_handle(bank.device)),
                "vp_bank_attributes")
     return out if raw else _columns(out)
 

@@ -28,7 +28,7 @@ import math
 
 import numpy as np
 
-from ._device import SAMPLE_KINDS
+from ._device import SAMPLE_KINDS, device_backing, trace_samples
 from .generate import ASSEMBLE_PIECE, WaveformBank
 from .stream import Stream, UTCDateTime, to_device, trim_cut
 
@@ -98,7 +98,7 @@ def plan_event(stream, p_time, s_time, component_order="ZNE", sampling_rate=100,
     rate = sampling_rate
     spans = []
     for tr in stream:
-        if np.ma.isMaskedArray(tr._data if hasattr(tr, "_dev") else tr.data):  # (a device-backed trace has no mask)
+        if device_backing(tr) is None and np.ma.isMaskedArray(tr.data):  # (a device-backed trace has no mask)
             raise NotImplementedError("masked traces cannot be converted; split the stream at its gaps first")
         if tr.stats.sampling_rate != rate:  # :153-159
             assert RESAMPLE_ONLY_DIFFERING
@@ -147,8 +147,8 @@ def piece_table(plans):
     sources, k = [], 0
     for i, pl in enumerate(plans):
         for pc in pl["pieces"]:
-            dev = getattr(pc["source"], "_dev", None)
-            if dev is None or str(dev.dtype) not in SAMPLE_KINDS:
+            dev = trace_samples(pc["source"])
+            if dev is None:
                 raise TypeError("piece_table: a source trace is not backed by an int32, float32 or float64 device array")
             dev = dev.contiguous()
             assert int(dev.shape[0]) == pc["mean_n"]
@@ -179,7 +179,7 @@ def bank_from_streams(streams, metadata, component_order="ZNE", sampling_rate=10
         raise ValueError(f"{len(streams)} streams, {len(p_times)} P and {len(s_times)} S arrival times")
     plans = []
     for st, p, s in zip(streams, p_times, s_times):
-        if any(getattr(tr, "_dev", None) is None for tr in st):
+        if any(device_backing(tr) is None for tr in st):
             st = to_device(st if isinstance(st, Stream) else Stream(list(st)), device)
         plans.append(plan_event(st, p, s, component_order, sampling_rate, cut_bounds, check_long_traces,
                                 check_long_traces_limit))

@@ -94,24 +94,15 @@ def _segments(recs):
     return r, seg
 
 
-def read_mseed(source, device=0, dtype=None, device_resident=False):
-    """miniSEED -> Stream (one Trace per continuous segment, sorted by id and time).
-
-    Integer encodings decode to int32 exactly; float32/float64 records to float32; text records
-    (encoding 0: log channels) to ObsPy's ``|S1`` characters.  ``dtype`` forces the sample type of
-    every trace (``np.float32`` decodes integers straight to fp32).
-    ``device_resident=True`` leaves the decoded samples on the GPU: the traces are backed by CUDA
-    tensors, ``classify`` / ``annotate`` assemble and consume them there, and ``trace.data`` copies
-    to the host only when somebody reads it.
-    """
-    buf = _as_bytes(source)
+def _decode(buf, r, bounds, bases, device, dtype, device_resident):
+    """The samples of the record table ``r`` (as :func:`_segments` orders it) of the bytes ``buf``, by one ``vp_mseed_decode``
+    per sample kind the table holds.  Returns ``(as_float, buffers)``: which records were decoded to float32 (the float
+    encodings; every record when ``dtype`` is float32), and per kind ``(out, index, status)`` -- the samples record after
+    record in a numpy array or, with ``device_resident``, a CUDA tensor; where each record starts in it; the decoder's status
+    per record.  ``bounds`` and ``bases`` are :func:`many_tables`' (one file: ``[0, len(r)]`` and ``[0]``): they name the file
+    of a short payload."""
     lib = _lib.load()
-    r, seg = _segments(scan_mseed(buf))
-    st = Stream()
-    if len(r) == 0:
-        return st
-    is_float = np.isin(r["encoding"], _FLOAT_ENCODINGS)
-    as_float = is_float | (dtype is not None and np.dtype(dtype) == np.float32)
+    as_float = np.isin(r["encoding"], _FLOAT_ENCODINGS) | (dtype is not None and np.dtype(dtype) == np.float32)
     recs_c = (_lib.VpMseedRecord * len(r)).from_buffer_copy(np.ascontiguousarray(r).tobytes())
     buffers = {}
     for kind, sel in ((_lib.VP_SAMPLES_INT32, ~as_float), (_lib.VP_SAMPLES_FLOAT32, as_float)):
@@ -135,13 +126,23 @@ def read_mseed(source, device=0, dtype=None, device_resident=False):
                                 index.ctypes.data_as(C.POINTER(C.c_int64)), None, len(r), kind,
                                 out_ptr, out_mem, n_out, 0,
                                 status.ctypes.data_as(C.POINTER(C.c_int32))), "vp_mseed_decode")
-        if (status == 2).any():
-            bad = int(np.flatnonzero(status == 2)[0])
-            raise ValueError(f"miniSEED record at byte {int(r['offset'][bad])}: payload holds fewer samples than its "
-                             "header says")
+        err = short_payload_error(r, status, bounds, bases)
+        if err is not None:
+            raise err
         buffers[kind] = (out, index, status)
+    return as_float, buffers
+
+
+def _segment_ranges(seg):
+    """``(first, last)``: segment ``i`` of the numbering ``seg`` (non-empty) is the records ``[first[i], last[i])``."""
     first = np.flatnonzero(np.concatenate([[True], seg[1:] != seg[:-1]]))
-    last = np.concatenate([first[1:], [len(r)]])
+    return first, np.concatenate([first[1:], [len(seg)]])
+
+
+def _add_traces(st, r, first, last, decoded, dtype, device_resident):
+    """One ``Trace`` per segment ``[first[i], last[i])`` of the table ``r``, appended to ``st``; ``decoded`` is what
+    :func:`_decode` returned for ``r``.  The traces are views into its buffers, except where a host trace is cast."""
+    as_float, buffers = decoded
     for a, b in zip(first, last):
         kind = _lib.VP_SAMPLES_FLOAT32 if as_float[a] else _lib.VP_SAMPLES_INT32
         out, index, status = buffers[kind]
@@ -167,6 +168,26 @@ def read_mseed(source, device=0, dtype=None, device_resident=False):
                                  steim_integrity_errors=int((status[a:b] == 1).sum()))
         tr.stats["_format"] = "MSEED"
         st.append(tr)
+
+
+def read_mseed(source, device=0, dtype=None, device_resident=False):
+    """miniSEED -> Stream (one Trace per continuous segment, sorted by id and time).
+
+    Integer encodings decode to int32 exactly; float32/float64 records to float32; text records
+    (encoding 0: log channels) to ObsPy's ``|S1`` characters.  ``dtype`` forces the sample type of
+    every trace (``np.float32`` decodes integers straight to fp32).
+    ``device_resident=True`` leaves the decoded samples on the GPU: the traces are backed by CUDA
+    tensors, ``classify`` / ``annotate`` assemble and consume them there, and ``trace.data`` copies
+    to the host only when somebody reads it.
+
+    The one-file case of :func:`read_many`, without its table and byte concatenation.
+    """
+    buf = _as_bytes(source)
+    r, seg = _segments(scan_mseed(buf))
+    st = Stream()
+    if len(r):
+        decoded = _decode(buf, r, (0, len(r)), (0,), device, dtype, device_resident)
+        _add_traces(st, r, *_segment_ranges(seg), decoded, dtype, device_resident)
     return st
 
 
@@ -195,8 +216,8 @@ def many_tables(bufs):
 
 
 def short_payload_error(table, status, bounds, bases):
-    """The ``ValueError`` :func:`read_mseed` raises for the first record (in table order) whose payload is shorter than its
-    header says, with the offset within the record's own file; ``None`` if there is none."""
+    """The ``ValueError`` :func:`read_mseed` and :func:`read_many` raise for the first record (in table order) whose payload is
+    shorter than its header says, with the offset within the record's own file; ``None`` if there is none."""
     bad = np.flatnonzero(status == 2)
     if len(bad) == 0:
         return None
@@ -208,73 +229,19 @@ def short_payload_error(table, status, bounds, bases):
 def read_many(sources, device=0, dtype=None, device_resident=True):
     """``[read(s, device_resident=...) for s in sources]`` for miniSEED sources, with one ``vp_mseed_decode`` per sample
     kind for all of them: every file is scanned on the host, the bytes are concatenated, and one record table over the
-    whole buffer is decoded at once.  Each returned ``Stream`` equals what :func:`read_mseed` returns for that file --
-    same traces, order, headers and ``stats.mseed``, samples bit for bit, same error for a short payload -- and its traces
-    are views into the decode buffers all files share."""
+    whole buffer is decoded at once.  Each returned ``Stream`` is what :func:`read_mseed` returns for that file -- the two
+    build their traces with the same code, and a short payload is the same error -- and its traces are views into the
+    decode buffers all files share."""
     bufs = [_as_bytes(s) for s in sources]
-    lib = _lib.load()
     r, seg, bounds, bases = many_tables(bufs)
     streams = [Stream() for _ in bufs]
     if len(r) == 0:
         return streams
-    buf = b"".join(bufs)
-    is_float = np.isin(r["encoding"], _FLOAT_ENCODINGS)
-    as_float = is_float | (dtype is not None and np.dtype(dtype) == np.float32)
-    recs_c = (_lib.VpMseedRecord * len(r)).from_buffer_copy(np.ascontiguousarray(r).tobytes())
-    buffers = {}
-    for kind, sel in ((_lib.VP_SAMPLES_INT32, ~as_float), (_lib.VP_SAMPLES_FLOAT32, as_float)):
-        if not sel.any():
-            continue
-        ns = np.where(sel, r["nsamples"], 0).astype(np.int64)
-        index = np.where(sel, np.cumsum(ns) - ns, -1).astype(np.int64)
-        n_out = int(ns.sum())
-        status = np.zeros(len(r), np.int32)
-        if device_resident:
-            import torch
-
-            out = torch.empty(n_out, dtype=torch.int32 if kind == _lib.VP_SAMPLES_INT32 else torch.float32,
-                              device=torch.device("cuda", device))
-            out_ptr, out_mem = C.c_void_p(out.data_ptr()), _lib.VP_MEM_DEVICE
-        else:
-            out = np.empty(n_out, dtype=np.int32 if kind == _lib.VP_SAMPLES_INT32 else np.float32)
-            out_ptr, out_mem = out.ctypes.data_as(C.c_void_p), _lib.VP_MEM_HOST
-        _lib.check(
-            lib.vp_mseed_decode(device, buf, _lib.VP_MEM_HOST, len(buf), recs_c,
-                                index.ctypes.data_as(C.POINTER(C.c_int64)), None, len(r), kind,
-                                out_ptr, out_mem, n_out, 0,
-                                status.ctypes.data_as(C.POINTER(C.c_int32))), "vp_mseed_decode")
-        err = short_payload_error(r, status, bounds, bases)
-        if err is not None:
-            raise err
-        buffers[kind] = (out, index, status)
-    first = np.flatnonzero(np.concatenate([[True], seg[1:] != seg[:-1]]))
-    last = np.concatenate([first[1:], [len(r)]])
-    file_of = np.searchsorted(bounds, first, side="right") - 1
-    for a, b, k in zip(first, last, file_of):
-        kind = _lib.VP_SAMPLES_FLOAT32 if as_float[a] else _lib.VP_SAMPLES_INT32
-        out, index, status = buffers[kind]
-        n = int(r["nsamples"][a:b].sum())
-        data = out[index[a]:index[a] + n]
-        if device_resident:
-            tr_args = dict(device_data=data)
-        else:
-            if dtype is not None and data.dtype != np.dtype(dtype):
-                data = data.astype(dtype)
-            elif int(r["encoding"][a]) == 0 and dtype is None:
-                data = data.astype(np.uint8).view("S1")
-            tr_args = dict(data=data)
-        tr = Trace(header=dict(network=r["network"][a].decode(), station=r["station"][a].decode(),
-                              location=r["location"][a].decode(), channel=r["channel"][a].decode(),
-                              starttime=UTCDateTime._from_us(int(r["start_us"][a])),
-                              sampling_rate=float(r["sample_rate"][a])), **tr_args)
-        q = int(r["quality"][a])
-        tr.stats["mseed"] = dict(dataquality=chr(q) if q < 256 else "", format_version=2 if q < 256 else 3,
-                                 publication_version=q & 255 if q >= 256 else None, number_of_records=int(b - a),
-                                 encoding=int(r["encoding"][a]), byteorder=">" if r["big_endian"][a] else "<",
-                                 record_length=int(r["reclen"][a]),
-                                 steim_integrity_errors=int((status[a:b] == 1).sum()))
-        tr.stats["_format"] = "MSEED"
-        streams[k].append(tr)
+    decoded = _decode(b"".join(bufs), r, bounds, bases, device, dtype, device_resident)
+    first, last = _segment_ranges(seg)
+    cut = np.searchsorted(first, bounds)  # a segment never reaches across a file boundary: file k owns [cut[k], cut[k + 1])
+    for k, st in enumerate(streams):
+        _add_traces(st, r, first[cut[k]:cut[k + 1]], last[cut[k]:cut[k + 1]], decoded, dtype, device_resident)
     return streams
 
 

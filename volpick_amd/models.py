@@ -28,6 +28,7 @@ from pathlib import Path
 import numpy as np
 
 from . import _lib
+from ._device import device_backing
 from ._lib import VolpickHipError
 from .picks import ClassifyOutput, Detection, DetectionList, Pick, PickList
 from .stream import Stream, Trace, UTCDateTime
@@ -951,7 +952,7 @@ def _group_stream(stream, component_order, sampling_rate, copy, in_samples, stre
             comp = tr.stats.channel[-1] if tr.stats.channel else ""
             comp = comp if comp in component_order else comp_alias.get(comp, comp)
             s0 = int(round((UTCDateTime(tr.stats.starttime) - t_start) * sampling_rate))
-            npts = int(tr.stats.npts) if getattr(tr, "_dev", None) is not None else len(tr.data)
+            npts = int(tr.stats.npts) if device_backing(tr) is not None else len(tr.data)
             pieces.append((s0, npts, component_order.index(comp) if comp in component_order else -1, tr))
         # contiguous covered runs (union over all components) become independent blocks; gaps are not bridged
         runs = []
@@ -968,7 +969,7 @@ def _group_stream(stream, component_order, sampling_rate, copy, in_samples, stre
                               "samples. Output might be empty.")
                 continue
             used = [p for p in pieces if p[2] >= 0 and min(p[0] + p[1], b1) > max(p[0], b0)]
-            on_device = bool(used) and all(getattr(p[3], "_dev", None) is not None for p in used)
+            on_device = bool(used) and all(device_backing(p[3]) is not None for p in used)
             # the common case -- one full-length trace per component -- is a single stack, no zero fill
             full = sorted((p for p in used if p[0] == b0 and p[1] == b1 - b0), key=lambda p: p[2])
             if len(used) != len(component_order) or [p[2] for p in full] != list(range(len(component_order))):

@@ -21,7 +21,7 @@ import warnings
 import numpy as np
 
 from . import _lib
-from ._device import SAMPLE_KINDS, device_samples, release_scratch, try_on_device
+from ._device import device_samples, release_scratch, replace_samples, sample_args, trace_on_device
 
 
 def lowpass_sos(freq, df, corners=4):
@@ -109,10 +109,8 @@ def decimate_device(x, rate_in, rate_out):
     if n == 0:
         return out
     sos = np.ascontiguousarray(lowpass_sos(rate_out * 0.5, rate_in), dtype=np.float64)
-    torch.cuda.current_stream(x.device).synchronize()  # the library works on the null stream: x is complete before it starts
-    _lib.check(_lib.load().vp_decimate_lowpass(
-        x.device.index, C.c_void_p(x.data_ptr()), SAMPLE_KINDS[str(x.dtype)], n, sos.ctypes.data_as(C.POINTER(C.c_double)),
-        len(sos), k, C.c_void_p(out.data_ptr()), out.shape[0]), "vp_decimate_lowpass")
+    _lib.check(_lib.load().vp_decimate_lowpass(*sample_args(x), sos.ctypes.data_as(C.POINTER(C.c_double)), len(sos), k,
+                                               C.c_void_p(out.data_ptr()), out.shape[0]), "vp_decimate_lowpass")
     return out
 
 
@@ -157,10 +155,8 @@ def fourier_device(x, rate_in, rate_out):
     if num < 1:
         raise ValueError(f"fourier_device: {n} samples at {rate_in} Hz give no sample at {rate_out} Hz")
     out = torch.empty(num, dtype=torch.float32, device=x.device)
-    torch.cuda.current_stream(x.device).synchronize()  # the library works on the null stream: x is complete before it starts
-    _lib.check(_lib.load().vp_resample_fourier(
-        x.device.index, C.c_void_p(x.data_ptr()), SAMPLE_KINDS[str(x.dtype)], n, rate_in, rate_out, num, df, d_large_f,
-        C.c_void_p(out.data_ptr()), num), "vp_resample_fourier")
+    _lib.check(_lib.load().vp_resample_fourier(*sample_args(x), rate_in, rate_out, num, df, d_large_f,
+                                               C.c_void_p(out.data_ptr()), num), "vp_resample_fourier")
     return out
 
 
@@ -182,25 +178,21 @@ def resample_trace(tr, rate_out, copy=True, fourier_on_device=False):
     rate_in = float(tr.stats.sampling_rate)
     if abs(rate_in - rate_out) <= 1e-6:
         return tr
-    dev = getattr(tr, "_dev", None)
-    integer_ratio = rate_in % float(rate_out) == 0 and rate_in > rate_out
-    if dev is not None and (integer_ratio or fourier_on_device) and str(dev.dtype) in SAMPLE_KINDS:
-        from .stream import Trace
+    # refused: a factor beyond the kernel's tile, a trace beyond the largest FFT: said aloud, then the host path below
+    y = None
+    if rate_in % float(rate_out) == 0 and rate_in > rate_out:
+        y = trace_on_device(tr, "decimation", "resampling", lambda dev: decimate_device(dev, rate_in, rate_out))
+    elif fourier_on_device:
+        y = trace_on_device(tr, "Fourier resampling", "resampling", lambda dev: fourier_device(dev, rate_in, float(rate_out)))
+    if y is not None:
+        if copy:
+            from .stream import Trace
 
-        # refused: a factor beyond the kernel's tile, a trace beyond the largest FFT: said aloud, then the host path below
-        if integer_ratio:
-            y = try_on_device(tr.id, "decimation", lambda: decimate_device(dev, rate_in, rate_out), "resampling")
+            tr = Trace(header=tr.stats.copy(), device_data=y)
         else:
-            y = try_on_device(tr.id, "Fourier resampling", lambda: fourier_device(dev, rate_in, float(rate_out)), "resampling")
-        if y is not None:
-            if copy:
-                hdr = tr.stats.copy()
-                hdr["sampling_rate"] = rate_out
-                return Trace(header=hdr, device_data=y)
-            tr._dev, tr._data = y, None
-            tr.stats["npts"] = int(y.shape[0])
-            tr.stats.sampling_rate = rate_out
-            return tr
+            replace_samples(tr, y)
+        tr.stats.sampling_rate = rate_out
+        return tr
     out = tr.copy() if copy else tr
     out.data = resample_array(out.data, rate_in, rate_out)
     out.stats.sampling_rate = rate_out

@@ -16,7 +16,7 @@ import warnings
 import numpy as np
 
 from . import _lib
-from ._device import SAMPLE_KINDS, device_samples, release_scratch, try_on_device
+from ._device import device_backing, device_samples, release_scratch, sample_args, trace_in_place
 from .resample import lowpass_sos
 
 FILTER_TYPES = ("lowpass", "highpass", "bandpass", "bandstop")
@@ -103,15 +103,12 @@ def sos_filter_device(x, sos, zerophase=False):
     import torch
 
     x = device_samples(x, "sos_filter_device")
-    n = int(x.shape[0])
-    out = torch.empty(n, dtype=torch.float32, device=x.device)
+    out = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
     sos = np.ascontiguousarray(np.atleast_2d(np.asarray(sos, dtype=np.float64)))
     if sos.ndim != 2 or sos.shape[1] != 6:
         raise ValueError("sos_filter_device: sos must have six columns (scipy's sos layout)")
-    torch.cuda.current_stream(x.device).synchronize()  # the library works on the null stream: x is complete before it starts
-    _lib.check(_lib.load().vp_sos_filter(
-        x.device.index, C.c_void_p(x.data_ptr()), SAMPLE_KINDS[str(x.dtype)], n, sos.ctypes.data_as(C.POINTER(C.c_double)),
-        len(sos), int(bool(zerophase)), C.c_void_p(out.data_ptr())), "vp_sos_filter")
+    _lib.check(_lib.load().vp_sos_filter(*sample_args(x), sos.ctypes.data_as(C.POINTER(C.c_double)), len(sos),
+                                         int(bool(zerophase)), C.c_void_p(out.data_ptr())), "vp_sos_filter")
     return out
 
 
@@ -124,11 +121,8 @@ def detrend_device(x, type="simple"):
     if type not in DETREND_TYPES:
         raise ValueError(f"detrend type {type!r} is not one of {sorted(DETREND_TYPES)}")
     x = device_samples(x, "detrend_device")
-    n = int(x.shape[0])
-    out = torch.empty(n, dtype=torch.float32, device=x.device)
-    torch.cuda.current_stream(x.device).synchronize()
-    _lib.check(_lib.load().vp_detrend(x.device.index, C.c_void_p(x.data_ptr()), SAMPLE_KINDS[str(x.dtype)], n,
-                                      DETREND_TYPES[type], C.c_void_p(out.data_ptr())), "vp_detrend")
+    out = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+    _lib.check(_lib.load().vp_detrend(*sample_args(x), DETREND_TYPES[type], C.c_void_p(out.data_ptr())), "vp_detrend")
     return out
 
 
@@ -137,32 +131,19 @@ def release_filter_scratch(device=0):
     return release_scratch("vp_sos_filter_release_scratch", device)
 
 
-def _on_device(tr, what, run, host):
-    """``tr`` processed in place: on the device if it lives there (``run``: device tensor -> float32 device tensor), on the host
-    otherwise or where the library refuses (``host``: ndarray -> float64 ndarray)."""
-    dev = getattr(tr, "_dev", None)
-    if dev is not None and str(dev.dtype) in SAMPLE_KINDS:
-        y = try_on_device(tr.id, what, lambda: run(dev), what)
-        if y is not None:
-            tr._dev, tr._data = y, None
-            return tr
-    tr.data = host(tr.data)
-    return tr
-
-
 def filter_trace(tr, type, **options):
     """``tr.filter(type, **options)`` in place (``volpick_amd.Trace``): device-backed traces on the device, where they stay."""
     zerophase = bool(options.pop("zerophase", False))
     df = float(tr.stats.sampling_rate)
-    return _on_device(tr, "filtering", lambda dev: sos_filter_device(dev, butter_sos(type, df, **options), zerophase),
-                      lambda a: filter_array(a, type, df, zerophase=zerophase, **options))
+    return trace_in_place(tr, "filtering", lambda dev: sos_filter_device(dev, butter_sos(type, df, **options), zerophase),
+                          lambda a: filter_array(a, type, df, zerophase=zerophase, **options))
 
 
 def detrend_trace(tr, type="simple"):
     """``tr.detrend(type)`` in place (``volpick_amd.Trace``): device-backed traces on the device, where they stay."""
     if type not in DETREND_TYPES:
         raise ValueError(f"detrend type {type!r} is not one of {sorted(DETREND_TYPES)}")
-    return _on_device(tr, "detrending", lambda dev: detrend_device(dev, type), lambda a: detrend_array(a, type))
+    return trace_in_place(tr, "detrending", lambda dev: detrend_device(dev, type), lambda a: detrend_array(a, type))
 
 
 def filtered_copy(tr, type, **options):
@@ -170,7 +151,7 @@ def filtered_copy(tr, type, **options):
     the device directly (``Trace.copy()`` would go through the host)."""
     from .stream import Trace
 
-    dev = getattr(tr, "_dev", None)
+    dev = device_backing(tr)
     if isinstance(tr, Trace) and dev is not None:
         out = Trace(header=tr.stats.copy(), device_data=dev)  # shares the samples: the filter writes a new tensor
     else:

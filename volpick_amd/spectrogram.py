@@ -22,7 +22,7 @@ from typing import NamedTuple
 import numpy as np
 
 from . import _lib
-from ._device import SAMPLE_KINDS, release_scratch
+from ._device import SAMPLE_KINDS, device_backing, release_scratch, stream_handle, upload_samples
 
 TILE_FRAMES = _lib.VP_SPECTROGRAM_TILE_FRAMES  # consecutive frames a workgroup of the kernel owns (at nfft <= 128)
 
@@ -130,11 +130,10 @@ def spectrogram(x, samp_rate=None, per_lap=0.9, wlen=None, dbscale=False, mult=8
     freq, time = axes(npts, samp_rate, nfft, pad, hop)
     with torch.cuda.device(x.device):
         out = torch.empty(lead + (pad // 2, hi - lo), dtype=torch.float32, device=x.device)
-        stream = torch.cuda.current_stream(x.device).cuda_stream
         if hi > lo:  # an empty tensor has no address to hand over
             _lib.check(_lib.load().vp_spectrogram(
                 x.device.index, C.c_void_p(x.data_ptr()), SAMPLE_KINDS[str(x.dtype)], n_series, stride, npts, samp_rate, nfft,
-                pad, hop, int(bool(dbscale)), lo, hi - lo, C.c_void_p(out.data_ptr()), C.c_void_p(stream)), "vp_spectrogram")
+                pad, hop, int(bool(dbscale)), lo, hi - lo, C.c_void_p(out.data_ptr()), stream_handle(x.device)), "vp_spectrogram")
     return Spectrogram(out, freq, time[lo:hi])
 
 
@@ -145,15 +144,9 @@ def trace_spectrogram(tr, device=0, **kw):
     import torch
 
     kw.pop("samp_rate", None)
-    dev = getattr(tr, "_dev", None)
+    dev = device_backing(tr)
     if dev is None:
-        a = tr.data
-        if np.ma.isMaskedArray(a):
-            raise NotImplementedError("masked traces have no spectrogram; split the stream at its gaps first")
-        a = np.ascontiguousarray(a)
-        if a.dtype not in (np.dtype(np.int32), np.dtype(np.float32), np.dtype(np.float64)):
-            a = a.astype(np.float32)
-        dev = torch.from_numpy(a).to(torch.device("cuda", int(device)))
+        dev = upload_samples(tr.data, torch.device("cuda", int(device)), "masked traces have no spectrogram")
     elif str(dev.dtype) not in SAMPLE_KINDS:
         dev = dev.to(torch.float32)
     return spectrogram(dev, float(tr.stats.sampling_rate), **kw)

@@ -18,6 +18,8 @@ from datetime import datetime, timedelta, timezone
 
 import numpy as np
 
+from ._device import device_backing, upload_samples
+
 _EPOCH = datetime(1970, 1, 1, tzinfo=timezone.utc)
 
 
@@ -424,18 +426,11 @@ def to_device(stream, device=0):
     dev = torch.device("cuda", int(device))
     out = Stream()
     for tr in stream:
-        d = getattr(tr, "_dev", None)
-        if d is None or d.device != dev:
-            if d is not None:
-                d = d.to(dev)
-            else:
-                a = tr.data
-                if np.ma.isMaskedArray(a):
-                    raise NotImplementedError("masked traces cannot be moved to the device; split the stream at its gaps first")
-                a = np.ascontiguousarray(a)
-                if a.dtype not in (np.dtype(np.int32), np.dtype(np.float32), np.dtype(np.float64)):
-                    a = a.astype(np.float32)
-                d = torch.from_numpy(a).to(dev)
+        d = device_backing(tr)
+        if d is None:
+            d = upload_samples(tr.data, dev, "masked traces cannot be moved to the device")
+        elif d.device != dev:
+            d = d.to(dev)
         hdr = Stats({k: v for k, v in dict(tr.stats).items() if k not in ("npts", "delta", "endtime")})
         hdr["starttime"] = UTCDateTime(tr.stats.starttime)
         out.append(Trace(header=hdr, device_data=d))

@@ -15,7 +15,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._device import SAMPLE_KINDS, release_scratch, try_on_device
+from ._device import (SAMPLE_KINDS, device_samples, is_cuda, release_scratch, sample_args, trace_in_place, trace_samples,
+                      try_on_device)
 
 TINY = float(np.finfo(np.float64).tiny)
 TYPES = {"classicstalta": _lib.VP_STALTA_CLASSIC, "recstalta": _lib.VP_STALTA_RECURSIVE}
@@ -79,31 +80,23 @@ def sta_lta_device(x, type, nsta, nlta, dtype=None):
     if type not in TYPES:
         raise ValueError(f"trigger type {type!r} is not one of {sorted(TYPES)}")
     nsta, nlta = _check_windows(nsta, nlta)
-    if not (torch.is_tensor(x) and x.is_cuda and x.dim() in (1, 2) and str(x.dtype) in SAMPLE_KINDS):
-        raise TypeError("sta_lta_device: need a 1-D or 2-D CUDA tensor of int32, float32 or float64 samples")
+    x = device_samples(x, "sta_lta_device", dims=(1, 2))
     dtype = torch.float64 if dtype is None else dtype
     if dtype not in (torch.float32, torch.float64):
         raise ValueError("sta_lta_device: dtype is torch.float32 or torch.float64")
-    x = x.contiguous()
-    n = int(x.shape[-1])
     n_series = int(x.shape[0]) if x.dim() == 2 else 1
     out = torch.empty_like(x, dtype=dtype)
-    if n_series == 0 or n == 0:
+    if out.numel() == 0:
         return out
-    torch.cuda.current_stream(x.device).synchronize()  # the library works on the null stream: x is complete before it starts
-    _lib.check(_lib.load().vp_sta_lta(
-        x.device.index, C.c_void_p(x.data_ptr()), SAMPLE_KINDS[str(x.dtype)], n_series, n, n, TYPES[type], nsta, nlta,
-        C.c_void_p(out.data_ptr()), SAMPLE_KINDS[str(dtype)]), "vp_sta_lta")
+    device, ptr, kind, n = sample_args(x)
+    _lib.check(_lib.load().vp_sta_lta(device, ptr, kind, n_series, n, n, TYPES[type], nsta, nlta, C.c_void_p(out.data_ptr()),
+                                      SAMPLE_KINDS[str(dtype)]), "vp_sta_lta")
     return out
-
-
-def _is_cuda(a):
-    return type(a).__module__.startswith("torch") and getattr(a, "is_cuda", False)
 
 
 def classic_sta_lta(a, nsta, nlta, dtype=None):
     """ObsPy's ``classic_sta_lta``.  numpy in, float64 numpy out (host); CUDA tensor in, CUDA tensor out (``vp_sta_lta``)."""
-    if _is_cuda(a):
+    if is_cuda(a):
         return sta_lta_device(a, "classicstalta", nsta, nlta, dtype)
     nsta, nlta = _check_windows(nsta, nlta)
     return _classic_host(_host_samples(a), nsta, nlta)
@@ -111,7 +104,7 @@ def classic_sta_lta(a, nsta, nlta, dtype=None):
 
 def recursive_sta_lta(a, nsta, nlta, dtype=None):
     """ObsPy's ``recursive_sta_lta``.  numpy in, float64 numpy out (host); CUDA tensor in, CUDA tensor out (``vp_sta_lta``)."""
-    if _is_cuda(a):
+    if is_cuda(a):
         return sta_lta_device(a, "recstalta", nsta, nlta, dtype)
     nsta, nlta = _check_windows(nsta, nlta)
     return _recursive_host(_host_samples(a), nsta, nlta)
@@ -167,7 +160,7 @@ def trigger_onset(cft, thr1, thr2, max_len=None, **kw):
     """ObsPy's ``trigger_onset``: an ``(m, 2)`` int64 array of on / off samples (empty: shape ``(0, 2)``).  A numpy array goes
     to the host mirror (``vp_pick_host``, the general rule); a 1-D float32 CUDA tensor goes to ``vp_trigger_onset``, which has
     the rule for ``thr2 <= thr1`` without ``max_len``."""
-    if _is_cuda(cft):
+    if is_cuda(cft):
         if max_len is not None or kw:
             raise ValueError("max_len is not available on the device: use the host path, trigger_onset(cft.cpu().numpy(), ...), "
                              "and cut the triggers there")
@@ -205,14 +198,8 @@ def trace_trigger(tr, type, sta, lta):
     nsta, nlta = _windows(tr, sta, lta)
     if nsta > nlta:
         raise ValueError(f"sta = {sta} s is longer than lta = {lta} s")
-    dev = getattr(tr, "_dev", None)
-    if dev is not None and str(dev.dtype) in SAMPLE_KINDS:
-        y = try_on_device(tr.id, "STA/LTA", lambda: sta_lta_device(dev, type, nsta, nlta, torch.float32), "STA/LTA")
-        if y is not None:
-            tr._dev, tr._data = y, None
-            return tr
-    tr.data = _cft_host(tr.data, type, nsta, nlta)
-    return tr
+    return trace_in_place(tr, "STA/LTA", lambda dev: sta_lta_device(dev, type, nsta, nlta, torch.float32),
+                          lambda a: _cft_host(a, type, nsta, nlta))
 
 
 def sta_lta_triggers(stream, type="recstalta", sta=5.0, lta=20.0, thr_on=2.0, thr_off=0.5):
@@ -236,12 +223,12 @@ def sta_lta_triggers(stream, type="recstalta", sta=5.0, lta=20.0, thr_on=2.0, th
 
     def on_device(trs):
         nsta, nlta = _windows(trs[0], sta, lta)
-        cft = sta_lta_device(torch.stack([t._dev for t in trs]), type, nsta, nlta, torch.float32)
+        cft = sta_lta_device(torch.stack([trace_samples(t) for t in trs]), type, nsta, nlta, torch.float32)
         return cft, trigger_onset_device(cft, float(thr_on), float(thr_off))
 
     for tr in stream:
-        dev = getattr(tr, "_dev", None)
-        if dev is not None and str(dev.dtype) in SAMPLE_KINDS and len(tr) > 0:
+        dev = trace_samples(tr)
+        if dev is not None and len(tr) > 0:
             key = (str(dev.device), str(dev.dtype), int(dev.shape[0]), float(tr.stats.sampling_rate))
             groups.setdefault(key, []).append(tr)
         else:
