@@ -672,6 +672,21 @@ int vp_bank_make_batch_aug(vp_bank* bank, const vp_aug_row* rows, int B, int T, 
 int vp_train_step_bank_aug(vp_trainer* t, vp_bank* bank, const vp_aug_row* rows, int B, float sigma, int norm,
                            const int* label_rows, float lr, int update, double* loss);
 
+/* EQTransformer's batch: block 1 of the reference's EQTransformerLit (volpick/model/models.py:606-666) on vp_plan_row rows,
+ * 1 <= T <= 6144.  vp_bank_make_batch_eqt writes x and y as vp_bank_make_batch does, with these rows of y:
+ *   label_rows[1] (P) and label_rows[2] (S): as there, to the bit (ProbabilisticLabeller with noise_column=False: no noise
+ *      row and no rescaling);
+ *   label_rows[0] (detection): SeisBench's DetectionLabeller.  With p and s the earliest finite P and S onset relative to
+ *      the window (float64), the row is 1 on the samples [max(int(p), 0), max(int(s + 1.4 (s - p)), 0)) that lie in the
+ *      window and 0 elsewhere; all 0 when the trace has no finite P or no finite S onset, or s < p.  int() truncates toward
+ *      zero; the product is rounded before the sum (no fused multiply-add), as Python rounds them.
+ *      det_fixed_window >= 0 (samples; the reference's detection_fixed_window): s = p + det_fixed_window and the factor is
+ *      0, S is not read.  Negative: the rule above.
+ * x equals what vp_bank_make_batch writes for the same rows, to the bit.  Checked as vp_bank_make_batch checks, and
+ * det_fixed_window negative or finite (VP_ERR_INVALID launches nothing and leaves x and y untouched). */
+int vp_bank_make_batch_eqt(vp_bank* bank, const vp_plan_row* rows, int B, int T, float sigma, int norm, const int* label_rows,
+                           float det_fixed_window, float* x, float* y, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Validation loss on the device: the reference's vector_cross_entropy (volpick/model/models.py:34-51) of predictions
  * that never leave the GPU, in float64, and the validation half of its training loop (validation_step, :171-174) on
@@ -688,7 +703,7 @@ int vp_train_step_bank_aug(vp_trainer* t, vp_bank* bank, const vp_aug_row* rows,
  * nowhere to put B doubles.  Checked on the host before any launch (VP_ERR_INVALID, outputs untouched): B >= 1,
  * 1 <= C <= 8, T >= 1, eps > 0, p and y not NULL.
  *
- * A validation pass on a PhaseNet handle; an EQTransformer handle gets VP_ERR_UNSUPPORTED, its loss has other labels:
+ * A validation pass on a PhaseNet handle; an EQTransformer handle gets VP_ERR_UNSUPPORTED, its loss has other labels (vp_validate_eqt_*):
  *   vp_validate_begin(h)        opens a pass: no batches yet.
  *   vp_validate_bank(h, ...)    enqueues one batch on the handle's stream and returns: rows cut, normalised and labelled as
  *                               vp_bank_make_batch does (T = vp_in_samples(h)) into scratch of the handle; the forward pass
@@ -715,6 +730,48 @@ int vp_validate_bank_aug(vp_handle* h, vp_bank* bank, const vp_aug_row* rows, in
                          const int* label_rows, double eps, float* pred_out_dev);
 int vp_validate_end(vp_handle* h, double* batch_losses, long long cap, long long* n_batches, double* per_window,
                     long long cap_windows, long long* n_windows);
+
+/* ---------------------------------------------------------------------------------------------
+ * EQTransformer's validation loss on the device: the weighted binary cross entropy of the reference's
+ * EQTransformerLit.shared_step (volpick/model/models.py:538-549; torch.nn.BCELoss, mean reduction, once per head), in
+ * float64, and a validation pass over a bank that computes it on the batch of vp_bank_make_batch_eqt.
+ *
+ * vp_bce_loss reads p and y, dense (B, C, T) fp32 on device `device_id`, and `weights`, C doubles on the HOST (read
+ * before the call returns), and writes on `stream` (hipStream_t, NULL = legacy default stream), without waiting for it:
+ *   term                = -( y max(log p, -100) + (1 - y) max(log(1 - p), -100) ),  p and y widened to double first
+ *   head_dev[b * C + c] = (1/T) sum_t term of row c, unweighted                        (B * C doubles, may be NULL)
+ *   per_window_dev[b]   = sum_c weights[c] * head[b][c]                                (B doubles, may be NULL)
+ *   batch_dev[0]        = (1/B) sum_b per_window[b]                                    (1 double, may be NULL)
+ * Every window has T samples, so batch_dev[0] = sum_c weights[c] * BCELoss(p[:, c], y[:, c]).  The clamp is torch's and
+ * keeps a NaN; NaN, Inf and p outside [0, 1] propagate as IEEE arithmetic takes them and are no error.  Both logarithms are
+ * taken of every element.  The order of every sum is fixed and there are no atomics: the same arrays at the same addresses
+ * give the same bits (the order depends on the addresses mod 16 only).  With per_window_dev NULL the batch loss is the
+ * same number, computed by one workgroup: slow.  Checked on the host before any launch (VP_ERR_INVALID, outputs
+ * untouched): B >= 1, 1 <= C <= 8, T >= 1, p, y and weights not NULL, the weights finite.
+ *
+ * A validation pass on an EQTransformer handle; a PhaseNet handle gets VP_ERR_UNSUPPORTED (its pass is vp_validate_*):
+ *   vp_validate_eqt_begin(h)       opens a pass: no batches yet.
+ *   vp_validate_eqt_bank(h, ...)   enqueues one batch on the handle's stream and returns: rows cut, normalised and labelled
+ *                                  as vp_bank_make_batch_eqt does (T = vp_in_samples(h) = 6000; label_rows = the rows of
+ *                                  detection, P and S in the model's output: 0, 1, 2) into scratch of the handle; the
+ *                                  forward pass as vp_forward(preprocess = 0) runs it, in chunks of max_batch windows; then
+ *                                  vp_bce_loss of all B windows with weights[0..2] = the weights of detection, P and S
+ *                                  (the reference's loss_weights: 0.05, 0.40, 0.55), appended to device arrays of the
+ *                                  handle.  pred_out_dev, when not NULL, receives the (B, 3, T) predictions.  Any B >= 1.
+ *                                  Everything is checked before anything is enqueued; a refused call appends nothing.
+ *   vp_validate_eqt_end(h, ...)    waits for the stream -- the pass's only host wait in the steady state -- and copies out
+ *                                  up to `cap` batch losses, `cap_windows` window values (per_window, may be NULL) and
+ *                                  3 * `cap_windows` head values (heads, [window][row of y], may be NULL), in the order
+ *                                  enqueued; *n_batches and *n_windows are how many the pass holds.  Closes the pass.
+ * The host waits inside a pass where vp_validate_bank does.  A pass may be open beside a prediction or sweep pass of the
+ * same handle; the results of a pass do not depend on what ran before it (bit for bit). */
+int vp_bce_loss(int device_id, const float* p_dev, const float* y_dev, int B, int C, int T, const double* weights,
+                double* head_dev, double* per_window_dev, double* batch_dev, void* stream);
+int vp_validate_eqt_begin(vp_handle* h);
+int vp_validate_eqt_bank(vp_handle* h, vp_bank* bank, const vp_plan_row* rows, int B, float sigma, int norm,
+                         const int* label_rows, float det_fixed_window, const double* weights, float* pred_out_dev);
+int vp_validate_eqt_end(vp_handle* h, double* batch_losses, long long cap, long long* n_batches, double* per_window,
+                        double* heads, long long cap_windows, long long* n_windows);
 
 /* ---------------------------------------------------------------------------------------------
  * Pick-benchmark tasks 1-3: the per-window scores of the reference's predict_step (volpick/model/models.py:454-480 for

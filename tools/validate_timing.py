@@ -9,7 +9,10 @@ At B = 512 and B = 64, medians after warm-up:
   stages  of the device batch, each alone between HIP events: generation, forward, loss kernel;
   export  ms of one ``PhaseNetTrainer.export()`` and of the handle rebuild (``model.cuda()``) that follows it;
   step    ms of one ``step_bank`` as ``fit_bank`` runs it (the loss read back every step) and with the steps queued.
-usage: validate_timing.py [--batches 20] [--passes 7]"""
+``--model eqtransformer`` times EQTransformer's pass instead (``validate_batches_eqt``, B = 256 and B = 64): the device
+batch, generation, forward and the weighted-BCE kernel each alone, the host route of ``EQTransformerLit.validation_step``,
+and ``vp_vce_loss`` on the loss kernel's arrays -- the same bytes with one float64 logarithm per element instead of two.
+usage: validate_timing.py [--batches 20] [--passes 7] [--model phasenet|eqtransformer]"""
 import argparse
 import ctypes as C
 import json
@@ -31,6 +34,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--batches", type=int, default=20, help="batches per device pass, and host batches / steps timed")
 ap.add_argument("--passes", type=int, default=7)
 ap.add_argument("--traces", type=int, default=128)
+ap.add_argument("--model", choices=("phasenet", "eqtransformer"), default="phasenet")
 args = ap.parse_args()
 N = max(20, args.batches)
 
@@ -65,13 +69,67 @@ def event_ms(fn, n, warm=3):
 rng = np.random.default_rng(0)
 xs, ps, ss = [], [], []
 for i in range(args.traces):
-    x, p, s = synthetic_stream_array(9000, seed=1000 + i, n_events=1)
+    x, p, s = synthetic_stream_array(20000 if args.model == "eqtransformer" else 9000, seed=1000 + i, n_events=1)
     xs.append(x * rng.uniform(0.1, 100.0))
     ps.append(float(p[0]))
     ss.append(float(s[0]))
 bank = G.WaveformBank(np.stack(xs).astype(np.float32), {"P": ps, "S": ss})
 lib = _lib.load()
 result = {}
+
+
+def eqtransformer_mode():
+    """--model eqtransformer: the device batch in a pass, its stages alone and the host route, at B = 256 and B = 64; and the
+    loss kernel beside vp_vce_loss on the same arrays (the same bytes, one float64 logarithm per element instead of two)."""
+    from volpick_amd import EQTransformer
+    from volpick_amd.train import EQTransformerLit, bce_loss, validate_batches_eqt
+
+    for B in (256, 64):
+        lit = EQTransformerLit(model=EQTransformer.from_pretrained("volpick").cuda())
+        model = lit.model
+        planner = lit.window_planner(bank, B, seed=B)
+        plans = [planner.plan(rng.integers(0, args.traces, B)) for _ in range(N)]
+        r = result[f"B{B}"] = {}
+        it = iter(plans * 4)
+        r["host_ms_per_batch"] = wall_ms(lambda: lit.validation_step(lit.make_batch(bank, next(it))), N)
+        r["device_ms_per_batch_in_a_pass"] = wall_ms(lambda: validate_batches_eqt(model, bank, plans, lit.sigma), args.passes, warm=2) / N
+        it = iter(plans * 4)
+        r["device_ms_single_batch_pass"] = wall_ms(lambda: validate_batches_eqt(model, bank, [next(it)], lit.sigma), N)
+
+        it = iter(plans * 4)
+        made = lit.make_batch(bank, plans[0])
+        r["stage_generate_ms"] = event_ms(lambda: lit.make_batch(bank, next(it)), N)
+        r["stage_forward_ms"] = wall_ms(lambda: model(made["X"]), N)  # (vp_forward waits for its stream itself)
+        pred = torch.stack(model(made["X"]), 1).contiguous()
+        y = torch.cat([made["detections"], made["y"]], 1).contiguous()
+        hd = torch.empty(3 * B, dtype=torch.float64, device="cuda")
+        pw = torch.empty(B, dtype=torch.float64, device="cuda")
+        bt = torch.empty(1, dtype=torch.float64, device="cuda")
+        w = (C.c_double * 3)(*lit.loss_weights)
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        ptr = lambda t: C.c_void_p(t.data_ptr())
+        r["stage_loss_kernel_ms"] = event_ms(
+            lambda: _lib.check(lib.vp_bce_loss(0, ptr(pred), ptr(y), B, 3, 6000, w, ptr(hd), ptr(pw), ptr(bt), stream)), N)
+        r["vce_kernel_same_arrays_ms"] = event_ms(
+            lambda: _lib.check(lib.vp_vce_loss(0, ptr(pred), ptr(y), B, 3, 6000, 1e-5, ptr(pw), ptr(bt), stream)), N)
+        r["loss_kernel_GB_per_s"] = 2 * 4 * pred.numel() / (1e6 * r["stage_loss_kernel_ms"])
+        p_host, y_host = pred.cpu().numpy(), y.cpu().numpy()
+        r["host_copy_back_ms"] = wall_ms(lambda: (pred.cpu(), y.cpu()), N)
+        t0 = time.perf_counter()
+        for _ in range(3):
+            bce_loss(p_host, y_host, lit.loss_weights)
+        r["host_numpy_loss_ms"] = 1e3 * (time.perf_counter() - t0) / 3
+        print(f"B = {B}")
+        for k, v in r.items():
+            print(f"  {k:34s} {v:9.3f}")
+
+
+if args.model == "eqtransformer":
+    eqtransformer_mode()
+    bank.close()
+    print(json.dumps({"validate_timing_eqtransformer": result}))
+    sys.exit(0)
+
 for B in (512, 64):
     lit = PhaseNetLit(lr=1e-3, model=PhaseNet.from_pretrained("volpick"), max_batch=B)
     tr = lit._ensure()

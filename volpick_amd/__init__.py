@@ -22,6 +22,7 @@ from .attributes import bank_attributes, pick_attributes, plan_rows  # noqa: F40
 from .signal import butter_sos, detrend_array, detrend_device, filter_array, sos_filter_device  # noqa: F401
 from .evaluate import (eval_task0, opt_prob_metrics, sweep_bank, sweep_windows, task0_counts, task0_metrics,  # noqa: F401
                        task0_residuals, task0_tnr, task0_truth)
+from .train import EQTransformerLit, bce_loss, validate_batches_eqt  # noqa: F401
 from . import spectrogram  # noqa: F401
 from .spectrogram import Spectrogram, release_spectrogram_scratch  # noqa: F401
 from . import trigger  # noqa: F401

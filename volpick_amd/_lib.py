@@ -329,6 +329,24 @@ SIGNATURES = {
         C.c_int, [_H, C.POINTER(C.c_double), C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(C.c_double), C.c_longlong,
                   C.POINTER(C.c_longlong)],
     ),
+    "vp_bank_make_batch_eqt": (
+        C.c_int,
+        [_H, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_int), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
+    "vp_bce_loss": (
+        C.c_int,
+        [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p,
+         C.c_void_p],
+    ),
+    "vp_validate_eqt_begin": (C.c_int, [_H]),
+    "vp_validate_eqt_bank": (
+        C.c_int,
+        [_H, _H, C.c_void_p, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_int), C.c_float, C.POINTER(C.c_double), C.c_void_p],
+    ),
+    "vp_validate_eqt_end": (
+        C.c_int, [_H, C.POINTER(C.c_double), C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                  C.c_longlong, C.POINTER(C.c_longlong)],
+    ),
     "vp_predict_windows": (
         C.c_int,
         [_H, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],

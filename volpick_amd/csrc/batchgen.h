@@ -69,6 +69,13 @@ int bank_check(const Bank& bk, const vp_plan_row* rows, int B, int T, float sigm
 // x, y: (B, 3, T) fp32 on the bank's device.  Arguments already checked by bank_check.
 int bank_launch(const Bank& bk, const vp_plan_row* rows_dev, int B, int T, float sigma, int norm, const int* label_rows,
                 float* x, float* y, hipStream_t s);
+// The EQTransformer batch (vp_bank_make_batch_eqt): label_rows = the rows of detection, P and S in y; x and the P / S rows
+// carry bank_launch's bits, the detection row is SeisBench's DetectionLabeller (det_fixed_window < 0: from P to
+// S + 1.4 (S - P); >= 0: that many samples from P).  bank_check's arguments plus det_fixed_window.
+int bank_check_eqt(const Bank& bk, const vp_plan_row* rows, int B, int T, float sigma, int norm, const int* label_rows,
+                   float det_fixed_window);
+int bank_launch_eqt(const Bank& bk, const vp_plan_row* rows_dev, int B, int T, float sigma, int norm, const int* label_rows,
+                    float det_fixed_window, float* x, float* y, hipStream_t s);
 // x alone -- the rows cut, demeaned and normalised exactly as bank_launch does, no labels (vp_predict_bank).
 int bank_check_windows(const Bank& bk, const vp_plan_row* rows, int B, int T, int norm);
 int bank_launch_windows(const Bank& bk, const vp_plan_row* rows_dev, int B, int T, int norm, float* x, hipStream_t s);

@@ -1,6 +1,7 @@
 // Training batches from a device-resident waveform bank (include/volpick_hip.h, vp_bank_*): window cut with zero fill,
-// demean + peak / std normalisation and Gaussian phase labels, one workgroup per window.  The host plans every random
-// choice (volpick_amd/generate.py); this file only executes the plan rows.
+// demean + peak / std normalisation and Gaussian phase labels -- with a noise row for PhaseNet, with SeisBench's detection
+// box for EQTransformer -- one workgroup per window.  The host plans every random choice (volpick_amd/generate.py); this file
+// only executes the plan rows.
 #include "batchgen.h"
 
 #include <cmath>
@@ -206,6 +207,67 @@ __global__ __launch_bounds__(GEN_NTH) void bank_batch_kernel(const GenArgs a) {
     yw[(long long)a.row_p * T + t] = ph[0];
     yw[(long long)a.row_s * T + t] = ph[1];
     yw[(long long)a.row_n * T + t] = fminf(fmaxf(1.f - ph[0] - ph[1], 0.f), 1.f);
+  }
+}
+
+// What bank_batch_eqt_kernel takes beside GenArgs (whose row_n it does not read): GenArgs keeps its layout, and with it the
+// other kernels their code.
+struct DetArgs {
+  int row_det;
+  double fixed_window;  // >= 0: the detection ends fixed_window samples behind P; < 0: it follows S
+};
+
+// SeisBench's DetectionLabeller (ndim == 2) on a window's onsets o (P, P, S, S; window-relative): the box is 1 on the
+// integer samples t with lo <= t < hi, lo = max(int(p), 0), hi = max(int(s + factor (s - p)), 0), p and s the earliest
+// finite P and S onsets, factor = 1.4; empty (lo = hi = 0) without a P or without an S, and for s < p.  A fixed window w
+// puts s = p + w and factor = 0.  int() truncates toward zero; lo and hi stay doubles, so no onset overflows an integer.
+__device__ __forceinline__ void detection_span(const double o[4], const bool has[4], double fixed_window, double& lo, double& hi) {
+  // Python rounds the product, then the sum.  With contraction off for this block the compiler emits a multiply and an add
+  // (what __dmul_rn / __dadd_rn stand for; the header's versions are plain operators that -ffp-contract=fast may still fuse):
+  // p = -2304, s = -1101.5 must end at 582.0, not at the fused 581.9999999999999.
+#pragma clang fp contract(off)
+  lo = hi = 0.0;
+  double p = INFINITY, s = INFINITY;
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    if (has[j]) p = fmin(p, o[j]);
+    if (has[2 + j]) s = fmin(s, o[2 + j]);
+  }
+  double factor = 1.4;
+  if (fixed_window >= 0.0) {
+    s = p + fixed_window;  // min_i (p_i + w) = min_i p_i + w: the sum is monotonic
+    factor = 0.0;
+  }
+  if (!(p < INFINITY) || !(s < INFINITY) || s < p) return;
+  const double span = s - p;
+  const double tail = factor * span;
+  const double end = s + tail;
+  lo = fmax(trunc(p), 0.0);
+  hi = fmax(trunc(end), 0.0);  // (a NaN end -- 0 * inf of onsets 10^308 apart -- gives 0: an empty box)
+}
+
+// The EQTransformer batch: x as bank_batch_kernel writes it, the P and S rows with its bits, no noise row, and the
+// detection box.
+__global__ __launch_bounds__(GEN_NTH) void bank_batch_eqt_kernel(const GenArgs a, const DetArgs d) {
+  __shared__ GenShared sh;
+  const int w = blockIdx.x, tid = threadIdx.x;
+  const int T = a.T;
+  const vp_plan_row r = a.rows[w];
+  write_window(a, r, w, tid, sh);
+
+  double o[4];
+  bool has[4];
+  window_onsets(a, r, o, has);
+  double lo, hi;
+  detection_span(o, has, d.fixed_window, lo, hi);
+  const float two_s2 = 2.f * a.sigma * a.sigma;
+  float* yw = a.y + (long long)w * 3 * T;
+  for (int t = tid; t < T; t += GEN_NTH) {
+    float ph[2];
+    phase_labels(o, has, t, two_s2, ph);
+    yw[(long long)a.row_p * T + t] = ph[0];
+    yw[(long long)a.row_s * T + t] = ph[1];
+    yw[(long long)d.row_det * T + t] = (double)t >= lo && (double)t < hi ? 1.f : 0.f;
   }
 }
 
@@ -554,6 +616,43 @@ int bank_launch(const Bank& bk, const vp_plan_row* rows_dev, int B, int T, float
   return launch(bank_batch_kernel, "bank_batch_kernel", bk, rows_dev, nullptr, B, T, sigma, norm, label_rows, x, y, s);
 }
 
+int bank_check_eqt(const Bank& bk, const vp_plan_row* rows, int B, int T, float sigma, int norm, const int* label_rows,
+                   float det_fixed_window) {
+  const int rc = bank_check(bk, rows, B, T, sigma, norm, label_rows);
+  if (rc != VP_OK) return rc;
+  VP_REQUIRE(det_fixed_window < 0.f || std::isfinite(det_fixed_window), "bank batch: det_fixed_window = %g is neither negative nor a finite length",
+             (double)det_fixed_window);  // (a NaN fails both)
+  return VP_OK;
+}
+
+int bank_launch_eqt(const Bank& bk, const vp_plan_row* rows_dev, int B, int T, float sigma, int norm, const int* label_rows,
+                    float det_fixed_window, float* x, float* y, hipStream_t s) {
+  GenArgs a{};
+  a.data = bk.data;
+  a.off = bk.off_dev;
+  a.len = bk.len_dev;
+  a.onset = bk.onset_dev;
+  a.rows = rows_dev;
+  a.x = x;
+  a.y = y;
+  a.T = T;
+  a.norm = norm;
+  a.sigma = sigma;
+  a.row_p = label_rows[1];
+  a.row_s = label_rows[2];
+  a.row_n = -1;  // there is no noise row
+  DetArgs d{};
+  d.row_det = label_rows[0];
+  d.fixed_window = det_fixed_window < 0.f ? -1.0 : (double)det_fixed_window;
+  hipLaunchKernelGGL(bank_batch_eqt_kernel, dim3(B), dim3(GEN_NTH), 0, s, a, d);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    set_error("bank_batch_eqt_kernel launch failed: %s", hipGetErrorString(e));
+    return VP_ERR_HIP;
+  }
+  return VP_OK;
+}
+
 int bank_launch_windows(const Bank& bk, const vp_plan_row* rows_dev, int B, int T, int norm, float* x, hipStream_t s) {
   const int unused_label_rows[3] = {0, 1, 2};
   return launch(bank_window_kernel, "bank_window_kernel", bk, rows_dev, nullptr, B, T, 1.f, norm, unused_label_rows, x, nullptr, s);
@@ -714,6 +813,22 @@ int vp_bank_make_batch(vp_bank* h, const vp_plan_row* rows, int B, int T, float 
                        float* x, float* y, void* stream) {
   VP_REQUIRE(h && x && y, "vp_bank_make_batch: null argument");
   return make_batch(*reinterpret_cast<Bank*>(h), rows, B, T, sigma, norm, label_rows, x, y, stream);
+}
+
+int vp_bank_make_batch_eqt(vp_bank* h, const vp_plan_row* rows, int B, int T, float sigma, int norm, const int* label_rows,
+                           float det_fixed_window, float* x, float* y, void* stream) {
+  VP_REQUIRE(h && x && y, "vp_bank_make_batch_eqt: null argument");
+  Bank& bk = *reinterpret_cast<Bank*>(h);
+  int rc = bank_check_eqt(bk, rows, B, T, sigma, norm, label_rows, det_fixed_window);
+  if (rc != VP_OK) return rc;
+  VP_HIP(hipSetDevice(bk.device));
+  const size_t bytes = (size_t)B * sizeof(vp_plan_row);
+  if ((rc = bk.ring.acquire(bytes)) != VP_OK) return rc;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const vp_plan_row* rd = static_cast<const vp_plan_row*>(bk.ring.stage({{rows, bytes}}, s));
+  if (!rd) return VP_ERR_HIP;
+  if ((rc = bank_launch_eqt(bk, rd, B, T, sigma, norm, label_rows, det_fixed_window, x, y, s)) != VP_OK) return rc;
+  return bk.ring.retire(s);
 }
 
 int vp_bank_make_batch_aug(vp_bank* h, const vp_aug_row* rows, int B, int T, float sigma, int norm, const int* label_rows,

@@ -1,11 +1,13 @@
-// C ABI of libvolpick_hip.so (include/volpick_hip.h): the passes over a waveform bank -- validation loss (vp_validate_*),
-// pick-benchmark tasks 1-3 (vp_predict_*) and the task-0 threshold sweep (vp_sweep_*) -- and the reducers of pre-cut
-// windows (vp_pick_windows, vp_predict_windows, vp_sweep_windows).
+// C ABI of libvolpick_hip.so (include/volpick_hip.h): the passes over a waveform bank -- validation loss (vp_validate_* for
+// PhaseNet, vp_validate_eqt_* for EQTransformer), pick-benchmark tasks 1-3 (vp_predict_*) and the task-0 threshold sweep
+// (vp_sweep_*) -- and the reducers of pre-cut windows (vp_pick_windows, vp_predict_windows, vp_sweep_windows).
 #include <algorithm>
+#include <cmath>
 #include <initializer_list>
 
 #include "api_handle.h"
 #include "batchgen.h"
+#include "bce.h"
 #include "predict.h"
 #include "sweep.h"
 #include "valloss.h"
@@ -15,7 +17,7 @@ using vp::run_batch;
 
 namespace vp {
 
-// What a handle keeps for its passes.  The three passes share the scratch of one batch: a handle is used by one thread at
+// What a handle keeps for its passes.  The passes share the scratch of one batch: a handle is used by one thread at
 // a time, and every batch is enqueued whole, in stream order, before the next one starts.  Their results are their own.
 struct Passes {
   template <class T>
@@ -31,6 +33,11 @@ struct Passes {
     Buf<double> batch, window;
     long long n_batches = 0, n_windows = 0;
   } val;
+  struct {  // vp_validate_eqt_begin ... vp_validate_eqt_end: one loss per batch and per window, three head values per window
+    bool open = false;
+    Buf<double> batch, window, head;
+    long long n_batches = 0, n_windows = 0;
+  } veq;
   struct {  // vp_predict_begin ... vp_predict_end: one record per window
     bool open = false;
     Buf<vp_predict_record> rec;
@@ -262,6 +269,82 @@ int vp_validate_end(vp_handle* h, double* batch_losses, long long cap, long long
   const long long nb = std::min(cap, v.n_batches), nw = std::min(cap_windows, v.n_windows);
   const int rc = download_and_wait(h, {{nb > 0 ? batch_losses : nullptr, v.batch.p, (size_t)nb * sizeof(double)},
                                        {nw > 0 ? per_window : nullptr, v.window.p, (size_t)nw * sizeof(double)}});
+  if (rc != VP_OK) return rc;
+  if (n_batches) *n_batches = v.n_batches;
+  if (n_windows) *n_windows = v.n_windows;
+  v.open = false;
+  return VP_OK;
+}
+
+// ---- EQTransformer's validation loss: detection, P and S heads (bce.hip) ----------------------------------------------------
+// The counterpart of the reference's EQTransformerLit.shared_step (volpick/model/models.py:538-549) on block 1's batch.
+int vp_validate_eqt_begin(vp_handle* h) {
+  VP_REQUIRE(h != nullptr, "vp_validate_eqt_begin: null handle");
+  if (h->net.model_kind != VP_MODEL_EQTRANSFORMER) {
+    vp::set_error("vp_validate_eqt_begin: only an EQTransformer handle has this loss (vp_validate_begin is PhaseNet's)");
+    return VP_ERR_UNSUPPORTED;
+  }
+  auto& v = passes_of(h).veq;
+  v.open = true;
+  v.n_batches = v.n_windows = 0;  // (launches of an abandoned pass run ahead of this one's on the same stream)
+  return VP_OK;
+}
+
+// generate -> forward -> the weighted BCE of all B windows, appended.
+int vp_validate_eqt_bank(vp_handle* h, vp_bank* bank, const vp_plan_row* rows, int B, float sigma, int norm, const int* label_rows,
+                         float det_fixed_window, const double* weights, float* pred_out_dev) {
+  VP_REQUIRE(h && bank && weights, "vp_validate_eqt_bank: null argument");
+  if (h->net.model_kind != VP_MODEL_EQTRANSFORMER) {
+    vp::set_error("vp_validate_eqt_bank: only an EQTransformer handle has this loss (vp_validate_bank is PhaseNet's)");
+    return VP_ERR_UNSUPPORTED;
+  }
+  auto& v = passes_of(h).veq;
+  VP_REQUIRE(v.open, "vp_validate_eqt_bank: no pass is open (vp_validate_eqt_begin)");
+  const vp::Bank& bk = *reinterpret_cast<const vp::Bank*>(bank);
+  VP_REQUIRE(bk.device == h->device, "vp_validate_eqt_bank: bank on device %d, handle on device %d", bk.device, h->device);
+  const int T = h->net.in_samples;
+  int rc = vp::bank_check_eqt(bk, rows, B, T, sigma, norm, label_rows, det_fixed_window);
+  if (rc != VP_OK) return rc;
+  double row_weights[3];  // weights are (detection, P, S); the kernel takes them by row of y
+  for (int i = 0; i < 3; ++i) {
+    VP_REQUIRE(std::isfinite(weights[i]), "vp_validate_eqt_bank: weights[%d] = %g is not finite", i, weights[i]);
+    row_weights[label_rows[i]] = weights[i];
+  }
+  VP_REQUIRE(h->net.n_out == 3, "vp_validate_eqt_bank: the model has %d outputs, the labels 3", h->net.n_out);
+  VP_HIP(hipSetDevice(h->device));
+  rc = pass_batch(
+      h, B, true, {{rows, (size_t)B * sizeof(vp_plan_row)}}, pred_out_dev,
+      [&] {
+        int r = grow_results(v.batch, (size_t)v.n_batches, (size_t)v.n_batches + 1, h->stream);
+        if (r == VP_OK) r = grow_results(v.window, (size_t)v.n_windows, (size_t)v.n_windows + B, h->stream);
+        if (r == VP_OK) r = grow_results(v.head, (size_t)v.n_windows * 3, ((size_t)v.n_windows + B) * 3, h->stream);
+        return r;
+      },
+      [&](const char* rows_dev, float* x, float* y) {
+        return vp::bank_launch_eqt(bk, reinterpret_cast<const vp_plan_row*>(rows_dev), B, T, sigma, norm, label_rows,
+                                   det_fixed_window, x, y, h->stream);
+      },
+      [&](const char*, const float* pred, const float* y) {
+        return vp::bce_launch(pred, y, B, 3, T, row_weights, v.head.p + v.n_windows * 3, v.window.p + v.n_windows,
+                              v.batch.p + v.n_batches, h->stream);
+      });
+  if (rc != VP_OK) return rc;
+  ++v.n_batches;
+  v.n_windows += B;
+  return VP_OK;
+}
+
+int vp_validate_eqt_end(vp_handle* h, double* batch_losses, long long cap, long long* n_batches, double* per_window, double* heads,
+                        long long cap_windows, long long* n_windows) {
+  VP_REQUIRE(h != nullptr, "vp_validate_eqt_end: null handle");
+  auto& v = passes_of(h).veq;
+  VP_REQUIRE(v.open, "vp_validate_eqt_end: no pass is open (vp_validate_eqt_begin)");
+  VP_REQUIRE(cap >= 0 && cap_windows >= 0 && (cap == 0 || batch_losses), "vp_validate_eqt_end: null output arrays");
+  VP_HIP(hipSetDevice(h->device));
+  const long long nb = std::min(cap, v.n_batches), nw = std::min(cap_windows, v.n_windows);
+  const int rc = download_and_wait(h, {{nb > 0 ? batch_losses : nullptr, v.batch.p, (size_t)nb * sizeof(double)},
+                                       {nw > 0 ? per_window : nullptr, v.window.p, (size_t)nw * sizeof(double)},
+                                       {nw > 0 ? heads : nullptr, v.head.p, (size_t)nw * 3 * sizeof(double)}});
   if (rc != VP_OK) return rc;
   if (n_batches) *n_batches = v.n_batches;
   if (n_windows) *n_windows = v.n_windows;

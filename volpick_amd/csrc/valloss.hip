@@ -13,6 +13,7 @@
 #include <cmath>
 #include <cstdint>
 
+#include "loss_reduce.h"
 #include "valloss.h"
 
 // every product and sum below rounds on its own, in whichever kernel it is compiled: the three kernels agree to the bit
@@ -26,46 +27,10 @@ constexpr int VCE_WAVES = VCE_NTH / 64;
 
 __device__ __forceinline__ double vce_term(float p, float y, double eps) { return (double)y * log((double)p + eps); }
 
-// Sum of v over the workgroup, the same bits in every thread.  `red`: VCE_WAVES doubles of LDS.
-__device__ __forceinline__ double block_sum(double v, double* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  __syncthreads();  // the previous sum has been read by everyone
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-#pragma unroll
-  for (int s = VCE_WAVES / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  return red[0];
-}
-
-// This thread's share of sum_i y[i] log(p[i] + eps), i in [0, n): step 1 of the header.
+// This thread's share of sum_i y[i] log(p[i] + eps), i in [0, n): step 1 of the header (loss_reduce.h).
 __device__ __forceinline__ double window_partial(const float* __restrict__ p, const float* __restrict__ y, long long n,
                                                  double eps) {
-  const int j = threadIdx.x;
-  double acc = 0.0;
-  if ((((uintptr_t)p ^ (uintptr_t)y) & 15) != 0) {
-    for (long long i = j; i < n; i += VCE_NTH) acc += vce_term(p[i], y[i], eps);
-    return acc;
-  }
-  long long head = (long long)(((16 - ((uintptr_t)p & 15)) & 15) >> 2);
-  if (head > n) head = n;
-  const long long nvec = (n - head) >> 2;
-  const long long tail = head + 4 * nvec;
-  if (j < head) acc += vce_term(p[j], y[j], eps);
-  const float4* p4 = reinterpret_cast<const float4*>(p + head);
-  const float4* y4 = reinterpret_cast<const float4*>(y + head);
-  for (long long v = j; v < nvec; v += VCE_NTH) {
-    const float4 a = p4[v], b = y4[v];
-    acc += vce_term(a.x, b.x, eps);
-    acc += vce_term(a.y, b.y, eps);
-    acc += vce_term(a.z, b.z, eps);
-    acc += vce_term(a.w, b.w, eps);
-  }
-  if (tail + j < n) acc += vce_term(p[tail + j], y[tail + j], eps);
-  return acc;
+  return strided_partial<VCE_NTH>(p, y, n, [eps](float pi, float yi) { return vce_term(pi, yi, eps); });
 }
 
 // One workgroup per window.
@@ -73,7 +38,7 @@ __global__ __launch_bounds__(VCE_NTH) void vce_window_kernel(const float* __rest
                                                              long long n, int T, double eps, double* __restrict__ per_window) {
   __shared__ double red[VCE_WAVES];
   const long long b = blockIdx.x;
-  const double s = block_sum(window_partial(p + b * n, y + b * n, n, eps), red);
+  const double s = block_sum<VCE_NTH>(window_partial(p + b * n, y + b * n, n, eps), red);
   if (threadIdx.x == 0) per_window[b] = -s / (double)T;
 }
 
@@ -83,7 +48,7 @@ __global__ __launch_bounds__(VCE_NTH) void vce_batch_kernel(const double* __rest
   __shared__ double red[VCE_WAVES];
   double acc = 0.0;
   for (int b = threadIdx.x; b < B; b += VCE_NTH) acc += per_window[b];
-  const double s = block_sum(acc, red);
+  const double s = block_sum<VCE_NTH>(acc, red);
   if (threadIdx.x == 0) *batch = s / (double)B;
 }
 
@@ -94,10 +59,10 @@ __global__ __launch_bounds__(VCE_NTH) void vce_batch_only_kernel(const float* __
   __shared__ double red[VCE_WAVES];
   double acc = 0.0;
   for (int b = 0; b < B; ++b) {
-    const double s = block_sum(window_partial(p + (long long)b * n, y + (long long)b * n, n, eps), red);
+    const double s = block_sum<VCE_NTH>(window_partial(p + (long long)b * n, y + (long long)b * n, n, eps), red);
     if (b % VCE_NTH == (int)threadIdx.x) acc += -s / (double)T;
   }
-  const double s = block_sum(acc, red);
+  const double s = block_sum<VCE_NTH>(acc, red);
   if (threadIdx.x == 0) *batch = s / (double)B;
 }
 

@@ -36,9 +36,18 @@ constant here:
 * ``GAP_DRAW`` and ``GAP_NOISE_ROW`` -- how ``AddGap`` draws its gap and which label row it sets to 1 there;
 * ``EVENT_END_INDEX`` -- how a non-integer first-event end becomes a sample index;
 * ``STEERED_CENTRE``, ``STEERED_CLAMP`` and ``STEERED_SHORT_TRACE`` -- where ``SteeredWindow(strategy="pad")`` puts the
-  window around its target (:class:`SteeredPlanner`, the evaluation windows of the pick-benchmark tasks 1-3).
+  window around its target (:class:`SteeredPlanner`, the evaluation windows of the pick-benchmark tasks 1-3);
+* ``DETECTION_FACTOR``, ``DETECTION_ONSET``, ``DETECTION_INDEX``, ``DETECTION_NEEDS`` and ``DETECTION_ORDER`` -- the
+  box ``DetectionLabeller`` draws from P to behind S (EQTransformer's ``detections`` row).
 
-Out of scope: array rotation (``rotate_array`` defaults to False and no config sets it).
+EQTransformer's block 1 (``EQTransformerLit.get_joint_augmentation_block1``, models.py:606-666) differs in three things:
+the windows (``samples_before=6000``, ``windowlen=12000``, ``RandomWindow(windowlen=6000)``), the labeller's
+``noise_column=False`` -- ``y`` is the P and S rows alone, not rescaled -- and a ``DetectionLabeller`` that writes
+``detections``.  ``vp_bank_make_batch_eqt`` executes it on the same plan rows; :meth:`WaveformBank.make_batch` chooses it
+for a model whose labels start with ``"Detection"``.
+
+Out of scope: array rotation (``rotate_array`` defaults to False and no config sets it); EQTransformer's stacked recipe
+(``SuperimposeEvent`` / ``MyDuplicateEvent`` with ``detection_keys``, ``AddGap`` on ``detections``).
 """
 from __future__ import annotations
 
@@ -64,6 +73,13 @@ STEERED_CENTRE = "floor"    # SteeredWindow: p0 = start - (windowlen - (end - st
                             # lies behind the target
 STEERED_CLAMP = True        # ... then p0 is moved into [0, L - windowlen]: a window inside the trace, not zeros beside it
 STEERED_SHORT_TRACE = "pad_end"  # a trace shorter than windowlen: p0 = 0, zeros behind the trace, borders as given
+# DetectionLabeller(p_phases, s_phases=s_phases), ndim == 2 (EQTransformer's block 1; fixed in the kernel, asserted where
+# the rule is restated): y[p0:p1] = 1 with p0 = max(int(p), 0), p1 = max(int(s + DETECTION_FACTOR * (s - p)), 0)
+DETECTION_FACTOR = 1.4      # the detection ends factor * (S - P) behind S; 0 with a fixed window, where s = p + fixed_window
+DETECTION_ONSET = "earliest"  # p and s: the minimum of the phase's finite onsets (window-relative)
+DETECTION_INDEX = np.trunc  # int(.): truncation toward zero, of p and of the end; the end rounds its product before its sum
+DETECTION_NEEDS = "P and S"  # no finite P onset or no finite S onset: the row is 0
+DETECTION_ORDER = "s >= p"  # an S before the P: the row is 0 (s == p with no tail: an empty slice)
 
 # the reference's phase_dict (volpick/model/models.py:26-31): metadata column -> phase, two columns per phase
 PHASE_DICT = {
@@ -124,6 +140,19 @@ def label_rows(labels) -> np.ndarray:
     if sorted(labels) != ["N", "P", "S"]:
         raise ValueError(f"labels must be a permutation of 'PSN', got {labels!r}")
     return np.array([labels.index("P"), labels.index("S"), labels.index("N")], np.int32)
+
+
+def has_detection_row(labels) -> bool:
+    """True for EQTransformer's labels (``["Detection", "P", "S"]``): the batch carries a detection row, not a noise row."""
+    return "Detection" in list(labels)
+
+
+def detection_label_rows(labels) -> np.ndarray:
+    """Output row of detection, P and S for an EQTransformer's ``labels`` (``["Detection", "P", "S"]`` in any order)."""
+    labels = list(labels)
+    if sorted(labels) != ["Detection", "P", "S"]:
+        raise ValueError(f"labels must be a permutation of ['Detection', 'P', 'S'], got {labels!r}")
+    return np.array([labels.index("Detection"), labels.index("P"), labels.index("S")], np.int32)
 
 
 def _onset_table(onsets, n):
@@ -251,21 +280,42 @@ class WaveformBank:
             onsets[phase] = np.stack(cols, axis=1)
         return cls(waveforms, onsets, device=device)
 
-    def make_batch(self, rows, model, sigma):
+    def make_batch(self, rows, model, sigma, detection_fixed_window=None):
         """``{"X", "y"}``: (B, 3, model.in_samples) fp32 CUDA tensors written on torch's current stream -- what
         ``PhaseNetLit.training_step`` / ``validation_step`` take.  ``rows``: plan rows (``PLAN_ROW``, block 1 alone) or
-        augmented rows (``AUG_ROW``, from :class:`AugmentedPlanner`)."""
+        augmented rows (``AUG_ROW``, from :class:`AugmentedPlanner`).
+
+        A model with a detection row (an EQTransformer) gets ``{"X": (B, 3, T), "y": (B, 2, T), "detections": (B, 1, T)}``,
+        what ``EQTransformerLit.shared_step`` reads: ``y`` holds P and S, and both are views of one (B, 3, T) tensor in the
+        order detection, P, S (``vp_bank_make_batch_eqt``; plan rows only).  ``detection_fixed_window``: the detection's
+        length in samples from P, ``None`` = to behind S (the module's ``DETECTION_*`` constants)."""
         import torch
 
         aug = getattr(rows, "dtype", None) == AUG_ROW
-        rows = as_aug_rows(rows) if aug else as_rows(rows)
-        name = "vp_bank_make_batch_aug" if aug else "vp_bank_make_batch"
         T = int(model.in_samples)
         dev = torch.device("cuda", self.device)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if has_detection_row(model.labels):
+            if aug:
+                raise ValueError("augmented rows with an EQTransformer model: its stacked recipe (detections through "
+                                 "SuperimposeEvent, MyDuplicateEvent and AddGap) is not implemented; plan block 1 alone")
+            detection_label_rows(model.labels)  # (the model's labels are what the batch is laid out for)
+            rows = as_rows(rows)
+            x = torch.empty((len(rows), 3, T), dtype=torch.float32, device=dev)
+            y = torch.empty_like(x)
+            lr_ = np.array([0, 1, 2], np.int32)
+            _lib.check(self._lib.vp_bank_make_batch_eqt(
+                self._h, rows.ctypes.data_as(C.c_void_p), len(rows), T, float(sigma), _norm(model.norm),
+                lr_.ctypes.data_as(C.POINTER(C.c_int)), _fixed_window(detection_fixed_window), C.c_void_p(x.data_ptr()),
+                C.c_void_p(y.data_ptr()), C.c_void_p(stream)), "vp_bank_make_batch_eqt")
+            return {"X": x, "y": y[:, 1:3], "detections": y[:, 0:1]}
+        if detection_fixed_window is not None:
+            raise ValueError("detection_fixed_window: the model has no detection row")
+        rows = as_aug_rows(rows) if aug else as_rows(rows)
+        name = "vp_bank_make_batch_aug" if aug else "vp_bank_make_batch"
         x = torch.empty((len(rows), 3, T), dtype=torch.float32, device=dev)
         y = torch.empty_like(x)
         lr_ = label_rows(model.labels)
-        stream = torch.cuda.current_stream(dev).cuda_stream
         _lib.check(getattr(self._lib, name)(self._h, rows.ctypes.data_as(C.c_void_p), len(rows), T, float(sigma),
                                             _norm(model.norm), lr_.ctypes.data_as(C.POINTER(C.c_int)),
                                             C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(stream)), name)
@@ -287,6 +337,16 @@ def _norm(norm):
     if norm not in ("peak", "std"):
         raise ValueError(f"norm must be 'peak' or 'std', got {norm!r}")
     return _lib.VP_NORM_PEAK if norm == "peak" else _lib.VP_NORM_STD
+
+
+def _fixed_window(detection_fixed_window):
+    """The C argument det_fixed_window: the length in samples, or -1 for ``None`` (the detection follows S)."""
+    if detection_fixed_window is None:
+        return -1.0
+    w = float(detection_fixed_window)
+    if not (np.isfinite(w) and w >= 0):
+        raise ValueError(f"detection_fixed_window must be None or a finite length >= 0, got {detection_fixed_window!r}")
+    return w
 
 
 class WindowPlanner:

@@ -20,6 +20,11 @@ batch from a bank, run the inference forward and reduce ``vector_cross_entropy``
 (``vp_validate_begin`` / ``_bank`` / ``_end``), and ``fit_bank`` feeds that loss to what the released config trains with
 (``configure_optimizers``, :187-219, and the callbacks of the reference's train.py:137-179): ``ReduceLROnPlateau`` (torch's
 arithmetic, restated here without torch), the weights of the lowest validation loss, and the early stop.
+
+EQTransformer has the validation half alone (``EQTransformerLit``, models.py:483-879): block 1's batch with its detection
+row from a bank, and ``shared_step``'s weighted binary cross entropy (``bce_loss`` on the host, ``validate_batches_eqt`` /
+``EQTransformerLit.validate_bank`` on the GPU: ``vp_validate_eqt_begin`` / ``_bank`` / ``_end``).  Its training step and its
+stacked recipe are not implemented.
 """
 from __future__ import annotations
 
@@ -29,7 +34,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .models import PhaseNet
+from .models import EQTransformer, PhaseNet
 
 
 def vector_cross_entropy(y_pred, y_true, eps=1e-5):
@@ -37,6 +42,29 @@ def vector_cross_entropy(y_pred, y_true, eps=1e-5):
     h = y_true * np.log(y_pred + eps)
     h = h.mean(-1).sum(-1) if y_pred.ndim == 3 else h.sum(-1)
     return -float(h.mean())
+
+
+EQT_LOSS_WEIGHTS = (0.05, 0.40, 0.55)  # the reference's EQTransformerLit loss_weights: detection, P, S
+
+
+def bce_heads(p, y):
+    """``torch.nn.BCELoss`` per window and row of (B, C, T) arrays, unreduced over both: the (B, C) float64 means over T
+    of ``-(y max(log p, -100) + (1 - y) max(log(1 - p), -100))``.  The clamp is torch's and keeps a NaN."""
+    p, y = np.asarray(p, np.float64), np.asarray(y, np.float64)
+    with np.errstate(all="ignore"):
+        term = -(y * np.maximum(np.log(p), -100.0) + (1.0 - y) * np.maximum(np.log(1.0 - p), -100.0))
+    return term.mean(-1)
+
+
+def bce_loss(p, y, weights):
+    """The loss of the reference's ``EQTransformerLit.shared_step`` (models.py:538-549) on numpy arrays (B, C, T):
+    ``sum_c weights[c] * BCELoss(p[:, c], y[:, c])``, as the mean over the windows of ``sum_c weights[c] * head[b][c]``
+    (every window has T samples, so the two are one number)."""
+    w = np.asarray(weights, np.float64)
+    heads = bce_heads(p, y)
+    if w.shape != (heads.shape[1],):
+        raise ValueError(f"weights: one per row, {heads.shape[1]}, got {w.shape}")
+    return float((heads * w).sum(-1).mean())
 
 
 def gaussian_labels(p_samples, s_samples, n_samples=3001, sigma=20.0):
@@ -541,3 +569,116 @@ class PhaseNetLit:
     @property
     def trainer_state(self):
         return self._ensure()
+
+
+def validate_batches_eqt(model, bank, batches, sigma, loss_weights=EQT_LOSS_WEIGHTS, detection_fixed_window=None,
+                         predictions=False):
+    """One validation pass of an EQTransformer on the GPU (``vp_validate_eqt_begin`` ... ``vp_validate_eqt_end``): every
+    element of ``batches`` (plan rows, any number per batch) is cut from ``bank`` and labelled as ``make_batch`` does for the
+    model (P, S and the detection box), run through the model's inference path and scored with
+    ``loss_weights[0] BCE(detection) + loss_weights[1] BCE(P) + loss_weights[2] BCE(S)`` in float64 on the device; the host
+    waits once, at the end.  Returns ``(batch_losses, window_losses, head_losses)``: float64 arrays with one loss per batch,
+    one per window and the unweighted (detection, P, S) values per window, (n_windows, 3); with ``predictions=True`` also the
+    list of the batches' (B, 3, T) predictions (CUDA tensors)."""
+    from .evaluate import prediction_tensor
+    from .generate import as_rows, detection_label_rows, _fixed_window, _norm
+
+    lib = _lib.load()
+    if model._device_index is None:
+        model.cuda(bank.device)
+    h = model._ensure_handle()
+    lrows = detection_label_rows(model.labels)
+    w = np.ascontiguousarray(loss_weights, np.float64)
+    if w.shape != (3,):
+        raise ValueError(f"loss_weights: three weights (detection, P, S), got {loss_weights!r}")
+    fixed = _fixed_window(detection_fixed_window)
+    preds, n_windows, n_batches = [], 0, 0
+    _lib.check(lib.vp_validate_eqt_begin(h), "vp_validate_eqt_begin")
+    try:
+        for rows in batches:
+            rows = as_rows(rows)
+            if predictions:
+                preds.append(prediction_tensor(model, len(rows)))
+            _lib.check(lib.vp_validate_eqt_bank(h, bank.handle, _lib.ptr(rows), len(rows), float(sigma), _norm(model.norm),
+                                                lrows.ctypes.data_as(C.POINTER(C.c_int)), fixed,
+                                                w.ctypes.data_as(C.POINTER(C.c_double)),
+                                                C.c_void_p(preds[-1].data_ptr()) if predictions else None), "vp_validate_eqt_bank")
+            n_batches += 1
+            n_windows += len(rows)
+    finally:
+        batch = np.empty(n_batches, np.float64)
+        window = np.empty(n_windows, np.float64)
+        heads = np.empty((n_windows, 3), np.float64)
+        nb, nw = C.c_longlong(), C.c_longlong()
+        dp = C.POINTER(C.c_double)
+        rc = lib.vp_validate_eqt_end(h, batch.ctypes.data_as(dp), n_batches, C.byref(nb), window.ctypes.data_as(dp),
+                                     heads.ctypes.data_as(dp), n_windows, C.byref(nw))
+    _lib.check(rc, "vp_validate_eqt_end")
+    assert (nb.value, nw.value) == (n_batches, n_windows)
+    heads = heads[:, lrows]  # by row of y -> (detection, P, S)
+    return (batch, window, heads, preds) if predictions else (batch, window, heads)
+
+
+class EQTransformerLit:
+    """The validation half of the reference's ``EQTransformerLit`` (models.py:483-879): block 1's batch and
+    ``shared_step``'s loss ``loss_weights[0] BCE(detection) + loss_weights[1] BCE(P) + loss_weights[2] BCE(S)``, by which
+    the reference selects its checkpoints.  ``validation_step(batch)`` takes what ``WaveformBank.make_batch`` returns for
+    the model: ``{"X": (B, 3, 6000), "y": (B, 2, 6000), "detections": (B, 1, 6000)}``.  Training is not implemented."""
+
+    def __init__(self, lr=1e-2, sigma=20, loss_weights=EQT_LOSS_WEIGHTS, detection_fixed_window=None,
+                 prob_label_shape="gaussian", model=None, device=0, **model_kwargs):
+        if prob_label_shape != "gaussian":
+            raise ValueError(f"prob_label_shape {prob_label_shape!r}: only 'gaussian' labels are implemented (every "
+                             "reference config uses them)")
+        if len(loss_weights) != 3:
+            raise ValueError(f"loss_weights: three weights (detection, P, S), got {loss_weights!r}")
+        self.prob_label_shape = prob_label_shape
+        self.lr = float(lr)
+        self.sigma = sigma
+        self.loss_weights = tuple(float(w) for w in loss_weights)
+        self.detection_fixed_window = detection_fixed_window
+        self.model = model if model is not None else EQTransformer(**model_kwargs)
+        self._device = device
+
+    def _model_on_device(self):
+        if self.model._device_index is None:
+            self.model.cuda(self._device)
+        return self.model
+
+    def training_step(self, batch, batch_idx=None):
+        raise NotImplementedError("EQTransformer training is not implemented: this class validates (validation_step, "
+                                  "validate_bank)")
+
+    def window_planner(self, bank, batch_size, seed=0):
+        """Block 1's windows for this model (models.py:606-652): around a pick with ``samples_before=6000`` in an extent of
+        12000 samples, then a random window of 6000."""
+        from .generate import WindowPlanner
+
+        return WindowPlanner(bank, batch_size, samples_before=6000, first_windowlen=12000, in_samples=self.model.in_samples,
+                             seed=seed)
+
+    def make_batch(self, bank, rows):
+        return bank.make_batch(rows, self.model, self.sigma, detection_fixed_window=self.detection_fixed_window)
+
+    def validation_step(self, batch, batch_idx=None):
+        """``shared_step`` on the host: the model's output copied back, ``bce_loss`` in numpy float64."""
+        host = lambda a: a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+        det, p, s = self._model_on_device()(batch["X"])
+        pred = np.stack([host(det), host(p), host(s)], axis=1)
+        y = np.concatenate([host(batch["detections"]), host(batch["y"])], axis=1)
+        return bce_loss(pred, y, self.loss_weights)
+
+    def validate_bank(self, val_bank, planner_or_rows, per_window=False):
+        """The validation loss of every batch of ``planner_or_rows`` -- a planner (its ``validation()`` batches), one array
+        of rows (one batch) or an iterable of such arrays -- on the GPU from end to end (``validate_batches_eqt``: one host
+        wait).  Returns the list of batch losses; with ``per_window=True`` ``(batch_losses, window_losses)``, the latter one
+        float64 array over all windows in order."""
+        if hasattr(planner_or_rows, "validation"):
+            batches = planner_or_rows.validation()
+        elif getattr(getattr(planner_or_rows, "dtype", None), "names", None):  # one array of rows: one batch
+            batches = [planner_or_rows]
+        else:
+            batches = planner_or_rows
+        batch, window, _ = validate_batches_eqt(self._model_on_device(), val_bank, batches, self.sigma, self.loss_weights,
+                                                self.detection_fixed_window)
+        return (batch.tolist(), window) if per_window else batch.tolist()
