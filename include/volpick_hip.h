@@ -687,6 +687,31 @@ int vp_train_step_bank_aug(vp_trainer* t, vp_bank* bank, const vp_aug_row* rows,
 int vp_bank_make_batch_eqt(vp_bank* bank, const vp_plan_row* rows, int B, int T, float sigma, int norm, const int* label_rows,
                            float det_fixed_window, float* x, float* y, void* stream);
 
+/* EQTransformer's augmented windows: the block 1 above, then the stacking slots, AddGap on y and detections and the second
+ * Normalize of the reference's EQTransformerLit (get_train_augmentations / get_val_augmentations with stack_data,
+ * volpick/model/models.py:668-844).  The records are the vp_aug_row of vp_bank_make_batch_aug, planned with EQTransformer's
+ * windows (volpick_amd/generate.py, AugmentedPlanner with its event_* arguments); y has the rows label_rows[0] (detection
+ * D), label_rows[1] (P) and label_rows[2] (S), no noise row.  One record per window is executed in this order:
+ *   1. primary: x, P, S and D as vp_bank_make_batch_eqt writes them for `primary`;
+ *   2. x[c][t] = 0 for t >= cut (cut = T: no truncation);
+ *   3. per event entry with kind != VP_AUG_NONE, in order: the source s is `row` cut, demeaned and normalised as in step 1,
+ *      with its own P_s, S_s and detection box D_s from the row's window-relative onsets (VP_AUG_BANK), or the primary
+ *      window with its labels as they were after step 1 (VP_AUG_SELF, `row` all zero).  VP_AUG_BANK only: every channel c
+ *      whose current x[c] is all |x| <= 1e-8 is zeroed in s.  s[:, :zero_before] = 0; then x[c][t] += scale * s[c][t - shift],
+ *      P[t] = max(P[t], P_s[t - shift]) and S likewise -- noise_label = False: no division by max(1, P + S) -- and
+ *      D[t] = max(D[t], D_s[t - shift]) ONLY WHEN shift != 0: the reference's shift of the detection row has no branch for
+ *      an unshifted source, whose detection is therefore dropped while its waveform and its P and S are merged.  A position
+ *      t - shift outside [0, T) contributes 0;
+ *   4. noise entries and 5. Gaussian noise: as steps 4 and 5 of vp_bank_make_batch_aug (the labels are untouched; the same
+ *      Philox key and counter);
+ *   6. x = P = S = D = 0 on [gap_lo, gap_hi): no row is set to 1;
+ *   7. x demeaned and normalised again with `norm` (float64 statistics, one rounding to fp32).
+ * Checked on the host as vp_bank_make_batch_aug checks, field for field, with 1 <= T <= 6144, and det_fixed_window negative
+ * or finite: VP_ERR_INVALID launches nothing and leaves x and y untouched.  vp_validate_eqt_bank_aug (below) is
+ * vp_validate_eqt_bank on such records. */
+int vp_bank_make_batch_eqt_aug(vp_bank* bank, const vp_aug_row* rows, int B, int T, float sigma, int norm,
+                               const int* label_rows, float det_fixed_window, float* x, float* y, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Validation loss on the device: the reference's vector_cross_entropy (volpick/model/models.py:34-51) of predictions
  * that never leave the GPU, in float64, and the validation half of its training loop (validation_step, :171-174) on
@@ -759,6 +784,8 @@ int vp_validate_end(vp_handle* h, double* batch_losses, long long cap, long long
  *                                  (the reference's loss_weights: 0.05, 0.40, 0.55), appended to device arrays of the
  *                                  handle.  pred_out_dev, when not NULL, receives the (B, 3, T) predictions.  Any B >= 1.
  *                                  Everything is checked before anything is enqueued; a refused call appends nothing.
+ *   vp_validate_eqt_bank_aug       the same on vp_aug_row records, generated as vp_bank_make_batch_eqt_aug does; it appends
+ *                                  to the same open pass, and batches of either kind may alternate within one pass.
  *   vp_validate_eqt_end(h, ...)    waits for the stream -- the pass's only host wait in the steady state -- and copies out
  *                                  up to `cap` batch losses, `cap_windows` window values (per_window, may be NULL) and
  *                                  3 * `cap_windows` head values (heads, [window][row of y], may be NULL), in the order
@@ -770,6 +797,8 @@ int vp_bce_loss(int device_id, const float* p_dev, const float* y_dev, int B, in
 int vp_validate_eqt_begin(vp_handle* h);
 int vp_validate_eqt_bank(vp_handle* h, vp_bank* bank, const vp_plan_row* rows, int B, float sigma, int norm,
                          const int* label_rows, float det_fixed_window, const double* weights, float* pred_out_dev);
+int vp_validate_eqt_bank_aug(vp_handle* h, vp_bank* bank, const vp_aug_row* rows, int B, float sigma, int norm,
+                             const int* label_rows, float det_fixed_window, const double* weights, float* pred_out_dev);
 int vp_validate_eqt_end(vp_handle* h, double* batch_losses, long long cap, long long* n_batches, double* per_window,
                         double* heads, long long cap_windows, long long* n_windows);
 

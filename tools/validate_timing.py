@@ -11,7 +11,11 @@ At B = 512 and B = 64, medians after warm-up:
   step    ms of one ``step_bank`` as ``fit_bank`` runs it (the loss read back every step) and with the steps queued.
 ``--model eqtransformer`` times EQTransformer's pass instead (``validate_batches_eqt``, B = 256 and B = 64): the device
 batch, generation, forward and the weighted-BCE kernel each alone, the host route of ``EQTransformerLit.validation_step``,
-and ``vp_vce_loss`` on the loss kernel's arrays -- the same bytes with one float64 logarithm per element instead of two.
+and ``vp_vce_loss`` on the loss kernel's arrays -- the same bytes with one float64 logarithm per element instead of two;
+then the stacked recipe beside block 1 (``aug_*``: ``EQTransformerLit.augmented_planner`` with the reference's branch
+probabilities, ``vp_bank_make_batch_eqt_aug`` / ``vp_validate_eqt_bank_aug``), the two alternating call by call: generation
+alone as one call between two events and as 20 calls queued between two events (the row upload of a call then runs under
+the previous call's kernel), and the device batch in a pass.
 usage: validate_timing.py [--batches 20] [--passes 7] [--model phasenet|eqtransformer]"""
 import argparse
 import ctypes as C
@@ -64,6 +68,18 @@ def event_ms(fn, n, warm=3):
         if i >= warm:
             out.append(a.elapsed_time(b))
     return float(np.median(out))
+
+
+def alternating_ms(fa, fb, n, warm=2, timer=None):
+    """Medians of fa() and fb() timed turn by turn (a, b, a, b, ...), so that both see the same machine."""
+    timer = timer or wall_ms
+    a, b = [], []
+    for i in range(warm + n):
+        ta, tb = timer(fa, 1, warm=0), timer(fb, 1, warm=0)
+        if i >= warm:
+            a.append(ta)
+            b.append(tb)
+    return float(np.median(a)), float(np.median(b))
 
 
 rng = np.random.default_rng(0)
@@ -119,9 +135,34 @@ def eqtransformer_mode():
         for _ in range(3):
             bce_loss(p_host, y_host, lit.loss_weights)
         r["host_numpy_loss_ms"] = 1e3 * (time.perf_counter() - t0) / 3
+        # the stacked recipe beside block 1: the first three quarters of the bank as event sources, the rest as noise sources
+        n_ev = 3 * args.traces // 4
+        aug = G.Augmentation(val_event_traces=np.arange(n_ev), val_noise_traces=np.arange(n_ev, args.traces))
+        aplanner = lit.augmented_planner(bank, B, aug, seed=B, validation=True)
+        aplans = [aplanner.plan(rng.integers(0, args.traces, B)) for _ in range(N)]
+        allrows = np.concatenate(aplans)
+        r["aug_fraction_with_event"] = float((allrows["event"]["kind"] != 0).any(axis=1).mean())
+        r["aug_fraction_with_stacked_noise"] = float((allrows["noise"]["kind"] != 0).any(axis=1).mean())
+        r["aug_fraction_with_gauss"] = float((allrows["gauss"] > 0).mean())
+        r["aug_fraction_with_gap"] = float((allrows["gap_hi"] > allrows["gap_lo"]).mean())
+        r["aug_source_windows_per_window"] = float(((allrows["event"]["kind"] != 0).sum(axis=1)
+                                                    + (allrows["noise"]["kind"] != 0).sum(axis=1)).mean())
+        ia, ib = iter(plans * 40), iter(aplans * 40)
+        r["generate_ms"], r["aug_generate_ms"] = alternating_ms(
+            lambda: lit.make_batch(bank, next(ia)), lambda: lit.make_batch(bank, next(ib)), 4 * N, warm=5, timer=event_ms)
+
+        def queued(batches):
+            for rows in batches:
+                lit.make_batch(bank, rows)
+
+        q0, q1 = alternating_ms(lambda: queued(plans), lambda: queued(aplans), 15, warm=3, timer=event_ms)
+        r["generate_ms_queued"], r["aug_generate_ms_queued"] = q0 / N, q1 / N
+        p0, p1 = alternating_ms(lambda: validate_batches_eqt(model, bank, plans, lit.sigma),
+                                lambda: validate_batches_eqt(model, bank, aplans, lit.sigma), max(args.passes, 9), warm=2)
+        r["device_ms_per_batch_in_a_pass_again"], r["aug_device_ms_per_batch_in_a_pass"] = p0 / N, p1 / N
         print(f"B = {B}")
         for k, v in r.items():
-            print(f"  {k:34s} {v:9.3f}")
+            print(f"  {k:38s} {v:9.3f}")
 
 
 if args.model == "eqtransformer":

@@ -333,6 +333,10 @@ SIGNATURES = {
         C.c_int,
         [_H, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_int), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p],
     ),
+    "vp_bank_make_batch_eqt_aug": (
+        C.c_int,
+        [_H, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_int), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
     "vp_bce_loss": (
         C.c_int,
         [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p,
@@ -340,6 +344,10 @@ SIGNATURES = {
     ),
     "vp_validate_eqt_begin": (C.c_int, [_H]),
     "vp_validate_eqt_bank": (
+        C.c_int,
+        [_H, _H, C.c_void_p, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_int), C.c_float, C.POINTER(C.c_double), C.c_void_p],
+    ),
+    "vp_validate_eqt_bank_aug": (
         C.c_int,
         [_H, _H, C.c_void_p, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_int), C.c_float, C.POINTER(C.c_double), C.c_void_p],
     ),

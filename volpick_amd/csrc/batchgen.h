@@ -83,5 +83,11 @@ int bank_launch_windows(const Bank& bk, const vp_plan_row* rows_dev, int B, int 
 int bank_check(const Bank& bk, const vp_aug_row* rows, int B, int T, float sigma, int norm, const int* label_rows);
 int bank_launch(const Bank& bk, const vp_aug_row* rows_dev, int B, int T, float sigma, int norm, const int* label_rows,
                 float* x, float* y, hipStream_t s);
+// EQTransformer's augmented rows (vp_bank_make_batch_eqt_aug): the checks of the augmented bank_check with T <= 6144, plus
+// det_fixed_window; label_rows = the rows of detection, P and S.
+int bank_check_eqt(const Bank& bk, const vp_aug_row* rows, int B, int T, float sigma, int norm, const int* label_rows,
+                   float det_fixed_window);
+int bank_launch_eqt(const Bank& bk, const vp_aug_row* rows_dev, int B, int T, float sigma, int norm, const int* label_rows,
+                    float det_fixed_window, float* x, float* y, hipStream_t s);
 
 }  // namespace vp

@@ -455,6 +455,201 @@ __global__ __launch_bounds__(GEN_NTH) void bank_aug_kernel(const GenArgs a) {
   }
 }
 
+// Row r cut, demeaned and normalised into v (fp32, 0 behind T): a primary window or a source.
+template <int E>
+__device__ __forceinline__ void load_normalised(const GenArgs& a, const vp_plan_row& r, int tid, GenShared& sh, float v[3][E]) {
+  const int T = a.T;
+  gather_window(a, r, tid, v);
+  double mean[3], den[3];
+  window_stats(v, T, a.norm == VP_NORM_PEAK, tid, sh, mean, den);
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int k = 0; k < E; ++k) v[c][k] = tid + k * GEN_NTH < T ? (float)(((double)v[c][k] - mean[c]) / den[c]) : 0.f;
+}
+
+// The labels of row r shifted by d samples, merged into P, S and -- with_det -- D by maximum: label(t) = label_r(t - d)
+// where 0 <= t - d < T, else 0 (which changes no maximum of labels >= 0).
+template <int E>
+__device__ __forceinline__ void merge_labels(const GenArgs& a, const vp_plan_row& r, int d, bool with_det, double fixed_window,
+                                             int tid, float P[E], float S[E], float D[E]) {
+  double o[4], lo, hi;
+  bool has[4];
+  window_onsets(a, r, o, has);
+  detection_span(o, has, fixed_window, lo, hi);
+  const float two_s2 = 2.f * a.sigma * a.sigma;
+#pragma unroll
+  for (int k = 0; k < E; ++k) {
+    const int ts = tid + k * GEN_NTH - d;
+    if (ts < 0 || ts >= a.T) continue;
+    float ph[2];
+    phase_labels(o, has, ts, two_s2, ph);
+    P[k] = fmaxf(P[k], ph[0]);
+    S[k] = fmaxf(S[k], ph[1]);
+    if (with_det && (double)ts >= lo && (double)ts < hi) D[k] = 1.f;
+  }
+}
+
+// v again, behind a wall the compiler does not see through: what follows from it (addresses, bounds predicates) is computed
+// where it is used, not hoisted to the head of the kernel and held in registers -- or spilled -- across every step.
+__device__ __forceinline__ int opaque(int v) {
+  asm volatile("" : "+v"(v));
+  return v;
+}
+
+// One augmented EQTransformer window per workgroup (include/volpick_hip.h, vp_bank_make_batch_eqt_aug): the record's steps
+// in order on x.  x, a source and the float64 statistics together do not fit the 128 registers of a 1024-thread workgroup,
+// so x lives in LDS between steps 1 and 7 -- xs[c][t], every sample read and written by the one thread t % 1024, hence
+// without barriers of its own -- and registers hold one window at a time: the primary, a source, then x for step 7.  A
+// source is shifted through a second LDS row, one channel at a time.  No step between 1 and 7 reads a label, and a label
+// is a maximum over the primary and the event sources of values that follow from onsets alone; so P, S and D are formed
+// once, behind the store of x.
+__global__ __launch_bounds__(GEN_NTH) void bank_aug_eqt_kernel(const GenArgs a, const DetArgs dt) {
+  constexpr int E = GEN_MAXE;
+  __shared__ GenShared sh;
+  __shared__ float stage[GEN_MAX_T];
+  __shared__ float xs[3][GEN_MAX_T];
+  const int w = blockIdx.x, tid0 = threadIdx.x;
+  const int T = a.T;
+  const vp_aug_row& rec = a.aug[w];
+  const vp_plan_row pr = rec.primary;
+  float v[3][E];
+
+  // max|x| per channel (sign = false) or max x (sign = true) over the window: m[c] for every thread
+  auto x_max = [&](bool sign, float m[3]) {
+    const int tid = opaque(tid0);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      m[c] = sign ? -INFINITY : 0.f;
+      for (int t = tid; t < T; t += GEN_NTH) m[c] = fmaxf(m[c], sign ? xs[c][t] : fabsf(xs[c][t]));
+    }
+    block_max3(m, tid, sh);
+  };
+  // a source window into v, its channels zeroed where the current x is all |x| <= 1e-8; returns max|x| over every channel
+  auto load_source = [&](const vp_plan_row& r, bool zero_rule) -> float {
+    float m[3] = {0.f, 0.f, 0.f};
+    if (zero_rule) x_max(false, m);
+    const int tid = opaque(tid0);
+    load_normalised(a, r, tid, sh, v);
+    if (!zero_rule) return 0.f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      if (!(m[c] > 1e-8f))
+#pragma unroll
+        for (int k = 0; k < E; ++k) v[c][k] = 0.f;
+    return fmaxf(fmaxf(m[0], m[1]), m[2]);
+  };
+
+  // 1. the primary window, as bank_batch_eqt_kernel writes it; 2. the truncation behind the first event
+  load_normalised(a, pr, opaque(tid0), sh, v);
+  const int cut = rec.cut;
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int k = 0; k < E; ++k) {
+      const int t = tid0 + k * GEN_NTH;
+      if (t < T) xs[c][t] = t < cut ? v[c][k] : 0.f;
+    }
+
+  // 3. events: a duplicate is the primary window as step 1 left it, cut and normalised again to the same bits
+#pragma unroll 1
+  for (int i = 0; i < 2; ++i) {
+    const vp_aug_event& ev = rec.event[i];
+    if (ev.kind == VP_AUG_NONE) continue;
+    load_source(ev.kind == VP_AUG_BANK ? ev.row : pr, ev.kind == VP_AUG_BANK);
+    const int zb = ev.zero_before, d = ev.shift;
+    const float scale = ev.scale;
+    const int tid = opaque(tid0);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+#pragma unroll
+      for (int k = 0; k < E; ++k) {
+        const int t = tid + k * GEN_NTH;
+        if (t < T) stage[t] = t < zb ? 0.f : v[c][k];
+      }
+      __syncthreads();
+      for (int t = tid; t < T; t += GEN_NTH) {
+        const int ts = t - d;
+        if (ts >= 0 && ts < T) xs[c][t] += scale * stage[ts];
+      }
+      __syncthreads();
+    }
+  }
+
+  // 4. noise windows
+#pragma unroll 1
+  for (int j = 0; j < 2; ++j) {
+    const vp_aug_noise& nz = rec.noise[j];
+    if (nz.kind == VP_AUG_NONE) continue;
+    const float f = load_source(nz.row, true) * nz.scale;
+    const int tid = opaque(tid0);
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+      for (int k = 0; k < E; ++k) {
+        const int t = tid + k * GEN_NTH;
+        if (t < T) xs[c][t] += v[c][k] * f;
+      }
+  }
+
+  // 5. Gaussian noise scaled by the signed maximum of x
+  if (rec.gauss > 0.f) {
+    float m[3];
+    x_max(true, m);
+    const double f = (double)rec.gauss * (double)fmaxf(fmaxf(m[0], m[1]), m[2]);
+    const uint64_t key = rec.noise_key;
+    const int tid = opaque(tid0);
+#pragma unroll 1
+    for (int c = 0; c < 3; ++c)
+#pragma unroll 1
+      for (int t = tid; t < T; t += GEN_NTH) xs[c][t] = (float)((double)xs[c][t] + f * gauss_noise(key, c, t));
+  }
+
+  // 6. the gap in x, 7. the second normalisation
+  const int g0 = rec.gap_lo, g1 = rec.gap_hi;
+  int tid = opaque(tid0);
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int k = 0; k < E; ++k) {
+      const int t = tid + k * GEN_NTH;
+      v[c][k] = t < T && !(t >= g0 && t < g1) ? xs[c][t] : 0.f;
+    }
+  double mean[3], den[3];
+  window_stats(v, T, a.norm == VP_NORM_PEAK, tid, sh, mean, den);
+  float* xw = a.x + (long long)w * 3 * T;
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int k = 0; k < E; ++k) {
+      const int t = tid + k * GEN_NTH;
+      if (t < T) xw[(long long)c * T + t] = (float)(((double)v[c][k] - mean[c]) / den[c]);
+    }
+
+  // the labels of steps 1, 3 and 6: an event's detection box is merged only when the event was shifted
+  float P[E], S[E], D[E];
+#pragma unroll
+  for (int k = 0; k < E; ++k) P[k] = S[k] = D[k] = 0.f;
+  tid = opaque(tid0);
+  merge_labels<E>(a, pr, 0, true, dt.fixed_window, tid, P, S, D);
+#pragma unroll 1
+  for (int i = 0; i < 2; ++i) {
+    const vp_aug_event& ev = rec.event[i];
+    if (ev.kind == VP_AUG_NONE) continue;
+    merge_labels<E>(a, ev.kind == VP_AUG_BANK ? ev.row : pr, ev.shift, ev.shift != 0, dt.fixed_window, opaque(tid0), P, S, D);
+  }
+  float* yw = a.y + (long long)w * 3 * T;
+#pragma unroll
+  for (int k = 0; k < E; ++k) {
+    const int t = tid + k * GEN_NTH;
+    if (t >= T) continue;
+    const bool gap = t >= g0 && t < g1;
+    yw[(long long)a.row_p * T + t] = gap ? 0.f : P[k];
+    yw[(long long)a.row_s * T + t] = gap ? 0.f : S[k];
+    yw[(long long)dt.row_det * T + t] = gap ? 0.f : D[k];
+  }
+}
+
 }  // namespace
 
 int RowRing::reserve(size_t bytes) {
@@ -556,6 +751,12 @@ int row_check(const Bank& bk, const vp_plan_row& r, int b, const char* what) {
 
 bool row_is_zero(const vp_plan_row& r) { return !r.trace && !r.reserved && !r.start && !r.lo && !r.hi; }
 
+int fixed_window_check(float det_fixed_window) {
+  VP_REQUIRE(det_fixed_window < 0.f || std::isfinite(det_fixed_window), "bank batch: det_fixed_window = %g is neither negative nor a finite length",
+             (double)det_fixed_window);  // (a NaN fails both)
+  return VP_OK;
+}
+
 }  // namespace
 
 int bank_check(const Bank& bk, const vp_plan_row* rows, int B, int T, float sigma, int norm, const int* label_rows) {
@@ -620,19 +821,22 @@ int bank_check_eqt(const Bank& bk, const vp_plan_row* rows, int B, int T, float 
                    float det_fixed_window) {
   const int rc = bank_check(bk, rows, B, T, sigma, norm, label_rows);
   if (rc != VP_OK) return rc;
-  VP_REQUIRE(det_fixed_window < 0.f || std::isfinite(det_fixed_window), "bank batch: det_fixed_window = %g is neither negative nor a finite length",
-             (double)det_fixed_window);  // (a NaN fails both)
-  return VP_OK;
+  return fixed_window_check(det_fixed_window);
 }
 
-int bank_launch_eqt(const Bank& bk, const vp_plan_row* rows_dev, int B, int T, float sigma, int norm, const int* label_rows,
-                    float det_fixed_window, float* x, float* y, hipStream_t s) {
+namespace {
+
+// bank_batch_eqt_kernel or bank_aug_eqt_kernel on their rows: label_rows = the rows of detection, P and S.
+int launch_eqt(void (*kernel)(GenArgs, DetArgs), const char* name, const Bank& bk, const vp_plan_row* rows_dev,
+               const vp_aug_row* aug_dev, int B, int T, float sigma, int norm, const int* label_rows, float det_fixed_window,
+               float* x, float* y, hipStream_t s) {
   GenArgs a{};
   a.data = bk.data;
   a.off = bk.off_dev;
   a.len = bk.len_dev;
   a.onset = bk.onset_dev;
   a.rows = rows_dev;
+  a.aug = aug_dev;
   a.x = x;
   a.y = y;
   a.T = T;
@@ -644,13 +848,21 @@ int bank_launch_eqt(const Bank& bk, const vp_plan_row* rows_dev, int B, int T, f
   DetArgs d{};
   d.row_det = label_rows[0];
   d.fixed_window = det_fixed_window < 0.f ? -1.0 : (double)det_fixed_window;
-  hipLaunchKernelGGL(bank_batch_eqt_kernel, dim3(B), dim3(GEN_NTH), 0, s, a, d);
+  hipLaunchKernelGGL(kernel, dim3(B), dim3(GEN_NTH), 0, s, a, d);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
-    set_error("bank_batch_eqt_kernel launch failed: %s", hipGetErrorString(e));
+    set_error("%s launch failed: %s", name, hipGetErrorString(e));
     return VP_ERR_HIP;
   }
   return VP_OK;
+}
+
+}  // namespace
+
+int bank_launch_eqt(const Bank& bk, const vp_plan_row* rows_dev, int B, int T, float sigma, int norm, const int* label_rows,
+                    float det_fixed_window, float* x, float* y, hipStream_t s) {
+  return launch_eqt(bank_batch_eqt_kernel, "bank_batch_eqt_kernel", bk, rows_dev, nullptr, B, T, sigma, norm, label_rows,
+                    det_fixed_window, x, y, s);
 }
 
 int bank_launch_windows(const Bank& bk, const vp_plan_row* rows_dev, int B, int T, int norm, float* x, hipStream_t s) {
@@ -658,11 +870,14 @@ int bank_launch_windows(const Bank& bk, const vp_plan_row* rows_dev, int B, int 
   return launch(bank_window_kernel, "bank_window_kernel", bk, rows_dev, nullptr, B, T, 1.f, norm, unused_label_rows, x, nullptr, s);
 }
 
-int bank_check(const Bank& bk, const vp_aug_row* rows, int B, int T, float sigma, int norm, const int* label_rows) {
+namespace {
+
+// Every field of every augmented row; max_T is what the executing kernel holds in registers.
+int aug_check(const Bank& bk, const vp_aug_row* rows, int B, int T, float sigma, int norm, const int* label_rows, int max_T) {
   VP_REQUIRE(rows, "bank batch: null rows");
   int rc = args_check(B, T, sigma, norm, label_rows);
   if (rc != VP_OK) return rc;
-  VP_REQUIRE(T <= AUG_MAX_T, "bank batch: augmented rows: T = %d outside [1, %d]", T, AUG_MAX_T);
+  VP_REQUIRE(T <= max_T, "bank batch: augmented rows: T = %d outside [1, %d]", T, max_T);
   for (int b = 0; b < B; ++b) {
     const vp_aug_row& r = rows[b];
     if ((rc = row_check(bk, r.primary, b, "row")) != VP_OK) return rc;
@@ -704,9 +919,28 @@ int bank_check(const Bank& bk, const vp_aug_row* rows, int B, int T, float sigma
   return VP_OK;
 }
 
+}  // namespace
+
+int bank_check(const Bank& bk, const vp_aug_row* rows, int B, int T, float sigma, int norm, const int* label_rows) {
+  return aug_check(bk, rows, B, T, sigma, norm, label_rows, AUG_MAX_T);
+}
+
 int bank_launch(const Bank& bk, const vp_aug_row* rows_dev, int B, int T, float sigma, int norm, const int* label_rows,
                     float* x, float* y, hipStream_t s) {
   return launch(bank_aug_kernel, "bank_aug_kernel", bk, nullptr, rows_dev, B, T, sigma, norm, label_rows, x, y, s);
+}
+
+int bank_check_eqt(const Bank& bk, const vp_aug_row* rows, int B, int T, float sigma, int norm, const int* label_rows,
+                   float det_fixed_window) {
+  const int rc = aug_check(bk, rows, B, T, sigma, norm, label_rows, GEN_MAX_T);
+  if (rc != VP_OK) return rc;
+  return fixed_window_check(det_fixed_window);
+}
+
+int bank_launch_eqt(const Bank& bk, const vp_aug_row* rows_dev, int B, int T, float sigma, int norm, const int* label_rows,
+                    float det_fixed_window, float* x, float* y, hipStream_t s) {
+  return launch_eqt(bank_aug_eqt_kernel, "bank_aug_eqt_kernel", bk, nullptr, rows_dev, B, T, sigma, norm, label_rows,
+                    det_fixed_window, x, y, s);
 }
 
 }  // namespace vp
@@ -729,6 +963,22 @@ int make_batch(Bank& bk, const Row* rows, int B, int T, float sigma, int norm, c
   const Row* rd = static_cast<const Row*>(bk.ring.stage({{rows, bytes}}, s));
   if (!rd) return VP_ERR_HIP;
   if ((r = bank_launch(bk, rd, B, T, sigma, norm, label_rows, x, y, s)) != VP_OK) return r;
+  return bk.ring.retire(s);
+}
+
+// vp_bank_make_batch_eqt(_aug): the same with the detection arguments.
+template <class Row>
+int make_batch_eqt(Bank& bk, const Row* rows, int B, int T, float sigma, int norm, const int* label_rows, float det_fixed_window,
+                   float* x, float* y, void* stream) {
+  int rc = bank_check_eqt(bk, rows, B, T, sigma, norm, label_rows, det_fixed_window);
+  if (rc != VP_OK) return rc;
+  VP_HIP(hipSetDevice(bk.device));
+  const size_t bytes = (size_t)B * sizeof(Row);
+  if ((rc = bk.ring.acquire(bytes)) != VP_OK) return rc;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const Row* rd = static_cast<const Row*>(bk.ring.stage({{rows, bytes}}, s));
+  if (!rd) return VP_ERR_HIP;
+  if ((rc = bank_launch_eqt(bk, rd, B, T, sigma, norm, label_rows, det_fixed_window, x, y, s)) != VP_OK) return rc;
   return bk.ring.retire(s);
 }
 
@@ -818,23 +1068,19 @@ int vp_bank_make_batch(vp_bank* h, const vp_plan_row* rows, int B, int T, float 
 int vp_bank_make_batch_eqt(vp_bank* h, const vp_plan_row* rows, int B, int T, float sigma, int norm, const int* label_rows,
                            float det_fixed_window, float* x, float* y, void* stream) {
   VP_REQUIRE(h && x && y, "vp_bank_make_batch_eqt: null argument");
-  Bank& bk = *reinterpret_cast<Bank*>(h);
-  int rc = bank_check_eqt(bk, rows, B, T, sigma, norm, label_rows, det_fixed_window);
-  if (rc != VP_OK) return rc;
-  VP_HIP(hipSetDevice(bk.device));
-  const size_t bytes = (size_t)B * sizeof(vp_plan_row);
-  if ((rc = bk.ring.acquire(bytes)) != VP_OK) return rc;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const vp_plan_row* rd = static_cast<const vp_plan_row*>(bk.ring.stage({{rows, bytes}}, s));
-  if (!rd) return VP_ERR_HIP;
-  if ((rc = bank_launch_eqt(bk, rd, B, T, sigma, norm, label_rows, det_fixed_window, x, y, s)) != VP_OK) return rc;
-  return bk.ring.retire(s);
+  return make_batch_eqt(*reinterpret_cast<Bank*>(h), rows, B, T, sigma, norm, label_rows, det_fixed_window, x, y, stream);
 }
 
 int vp_bank_make_batch_aug(vp_bank* h, const vp_aug_row* rows, int B, int T, float sigma, int norm, const int* label_rows,
                            float* x, float* y, void* stream) {
   VP_REQUIRE(h && x && y, "vp_bank_make_batch_aug: null argument");
   return make_batch(*reinterpret_cast<Bank*>(h), rows, B, T, sigma, norm, label_rows, x, y, stream);
+}
+
+int vp_bank_make_batch_eqt_aug(vp_bank* h, const vp_aug_row* rows, int B, int T, float sigma, int norm, const int* label_rows,
+                               float det_fixed_window, float* x, float* y, void* stream) {
+  VP_REQUIRE(h && x && y, "vp_bank_make_batch_eqt_aug: null argument");
+  return make_batch_eqt(*reinterpret_cast<Bank*>(h), rows, B, T, sigma, norm, label_rows, det_fixed_window, x, y, stream);
 }
 
 }  // extern "C"

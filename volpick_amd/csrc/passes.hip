@@ -163,6 +163,51 @@ int validate_batch(vp_handle* h, vp_bank* bank, const Row* rows, int B, float si
   return VP_OK;
 }
 
+// vp_validate_eqt_bank(_aug): generate -> forward -> the weighted BCE of all B windows, appended.
+template <class Row>
+int validate_eqt_batch(vp_handle* h, vp_bank* bank, const Row* rows, int B, float sigma, int norm, const int* label_rows,
+                       float det_fixed_window, const double* weights, float* pred_out_dev, const char* who) {
+  VP_REQUIRE(h && bank && weights, "%s: null argument", who);
+  if (h->net.model_kind != VP_MODEL_EQTRANSFORMER) {
+    vp::set_error("%s: only an EQTransformer handle has this loss (vp_validate_bank is PhaseNet's)", who);
+    return VP_ERR_UNSUPPORTED;
+  }
+  auto& v = passes_of(h).veq;
+  VP_REQUIRE(v.open, "%s: no pass is open (vp_validate_eqt_begin)", who);
+  const vp::Bank& bk = *reinterpret_cast<const vp::Bank*>(bank);
+  VP_REQUIRE(bk.device == h->device, "%s: bank on device %d, handle on device %d", who, bk.device, h->device);
+  const int T = h->net.in_samples;
+  int rc = vp::bank_check_eqt(bk, rows, B, T, sigma, norm, label_rows, det_fixed_window);
+  if (rc != VP_OK) return rc;
+  double row_weights[3];  // weights are (detection, P, S); the kernel takes them by row of y
+  for (int i = 0; i < 3; ++i) {
+    VP_REQUIRE(std::isfinite(weights[i]), "%s: weights[%d] = %g is not finite", who, i, weights[i]);
+    row_weights[label_rows[i]] = weights[i];
+  }
+  VP_REQUIRE(h->net.n_out == 3, "%s: the model has %d outputs, the labels 3", who, h->net.n_out);
+  VP_HIP(hipSetDevice(h->device));
+  rc = pass_batch(
+      h, B, true, {{rows, (size_t)B * sizeof(Row)}}, pred_out_dev,
+      [&] {
+        int r = grow_results(v.batch, (size_t)v.n_batches, (size_t)v.n_batches + 1, h->stream);
+        if (r == VP_OK) r = grow_results(v.window, (size_t)v.n_windows, (size_t)v.n_windows + B, h->stream);
+        if (r == VP_OK) r = grow_results(v.head, (size_t)v.n_windows * 3, ((size_t)v.n_windows + B) * 3, h->stream);
+        return r;
+      },
+      [&](const char* rows_dev, float* x, float* y) {
+        return vp::bank_launch_eqt(bk, reinterpret_cast<const Row*>(rows_dev), B, T, sigma, norm, label_rows, det_fixed_window,
+                                   x, y, h->stream);
+      },
+      [&](const char*, const float* pred, const float* y) {
+        return vp::bce_launch(pred, y, B, 3, T, row_weights, v.head.p + v.n_windows * 3, v.window.p + v.n_windows,
+                              v.batch.p + v.n_batches, h->stream);
+      });
+  if (rc != VP_OK) return rc;
+  ++v.n_batches;
+  v.n_windows += B;
+  return VP_OK;
+}
+
 // What vp_predict_bank and vp_sweep_bank stage and generate alike: the plan rows, then the B lower and the B upper borders
 // when there are any; the windows alone, no labels; and reduce(pred, lo_dev, hi_dev), the borders null when there are none.
 template <class Room, class Reduce>
@@ -290,48 +335,16 @@ int vp_validate_eqt_begin(vp_handle* h) {
   return VP_OK;
 }
 
-// generate -> forward -> the weighted BCE of all B windows, appended.
 int vp_validate_eqt_bank(vp_handle* h, vp_bank* bank, const vp_plan_row* rows, int B, float sigma, int norm, const int* label_rows,
                          float det_fixed_window, const double* weights, float* pred_out_dev) {
-  VP_REQUIRE(h && bank && weights, "vp_validate_eqt_bank: null argument");
-  if (h->net.model_kind != VP_MODEL_EQTRANSFORMER) {
-    vp::set_error("vp_validate_eqt_bank: only an EQTransformer handle has this loss (vp_validate_bank is PhaseNet's)");
-    return VP_ERR_UNSUPPORTED;
-  }
-  auto& v = passes_of(h).veq;
-  VP_REQUIRE(v.open, "vp_validate_eqt_bank: no pass is open (vp_validate_eqt_begin)");
-  const vp::Bank& bk = *reinterpret_cast<const vp::Bank*>(bank);
-  VP_REQUIRE(bk.device == h->device, "vp_validate_eqt_bank: bank on device %d, handle on device %d", bk.device, h->device);
-  const int T = h->net.in_samples;
-  int rc = vp::bank_check_eqt(bk, rows, B, T, sigma, norm, label_rows, det_fixed_window);
-  if (rc != VP_OK) return rc;
-  double row_weights[3];  // weights are (detection, P, S); the kernel takes them by row of y
-  for (int i = 0; i < 3; ++i) {
-    VP_REQUIRE(std::isfinite(weights[i]), "vp_validate_eqt_bank: weights[%d] = %g is not finite", i, weights[i]);
-    row_weights[label_rows[i]] = weights[i];
-  }
-  VP_REQUIRE(h->net.n_out == 3, "vp_validate_eqt_bank: the model has %d outputs, the labels 3", h->net.n_out);
-  VP_HIP(hipSetDevice(h->device));
-  rc = pass_batch(
-      h, B, true, {{rows, (size_t)B * sizeof(vp_plan_row)}}, pred_out_dev,
-      [&] {
-        int r = grow_results(v.batch, (size_t)v.n_batches, (size_t)v.n_batches + 1, h->stream);
-        if (r == VP_OK) r = grow_results(v.window, (size_t)v.n_windows, (size_t)v.n_windows + B, h->stream);
-        if (r == VP_OK) r = grow_results(v.head, (size_t)v.n_windows * 3, ((size_t)v.n_windows + B) * 3, h->stream);
-        return r;
-      },
-      [&](const char* rows_dev, float* x, float* y) {
-        return vp::bank_launch_eqt(bk, reinterpret_cast<const vp_plan_row*>(rows_dev), B, T, sigma, norm, label_rows,
-                                   det_fixed_window, x, y, h->stream);
-      },
-      [&](const char*, const float* pred, const float* y) {
-        return vp::bce_launch(pred, y, B, 3, T, row_weights, v.head.p + v.n_windows * 3, v.window.p + v.n_windows,
-                              v.batch.p + v.n_batches, h->stream);
-      });
-  if (rc != VP_OK) return rc;
-  ++v.n_batches;
-  v.n_windows += B;
-  return VP_OK;
+  return validate_eqt_batch(h, bank, rows, B, sigma, norm, label_rows, det_fixed_window, weights, pred_out_dev,
+                            "vp_validate_eqt_bank");
+}
+
+int vp_validate_eqt_bank_aug(vp_handle* h, vp_bank* bank, const vp_aug_row* rows, int B, float sigma, int norm,
+                             const int* label_rows, float det_fixed_window, const double* weights, float* pred_out_dev) {
+  return validate_eqt_batch(h, bank, rows, B, sigma, norm, label_rows, det_fixed_window, weights, pred_out_dev,
+                            "vp_validate_eqt_bank_aug");
 }
 
 int vp_validate_eqt_end(vp_handle* h, double* batch_losses, long long cap, long long* n_batches, double* per_window, double* heads,

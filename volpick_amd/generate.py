@@ -38,7 +38,8 @@ constant here:
 * ``STEERED_CENTRE``, ``STEERED_CLAMP`` and ``STEERED_SHORT_TRACE`` -- where ``SteeredWindow(strategy="pad")`` puts the
   window around its target (:class:`SteeredPlanner`, the evaluation windows of the pick-benchmark tasks 1-3);
 * ``DETECTION_FACTOR``, ``DETECTION_ONSET``, ``DETECTION_INDEX``, ``DETECTION_NEEDS`` and ``DETECTION_ORDER`` -- the
-  box ``DetectionLabeller`` draws from P to behind S (EQTransformer's ``detections`` row).
+  box ``DetectionLabeller`` draws from P to behind S (EQTransformer's ``detections`` row);
+* ``DETECTION_UNSHIFTED`` -- what the stacked events do with the detection box of a source whose shift is 0.
 
 EQTransformer's block 1 (``EQTransformerLit.get_joint_augmentation_block1``, models.py:606-666) differs in three things:
 the windows (``samples_before=6000``, ``windowlen=12000``, ``RandomWindow(windowlen=6000)``), the labeller's
@@ -46,8 +47,25 @@ the windows (``samples_before=6000``, ``windowlen=12000``, ``RandomWindow(window
 ``detections``.  ``vp_bank_make_batch_eqt`` executes it on the same plan rows; :meth:`WaveformBank.make_batch` chooses it
 for a model whose labels start with ``"Detection"``.
 
-Out of scope: array rotation (``rotate_array`` defaults to False and no config sets it); EQTransformer's stacked recipe
-(``SuperimposeEvent`` / ``MyDuplicateEvent`` with ``detection_keys``, ``AddGap`` on ``detections``).
+EQTransformer's stacked recipe (``EQTransformerLit.get_train_augmentations`` / ``get_val_augmentations``, models.py:668-844)
+is block 1, the stacking block, ``AddGap`` and a second ``Normalize`` as well.  :class:`AugmentedPlanner` plans it with
+the model's windows -- the primary and the noise sources with the block 1 above, the event sources with
+``samples_before=3000``, ``windowlen=8000`` (``event_samples_before`` / ``event_windowlen``;
+``EQTransformerLit.augmented_planner`` sets them) -- and ``vp_bank_make_batch_eqt_aug``
+(:meth:`WaveformBank.make_batch_eqt_aug`) executes the same :data:`AUG_ROW` records with three differences:
+
+* ``noise_label=False``: behind an event ``y = max(y, y')`` and nothing else -- no division by ``max(1, P + S)``, no noise
+  row;
+* ``detection_keys=["detections"]``: a source carries its own detection box (``DetectionLabeller`` on the source window's
+  onsets; for a duplicate the window's own box), shifted with zero fill and merged by maximum -- but the reference's shift
+  has no branch for a shift of 0, so an unshifted source's box is dropped while its waveform and its P and S are merged
+  (``DETECTION_UNSHIFTED``);
+* ``AddGap(label_keys=["y", "detections"], noise_id={})``: in the gap x, P, S and the detection row are all 0, no row is 1.
+
+Stacked noise leaves the labels alone and the second ``Normalize`` is PhaseNet's.  Everything the planner decides from
+onsets alone carries over unchanged.
+
+Out of scope: array rotation (``rotate_array`` defaults to False and no config sets it); EQTransformer training.
 """
 from __future__ import annotations
 
@@ -80,6 +98,9 @@ DETECTION_ONSET = "earliest"  # p and s: the minimum of the phase's finite onset
 DETECTION_INDEX = np.trunc  # int(.): truncation toward zero, of p and of the end; the end rounds its product before its sum
 DETECTION_NEEDS = "P and S"  # no finite P onset or no finite S onset: the row is 0
 DETECTION_ORDER = "s >= p"  # an S before the P: the row is 0 (s == p with no tail: an empty slice)
+# SuperimposeEvent / MyDuplicateEvent with detection_keys (EQTransformer's stacked recipe; fixed in the kernel): the shift of
+# the source's detection row has a branch for a shift to the right and one for a shift to the left, none for a shift of 0
+DETECTION_UNSHIFTED = "dropped"  # shifted_first_pick == original_first_pick: the source's detection row is not merged
 
 # the reference's phase_dict (volpick/model/models.py:26-31): metadata column -> phase, two columns per phase
 PHASE_DICT = {
@@ -287,7 +308,8 @@ class WaveformBank:
 
         A model with a detection row (an EQTransformer) gets ``{"X": (B, 3, T), "y": (B, 2, T), "detections": (B, 1, T)}``,
         what ``EQTransformerLit.shared_step`` reads: ``y`` holds P and S, and both are views of one (B, 3, T) tensor in the
-        order detection, P, S (``vp_bank_make_batch_eqt``; plan rows only).  ``detection_fixed_window``: the detection's
+        order detection, P, S (``vp_bank_make_batch_eqt``; plan rows only -- augmented rows go to
+        :meth:`make_batch_eqt_aug`).  ``detection_fixed_window``: the detection's
         length in samples from P, ``None`` = to behind S (the module's ``DETECTION_*`` constants)."""
         import torch
 
@@ -297,8 +319,8 @@ class WaveformBank:
         stream = torch.cuda.current_stream(dev).cuda_stream
         if has_detection_row(model.labels):
             if aug:
-                raise ValueError("augmented rows with an EQTransformer model: its stacked recipe (detections through "
-                                 "SuperimposeEvent, MyDuplicateEvent and AddGap) is not implemented; plan block 1 alone")
+                raise ValueError("augmented rows with an EQTransformer model: make_batch executes block 1 alone for it; "
+                                 "its stacked recipe is WaveformBank.make_batch_eqt_aug (EQTransformerLit.make_batch)")
             detection_label_rows(model.labels)  # (the model's labels are what the batch is laid out for)
             rows = as_rows(rows)
             x = torch.empty((len(rows), 3, T), dtype=torch.float32, device=dev)
@@ -320,6 +342,29 @@ class WaveformBank:
                                             _norm(model.norm), lr_.ctypes.data_as(C.POINTER(C.c_int)),
                                             C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(stream)), name)
         return {"X": x, "y": y}
+
+    def make_batch_eqt_aug(self, rows, model, sigma, detection_fixed_window=None):
+        """EQTransformer's stacked recipe (``vp_bank_make_batch_eqt_aug``) on augmented rows (``AUG_ROW``, from
+        ``EQTransformerLit.augmented_planner``): ``{"X": (B, 3, T), "y": (B, 2, T), "detections": (B, 1, T)}`` on torch's
+        current stream, ``y`` and ``detections`` views of one (B, 3, T) tensor in the order detection, P, S, as
+        :meth:`make_batch` returns them for plan rows.  ``model`` must have a detection row."""
+        import torch
+
+        if not has_detection_row(model.labels):
+            raise ValueError("make_batch_eqt_aug: the model has no detection row (make_batch takes its augmented rows)")
+        detection_label_rows(model.labels)
+        rows = as_aug_rows(rows)
+        T = int(model.in_samples)
+        dev = torch.device("cuda", self.device)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        x = torch.empty((len(rows), 3, T), dtype=torch.float32, device=dev)
+        y = torch.empty_like(x)
+        lr_ = np.array([0, 1, 2], np.int32)
+        _lib.check(self._lib.vp_bank_make_batch_eqt_aug(
+            self._h, rows.ctypes.data_as(C.c_void_p), len(rows), T, float(sigma), _norm(model.norm),
+            lr_.ctypes.data_as(C.POINTER(C.c_int)), _fixed_window(detection_fixed_window), C.c_void_p(x.data_ptr()),
+            C.c_void_p(y.data_ptr()), C.c_void_p(stream)), "vp_bank_make_batch_eqt_aug")
+        return {"X": x, "y": y[:, 1:3], "detections": y[:, 0:1]}
 
     @property
     def handle(self):
@@ -507,9 +552,12 @@ class Augmentation:
                            noise_inv_scale=noise_inv_scale, gauss_scale=gauss_scale, sep=sep,
                            tail_length_factor=tail_length_factor, prob_num_events=prob_num_events)
 
-    def planner(self, bank, batch_size, seed, in_samples=3001, sigma=20, validation=False):
+    def planner(self, bank, batch_size, seed, in_samples=3001, sigma=20, validation=False, event_samples_before=1500,
+                event_windowlen=4000, **block1):
         ev, nz = (self.val_event_traces, self.val_noise_traces) if validation else (self.event_traces, self.noise_traces)
-        return AugmentedPlanner(bank, batch_size, ev, nz, seed=seed, in_samples=in_samples, sigma=sigma, **self.params)
+        return AugmentedPlanner(bank, batch_size, ev, nz, seed=seed, in_samples=in_samples, sigma=sigma,
+                                event_samples_before=event_samples_before, event_windowlen=event_windowlen, **self.params,
+                                **block1)
 
 
 # columns of AugmentedPlanner's uniform draws, one row per window (AugmentedPlanner.last_draws["u"])
@@ -563,9 +611,11 @@ class AugmentedPlanner:
     The primary rows come from ``WindowPlanner(bank, batch_size, seed=seed, ...)`` itself, so they equal its rows batch
     for batch; everything else is drawn from a second generator seeded from ``seed``.  ``event_traces`` /
     ``noise_traces`` are index subsets of ``bank``; an empty or ``None`` subset switches its slot off.  Event sources are
-    planned as the reference's stacked-event generator does (block 1 with ``samples_before=1500``, ``windowlen=4000``,
-    ``selection="first"``, probabilities ``[1, 0]``), noise sources with the default block 1.  ``sigma`` must be the
-    label width the batches are made with: the sources' P-label check and label argmax depend on it.
+    planned as the reference's stacked-event generator does (block 1 with ``samples_before=event_samples_before``,
+    ``windowlen=event_windowlen``, ``selection="first"``, probabilities ``[1, 0]``: 1500 / 4000 for PhaseNet, 3000 / 8000
+    for EQTransformer), noise sources with the primary's block 1 (``**block1``: ``samples_before``, ``first_windowlen``,
+    ...; PhaseNet's defaults when empty).  ``sigma`` must be the label width the batches are made with: the sources'
+    P-label check and label argmax depend on it.
 
     Per window, in order (``u`` = the window's uniforms, columns :data:`U_COLS`): the event slot ``OneOf([superimpose,
     duplicate, null], event_prob)``, the noise slot ``OneOf([superimpose noise, Gaussian noise, null], noise_prob)``, the
@@ -576,7 +626,7 @@ class AugmentedPlanner:
     def __init__(self, bank, batch_size, event_traces=None, noise_traces=None, seed=0, in_samples=3001, sigma=20,
                  event_prob=(0.2, 0.2, 0.6), noise_prob=(0.25, 0.25, 0.5), gap_prob=(0.2, 0.8), event_inv_scale=(0.25, 4),
                  noise_inv_scale=(2, 50), gauss_scale=(0, 0.15), sep=200, tail_length_factor=1.4, prob_num_events=None,
-                 **block1):
+                 event_samples_before=1500, event_windowlen=4000, **block1):
         self.primary = WindowPlanner(bank, batch_size, in_samples=in_samples, seed=seed, **block1)
         self.lengths, self.onsets = self.primary.lengths, self.primary.onsets
         self.batch_size, self.T = self.primary.batch_size, int(in_samples)
@@ -607,10 +657,11 @@ class AugmentedPlanner:
         self.gauss_scale = gauss_scale
         self.sep, self.tail = int(sep), float(tail_length_factor)
         self.two_s2 = 2.0 * float(sigma) ** 2
-        # the sources' block 1 (models.py:274-280), drawing from the augmentation stream
-        self.event_planner = WindowPlanner(bank, batch_size, samples_before=1500, first_windowlen=4000,
-                                           first_window_prob=(1, 0), in_samples=in_samples, selection="first")
-        self.noise_planner = WindowPlanner(bank, batch_size, in_samples=in_samples)
+        # the sources' block 1 (models.py:274-280; EQTransformer's :679-682), drawing from the augmentation stream
+        self.event_planner = WindowPlanner(bank, batch_size, samples_before=event_samples_before,
+                                           first_windowlen=event_windowlen, first_window_prob=(1, 0), in_samples=in_samples,
+                                           selection="first")
+        self.noise_planner = WindowPlanner(bank, batch_size, in_samples=in_samples, **block1)
         self.event_planner.rng = self.noise_planner.rng = self.rng
         self.last_draws = None
 

@@ -22,9 +22,9 @@ batch from a bank, run the inference forward and reduce ``vector_cross_entropy``
 arithmetic, restated here without torch), the weights of the lowest validation loss, and the early stop.
 
 EQTransformer has the validation half alone (``EQTransformerLit``, models.py:483-879): block 1's batch with its detection
-row from a bank, and ``shared_step``'s weighted binary cross entropy (``bce_loss`` on the host, ``validate_batches_eqt`` /
-``EQTransformerLit.validate_bank`` on the GPU: ``vp_validate_eqt_begin`` / ``_bank`` / ``_end``).  Its training step and its
-stacked recipe are not implemented.
+row from a bank, or the stacked recipe's (``augmented_planner``, ``vp_bank_make_batch_eqt_aug``), and ``shared_step``'s
+weighted binary cross entropy (``bce_loss`` on the host, ``validate_batches_eqt`` / ``EQTransformerLit.validate_bank`` on the
+GPU: ``vp_validate_eqt_begin`` / ``_bank`` / ``_bank_aug`` / ``_end``).  Its training step is not implemented.
 """
 from __future__ import annotations
 
@@ -574,14 +574,15 @@ class PhaseNetLit:
 def validate_batches_eqt(model, bank, batches, sigma, loss_weights=EQT_LOSS_WEIGHTS, detection_fixed_window=None,
                          predictions=False):
     """One validation pass of an EQTransformer on the GPU (``vp_validate_eqt_begin`` ... ``vp_validate_eqt_end``): every
-    element of ``batches`` (plan rows, any number per batch) is cut from ``bank`` and labelled as ``make_batch`` does for the
+    element of ``batches`` (plan rows, or augmented rows of the stacked recipe -- ``vp_validate_eqt_bank_aug``; any number per
+    batch, both kinds in one pass) is cut from ``bank`` and labelled as ``make_batch`` / ``make_batch_eqt_aug`` does for the
     model (P, S and the detection box), run through the model's inference path and scored with
     ``loss_weights[0] BCE(detection) + loss_weights[1] BCE(P) + loss_weights[2] BCE(S)`` in float64 on the device; the host
     waits once, at the end.  Returns ``(batch_losses, window_losses, head_losses)``: float64 arrays with one loss per batch,
     one per window and the unweighted (detection, P, S) values per window, (n_windows, 3); with ``predictions=True`` also the
     list of the batches' (B, 3, T) predictions (CUDA tensors)."""
     from .evaluate import prediction_tensor
-    from .generate import as_rows, detection_label_rows, _fixed_window, _norm
+    from .generate import AUG_ROW, as_aug_rows, as_rows, detection_label_rows, _fixed_window, _norm
 
     lib = _lib.load()
     if model._device_index is None:
@@ -596,13 +597,15 @@ def validate_batches_eqt(model, bank, batches, sigma, loss_weights=EQT_LOSS_WEIG
     _lib.check(lib.vp_validate_eqt_begin(h), "vp_validate_eqt_begin")
     try:
         for rows in batches:
-            rows = as_rows(rows)
+            aug = getattr(rows, "dtype", None) == AUG_ROW
+            rows = as_aug_rows(rows) if aug else as_rows(rows)
+            name = "vp_validate_eqt_bank_aug" if aug else "vp_validate_eqt_bank"
             if predictions:
                 preds.append(prediction_tensor(model, len(rows)))
-            _lib.check(lib.vp_validate_eqt_bank(h, bank.handle, _lib.ptr(rows), len(rows), float(sigma), _norm(model.norm),
-                                                lrows.ctypes.data_as(C.POINTER(C.c_int)), fixed,
-                                                w.ctypes.data_as(C.POINTER(C.c_double)),
-                                                C.c_void_p(preds[-1].data_ptr()) if predictions else None), "vp_validate_eqt_bank")
+            _lib.check(getattr(lib, name)(h, bank.handle, _lib.ptr(rows), len(rows), float(sigma), _norm(model.norm),
+                                          lrows.ctypes.data_as(C.POINTER(C.c_int)), fixed,
+                                          w.ctypes.data_as(C.POINTER(C.c_double)),
+                                          C.c_void_p(preds[-1].data_ptr()) if predictions else None), name)
             n_batches += 1
             n_windows += len(rows)
     finally:
@@ -620,8 +623,8 @@ def validate_batches_eqt(model, bank, batches, sigma, loss_weights=EQT_LOSS_WEIG
 
 
 class EQTransformerLit:
-    """The validation half of the reference's ``EQTransformerLit`` (models.py:483-879): block 1's batch and
-    ``shared_step``'s loss ``loss_weights[0] BCE(detection) + loss_weights[1] BCE(P) + loss_weights[2] BCE(S)``, by which
+    """The validation half of the reference's ``EQTransformerLit`` (models.py:483-879): block 1's batch or the stacked
+    recipe's (``augmented_planner``; the reference's ``get_val_augmentations`` with ``stack_data``) and ``shared_step``'s loss ``loss_weights[0] BCE(detection) + loss_weights[1] BCE(P) + loss_weights[2] BCE(S)``, by which
     the reference selects its checkpoints.  ``validation_step(batch)`` takes what ``WaveformBank.make_batch`` returns for
     the model: ``{"X": (B, 3, 6000), "y": (B, 2, 6000), "detections": (B, 1, 6000)}``.  Training is not implemented."""
 
@@ -657,8 +660,19 @@ class EQTransformerLit:
         return WindowPlanner(bank, batch_size, samples_before=6000, first_windowlen=12000, in_samples=self.model.in_samples,
                              seed=seed)
 
+    def augmented_planner(self, bank, batch_size, augment, seed=0, validation=False):
+        """The stacked recipe's windows for this model (models.py:668-844): ``augment`` (a ``generate.Augmentation``) planned
+        with block 1's windows above for the primary and the noise sources, ``samples_before=3000`` in an extent of 8000
+        samples for the event sources, and this lit's label width."""
+        return augment.planner(bank, batch_size, seed, in_samples=self.model.in_samples, sigma=self.sigma, validation=validation,
+                               event_samples_before=3000, event_windowlen=8000, samples_before=6000, first_windowlen=12000)
+
     def make_batch(self, bank, rows):
-        return bank.make_batch(rows, self.model, self.sigma, detection_fixed_window=self.detection_fixed_window)
+        """The batch of plan rows (block 1) or of augmented rows (the stacked recipe), by the rows' dtype."""
+        from .generate import AUG_ROW
+
+        make = bank.make_batch_eqt_aug if getattr(rows, "dtype", None) == AUG_ROW else bank.make_batch
+        return make(rows, self.model, self.sigma, detection_fixed_window=self.detection_fixed_window)
 
     def validation_step(self, batch, batch_idx=None):
         """``shared_step`` on the host: the model's output copied back, ``bce_loss`` in numpy float64."""
@@ -669,9 +683,9 @@ class EQTransformerLit:
         return bce_loss(pred, y, self.loss_weights)
 
     def validate_bank(self, val_bank, planner_or_rows, per_window=False):
-        """The validation loss of every batch of ``planner_or_rows`` -- a planner (its ``validation()`` batches), one array
-        of rows (one batch) or an iterable of such arrays -- on the GPU from end to end (``validate_batches_eqt``: one host
-        wait).  Returns the list of batch losses; with ``per_window=True`` ``(batch_losses, window_losses)``, the latter one
+        """The validation loss of every batch of ``planner_or_rows`` -- a planner (its ``validation()`` batches; with an
+        ``augmented_planner`` this is the reference's validation pass), one array of rows (one batch) or an iterable of such
+        arrays, plan rows or augmented rows -- on the GPU from end to end (``validate_batches_eqt``: one host wait).  Returns the list of batch losses; with ``per_window=True`` ``(batch_losses, window_losses)``, the latter one
         float64 array over all windows in order."""
         if hasattr(planner_or_rows, "validation"):
             batches = planner_or_rows.validation()
