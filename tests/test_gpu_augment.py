@@ -1,5 +1,5 @@
 """GPU: augmented training windows (stacked events and noise, Gaussian noise, gap, second normalisation) generated from
-a device-resident waveform bank (csrc/batchgen.hip, bank_aug_kernel) against the float64 restatement of their records
+a device-resident waveform bank (csrc/batchgen.hip, bank_aug_kernel<3, LABEL_PSN>) against the float64 restatement of their records
 (tests/augment_restate.py), invalid records, and the fused trainer path (vp_train_step_bank_aug) against ``step``."""
 import ctypes as C
 from types import SimpleNamespace

@@ -1,5 +1,5 @@
 """GPU: EQTransformer's stacked recipe generated from a device-resident waveform bank (csrc/batchgen.hip,
-bank_aug_eqt_kernel; vp_bank_make_batch_eqt_aug) against the float64 restatement of its records
+bank_aug_kernel<6, LABEL_DET>; vp_bank_make_batch_eqt_aug) against the float64 restatement of its records
 (tests/eqt_augment_restate.py): planned batches, hand-made records, the null record against block 1's kernel, the shapes
 at which the register tiling changes, invalid records, stream order; and the validation pass on such batches
 (vp_validate_eqt_bank_aug, EQTransformerLit.validate_bank) against the loss of the same batches computed apart."""

@@ -205,6 +205,17 @@ for B in (512, 64):
         vector_cross_entropy(p_host.astype(np.float64), y_host.astype(np.float64))
     r["host_numpy_loss_ms"] = 1e3 * (time.perf_counter() - t0) / 5
 
+    # the stacked recipe (vp_bank_make_batch_aug, vp_train_step_bank_aug): sources as in the EQTransformer mode
+    n_ev = 3 * args.traces // 4
+    aug = G.Augmentation(val_event_traces=np.arange(n_ev), val_noise_traces=np.arange(n_ev, args.traces))
+    aplanner = aug.planner(bank, B, seed=B, sigma=lit.sigma, validation=True)
+    aplans = [aplanner.plan(rng.integers(0, args.traces, B)) for _ in range(N)]
+    ib = iter(aplans * 40)
+    r["aug_generate_ms"] = event_ms(lambda: bank.make_batch(next(ib), model, lit.sigma), 4 * N, warm=5)
+    r["aug_generate_ms_queued"] = event_ms(lambda: [bank.make_batch(rows, model, lit.sigma) for rows in aplans], 15) / N
+    ib = iter(aplans * 4)
+    r["aug_train_step_ms_fp32"] = wall_ms(lambda: tr.step_bank(bank, next(ib), 1e-3, lit.sigma), N)
+
     for prec in ("32", "bf16-mixed"):
         lt = lit if prec == "32" else PhaseNetLit(lr=1e-3, model=PhaseNet.from_pretrained("volpick"), max_batch=B, precision=prec)
         t = lt._ensure()

@@ -1,5 +1,6 @@
 // Training-batch generation from a device-resident waveform bank (batchgen.hip): the pieces the trainer's
-// vp_train_step_bank (train_phasenet.hip) and the passes over a bank (passes.hip) share with vp_bank_make_batch.
+// vp_train_step_bank (train_phasenet.hip) and the passes over a bank (passes.hip) share with vp_bank_make_batch -- the
+// staging rings, the bank, and one descriptor, one check and one launch for every recipe (BatchSpec, BatchRows).
 #pragma once
 #include <initializer_list>
 
@@ -64,30 +65,40 @@ struct Bank {
   ~Bank();
 };
 
-// Checks every argument of one generation launch on the host; VP_ERR_INVALID (with the message set) on the first bad one.
-int bank_check(const Bank& bk, const vp_plan_row* rows, int B, int T, float sigma, int norm, const int* label_rows);
-// x, y: (B, 3, T) fp32 on the bank's device.  Arguments already checked by bank_check.
-int bank_launch(const Bank& bk, const vp_plan_row* rows_dev, int B, int T, float sigma, int norm, const int* label_rows,
-                float* x, float* y, hipStream_t s);
-// The EQTransformer batch (vp_bank_make_batch_eqt): label_rows = the rows of detection, P and S in y; x and the P / S rows
-// carry bank_launch's bits, the detection row is SeisBench's DetectionLabeller (det_fixed_window < 0: from P to
-// S + 1.4 (S - P); >= 0: that many samples from P).  bank_check's arguments plus det_fixed_window.
-int bank_check_eqt(const Bank& bk, const vp_plan_row* rows, int B, int T, float sigma, int norm, const int* label_rows,
-                   float det_fixed_window);
-int bank_launch_eqt(const Bank& bk, const vp_plan_row* rows_dev, int B, int T, float sigma, int norm, const int* label_rows,
-                    float det_fixed_window, float* x, float* y, hipStream_t s);
-// x alone -- the rows cut, demeaned and normalised exactly as bank_launch does, no labels (vp_predict_bank).
-int bank_check_windows(const Bank& bk, const vp_plan_row* rows, int B, int T, int norm);
-int bank_launch_windows(const Bank& bk, const vp_plan_row* rows_dev, int B, int T, int norm, float* x, hipStream_t s);
-// The same for augmented rows (vp_bank_make_batch_aug): bank_check's arguments plus every field of every vp_aug_row.
-int bank_check(const Bank& bk, const vp_aug_row* rows, int B, int T, float sigma, int norm, const int* label_rows);
-int bank_launch(const Bank& bk, const vp_aug_row* rows_dev, int B, int T, float sigma, int norm, const int* label_rows,
-                float* x, float* y, hipStream_t s);
-// EQTransformer's augmented rows (vp_bank_make_batch_eqt_aug): the checks of the augmented bank_check with T <= 6144, plus
-// det_fixed_window; label_rows = the rows of detection, P and S.
-int bank_check_eqt(const Bank& bk, const vp_aug_row* rows, int B, int T, float sigma, int norm, const int* label_rows,
-                   float det_fixed_window);
-int bank_launch_eqt(const Bank& bk, const vp_aug_row* rows_dev, int B, int T, float sigma, int norm, const int* label_rows,
-                    float det_fixed_window, float* x, float* y, hipStream_t s);
+// What a batch carries beside x: nothing (vp_predict_bank, vp_sweep_bank), PhaseNet's P, S and noise rows, or
+// EQTransformer's detection box (SeisBench's DetectionLabeller), P and S.
+enum LabelKind { LABEL_NONE, LABEL_PSN, LABEL_DET };
+
+// One generation launch, whichever recipe: the window length, the label width, the normalisation and the labels.
+struct BatchSpec {
+  int T = 0;
+  float sigma = 1.f;  // (LABEL_NONE: not read)
+  int norm = 0;       // VP_NORM_PEAK or VP_NORM_STD
+  LabelKind labels = LABEL_NONE;
+  // the caller's three rows of y, unchecked until bank_check: P, S, noise (LABEL_PSN) or detection, P, S (LABEL_DET)
+  const int* label_rows = nullptr;
+  float det_fixed_window = -1.f;  // LABEL_DET; < 0: the detection runs from P to S + 1.4 (S - P); >= 0: that many samples from P
+};
+
+// The B rows of a batch, on the host or on the device: plan rows (block 1) or augmented rows (block 1, stacking, gap and
+// second normalisation; they carry labels, and PhaseNet's hold T <= 3072).
+struct BatchRows {
+  const void* p;
+  bool aug;
+  BatchRows(const vp_plan_row* rows) : p(rows), aug(false) {}
+  BatchRows(const vp_aug_row* rows) : p(rows), aug(true) {}
+  size_t bytes(int B) const { return (size_t)B * (aug ? sizeof(vp_aug_row) : sizeof(vp_plan_row)); }
+  BatchRows at(const void* copy) const {  // the same rows where they were copied to
+    BatchRows r = *this;
+    r.p = copy;
+    return r;
+  }
+};
+
+// Checks every argument of one generation launch on the host -- B, the spec, every field of every row against the bank;
+// VP_ERR_INVALID (with the message set) on the first bad one.
+int bank_check(const Bank& bk, const BatchSpec& spec, BatchRows rows, int B);
+// x, y: (B, 3, T) fp32 on the bank's device (y unused with LABEL_NONE).  Arguments already checked by bank_check.
+int bank_launch(const Bank& bk, const BatchSpec& spec, BatchRows rows_dev, int B, float* x, float* y, hipStream_t s);
 
 }  // namespace vp

@@ -1,7 +1,9 @@
 // Training batches from a device-resident waveform bank (include/volpick_hip.h, vp_bank_*): window cut with zero fill,
 // demean + peak / std normalisation and Gaussian phase labels -- with a noise row for PhaseNet, with SeisBench's detection
 // box for EQTransformer -- one workgroup per window.  The host plans every random choice (volpick_amd/generate.py); this file
-// only executes the plan rows.
+// only executes the plan rows.  One descriptor (BatchSpec, batchgen.h) names a launch, bank_check and bank_launch serve every
+// recipe, and the kernels are bank_block1_kernel<label kind> for plan rows, bank_aug_psn_kernel (x in registers, T <= 3072)
+// and bank_aug_kernel<6, LABEL_DET> (x in LDS, T <= 6144) for augmented rows, the two on the same step helpers.
 #include "batchgen.h"
 
 #include <cmath>
@@ -11,24 +13,27 @@ namespace vp {
 
 namespace {
 
+// What every generation kernel takes.  A kernel reads the fields of its label kind and of its kind of rows alone.
 struct GenArgs {
   const float* data;
   const long long* off;
   const long long* len;
   const double* onset;  // [trace][4]
-  const vp_plan_row* rows;
-  const vp_aug_row* aug;  // bank_aug_kernel's records (rows unused)
+  const vp_plan_row* rows;  // block 1's kernels: one plan row per window ...
+  const vp_aug_row* aug;    // ... the augmented kernels: one record per window
   float* x;
   float* y;
   int T;
   int norm;
   float sigma;
-  int row_p, row_s, row_n;
+  int row_p, row_s, row_n;  // rows of y; row_n: the noise row (LABEL_PSN)
+  int row_det;              // the detection row (LABEL_DET)
+  double fixed_window;      // LABEL_DET; >= 0: the detection ends fixed_window samples behind P; < 0: it follows S
 };
 
 constexpr int GEN_NTH = 1024, GEN_NWV = GEN_NTH / 64, GEN_MAXE = 6;  // T <= 6144: the window lives in registers
 constexpr int GEN_MAX_T = GEN_NTH * GEN_MAXE;
-constexpr int AUG_MAXE = 3, AUG_MAX_T = GEN_NTH * AUG_MAXE;  // bank_aug_kernel holds x, a source and P / S: T <= 3072
+constexpr int AUG_MAXE = 3, AUG_MAX_T = GEN_NTH * AUG_MAXE;  // augmented PhaseNet rows: T <= 3072 (three samples per thread)
 
 __device__ __forceinline__ double wave_sum_d(double v) {
 #pragma unroll
@@ -183,40 +188,6 @@ __device__ __forceinline__ void write_window(const GenArgs& a, const vp_plan_row
   }
 }
 
-// x alone, for callers that need no labels (vp_predict_bank): a.y, a.onset, a.sigma and the label rows are not read.
-__global__ __launch_bounds__(GEN_NTH) void bank_window_kernel(const GenArgs a) {
-  __shared__ GenShared sh;
-  write_window(a, a.rows[blockIdx.x], blockIdx.x, threadIdx.x, sh);
-}
-
-__global__ __launch_bounds__(GEN_NTH) void bank_batch_kernel(const GenArgs a) {
-  __shared__ GenShared sh;
-  const int w = blockIdx.x, tid = threadIdx.x;
-  const int T = a.T;
-  const vp_plan_row r = a.rows[w];
-  write_window(a, r, w, tid, sh);
-
-  double o[4];
-  bool has[4];
-  window_onsets(a, r, o, has);
-  const float two_s2 = 2.f * a.sigma * a.sigma;
-  float* yw = a.y + (long long)w * 3 * T;
-  for (int t = tid; t < T; t += GEN_NTH) {
-    float ph[2];
-    phase_labels(o, has, t, two_s2, ph);
-    yw[(long long)a.row_p * T + t] = ph[0];
-    yw[(long long)a.row_s * T + t] = ph[1];
-    yw[(long long)a.row_n * T + t] = fminf(fmaxf(1.f - ph[0] - ph[1], 0.f), 1.f);
-  }
-}
-
-// What bank_batch_eqt_kernel takes beside GenArgs (whose row_n it does not read): GenArgs keeps its layout, and with it the
-// other kernels their code.
-struct DetArgs {
-  int row_det;
-  double fixed_window;  // >= 0: the detection ends fixed_window samples behind P; < 0: it follows S
-};
-
 // SeisBench's DetectionLabeller (ndim == 2) on a window's onsets o (P, P, S, S; window-relative): the box is 1 on the
 // integer samples t with lo <= t < hi, lo = max(int(p), 0), hi = max(int(s + factor (s - p)), 0), p and s the earliest
 // finite P and S onsets, factor = 1.4; empty (lo = hi = 0) without a P or without an S, and for s < p.  A fixed window w
@@ -246,28 +217,33 @@ __device__ __forceinline__ void detection_span(const double o[4], const bool has
   hi = fmax(trunc(end), 0.0);  // (a NaN end -- 0 * inf of onsets 10^308 apart -- gives 0: an empty box)
 }
 
-// The EQTransformer batch: x as bank_batch_kernel writes it, the P and S rows with its bits, no noise row, and the
-// detection box.
-__global__ __launch_bounds__(GEN_NTH) void bank_batch_eqt_kernel(const GenArgs a, const DetArgs d) {
+// Block 1, one window per workgroup: x for every label kind; LABEL_NONE: nothing else (vp_predict_bank: a.y, a.onset,
+// a.sigma and the label rows are not read); LABEL_PSN: the P and S Gaussians and the noise row clip(1 - P - S, 0, 1);
+// LABEL_DET: the same P and S bits, no noise row, and the detection box.
+template <LabelKind K>
+__global__ __launch_bounds__(GEN_NTH) void bank_block1_kernel(const GenArgs a) {
   __shared__ GenShared sh;
   const int w = blockIdx.x, tid = threadIdx.x;
   const int T = a.T;
   const vp_plan_row r = a.rows[w];
   write_window(a, r, w, tid, sh);
-
-  double o[4];
-  bool has[4];
-  window_onsets(a, r, o, has);
-  double lo, hi;
-  detection_span(o, has, d.fixed_window, lo, hi);
-  const float two_s2 = 2.f * a.sigma * a.sigma;
-  float* yw = a.y + (long long)w * 3 * T;
-  for (int t = tid; t < T; t += GEN_NTH) {
-    float ph[2];
-    phase_labels(o, has, t, two_s2, ph);
-    yw[(long long)a.row_p * T + t] = ph[0];
-    yw[(long long)a.row_s * T + t] = ph[1];
-    yw[(long long)d.row_det * T + t] = (double)t >= lo && (double)t < hi ? 1.f : 0.f;
+  if constexpr (K != LABEL_NONE) {
+    double o[4], lo = 0.0, hi = 0.0;
+    bool has[4];
+    window_onsets(a, r, o, has);
+    if constexpr (K == LABEL_DET) detection_span(o, has, a.fixed_window, lo, hi);
+    const float two_s2 = 2.f * a.sigma * a.sigma;
+    float* yw = a.y + (long long)w * 3 * T;
+    for (int t = tid; t < T; t += GEN_NTH) {
+      float ph[2];
+      phase_labels(o, has, t, two_s2, ph);
+      yw[(long long)a.row_p * T + t] = ph[0];
+      yw[(long long)a.row_s * T + t] = ph[1];
+      if constexpr (K == LABEL_PSN)
+        yw[(long long)a.row_n * T + t] = fminf(fmaxf(1.f - ph[0] - ph[1], 0.f), 1.f);
+      else
+        yw[(long long)a.row_det * T + t] = (double)t >= lo && (double)t < hi ? 1.f : 0.f;
+    }
   }
 }
 
@@ -296,165 +272,7 @@ __device__ __forceinline__ double gauss_noise(uint64_t key, int c, int t) {
   return sqrt(-2.0 * log(1.0 - u0)) * cos(2.0 * M_PI * u1);
 }
 
-// One augmented window per workgroup (include/volpick_hip.h, vp_aug_row): the record's steps in order, x and the P / S
-// labels in registers, each source shifted through LDS one channel at a time.
-__global__ __launch_bounds__(GEN_NTH) void bank_aug_kernel(const GenArgs a) {
-  __shared__ GenShared sh;
-  __shared__ float stage[AUG_MAX_T];
-  const int w = blockIdx.x, tid = threadIdx.x;
-  const int T = a.T;
-  const vp_aug_row& rec = a.aug[w];
-  const bool peak = a.norm == VP_NORM_PEAK;
-  const float two_s2 = 2.f * a.sigma * a.sigma;
-
-  // 1. the primary window, as bank_batch_kernel writes it
-  float x[3][AUG_MAXE], s[3][AUG_MAXE], P[AUG_MAXE], S[AUG_MAXE];
-  // a window cut and normalised into v (the primary, or a source); with zero_rule, its channels zeroed where the current
-  // x is all |x| <= 1e-8.  Returns max|x| of the current x over every channel (zero_rule only).
-  auto load = [&](const vp_plan_row& r, float v[3][AUG_MAXE], bool zero_rule) -> float {
-    gather_window(a, r, tid, v);
-    double mean[3], den[3];
-    window_stats(v, T, peak, tid, sh, mean, den);
-    float m[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-#pragma unroll
-      for (int k = 0; k < AUG_MAXE; ++k) {
-        v[c][k] = tid + k * GEN_NTH < T ? (float)(((double)v[c][k] - mean[c]) / den[c]) : 0.f;
-        if (zero_rule) m[c] = fmaxf(m[c], fabsf(x[c][k]));
-      }
-    if (!zero_rule) return 0.f;
-    block_max3(m, tid, sh);
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-      if (!(m[c] > 1e-8f))
-#pragma unroll
-        for (int k = 0; k < AUG_MAXE; ++k) v[c][k] = 0.f;
-    return fmaxf(fmaxf(m[0], m[1]), m[2]);
-  };
-  const vp_plan_row pr = rec.primary;
-  double po[4];
-  bool phas[4];
-  load(pr, x, false);
-  window_onsets(a, pr, po, phas);
-#pragma unroll
-  for (int k = 0; k < AUG_MAXE; ++k) {
-    float ph[2];
-    phase_labels(po, phas, tid + k * GEN_NTH, two_s2, ph);
-    P[k] = ph[0];
-    S[k] = ph[1];
-  }
-  // 2. the truncation behind the first event
-  const int cut = rec.cut;
-#pragma unroll
-  for (int c = 0; c < 3; ++c)
-#pragma unroll
-    for (int k = 0; k < AUG_MAXE; ++k)
-      if (tid + k * GEN_NTH >= cut) x[c][k] = 0.f;
-
-  bool renorm = false;  // y renormalised by an event: noise = 1 - P - S, else clip(1 - P - S, 0, 1)
-  // 3. events
-#pragma unroll 1
-  for (int i = 0; i < 2; ++i) {
-    const vp_aug_event& ev = rec.event[i];
-    if (ev.kind == VP_AUG_NONE) continue;
-    double so[4];
-    bool shas[4];
-    // a duplicate is the primary window as step 1 left it: cut and normalised again, to the same bits
-    const vp_plan_row& sr = ev.kind == VP_AUG_BANK ? ev.row : pr;
-    load(sr, s, ev.kind == VP_AUG_BANK);
-    window_onsets(a, sr, so, shas);
-    const int zb = ev.zero_before, d = ev.shift;
-    const float scale = ev.scale;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-#pragma unroll
-      for (int k = 0; k < AUG_MAXE; ++k) {
-        const int t = tid + k * GEN_NTH;
-        if (t < T) stage[t] = t < zb ? 0.f : s[c][k];
-      }
-      __syncthreads();
-#pragma unroll
-      for (int k = 0; k < AUG_MAXE; ++k) {
-        const int t = tid + k * GEN_NTH, ts = t - d;
-        if (t < T && ts >= 0 && ts < T) x[c][k] += scale * stage[ts];
-      }
-      __syncthreads();
-    }
-#pragma unroll
-    for (int k = 0; k < AUG_MAXE; ++k) {
-      const int t = tid + k * GEN_NTH, ts = t - d;
-      float ph[2] = {0.f, 0.f};
-      if (ts >= 0 && ts < T) phase_labels(so, shas, ts, two_s2, ph);
-      const float p = fmaxf(P[k], ph[0]), q = fmaxf(S[k], ph[1]);
-      const float dn = fmaxf(1.f, p + q);
-      P[k] = p / dn;
-      S[k] = q / dn;
-    }
-    renorm = true;
-  }
-
-  // 4. noise windows
-#pragma unroll 1
-  for (int j = 0; j < 2; ++j) {
-    const vp_aug_noise& nz = rec.noise[j];
-    if (nz.kind == VP_AUG_NONE) continue;
-    const float amax = load(nz.row, s, true);
-    const float f = amax * nz.scale;
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-#pragma unroll
-      for (int k = 0; k < AUG_MAXE; ++k) x[c][k] += s[c][k] * f;
-  }
-
-  // 5. Gaussian noise scaled by the signed maximum of x
-  if (rec.gauss > 0.f) {
-    float m[3] = {-INFINITY, -INFINITY, -INFINITY};
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-#pragma unroll
-      for (int k = 0; k < AUG_MAXE; ++k)
-        if (tid + k * GEN_NTH < T) m[c] = fmaxf(m[c], x[c][k]);
-    block_max3(m, tid, sh);
-    const double f = (double)rec.gauss * (double)fmaxf(fmaxf(m[0], m[1]), m[2]);
-    const uint64_t key = rec.noise_key;
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-#pragma unroll
-      for (int k = 0; k < AUG_MAXE; ++k) {
-        const int t = tid + k * GEN_NTH;
-        if (t < T) x[c][k] = (float)((double)x[c][k] + f * gauss_noise(key, c, t));
-      }
-  }
-
-  // 6. the gap, 7. the second normalisation
-  const int g0 = rec.gap_lo, g1 = rec.gap_hi;
-#pragma unroll
-  for (int k = 0; k < AUG_MAXE; ++k) {
-    const int t = tid + k * GEN_NTH;
-    if (t >= g0 && t < g1) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) x[c][k] = 0.f;
-      P[k] = S[k] = 0.f;
-    }
-  }
-  double mean[3], den[3];
-  window_stats(x, T, peak, tid, sh, mean, den);
-  float* xw = a.x + (long long)w * 3 * T;
-  float* yw = a.y + (long long)w * 3 * T;
-#pragma unroll
-  for (int k = 0; k < AUG_MAXE; ++k) {
-    const int t = tid + k * GEN_NTH;
-    if (t >= T) continue;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) xw[(long long)c * T + t] = (float)(((double)x[c][k] - mean[c]) / den[c]);
-    const float n = 1.f - P[k] - S[k];
-    yw[(long long)a.row_p * T + t] = P[k];
-    yw[(long long)a.row_s * T + t] = S[k];
-    yw[(long long)a.row_n * T + t] = renorm ? n : fminf(fmaxf(n, 0.f), 1.f);
-  }
-}
-
+// ---- augmented rows (include/volpick_hip.h, vp_aug_row): what the two kernels below share -------------------------------------
 // Row r cut, demeaned and normalised into v (fp32, 0 behind T): a primary window or a source.
 template <int E>
 __device__ __forceinline__ void load_normalised(const GenArgs& a, const vp_plan_row& r, int tid, GenShared& sh, float v[3][E]) {
@@ -468,15 +286,56 @@ __device__ __forceinline__ void load_normalised(const GenArgs& a, const vp_plan_
     for (int k = 0; k < E; ++k) v[c][k] = tid + k * GEN_NTH < T ? (float)(((double)v[c][k] - mean[c]) / den[c]) : 0.f;
 }
 
-// The labels of row r shifted by d samples, merged into P, S and -- with_det -- D by maximum: label(t) = label_r(t - d)
-// where 0 <= t - d < T, else 0 (which changes no maximum of labels >= 0).
+// A source window into v.  With zero_rule: the source's channels are zeroed where the current x is all |x| <= 1e-8, and
+// max|x| over every channel is returned; x_max(false, m) is the kernel's max|x| per channel, taken behind the source's loads.
+template <int E, class XMax>
+__device__ __forceinline__ float load_source(const GenArgs& a, const vp_plan_row& r, int tid, GenShared& sh, float v[3][E],
+                                             bool zero_rule, XMax x_max) {
+  load_normalised(a, r, tid, sh, v);
+  if (!zero_rule) return 0.f;
+  float xmax[3];
+  x_max(false, xmax);
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+    if (!(xmax[c] > 1e-8f))
+#pragma unroll
+      for (int k = 0; k < E; ++k) v[c][k] = 0.f;
+  return fmaxf(fmaxf(xmax[0], xmax[1]), xmax[2]);
+}
+
+// Step 5: x plus Gaussian noise scaled by f = gauss * the signed maximum of x over every channel.
+__device__ __forceinline__ double gauss_scale(const vp_aug_row& rec, const float xmax[3]) {
+  return (double)rec.gauss * (double)fmaxf(fmaxf(xmax[0], xmax[1]), xmax[2]);
+}
+__device__ __forceinline__ float gauss_add(float x, double f, uint64_t key, int c, int t) {
+  return (float)((double)x + f * gauss_noise(key, c, t));
+}
+
+// Step 7 (and block 1's last step): v demeaned and normalised into window w of a.x.
 template <int E>
-__device__ __forceinline__ void merge_labels(const GenArgs& a, const vp_plan_row& r, int d, bool with_det, double fixed_window,
-                                             int tid, float P[E], float S[E], float D[E]) {
-  double o[4], lo, hi;
+__device__ __forceinline__ void store_normalised(const GenArgs& a, const float v[3][E], int w, int tid, GenShared& sh) {
+  const int T = a.T;
+  double mean[3], den[3];
+  window_stats(v, T, a.norm == VP_NORM_PEAK, tid, sh, mean, den);
+  float* xw = a.x + (long long)w * 3 * T;
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int k = 0; k < E; ++k) {
+      const int t = tid + k * GEN_NTH;
+      if (t < T) xw[(long long)c * T + t] = (float)(((double)v[c][k] - mean[c]) / den[c]);
+    }
+}
+
+// The labels of row r shifted by d samples, merged into P, S and -- LABEL_DET and with_det -- D by maximum:
+// label(t) = label_r(t - d) where 0 <= t - d < T, else 0 (which changes no maximum of labels >= 0).
+template <int E, LabelKind K>
+__device__ __forceinline__ void merge_labels(const GenArgs& a, const vp_plan_row& r, int d, bool with_det, int tid, float P[E],
+                                             float S[E], float D[E]) {
+  double o[4], lo = 0.0, hi = 0.0;
   bool has[4];
   window_onsets(a, r, o, has);
-  detection_span(o, has, fixed_window, lo, hi);
+  if constexpr (K == LABEL_DET) detection_span(o, has, a.fixed_window, lo, hi);
   const float two_s2 = 2.f * a.sigma * a.sigma;
 #pragma unroll
   for (int k = 0; k < E; ++k) {
@@ -486,7 +345,7 @@ __device__ __forceinline__ void merge_labels(const GenArgs& a, const vp_plan_row
     phase_labels(o, has, ts, two_s2, ph);
     P[k] = fmaxf(P[k], ph[0]);
     S[k] = fmaxf(S[k], ph[1]);
-    if (with_det && (double)ts >= lo && (double)ts < hi) D[k] = 1.f;
+    if (K == LABEL_DET && with_det && (double)ts >= lo && (double)ts < hi) D[k] = 1.f;
   }
 }
 
@@ -497,18 +356,193 @@ __device__ __forceinline__ int opaque(int v) {
   return v;
 }
 
-// One augmented EQTransformer window per workgroup (include/volpick_hip.h, vp_bank_make_batch_eqt_aug): the record's steps
-// in order on x.  x, a source and the float64 statistics together do not fit the 128 registers of a 1024-thread workgroup,
-// so x lives in LDS between steps 1 and 7 -- xs[c][t], every sample read and written by the one thread t % 1024, hence
-// without barriers of its own -- and registers hold one window at a time: the primary, a source, then x for step 7.  A
-// source is shifted through a second LDS row, one channel at a time.  No step between 1 and 7 reads a label, and a label
-// is a maximum over the primary and the event sources of values that follow from onsets alone; so P, S and D are formed
-// once, behind the store of x.
-__global__ __launch_bounds__(GEN_NTH) void bank_aug_eqt_kernel(const GenArgs a, const DetArgs dt) {
-  constexpr int E = GEN_MAXE;
+// The labels of window w (steps 1, 3 and 6).  No step on x reads a label, and a label follows from onsets, shifts and the
+// gap alone; so both kernels form P, S and D once, behind the store of x:
+//   LABEL_DET (vp_bank_make_batch_eqt_aug): the maximum over the primary and the event sources, the detection box of an
+//     event merged only when the event was shifted; 0 in the gap;
+//   LABEL_PSN (vp_bank_make_batch_aug): behind each event's maximum P and S are divided by max(1, P + S), in event order;
+//     0 in the gap; noise = 1 - P - S, clipped to [0, 1] unless an event renormalised y.
+template <int E, LabelKind K>
+__device__ __forceinline__ void write_aug_labels(const GenArgs& a, const vp_aug_row& rec, const vp_plan_row& pr, int w, int tid0) {
+  static_assert(K != LABEL_NONE, "augmented rows carry labels");
+  const int T = a.T, g0 = rec.gap_lo, g1 = rec.gap_hi;
+  float P[E], S[E], D[E];
+#pragma unroll
+  for (int k = 0; k < E; ++k) P[k] = S[k] = D[k] = 0.f;
+  const int tid = opaque(tid0);
+  merge_labels<E, K>(a, pr, 0, true, tid, P, S, D);
+  bool renorm = false;
+#pragma unroll 1
+  for (int i = 0; i < 2; ++i) {
+    const vp_aug_event& ev = rec.event[i];
+    if (ev.kind == VP_AUG_NONE) continue;
+    vp_plan_row sr = pr;
+    if (ev.kind == VP_AUG_BANK) sr = ev.row;
+    merge_labels<E, K>(a, sr, ev.shift, ev.shift != 0, opaque(tid0), P, S, D);
+    if constexpr (K == LABEL_PSN) {
+#pragma unroll
+      for (int k = 0; k < E; ++k) {
+        const float dn = fmaxf(1.f, P[k] + S[k]);
+        P[k] = P[k] / dn;
+        S[k] = S[k] / dn;
+      }
+      renorm = true;
+    }
+  }
+  float* yw = a.y + (long long)w * 3 * T;
+#pragma unroll
+  for (int k = 0; k < E; ++k) {
+    const int t = tid + k * GEN_NTH;
+    if (t >= T) continue;
+    const bool gap = t >= g0 && t < g1;
+    const float p = gap ? 0.f : P[k], q = gap ? 0.f : S[k];
+    yw[(long long)a.row_p * T + t] = p;
+    yw[(long long)a.row_s * T + t] = q;
+    if constexpr (K == LABEL_PSN) {
+      const float n = 1.f - p - q;
+      yw[(long long)a.row_n * T + t] = renorm ? n : fminf(fmaxf(n, 0.f), 1.f);
+    } else {
+      yw[(long long)a.row_det * T + t] = gap ? 0.f : D[k];
+    }
+  }
+}
+
+// One augmented PhaseNet window per workgroup (vp_bank_make_batch_aug, T <= 3072): the record's steps in order with x and
+// the P / S labels in registers, three samples per thread beside one source; each event source is shifted through LDS one
+// channel at a time.  (The LDS form below, instantiated at E = 3, writes the same bits and is slower, and so is this form
+// with its labels formed behind the store of x: profiles/batchgen_refactor_ab_parent.txt.)
+__global__ __launch_bounds__(GEN_NTH) void bank_aug_psn_kernel(const GenArgs a) {
+  constexpr int E = AUG_MAXE;
   __shared__ GenShared sh;
-  __shared__ float stage[GEN_MAX_T];
-  __shared__ float xs[3][GEN_MAX_T];
+  __shared__ float stage[AUG_MAX_T];
+  const int w = blockIdx.x, tid = threadIdx.x;
+  const int T = a.T;
+  const vp_aug_row& rec = a.aug[w];
+  const vp_plan_row pr = rec.primary;
+  float x[3][E], s[3][E];
+
+  // max|x| per channel (sign = false) or max x (sign = true) over the window: m[c] for every thread
+  auto x_max = [&](bool sign, float m[3]) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      m[c] = sign ? -INFINITY : 0.f;
+#pragma unroll
+      for (int k = 0; k < E; ++k)
+        if (tid + k * GEN_NTH < T) m[c] = fmaxf(m[c], sign ? x[c][k] : fabsf(x[c][k]));
+    }
+    block_max3(m, tid, sh);
+  };
+
+  // 1. the primary window, as bank_block1_kernel writes it; 2. the truncation behind the first event
+  load_normalised(a, pr, tid, sh, x);
+  const int cut = rec.cut;
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int k = 0; k < E; ++k)
+      if (tid + k * GEN_NTH >= cut) x[c][k] = 0.f;
+  float P[E], S[E], D[E];  // (D: LABEL_DET's, unused)
+#pragma unroll
+  for (int k = 0; k < E; ++k) P[k] = S[k] = D[k] = 0.f;
+  merge_labels<E, LABEL_PSN>(a, pr, 0, false, tid, P, S, D);
+  bool renorm = false;  // y renormalised by an event: noise = 1 - P - S, else clip(1 - P - S, 0, 1)
+
+  // 3. events: a duplicate is the primary window as step 1 left it, cut and normalised again to the same bits
+#pragma unroll 1
+  for (int i = 0; i < 2; ++i) {
+    const vp_aug_event& ev = rec.event[i];
+    if (ev.kind == VP_AUG_NONE) continue;
+    const bool bank = ev.kind == VP_AUG_BANK;
+    vp_plan_row sr = pr;  // (a copy, not a reference to one of two: pr stays in registers)
+    if (bank) sr = ev.row;
+    load_source(a, sr, tid, sh, s, bank, x_max);
+    const int zb = ev.zero_before, d = ev.shift;
+    const float scale = ev.scale;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+#pragma unroll
+      for (int k = 0; k < E; ++k) {
+        const int t = tid + k * GEN_NTH;
+        if (t < T) stage[t] = t < zb ? 0.f : s[c][k];
+      }
+      __syncthreads();
+#pragma unroll
+      for (int k = 0; k < E; ++k) {
+        const int t = tid + k * GEN_NTH, ts = t - d;
+        if (t < T && ts >= 0 && ts < T) x[c][k] += scale * stage[ts];
+      }
+      __syncthreads();
+    }
+    merge_labels<E, LABEL_PSN>(a, sr, d, false, tid, P, S, D);
+#pragma unroll
+    for (int k = 0; k < E; ++k) {
+      const float dn = fmaxf(1.f, P[k] + S[k]);
+      P[k] = P[k] / dn;
+      S[k] = S[k] / dn;
+    }
+    renorm = true;
+  }
+
+  // 4. noise windows
+#pragma unroll 1
+  for (int j = 0; j < 2; ++j) {
+    const vp_aug_noise& nz = rec.noise[j];
+    if (nz.kind == VP_AUG_NONE) continue;
+    const float f = load_source(a, nz.row, tid, sh, s, true, x_max) * nz.scale;
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+      for (int k = 0; k < E; ++k) x[c][k] += s[c][k] * f;
+  }
+
+  // 5. Gaussian noise scaled by the signed maximum of x
+  if (rec.gauss > 0.f) {
+    float m[3];
+    x_max(true, m);
+    const double f = gauss_scale(rec, m);
+    const uint64_t key = rec.noise_key;
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+      for (int k = 0; k < E; ++k) {
+        const int t = tid + k * GEN_NTH;
+        if (t < T) x[c][k] = gauss_add(x[c][k], f, key, c, t);
+      }
+  }
+
+  // 6. the gap in x, 7. the second normalisation
+  const int g0 = rec.gap_lo, g1 = rec.gap_hi;
+#pragma unroll
+  for (int k = 0; k < E; ++k) {
+    const int t = tid + k * GEN_NTH;
+    if (t >= g0 && t < g1)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) x[c][k] = 0.f;
+  }
+  store_normalised(a, x, w, tid, sh);
+  float* yw = a.y + (long long)w * 3 * T;
+#pragma unroll
+  for (int k = 0; k < E; ++k) {
+    const int t = tid + k * GEN_NTH;
+    if (t >= T) continue;
+    const bool gap = t >= g0 && t < g1;
+    const float p = gap ? 0.f : P[k], q = gap ? 0.f : S[k], n = 1.f - p - q;
+    yw[(long long)a.row_p * T + t] = p;
+    yw[(long long)a.row_s * T + t] = q;
+    yw[(long long)a.row_n * T + t] = renorm ? n : fminf(fmaxf(n, 0.f), 1.f);
+  }
+}
+
+// One augmented window per workgroup, T <= 1024 E (vp_bank_make_batch_eqt_aug at E = 6): the same steps where x, a source
+// and the float64 statistics together do not fit the 128 registers of a 1024-thread workgroup.  x lives in LDS between
+// steps 1 and 7 -- xs[c][t], every sample read and written by the one thread t % 1024, hence without barriers of its own --
+// and registers hold one window at a time: the primary, a source, then x for step 7.  A source is shifted through a second
+// LDS row, one channel at a time.
+template <int E, LabelKind K>
+__global__ __launch_bounds__(GEN_NTH) void bank_aug_kernel(const GenArgs a) {
+  __shared__ GenShared sh;
+  __shared__ float stage[E * GEN_NTH];
+  __shared__ float xs[3][E * GEN_NTH];
   const int w = blockIdx.x, tid0 = threadIdx.x;
   const int T = a.T;
   const vp_aug_row& rec = a.aug[w];
@@ -525,22 +559,8 @@ __global__ __launch_bounds__(GEN_NTH) void bank_aug_eqt_kernel(const GenArgs a, 
     }
     block_max3(m, tid, sh);
   };
-  // a source window into v, its channels zeroed where the current x is all |x| <= 1e-8; returns max|x| over every channel
-  auto load_source = [&](const vp_plan_row& r, bool zero_rule) -> float {
-    float m[3] = {0.f, 0.f, 0.f};
-    if (zero_rule) x_max(false, m);
-    const int tid = opaque(tid0);
-    load_normalised(a, r, tid, sh, v);
-    if (!zero_rule) return 0.f;
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-      if (!(m[c] > 1e-8f))
-#pragma unroll
-        for (int k = 0; k < E; ++k) v[c][k] = 0.f;
-    return fmaxf(fmaxf(m[0], m[1]), m[2]);
-  };
 
-  // 1. the primary window, as bank_batch_eqt_kernel writes it; 2. the truncation behind the first event
+  // 1. the primary window, as bank_block1_kernel writes it; 2. the truncation behind the first event
   load_normalised(a, pr, opaque(tid0), sh, v);
   const int cut = rec.cut;
 #pragma unroll
@@ -556,7 +576,10 @@ __global__ __launch_bounds__(GEN_NTH) void bank_aug_eqt_kernel(const GenArgs a, 
   for (int i = 0; i < 2; ++i) {
     const vp_aug_event& ev = rec.event[i];
     if (ev.kind == VP_AUG_NONE) continue;
-    load_source(ev.kind == VP_AUG_BANK ? ev.row : pr, ev.kind == VP_AUG_BANK);
+    const bool bank = ev.kind == VP_AUG_BANK;
+    vp_plan_row sr = pr;  // (a copy, not a reference to one of two: pr stays in registers)
+    if (bank) sr = ev.row;
+    load_source(a, sr, opaque(tid0), sh, v, bank, x_max);
     const int zb = ev.zero_before, d = ev.shift;
     const float scale = ev.scale;
     const int tid = opaque(tid0);
@@ -581,7 +604,7 @@ __global__ __launch_bounds__(GEN_NTH) void bank_aug_eqt_kernel(const GenArgs a, 
   for (int j = 0; j < 2; ++j) {
     const vp_aug_noise& nz = rec.noise[j];
     if (nz.kind == VP_AUG_NONE) continue;
-    const float f = load_source(nz.row, true) * nz.scale;
+    const float f = load_source(a, nz.row, opaque(tid0), sh, v, true, x_max) * nz.scale;
     const int tid = opaque(tid0);
 #pragma unroll
     for (int c = 0; c < 3; ++c)
@@ -596,18 +619,18 @@ __global__ __launch_bounds__(GEN_NTH) void bank_aug_eqt_kernel(const GenArgs a, 
   if (rec.gauss > 0.f) {
     float m[3];
     x_max(true, m);
-    const double f = (double)rec.gauss * (double)fmaxf(fmaxf(m[0], m[1]), m[2]);
+    const double f = gauss_scale(rec, m);
     const uint64_t key = rec.noise_key;
     const int tid = opaque(tid0);
 #pragma unroll 1
     for (int c = 0; c < 3; ++c)
 #pragma unroll 1
-      for (int t = tid; t < T; t += GEN_NTH) xs[c][t] = (float)((double)xs[c][t] + f * gauss_noise(key, c, t));
+      for (int t = tid; t < T; t += GEN_NTH) xs[c][t] = gauss_add(xs[c][t], f, key, c, t);
   }
 
   // 6. the gap in x, 7. the second normalisation
   const int g0 = rec.gap_lo, g1 = rec.gap_hi;
-  int tid = opaque(tid0);
+  const int tid = opaque(tid0);
 #pragma unroll
   for (int c = 0; c < 3; ++c)
 #pragma unroll
@@ -615,39 +638,8 @@ __global__ __launch_bounds__(GEN_NTH) void bank_aug_eqt_kernel(const GenArgs a, 
       const int t = tid + k * GEN_NTH;
       v[c][k] = t < T && !(t >= g0 && t < g1) ? xs[c][t] : 0.f;
     }
-  double mean[3], den[3];
-  window_stats(v, T, a.norm == VP_NORM_PEAK, tid, sh, mean, den);
-  float* xw = a.x + (long long)w * 3 * T;
-#pragma unroll
-  for (int c = 0; c < 3; ++c)
-#pragma unroll
-    for (int k = 0; k < E; ++k) {
-      const int t = tid + k * GEN_NTH;
-      if (t < T) xw[(long long)c * T + t] = (float)(((double)v[c][k] - mean[c]) / den[c]);
-    }
-
-  // the labels of steps 1, 3 and 6: an event's detection box is merged only when the event was shifted
-  float P[E], S[E], D[E];
-#pragma unroll
-  for (int k = 0; k < E; ++k) P[k] = S[k] = D[k] = 0.f;
-  tid = opaque(tid0);
-  merge_labels<E>(a, pr, 0, true, dt.fixed_window, tid, P, S, D);
-#pragma unroll 1
-  for (int i = 0; i < 2; ++i) {
-    const vp_aug_event& ev = rec.event[i];
-    if (ev.kind == VP_AUG_NONE) continue;
-    merge_labels<E>(a, ev.kind == VP_AUG_BANK ? ev.row : pr, ev.shift, ev.shift != 0, dt.fixed_window, opaque(tid0), P, S, D);
-  }
-  float* yw = a.y + (long long)w * 3 * T;
-#pragma unroll
-  for (int k = 0; k < E; ++k) {
-    const int t = tid + k * GEN_NTH;
-    if (t >= T) continue;
-    const bool gap = t >= g0 && t < g1;
-    yw[(long long)a.row_p * T + t] = gap ? 0.f : P[k];
-    yw[(long long)a.row_s * T + t] = gap ? 0.f : S[k];
-    yw[(long long)dt.row_det * T + t] = gap ? 0.f : D[k];
-  }
+  store_normalised(a, v, w, tid, sh);
+  write_aug_labels<E, K>(a, rec, pr, w, tid0);
 }
 
 }  // namespace
@@ -721,18 +713,21 @@ Bank::~Bank() {
 
 namespace {
 
-int args_check(int B, int T, float sigma, int norm, const int* label_rows) {
-  VP_REQUIRE(label_rows, "bank batch: null label_rows");
-  VP_REQUIRE(B >= 1, "bank batch: B = %d", B);
-  VP_REQUIRE(T >= 1 && T <= GEN_MAX_T, "bank batch: T = %d outside [1, %d]", T, GEN_MAX_T);
-  VP_REQUIRE(std::isfinite(sigma) && sigma > 0.f, "bank batch: sigma = %g must be finite and > 0", (double)sigma);
-  VP_REQUIRE(norm == VP_NORM_PEAK || norm == VP_NORM_STD, "bank batch: norm %d is neither VP_NORM_PEAK nor VP_NORM_STD", norm);
-  int seen = 0;
-  for (int i = 0; i < 3; ++i) {
-    VP_REQUIRE(label_rows[i] >= 0 && label_rows[i] < 3, "bank batch: label_rows[%d] = %d outside [0, 3)", i, label_rows[i]);
-    seen |= 1 << label_rows[i];
+// B and the spec's own fields; `pre` names the kind of batch in the messages ("bank batch", "bank windows").  A batch
+// without labels has no label rows and no sigma to check.
+int args_check(const char* pre, int B, const BatchSpec& sp) {
+  const bool labelled = sp.labels != LABEL_NONE;
+  VP_REQUIRE(!labelled || sp.label_rows, "%s: null label_rows", pre);
+  VP_REQUIRE(B >= 1, "%s: B = %d", pre, B);
+  VP_REQUIRE(sp.T >= 1 && sp.T <= GEN_MAX_T, "%s: T = %d outside [1, %d]", pre, sp.T, GEN_MAX_T);
+  VP_REQUIRE(!labelled || (std::isfinite(sp.sigma) && sp.sigma > 0.f), "%s: sigma = %g must be finite and > 0", pre, (double)sp.sigma);
+  VP_REQUIRE(sp.norm == VP_NORM_PEAK || sp.norm == VP_NORM_STD, "%s: norm %d is neither VP_NORM_PEAK nor VP_NORM_STD", pre, sp.norm);
+  int seen = labelled ? 0 : 7;
+  for (int i = 0; labelled && i < 3; ++i) {
+    VP_REQUIRE(sp.label_rows[i] >= 0 && sp.label_rows[i] < 3, "%s: label_rows[%d] = %d outside [0, 3)", pre, i, sp.label_rows[i]);
+    seen |= 1 << sp.label_rows[i];
   }
-  VP_REQUIRE(seen == 7, "bank batch: label_rows is not a permutation of 0, 1, 2");
+  VP_REQUIRE(seen == 7, "%s: label_rows is not a permutation of 0, 1, 2", pre);
   return VP_OK;
 }
 
@@ -751,196 +746,112 @@ int row_check(const Bank& bk, const vp_plan_row& r, int b, const char* what) {
 
 bool row_is_zero(const vp_plan_row& r) { return !r.trace && !r.reserved && !r.start && !r.lo && !r.hi; }
 
-int fixed_window_check(float det_fixed_window) {
-  VP_REQUIRE(det_fixed_window < 0.f || std::isfinite(det_fixed_window), "bank batch: det_fixed_window = %g is neither negative nor a finite length",
-             (double)det_fixed_window);  // (a NaN fails both)
+// Every field of one augmented row.
+int aug_row_check(const Bank& bk, const vp_aug_row& r, int b, int T) {
+  int rc;
+  if ((rc = row_check(bk, r.primary, b, "row")) != VP_OK) return rc;
+  for (int i = 0; i < 2; ++i) {
+    const vp_aug_event& e = r.event[i];
+    VP_REQUIRE(e.kind >= VP_AUG_NONE && e.kind <= VP_AUG_SELF, "bank batch: row %d: event %d: kind %d", b, i, (int)e.kind);
+    if (e.kind == VP_AUG_NONE) {
+      VP_REQUIRE(row_is_zero(e.row) && !e.zero_before && !e.shift && e.scale == 0.f,
+                 "bank batch: row %d: event %d is unused but not zero", b, i);
+      continue;
+    }
+    if (e.kind == VP_AUG_BANK) {
+      if ((rc = row_check(bk, e.row, b, "event source of row")) != VP_OK) return rc;
+    } else {
+      VP_REQUIRE(row_is_zero(e.row), "bank batch: row %d: event %d duplicates the window but has a source row", b, i);
+    }
+    VP_REQUIRE(e.zero_before >= 0 && e.zero_before <= T, "bank batch: row %d: event %d: zero_before %d outside [0, %d]",
+               b, i, (int)e.zero_before, T);
+    VP_REQUIRE(e.shift >= -T && e.shift <= T, "bank batch: row %d: event %d: |shift| = |%d| > T = %d", b, i, (int)e.shift,
+               T);
+    VP_REQUIRE(std::isfinite(e.scale) && e.scale >= 0.f, "bank batch: row %d: event %d: scale %g", b, i, (double)e.scale);
+  }
+  for (int j = 0; j < 2; ++j) {
+    const vp_aug_noise& n = r.noise[j];
+    VP_REQUIRE(n.kind == VP_AUG_NONE || n.kind == VP_AUG_BANK, "bank batch: row %d: noise %d: kind %d", b, j, (int)n.kind);
+    if (n.kind == VP_AUG_NONE) {
+      VP_REQUIRE(row_is_zero(n.row) && n.scale == 0.f, "bank batch: row %d: noise %d is unused but not zero", b, j);
+      continue;
+    }
+    if ((rc = row_check(bk, n.row, b, "noise source of row")) != VP_OK) return rc;
+    VP_REQUIRE(std::isfinite(n.scale) && n.scale >= 0.f, "bank batch: row %d: noise %d: scale %g", b, j, (double)n.scale);
+  }
+  VP_REQUIRE(std::isfinite(r.gauss) && r.gauss >= 0.f, "bank batch: row %d: gauss %g", b, (double)r.gauss);
+  VP_REQUIRE(r.gauss > 0.f || r.noise_key == 0, "bank batch: row %d: a noise key without Gaussian noise", b);
+  VP_REQUIRE(r.cut >= 0 && r.cut <= T, "bank batch: row %d: cut %d outside [0, %d]", b, (int)r.cut, T);
+  VP_REQUIRE(r.gap_lo >= 0 && r.gap_lo <= r.gap_hi && r.gap_hi <= T, "bank batch: row %d: gap [%d, %d) outside [0, %d]", b,
+             (int)r.gap_lo, (int)r.gap_hi, T);
   return VP_OK;
 }
 
 }  // namespace
 
-int bank_check(const Bank& bk, const vp_plan_row* rows, int B, int T, float sigma, int norm, const int* label_rows) {
-  VP_REQUIRE(rows, "bank batch: null rows");
-  const int rc = args_check(B, T, sigma, norm, label_rows);
+int bank_check(const Bank& bk, const BatchSpec& sp, BatchRows rows, int B) {
+  const char* pre = sp.labels == LABEL_NONE ? "bank windows" : "bank batch";
+  VP_REQUIRE(rows.p, "%s: null rows", pre);
+  int rc = args_check(pre, B, sp);
   if (rc != VP_OK) return rc;
+  if (rows.aug) {
+    VP_REQUIRE(sp.labels != LABEL_NONE, "%s: augmented rows carry labels", pre);
+    const int max_T = sp.labels == LABEL_PSN ? AUG_MAX_T : GEN_MAX_T;  // what the executing kernel holds
+    VP_REQUIRE(sp.T <= max_T, "bank batch: augmented rows: T = %d outside [1, %d]", sp.T, max_T);
+  }
   for (int b = 0; b < B; ++b) {
-    const int rc = row_check(bk, rows[b], b, "row");
+    rc = rows.aug ? aug_row_check(bk, static_cast<const vp_aug_row*>(rows.p)[b], b, sp.T)
+                  : row_check(bk, static_cast<const vp_plan_row*>(rows.p)[b], b, "row");
     if (rc != VP_OK) return rc;
   }
+  VP_REQUIRE(sp.labels != LABEL_DET || sp.det_fixed_window < 0.f || std::isfinite(sp.det_fixed_window),
+             "bank batch: det_fixed_window = %g is neither negative nor a finite length", (double)sp.det_fixed_window);  // (a NaN fails both)
   return VP_OK;
 }
 
-int bank_check_windows(const Bank& bk, const vp_plan_row* rows, int B, int T, int norm) {
-  VP_REQUIRE(rows, "bank windows: null rows");
-  VP_REQUIRE(B >= 1, "bank windows: B = %d", B);
-  VP_REQUIRE(T >= 1 && T <= GEN_MAX_T, "bank windows: T = %d outside [1, %d]", T, GEN_MAX_T);
-  VP_REQUIRE(norm == VP_NORM_PEAK || norm == VP_NORM_STD, "bank windows: norm %d is neither VP_NORM_PEAK nor VP_NORM_STD", norm);
-  for (int b = 0; b < B; ++b) {
-    const int rc = row_check(bk, rows[b], b, "row");
-    if (rc != VP_OK) return rc;
+int bank_launch(const Bank& bk, const BatchSpec& sp, BatchRows rows_dev, int B, float* x, float* y, hipStream_t s) {
+  struct Kernel {
+    void (*fn)(GenArgs);
+    const char* name;
+  };
+  static const Kernel kernels[2][3] = {  // [augmented rows][label kind]
+      {{bank_block1_kernel<LABEL_NONE>, "bank_block1_kernel<LABEL_NONE>"},
+       {bank_block1_kernel<LABEL_PSN>, "bank_block1_kernel<LABEL_PSN>"},
+       {bank_block1_kernel<LABEL_DET>, "bank_block1_kernel<LABEL_DET>"}},
+      {{nullptr, "no kernel for augmented rows without labels"},
+       {bank_aug_psn_kernel, "bank_aug_psn_kernel"},
+       {bank_aug_kernel<GEN_MAXE, LABEL_DET>, "bank_aug_kernel<6, LABEL_DET>"}}};
+  const Kernel& k = kernels[rows_dev.aug][sp.labels];
+  if (!k.fn) {  // (bank_check refuses them)
+    set_error("%s", k.name);
+    return VP_ERR_INVALID;
   }
-  return VP_OK;
-}
-
-namespace {
-
-int launch(void (*kernel)(GenArgs), const char* name, const Bank& bk, const vp_plan_row* rows_dev, const vp_aug_row* aug_dev,
-           int B, int T, float sigma, int norm, const int* label_rows, float* x, float* y, hipStream_t s) {
   GenArgs a{};
   a.data = bk.data;
   a.off = bk.off_dev;
   a.len = bk.len_dev;
   a.onset = bk.onset_dev;
-  a.rows = rows_dev;
-  a.aug = aug_dev;
+  if (rows_dev.aug)
+    a.aug = static_cast<const vp_aug_row*>(rows_dev.p);
+  else
+    a.rows = static_cast<const vp_plan_row*>(rows_dev.p);
   a.x = x;
   a.y = y;
-  a.T = T;
-  a.norm = norm;
-  a.sigma = sigma;
-  a.row_p = label_rows[0];
-  a.row_s = label_rows[1];
-  a.row_n = label_rows[2];
-  hipLaunchKernelGGL(kernel, dim3(B), dim3(GEN_NTH), 0, s, a);
+  a.T = sp.T;
+  a.norm = sp.norm;
+  a.sigma = sp.sigma;
+  const int* lr = sp.label_rows;
+  a.row_p = a.row_s = a.row_n = a.row_det = -1;  // a kernel reads the rows of its label kind alone
+  if (sp.labels == LABEL_PSN) a.row_p = lr[0], a.row_s = lr[1], a.row_n = lr[2];
+  if (sp.labels == LABEL_DET) a.row_det = lr[0], a.row_p = lr[1], a.row_s = lr[2];
+  a.fixed_window = sp.det_fixed_window < 0.f ? -1.0 : (double)sp.det_fixed_window;
+  hipLaunchKernelGGL(k.fn, dim3(B), dim3(GEN_NTH), 0, s, a);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
-    set_error("%s launch failed: %s", name, hipGetErrorString(e));
+    set_error("%s launch failed: %s", k.name, hipGetErrorString(e));
     return VP_ERR_HIP;
   }
   return VP_OK;
-}
-
-}  // namespace
-
-int bank_launch(const Bank& bk, const vp_plan_row* rows_dev, int B, int T, float sigma, int norm, const int* label_rows,
-                float* x, float* y, hipStream_t s) {
-  return launch(bank_batch_kernel, "bank_batch_kernel", bk, rows_dev, nullptr, B, T, sigma, norm, label_rows, x, y, s);
-}
-
-int bank_check_eqt(const Bank& bk, const vp_plan_row* rows, int B, int T, float sigma, int norm, const int* label_rows,
-                   float det_fixed_window) {
-  const int rc = bank_check(bk, rows, B, T, sigma, norm, label_rows);
-  if (rc != VP_OK) return rc;
-  return fixed_window_check(det_fixed_window);
-}
-
-namespace {
-
-// bank_batch_eqt_kernel or bank_aug_eqt_kernel on their rows: label_rows = the rows of detection, P and S.
-int launch_eqt(void (*kernel)(GenArgs, DetArgs), const char* name, const Bank& bk, const vp_plan_row* rows_dev,
-               const vp_aug_row* aug_dev, int B, int T, float sigma, int norm, const int* label_rows, float det_fixed_window,
-               float* x, float* y, hipStream_t s) {
-  GenArgs a{};
-  a.data = bk.data;
-  a.off = bk.off_dev;
-  a.len = bk.len_dev;
-  a.onset = bk.onset_dev;
-  a.rows = rows_dev;
-  a.aug = aug_dev;
-  a.x = x;
-  a.y = y;
-  a.T = T;
-  a.norm = norm;
-  a.sigma = sigma;
-  a.row_p = label_rows[1];
-  a.row_s = label_rows[2];
-  a.row_n = -1;  // there is no noise row
-  DetArgs d{};
-  d.row_det = label_rows[0];
-  d.fixed_window = det_fixed_window < 0.f ? -1.0 : (double)det_fixed_window;
-  hipLaunchKernelGGL(kernel, dim3(B), dim3(GEN_NTH), 0, s, a, d);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("%s launch failed: %s", name, hipGetErrorString(e));
-    return VP_ERR_HIP;
-  }
-  return VP_OK;
-}
-
-}  // namespace
-
-int bank_launch_eqt(const Bank& bk, const vp_plan_row* rows_dev, int B, int T, float sigma, int norm, const int* label_rows,
-                    float det_fixed_window, float* x, float* y, hipStream_t s) {
-  return launch_eqt(bank_batch_eqt_kernel, "bank_batch_eqt_kernel", bk, rows_dev, nullptr, B, T, sigma, norm, label_rows,
-                    det_fixed_window, x, y, s);
-}
-
-int bank_launch_windows(const Bank& bk, const vp_plan_row* rows_dev, int B, int T, int norm, float* x, hipStream_t s) {
-  const int unused_label_rows[3] = {0, 1, 2};
-  return launch(bank_window_kernel, "bank_window_kernel", bk, rows_dev, nullptr, B, T, 1.f, norm, unused_label_rows, x, nullptr, s);
-}
-
-namespace {
-
-// Every field of every augmented row; max_T is what the executing kernel holds in registers.
-int aug_check(const Bank& bk, const vp_aug_row* rows, int B, int T, float sigma, int norm, const int* label_rows, int max_T) {
-  VP_REQUIRE(rows, "bank batch: null rows");
-  int rc = args_check(B, T, sigma, norm, label_rows);
-  if (rc != VP_OK) return rc;
-  VP_REQUIRE(T <= max_T, "bank batch: augmented rows: T = %d outside [1, %d]", T, max_T);
-  for (int b = 0; b < B; ++b) {
-    const vp_aug_row& r = rows[b];
-    if ((rc = row_check(bk, r.primary, b, "row")) != VP_OK) return rc;
-    for (int i = 0; i < 2; ++i) {
-      const vp_aug_event& e = r.event[i];
-      VP_REQUIRE(e.kind >= VP_AUG_NONE && e.kind <= VP_AUG_SELF, "bank batch: row %d: event %d: kind %d", b, i, (int)e.kind);
-      if (e.kind == VP_AUG_NONE) {
-        VP_REQUIRE(row_is_zero(e.row) && !e.zero_before && !e.shift && e.scale == 0.f,
-                   "bank batch: row %d: event %d is unused but not zero", b, i);
-        continue;
-      }
-      if (e.kind == VP_AUG_BANK) {
-        if ((rc = row_check(bk, e.row, b, "event source of row")) != VP_OK) return rc;
-      } else {
-        VP_REQUIRE(row_is_zero(e.row), "bank batch: row %d: event %d duplicates the window but has a source row", b, i);
-      }
-      VP_REQUIRE(e.zero_before >= 0 && e.zero_before <= T, "bank batch: row %d: event %d: zero_before %d outside [0, %d]",
-                 b, i, (int)e.zero_before, T);
-      VP_REQUIRE(e.shift >= -T && e.shift <= T, "bank batch: row %d: event %d: |shift| = |%d| > T = %d", b, i, (int)e.shift,
-                 T);
-      VP_REQUIRE(std::isfinite(e.scale) && e.scale >= 0.f, "bank batch: row %d: event %d: scale %g", b, i, (double)e.scale);
-    }
-    for (int j = 0; j < 2; ++j) {
-      const vp_aug_noise& n = r.noise[j];
-      VP_REQUIRE(n.kind == VP_AUG_NONE || n.kind == VP_AUG_BANK, "bank batch: row %d: noise %d: kind %d", b, j, (int)n.kind);
-      if (n.kind == VP_AUG_NONE) {
-        VP_REQUIRE(row_is_zero(n.row) && n.scale == 0.f, "bank batch: row %d: noise %d is unused but not zero", b, j);
-        continue;
-      }
-      if ((rc = row_check(bk, n.row, b, "noise source of row")) != VP_OK) return rc;
-      VP_REQUIRE(std::isfinite(n.scale) && n.scale >= 0.f, "bank batch: row %d: noise %d: scale %g", b, j, (double)n.scale);
-    }
-    VP_REQUIRE(std::isfinite(r.gauss) && r.gauss >= 0.f, "bank batch: row %d: gauss %g", b, (double)r.gauss);
-    VP_REQUIRE(r.gauss > 0.f || r.noise_key == 0, "bank batch: row %d: a noise key without Gaussian noise", b);
-    VP_REQUIRE(r.cut >= 0 && r.cut <= T, "bank batch: row %d: cut %d outside [0, %d]", b, (int)r.cut, T);
-    VP_REQUIRE(r.gap_lo >= 0 && r.gap_lo <= r.gap_hi && r.gap_hi <= T, "bank batch: row %d: gap [%d, %d) outside [0, %d]", b,
-               (int)r.gap_lo, (int)r.gap_hi, T);
-  }
-  return VP_OK;
-}
-
-}  // namespace
-
-int bank_check(const Bank& bk, const vp_aug_row* rows, int B, int T, float sigma, int norm, const int* label_rows) {
-  return aug_check(bk, rows, B, T, sigma, norm, label_rows, AUG_MAX_T);
-}
-
-int bank_launch(const Bank& bk, const vp_aug_row* rows_dev, int B, int T, float sigma, int norm, const int* label_rows,
-                    float* x, float* y, hipStream_t s) {
-  return launch(bank_aug_kernel, "bank_aug_kernel", bk, nullptr, rows_dev, B, T, sigma, norm, label_rows, x, y, s);
-}
-
-int bank_check_eqt(const Bank& bk, const vp_aug_row* rows, int B, int T, float sigma, int norm, const int* label_rows,
-                   float det_fixed_window) {
-  const int rc = aug_check(bk, rows, B, T, sigma, norm, label_rows, GEN_MAX_T);
-  if (rc != VP_OK) return rc;
-  return fixed_window_check(det_fixed_window);
-}
-
-int bank_launch_eqt(const Bank& bk, const vp_aug_row* rows_dev, int B, int T, float sigma, int norm, const int* label_rows,
-                    float det_fixed_window, float* x, float* y, hipStream_t s) {
-  return launch_eqt(bank_aug_eqt_kernel, "bank_aug_eqt_kernel", bk, nullptr, rows_dev, B, T, sigma, norm, label_rows,
-                    det_fixed_window, x, y, s);
 }
 
 }  // namespace vp
@@ -949,36 +860,19 @@ using namespace vp;
 
 namespace {
 
-// vp_bank_make_batch(_aug): rows staged through the bank's ring, slot k reused once the kernel that last read it has run.
-template <class Row>
-int make_batch(Bank& bk, const Row* rows, int B, int T, float sigma, int norm, const int* label_rows, float* x, float* y,
-               void* stream) {
-  const int rc = bank_check(bk, rows, B, T, sigma, norm, label_rows);
+// The four vp_bank_make_batch* entry points: the rows staged through the bank's ring, slot k reused once the kernel that
+// last read it has run.
+int make_batch(vp_bank* h, const char* who, const BatchSpec& sp, BatchRows rows, int B, float* x, float* y, void* stream) {
+  VP_REQUIRE(h && x && y, "%s: null argument", who);
+  Bank& bk = *reinterpret_cast<Bank*>(h);
+  int rc = bank_check(bk, sp, rows, B);
   if (rc != VP_OK) return rc;
   VP_HIP(hipSetDevice(bk.device));
-  const size_t bytes = (size_t)B * sizeof(Row);
-  int r = bk.ring.acquire(bytes);
-  if (r != VP_OK) return r;
+  if ((rc = bk.ring.acquire(rows.bytes(B))) != VP_OK) return rc;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const Row* rd = static_cast<const Row*>(bk.ring.stage({{rows, bytes}}, s));
+  const void* rd = bk.ring.stage({{rows.p, rows.bytes(B)}}, s);
   if (!rd) return VP_ERR_HIP;
-  if ((r = bank_launch(bk, rd, B, T, sigma, norm, label_rows, x, y, s)) != VP_OK) return r;
-  return bk.ring.retire(s);
-}
-
-// vp_bank_make_batch_eqt(_aug): the same with the detection arguments.
-template <class Row>
-int make_batch_eqt(Bank& bk, const Row* rows, int B, int T, float sigma, int norm, const int* label_rows, float det_fixed_window,
-                   float* x, float* y, void* stream) {
-  int rc = bank_check_eqt(bk, rows, B, T, sigma, norm, label_rows, det_fixed_window);
-  if (rc != VP_OK) return rc;
-  VP_HIP(hipSetDevice(bk.device));
-  const size_t bytes = (size_t)B * sizeof(Row);
-  if ((rc = bk.ring.acquire(bytes)) != VP_OK) return rc;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const Row* rd = static_cast<const Row*>(bk.ring.stage({{rows, bytes}}, s));
-  if (!rd) return VP_ERR_HIP;
-  if ((rc = bank_launch_eqt(bk, rd, B, T, sigma, norm, label_rows, det_fixed_window, x, y, s)) != VP_OK) return rc;
+  if ((rc = bank_launch(bk, sp, rows.at(rd), B, x, y, s)) != VP_OK) return rc;
   return bk.ring.retire(s);
 }
 
@@ -1061,26 +955,23 @@ int vp_bank_destroy(vp_bank* h) {
 
 int vp_bank_make_batch(vp_bank* h, const vp_plan_row* rows, int B, int T, float sigma, int norm, const int* label_rows,
                        float* x, float* y, void* stream) {
-  VP_REQUIRE(h && x && y, "vp_bank_make_batch: null argument");
-  return make_batch(*reinterpret_cast<Bank*>(h), rows, B, T, sigma, norm, label_rows, x, y, stream);
+  return make_batch(h, "vp_bank_make_batch", {T, sigma, norm, LABEL_PSN, label_rows}, rows, B, x, y, stream);
 }
 
 int vp_bank_make_batch_eqt(vp_bank* h, const vp_plan_row* rows, int B, int T, float sigma, int norm, const int* label_rows,
                            float det_fixed_window, float* x, float* y, void* stream) {
-  VP_REQUIRE(h && x && y, "vp_bank_make_batch_eqt: null argument");
-  return make_batch_eqt(*reinterpret_cast<Bank*>(h), rows, B, T, sigma, norm, label_rows, det_fixed_window, x, y, stream);
+  return make_batch(h, "vp_bank_make_batch_eqt", {T, sigma, norm, LABEL_DET, label_rows, det_fixed_window}, rows, B, x, y, stream);
 }
 
 int vp_bank_make_batch_aug(vp_bank* h, const vp_aug_row* rows, int B, int T, float sigma, int norm, const int* label_rows,
                            float* x, float* y, void* stream) {
-  VP_REQUIRE(h && x && y, "vp_bank_make_batch_aug: null argument");
-  return make_batch(*reinterpret_cast<Bank*>(h), rows, B, T, sigma, norm, label_rows, x, y, stream);
+  return make_batch(h, "vp_bank_make_batch_aug", {T, sigma, norm, LABEL_PSN, label_rows}, rows, B, x, y, stream);
 }
 
 int vp_bank_make_batch_eqt_aug(vp_bank* h, const vp_aug_row* rows, int B, int T, float sigma, int norm, const int* label_rows,
                                float det_fixed_window, float* x, float* y, void* stream) {
-  VP_REQUIRE(h && x && y, "vp_bank_make_batch_eqt_aug: null argument");
-  return make_batch_eqt(*reinterpret_cast<Bank*>(h), rows, B, T, sigma, norm, label_rows, det_fixed_window, x, y, stream);
+  return make_batch(h, "vp_bank_make_batch_eqt_aug", {T, sigma, norm, LABEL_DET, label_rows, det_fixed_window}, rows, B, x, y,
+                    stream);
 }
 
 }  // extern "C"

@@ -28,16 +28,13 @@ struct Passes {
   // probabilities, (B, 3, T) each, and the staging of its plan rows (and borders)
   Buf<float> x, y, pred;
   StagingRing ring;
-  struct {  // vp_validate_begin ... vp_validate_end: one loss per batch, one per window
-    bool open = false;
-    Buf<double> batch, window;
-    long long n_batches = 0, n_windows = 0;
-  } val;
-  struct {  // vp_validate_eqt_begin ... vp_validate_eqt_end: one loss per batch and per window, three head values per window
+  struct Validation {  // one loss per batch, one per window and -- EQTransformer's -- three head values per window
     bool open = false;
     Buf<double> batch, window, head;
     long long n_batches = 0, n_windows = 0;
-  } veq;
+  };
+  Validation val;  // vp_validate_begin ... vp_validate_end
+  Validation veq;  // vp_validate_eqt_begin ... vp_validate_eqt_end
   struct {  // vp_predict_begin ... vp_predict_end: one record per window
     bool open = false;
     Buf<vp_predict_record> rec;
@@ -127,35 +124,50 @@ int pass_batch(vp_handle* h, int B, bool labels, std::initializer_list<vp::Stagi
   return VP_OK;
 }
 
-// vp_validate_bank(_aug): generate, forward, loss of all B windows, results appended.
-template <class Row>
-int validate_batch(vp_handle* h, vp_bank* bank, const Row* rows, int B, float sigma, int norm, const int* label_rows, double eps,
-                   float* pred_out_dev, const char* who) {
-  VP_REQUIRE(h && bank, "%s: null argument", who);
-  if (h->net.model_kind != VP_MODEL_PHASENET) {
-    vp::set_error("%s: only a PhaseNet handle has a validation loss", who);
+// Which handles a pass over a bank is for and which call opens it.
+struct PassKind {
+  int model_kind;           // < 0: any
+  const char* unsupported;  // the message for another model kind, with %s for the caller
+  const char* begin;
+};
+const PassKind VALIDATION{VP_MODEL_PHASENET, "%s: only a PhaseNet handle has a validation loss", "vp_validate_begin"};
+const PassKind VALIDATION_EQT{VP_MODEL_EQTRANSFORMER,
+                              "%s: only an EQTransformer handle has this loss (vp_validate_bank is PhaseNet's)", "vp_validate_eqt_begin"};
+const PassKind PREDICTION{-1, nullptr, "vp_predict_begin"};
+const PassKind SWEEP{-1, nullptr, "vp_sweep_begin"};
+
+// What every *_bank call of a pass opens with: the handle, the bank and `others` given, the right model, the pass `state`
+// open, handle and bank on one device.  `who` is the caller, for the messages.
+template <class State>
+int bank_call_check(vp_handle* h, vp_bank* bank, bool others, const PassKind& kind, State vp::Passes::*state, const char* who) {
+  VP_REQUIRE(h && bank && others, "%s: null argument", who);
+  if (kind.model_kind >= 0 && h->net.model_kind != kind.model_kind) {
+    vp::set_error(kind.unsupported, who);
     return VP_ERR_UNSUPPORTED;
   }
-  auto& v = passes_of(h).val;
-  VP_REQUIRE(v.open, "%s: no pass is open (vp_validate_begin)", who);
+  VP_REQUIRE((passes_of(h).*state).open, "%s: no pass is open (%s)", who, kind.begin);
   const vp::Bank& bk = *reinterpret_cast<const vp::Bank*>(bank);
   VP_REQUIRE(bk.device == h->device, "%s: bank on device %d, handle on device %d", who, bk.device, h->device);
-  VP_REQUIRE(eps > 0.0, "%s: eps = %g must be > 0", who, eps);
-  const int T = h->net.in_samples;
-  int rc = vp::bank_check(bk, rows, B, T, sigma, norm, label_rows);
-  if (rc != VP_OK) return rc;
+  return VP_OK;
+}
+
+// A validation batch behind its checks: generate -> forward -> loss(pred, y, heads, per window, per batch) of all B windows,
+// the results appended to v (the three head values per window only with keep_heads).
+template <class Loss>
+int validation_batch(vp_handle* h, const vp::Bank& bk, vp::Passes::Validation& v, const vp::BatchSpec& spec, vp::BatchRows rows,
+                     int B, bool keep_heads, float* pred_out_dev, Loss loss) {
   VP_HIP(hipSetDevice(h->device));
-  rc = pass_batch(
-      h, B, true, {{rows, (size_t)B * sizeof(Row)}}, pred_out_dev,
+  const int rc = pass_batch(
+      h, B, true, {{rows.p, rows.bytes(B)}}, pred_out_dev,
       [&] {
-        const int r = grow_results(v.batch, (size_t)v.n_batches, (size_t)v.n_batches + 1, h->stream);
-        return r != VP_OK ? r : grow_results(v.window, (size_t)v.n_windows, (size_t)v.n_windows + B, h->stream);
+        int r = grow_results(v.batch, (size_t)v.n_batches, (size_t)v.n_batches + 1, h->stream);
+        if (r == VP_OK) r = grow_results(v.window, (size_t)v.n_windows, (size_t)v.n_windows + B, h->stream);
+        if (r == VP_OK && keep_heads) r = grow_results(v.head, (size_t)v.n_windows * 3, ((size_t)v.n_windows + B) * 3, h->stream);
+        return r;
       },
-      [&](const char* rows_dev, float* x, float* y) {
-        return vp::bank_launch(bk, reinterpret_cast<const Row*>(rows_dev), B, T, sigma, norm, label_rows, x, y, h->stream);
-      },
+      [&](const char* rows_dev, float* x, float* y) { return vp::bank_launch(bk, spec, rows.at(rows_dev), B, x, y, h->stream); },
       [&](const char*, const float* pred, const float* y) {
-        return vp::vce_launch(pred, y, B, 3, T, eps, v.window.p + v.n_windows, v.batch.p + v.n_batches, h->stream);
+        return loss(pred, y, keep_heads ? v.head.p + v.n_windows * 3 : nullptr, v.window.p + v.n_windows, v.batch.p + v.n_batches);
       });
   if (rc != VP_OK) return rc;
   ++v.n_batches;
@@ -163,62 +175,54 @@ int validate_batch(vp_handle* h, vp_bank* bank, const Row* rows, int B, float si
   return VP_OK;
 }
 
-// vp_validate_eqt_bank(_aug): generate -> forward -> the weighted BCE of all B windows, appended.
-template <class Row>
-int validate_eqt_batch(vp_handle* h, vp_bank* bank, const Row* rows, int B, float sigma, int norm, const int* label_rows,
-                       float det_fixed_window, const double* weights, float* pred_out_dev, const char* who) {
-  VP_REQUIRE(h && bank && weights, "%s: null argument", who);
-  if (h->net.model_kind != VP_MODEL_EQTRANSFORMER) {
-    vp::set_error("%s: only an EQTransformer handle has this loss (vp_validate_bank is PhaseNet's)", who);
-    return VP_ERR_UNSUPPORTED;
-  }
-  auto& v = passes_of(h).veq;
-  VP_REQUIRE(v.open, "%s: no pass is open (vp_validate_eqt_begin)", who);
-  const vp::Bank& bk = *reinterpret_cast<const vp::Bank*>(bank);
-  VP_REQUIRE(bk.device == h->device, "%s: bank on device %d, handle on device %d", who, bk.device, h->device);
-  const int T = h->net.in_samples;
-  int rc = vp::bank_check_eqt(bk, rows, B, T, sigma, norm, label_rows, det_fixed_window);
+// vp_validate_bank(_aug): the vector cross-entropy of all B windows.
+int validate_batch(vp_handle* h, vp_bank* bank, vp::BatchRows rows, int B, float sigma, int norm, const int* label_rows, double eps,
+                   float* pred_out_dev, const char* who) {
+  int rc = bank_call_check(h, bank, true, VALIDATION, &vp::Passes::val, who);
   if (rc != VP_OK) return rc;
+  VP_REQUIRE(eps > 0.0, "%s: eps = %g must be > 0", who, eps);
+  const vp::Bank& bk = *reinterpret_cast<const vp::Bank*>(bank);
+  const int T = h->net.in_samples;
+  const vp::BatchSpec spec{T, sigma, norm, vp::LABEL_PSN, label_rows};
+  if ((rc = vp::bank_check(bk, spec, rows, B)) != VP_OK) return rc;
+  return validation_batch(h, bk, passes_of(h).val, spec, rows, B, false, pred_out_dev,
+                          [&](const float* pred, const float* y, double*, double* window, double* batch) {
+                            return vp::vce_launch(pred, y, B, 3, T, eps, window, batch, h->stream);
+                          });
+}
+
+// vp_validate_eqt_bank(_aug): the weighted BCE of all B windows.
+int validate_eqt_batch(vp_handle* h, vp_bank* bank, vp::BatchRows rows, int B, float sigma, int norm, const int* label_rows,
+                       float det_fixed_window, const double* weights, float* pred_out_dev, const char* who) {
+  int rc = bank_call_check(h, bank, weights != nullptr, VALIDATION_EQT, &vp::Passes::veq, who);
+  if (rc != VP_OK) return rc;
+  const vp::Bank& bk = *reinterpret_cast<const vp::Bank*>(bank);
+  const int T = h->net.in_samples;
+  const vp::BatchSpec spec{T, sigma, norm, vp::LABEL_DET, label_rows, det_fixed_window};
+  if ((rc = vp::bank_check(bk, spec, rows, B)) != VP_OK) return rc;
   double row_weights[3];  // weights are (detection, P, S); the kernel takes them by row of y
   for (int i = 0; i < 3; ++i) {
     VP_REQUIRE(std::isfinite(weights[i]), "%s: weights[%d] = %g is not finite", who, i, weights[i]);
     row_weights[label_rows[i]] = weights[i];
   }
   VP_REQUIRE(h->net.n_out == 3, "%s: the model has %d outputs, the labels 3", who, h->net.n_out);
-  VP_HIP(hipSetDevice(h->device));
-  rc = pass_batch(
-      h, B, true, {{rows, (size_t)B * sizeof(Row)}}, pred_out_dev,
-      [&] {
-        int r = grow_results(v.batch, (size_t)v.n_batches, (size_t)v.n_batches + 1, h->stream);
-        if (r == VP_OK) r = grow_results(v.window, (size_t)v.n_windows, (size_t)v.n_windows + B, h->stream);
-        if (r == VP_OK) r = grow_results(v.head, (size_t)v.n_windows * 3, ((size_t)v.n_windows + B) * 3, h->stream);
-        return r;
-      },
-      [&](const char* rows_dev, float* x, float* y) {
-        return vp::bank_launch_eqt(bk, reinterpret_cast<const Row*>(rows_dev), B, T, sigma, norm, label_rows, det_fixed_window,
-                                   x, y, h->stream);
-      },
-      [&](const char*, const float* pred, const float* y) {
-        return vp::bce_launch(pred, y, B, 3, T, row_weights, v.head.p + v.n_windows * 3, v.window.p + v.n_windows,
-                              v.batch.p + v.n_batches, h->stream);
-      });
-  if (rc != VP_OK) return rc;
-  ++v.n_batches;
-  v.n_windows += B;
-  return VP_OK;
+  return validation_batch(h, bk, passes_of(h).veq, spec, rows, B, true, pred_out_dev,
+                          [&](const float* pred, const float* y, double* heads, double* window, double* batch) {
+                            return vp::bce_launch(pred, y, B, 3, T, row_weights, heads, window, batch, h->stream);
+                          });
 }
 
 // What vp_predict_bank and vp_sweep_bank stage and generate alike: the plan rows, then the B lower and the B upper borders
 // when there are any; the windows alone, no labels; and reduce(pred, lo_dev, hi_dev), the borders null when there are none.
 template <class Room, class Reduce>
-int window_batch(vp_handle* h, const vp::Bank& bk, const vp_plan_row* rows, const int32_t* lo, const int32_t* hi, int B, int norm,
-                 float* pred_out_dev, Room room_for_results, Reduce reduce) {
+int window_batch(vp_handle* h, const vp::Bank& bk, const vp::BatchSpec& spec, const vp_plan_row* rows, const int32_t* lo,
+                 const int32_t* hi, int B, float* pred_out_dev, Room room_for_results, Reduce reduce) {
   static_assert(sizeof(vp_plan_row) % alignof(int32_t) == 0, "the borders follow the rows in a ring slot");
   const size_t row_bytes = (size_t)B * sizeof(vp_plan_row), border_bytes = lo ? (size_t)B * sizeof(int32_t) : 0;
   return pass_batch(
       h, B, false, {{rows, row_bytes}, {lo, border_bytes}, {hi, border_bytes}}, pred_out_dev, room_for_results,
       [&](const char* rows_dev, float* x, float*) {
-        return vp::bank_launch_windows(bk, reinterpret_cast<const vp_plan_row*>(rows_dev), B, h->net.in_samples, norm, x, h->stream);
+        return vp::bank_launch(bk, spec, reinterpret_cast<const vp_plan_row*>(rows_dev), B, x, nullptr, h->stream);
       },
       [&](const char* rows_dev, const float* pred, const float*) {
         const int* d_lo = lo ? reinterpret_cast<const int*>(rows_dev + row_bytes) : nullptr;
@@ -269,6 +273,28 @@ int download_and_wait(vp_handle* h, std::initializer_list<Download> parts) {
   return VP_OK;
 }
 
+// vp_validate_end and vp_validate_eqt_end: the results of the pass `state` down, as many as the arrays hold, and the pass
+// closed.  `heads` is EQTransformer's; PhaseNet's call must be given per_window wherever it holds anything.
+int validation_end(vp_handle* h, vp::Passes::Validation vp::Passes::*state, const PassKind& kind, const char* who, double* batch_losses,
+                   long long cap, long long* n_batches, double* per_window, bool need_per_window, double* heads,
+                   long long cap_windows, long long* n_windows) {
+  VP_REQUIRE(h != nullptr, "%s: null handle", who);
+  auto& v = passes_of(h).*state;
+  VP_REQUIRE(v.open, "%s: no pass is open (%s)", who, kind.begin);
+  VP_REQUIRE(cap >= 0 && cap_windows >= 0 && (cap == 0 || batch_losses) && (!need_per_window || cap_windows == 0 || per_window),
+             "%s: null output arrays", who);
+  VP_HIP(hipSetDevice(h->device));
+  const long long nb = std::min(cap, v.n_batches), nw = std::min(cap_windows, v.n_windows);
+  const int rc = download_and_wait(h, {{nb > 0 ? batch_losses : nullptr, v.batch.p, (size_t)nb * sizeof(double)},
+                                       {nw > 0 ? per_window : nullptr, v.window.p, (size_t)nw * sizeof(double)},
+                                       {nw > 0 ? heads : nullptr, v.head.p, (size_t)nw * 3 * sizeof(double)}});
+  if (rc != VP_OK) return rc;
+  if (n_batches) *n_batches = v.n_batches;
+  if (n_windows) *n_windows = v.n_windows;
+  v.open = false;
+  return VP_OK;
+}
+
 void sweep_args(vp::SweepArgs& a, int B, int n_rows, int T, int p_row, int s_row, const float* thr_on, const float* thr_off,
                 int NT, int K) {
   a.B = B, a.n_rows = n_rows, a.T = T, a.p_row = p_row, a.s_row = s_row, a.NT = NT, a.K = K;
@@ -305,20 +331,8 @@ int vp_validate_bank_aug(vp_handle* h, vp_bank* bank, const vp_aug_row* rows, in
 
 int vp_validate_end(vp_handle* h, double* batch_losses, long long cap, long long* n_batches, double* per_window,
                     long long cap_windows, long long* n_windows) {
-  VP_REQUIRE(h != nullptr, "vp_validate_end: null handle");
-  auto& v = passes_of(h).val;
-  VP_REQUIRE(v.open, "vp_validate_end: no pass is open (vp_validate_begin)");
-  VP_REQUIRE(cap >= 0 && cap_windows >= 0 && (cap == 0 || batch_losses) && (cap_windows == 0 || per_window),
-             "vp_validate_end: null output arrays");
-  VP_HIP(hipSetDevice(h->device));
-  const long long nb = std::min(cap, v.n_batches), nw = std::min(cap_windows, v.n_windows);
-  const int rc = download_and_wait(h, {{nb > 0 ? batch_losses : nullptr, v.batch.p, (size_t)nb * sizeof(double)},
-                                       {nw > 0 ? per_window : nullptr, v.window.p, (size_t)nw * sizeof(double)}});
-  if (rc != VP_OK) return rc;
-  if (n_batches) *n_batches = v.n_batches;
-  if (n_windows) *n_windows = v.n_windows;
-  v.open = false;
-  return VP_OK;
+  return validation_end(h, &vp::Passes::val, VALIDATION, "vp_validate_end", batch_losses, cap, n_batches, per_window, true, nullptr,
+                        cap_windows, n_windows);
 }
 
 // ---- EQTransformer's validation loss: detection, P and S heads (bce.hip) ----------------------------------------------------
@@ -349,20 +363,8 @@ int vp_validate_eqt_bank_aug(vp_handle* h, vp_bank* bank, const vp_aug_row* rows
 
 int vp_validate_eqt_end(vp_handle* h, double* batch_losses, long long cap, long long* n_batches, double* per_window, double* heads,
                         long long cap_windows, long long* n_windows) {
-  VP_REQUIRE(h != nullptr, "vp_validate_eqt_end: null handle");
-  auto& v = passes_of(h).veq;
-  VP_REQUIRE(v.open, "vp_validate_eqt_end: no pass is open (vp_validate_eqt_begin)");
-  VP_REQUIRE(cap >= 0 && cap_windows >= 0 && (cap == 0 || batch_losses), "vp_validate_eqt_end: null output arrays");
-  VP_HIP(hipSetDevice(h->device));
-  const long long nb = std::min(cap, v.n_batches), nw = std::min(cap_windows, v.n_windows);
-  const int rc = download_and_wait(h, {{nb > 0 ? batch_losses : nullptr, v.batch.p, (size_t)nb * sizeof(double)},
-                                       {nw > 0 ? per_window : nullptr, v.window.p, (size_t)nw * sizeof(double)},
-                                       {nw > 0 ? heads : nullptr, v.head.p, (size_t)nw * 3 * sizeof(double)}});
-  if (rc != VP_OK) return rc;
-  if (n_batches) *n_batches = v.n_batches;
-  if (n_windows) *n_windows = v.n_windows;
-  v.open = false;
-  return VP_OK;
+  return validation_end(h, &vp::Passes::veq, VALIDATION_EQT, "vp_validate_eqt_end", batch_losses, cap, n_batches, per_window, false,
+                        heads, cap_windows, n_windows);
 }
 
 // ---- tasks 1-3: per-window records (predict.hip) ----------------------------------------------------------------------------
@@ -400,15 +402,16 @@ int vp_predict_begin(vp_handle* h) {
 // generate -> forward -> the records of all B windows, appended.
 int vp_predict_bank(vp_handle* h, vp_bank* bank, const vp_plan_row* rows, const int32_t* lo, const int32_t* hi, int B,
                     int norm, int det_row, int p_row, int s_row, float* pred_out_dev) {
-  VP_REQUIRE(h && bank, "vp_predict_bank: null argument");
+  int rc = bank_call_check(h, bank, true, PREDICTION, &vp::Passes::prd, "vp_predict_bank");
+  if (rc != VP_OK) return rc;
   auto& v = passes_of(h).prd;
-  VP_REQUIRE(v.open, "vp_predict_bank: no pass is open (vp_predict_begin)");
   const vp::Bank& bk = *reinterpret_cast<const vp::Bank*>(bank);
-  VP_REQUIRE(bk.device == h->device, "vp_predict_bank: bank on device %d, handle on device %d", bk.device, h->device);
   vp::Net& net = h->net;
   const int T = net.in_samples;
   const int det_mode = net.model_kind == VP_MODEL_PHASENET ? VP_DET_ONE_MINUS_NOISE : VP_DET_ROW;
-  int rc = vp::bank_check_windows(bk, rows, B, T, norm);
+  vp::BatchSpec spec;  // the windows alone, no labels
+  spec.T = T, spec.norm = norm;
+  rc = vp::bank_check(bk, spec, rows, B);
   if (rc == VP_OK) rc = vp::predict_check(B, net.n_out, T, det_row, p_row, s_row, det_mode, lo, hi, "vp_predict_bank");
   if (rc != VP_OK) return rc;
   VP_HIP(hipSetDevice(h->device));
@@ -417,7 +420,7 @@ int vp_predict_bank(vp_handle* h, vp_bank* bank, const vp_plan_row* rows, const 
   a.B = B, a.n_rows = net.n_out, a.T = T;
   a.det_row = det_row, a.p_row = p_row, a.s_row = s_row, a.det_mode = det_mode;
   rc = window_batch(
-      h, bk, rows, lo, hi, B, norm, pred_out_dev,
+      h, bk, spec, rows, lo, hi, B, pred_out_dev,
       [&] { return grow_results(v.rec, (size_t)v.n_windows, (size_t)v.n_windows + B, h->stream); },
       [&](const float* pred, const int* d_lo, const int* d_hi) {
         a.prob = pred, a.lo = d_lo, a.hi = d_hi;
@@ -486,14 +489,15 @@ int vp_sweep_begin(vp_handle* h, const float* thr_on, const float* thr_off, int 
 // generate -> forward -> the picks of all B windows at every threshold, appended.
 int vp_sweep_bank(vp_handle* h, vp_bank* bank, const vp_plan_row* rows, const int32_t* lo, const int32_t* hi, int B, int norm,
                   int p_row, int s_row, float* pred_out_dev) {
-  VP_REQUIRE(h && bank, "vp_sweep_bank: null argument");
+  int rc = bank_call_check(h, bank, true, SWEEP, &vp::Passes::swp, "vp_sweep_bank");
+  if (rc != VP_OK) return rc;
   auto& v = passes_of(h).swp;
-  VP_REQUIRE(v.open, "vp_sweep_bank: no pass is open (vp_sweep_begin)");
   const vp::Bank& bk = *reinterpret_cast<const vp::Bank*>(bank);
-  VP_REQUIRE(bk.device == h->device, "vp_sweep_bank: bank on device %d, handle on device %d", bk.device, h->device);
   vp::Net& net = h->net;
   const int T = net.in_samples;
-  int rc = vp::bank_check_windows(bk, rows, B, T, norm);
+  vp::BatchSpec spec;  // the windows alone, no labels
+  spec.T = T, spec.norm = norm;
+  rc = vp::bank_check(bk, spec, rows, B);
   if (rc == VP_OK) rc = vp::sweep_check(B, net.n_out, T, p_row, s_row, lo, hi, v.thr_on, v.thr_off, v.NT, v.K, "vp_sweep_bank");
   if (rc != VP_OK) return rc;
   VP_HIP(hipSetDevice(h->device));
@@ -501,7 +505,7 @@ int vp_sweep_bank(vp_handle* h, vp_bank* bank, const vp_plan_row* rows, const in
   vp::SweepArgs a{};
   sweep_args(a, B, net.n_out, T, p_row, s_row, v.thr_on, v.thr_off, v.NT, v.K);
   rc = window_batch(
-      h, bk, rows, lo, hi, B, norm, pred_out_dev,
+      h, bk, spec, rows, lo, hi, B, pred_out_dev,
       [&] {
         int r = grow_results(v.count, nw * per_cnt, (nw + B) * per_cnt, h->stream);
         if (r == VP_OK) r = grow_results(v.peak, nw * per_pk, (nw + B) * per_pk, h->stream);

@@ -942,13 +942,14 @@ int step_and_loss(Trainer& tr, const float* x_dev, const float* y_dev, int B, fl
   return VP_OK;
 }
 
-// vp_train_step_bank(_aug): exactly one of rows / aug is set.
-int step_bank(Trainer& tr, const Bank& bk, const vp_plan_row* rows, const vp_aug_row* aug, int B, float sigma, int norm,
-              const int* label_rows, float lr, int update, double* loss) {
+// vp_train_step_bank(_aug): the batch of `rows` generated into the trainer's input buffers, then the step.
+int step_bank(Trainer& tr, const Bank& bk, BatchRows rows, int B, float sigma, int norm, const int* label_rows, float lr,
+              int update, double* loss) {
   VP_REQUIRE(B >= 2 && B <= tr.max_batch, "vp_train_step_bank: batch %d outside [2, %d]", B, tr.max_batch);
   VP_REQUIRE(bk.device == tr.device, "vp_train_step_bank: bank on device %d, trainer on device %d", bk.device, tr.device);
   static_assert(RowRing::N == Trainer::EV_RING, "one plan-row slot per step event");
-  int rc = aug ? bank_check(bk, aug, B, T0, sigma, norm, label_rows) : bank_check(bk, rows, B, T0, sigma, norm, label_rows);
+  const BatchSpec spec{T0, sigma, norm, LABEL_PSN, label_rows};
+  int rc = bank_check(bk, spec, rows, B);
   if (rc != VP_OK) return rc;
   VP_HIP(hipSetDevice(tr.device));
   if (!tr.plan_rows.cap) {  // once, for either kind of row: a regrowth would have to wait for every slot
@@ -959,14 +960,9 @@ int step_bank(Trainer& tr, const Bank& bk, const vp_plan_row* rows, const vp_aug
   // that read the slot's device copy, which ran after the copy that read the host slot
   const int slot = (int)(tr.seq % Trainer::EV_RING);
   if (tr.ev_inputs_seq[slot] >= 0) VP_HIP(hipEventSynchronize(tr.ev_inputs[slot]));
-  const void* rd = aug ? tr.plan_rows.stage(slot, {{aug, (size_t)B * sizeof(vp_aug_row)}}, tr.stream)
-                       : tr.plan_rows.stage(slot, {{rows, (size_t)B * sizeof(vp_plan_row)}}, tr.stream);
+  const void* rd = tr.plan_rows.stage(slot, {{rows.p, rows.bytes(B)}}, tr.stream);
   if (!rd) return VP_ERR_HIP;
-  rc = aug ? bank_launch(bk, static_cast<const vp_aug_row*>(rd), B, T0, sigma, norm, label_rows, tr.x_dev, tr.y_dev,
-                             tr.stream)
-           : bank_launch(bk, static_cast<const vp_plan_row*>(rd), B, T0, sigma, norm, label_rows, tr.x_dev, tr.y_dev,
-                         tr.stream);
-  if (rc != VP_OK) return rc;
+  if ((rc = bank_launch(bk, spec, rows.at(rd), B, tr.x_dev, tr.y_dev, tr.stream)) != VP_OK) return rc;
   return step_and_loss(tr, tr.x_dev, tr.y_dev, B, lr, update, loss);
 }
 
@@ -1058,14 +1054,14 @@ int vp_train_step(vp_trainer* h, const float* x, const float* y, int mem, int B,
 int vp_train_step_bank(vp_trainer* h, vp_bank* bank, const vp_plan_row* rows, int B, float sigma, int norm,
                        const int* label_rows, float lr, int update, double* loss) {
   VP_REQUIRE(h && bank, "vp_train_step_bank: null argument");
-  return step_bank(*reinterpret_cast<Trainer*>(h), *reinterpret_cast<const Bank*>(bank), rows, nullptr, B, sigma, norm,
+  return step_bank(*reinterpret_cast<Trainer*>(h), *reinterpret_cast<const Bank*>(bank), rows, B, sigma, norm,
                    label_rows, lr, update, loss);
 }
 
 int vp_train_step_bank_aug(vp_trainer* h, vp_bank* bank, const vp_aug_row* rows, int B, float sigma, int norm,
                            const int* label_rows, float lr, int update, double* loss) {
   VP_REQUIRE(h && bank, "vp_train_step_bank_aug: null argument");
-  return step_bank(*reinterpret_cast<Trainer*>(h), *reinterpret_cast<const Bank*>(bank), nullptr, rows, B, sigma, norm,
+  return step_bank(*reinterpret_cast<Trainer*>(h), *reinterpret_cast<const Bank*>(bank), rows, B, sigma, norm,
                    label_rows, lr, update, loss);
 }
 

@@ -311,60 +311,48 @@ class WaveformBank:
         order detection, P, S (``vp_bank_make_batch_eqt``; plan rows only -- augmented rows go to
         :meth:`make_batch_eqt_aug`).  ``detection_fixed_window``: the detection's
         length in samples from P, ``None`` = to behind S (the module's ``DETECTION_*`` constants)."""
-        import torch
-
         aug = getattr(rows, "dtype", None) == AUG_ROW
-        T = int(model.in_samples)
-        dev = torch.device("cuda", self.device)
-        stream = torch.cuda.current_stream(dev).cuda_stream
         if has_detection_row(model.labels):
             if aug:
                 raise ValueError("augmented rows with an EQTransformer model: make_batch executes block 1 alone for it; "
                                  "its stacked recipe is WaveformBank.make_batch_eqt_aug (EQTransformerLit.make_batch)")
-            detection_label_rows(model.labels)  # (the model's labels are what the batch is laid out for)
-            rows = as_rows(rows)
-            x = torch.empty((len(rows), 3, T), dtype=torch.float32, device=dev)
-            y = torch.empty_like(x)
-            lr_ = np.array([0, 1, 2], np.int32)
-            _lib.check(self._lib.vp_bank_make_batch_eqt(
-                self._h, rows.ctypes.data_as(C.c_void_p), len(rows), T, float(sigma), _norm(model.norm),
-                lr_.ctypes.data_as(C.POINTER(C.c_int)), _fixed_window(detection_fixed_window), C.c_void_p(x.data_ptr()),
-                C.c_void_p(y.data_ptr()), C.c_void_p(stream)), "vp_bank_make_batch_eqt")
-            return {"X": x, "y": y[:, 1:3], "detections": y[:, 0:1]}
-        if detection_fixed_window is not None:
+        elif detection_fixed_window is not None:
             raise ValueError("detection_fixed_window: the model has no detection row")
-        rows = as_aug_rows(rows) if aug else as_rows(rows)
-        name = "vp_bank_make_batch_aug" if aug else "vp_bank_make_batch"
-        x = torch.empty((len(rows), 3, T), dtype=torch.float32, device=dev)
-        y = torch.empty_like(x)
-        lr_ = label_rows(model.labels)
-        _lib.check(getattr(self._lib, name)(self._h, rows.ctypes.data_as(C.c_void_p), len(rows), T, float(sigma),
-                                            _norm(model.norm), lr_.ctypes.data_as(C.POINTER(C.c_int)),
-                                            C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(stream)), name)
-        return {"X": x, "y": y}
+        return self._make(rows, model, sigma, detection_fixed_window)
 
     def make_batch_eqt_aug(self, rows, model, sigma, detection_fixed_window=None):
         """EQTransformer's stacked recipe (``vp_bank_make_batch_eqt_aug``) on augmented rows (``AUG_ROW``, from
         ``EQTransformerLit.augmented_planner``): ``{"X": (B, 3, T), "y": (B, 2, T), "detections": (B, 1, T)}`` on torch's
         current stream, ``y`` and ``detections`` views of one (B, 3, T) tensor in the order detection, P, S, as
         :meth:`make_batch` returns them for plan rows.  ``model`` must have a detection row."""
-        import torch
-
         if not has_detection_row(model.labels):
             raise ValueError("make_batch_eqt_aug: the model has no detection row (make_batch takes its augmented rows)")
         detection_label_rows(model.labels)
-        rows = as_aug_rows(rows)
-        T = int(model.in_samples)
+        return self._make(as_aug_rows(rows), model, sigma, detection_fixed_window)
+
+    def _make(self, rows, model, sigma, detection_fixed_window):
+        """The batch of ``rows`` for ``model`` by one of the four ``vp_bank_make_batch*``: ``_aug`` for augmented rows,
+        ``_eqt`` (with the detection window, the rows of y in the order detection, P, S) for a model with a detection row."""
+        import torch
+
+        aug = getattr(rows, "dtype", None) == AUG_ROW
+        det = has_detection_row(model.labels)
+        if det:
+            detection_label_rows(model.labels)  # (the model's labels are what the batch is laid out for)
+        rows = as_aug_rows(rows) if aug else as_rows(rows)
+        name = "vp_bank_make_batch" + ("_eqt" if det else "") + ("_aug" if aug else "")
+        if det:
+            lr_, tail = np.array([0, 1, 2], np.int32), (_fixed_window(detection_fixed_window),)
+        else:
+            lr_, tail = label_rows(model.labels), ()
         dev = torch.device("cuda", self.device)
         stream = torch.cuda.current_stream(dev).cuda_stream
-        x = torch.empty((len(rows), 3, T), dtype=torch.float32, device=dev)
+        x = torch.empty((len(rows), 3, int(model.in_samples)), dtype=torch.float32, device=dev)
         y = torch.empty_like(x)
-        lr_ = np.array([0, 1, 2], np.int32)
-        _lib.check(self._lib.vp_bank_make_batch_eqt_aug(
-            self._h, rows.ctypes.data_as(C.c_void_p), len(rows), T, float(sigma), _norm(model.norm),
-            lr_.ctypes.data_as(C.POINTER(C.c_int)), _fixed_window(detection_fixed_window), C.c_void_p(x.data_ptr()),
-            C.c_void_p(y.data_ptr()), C.c_void_p(stream)), "vp_bank_make_batch_eqt_aug")
-        return {"X": x, "y": y[:, 1:3], "detections": y[:, 0:1]}
+        _lib.check(getattr(self._lib, name)(self._h, rows.ctypes.data_as(C.c_void_p), len(rows), int(model.in_samples),
+                                            float(sigma), _norm(model.norm), lr_.ctypes.data_as(C.POINTER(C.c_int)), *tail,
+                                            C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(stream)), name)
+        return {"X": x, "y": y[:, 1:3], "detections": y[:, 0:1]} if det else {"X": x, "y": y}
 
     @property
     def handle(self):

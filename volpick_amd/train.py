@@ -349,36 +349,49 @@ def validate_batches(model, bank, batches, sigma, eps=1e-5, predictions=False):
     with ``vector_cross_entropy`` in float64 on the device; the host waits once, at the end.  Returns
     ``(batch_losses, window_losses)``: a float64 array with one loss per batch and one with one per window, in order;
     with ``predictions=True`` also the list of the batches' (B, 3, T) predictions (CUDA tensors)."""
+    from .generate import label_rows
+
+    lrows = label_rows(model.labels)
+    batch, window, _, preds = _validation_pass(model, bank, batches, "vp_validate", lrows, sigma, (float(eps),), False, predictions)
+    return (batch, window, preds) if predictions else (batch, window)
+
+
+def _validation_pass(model, bank, batches, prefix, lrows, sigma, tail, with_heads, predictions):
+    """``<prefix>_begin``, ``<prefix>_bank`` or ``<prefix>_bank_aug`` per element of ``batches`` (by the rows' dtype; ``tail``:
+    the call's arguments between ``label_rows`` and ``pred_out_dev``), ``<prefix>_end``.  Returns ``(batch_losses,
+    window_losses, head_values or None, predictions)``, the head values (n_windows, 3) by row of y."""
     from .evaluate import prediction_tensor
-    from .generate import AUG_ROW, as_aug_rows, as_rows, label_rows, _norm
+    from .generate import AUG_ROW, as_aug_rows, as_rows, _norm
 
     lib = _lib.load()
     if model._device_index is None:
         model.cuda(bank.device)
     h = model._ensure_handle()
-    lrows = label_rows(model.labels).ctypes.data_as(C.POINTER(C.c_int))
     preds, n_windows, n_batches = [], 0, 0
-    _lib.check(lib.vp_validate_begin(h), "vp_validate_begin")
+    _lib.check(getattr(lib, prefix + "_begin")(h), prefix + "_begin")
     try:
         for rows in batches:
             aug = getattr(rows, "dtype", None) == AUG_ROW
             rows = as_aug_rows(rows) if aug else as_rows(rows)
-            name = "vp_validate_bank_aug" if aug else "vp_validate_bank"
+            name = prefix + ("_bank_aug" if aug else "_bank")
             if predictions:
                 preds.append(prediction_tensor(model, len(rows)))
-            _lib.check(getattr(lib, name)(h, bank.handle, _lib.ptr(rows), len(rows), float(sigma), _norm(model.norm), lrows,
-                                          float(eps), C.c_void_p(preds[-1].data_ptr()) if predictions else None), name)
+            _lib.check(getattr(lib, name)(h, bank.handle, _lib.ptr(rows), len(rows), float(sigma), _norm(model.norm),
+                                          lrows.ctypes.data_as(C.POINTER(C.c_int)), *tail,
+                                          C.c_void_p(preds[-1].data_ptr()) if predictions else None), name)
             n_batches += 1
             n_windows += len(rows)
     finally:
         batch = np.empty(n_batches, np.float64)
         window = np.empty(n_windows, np.float64)
+        heads = np.empty((n_windows, 3), np.float64) if with_heads else None
         nb, nw = C.c_longlong(), C.c_longlong()
-        rc = lib.vp_validate_end(h, batch.ctypes.data_as(C.POINTER(C.c_double)), n_batches, C.byref(nb),
-                                 window.ctypes.data_as(C.POINTER(C.c_double)), n_windows, C.byref(nw))
-    _lib.check(rc, "vp_validate_end")
+        dp = C.POINTER(C.c_double)
+        rc = getattr(lib, prefix + "_end")(h, batch.ctypes.data_as(dp), n_batches, C.byref(nb), window.ctypes.data_as(dp),
+                                           *((heads.ctypes.data_as(dp),) if with_heads else ()), n_windows, C.byref(nw))
+    _lib.check(rc, prefix + "_end")
     assert (nb.value, nw.value) == (n_batches, n_windows)
-    return (batch, window, preds) if predictions else (batch, window)
+    return batch, window, heads, preds
 
 
 class PhaseNetLit:
@@ -581,43 +594,14 @@ def validate_batches_eqt(model, bank, batches, sigma, loss_weights=EQT_LOSS_WEIG
     waits once, at the end.  Returns ``(batch_losses, window_losses, head_losses)``: float64 arrays with one loss per batch,
     one per window and the unweighted (detection, P, S) values per window, (n_windows, 3); with ``predictions=True`` also the
     list of the batches' (B, 3, T) predictions (CUDA tensors)."""
-    from .evaluate import prediction_tensor
-    from .generate import AUG_ROW, as_aug_rows, as_rows, detection_label_rows, _fixed_window, _norm
+    from .generate import detection_label_rows, _fixed_window
 
-    lib = _lib.load()
-    if model._device_index is None:
-        model.cuda(bank.device)
-    h = model._ensure_handle()
     lrows = detection_label_rows(model.labels)
     w = np.ascontiguousarray(loss_weights, np.float64)
     if w.shape != (3,):
         raise ValueError(f"loss_weights: three weights (detection, P, S), got {loss_weights!r}")
-    fixed = _fixed_window(detection_fixed_window)
-    preds, n_windows, n_batches = [], 0, 0
-    _lib.check(lib.vp_validate_eqt_begin(h), "vp_validate_eqt_begin")
-    try:
-        for rows in batches:
-            aug = getattr(rows, "dtype", None) == AUG_ROW
-            rows = as_aug_rows(rows) if aug else as_rows(rows)
-            name = "vp_validate_eqt_bank_aug" if aug else "vp_validate_eqt_bank"
-            if predictions:
-                preds.append(prediction_tensor(model, len(rows)))
-            _lib.check(getattr(lib, name)(h, bank.handle, _lib.ptr(rows), len(rows), float(sigma), _norm(model.norm),
-                                          lrows.ctypes.data_as(C.POINTER(C.c_int)), fixed,
-                                          w.ctypes.data_as(C.POINTER(C.c_double)),
-                                          C.c_void_p(preds[-1].data_ptr()) if predictions else None), name)
-            n_batches += 1
-            n_windows += len(rows)
-    finally:
-        batch = np.empty(n_batches, np.float64)
-        window = np.empty(n_windows, np.float64)
-        heads = np.empty((n_windows, 3), np.float64)
-        nb, nw = C.c_longlong(), C.c_longlong()
-        dp = C.POINTER(C.c_double)
-        rc = lib.vp_validate_eqt_end(h, batch.ctypes.data_as(dp), n_batches, C.byref(nb), window.ctypes.data_as(dp),
-                                     heads.ctypes.data_as(dp), n_windows, C.byref(nw))
-    _lib.check(rc, "vp_validate_eqt_end")
-    assert (nb.value, nw.value) == (n_batches, n_windows)
+    tail = (_fixed_window(detection_fixed_window), w.ctypes.data_as(C.POINTER(C.c_double)))
+    batch, window, heads, preds = _validation_pass(model, bank, batches, "vp_validate_eqt", lrows, sigma, tail, True, predictions)
     heads = heads[:, lrows]  # by row of y -> (detection, P, S)
     return (batch, window, heads, preds) if predictions else (batch, window, heads)
 
