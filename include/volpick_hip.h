@@ -510,6 +510,11 @@ int vp_train_create_dtype(int device_id, int model_kind, const float* weights, s
                           vp_trainer** out);
 int vp_train_dtype(const vp_trainer* t); /* VP_TRAIN_FP32 / VP_TRAIN_BF16 */
 int vp_train_destroy(vp_trainer* t);
+/* Adam's betas and eps, the BatchNorm momentum and the eps of log(p + eps) (defaults 0.9, 0.999, 1e-8, 0.1, 1e-5), in force
+ * from the next vp_train_step.  VP_ERR_INVALID, with the previous five still in force, unless 0 <= beta1, beta2 < 1 (the
+ * update divides by 1 - beta^t), adam_eps and loss_eps are finite and > 0, and 0 < bn_momentum <= 1; a NaN fails each of
+ * these.  The update count t is the number of vp_train_step calls with update != 0: a step with update == 0 leaves the
+ * weights, both moments, t and the EMA alone and still moves the BatchNorm running statistics. */
 int vp_train_set_hyper(vp_trainer* t, float beta1, float beta2, float adam_eps, float bn_momentum, float loss_eps);
 /* Optional exponential moving average of the weights after every update (the reference's EMA callback,
  * volpick/model/train.py:153-176: decay 0.999, every step); starts at the current weights. */
@@ -528,6 +533,11 @@ int vp_train_wait_inputs_consumed(vp_trainer* t, void* stream);
 long long vp_train_inputs_consumed_upto(vp_trainer* t);
 long long vp_train_steps_enqueued(const vp_trainer* t);  /* the step a vp_train_step call just queued has the number (this - 1) */
 int vp_train_read(vp_trainer* t, int which, float* out, size_t n_floats);
+/* Replaces the whole flat blob (host pointer, the layout of vp_train_create: weights AND BatchNorm running statistics) once
+ * the queued steps have finished.  Nothing else moves: the Adam moments, the update count t, the hyper-parameters and the
+ * EMA stay what they were.  The next step therefore computes, bit for bit, what a new trainer created from the blob
+ * computes for the same batch (loss, gradients, stored tensors, running statistics), and the next update continues Adam
+ * from the old moments with t + 1.  A caller that wants a fresh optimiser creates a new trainer. */
 int vp_train_write_weights(vp_trainer* t, const float* weights, size_t n_floats);
 int vp_train_predictions(vp_trainer* t, float* out, int B);
 /* Debug / parity tests: the z, a, gz, ga tensors of the last step as dense (B, C, L) arrays. */

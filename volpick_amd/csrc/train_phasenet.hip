@@ -17,6 +17,7 @@
 // (WgradQueue), and the C entry points.
 #include <hip/hip_ext.h>
 
+#include <cmath>
 #include <memory>
 
 #include "batchgen.h"
@@ -1012,6 +1013,12 @@ int vp_train_destroy(vp_trainer* h) {
 
 int vp_train_set_hyper(vp_trainer* h, float beta1, float beta2, float adam_eps, float bn_momentum, float loss_eps) {
   VP_REQUIRE(h, "vp_train_set_hyper: null handle");
+  // (every comparison is false for a NaN; nothing is stored before all five have passed)
+  VP_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f,
+             "vp_train_set_hyper: beta1 %g, beta2 %g outside [0, 1) (1 - beta^t divides the step)", (double)beta1, (double)beta2);
+  VP_REQUIRE(adam_eps > 0.f && std::isfinite(adam_eps), "vp_train_set_hyper: adam_eps %g is not finite and positive", (double)adam_eps);
+  VP_REQUIRE(bn_momentum > 0.f && bn_momentum <= 1.f, "vp_train_set_hyper: bn_momentum %g outside (0, 1]", (double)bn_momentum);
+  VP_REQUIRE(loss_eps > 0.f && std::isfinite(loss_eps), "vp_train_set_hyper: loss_eps %g is not finite and positive", (double)loss_eps);
   Trainer& tr = *reinterpret_cast<Trainer*>(h);
   tr.beta1 = beta1;
   tr.beta2 = beta2;

@@ -109,7 +109,11 @@ class PhaseNetTrainer:
         w = np.ascontiguousarray(model._weights, dtype=np.float32)
         _lib.check(self._lib.vp_train_create_dtype(int(device), _lib.VP_MODEL_PHASENET, _lib.ptr(w), w.size,
                                                    self.max_batch, self.DTYPES[str(dtype)], C.byref(self._h)), "vp_train_create")
-        _lib.check(self._lib.vp_train_set_hyper(self._h, betas[0], betas[1], eps, bn_momentum, loss_eps))
+        try:
+            _lib.check(self._lib.vp_train_set_hyper(self._h, betas[0], betas[1], eps, bn_momentum, loss_eps), "vp_train_set_hyper")
+        except Exception:
+            self.close()  # the handle exists already: release it with the refusal
+            raise
         self.global_step = 0
         self._in_flight = collections.deque()  # (number of a queued step, its x, its y): device inputs kept alive
 
@@ -244,6 +248,14 @@ class PhaseNetTrainer:
 
     def gradients(self):
         return self._named(self._read(1))
+
+    def write_weights(self, blob):
+        """Replace the flat weight blob (weights and BatchNorm running statistics, the layout of ``model._weights``).  The Adam
+        moments, the update count and the EMA stay as they are (``vp_train_write_weights``)."""
+        blob = np.ascontiguousarray(blob, dtype=np.float32)
+        if blob.shape != (self.n_params,):
+            raise ValueError(f"expected a flat blob of {self.n_params} floats, got shape {blob.shape}")
+        _lib.check(self._lib.vp_train_write_weights(self._h, _lib.ptr(blob), blob.size), "vp_train_write_weights")
 
     def enable_ema(self, decay=0.999):
         """Exponential moving average of the weights after every update (train.py:153-176 of the reference)."""
