@@ -69,13 +69,15 @@ typedef struct {
                                  [2]: PhaseNet: (1 = hand-pipelined K loop in the MFMA layers: removed in round 6, rejected);
                                       EQTransformer: 1 = the three
                                       BiLSTM blocks, two transformer blocks and the pick branches as six launches instead
-                                      of the one-launch middle kernel, 2 = eqt_mid_kernel with one window per 512-thread
-                                      workgroup, 3 = with two windows per 1024-thread workgroup (teams of eight waves: the
-                                      default of rounds 3-5); default: eqt_mid4_kernel, FOUR windows per 1024-thread
-                                      workgroup in teams of four waves, so that a batch of 256 holds 64 CUs and leaves the
-                                      rest to the kernels of the other device contexts (all three bit-identical);
-                                 [3]: 1 = the tiled level-0 up kernel of the three-launch plans with one workgroup per tile
-                                      (A/B; 2, the persistent down kernel, was removed in round 6); 64 = PhaseNet's one-launch plan
+                                      of the one-launch middle kernel (the independent reference: scalar FMA chains),
+                                      2 = the one-launch kernel with ONE window per 256-thread workgroup (the bit reference
+                                      of the tests); default: eqt_mid4_kernel, FOUR windows per 1024-thread workgroup in
+                                      teams of four waves, so that a batch of 256 holds 64 CUs and leaves the rest to the
+                                      kernels of the other device contexts (bit-identical to 2); (3, two windows per
+                                      workgroup in teams of eight waves, was removed and is rejected);
+                                 [3]: PhaseNet: 1 = the tiled level-0 up kernel of the three-launch plans with one workgroup
+                                      per tile (A/B; 2, the persistent down kernel, was removed in round 6); EQTransformer:
+                                      (1, half-width tiles for decoder stages 3-6, was removed and is rejected); 64 = PhaseNet's one-launch plan
                                       WITHOUT the first-come-first-served gate between the device contexts' forward
                                       launches (A/B: csrc/api.hip ForwardGate);
                                  [4]: 1 = no L2 warm-up of the weight streams;
@@ -108,12 +110,11 @@ typedef struct {
                                       blind the output (default: only the tiles that hold kept samples),
                                       bit11 = stage 3 of the fused decoder 0-3 kernel shares its n-tiles evenly between
                                       the two waves of a SIMD (default: 14 + 10),
-                                      bit13 = the bf16-piece ResCNN kernel with four waves per window and TWO windows per
-                                      512-thread workgroup (the default of rounds 5-6; default now: eqt_res3t_kernel, eight
-                                      waves per THREE windows, a wave taking 16 output channels of five or four of the nine
-                                      n-tiles; the three forms are bit-identical),
+                                      (default ResCNN kernel: eqt_res3t_kernel, eight waves per THREE windows, a wave taking 16
+                                      output channels of five or four of the nine n-tiles; bit-identical to bit9),
                                       (bit12, the bf16-piece ResCNN kernel with eight waves per window and K split over
-                                      wave pairs, was removed in round 6 and is rejected) */
+                                      wave pairs, was removed in round 6 and is rejected; so is bit13, the same kernel as
+                                      bit9 with TWO windows per 512-thread workgroup) */
   int32_t reserved[4];        /* must be 0 */
 } vp_config;
 

@@ -3,7 +3,7 @@ tests/test_gpu_parity_wide.py runs each, tools/plan_table.py and tests/test_gpu_
 PLAN_SELECTORS = {
     "phasenet": [(1,), (0, 1), (0, 0, 0, 1), (0, 0, 0, 0, 1), (0, 0, 0, 0, 0, 1), (0, 0, 0, 0, 0, 2),
                  (0, 0, 0, 0, 0, 3), (0, 0, 0, 0, 0, 8), (0, 0, 0, 0, 0, 0, 1), (0, 4)],
-    "eqtransformer": [(1,), (0, 0, 1), (0, 0, 2), (0, 0, 3), (0, 0, 0, 0, 1), (0, 0, 0, 0, 0, 0, 2)] +
+    "eqtransformer": [(1,), (0, 0, 1), (0, 0, 2), (0, 0, 0, 0, 1), (0, 0, 0, 0, 0, 0, 2)] +
                      [(0, 0, 0, 0, 0, 0, 0, 1 << b) for b in range(12)] + [(0, 0, 0, 0, 0, 0, 0, 0x1F0), (0, 0, 0, 0, 0, 0, 0, 0xF)] +
                      [(0, 4), (0, 4, 0, 0, 0, 0, 0, 1024)],
 }

@@ -248,7 +248,15 @@ def test_regression_bar_full_batch(default_pair):
 # A/B forms that round 6 removed: the library says so instead of running something else
 REMOVED_SELECTORS = {
     "phasenet": [(0, 0, 1), (0, 0, 0, 2), (0, 0, 0, 0, 0, 4), (0, 0, 0, 0, 0, 5), (0, 0, 0, 0, 0, 6), (0, 0, 0, 0, 0, 7), (0, 0, 0, 0, 0, 9)],
-    "eqtransformer": [(0, 0, 0, 0, 0, 0, 0, 4096)],
+    "eqtransformer": [(0, 0, 0, 0, 0, 0, 0, 4096), (0, 0, 3), (0, 0, 0, 1), (0, 0, 0, 0, 0, 0, 0, 8192)],
+}
+# what the error of a selector removed since then says; every other one says "removed in round 6"
+REMOVED_MATCH = {
+    ("eqtransformer", (0, 0, 3)): r"plan_flags\[2\] = 3 \(middle kernel with two windows per workgroup in teams of eight waves\): removed; "
+                                  r"the default runs four windows per workgroup in teams of four waves, plan_flags\[2\] = 2 the same kernel with one",
+    ("eqtransformer", (0, 0, 0, 1)): r"plan_flags\[3\] = 1 \(half-width decoder tiles\): removed; decoder.3 .. .6 run on the full-width tiles",
+    ("eqtransformer", (0, 0, 0, 0, 0, 0, 0, 8192)): r"plan_flags\[7\] bit 13 \(ResCNN kernel with two windows per workgroup\): removed; "
+                                                    r"the default runs three windows per workgroup \(eqt_res3t_kernel\), bit 9 one",
 }
 
 
@@ -259,7 +267,7 @@ def test_removed_plan_selectors_are_rejected(name, flags):
 
     m = MODELS[name].from_pretrained("volpick")
     m._plan_flags = flags
-    with pytest.raises(VolpickHipError, match="removed in round 6"):
+    with pytest.raises(VolpickHipError, match=REMOVED_MATCH.get((name, flags), "removed in round 6")):
         m.cuda()
         m(torch.zeros((1, 3, m.in_samples)).cuda())
 

@@ -1,4 +1,4 @@
-// One LSTM direction (H = 16, T = 47) on ONE wavefront: what a recurrent step of eqt_mid_kernel costs, per form of the
+// One LSTM direction (H = 16, T = 47) on ONE wavefront: what a recurrent step of eqt_mid4_kernel costs, per form of the
 // step.  Lane l = 4 * unit + gate (i, f, g, o) owns gate row (gate, unit) of W_hh (16 weights as 8 register pairs); gx[t][l] is
 // the input projection of the step, already scaled for v_exp_f32 (rows i, f, o by -log2 e, row g by -2 log2 e).
 //   0  the step as eqt_kernels.hip lstm_recur<GS, SCALED = true> has it (C++ with one DPP asm block)

@@ -20,7 +20,7 @@ RANGES = [(0, 0), (500, 5500), (250, 5750)]
 
 
 def selectors():
-    return [()] + list(PLAN_SELECTORS["eqtransformer"]) + [(0, 0, 0, 0, 0, 0, 0, 8192)]
+    return [()] + list(PLAN_SELECTORS["eqtransformer"])
 
 
 def key(flags):

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Cycles per phase of the fused ResCNN kernel (eqt_res3t_kernel; eqt_res3_kernel with VOLPICK_PLAN_FLAGS=0,0,0,0,0,0,0,8192):
+"""Cycles per phase of the fused ResCNN kernel (eqt_res3t_kernel; eqt_res3_kernel with VOLPICK_PLAN_FLAGS=0,0,0,0,0,0,0,512):
 debug plan flag bit 1 = shader-clock stamps of workgroup 0 (a -DR3_CLOCK=1 build of the library, VOLPICK_HIP_LIB).
 `res3_clock.py waves` reads a -DR3_CLOCK=2 build: wave 0 of EACH half (team) of workgroup 0, with stamps inside the phases (MFMAs
 issued / last epilogue done / barrier passed).  Builds: make BUILD=build_x TARGET=../../exp/lib_x.so EXTRA=-DR3_CLOCK=2"""

@@ -51,11 +51,6 @@ using EQ_d5 = ConvCfg<16, 0, 16, 2, 5, 1, -2, 0, 2, 2, 6, 1, EPI_STORE, 0, 1>;
 // NW = 6 (376-column steps): 8 tiles x 768 rows = 6144 workgroups at 6 per CU = exactly four residencies of the chip
 // (NW = 8: 4608 workgroups at 4 per CU = 4.5, the last one half empty); 96.6 -> 95 us.
 using EQ_d6 = ConvCfg<16, 0, 8, 2, 7, 1, -3, 0, 1, 4, 6, 1, EPI_HEAD, 1>;  // + Conv1d(8,1,11) + sigmoid head
-// A/B tile variants (plan flag plan_flags[3] = 1): half-width tiles, twice the workgroups per CU
-using EQ_d3b = ConvCfg<32, 0, 32, 2, 5, 1, -2, 0, 2, 2, 3, 1, EPI_STORE>;
-using EQ_d4b = ConvCfg<32, 0, 16, 2, 5, 1, -2, 0, 2, 2, 3, 1, EPI_STORE>;
-using EQ_d5b = ConvCfg<16, 0, 16, 2, 5, 1, -2, 0, 2, 2, 3, 1, EPI_STORE>;
-using EQ_d6b = ConvCfg<16, 0, 8, 2, 7, 1, -3, 0, 1, 4, 4, 1, EPI_HEAD>;
 
 // Right edge of decoder stage 2 (module comment): y[t] = relu(b + sum_ci sum_k W[co][ci][k] u[t + k - 2]) for the last
 // two samples t = l_out - 2, l_out - 1 (373, 374), with u[i] = x[ci][i >> 1] inside the cropped upsampled row [0, l_out)
@@ -152,6 +147,16 @@ int plan_eqt(Net& net, const ParamView& pv) {
               "[2], [3], [7] other than bit 10 unset, [6] != 2)");
     return VP_ERR_UNSUPPORTED;
   }
+  if (pf::get(cfg, pf::MID) == pf::MID_EQT_REMOVED) {
+    set_error("EQTransformer plan_flags[2] = 3 (middle kernel with two windows per workgroup in teams of eight waves): removed; "
+              "the default runs four windows per workgroup in teams of four waves, plan_flags[2] = 2 the same kernel with one");
+    return VP_ERR_UNSUPPORTED;
+  }
+  if (pf::get(cfg, pf::TILES) == pf::TILES_EQT_REMOVED) {
+    set_error("EQTransformer plan_flags[3] = 1 (half-width decoder tiles): removed; decoder.3 .. .6 run on the full-width tiles "
+              "of the default plan");
+    return VP_ERR_UNSUPPORTED;
+  }
   const float eps = net.cfg.bn_eps;
   const int T = 6000;
   net.in_samples = T;
@@ -232,7 +237,7 @@ int plan_eqt(Net& net, const ParamView& pv) {
   // ---- BiLSTM stack ---------------------------------------------------------------------
   std::vector<std::function<BiLstmArgs(Net&)>> mk_lstm;
   std::vector<std::function<TransformerArgs(Net&)>> mk_tr;
-  int mid_first = -1;  // first of the six steps that eqt_mid_kernel replaces
+  int mid_first = -1;  // first of the six steps that eqt_mid4_kernel replaces
   double mid_flops = 0;
   int lstm_in = res_out;
   for (int i = 0; i < 3; ++i) {
@@ -278,7 +283,7 @@ int plan_eqt(Net& net, const ParamView& pv) {
     const std::string p = tr_names[i];
     const int out = net.add_tensor(p, 16, EQT_T);
     AttnWeights aw = attn_weights(net, pv, p + ".attention.");
-    std::vector<float> ln4;  // gamma1 | beta1 | gamma2 | beta2 in ONE blob: eqt_mid_kernel fetches it as ln4[lane]
+    std::vector<float> ln4;  // gamma1 | beta1 | gamma2 | beta2 in ONE blob: eqt_mid4_kernel fetches it as ln4[lane]
     for (const char* nm : {".norm1.gamma", ".norm1.beta", ".norm2.gamma", ".norm2.beta"}) {
       const std::vector<float> part = vec(pv.get(p + nm), 16);
       ln4.insert(ln4.end(), part.begin(), part.end());
@@ -348,15 +353,15 @@ int plan_eqt(Net& net, const ParamView& pv) {
     st.run = [=](Net& n, int B, hipStream_t s_) -> int { return launch_pick_branch(mk_pick(n, B), s_); };
     mid_flops += st.flops_per_window;
     net.steps.push_back(std::move(st));
-    // plan_flags[2] = 1 keeps the six separate launches (A/B timing); default: one launch for the whole latency-bound chain,
-    // four windows per workgroup in teams of four waves (eqt_mid4.hip); plan_flags[2] = 3: two windows per workgroup in teams
-    // of eight waves (the default of rounds 3-5); plan_flags[2] = 2: one window per workgroup (the form of rounds 1-2)
+    // plan_flags[2] = 1 keeps the six separate launches (A/B timing, the independent reference); default: one launch for the
+    // whole latency-bound chain, four windows per workgroup in teams of four waves (eqt_mid4.hip); plan_flags[2] = 2: the same
+    // kernel with one window per workgroup (the bit reference of the tests)
     const int mid_form = pf::get(cfg, pf::MID);
     if (mid_form != pf::MID_SIX_LAUNCHES && mid_first >= 0 && (int)net.steps.size() == mid_first + 6) {
       Step fused;
       fused.name = "fused.mid (3 BiLSTM + 2 transformer blocks + pick branches)";
       fused.flops_per_window = mid_flops;
-      // issued per window (eqt_kernels.hip): 16 x 16 x 4 fp32 tiles of the dense products -- BiLSTM input projections 8 waves x 3
+      // issued per window (eqt_mid4.hip): 16 x 16 x 4 fp32 tiles of the dense products -- BiLSTM input projections 8 gate blocks x 3
       // n-tiles x CIN / 4 K-steps (CIN 64, 16, 16) + Conv1d(32,16,1) 3 x 8; per transformer q / k 12 x 4, a.x 3 x 12, the two
       // feed-forward layers 24 x 4 and 6 x 16; pick branches 24 x 4 + 2 x (12 x 4 + 3 x 12) -- and, on the vector ALUs, the
       // eight 47-step recurrences (64 gate rows x 16 units) and the four 47 x 47 x 32 score loops (two packed FMAs per pair)
@@ -388,7 +393,7 @@ int plan_eqt(Net& net, const ParamView& pv) {
         m.pick = mk_pick(n, B);
         m.clk = clock_words(n, ClockRegions(n.max_batch).mid);  // slots [B][8] (tools/mid_clock.py)
         m.B = B;
-        if (mid_form == pf::MID_ONE_WINDOW || mid_form == pf::MID_TWO_WINDOWS) return launch_eqt_mid(m, B, s_, mid_form == pf::MID_ONE_WINDOW);
+        if (mid_form == pf::MID_ONE_WINDOW) return launch_eqt_mid4_one_window(m, B, s_);
         if (!mdbg.empty()) {
           MidDumpArgs d{};
           static_cast<MidArgs&>(d) = m;
@@ -410,18 +415,13 @@ int plan_eqt(Net& net, const ParamView& pv) {
   const int dk[7] = {3, 5, 5, 7, 7, 9, 11};
   const char* dec_prefix[3] = {"decoder_d", "pick_decoders.0", "pick_decoders.1"};
   int dsrc = dec_in;
-  const bool alt = pf::get(cfg, pf::TILES) == pf::TILES_ALT;
   for (int i = 0; i < 7; ++i) {
-    const bool polyphase = true;
     const int dst_len = dout[i];
     const int dst = (i == 6) ? kDenseOut : net.add_tensor("decoder." + std::to_string(i), dco[i], dst_len, 3);
     auto pack3 = [&](const ConvGeom& g, std::vector<float>* af, std::vector<float>* bs) {
       for (int d = 0; d < 3; ++d) {
         const std::string c = std::string(dec_prefix[d]) + ".convs." + std::to_string(i);
-        std::vector<float> a =
-            polyphase ? pack_afrag(amat_upconv(pv.get(c + ".weight"), dco[i], dci[i], dk[i], g.cinp()), g.M(), g.cinp(),
-                                   g.taps)
-                      : pack_plain(pv, c, dco[i], dci[i], dk[i], g);
+        std::vector<float> a = pack_afrag(amat_upconv(pv.get(c + ".weight"), dco[i], dci[i], dk[i], g.cinp()), g.M(), g.cinp(), g.taps);
         af->insert(af->end(), a.begin(), a.end());
         const float* b = pv.get(c + ".bias");
         bs->insert(bs->end(), b, b + dco[i]);
@@ -437,10 +437,10 @@ int plan_eqt(Net& net, const ParamView& pv) {
       case 0: EQ_DEC(EQ_d0) break;
       case 1: EQ_DEC(EQ_d1) break;
       case 2: EQ_DEC(EQ_d2) break;
-      case 3: if (alt) { EQ_DEC(EQ_d3b) } else { EQ_DEC(EQ_d3) } break;
-      case 4: if (alt) { EQ_DEC(EQ_d4b) } else { EQ_DEC(EQ_d4) } break;
-      case 5: if (alt) { EQ_DEC(EQ_d5b) } else { EQ_DEC(EQ_d5) } break;
-      default: if (alt) { EQ_DEC(EQ_d6b) } else { EQ_DEC(EQ_d6) } break;
+      case 3: EQ_DEC(EQ_d3) break;
+      case 4: EQ_DEC(EQ_d4) break;
+      case 5: EQ_DEC(EQ_d5) break;
+      default: EQ_DEC(EQ_d6) break;
     }
 #undef EQ_DEC
     L->l_dst = dst_len;
@@ -510,7 +510,7 @@ int plan_eqt(Net& net, const ParamView& pv) {
     if (rc != VP_OK) return rc;
   }
   // plan_flags[7] bit 0 keeps decoder.4 / .5 / .6+heads as three launches (layer tests, A/B timing)
-  if (!pf::eqt(cfg, pf::EQT_TAIL_LAYERS) && !alt) {
+  if (!pf::eqt(cfg, pf::EQT_TAIL_LAYERS)) {
     int rc = pf::eqt(cfg, pf::EQT_TAIL_FP32) ? plan_eqt_fuse_tail(net) : plan_eqt_fuse_tail_b3(net);  // bit 6: the fp32-MFMA kernel
     if (rc != VP_OK) return rc;
   }

@@ -73,22 +73,20 @@ struct PickBranchArgs {
 };
 
 // The three BiLSTM blocks, the two transformer blocks and the two pick branches of one window as ONE launch
-// (eqt_mid_kernel): the six launches it replaces are a chain of latency-bound kernels (47 sequential LSTM steps four
-// times over) that the three device contexts cannot hide behind each other's MFMA work — measured: with them removed
+// (eqt_mid4_kernel, eqt_mid4.hip): the six launches it replaces are a chain of latency-bound kernels (47 sequential LSTM steps
+// four times over) that the three device contexts cannot hide behind each other's MFMA work — measured: with them removed
 // from the pipeline a 256-window step takes 510 instead of 615 us.
 struct MidArgs {
   BiLstmArgs lstm[3];     // lstm[0].src: ResCNN output (64 channels); the others chain through LDS
   TransformerArgs tr[2];
   PickBranchArgs pick;
   unsigned long long* clk;  // optional debug: 8 shader-clock stamps per window (start, after each of the six stages, end)
-  int B;                    // windows (the two-window workgroups clamp their last window to it)
+  int B;                    // windows (the last workgroup clamps its windows to it)
 };
-// teams of eight waves: two windows per 1024-thread workgroup (128 CUs for a batch of 256; the default of rounds 3-5), or
-// one_window_per_workgroup: the 512-thread form
-int launch_eqt_mid(const MidArgs& a, int B, hipStream_t s, bool one_window_per_workgroup);
-// default since round 6: teams of four waves, FOUR windows per 1024-thread workgroup (64 CUs for a batch of 256), eqt_mid4.hip;
-// bit-identical to the forms above
+// default: teams of four waves, FOUR windows per 1024-thread workgroup (64 CUs for a batch of 256)
 int launch_eqt_mid4(const MidArgs& a, int B, hipStream_t s);
+// plan_flags[2] = 2: the same kernel with ONE window per 256-thread workgroup, the bit reference of the tests
+int launch_eqt_mid4_one_window(const MidArgs& a, int B, hipStream_t s);
 // The DUMP instance of eqt_mid4_kernel (plan_flags[1] & 4, tests/test_gpu_layers_f64.py) also writes the fp32 values every stage
 // computed into haloed [C][47] debug tensors, index MD_* below (the order of the tensors plan_eqt adds for it).  A struct of its
 // own: the kernel requests sizeof(its argument struct) of kernel arguments up front, so a longer MidArgs would change the

@@ -1,22 +1,38 @@
-// EQTransformer bottleneck (3 BiLSTM + 2 transformer blocks + P / S pick branches), FOUR windows per 1024-thread workgroup:
-// a window's team is four waves (eqt_kernels.hip: eight), its LDS 39 KB (67), so a 256-window batch holds 64 CUs (128).
+// EQTransformer bottleneck (3 BiLSTM + 2 transformer blocks + P / S pick branches) as ONE launch, FOUR windows per 1024-thread
+// workgroup: a window's team is four waves, its LDS 39 KB, so a 256-window batch holds 64 CUs.
 //
-// Why.  The chain is latency-bound where it is serial (4 x 47 LSTM steps on ONE wave per direction) and bound by the quarter-rate
-// reciprocals where it is parallel (the 47 x 47 x 32 score loops: 22 k CU-cycles per window whatever the team size).  A CU that
-// holds one of these workgroups holds nothing else (16 waves x 128 registers, > 130 KB of LDS), so what the launch costs the
-// pipeline is CUs x time.  With four windows per CU the serial phases cost a quarter of a CU each instead of half, the parallel
-// phases the same as before: CUs x time per batch falls by ~40 % (profiles/r06_*), and the CUs left free run the other device
-// contexts' kernels.
+// A team walks bilstm.0-2 -> transformer_d0 -> transformer_d -> pick branches.  The current activation travels through LDS as
+// [16 channels][48] rows (`cur`; column 47 is the zero K-padding of the a.x products); every stage still writes its tensor to
+// memory (decoder inputs; the others for the layer tests).  Against the separate kernels of eqt_kernels.hip (kept as the
+// six-launch plan, plan_flags[2] = 1):
+//   * every dense product is a set of 16x16x4 fp32 matrix-core tiles with the time steps as columns (mfma_tile): LSTM input
+//     projections, Conv1d(32,16,1), q / k projections, a.x, both feed-forward layers; LayerNorm runs in the epilogues of a.x and
+//     of the second feed-forward product (layer_norm_mfma);
+//   * the operands of a stage (Bi4Frags / Tr4Frags / Pick4Frags) are requested one stage ahead, under the 47 LSTM steps or the
+//     attention score loop of the stage before, as 16-byte loads in fragment order, so that no stage but the first waits for
+//     memory;
+//   * the two pick LSTMs run side by side and five kernel boundaries are gone.
+// Serial or transcendental work stays on the VALU: the recurrences (one wave per direction), the 47 x 47 x 32 score loops, the
+// row softmax.  DESIGN.md section 6 lists what each of these steps was worth in cycles.
 //
-// What changes against the eight-wave team (same arithmetic, same summation order in every product: results bit-identical):
+// Why four windows per workgroup.  The chain is latency-bound where it is serial (4 x 47 LSTM steps on ONE wave per direction) and
+// bound by the quarter-rate reciprocals where it is parallel (the 47 x 47 x 32 score loops: 22 k CU-cycles per window whatever
+// the team size).  A CU that holds one of these workgroups holds nothing else (16 waves x 128 registers, > 130 KB of LDS), so
+// what the launch costs the pipeline is CUs x time.  With four windows per CU the serial phases cost a quarter of a CU each, the
+// parallel phases the same as with fewer: CUs x time per batch fell by ~40 % against two windows in teams of eight waves
+// (profiles/r06_*), and the CUs left free run the other device contexts' kernels.
+//
+// Who does what in a team:
 //   * a wave owns a gate block of BOTH directions of a BiLSTM input projection (of both pick branches), one m-tile of the q / k
 //     projection with all three column tiles, two m-tiles of Linear(16,128), one K half of Linear(128,16) for one or two column
-//     tiles (the halves are added as the eight-wave form adds them);
+//     tiles (bias + first half, plus the second half: the order of that sum is fixed);
 //   * the stage pools alias what is dead: the first stage's input rows lie where the recurrence writes its outputs, the hidden
 //     layer of the feed-forward lies over q / k / e, the pick branches' q / k / e over the input projections;
-//   * the odd teams' roles are rotated by two waves, so that the eight recurrence waves of a workgroup sit two per SIMD.
+//   * the odd teams' roles are rotated by two waves, so that the eight recurrence waves of a workgroup sit two per SIMD
+//     (hardware wave h runs on SIMD h % 4).
 // A vote (which form a window's attention scores take) stays per team (team_vote_or): what a window computes never depends on
-// the windows it shares a workgroup with (tests/test_gpu_round4.py).
+// the windows it shares a workgroup with (tests/test_gpu_round4.py).  The one-window instance (plan_flags[2] = 2: one team per
+// 256-thread workgroup) is the reference the tests hold the default to, bit for bit.
 #define MID_TEAM (threadIdx.x >> 8)
 #define MID_TID ((threadIdx.x + (((threadIdx.x >> 8) & 1u) << 7)) & 255u)
 #define MID_NT 256u
@@ -27,11 +43,14 @@ namespace vp {
 namespace {
 
 constexpr int M4_NTH = 256;    // threads of a window's team
-constexpr int M4_WPB = 4;      // windows per workgroup
+constexpr int M4_WPB = 4;      // windows per workgroup of the default instance
 constexpr int M4_POOL = 9184;  // floats per window; the stages carve it up in turn
 static_assert((M4_POOL * 4) % 16 == 0 && M4_WPB * (M4_POOL + 16 * 48) * 4 <= 160 * 1024 - 256, "four windows fit a CU's LDS");
 
-// Debug clock stamps inside the stages (slots 8.. of the window's 32, the slots of eqt_mid_kernel: tools/mid_clock.py)
+// Debug clock stamps inside the stages, slots 8.. of the window's 32 (tools/mid_clock.py); the last caller of a stage wins.
+//   8-10 BiLSTM (x in LDS, projection done, recurrence done), 11 transformer start, 13-16 its feed-forward phases and LN2,
+//   17-19 pick branches (start, projection done, recurrences done); an attention stamps sub[0..4] of the base its caller
+//   passes: 20.. for a transformer, 26.. for the S branch (1 q / k stored, 0 requests issued, 2 scores, 3 softmax, 4 a.x)
 #define M4_SUB(slot) \
   if (sub && MID_TID == 0) sub[slot] = __builtin_readcyclecounter();
 
@@ -58,7 +77,8 @@ struct Bi4Frags {
 template <int CIN>
 __device__ __forceinline__ void bi4_load(Bi4Frags<CIN>& g, const BiLstmArgs& a) {
   const int lane = MID_TID & 63, wave = m4_wave();
-  // no branches (waves that do not need an operand fetch it anyway): see bi_load in eqt_kernels.hip
+  // no branches (waves that do not need an operand fetch it anyway): in one basic block the reads of the argument block cluster
+  // into a single wait; behind wave-dependent branches they serialised, ~1 k cycles apiece
   lstm_project_load<CIN>(g.f[0], a.fwd, wave);
   lstm_project_load<CIN>(g.f[1], a.bwd, wave);
   lstm_load_whh(g.whh, (wave & 1) ? a.bwd : a.fwd);
@@ -136,7 +156,9 @@ __device__ void mid4_bilstm(const BiLstmArgs& a, Bi4Frags<CIN>& g, const int b, 
   __syncthreads();
 }
 
-// The attention of a four-wave team (mid_attention of eqt_kernels.hip with the q / k projection as one m-tile per wave).
+// The attention of a four-wave team: every dense product on the matrix cores, the q / k projection as one m-tile per wave.
+// `prefetch` runs at the start of the score loop, the longest stretch of pure arithmetic of the stage: the caller requests the
+// NEXT stage's weights there.
 //   x:  [16][48] input rows (column 47 must be finite: it meets the zero column of a in the a.x product)
 //   q, k: [T][KP],  e: [48][AES];  `finish(acc, n0)`: what waves 0-2 do with their tile of a.x
 template <class Prefetch, class Finish>
@@ -201,8 +223,8 @@ struct Tr4Frags {
   float a2[16], b2v[4];       // Linear(128,16): K half = wave / 2; waves 0, 2 the column tiles 0 and 1, waves 1, 3 tile 2
 };
 // early: what the stage needs up to its score loop (requested during the stage before); late: everything else, requested by
-// the stage itself at the start of its score loop (11 k cycles of pure arithmetic) -- a four-wave team holds twice the operands
-// of an eight-wave one per wave, and the score loop wants 64 registers of q / k rows in flight
+// the stage itself at the start of its score loop (11 k cycles of pure arithmetic) -- a wave holds two m-tiles of Linear(16,128)
+// and a K half of Linear(128,16), and the score loop wants 64 registers of q / k rows in flight
 __device__ __forceinline__ void tr4_load_early(Tr4Frags& g, const TransformerArgs& a) {
   const int lane = MID_TID & 63;
   attn_load(g.af, a.att);
@@ -278,8 +300,7 @@ __device__ void mid4_transformer(const TransformerArgs& a, Tr4Frags& g, const in
   __syncthreads();
   M4_SUB(14)
   if constexpr (DUMP) md_copy(d, D0 + MD_TR_FF1, b, h1T, 128, 48);  // h1T is only read from here on
-  // Linear(128,16) in two K halves, as the eight-wave team sums them: bias + first half (waves 0, 1), plus the second half
-  // (waves 2, 3, handed over through LDS)
+  // Linear(128,16) in two K halves: bias + first half (waves 0, 1), plus the second half (waves 2, 3, handed over through LDS)
   const int half = wave >> 1, nt0 = (wave & 1) ? 2 : 0, ntn = (wave & 1) ? 1 : 2;
   f32x4 acc2[2];
 #pragma unroll
@@ -355,7 +376,7 @@ __device__ void mid4_pick(const PickBranchArgs& a, Pick4Frags& g, const int b, f
   static_assert(2 * T * KP + 48 * AES <= 2 * T * GXS && 2 * T * GXS + 3 * 16 * 48 <= M4_POOL, "pick stage fits the pool");
   M4_SUB(17)
   if (tid < 32) hl[tid * 48 + 47] = 0.f;  // K padding of the a.x products
-  lstm_load_whh(g.whh, (wave & 1) ? a.lstm[1] : a.lstm[0]);  // every wave: no branch, see bi_load
+  lstm_load_whh(g.whh, (wave & 1) ? a.lstm[1] : a.lstm[0]);  // every wave: no branch, see bi4_load
   lstm_project_mfma<EQT_H>(g.f[0], cur, gx, wave);
   lstm_project_mfma<EQT_H>(g.f[1], cur, gx + T * GXS, wave);
   __syncthreads();
@@ -409,24 +430,28 @@ __device__ void mid4_pick(const PickBranchArgs& a, Pick4Frags& g, const int b, f
   }
 }
 
-// The four teams execute the same barriers in the same order (same code, same trip counts); the last workgroup of a batch that
-// is not a multiple of four computes its last window more than once (identical stores).
+// WINDOWS teams per workgroup (4: the default; 1: the one-window reference).  The teams execute the same barriers in the same
+// order (same code, same trip counts); the last workgroup of a batch that is not a multiple of WINDOWS computes its last window
+// more than once (identical stores).
 // DUMP (tests only, plan_flags[1] & 4): the same kernel writing every stage's fp32 values to MidDumpArgs::dbg as well, from the
 // LDS images the next stage reads (copies behind the barriers that close them; the attention weights of a transformer before
 // its hidden layer is written over them, behind one more barrier), from registers (a.x, the second linear layer) and from
 // the recurrences (cell states)
-template <bool DUMP = false>
-__global__ __launch_bounds__(M4_WPB* M4_NTH) void eqt_mid4_kernel(const std::conditional_t<DUMP, MidDumpArgs, MidArgs> a) {
-  __shared__ __attribute__((aligned(16))) float P_all[M4_WPB * M4_POOL];
-  __shared__ float cur_all[M4_WPB * 16 * 48];
+template <int WINDOWS, bool DUMP>
+__global__ __launch_bounds__(WINDOWS* M4_NTH) void eqt_mid4_kernel(const std::conditional_t<DUMP, MidDumpArgs, MidArgs> a) {
+  static_assert(WINDOWS == M4_WPB || WINDOWS == 1, "MID_TEAM / MID_TID cut a workgroup into one or four teams");
+  __shared__ __attribute__((aligned(16))) float P_all[WINDOWS * M4_POOL];
+  __shared__ float cur_all[WINDOWS * 16 * 48];
   const int team = __builtin_amdgcn_readfirstlane(MID_TEAM);
   float* P = P_all + team * M4_POOL;
   float* cur = cur_all + team * 16 * 48;
-  const int b = min((int)blockIdx.x * M4_WPB + team, a.B - 1);
+  const int b = min((int)blockIdx.x * WINDOWS + team, a.B - 1);
   int stamp = 0;
   unsigned long long* sub = a.clk ? a.clk + (long)b * 32 : nullptr;
   if (MID_TID < 16) cur[MID_TID * 48 + 47] = 0.f;  // K padding of the a.x products; no stage writes column 47
-  {  // every cache line of the argument block requested at once (see eqt_mid_kernel)
+  {  // The argument block is 13 cache lines and every stage reads its own part of it when it starts: a cold line costs ~3.5 k
+     // cycles (measured: the stage that first touched another stage's arguments grew by that much).  All lines are requested
+     // here at once, so the later reads hit the scalar cache.
     typedef const unsigned __attribute__((address_space(4))) * uptr_t;
     const uptr_t ka = (uptr_t)__builtin_amdgcn_kernarg_segment_ptr();
     unsigned acc = 0;
@@ -461,12 +486,17 @@ __global__ __launch_bounds__(M4_WPB* M4_NTH) void eqt_mid4_kernel(const std::con
 }  // namespace
 
 int launch_eqt_mid4(const MidArgs& a, int B, hipStream_t s) {
-  hipLaunchKernelGGL(eqt_mid4_kernel<false>, dim3((B + M4_WPB - 1) / M4_WPB), dim3(M4_WPB * M4_NTH), 0, s, a);
+  hipLaunchKernelGGL((eqt_mid4_kernel<M4_WPB, false>), dim3((B + M4_WPB - 1) / M4_WPB), dim3(M4_WPB * M4_NTH), 0, s, a);
+  return 0;
+}
+
+int launch_eqt_mid4_one_window(const MidArgs& a, int B, hipStream_t s) {
+  hipLaunchKernelGGL((eqt_mid4_kernel<1, false>), dim3(B), dim3(M4_NTH), 0, s, a);
   return 0;
 }
 
 int launch_eqt_mid4_dump(const MidDumpArgs& a, int B, hipStream_t s) {
-  hipLaunchKernelGGL(eqt_mid4_kernel<true>, dim3((B + M4_WPB - 1) / M4_WPB), dim3(M4_WPB * M4_NTH), 0, s, a);
+  hipLaunchKernelGGL((eqt_mid4_kernel<M4_WPB, true>), dim3((B + M4_WPB - 1) / M4_WPB), dim3(M4_WPB * M4_NTH), 0, s, a);
   return 0;
 }
 

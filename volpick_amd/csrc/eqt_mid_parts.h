@@ -1,5 +1,6 @@
-// Device helpers shared by the EQTransformer bottleneck kernels (eqt_kernels.hip: teams of eight waves per window;
-// eqt_mid4.hip: teams of four).  The includer defines, BEFORE this header, how a workgroup is cut into per-window teams:
+// Device helpers shared by the EQTransformer bottleneck kernels: the one-launch kernel (eqt_mid4.hip: teams of four waves per
+// window, one or four teams per workgroup) and the six layer kernels (eqt_kernels.hip: the workgroup is the team).  The includer
+// defines, BEFORE this header, how a workgroup is cut into per-window teams:
 //   MID_TID   thread index within the window's team      MID_NT   threads of a team      MID_TEAM   team index
 // Everything below is written against those three only.
 #pragma once
@@ -10,9 +11,9 @@
 #error "define MID_TID / MID_NT / MID_TEAM before including eqt_mid_parts.h"
 #endif
 
-// The two-window form shares its barriers, not its decisions: a vote (which form a window's attention scores take) is ONE
-// workgroup-wide OR reduction in which every team sets its own bit and reads only that bit back, so what a window computes
-// never depends on the window it shares a workgroup with (same barrier count on both teams, no extra LDS).
+// The teams of a workgroup share their barriers, not their decisions: a vote (which form a window's attention scores take) is
+// ONE workgroup-wide OR reduction in which every team sets its own bit and reads only that bit back, so what a window computes
+// never depends on the windows it shares a workgroup with (same barrier count on every team, no extra LDS).
 __device__ __forceinline__ bool team_vote_or(bool mine) {
   const int team = __builtin_amdgcn_readfirstlane(MID_TEAM);  // wave-uniform: the result steers scalar branches
   return __builtin_amdgcn_readfirstlane((__ockl_wgred_or_i32(mine ? (1 << team) : 0) >> team) & 1) != 0;
@@ -24,8 +25,6 @@ namespace {
 
 constexpr int T = EQT_T;
 
-__device__ inline float wave_sum64(float v) { return wave_sum(v); }  // DPP reductions of prepost.h
-__device__ inline float wave_max64(float v) { return wave_max(v); }
 __device__ inline float lane_bcast(float v, int lane) {  // lane is a compile-time constant
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
 }
@@ -33,7 +32,6 @@ __device__ inline float lane_bcast(float v, int lane) {  // lane is a compile-ti
 // (v_div_scale, v_rcp, four FMAs, v_div_fmas, v_div_fixup) — ten instructions on the critical path of every LSTM step
 // and of every element of the attention loop.
 __device__ inline float rcp_fast(float x) { return __builtin_amdgcn_rcpf(x); }
-__device__ inline float sigmoid_f(float x) { return 1.f / (1.f + expf(-x)); }
 // recurrent gates: v_exp_f32 + v_rcp_f32 (abs error ~1e-7); 47 dependent steps make this the critical path
 __device__ inline float sigmoid_fast(float x) { return rcp_fast(1.f + __expf(-x)); }
 // tanh via one exp; abs error ~1e-7, saturates correctly at +-inf
@@ -93,7 +91,7 @@ __device__ inline void lstm_load_whh(f32x2 (&whh)[EQT_H / 2], const LstmWeights 
 // step feeds v_exp_f32 directly: three instructions fewer on the serial path of each of the 47 steps.
 __device__ __forceinline__ float lstm_gate_scale(const int gate) { return gate == 2 ? -2.885390082f : -1.442695041f; }
 // GS: row stride of gx (64, or 65 where the projection writes it with lane = time step).
-// SCALED: gx and whh already carry lstm_gate_scale (eqt_mid_kernel); the gate combination then runs as four fused DPP
+// SCALED: gx and whh already carry lstm_gate_scale (eqt_mid4_kernel); the gate combination then runs as four fused DPP
 // instructions (v_mul_f32_dpp / v_fmac_f32_dpp read the quad's i and f gates in place).
 // DUMP_C (the DUMP instance of eqt_mid4_kernel only): the cell state c_t of each unit goes to cout[unit * cs + t] as well,
 // from the quad's lane 0, the lane that stores h.
@@ -242,8 +240,8 @@ __device__ __forceinline__ void attn_wa(float (&wa)[32], const float wa_lane) {
 // tanh(q + k) = 1 - 2 / (exp(2q) exp(2k) + 1): with E_q = exp(2q), E_k = exp(2k) stored instead of q and k (plain = false) the
 // 47 x 47 x 32 inner loop needs ONE transcendental (v_rcp) per element instead of two (they issue at quarter rate and
 // were 60 % of its cycles), and the constant sum_u Wa[u] drops out.  plain = true: q, k hold the raw projections.
-// UH: channel pairs whose q / k words are requested together (16: all of an element's 64 registers at once; 8: in two halves,
-// for the kernels that cannot spare the registers -- the order of the sums is the same).
+// UH: channel pairs whose q / k words are requested together (16: all of an element's 64 registers at once, the layer kernels;
+// 8: in two halves, eqt_mid4_kernel, which cannot spare the registers -- the order of the sums is the same).
 template <int ES, int UH = 16>
 __device__ __forceinline__ void attn_scores(const float (*q)[KP], const float (*k)[KP], float* e, const float (&wa)[32], const bool plain) {
   const int tid = MID_TID, nt = MID_NT;
@@ -358,16 +356,16 @@ __device__ void attention_core(const float (*xs)[EQT_H], float (*q)[KP], float (
   __syncthreads();
 }
 
-// The attention of the fused kernel: every dense product on the matrix cores, activations as [channel][48] rows.
+// The attention of eqt_mid4_kernel (mid4_attention): every dense product on the matrix cores, activations as [channel][48] rows.
 //   x:  [16][48] input rows (column 47 must be finite: it meets the zero column of a in the a.x product)
 //   vT: [16][48] result rows,  q, k: [T][KP],  e: [T][AES]
 constexpr int AES = 49;  // row stride of e: the B fragments of a.x (lane -> row) spread over the banks
 struct AttnFrag {
   float a[4], bias[4];
 };
-// fragments of the q / k projection of this wave: m-tile mt = wave & 3 (q rows 0-15, 16-31, k rows 0-15, 16-31)
+// fragments of the q / k projection of this wave of a four-wave team: m-tile mt = wave (q rows 0-15, 16-31, k rows 0-15, 16-31)
 __device__ __forceinline__ void attn_load(AttnFrag& f, const AttnWeights w) {
-  const int lane = MID_TID & 63, mt = (MID_TID >> 6) & 3;
+  const int lane = MID_TID & 63, mt = MID_TID >> 6;
   mfma_load_a_t<4>(f.a, (mt < 2 ? w.Wt : w.Wx) + 16 * (mt & 1), 32);
   // loaded unconditionally (q rows ignore it at use): a select on a loaded value would make the wave wait for the
   // load right here, at the point that exists to leave it in flight

@@ -192,7 +192,7 @@ struct Res3Args {
   const float* b_next[7];
   long af_bytes_k3, af_bytes_k2;  // size of one conv's operand (L2 warm-up)
   int warm;                       // 0: no pre-touch of the weights (plan flag plan_flags[4] = 1)
-  int n_windows;                  // eqt_res3_kernel<2>: the last workgroup of an odd batch clamps its second window to it
+  int n_windows;                  // the last workgroup of a batch clamps its windows to it
   unsigned long long* clk;        // debug (plan_flags[1] & 2): shader-clock stamps of workgroup 0 (tools/res3_clock.py)
 };
 // The DUMP instance of eqt_res3t_kernel (plan_flags[1] & 4, tests/test_gpu_layers_f64.py) writes, per block i, the fp32 values its
@@ -324,26 +324,24 @@ __device__ __forceinline__ void res3_mac(const bf16_t* src, const Res3A<TAPS>& A
   }
 }
 
-// WPB windows per workgroup: team = threadIdx.x / 256 takes window WPB blockIdx.x + team with its own images; the teams run the
-// same barriers in lock step.  WPB = 2: one wave of each team per SIMD -- the two-waves-per-SIMD issue rate of eqt_res3k_kernel
-// without its partial-sum exchange -- and a batch of 256 windows holds 128 CUs (the other contexts' kernels run on the rest,
-// as beside eqt_mid_kernel<2>).  An odd batch's last workgroup computes its last window twice (identical stores).
-template <int WPB>
-__global__ __launch_bounds__(256 * WPB) void eqt_res3_kernel(const Res3Args a) {
-  __shared__ __attribute__((aligned(16))) float X_all[WPB * 64 * R3_XS];
-  __shared__ __attribute__((aligned(16))) bf16_t ACT_all[WPB * 3 * R3_PS];
-  __shared__ __attribute__((aligned(16))) bf16_t MID_all[WPB * 3 * R3_PS];
-  const int team = WPB > 1 ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 8) : 0;
-  float* X = X_all + team * 64 * R3_XS;
-  bf16_t* ACT = ACT_all + team * 3 * R3_PS;
-  bf16_t* MID = MID_all + team * 3 * R3_PS;
+// One window per 256-thread workgroup, four waves, wave = m-tile (16 output channels) with all three n-tiles: the one-window
+// reference of eqt_res3t_kernel (plan_flags[7] bit 9; the tests hold the default to it bit for bit).
+__global__ __launch_bounds__(256) void eqt_res3_kernel(const Res3Args a) {
+  __shared__ __attribute__((aligned(16))) float X_lds[64 * R3_XS];
+  __shared__ __attribute__((aligned(16))) bf16_t ACT_lds[3 * R3_PS];
+  __shared__ __attribute__((aligned(16))) bf16_t MID_lds[3 * R3_PS];
+  // The images through pointers and the (redundant) mask on threadIdx.x: hipcc's code for this kernel depends on both spellings,
+  // and these give the instruction stream the tests' reference has had since the kernel was written (tools/kernel_digest.py).
+  float* X = X_lds;
+  bf16_t* ACT = ACT_lds;
+  bf16_t* MID = MID_lds;
   const int tid = threadIdx.x & 255, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int win = min((int)blockIdx.x * WPB + team, a.n_windows - 1);
+  const int win = min((int)blockIdx.x, a.n_windows - 1);
   const int g = lane >> 4, n = lane & 15;
   // Debug stamps (tools/res3_clock.py) exist in -DR3_CLOCK=1 builds only: the kernel stands at 256 registers and the three
   // values a run-time switch keeps alive spilled 21 of them.
-#if R3_CLOCK == 2  // wave 0 of EACH team, and inside the phases: after the MFMAs are issued, after the epilogue, after the barrier
-  unsigned long long* clk = (a.clk && tid == 0 && blockIdx.x == 0) ? a.clk + team * 128 : nullptr;
+#if R3_CLOCK == 2  // inside the phases too: after the MFMAs are issued, after the epilogue, after the barrier
+  unsigned long long* clk = (a.clk && tid == 0 && blockIdx.x == 0) ? a.clk : nullptr;
   int stamp = 0;
 #define R3_STAMP() \
   if (clk) clk[stamp++] = __builtin_readcyclecounter();
@@ -383,7 +381,7 @@ __global__ __launch_bounds__(256 * WPB) void eqt_res3_kernel(const Res3Args a) {
   Res3A<3> w1_0;
   w1_0.load(a.af1[0], a.bs1[0], nullptr, nullptr, wave, lane);
   unsigned wv[14] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};  // looked at behind the prologue's LDS stores, not here
-  if (a.warm && team == 0) {
+  if (a.warm) {
     // The weights (1 MB) have left L2 since the last launch (the other kernels of the step move 0.3 GB): every XCD's L2 is
     // warmed up front, one word per 128-byte line (see eqt_res_kernel) -- by ALL workgroups of the XCD, each a slice of the
     // lines (consecutive workgroups go to consecutive XCDs): as the job of the first workgroup of each XCD, pulling 2 MB
@@ -515,9 +513,9 @@ __global__ __launch_bounds__(256 * WPB) void eqt_res3_kernel(const Res3Args a) {
 }
 
 // ---- THREE windows per workgroup, eight waves (round 6) ----------------------------------------------------------------------------
-// Where eqt_res3_kernel<2> spent its conv phases (tools/res3_clock.py waves, profiles/r06_g_*): 6.8 k cycles per k = 3 conv for
-// 3.5 k of matrix time per SIMD -- the same 6 k with the MFMAs taken out, the same with the fragment reads taken out, 4.3 k with
-// the WEIGHT STREAM taken out.  Wave w of either team requests the same 18 KB operand of m-tile w (144 KB per conv and CU, 21
+// Where eqt_res3_kernel with two windows per workgroup (two teams of four waves) spent its conv phases (tools/res3_clock.py
+// waves, profiles/r06_g_*): 6.8 k cycles per k = 3 conv for 3.5 k of matrix time per SIMD -- the same 6 k with the MFMAs taken
+// out, the same with the fragment reads taken out, 4.3 k with the WEIGHT STREAM taken out.  Wave w of either team requests the same 18 KB operand of m-tile w (144 KB per conv and CU, 21
 // 1-KB requests per wave), and those requests stood in program order in front of the conv's MFMAs: a wave issues in order, the
 // texture path takes ~25 cycles per request.  Three steps from there, each measured:
 //   (1) the requests in PARTS between the K-steps of the conv before (Res3A::load_part; now the form of eqt_res3_kernel too):
@@ -735,7 +733,8 @@ __global__ __launch_bounds__(512) void eqt_res3t_kernel(const std::conditional_t
 }
 
 // (eqt_res3k_kernel -- eight waves per window, K split over wave pairs with a partial-sum exchange through LDS; round 2's default,
-// 31.5 us on 256 CUs against 44.5 us on 128 -- was removed in round 6: plan_flags[7] bit 12 is rejected.)
+// 31.5 us on 256 CUs against 44.5 us on 128 -- was removed in round 6: plan_flags[7] bit 12 is rejected.  So is bit 13, the
+// two-window form of eqt_res3_kernel that eqt_res3t_kernel replaced.)
 
 }  // namespace
 
@@ -743,6 +742,11 @@ __global__ __launch_bounds__(512) void eqt_res3t_kernel(const std::conditional_t
 int plan_eqt_fuse_res(Net& net) {
   if (pf::eqt(net.cfg, pf::EQT_RES_KSPLIT)) {
     set_error("EQTransformer plan_flags[7] bit 12 (ResCNN kernel with K split over wave pairs): removed in round 6");
+    return VP_ERR_UNSUPPORTED;
+  }
+  if (pf::eqt(net.cfg, pf::EQT_RES_TWO_REMOVED)) {
+    set_error("EQTransformer plan_flags[7] bit 13 (ResCNN kernel with two windows per workgroup): removed; the default runs three "
+              "windows per workgroup (eqt_res3t_kernel), bit 9 one");
     return VP_ERR_UNSUPPORTED;
   }
   FuseSite site;
@@ -830,9 +834,7 @@ int plan_eqt_fuse_res(Net& net) {
         }
         hipLaunchKernelGGL(eqt_res3t_kernel<true>, dim3((B + 2) / 3), dim3(512), 0, s, d);
       } else if (pf::eqt(n.cfg, pf::EQT_RES_ONE_WINDOW))  // bit 9: four waves per window, one window per workgroup
-        hipLaunchKernelGGL(eqt_res3_kernel<1>, dim3(B), dim3(256), 0, s, a);
-      else if (pf::eqt(n.cfg, pf::EQT_RES_TWO_WINDOWS))  // bit 13: four waves per window, two windows per workgroup (rounds 5-6: 45 us on 128 CUs)
-        hipLaunchKernelGGL(eqt_res3_kernel<2>, dim3((B + 1) / 2), dim3(512), 0, s, a);
+        hipLaunchKernelGGL(eqt_res3_kernel, dim3(B), dim3(256), 0, s, a);
       else  // eight waves per THREE windows
         hipLaunchKernelGGL(eqt_res3t_kernel<false>, dim3((B + 2) / 3), dim3(512), 0, s, a);
       return 0;

@@ -10,7 +10,7 @@ namespace pf {
 enum Index {
   LAYERS = 0,   // 1: PhaseNet layer by layer / EQTransformer's 14 ResCNN conv launches
   DEBUG = 1,    // bits DBG_*
-  MID = 2,      // EQTransformer's middle (BiLSTM, transformers, pick branches): MID_*; PhaseNet: 1 removed
+  MID = 2,      // EQTransformer's middle (BiLSTM, transformers, pick branches): MID_*; PhaseNet: 1 removed; EQTransformer: 3 removed
   TILES = 3,    // TILES_*
   WARM = 4,     // 1: no L2 warm-up of the weight streams
   PN_FORM = 5,  // PhaseNet: PN_*
@@ -28,11 +28,12 @@ constexpr int DBG_LAYER_DUMPS = 4;  // the DUMP instances of the default kernels
 // [MID]
 constexpr int MID_PN_REMOVED = 1;    // PhaseNet: the hand-pipelined K loop
 constexpr int MID_SIX_LAUNCHES = 1;  // EQTransformer: the layer launches of the middle
-constexpr int MID_ONE_WINDOW = 2;    // eqt_mid_kernel, one window per workgroup
-constexpr int MID_TWO_WINDOWS = 3;   // eqt_mid_kernel, two windows per workgroup
+constexpr int MID_ONE_WINDOW = 2;    // eqt_mid4_kernel<1, false>: one window per workgroup, the bit reference of the default
+constexpr int MID_EQT_REMOVED = 3;   // EQTransformer: two windows per workgroup in teams of eight waves
 
 // [TILES]
-constexpr int TILES_ALT = 1;          // PhaseNet: up3 with one workgroup per tile; EQTransformer: half-width decoder tiles
+constexpr int TILES_ALT = 1;          // PhaseNet: up3 with one workgroup per tile
+constexpr int TILES_EQT_REMOVED = 1;  // EQTransformer's half-width decoder tiles
 constexpr int TILES_PN_REMOVED = 2;   // PhaseNet's persistent level-0 down kernel
 constexpr int TILES_PN_NO_GATE = 64;  // PhaseNet's one-launch plan without the gate between device contexts (api.hip ForwardGate)
 
@@ -58,11 +59,11 @@ constexpr int EQT_DEC03_FP32 = 1 << 5;        // eqt_dec03_kernel<false>
 constexpr int EQT_TAIL_FP32 = 1 << 6;         // eqt_tail_kernel
 constexpr int EQT_ENC36_FP32 = 1 << 7;        // eqt_enc36_kernel
 constexpr int EQT_FRONT_FP32 = 1 << 8;        // eqt_front_kernel<false, ..>
-constexpr int EQT_RES_ONE_WINDOW = 1 << 9;    // eqt_res3_kernel<1>
+constexpr int EQT_RES_ONE_WINDOW = 1 << 9;    // eqt_res3_kernel
 constexpr int EQT_TAIL_WHOLE_ROW = 1 << 10;   // the tail computes every tile whatever the caller blinds
 constexpr int EQT_DEC03_EVEN = 1 << 11;       // stage 3's n-tiles 12 + 12 over a SIMD's two waves
 constexpr int EQT_RES_KSPLIT = 1 << 12;       // removed in round 6, rejected
-constexpr int EQT_RES_TWO_WINDOWS = 1 << 13;  // eqt_res3_kernel<2>
+constexpr int EQT_RES_TWO_REMOVED = 1 << 13;  // eqt_res3_kernel with two windows per workgroup: removed, rejected
 
 inline int get(const vp_config& c, Index i) { return c.plan_flags[i]; }
 inline bool has(const vp_config& c, Index i, int bits) { return (c.plan_flags[i] & bits) != 0; }
