@@ -357,6 +357,30 @@ int vp_mseed_scan(const uint8_t* buf, size_t nbytes, vp_mseed_record* recs, int6
 int vp_mseed_decode(int device_id, const uint8_t* buf, int buf_mem, size_t nbytes, const vp_mseed_record* recs,
                     const int64_t* out_index, const int64_t* out_count, int64_t n_recs, int out_kind, void* out,
                     int out_mem, int64_t out_len, int zero_fill, int32_t* status);
+/* vp_mseed_scan_segments (host only, no GPU, callable from any thread: vp_mseed_scan's class) is vp_mseed_scan plus the
+ * bookkeeping a reader does next: the records with samples (nsamples > 0) are put in the order (network, station, location,
+ * channel, start_us, offset) and chained into continuous segments by libmseed's trace-list rule -- a record extends the
+ * previous one's segment when id, rate and sample kind (float encodings 4 / 5 against the rest) are the same and it starts one
+ * period after that record's last sample, within half a period.  recs[0 .. *n_kept) is the ordered table and seg[i] the
+ * segment number of recs[i] (from 0, non-decreasing); `seg` holds `cap` words.  *n_found is vp_mseed_scan's total: when it
+ * exceeds `cap` nothing was ordered (*n_kept = 0) and the call is to be repeated with room.  Errors are vp_mseed_scan's. */
+int vp_mseed_scan_segments(const uint8_t* buf, size_t nbytes, vp_mseed_record* recs, int64_t* seg, int64_t cap,
+                           int64_t* n_found, int64_t* n_kept);
+/* vp_mseed_decode for a pipeline: the same kernel and the same record checks, enqueued on the caller's `stream` (a
+ * hipStream_t, not the null stream) and never waited for.  buf_dev (4-byte aligned, nbytes rounded up to a whole word
+ * readable), out_dev (out_len samples of out_kind) and status_dev are device memory; recs, out_index, out_count are host
+ * arrays read before the call returns.  Records are skipped as in vp_mseed_decode (out_index[r] < 0, nsamples <= 0); the
+ * others -- *n_decoded of them, in table order -- get one status word each, status_dev[0 .. *n_decoded), with
+ * vp_mseed_decode's values.  out_count[r] = 0 decodes a record for its status alone.  The launch table travels through
+ * memory of the caller's: table_host (page-locked, to stay untouched until the copy has run on `stream`) and table_dev
+ * (until the kernel has), each table_bytes >= VP_MSEED_TABLE_BYTES_PER_RECORD * n_recs.  Holds no lock and no scratch: any
+ * number of calls may be in flight, on any streams.  With out_index[r] = row * N + offset, VP_SAMPLES_FLOAT32 and
+ * zero_fill it writes a station's (C, N) float32 block -- gap fill, missing components and component order -- in one launch. */
+enum { VP_MSEED_TABLE_BYTES_PER_RECORD = 32 };
+int vp_mseed_decode_on(int device_id, const uint8_t* buf_dev, size_t nbytes, const vp_mseed_record* recs,
+                       const int64_t* out_index, const int64_t* out_count, int64_t n_recs, int out_kind, void* out_dev,
+                       int64_t out_len, int zero_fill, int32_t* status_dev, void* table_host, void* table_dev,
+                       size_t table_bytes, int64_t* n_decoded, void* stream);
 /* Mean kernel time (ms, HIP events) of `iters` decodes of the same device-resident inputs: bench only. */
 int vp_mseed_decode_bench(int device_id, const uint8_t* buf_dev, size_t nbytes, const vp_mseed_record* recs,
                           const int64_t* out_index, int64_t n_recs, int out_kind, void* out_dev, int64_t out_len,

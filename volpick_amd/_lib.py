@@ -103,6 +103,7 @@ class VpMseedRecord(C.Structure):
 
 
 VP_SAMPLES_INT32, VP_SAMPLES_FLOAT32, VP_SAMPLES_FLOAT64 = 0, 1, 2
+VP_MSEED_TABLE_BYTES_PER_RECORD = 32
 
 VP_DETREND_DEMEAN, VP_DETREND_LINEAR, VP_DETREND_SIMPLE = 0, 1, 2
 
@@ -241,6 +242,12 @@ SIGNATURES = {
         C.c_int,
         [C.c_int, C.c_void_p, C.c_int, C.c_size_t, C.POINTER(VpMseedRecord), _I64P, _I64P, C.c_int64, C.c_int,
          C.c_void_p, C.c_int, C.c_int64, C.c_int, C.POINTER(C.c_int32)],
+    ),
+    "vp_mseed_scan_segments": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(VpMseedRecord), _I64P, C.c_int64, _I64P, _I64P]),
+    "vp_mseed_decode_on": (
+        C.c_int,
+        [C.c_int, C.c_void_p, C.c_size_t, C.POINTER(VpMseedRecord), _I64P, _I64P, C.c_int64, C.c_int, C.c_void_p,
+         C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, _I64P, C.c_void_p],
     ),
     "vp_mseed_release_scratch": (C.c_int, [C.c_int, C.POINTER(C.c_size_t)]),
     "vp_mseed_decode_bench": (

@@ -8,6 +8,11 @@
 // at a time, and the two serial steps -- where each word's differences start (1..7 per word)
 // and the running sum -- are two DPP prefix scans over the lanes; the <= 7 differences of a
 // word are integrated in registers and stored straight to their place in the output.
+#include <algorithm>
+#include <array>
+#include <cmath>
+#include <cstddef>
+
 #include "device_scratch.h"
 
 namespace vp {
@@ -474,6 +479,121 @@ extern "C" int vp_mseed_scan(const uint8_t* buf, size_t nbytes, vp_mseed_record*
     off += reclen;
   }
   *n_found = n;
+  return VP_OK;
+}
+
+// The record table as a reader wants it: vp_mseed_scan, then the records with samples in the order (network, station,
+// location, channel, start, offset) and a segment number per record.  A record extends the previous one's segment when it
+// has the same id, rate and sample kind and starts one period after that record's last sample, within half a period
+// (libmseed's trace-list tolerance).  Host only.
+extern "C" int vp_mseed_scan_segments(const uint8_t* buf, size_t nbytes, vp_mseed_record* recs, int64_t* seg, int64_t cap,
+                                      int64_t* n_found, int64_t* n_kept) {
+  VP_REQUIRE(n_kept && (seg || cap == 0), "vp_mseed_scan_segments: null argument");
+  *n_kept = 0;
+  const int rc = vp_mseed_scan(buf, nbytes, recs, cap, n_found);
+  if (rc != VP_OK || *n_found > cap) return rc;  // a table that did not fit is not ordered: call again with room
+  const int64_t n = *n_found;
+  // The four codes lie side by side in the record, in sort order: one 20-byte string per id.  A file holds few ids and
+  // long runs of each, so every id gets its rank once and the sort compares three integers.
+  typedef std::array<unsigned char, 20> Id;
+  static_assert(offsetof(vp_mseed_record, channel) + sizeof(recs->channel) - offsetof(vp_mseed_record, network) == sizeof(Id) &&
+                    offsetof(vp_mseed_record, station) == offsetof(vp_mseed_record, network) + 4 &&
+                    offsetof(vp_mseed_record, location) == offsetof(vp_mseed_record, station) + 8 &&
+                    offsetof(vp_mseed_record, channel) == offsetof(vp_mseed_record, location) + 4,
+                "network, station, location, channel are contiguous");
+  const auto id_of = [recs](int64_t i) {
+    Id id;
+    std::memcpy(id.data(), recs[i].network, sizeof(Id));
+    return id;
+  };
+  struct Key {
+    int64_t start, offset, index;
+    int id;
+  };
+  std::map<Id, int> ids;
+  std::vector<Key> keys;
+  keys.reserve((size_t)n);
+  const std::pair<const Id, int>* last = nullptr;
+  for (int64_t i = 0; i < n; ++i) {
+    if (recs[i].nsamples <= 0) continue;
+    const Id id = id_of(i);
+    if (!last || last->first != id) last = &*ids.emplace(id, (int)ids.size()).first;
+    keys.push_back(Key{recs[i].start_us, recs[i].offset, i, last->second});
+  }
+  std::vector<int> rank(ids.size());
+  int next_rank = 0;
+  for (const auto& kv : ids) rank[(size_t)kv.second] = next_rank++;  // (the map iterates in the ids' order)
+  for (Key& k : keys) k.id = rank[(size_t)k.id];
+  std::sort(keys.begin(), keys.end(), [](const Key& a, const Key& b) {
+    if (a.id != b.id) return a.id < b.id;
+    if (a.start != b.start) return a.start < b.start;
+    return a.offset < b.offset;
+  });
+  std::vector<vp_mseed_record> sorted(keys.size());
+  for (size_t i = 0; i < keys.size(); ++i) sorted[i] = recs[keys[i].index];
+  const auto period_us = [](const vp_mseed_record& m) { return m.sample_rate > 0 ? 1e6 / m.sample_rate : 0.0; };
+  const auto is_float = [](const vp_mseed_record& m) { return m.encoding == 4 || m.encoding == 5; };
+  int64_t s = 0;
+  for (size_t i = 0; i < sorted.size(); ++i) {
+    if (i > 0) {
+      const vp_mseed_record &p = sorted[i - 1], &m = sorted[i];
+      bool same = std::memcmp(p.network, m.network, sizeof p.network) == 0 &&
+                  std::memcmp(p.station, m.station, sizeof p.station) == 0 &&
+                  std::memcmp(p.location, m.location, sizeof p.location) == 0 &&
+                  std::memcmp(p.channel, m.channel, sizeof p.channel) == 0 && p.sample_rate == m.sample_rate &&
+                  is_float(p) == is_float(m);
+      if (same) {
+        const double period = period_us(p), span = std::nearbyint(p.nsamples * period);  // halves to even, as numpy rounds
+        // (a span no int64 holds -- a denormal rate -- is the most negative one, as the conversion gives it on the host)
+        const uint64_t span_us = span < 9.2e18 ? (uint64_t)(int64_t)span : (uint64_t)INT64_MIN;
+        const int64_t d = (int64_t)((uint64_t)m.start_us - ((uint64_t)p.start_us + span_us));
+        const int64_t ad = d < 0 ? (int64_t)(0 - (uint64_t)d) : d;
+        same = (double)ad <= 0.5 * period;
+      }
+      if (!same) ++s;
+    }
+    recs[i] = sorted[i];
+    seg[i] = s;
+  }
+  *n_kept = (int64_t)sorted.size();
+  return VP_OK;
+}
+
+static_assert(sizeof(DevRec) == VP_MSEED_TABLE_BYTES_PER_RECORD, "the header promises callers this size");
+
+// vp_mseed_decode's launch, stream-ordered: byte image, samples and status words all on the device, everything enqueued on
+// the caller's stream, nothing waited for and nothing owned -- the launch table is built in the caller's page-locked
+// `table_host` and copied to the caller's `table_dev`.
+extern "C" int vp_mseed_decode_on(int device_id, const uint8_t* buf_dev, size_t nbytes, const vp_mseed_record* recs,
+                                  const int64_t* out_index, const int64_t* out_count, int64_t n_recs, int out_kind,
+                                  void* out_dev, int64_t out_len, int zero_fill, int32_t* status_dev, void* table_host,
+                                  void* table_dev, size_t table_bytes, int64_t* n_decoded, void* stream) {
+  VP_REQUIRE(buf_dev && out_dev && out_len >= 0 && n_recs >= 0 && n_decoded && (n_recs == 0 || (recs && out_index)),
+             "vp_mseed_decode_on: null argument");
+  VP_REQUIRE(out_kind == VP_SAMPLES_INT32 || out_kind == VP_SAMPLES_FLOAT32, "vp_mseed_decode_on: bad out_kind");
+  VP_REQUIRE(stream, "vp_mseed_decode_on: the null stream is not a stream of the caller's");
+  VP_REQUIRE(((uintptr_t)buf_dev & 3) == 0, "vp_mseed_decode_on: buffer is not 4-byte aligned");
+  *n_decoded = 0;
+  std::vector<DevRec> dev;
+  std::vector<int64_t> origin;
+  const int rc = build_dev_recs(recs, out_index, out_count, n_recs, nbytes, out_kind, &dev, &origin);
+  if (rc != VP_OK) return rc;
+  const size_t need = dev.size() * sizeof(DevRec);
+  VP_REQUIRE(need == 0 || (table_host && table_dev && table_bytes >= need),
+             "vp_mseed_decode_on: the launch table needs %zu bytes of page-locked and of device memory, %zu given", need,
+             table_bytes);
+  VP_HIP(hipSetDevice(device_id));
+  hipStream_t s = (hipStream_t)stream;
+  if (zero_fill) VP_HIP(hipMemsetAsync(out_dev, 0, (size_t)out_len * 4, s));
+  if (!dev.empty()) {
+    std::memcpy(table_host, dev.data(), need);
+    VP_HIP(hipMemcpyAsync(table_dev, table_host, need, hipMemcpyHostToDevice, s));
+    if (status_dev) VP_HIP(hipMemsetAsync(status_dev, 0, dev.size() * sizeof(int), s));
+    launch_decode(buf_dev, (long long)nbytes, (const DevRec*)table_dev, (long long)dev.size(), out_kind, out_dev, out_len,
+                  status_dev, s);
+    VP_HIP(hipGetLastError());
+  }
+  *n_decoded = (int64_t)dev.size();
   return VP_OK;
 }
 

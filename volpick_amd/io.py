@@ -23,7 +23,7 @@ import numpy as np
 
 from . import _lib
 from ._device import release_scratch
-from .stream import Stream, Trace, UTCDateTime
+from .stream import Stream, Trace, UTCDateTime, block_start, component_index, sample_offset, warn_short_fragment
 
 _REC_DTYPE = np.dtype(
     [("offset", "<i8"), ("start_us", "<i8"), ("sample_rate", "<f8"), ("reclen", "<i4"), ("data_offset", "<i4"),
@@ -92,6 +92,104 @@ def _segments(recs):
     same &= np.abs(r["start_us"][1:] - expect) <= 0.5 * period[:-1]
     seg = np.concatenate([[0], np.cumsum(~same)]).astype(np.int64)
     return r, seg
+
+
+def scan_segments(buf):
+    """``_segments(scan_mseed(buf))`` in one host-only library call (``vp_mseed_scan_segments``): the ordered record table and
+    the segment number of each record.  Touches no GPU and no handle: any thread may call it."""
+    lib = _lib.load()
+    n, kept = C.c_int64(0), C.c_int64(0)
+    guess = 512  # (scan_mseed's capacity rule)
+    if len(buf) >= 56 and buf[:3] != b"MS\x03" and buf[48:50] in (b"\x03\xe8", b"\xe8\x03") and 7 <= buf[54] <= 24:
+        guess = 1 << buf[54]
+    cap = max(16, len(buf) // guess + 16)
+    while True:
+        recs, seg = np.empty(cap, _REC_DTYPE), np.empty(cap, np.int64)
+        _lib.check(lib.vp_mseed_scan_segments(buf, len(buf), recs.ctypes.data_as(C.POINTER(_lib.VpMseedRecord)),
+                                              seg.ctypes.data_as(C.POINTER(C.c_int64)), cap, C.byref(n), C.byref(kept)),
+                   "vp_mseed_scan_segments")
+        if n.value <= cap:
+            break
+        cap = n.value
+    return recs[:kept.value], seg[:kept.value]
+
+
+class FilePlan:
+    """What :func:`plan_file_blocks` found.  ``reason`` is ``None`` when the file can be decoded straight into its station
+    blocks, else why not (the file then goes through :func:`read_mseed`).  ``blocks``: one dict per block, in the order
+    ``models._group_stream`` yields them -- ``trace_id``, ``network``, ``station``, ``location``, ``start_us``, ``shape``
+    ``(C, N)`` and ``offset``, where the block begins in the file's float32 sample array (-1: no record feeds the block, it
+    is all zeros).  ``out_index[r]``: where record ``r``'s first sample goes in that array, -1 for a record of no block.
+    ``n_out``: the array's length.  ``short_runs``: how many runs were skipped as shorter than the model's window."""
+
+    __slots__ = ("reason", "blocks", "out_index", "n_out", "short_runs")
+
+    def __init__(self, reason=None, blocks=(), out_index=None, n_out=0, short_runs=0):
+        self.reason, self.blocks, self.out_index, self.n_out, self.short_runs = reason, list(blocks), out_index, n_out, short_runs
+
+
+BLOCK_ALIGN = 64  # blocks start on 256-byte boundaries of the file's sample array
+
+
+def plan_file_blocks(table, seg, component_order, sampling_rate, in_samples, has_filter=False, warn=True):
+    """``models._group_stream`` restated on a record table: from the headers alone, the station blocks of a miniSEED file and
+    where every record's samples go in them, so that one decode launch (``vp_mseed_decode_on`` with float32 output and zero
+    fill) writes the blocks ``_group_stream`` would assemble from the traces of ``read(..., device_resident=True)``.
+    ``table`` and ``seg`` are :func:`scan_segments`'.  Instruments, component rows, sample offsets, runs and start times
+    come from the helpers ``_group_stream`` uses (``stream.component_index``, ``sample_offset``, ``block_start``).
+
+    No plan (``FilePlan.reason`` set) when the file has no records; the model filters its input (``has_filter``); a trace is
+    not at the model's rate (any trace: a resampled one changes length, and with it the runs); two segments of one component
+    overlap inside a block (the assembly's "longer trace wins" is not a per-record rule); or a text record (encoding 0)
+    belongs to a used component.  ``warn=False`` leaves the short-fragment warnings to the caller (``short_runs`` of them)."""
+    if len(table) == 0:
+        return FilePlan("no records")
+    if has_filter:
+        return FilePlan("the model filters its input")
+    first, last = _segment_ranges(seg)
+    if (np.abs(table["sample_rate"][first] - float(sampling_rate)) > 1e-6).any():
+        return FilePlan("a trace is not at the model's rate")
+    ns = table["nsamples"].astype(np.int64)
+    before = np.cumsum(ns) - ns  # samples ahead of each record in the table
+    groups = {}
+    for a, b in zip(first.tolist(), last.tolist()):
+        cha = table["channel"][a].decode()
+        key = (table["network"][a].decode(), table["station"][a].decode(), table["location"][a].decode(), cha[:-1])
+        groups.setdefault(key, []).append((a, b, int(table["start_us"][a]), int(before[b - 1] + ns[b - 1] - before[a]),
+                                           component_index(cha, component_order)))
+    plan = FilePlan(out_index=np.full(len(table), -1, np.int64))
+    n_rows, cursor = len(component_order), 0
+    for (net, sta, loc, _), segs in sorted(groups.items()):
+        t_start = UTCDateTime._from_us(min(s[2] for s in segs))
+        pieces = [(sample_offset(UTCDateTime._from_us(us), t_start, sampling_rate), npts, ci, a, b) for a, b, us, npts, ci in segs]
+        runs = []
+        for s0, l, _, _, _ in sorted(pieces, key=lambda p: p[0]):
+            if runs and s0 <= runs[-1][1]:
+                runs[-1][1] = max(runs[-1][1], s0 + l)
+            else:
+                runs.append([s0, s0 + l])
+        for b0, b1 in runs:
+            if b1 - b0 < in_samples:
+                plan.short_runs += 1
+                if warn:
+                    warn_short_fragment()
+                continue
+            used = sorted((p for p in pieces if p[2] >= 0 and b0 <= p[0] < b1), key=lambda p: (p[2], p[0]))
+            for p, q in zip(used, used[1:]):
+                if p[2] == q[2] and q[0] < p[0] + p[1]:
+                    return FilePlan("two segments of one component overlap")
+            if any(int(table["encoding"][p[3]]) == 0 for p in used):
+                return FilePlan("a text record belongs to a used component")
+            n = b1 - b0
+            plan.blocks.append(dict(trace_id=f"{net}.{sta}.{loc}", network=net, station=sta, location=loc,
+                                    start_us=block_start(t_start, b0, sampling_rate)._us, shape=(n_rows, n),
+                                    offset=cursor if used else -1))
+            for s0, _, ci, a, b in used:
+                plan.out_index[a:b] = cursor + ci * n + (s0 - b0) + (before[a:b] - before[a])
+            if used:
+                cursor += -(-n_rows * n // BLOCK_ALIGN) * BLOCK_ALIGN
+    plan.n_out = cursor
+    return plan
 
 
 def _decode(buf, r, bounds, bases, device, dtype, device_resident):

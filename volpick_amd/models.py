@@ -704,6 +704,14 @@ class WaveformModel:
         self._lap("emit_records_ms", t_mark)
         return ClassifyOutput(self.name, picks=picks, detections=detections)
 
+    def classify_files(self, sources, depth=2, workers=2, **kwargs):
+        """``[self.classify(volpick_amd.read(s, device_resident=True), **kwargs) for s in sources]`` -- the same picks and
+        detections, bit for bit -- with the host work and the upload of the files ahead running beside the classification of
+        the one in flight (volpick_amd/files.py).  ``sources``: paths, bytes or file objects, as ``read`` takes them."""
+        from .files import classify_files
+
+        return classify_files(self, sources, depth=depth, workers=workers, **kwargs)
+
 
 class _ClassifyRun:
     """One classify() call: the station blocks on their way through the device and the triggers back so far.  A block takes

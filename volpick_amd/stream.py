@@ -121,6 +121,35 @@ class UTCDateTime:
         return f"UTCDateTime({str(self)!r})"
 
 
+# --- where a trace sits in its instrument's block: ``models._group_stream`` places samples with these, and ``io.plan_file_blocks``
+# places miniSEED records with the same ones, so the two cannot disagree by a sample or a microsecond
+def sample_offset(start, origin, sampling_rate):
+    """The sample number of the time ``start`` in a block that begins at ``origin`` (both ``UTCDateTime``)."""
+    return int(round((start - origin) * sampling_rate))
+
+
+def block_start(origin, first_sample, sampling_rate):
+    """The start time of the block that begins ``first_sample`` samples after ``origin``."""
+    return origin + first_sample / sampling_rate
+
+
+COMPONENT_ALIAS = {"1": "N", "2": "E", "3": "Z"}  # flexible horizontal components
+
+
+def component_index(channel, component_order):
+    """The row of ``channel``'s component in a block ordered as ``component_order``; -1: the block has no row for it."""
+    comp = channel[-1] if channel else ""
+    comp = comp if comp in component_order else COMPONENT_ALIAS.get(comp, comp)
+    return component_order.index(comp) if comp in component_order else -1
+
+
+def warn_short_fragment():
+    import warnings
+
+    warnings.warn("Parts of the input stream consist of fragments shorter than the number of input "
+                  "samples. Output might be empty.")
+
+
 # --- ObsPy's Trace.trim(starttime, endtime) with its defaults, restated (ObsPy is not available to pin it) ------------------
 TRIM_PAD = False              # pad=False: a time outside the trace cuts nothing, it never adds samples
 TRIM_NEAREST_SAMPLE = True    # nearest_sample=True: the cut lands on the sample nearest to the given time ...
