@@ -392,6 +392,64 @@ int vp_mseed_decode_bench(int device_id, const uint8_t* buf_dev, size_t nbytes, 
 int vp_mseed_release_scratch(int device_id, size_t* bytes_freed);
 
 /* ---------------------------------------------------------------------------------------------
+ * Traces to miniSEED: the other direction, the reference's waveforms.write(path, format="MSEED")
+ * (volpick/data/data.py:1353).  miniSEED 2 only: records of `reclen` bytes (a power of two in 128..65536) with the fixed
+ * header, blockette 1000 at byte 48, an optional blockette 1001 at byte 56 and the data at byte 64; traces in the order
+ * given, record after record, sequence numbers from 1 through the whole output.
+ *
+ * vp_mseed_encode packs the samples of `n_traces` traces: trace t is samples[first_sample .. first_sample + nsamples) of
+ * `samples` (host or device memory, samples_mem; elements of sample_kind, a VP_SAMPLES_* value; `first_sample` may be any
+ * element offset from the base, so traces in separate device arrays are read where they lie).  Encodings by sample kind:
+ * int32 -> 11 (Steim-2), 10 (Steim-1), 3 (int32), 1 (int16); float32 -> 4; float64 -> 5.  Steim words are packed greedily
+ * over the differences d[i] = x[i] - x[i-1] (wrapped to int32, x[-1] = 0 at the start of a trace): the first option that
+ * still has enough differences left in the trace and fits all of them wins -- Steim-2: 7x4, 6x5, 5x6, 4x8, 3x10, 2x15, 1x30
+ * bits; Steim-1: 4x8, 2x16, 1x32 -- and a record holds 15 * (reclen / 64 - 1) - 2 data words behind X0 and Xn; unused words of
+ * a trace's last record are zero.  The first difference of a trace is stored as 0 under Steim-2 when x[0] does not fit 30
+ * bits (decoders start from X0).  Any other Steim-2 difference outside 30 bits, and an int32 sample outside int16 under
+ * encoding 1, refuses the whole call: VP_ERR_INVALID, *bad_trace and *bad_sample name the first trace with such a sample and
+ * its lowest offending index (otherwise both are -1), nothing is written.  Float bits pass unchanged.
+ * b1001_mode: 0 never, 1 always, -1 for every record of a trace as soon as one record of that trace starts at a time that
+ * is no multiple of 100 microseconds.  A record that starts at sample `pos` starts at start_us + nearbyint(pos * 1e6 /
+ * sample_rate) (halves to even).  Traces with nsamples <= 0 are skipped.
+ * The output goes to out_host (host memory, out_cap bytes); *out_bytes and *n_records are always reported, and when
+ * *out_bytes > out_cap nothing is written and the call is to be repeated with room (vp_mseed_scan's idiom; (number of
+ * traces + total samples / samples per record at one difference per word) records are always enough).
+ * VP_ERR_INVALID: a null pointer, a bad kind / encoding / reclen / rate (vp_mseed_rate_fields refuses it), a code longer
+ * than its header field.  VP_ERR_UNSUPPORTED: a record could hold more than 65535 samples (Steim-2 at 65536 bytes).  Runs on
+ * the device's null stream and returns when the bytes are there.  The scratch (classes, word starts, chunk maps, the file
+ * image) is kept per device, grow-only; vp_mseed_encode_release_scratch frees it -- the other release calls do not touch
+ * it.  No counterpart of the kernels in the reference (ObsPy packs with libmseed on the host). */
+typedef struct {
+  int64_t start_us;      /* first sample, microseconds since 1970-01-01T00:00:00 UTC */
+  double sample_rate;    /* Hz */
+  int64_t first_sample;  /* where the trace begins in `samples`, in elements */
+  int64_t nsamples;
+  int32_t quality;       /* data quality indicator character: 'D', 'R', 'Q' or 'M' */
+  char network[4], station[8], location[4], channel[4]; /* NUL terminated, as in vp_mseed_record */
+} vp_mseed_trace;
+enum { VP_MSEED_ENCODE_CHUNK = 2048 };  /* samples per chunk of the Steim packer: sizes around it take other paths */
+enum { VP_MSEED_ENCODE_STAGES = 6 };    /* classify, chunk maps, compose, emit, pack, plain */
+int vp_mseed_encode(int device_id, const void* samples, int samples_mem, int sample_kind, const vp_mseed_trace* traces,
+                    int64_t n_traces, int reclen, int encoding, int big_endian, int b1001_mode, uint8_t* out_host,
+                    size_t out_cap, size_t* out_bytes, int64_t* n_records, int64_t* bad_trace, int64_t* bad_sample);
+/* The SEED sample-rate factor and multiplier of `rate` (host only): the smallest m in 1..32767 with rate * m an integer in
+ * 1..32767 gives (rate * m, 1 if m == 1 else -m); else an integer period 1 / rate in 1..32767 gives (-1 / rate, 1); the pair
+ * must give `rate` back exactly, anything else is VP_ERR_INVALID. */
+int vp_mseed_rate_fields(double rate, int32_t* factor, int32_t* multiplier);
+/* The 64-byte headers of the records of one trace (host only, no GPU, callable from any thread): record r holds
+ * rec_count[r] samples from the trace's sample rec_first[r], and gets sequence number first_sequence + r (modulo 10^6).
+ * headers: n_records * 64 bytes.  b1001_mode as above, decided over these records.  VP_ERR_INVALID as for vp_mseed_encode;
+ * a rec_count beyond 65535 too. */
+int vp_mseed_record_headers(const vp_mseed_trace* trace, const int64_t* rec_first, const int64_t* rec_count,
+                            int64_t n_records, int64_t first_sequence, int reclen, int encoding, int big_endian,
+                            int b1001_mode, uint8_t* headers);
+/* Mean kernel time (ms, HIP events, after warm-up) of each stage of `iters` encodes of device-resident samples:
+ * ms[VP_MSEED_ENCODE_STAGES] = classify, chunk maps, compose, emit, pack (Steim; 0 otherwise), plain (0 for Steim).  Bench only. */
+int vp_mseed_encode_bench(int device_id, const void* samples_dev, int sample_kind, const vp_mseed_trace* traces,
+                          int64_t n_traces, int reclen, int encoding, int big_endian, int iters, float* ms);
+int vp_mseed_encode_release_scratch(int device_id, size_t* bytes_freed);
+
+/* ---------------------------------------------------------------------------------------------
  * Sampling-rate conversion by an integer factor, on the device: what SeisBench's annotate() does to a trace whose rate
  * is an integer multiple of the model's -- trace.filter("lowpass", freq = new Nyquist, zerophase = True), then
  * trace.decimate(factor, no_filter = True) -- and volpick_amd/resample.py restates on the host with scipy:

@@ -16,7 +16,7 @@ from .models import EQTransformer, PhaseNet, WaveformModel  # noqa: F401
 from .picks import ClassifyOutput, Detection, DetectionList, Pick, PickList  # noqa: F401
 from .stream import Stream, Trace, UTCDateTime, pinned_array, to_device  # noqa: F401
 from ._lib import VolpickHipError  # noqa: F401
-from .io import plan_file_blocks, read, read_many, scan_segments  # noqa: F401
+from .io import plan_file_blocks, read, read_many, scan_segments, write_mseed  # noqa: F401
 from .files import classify_files  # noqa: F401
 from .convert import bank_from_mseed, bank_from_streams, plan_event  # noqa: F401
 from .attributes import bank_attributes, pick_attributes, plan_rows  # noqa: F401

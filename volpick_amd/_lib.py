@@ -105,6 +105,24 @@ class VpMseedRecord(C.Structure):
 VP_SAMPLES_INT32, VP_SAMPLES_FLOAT32, VP_SAMPLES_FLOAT64 = 0, 1, 2
 VP_MSEED_TABLE_BYTES_PER_RECORD = 32
 
+
+class VpMseedTrace(C.Structure):
+    _fields_ = [
+        ("start_us", C.c_int64),
+        ("sample_rate", C.c_double),
+        ("first_sample", C.c_int64),
+        ("nsamples", C.c_int64),
+        ("quality", C.c_int32),
+        ("network", C.c_char * 4),
+        ("station", C.c_char * 8),
+        ("location", C.c_char * 4),
+        ("channel", C.c_char * 4),
+    ]
+
+
+VP_MSEED_ENCODE_CHUNK = 2048
+VP_MSEED_ENCODE_STAGES = 6
+
 VP_DETREND_DEMEAN, VP_DETREND_LINEAR, VP_DETREND_SIMPLE = 0, 1, 2
 
 VP_ATTR_DEMEAN, VP_ATTR_MAX_WINDOW, VP_ATTR_OUT = 1, 2048, 14
@@ -255,6 +273,19 @@ SIGNATURES = {
         [C.c_int, C.c_void_p, C.c_size_t, C.POINTER(VpMseedRecord), _I64P, C.c_int64, C.c_int, C.c_void_p, C.c_int64,
          C.c_int, _FP],
     ),
+    "vp_mseed_encode": (
+        C.c_int,
+        [C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(VpMseedTrace), C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
+         C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), _I64P, _I64P, _I64P],
+    ),
+    "vp_mseed_rate_fields": (C.c_int, [C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "vp_mseed_record_headers": (
+        C.c_int, [C.POINTER(VpMseedTrace), _I64P, _I64P, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p],
+    ),
+    "vp_mseed_encode_bench": (
+        C.c_int, [C.c_int, C.c_void_p, C.c_int, C.POINTER(VpMseedTrace), C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _FP],
+    ),
+    "vp_mseed_encode_release_scratch": (C.c_int, [C.c_int, C.POINTER(C.c_size_t)]),
     "vp_decimate_lowpass": (
         C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int64, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_void_p, C.c_int64],
     ),

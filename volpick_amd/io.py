@@ -11,18 +11,23 @@ decoder in the product -- without a GPU ``read`` of a miniSEED file raises.  SAC
 header plus raw float32 samples and need no kernel.
 
 ``stream_to_array`` is the array-assembly rule of volpick/data/convert.py:26-70.
+
+``write_mseed()`` is the other direction, the reference's ``waveforms.write(path, format="MSEED")``
+(volpick/data/data.py:1353): miniSEED 2 records packed on the GPU (``vp_mseed_encode``: Steim-1/2 and the plain
+encodings), headers built by the library on the host; no host encoder either.
 """
 from __future__ import annotations
 
 import ctypes as C
 import os
 import struct
+import threading
 from datetime import datetime, timedelta, timezone
 
 import numpy as np
 
 from . import _lib
-from ._device import release_scratch
+from ._device import device_backing, release_scratch, upload_samples
 from .stream import Stream, Trace, UTCDateTime, block_start, component_index, sample_offset, warn_short_fragment
 
 _REC_DTYPE = np.dtype(
@@ -346,6 +351,209 @@ def read_many(sources, device=0, dtype=None, device_resident=True):
 def release_decode_scratch(device=0):
     """Free the device scratch `read_mseed` keeps per device between calls (vp_mseed_release_scratch); returns the bytes freed."""
     return release_scratch("vp_mseed_release_scratch", device)
+
+
+# ----------------------------------------------------------------------------- traces to miniSEED
+WRITE_RECLEN, WRITE_BYTEORDER, WRITE_QUALITY = 4096, ">", "D"  # ObsPy's defaults
+WRITE_ENCODINGS = {"int32": (11, 10, 3, 1), "int16": (1,), "float32": (4,), "float64": (5,)}  # the first is the type's default
+_WRITE_KINDS = {"int32": _lib.VP_SAMPLES_INT32, "int16": _lib.VP_SAMPLES_INT32, "float32": _lib.VP_SAMPLES_FLOAT32,
+                "float64": _lib.VP_SAMPLES_FLOAT64}
+_CODE_FIELDS = (("network", 2), ("station", 5), ("location", 2), ("channel", 3))
+
+
+def rate_fields(rate):
+    """The SEED sample-rate factor and multiplier the writer stores for ``rate`` (``vp_mseed_rate_fields``, host only): the
+    smallest ``m`` in 1..32767 with ``rate * m`` an integer in 1..32767 gives ``(rate * m, 1 if m == 1 else -m)``; else an
+    integer period ``1 / rate`` in 1..32767 gives ``(-1 / rate, 1)``.  ``ValueError`` where no pair gives ``rate`` back exactly."""
+    f, m = C.c_int32(0), C.c_int32(0)
+    if _lib.load().vp_mseed_rate_fields(float(rate), C.byref(f), C.byref(m)) < 0:
+        raise ValueError(f"sampling rate {float(rate)!r} has no exact SEED factor / multiplier pair")
+    return f.value, m.value
+
+
+def _sample_type(tr):
+    """The name of a trace's sample type without touching a device trace's host copy; masked traces are refused."""
+    dev = device_backing(tr)
+    if dev is not None:
+        return str(dev.dtype).replace("torch.", "")
+    if np.ma.isMaskedArray(tr.data):
+        raise ValueError(f"{tr.id}: masked traces cannot be written; split the stream at its gaps first")
+    return np.asarray(tr.data).dtype.name
+
+
+def plan_write(stream_or_trace, reclen=None, encoding=None, byteorder=None, dataquality=None):
+    """What :func:`write_mseed` will write, decided on the host before any GPU work: one dict per trace with samples, in
+    stream order -- ``trace``, ``dtype`` (the sample type's name), ``kind`` (the library's sample kind), ``reclen``,
+    ``encoding``, ``byteorder`` (``">"`` / ``"<"``), ``dataquality`` and the rate's ``factor`` / ``multiplier``.  Per trace a
+    keyword wins over ``stats.mseed`` (what ``read`` recorded), which wins over ObsPy's defaults; every refusal of
+    :func:`write_mseed` is raised here."""
+    traces = [stream_or_trace] if isinstance(stream_or_trace, Trace) or not hasattr(stream_or_trace, "__iter__") else list(stream_or_trace)
+    plan = []
+    for tr in traces:
+        if int(tr.stats.npts) == 0:
+            continue
+        dtype = _sample_type(tr)
+        if dtype not in WRITE_ENCODINGS:
+            raise ValueError(f"{tr.id}: samples of type {dtype} cannot be written (int32, int16, float32 and float64 can; "
+                             "text records are not written)")
+        was = tr.stats.get("mseed") or {}
+        enc = encoding
+        if enc is None:
+            enc = was.get("encoding")
+            if enc not in WRITE_ENCODINGS[dtype]:  # e.g. a Steim trace decoded or filtered to float32: the type decides
+                enc = WRITE_ENCODINGS[dtype][0]
+        elif enc not in WRITE_ENCODINGS[dtype]:
+            raise ValueError(f"{tr.id}: encoding {enc!r} cannot hold {dtype} samples (allowed: "
+                             f"{', '.join(str(e) for e in WRITE_ENCODINGS[dtype])})")
+        rl = reclen
+        if rl is None:
+            rl = was.get("record_length")
+            if not (isinstance(rl, int) and 128 <= rl <= 65536 and rl & (rl - 1) == 0):  # (a miniSEED 3 record has any length)
+                rl = WRITE_RECLEN
+        elif not (isinstance(rl, (int, np.integer)) and 128 <= rl <= 65536 and int(rl) & (int(rl) - 1) == 0):
+            raise ValueError(f"reclen {rl!r} is not a power of two in 128..65536")
+        if int(enc) == 11 and int(rl) == 65536:
+            raise ValueError("reclen 65536 with encoding 11: a record could hold more samples than the header's 16-bit count")
+        bo = byteorder if byteorder is not None else was.get("byteorder") or WRITE_BYTEORDER
+        bo = {1: ">", 0: "<", ">": ">", "<": "<"}.get(bo)
+        if bo is None:
+            raise ValueError(f"byteorder {byteorder!r} is none of '>', '<', 1, 0")
+        q = dataquality if dataquality is not None else was.get("dataquality") or WRITE_QUALITY
+        if q not in ("D", "R", "Q", "M"):
+            raise ValueError(f"dataquality {q!r} is none of D, R, Q, M")
+        for field, width in _CODE_FIELDS:
+            code = str(tr.stats[field])
+            if len(code.encode("ascii", "replace")) > width:
+                raise ValueError(f"{tr.id}: {field} {code!r} is longer than {width} characters")
+        rate = float(tr.stats.sampling_rate)
+        if not rate > 0:
+            raise ValueError(f"{tr.id}: sampling rate {rate!r} is not positive")
+        try:
+            factor, mult = rate_fields(rate)
+        except ValueError as e:
+            raise ValueError(f"{tr.id}: {e}") from None
+        plan.append(dict(trace=tr, dtype=dtype, kind=_WRITE_KINDS[dtype], reclen=int(rl), encoding=int(enc), byteorder=bo,
+                         dataquality=q, factor=factor, multiplier=mult))
+    return plan
+
+
+def _encode_group(group, b1001, device):
+    """One ``vp_mseed_encode`` for consecutive planned traces that share sample kind, encoding, record length and byte
+    order: ``(bytes of the records, number of records)``.  Device traces are read where they lie -- the call gets the lowest
+    address as its base and every trace's offset from it -- host traces are uploaded first."""
+    import torch
+
+    lib = _lib.load()
+    dev = torch.device("cuda", int(device))
+    tensors = []
+    for p in group:
+        d = device_backing(p["trace"])
+        if d is None:
+            a = p["trace"].data  # (int16 travels as int32: upload_samples would make it float32)
+            d = upload_samples(a.astype(np.int32) if p["dtype"] == "int16" else a, dev, "masked traces cannot be written")
+        elif d.device != dev:
+            d = d.to(dev)
+        if d.dtype == torch.int16:
+            d = d.to(torch.int32)
+        tensors.append(d.contiguous())
+    torch.cuda.current_stream(dev).synchronize()  # the library works on the null stream: the samples are complete first
+    itemsize = tensors[0].element_size()
+    base = min(t.data_ptr() for t in tensors)
+    traces = (_lib.VpMseedTrace * len(group))()
+    for k, (p, t) in enumerate(zip(group, tensors)):
+        tr = p["trace"]
+        assert (t.data_ptr() - base) % itemsize == 0
+        traces[k].start_us, traces[k].sample_rate = UTCDateTime(tr.stats.starttime)._us, float(tr.stats.sampling_rate)
+        traces[k].first_sample, traces[k].nsamples = (t.data_ptr() - base) // itemsize, int(t.shape[0])
+        traces[k].quality = ord(p["dataquality"])
+        for field, _ in _CODE_FIELDS:
+            setattr(traces[k], field, str(tr.stats[field]).encode("ascii", "replace"))
+    reclen, enc = group[0]["reclen"], group[0]["encoding"]
+    # room for the worst case, one difference per word, so the call never has to be repeated
+    per = 15 * (reclen // 64 - 1) - 2 if enc in (10, 11) else (reclen - 64) // {1: 2, 3: 4, 4: 4, 5: 8}[enc]
+    cap = sum(-(-int(t.shape[0]) // per) for t in tensors) * reclen
+    out = _host_buffer(cap)
+    nbytes, nrec, bad_trace, bad_sample = C.c_size_t(0), C.c_int64(0), C.c_int64(-1), C.c_int64(-1)
+    rc = lib.vp_mseed_encode(dev.index, C.c_void_p(base), _lib.VP_MEM_DEVICE, group[0]["kind"], traces, len(group), reclen, enc,
+                             int(group[0]["byteorder"] == ">"), b1001, _lib.ptr(out), cap, C.byref(nbytes), C.byref(nrec),
+                             C.byref(bad_trace), C.byref(bad_sample))
+    if rc < 0 and bad_trace.value >= 0:
+        why = ("does not fit int16 (encoding 1)" if enc == 1 else
+               "differs from the sample before it by more than Steim-2's 30 bits hold (encoding 11)")
+        raise ValueError(f"{group[bad_trace.value]['trace'].id}: sample {bad_sample.value} {why}; nothing was written")
+    _lib.check(rc, "vp_mseed_encode")
+    assert nbytes.value <= cap
+    return out[:nbytes.value], int(nrec.value)
+
+
+_HOST = threading.local()
+
+
+def _host_buffer(nbytes):
+    """The calling thread's output buffer of at least ``nbytes`` (grow-only; a write leaves a copy of what it used): pages
+    that were touched once are not faulted in again by the next write."""
+    buf = getattr(_HOST, "buf", None)
+    if buf is None or len(buf) < nbytes:
+        buf = _HOST.buf = np.empty(nbytes + nbytes // 4, np.uint8)
+    return buf
+
+
+def write_mseed(stream_or_trace, target=None, reclen=None, encoding=None, byteorder=None, dataquality=None,
+                blockette1001=None, device=0):
+    """A ``Stream`` or ``Trace`` as miniSEED 2 records, packed on the GPU (``vp_mseed_encode``): what the reference does with
+    ``waveforms.write(path, format="MSEED")``.  ``target`` is a path or a binary file object; with ``None`` the call returns the
+    ``bytes``, otherwise the number of records written.  Traces are written in stream order, empty ones are skipped, sequence
+    numbers run from 1 through the file.
+
+    Per trace a keyword wins over ``stats.mseed`` (``encoding``, ``byteorder``, ``record_length``, ``dataquality`` as ``read``
+    recorded them), which wins over ObsPy's defaults: 4096-byte big-endian records of quality ``D``.  The default encoding
+    follows the sample type: int32 -> 11 (Steim-2; 10, 3 and 1 on request), int16 -> 1, float32 -> 4, float64 -> 5.  A
+    ``stats.mseed["encoding"]`` that no longer matches the sample type -- a Steim trace decoded or filtered to float32 -- gives
+    way to the type's default; ObsPy refuses such a trace instead.  ``blockette1001``: ``None`` adds blockette 1001 to every
+    record of a trace as soon as one of its records starts off the 100-microsecond grid, ``True`` / ``False`` force it.
+
+    ``ValueError`` before any GPU work: other sample types and text records, an encoding the sample type cannot take
+    (encoding 2 among them), masked traces, ``reclen`` not a power of two in 128..65536, a network / station / location /
+    channel longer than 2 / 5 / 2 / 3 characters, a sampling rate that is not positive or has no exact SEED factor /
+    multiplier pair (:func:`rate_fields`).  ``ValueError`` from the device, with nothing written to ``target``: a Steim-2
+    difference beyond 30 bits or, under encoding 1, an int32 sample beyond int16 -- the message names the trace and its lowest
+    such sample.  One deviation from a strict packer: a trace whose *first* sample does not fit 30 bits is written under
+    Steim-2 with a first difference of 0 (decoders start from the record's X0 and never read it).
+
+    A device-backed trace is read where it lies and its host copy is not materialised; a host trace is uploaded to
+    ``cuda:device`` and takes the same kernels -- there is no host encoder.  All traces that share sample kind, encoding,
+    record length and byte order go through one set of launches.  :func:`release_encode_scratch` frees the device scratch."""
+    plan = plan_write(stream_or_trace, reclen, encoding, byteorder, dataquality)
+    b1001 = -1 if blockette1001 is None else int(bool(blockette1001))
+    parts, n_records, a = [], 0, 0
+    while a < len(plan):
+        b = a + 1
+        while b < len(plan) and all(plan[b][k] == plan[a][k] for k in ("kind", "encoding", "reclen", "byteorder")):
+            b += 1
+        out, nrec = _encode_group(plan[a:b], b1001, device)
+        if n_records:  # a later group: its sequence numbers go on where the group before stopped
+            seq = (np.arange(nrec) + n_records + 1) % 1_000_000
+            digits = (seq[:, None] // 10 ** np.arange(5, -1, -1)) % 10 + ord("0")
+            out.reshape(nrec, plan[a]["reclen"])[:, :6] = digits.astype(np.uint8)
+        parts.append(out.tobytes())  # (the buffer is the next group's too)
+        n_records += nrec
+        a = b
+    data = b"".join(parts)
+    if target is None:
+        return data
+    if hasattr(target, "write"):
+        target.write(data)
+    else:
+        with open(os.fspath(target), "wb") as f:
+            f.write(data)
+    return n_records
+
+
+def release_encode_scratch(device=0):
+    """Free the device scratch `write_mseed` keeps per device between calls (vp_mseed_encode_release_scratch) and the calling
+    thread's host buffer; returns the device bytes freed."""
+    _HOST.buf = None
+    return release_scratch("vp_mseed_encode_release_scratch", device)
 
 
 def read_sac(source):

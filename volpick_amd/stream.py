@@ -187,6 +187,14 @@ def trim_cut(starttime, npts, rate, t_start=None, t_end=None):
     return first, count
 
 
+def _write(stream_or_trace, target, format, kw):
+    if str(format).upper() != "MSEED":
+        raise ValueError(f"unsupported output format {format!r} (MSEED is implemented)")
+    from .io import write_mseed
+
+    return write_mseed(stream_or_trace, target, **kw)
+
+
 class Stats(dict):
     """Trace header; attribute and item access, derived npts / delta / endtime."""
 
@@ -319,6 +327,11 @@ class Trace:
 
         return trace_trigger(self, type, sta, lta)
 
+    def write(self, target, format="MSEED", **kw):
+        """ObsPy's ``Trace.write`` for miniSEED: ``volpick_amd.io.write_mseed(self, target, **kw)``.  A device-backed trace is
+        packed from where it lies; any other ``format`` is refused."""
+        return _write(self, target, format, kw)
+
     def __len__(self):
         return int(self.stats["npts"])
 
@@ -383,6 +396,11 @@ class Stream:
         for tr in self.traces:
             tr.trigger(type, sta=sta, lta=lta)
         return self
+
+    def write(self, target, format="MSEED", **kw):
+        """ObsPy's ``Stream.write`` for miniSEED: ``volpick_amd.io.write_mseed(self, target, **kw)``, the traces in stream order
+        through one set of launches; any other ``format`` is refused."""
+        return _write(self, target, format, kw)
 
     def sort(self, keys=("network", "station", "location", "channel", "starttime")):
         self.traces.sort(key=lambda t: tuple(str(t.stats[k]) if k != "starttime" else t.stats[k]._us for k in keys))
