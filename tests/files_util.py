@@ -1,7 +1,9 @@
 """Station layouts and file bytes shared by the file-pipeline tests (tests/test_files_plan_cpu.py,
-tests/test_gpu_classify_files.py): every way a miniSEED file's traces can sit in their station blocks."""
+tests/test_gpu_classify_files.py, the file route of tests/test_group_stream_cpu.py): every way a miniSEED file's traces can sit
+in their station blocks, and a block plan's cells by sample number."""
 import numpy as np
 
+import volpick_amd.io as vio
 from oracle import mseed as OM
 from tests.mseed_util import T0, file_bytes, seismogram
 
@@ -39,6 +41,42 @@ def layouts(n=7001, seed=3):
 def layout_bytes(traces, version=2, **kw):
     """The layout as one file: miniSEED 2 (``file_bytes``' arguments) or miniSEED 3 (``write_mseed3``'s)."""
     return file_bytes(traces, **kw) if version == 2 else OM.write_mseed3(traces, **kw)
+
+
+def table_layout(table, seg):
+    """The segments of ``scan_segments``' table as a layout of tests/stream_restate.py, in table order: each segment's samples
+    are 1 + their global sample number (0 is then a cell nothing fed), so that a block cell names the record and the offset it
+    came from."""
+    ns = table["nsamples"].astype(np.int64)
+    base = np.cumsum(ns) - ns
+    text = lambda field, a: table[field][a].decode()  # noqa: E731
+    return [(text("network", a), text("station", a), text("location", a), text("channel", a), int(table["start_us"][a]),
+             np.arange(base[a] + 1, base[a] + 1 + int(ns[a:b].sum()), dtype=np.float32))
+            for a, b in zip(*vio._segment_ranges(seg))]
+
+
+def planned_blocks(table, plan):
+    """The blocks of ``io.plan_file_blocks``' plan as arrays: every record writes 1 + its global sample numbers where
+    ``out_index`` sends it.  No two records may share a cell, none may land outside the blocks, no two blocks overlap."""
+    ns = table["nsamples"].astype(np.int64)
+    base = np.cumsum(ns) - ns
+    cells, writes = np.zeros(plan.n_out, np.float32), np.zeros(plan.n_out, np.int32)
+    for r in np.flatnonzero(plan.out_index >= 0):
+        lo = int(plan.out_index[r])
+        cells[lo:lo + ns[r]] = np.arange(base[r] + 1, base[r] + 1 + ns[r], dtype=np.float32)
+        writes[lo:lo + ns[r]] += 1
+    assert writes.max(initial=0) <= 1  # no two records share a cell
+    out, claimed = [], np.zeros(plan.n_out, bool)
+    for b in plan.blocks:
+        c, n = b["shape"]
+        if b["offset"] < 0:
+            out.append(np.zeros((c, n), np.float32))
+            continue
+        assert b["offset"] % vio.BLOCK_ALIGN == 0 and not claimed[b["offset"]:b["offset"] + c * n].any()
+        claimed[b["offset"]:b["offset"] + c * n] = True
+        out.append(cells[b["offset"]:b["offset"] + c * n].reshape(c, n))
+    assert not writes[~claimed].any()  # and none lands outside the blocks
+    return out
 
 
 def log_channel_bytes(n=4000, reclen=512):

@@ -44,11 +44,12 @@ def _component(letter, component_order):
 
 
 def _blocks(layout, component_order, sampling_rate, in_samples):
-    """One dict per block: trace_id, start_us, data (C, N) float32, fast (every component is exactly one trace that spans
-    the block, and no other trace of a known component touches it)."""
+    """``(blocks, dropped)``.  One dict per block: trace_id, start_us, data (C, N) float32, fast (every component is exactly
+    one trace that spans the block, and no other trace of a known component touches it); ``dropped``: how many runs were
+    shorter than ``in_samples``."""
     rate = Fraction(sampling_rate)
     n_comp = len(component_order)
-    out = []
+    out, dropped = [], 0
     for (net, sta, loc, _), traces in _instruments(layout):
         t_start = min(start_us for _, _, start_us, _ in traces)
         pieces = []  # (first sample, length, component or -1, position in the stream, samples)
@@ -65,6 +66,7 @@ def _blocks(layout, component_order, sampling_rate, in_samples):
                 runs.append([s0, s0 + n])
         for b0, b1 in runs:
             if b1 - b0 < in_samples:
+                dropped += 1
                 continue
             data = np.zeros((n_comp, b1 - b0), np.float32)
             best = np.full((n_comp, b1 - b0), -1, np.int64)  # rank of the trace whose sample the cell holds
@@ -83,17 +85,22 @@ def _blocks(layout, component_order, sampling_rate, in_samples):
             fast = sorted(touching) == [(c, True) for c in range(n_comp)]
             out.append(dict(trace_id=f"{net}.{sta}.{loc}", start_us=t_start + round(Fraction(b0 * 1_000_000) / rate), data=data,
                             fast=fast))
-    return out
+    return out, dropped
 
 
 def restate(layout, component_order="ZNE", sampling_rate=100, in_samples=3001):
     """[(trace_id, block_start_us, float32 (C, N) array)], instruments sorted, runs ascending."""
-    return [(b["trace_id"], b["start_us"], b["data"]) for b in _blocks(layout, component_order, sampling_rate, in_samples)]
+    return [(b["trace_id"], b["start_us"], b["data"]) for b in _blocks(layout, component_order, sampling_rate, in_samples)[0]]
 
 
 def full_rows(layout, component_order="ZNE", sampling_rate=100, in_samples=3001):
     """One bool per block of ``restate``: the block is nothing but one full-length trace per component."""
-    return [b["fast"] for b in _blocks(layout, component_order, sampling_rate, in_samples)]
+    return [b["fast"] for b in _blocks(layout, component_order, sampling_rate, in_samples)[0]]
+
+
+def short_runs(layout, component_order="ZNE", sampling_rate=100, in_samples=3001):
+    """How many runs ``restate`` dropped as shorter than ``in_samples``: one warning each in the code under test."""
+    return _blocks(layout, component_order, sampling_rate, in_samples)[1]
 
 
 # --------------------------------------------------------------------------- seeded irregular layouts

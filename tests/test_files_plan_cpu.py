@@ -1,7 +1,7 @@
 """Host side of ``classify_files`` (no GPU): the library's ordered record table (``vp_mseed_scan_segments``) against
-``scan_mseed`` + ``_segments``, and the block plan from headers (``io.plan_file_blocks``) against ``models._group_stream``
-run on host traces whose samples are their own global sample numbers, so that every block cell names the record and the
-offset it came from."""
+``scan_mseed`` + ``_segments``, and the block plan from headers (``io.plan_file_blocks``) against the independent restatement
+of the assembly rule (tests/stream_restate.py) and against ``models._group_stream``, both run on traces whose samples are
+their own global sample numbers, so that every block cell names the record and the offset it came from."""
 import ctypes as C
 import re
 import warnings
@@ -12,7 +12,8 @@ import pytest
 
 import volpick_amd.io as vio
 from oracle import mseed as OM
-from tests.files_util import PERIOD_US, layout_bytes, layouts, log_channel_bytes, trace
+from tests import stream_restate as R
+from tests.files_util import PERIOD_US, layout_bytes, layouts, log_channel_bytes, planned_blocks, table_layout, trace
 from tests.mseed_util import T0, file_bytes, mixed_file_bytes, seismogram
 from volpick_amd import Stream, Trace, UTCDateTime, _lib
 from volpick_amd.models import _group_stream
@@ -150,29 +151,10 @@ def restated_blocks(table, seg, order, rate, in_samples):
     return list(_group_stream(st, order, rate, True, in_samples))
 
 
-def planned_blocks(table, plan):
-    ns = table["nsamples"].astype(np.int64)
-    base = np.cumsum(ns) - ns
-    cells, writes = np.zeros(plan.n_out, np.float32), np.zeros(plan.n_out, np.int32)
-    for r in np.flatnonzero(plan.out_index >= 0):
-        lo = int(plan.out_index[r])
-        cells[lo:lo + ns[r]] = np.arange(base[r] + 1, base[r] + 1 + ns[r], dtype=np.float32)
-        writes[lo:lo + ns[r]] += 1
-    assert writes.max(initial=0) <= 1  # no two records share a cell
-    out, claimed = [], np.zeros(plan.n_out, bool)
-    for b in plan.blocks:
-        c, n = b["shape"]
-        if b["offset"] < 0:
-            out.append(np.zeros((c, n), np.float32))
-            continue
-        assert b["offset"] % vio.BLOCK_ALIGN == 0 and not claimed[b["offset"]:b["offset"] + c * n].any()
-        claimed[b["offset"]:b["offset"] + c * n] = True
-        out.append(cells[b["offset"]:b["offset"] + c * n].reshape(c, n))
-    assert not writes[~claimed].any()  # and none lands outside the blocks
-    return out
-
-
 def assert_plan_matches(buf, order="ZNE", rate=100, in_samples=3001):
+    """The plan against two expectations.  ``tests/stream_restate.py`` shares no code with the package: it says which blocks
+    there are, where they start, what every cell holds and how many runs were too short.  ``_group_stream`` asks the same
+    planner as the plan, so agreeing with it says only that ``out_index`` places records where the assembly places samples."""
     table, seg = vio.scan_segments(buf)
     assert int(table["nsamples"].sum()) < 1 << 24  # float32 holds every sample number
     with warnings.catch_warnings(record=True) as w_want:
@@ -184,6 +166,13 @@ def assert_plan_matches(buf, order="ZNE", rate=100, in_samples=3001):
     assert plan.reason is None
     assert [str(w.message) for w in w_got] == [str(w.message) for w in w_want] and plan.short_runs == len(w_want)
     got = planned_blocks(table, plan)
+    layout = table_layout(table, seg)
+    rule = R.restate(layout, order, rate, in_samples)
+    assert len(got) == len(rule)
+    for b, cells, (trace_id, start_us, data) in zip(plan.blocks, got, rule):
+        assert (b["trace_id"], b["start_us"], b["shape"]) == (trace_id, start_us, data.shape)
+        assert cells.shape == data.shape and np.array_equal(cells, data)
+    assert plan.short_runs == len(w_got) == R.short_runs(layout, order, rate, in_samples)
     assert len(got) == len(want)
     for b, cells, grp in zip(plan.blocks, got, want):
         data = np.asarray(grp["data"])

@@ -3,11 +3,13 @@
 The order in which the host path issues uploads, submits and collects over the device contexts and submit slots is what
 overlaps one block's copy with another's compute.  The result tests (long against unsplit, multi against per-block, many
 stations against single calls, pinned against pageable) cannot see it move.  tests/golden/classify_call_trace.json holds, for
-four calls, one row per vp_annotate / vp_classify_submit / vp_classify_collect / vp_classify_multi / vp_pick_rows (function,
+five calls (four of classify() / annotate(), one of classify_files(), whose files take the long route, the resident route and
+the way through read()), one row per vp_annotate / vp_classify_submit / vp_classify_collect / vp_classify_multi / vp_pick_rows (function,
 context, slot, sample count or block lengths, number of trigger specs, capacity, overlap, blinding, stacking, batch) and
 the pick lists (times in microseconds, the float32 value's bits).  It was recorded on the GPU from the commit BEFORE the
 consolidation of volpick_amd/models.py with tools/record_classify_call_trace.py, which also holds the cases and the recorder:
-a forwarding stand-in for the loaded library (`volpick_amd._lib._lib`), installed for the duration of the call.
+a forwarding stand-in for the loaded library (`volpick_amd._lib._lib`), installed for the duration of the call.  The
+classify_files() case was recorded from the commit before that call's loop over the blocks became classify()'s own.
 
 What a disturbed schedule looks like: a long block's collects ahead of the next block's submits (the upload no longer runs
 beside the last segments), both blocks on one set of submit slots, the block behind cut as finely as the first, short host
@@ -72,3 +74,7 @@ def test_the_cases_exercise_every_route(golden):
     eqt = [r for r in golden["eqtransformer_classify"]["calls"] if r[0] == "classify_submit" and r[col["n_specs"]] == 0]
     assert {r[col["context"]] for r in eqt} == {0, 1, 2, 3}
     assert [r[0] for r in golden["phasenet_annotate"]["calls"]].count("annotate") == 1
+    files = golden["phasenet_classify_files"]
+    assert sum(r[0] == "classify_submit" and r[col["n_specs"]] == 0 for r in files["calls"]) == 6  # file 0: one long block
+    assert [r[col["samples"]] for r in files["calls"] if r[0] == "classify_multi"] == [[20000, 15000], [20000, 15000, 8000]]
+    assert {p[0] for p in files["picks"]} == {0, 1, 2} and any(p[1] == "XX.H2." for p in files["picks"])  # the 50 Hz trace, resampled

@@ -1,4 +1,5 @@
-"""models._group_stream (host path) against tests/stream_restate.py: seeded irregular layouts and hand cases.
+"""models._group_stream (host path) against tests/stream_restate.py: seeded irregular layouts and hand cases; at the end
+the file route (io.plan_file_blocks), which asks the same planner, beside it on the same layouts.
 
 Everything is compared for equality -- block count, trace id, start in microseconds, shape, the bits of the float32 block:
 the assembly copies samples and casts each once, so there is no rounding to allow for."""
@@ -8,7 +9,10 @@ import numpy as np
 import pytest
 
 import volpick_amd as va
+import volpick_amd.io as vio
 from tests import stream_restate as R
+from tests.files_util import layout_bytes, planned_blocks, table_layout
+from tests.files_util import trace as file_trace
 from volpick_amd.models import _group_stream, _Rows, _trigger_columns
 
 T = 301  # the issue's window length for the CPU layouts: large enough for every relation between pieces, small enough for 300
@@ -268,3 +272,41 @@ def test_the_rows_form_is_taken_exactly_for_three_full_length_traces(name, layou
     assert len(got) == 1 and isinstance(got[0]["data"], _Rows) == rows == R.full_rows(layout, "ZNE", 100, T)[0]
     assert_blocks_equal(got, R.restate(layout, "ZNE", 100, T), name)
     assert_blocks_equal(grouped(layout[::-1]), R.restate(layout[::-1], "ZNE", 100, T), name + ", reversed")
+
+
+# --------------------------------------------------------------------------- one planner, two callers
+# ``_group_stream`` and the file route (``io.scan_segments`` + ``io.plan_file_blocks``) ask ``stream.plan_blocks`` which samples
+# form a block.  Before they shared it each worded these relations in its own way: held here, through both, against the rule.
+def n(channel, samples, first=0):
+    return file_trace(channel, samples, first, np.random.default_rng(samples + first))
+
+
+@pytest.mark.parametrize("name,traces,order,shapes,short", [
+    ("a piece that ends exactly at the run's end", [n("HHZ", 500), n("HHN", 300, 200)], "ZNE", [(3, 500)], 0),
+    ("a piece that starts exactly at the end of the run so far: it merges", [n("HHZ", 400), n("HHN", 350, 400)], "ZNE", [(3, 750)], 0),
+    ("a piece one sample past the run's end: a new run", [n("HHZ", 400), n("HHN", 350, 401)], "ZNE", [(3, 400), (3, 350)], 0),
+    ("... which is too short", [n("HHZ", 400), n("HHN", 300, 401)], "ZNE", [(3, 400)], 1),
+    ("an unknown component bridges two known ones", [n("HHZ", 350), n("HHX", 100, 350), n("HHN", 350, 450)], "ZNE", [(3, 800)], 0),
+    ("... and without it they are two runs", [n("HHZ", 350), n("HHN", 350, 450)], "ZNE", [(3, 350), (3, 350)], 0),
+    ("1 / 2 / 3 are N / E / Z", [n("HH3", 400), n("HH1", 350, 50), n("HH2", 450)], "ZNE", [(3, 450)], 0),
+    ("2 is E, which 'ZN' has no row for: it still extends the run", [n("HH3", 400), n("HH1", 350, 50), n("HH2", 450)], "ZN", [(2, 450)], 0),
+])
+def test_both_callers_of_the_planner_equal_the_restated_rule(lib, name, traces, order, shapes, short):
+    table, seg = vio.scan_segments(layout_bytes(traces))
+    layout = table_layout(table, seg)  # samples: 1 + their number in the file
+    want = R.restate(layout, order, 100, T)
+    assert [data.shape for _, _, data in want] == shapes and R.short_runs(layout, order, 100, T) == short, name
+    with warnings.catch_warnings(record=True) as warned:
+        warnings.simplefilter("always")
+        got = list(_group_stream(to_stream(layout), order, 100.0, True, T))
+    assert_blocks_equal(got, want, name + ", assembly")
+    assert len(warned) == short and all(SHORT in str(w.message) for w in warned)
+    with warnings.catch_warnings(record=True) as warned:
+        warnings.simplefilter("always")
+        plan = vio.plan_file_blocks(table, seg, order, 100.0, T)
+    assert plan.reason is None and plan.short_runs == len(warned) == short and all(SHORT in str(w.message) for w in warned)
+    cells = planned_blocks(table, plan)
+    assert len(cells) == len(want), name
+    for b, c, (trace_id, start_us, data) in zip(plan.blocks, cells, want):
+        assert (b["trace_id"], b["start_us"], b["shape"]) == (trace_id, start_us, data.shape), name + ", file route"
+        assert np.array_equal(c, data), name + ", file route"

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Record tests/golden/classify_call_trace.json: the SEQUENCE of library calls behind classify() / annotate(), and their picks.
+"""Record tests/golden/classify_call_trace.json: the SEQUENCE of library calls behind classify() / annotate() / classify_files(),
+and their picks.
 
 The order in which the picker's host path issues uploads, submits and collects over the device contexts is what overlaps one
 block's copy with another's compute; no result depends on it, so no result test notices when it moves.  This fixture pins it
@@ -163,8 +164,33 @@ def case_eqtransformer_classify(record):
     return _records(record(m, lambda: m.classify(st, overlap=3000, P_threshold=0.2, S_threshold=0.2)))
 
 
+def _file(stations, extra=()):
+    """The stations' traces as int32 counts (seeded as ``_stream``'s) plus the trace dicts ``extra``: one miniSEED 2 file."""
+    from oracle import mseed as OM
+
+    traces = [dict(network=tr.stats.network, station=tr.stats.station, location=tr.stats.location, channel=tr.stats.channel,
+                   start_us=tr.stats.starttime._us, rate=tr.stats.sampling_rate, data=tr.data)
+              for k, (name, n, seed) in enumerate(stations) for tr in _station(name, n, seed, k, counts=True)]
+    return OM.write_mseed(traces + list(extra), reclen=4096, encoding=OM.ENC_INT32)
+
+
+def case_phasenet_classify_files(record):
+    """classify_files() goes through classify()'s loop, whichever way a file takes: F0 is one long block; G0, G1 are planned
+    from the headers and share one multi call; the third file has the same two stations and a 50 Hz trace, so it has no plan
+    and is read and assembled as classify() does (that trace, resampled, is a third block of the multi call)."""
+    m = _model("PhaseNet")
+    m._max_windows_per_call = WINDOW_BUDGET
+    slow = _station("H2", 4000, 925, 2, counts=True)[0]
+    slow = dict(network="XX", station="H2", location="", channel="HHZ", start_us=slow.stats.starttime._us, rate=50.0, data=slow.data)
+    files = [_file([("F0", PN_LONG, 910)]), _file([("G0", 20_000, 920), ("G1", 15_000, 921)]),
+             _file([("H0", 20_000, 922), ("H1", 15_000, 923)], [slow])]
+    outs = [_records(out) for out in record(m, lambda: m.classify_files(files, depth=2, workers=1, **PN_KW))]
+    return {key: [[k] + row for k, out in enumerate(outs) for row in out[key]] for key in ("picks", "detections")}
+
+
 CASES = {"phasenet_classify": case_phasenet_classify, "phasenet_classify_profiled": case_phasenet_classify_profiled,
-         "phasenet_annotate": case_phasenet_annotate, "eqtransformer_classify": case_eqtransformer_classify}
+         "phasenet_annotate": case_phasenet_annotate, "eqtransformer_classify": case_eqtransformer_classify,
+         "phasenet_classify_files": case_phasenet_classify_files}
 
 
 def run_case(name, install):

@@ -28,6 +28,7 @@ import numpy as np
 
 from . import _lib
 from ._device import stream_handle
+from .stream import sample_offset
 
 ATTR_ROW = np.dtype([
     ("trace", np.int32), ("flags", np.int32),
@@ -192,7 +193,7 @@ def pick_attributes(stream, picks, sampling_rate=100, component_order="ZNE", in_
         n = int(grp["data"].shape[1])
         idx, samples = [], []
         for i in by_id.get(grp["trace_id"], ()):
-            k = int(round((picks[i].peak_time - grp["starttime"]) * sampling_rate))
+            k = sample_offset(picks[i].peak_time, grp["starttime"], sampling_rate)
             if 0 <= k < n and not done[i]:
                 idx.append(i)
                 samples.append(k)

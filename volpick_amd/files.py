@@ -28,7 +28,7 @@ import numpy as np
 
 from . import _lib
 from .io import _as_bytes, _looks_like_mseed, plan_file_blocks, read, scan_segments
-from .stream import UTCDateTime, warn_short_fragment
+from .stream import UTCDateTime, block_dict, warn_short_fragment
 
 _I64P = C.POINTER(C.c_int64)
 _GROW = 1.25  # a buffer that has to grow takes a quarter more than asked: file sizes of one archive scatter by less
@@ -135,32 +135,8 @@ def plan_groups(plan, out):
     for b in plan.blocks:
         c, n = b["shape"]
         data = out[b["offset"]:b["offset"] + c * n].view(c, n) if b["offset"] >= 0 else np.zeros((c, n), np.float32)
-        groups.append(dict(data=data, starttime=UTCDateTime._from_us(b["start_us"]), trace_id=b["trace_id"],
-                           network=b["network"], station=b["station"], location=b["location"]))
+        groups.append(block_dict(data, b["network"], b["station"], b["location"], UTCDateTime._from_us(b["start_us"])))
     return groups
-
-
-def _classify_groups(model, groups, args, specs):
-    """``classify()``'s own loop over the station blocks ``groups`` (``_group_stream``'s dicts): the same routes of a
-    ``_ClassifyRun``, chosen and drained in the same order, the same records at the end."""
-    from .models import ClassifyOutput, _ClassifyRun, _records_from_columns, _torch
-
-    torch = _torch()
-    run = _ClassifyRun(model, args, specs)
-    for grp in groups:
-        if model._is_long(grp["data"].shape[1], args):
-            run.add_long(grp)
-        elif model.batch_across_blocks and torch.is_tensor(grp["data"]):
-            run.add_resident(grp)
-        else:
-            run.add_host(grp)
-    run.drain_long()
-    run.drain_host()
-    run.drain_resident()
-    t_mark = time.perf_counter()
-    picks, detections = _records_from_columns(run.cols, run.tids, run.t0s, [sp[1] for sp in specs], model.sampling_rate)
-    model._lap("emit_records_ms", t_mark)
-    return ClassifyOutput(model.name, picks=picks, detections=detections)
 
 
 def pipeline_streams(model, torch, dev):
@@ -244,7 +220,7 @@ def classify_files(model, sources, depth=2, workers=2, copy=True, _stats=None, *
         """The per-file call itself: whatever it computes, warns or raises is the contract."""
         stats["fallback_files"] = stats.get("fallback_files", 0) + 1
         st = read(p.buf, device=device, device_resident=True)
-        return _classify_groups(model, _group_stream(st, model.component_order, model.sampling_rate, copy, model.in_samples,
+        return model._classify_groups(_group_stream(st, model.component_order, model.sampling_rate, copy, model.in_samples,
                                                     model._stream_filter()), args, specs)
 
     def fast(j, p, up):
@@ -267,7 +243,7 @@ def classify_files(model, sources, depth=2, workers=2, copy=True, _stats=None, *
             return fallback(p)  # a payload shorter than its header says: read() raises for it
         for _ in range(plan.short_runs):
             warn_short_fragment()
-        res = _classify_groups(model, iter(plan_groups(plan, out)), args, specs)
+        res = model._classify_groups(iter(plan_groups(plan, out)), args, specs)
         lap("classify_ms", t0)
         return res
 

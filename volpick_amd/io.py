@@ -28,7 +28,7 @@ import numpy as np
 
 from . import _lib
 from ._device import device_backing, release_scratch, upload_samples
-from .stream import Stream, Trace, UTCDateTime, block_start, component_index, sample_offset, warn_short_fragment
+from .stream import Stream, Trace, UTCDateTime, block_start, plan_blocks, warn_short_fragment
 
 _REC_DTYPE = np.dtype(
     [("offset", "<i8"), ("start_us", "<i8"), ("sample_rate", "<f8"), ("reclen", "<i4"), ("data_offset", "<i4"),
@@ -55,24 +55,34 @@ def _looks_like_mseed(buf):
     return len(h) >= 8 and all(48 <= c <= 57 or c == 32 for c in h[:6]) and h[6:7] in (b"D", b"R", b"Q", b"M")
 
 
-def scan_mseed(buf):
-    """Record table of a miniSEED byte string as a numpy structured array (host only)."""
-    lib = _lib.load()
-    n = C.c_int64(0)
-    # capacity from the first record's length (miniSEED 2: 2 ** byte 6 of blockette 1000, usually at byte 48 + 6; miniSEED 3
-    # records vary) -- a table sized for 256-byte records is 10 MB of zeroed ctypes memory for a 35 MB station-day of
-    # 4096-byte records; the scanner reports the real count, so a low guess costs one more pass
+def _scan_to_fit(buf, scan):
+    """``scan(cap)`` -> ``(result, records found)`` with a table of ``cap`` records, again with room for all of them if the
+    first table was too small; returns the result.  The first capacity comes from the first record's length (miniSEED 2:
+    2 ** byte 6 of blockette 1000, usually at byte 48 + 6; miniSEED 3 records vary) -- a table sized for 256-byte records is
+    10 MB of zeroed ctypes memory for a 35 MB station-day of 4096-byte records; the scanner reports the real count, so a low
+    guess costs one more pass."""
     guess = 512
     if len(buf) >= 56 and buf[:3] != b"MS\x03" and buf[48:50] in (b"\x03\xe8", b"\xe8\x03") and 7 <= buf[54] <= 24:
         guess = 1 << buf[54]
     cap = max(16, len(buf) // guess + 16)
     while True:
+        result, found = scan(cap)
+        if found <= cap:
+            return result
+        cap = found
+
+
+def scan_mseed(buf):
+    """Record table of a miniSEED byte string as a numpy structured array (host only)."""
+    lib = _lib.load()
+    n = C.c_int64(0)
+
+    def scan(cap):
         recs = (_lib.VpMseedRecord * cap)()
         _lib.check(lib.vp_mseed_scan(buf, len(buf), recs, cap, C.byref(n)), "vp_mseed_scan")
-        if n.value <= cap:
-            break
-        cap = n.value
-    return np.frombuffer(recs, dtype=_REC_DTYPE, count=n.value).copy()
+        return recs, n.value
+
+    return np.frombuffer(_scan_to_fit(buf, scan), dtype=_REC_DTYPE, count=n.value).copy()
 
 
 def _segments(recs):
@@ -104,18 +114,15 @@ def scan_segments(buf):
     the segment number of each record.  Touches no GPU and no handle: any thread may call it."""
     lib = _lib.load()
     n, kept = C.c_int64(0), C.c_int64(0)
-    guess = 512  # (scan_mseed's capacity rule)
-    if len(buf) >= 56 and buf[:3] != b"MS\x03" and buf[48:50] in (b"\x03\xe8", b"\xe8\x03") and 7 <= buf[54] <= 24:
-        guess = 1 << buf[54]
-    cap = max(16, len(buf) // guess + 16)
-    while True:
+
+    def scan(cap):
         recs, seg = np.empty(cap, _REC_DTYPE), np.empty(cap, np.int64)
         _lib.check(lib.vp_mseed_scan_segments(buf, len(buf), recs.ctypes.data_as(C.POINTER(_lib.VpMseedRecord)),
                                               seg.ctypes.data_as(C.POINTER(C.c_int64)), cap, C.byref(n), C.byref(kept)),
                    "vp_mseed_scan_segments")
-        if n.value <= cap:
-            break
-        cap = n.value
+        return (recs, seg), n.value
+
+    recs, seg = _scan_to_fit(buf, scan)
     return recs[:kept.value], seg[:kept.value]
 
 
@@ -137,11 +144,11 @@ BLOCK_ALIGN = 64  # blocks start on 256-byte boundaries of the file's sample arr
 
 
 def plan_file_blocks(table, seg, component_order, sampling_rate, in_samples, has_filter=False, warn=True):
-    """``models._group_stream`` restated on a record table: from the headers alone, the station blocks of a miniSEED file and
-    where every record's samples go in them, so that one decode launch (``vp_mseed_decode_on`` with float32 output and zero
-    fill) writes the blocks ``_group_stream`` would assemble from the traces of ``read(..., device_resident=True)``.
-    ``table`` and ``seg`` are :func:`scan_segments`'.  Instruments, component rows, sample offsets, runs and start times
-    come from the helpers ``_group_stream`` uses (``stream.component_index``, ``sample_offset``, ``block_start``).
+    """From the headers alone, the station blocks of a miniSEED file and where every record's samples go in them, so that one
+    decode launch (``vp_mseed_decode_on`` with float32 output and zero fill) writes the blocks ``models._group_stream`` would
+    assemble from the traces of ``read(..., device_resident=True)``.  ``table`` and ``seg`` are :func:`scan_segments`'.  Every
+    segment is a piece of ``stream.plan_blocks``, the planner ``_group_stream`` asks too: instruments, component rows, sample
+    offsets, runs, used pieces and start times are its answers, and only ``out_index`` is worked out here.
 
     No plan (``FilePlan.reason`` set) when the file has no records; the model filters its input (``has_filter``); a trace is
     not at the model's rate (any trace: a resampled one changes length, and with it the runs); two segments of one component
@@ -156,43 +163,33 @@ def plan_file_blocks(table, seg, component_order, sampling_rate, in_samples, has
         return FilePlan("a trace is not at the model's rate")
     ns = table["nsamples"].astype(np.int64)
     before = np.cumsum(ns) - ns  # samples ahead of each record in the table
-    groups = {}
-    for a, b in zip(first.tolist(), last.tolist()):
-        cha = table["channel"][a].decode()
-        key = (table["network"][a].decode(), table["station"][a].decode(), table["location"][a].decode(), cha[:-1])
-        groups.setdefault(key, []).append((a, b, int(table["start_us"][a]), int(before[b - 1] + ns[b - 1] - before[a]),
-                                           component_index(cha, component_order)))
+    code = lambda field, a: table[field][a].decode()  # noqa: E731
+    pieces = [(code("network", a), code("station", a), code("location", a), code("channel", a),
+               UTCDateTime._from_us(int(table["start_us"][a])), int(before[b - 1] + ns[b - 1] - before[a]), (a, b))
+              for a, b in zip(first.tolist(), last.tolist())]  # a segment's ``ref`` is its records [a, b)
     plan = FilePlan(out_index=np.full(len(table), -1, np.int64))
     n_rows, cursor = len(component_order), 0
-    for (net, sta, loc, _), segs in sorted(groups.items()):
-        t_start = UTCDateTime._from_us(min(s[2] for s in segs))
-        pieces = [(sample_offset(UTCDateTime._from_us(us), t_start, sampling_rate), npts, ci, a, b) for a, b, us, npts, ci in segs]
-        runs = []
-        for s0, l, _, _, _ in sorted(pieces, key=lambda p: p[0]):
-            if runs and s0 <= runs[-1][1]:
-                runs[-1][1] = max(runs[-1][1], s0 + l)
-            else:
-                runs.append([s0, s0 + l])
-        for b0, b1 in runs:
-            if b1 - b0 < in_samples:
-                plan.short_runs += 1
-                if warn:
-                    warn_short_fragment()
-                continue
-            used = sorted((p for p in pieces if p[2] >= 0 and b0 <= p[0] < b1), key=lambda p: (p[2], p[0]))
-            for p, q in zip(used, used[1:]):
-                if p[2] == q[2] and q[0] < p[0] + p[1]:
-                    return FilePlan("two segments of one component overlap")
-            if any(int(table["encoding"][p[3]]) == 0 for p in used):
-                return FilePlan("a text record belongs to a used component")
-            n = b1 - b0
-            plan.blocks.append(dict(trace_id=f"{net}.{sta}.{loc}", network=net, station=sta, location=loc,
-                                    start_us=block_start(t_start, b0, sampling_rate)._us, shape=(n_rows, n),
-                                    offset=cursor if used else -1))
-            for s0, _, ci, a, b in used:
-                plan.out_index[a:b] = cursor + ci * n + (s0 - b0) + (before[a:b] - before[a])
-            if used:
-                cursor += -(-n_rows * n // BLOCK_ALIGN) * BLOCK_ALIGN
+    for run in plan_blocks(pieces, component_order, sampling_rate, in_samples):
+        if run.short:
+            plan.short_runs += 1
+            if warn:
+                warn_short_fragment()
+            continue
+        used = sorted(run.used, key=lambda p: (p[2], p[0]))
+        for p, q in zip(used, used[1:]):
+            if p[2] == q[2] and q[0] < p[0] + p[1]:
+                return FilePlan("two segments of one component overlap")
+        if any(int(table["encoding"][a]) == 0 for _, _, _, (a, _) in used):
+            return FilePlan("a text record belongs to a used component")
+        n = run.b1 - run.b0
+        plan.blocks.append(dict(trace_id=f"{run.network}.{run.station}.{run.location}", network=run.network,
+                                station=run.station, location=run.location,
+                                start_us=block_start(run.t_start, run.b0, sampling_rate)._us, shape=(n_rows, n),
+                                offset=cursor if used else -1))
+        for s0, _, row, (a, b) in used:
+            plan.out_index[a:b] = cursor + row * n + (s0 - run.b0) + (before[a:b] - before[a])
+        if used:
+            cursor += -(-n_rows * n // BLOCK_ALIGN) * BLOCK_ALIGN
     plan.n_out = cursor
     return plan
 

@@ -31,7 +31,7 @@ from . import _lib
 from ._device import device_backing
 from ._lib import VolpickHipError
 from .picks import ClassifyOutput, Detection, DetectionList, Pick, PickList
-from .stream import Stream, Trace, UTCDateTime
+from .stream import Stream, Trace, UTCDateTime, block_dict, block_start, plan_blocks, warn_short_fragment
 
 WEIGHTS_DIR = Path(__file__).resolve().parent / "weights"
 
@@ -687,9 +687,15 @@ class WaveformModel:
         block takes one of the three routes of ``_ClassifyRun``."""
         args = self._argdict(kwargs)
         specs = self._trigger_specs(args)
+        return self._classify_groups(_group_stream(stream, self.component_order, self.sampling_rate, copy, self.in_samples,
+                                                   self._stream_filter()), args, specs)
+
+    def _classify_groups(self, groups, args, specs):
+        """The station blocks ``groups`` (an iterator of ``block_dict``s: ``_group_stream``'s, or ``classify_files``' decoded
+        ones) through the routes of one ``_ClassifyRun``, then the records."""
         torch = _torch()
         run = _ClassifyRun(self, args, specs)
-        for grp in _group_stream(stream, self.component_order, self.sampling_rate, copy, self.in_samples, self._stream_filter()):
+        for grp in groups:
             if self._is_long(grp["data"].shape[1], args):
                 run.add_long(grp)
             elif self.batch_across_blocks and torch.is_tensor(grp["data"]):
@@ -946,48 +952,24 @@ def _group_stream(stream, component_order, sampling_rate, copy, in_samples, stre
     # resampled as SeisBench's annotate() does (on copies, or in place with copy=False); device-backed ones on the device,
     # whichever branch of the rule they take
     traces = [_prepare_trace(tr, float(sampling_rate), copy, stream_filter) for tr in stream]
-    if len(traces) == 0:
-        return
-    groups = {}
-    for tr in traces:
-        s = tr.stats
-        groups.setdefault((s.network, s.station, s.location, s.channel[:-1]), []).append(tr)
-    comp_alias = {"1": "N", "2": "E", "3": "Z"}  # flexible horizontal components
-    for (net, sta, loc, cha), trs in sorted(groups.items()):
-        t_start = min(UTCDateTime(t.stats.starttime) for t in trs)
-        pieces = []  # (first sample, length, component index or -1, trace)
-        for tr in trs:
-            comp = tr.stats.channel[-1] if tr.stats.channel else ""
-            comp = comp if comp in component_order else comp_alias.get(comp, comp)
-            s0 = int(round((UTCDateTime(tr.stats.starttime) - t_start) * sampling_rate))
-            npts = int(tr.stats.npts) if device_backing(tr) is not None else len(tr.data)
-            pieces.append((s0, npts, component_order.index(comp) if comp in component_order else -1, tr))
-        # contiguous covered runs (union over all components) become independent blocks; gaps are not bridged
-        runs = []
-        for s0, l, _, _ in sorted(pieces, key=lambda p: p[0]):
-            if l <= 0:
-                continue
-            if runs and s0 <= runs[-1][1]:
-                runs[-1][1] = max(runs[-1][1], s0 + l)
-            else:
-                runs.append([s0, s0 + l])
-        for b0, b1 in runs:
-            if b1 - b0 < in_samples:
-                warnings.warn("Parts of the input stream consist of fragments shorter than the number of input "
-                              "samples. Output might be empty.")
-                continue
-            used = [p for p in pieces if p[2] >= 0 and min(p[0] + p[1], b1) > max(p[0], b0)]
-            on_device = bool(used) and all(device_backing(p[3]) is not None for p in used)
-            # the common case -- one full-length trace per component -- is a single stack, no zero fill
-            full = sorted((p for p in used if p[0] == b0 and p[1] == b1 - b0), key=lambda p: p[2])
-            if len(used) != len(component_order) or [p[2] for p in full] != list(range(len(component_order))):
-                data = _zero_filled(pieces, b0, b1, len(component_order), used[0][3]._dev.device if on_device else None)
-            elif on_device:
-                data = _torch().stack([p[3]._dev for p in full]).float()
-            else:
-                data = _Rows([p[3].data.filled(0) if np.ma.isMaskedArray(p[3].data) else p[3].data for p in full])
-            yield {"data": data, "starttime": t_start + b0 / sampling_rate, "trace_id": f"{net}.{sta}.{loc}",
-                   "network": net, "station": sta, "location": loc}
+    pieces = [(tr.stats.network, tr.stats.station, tr.stats.location, tr.stats.channel, UTCDateTime(tr.stats.starttime),
+               int(tr.stats.npts) if device_backing(tr) is not None else len(tr.data), tr) for tr in traces]
+    # which samples form a block is ``plan_blocks``' rule; here a block gets its samples, and only when it is reached
+    for run in plan_blocks(pieces, component_order, sampling_rate, in_samples):
+        if run.short:
+            warn_short_fragment()
+            continue
+        b0, b1, used = run.b0, run.b1, run.used  # pieces: (first sample, length, component row or -1, trace)
+        on_device = bool(used) and all(device_backing(p[3]) is not None for p in used)
+        # the common case -- one full-length trace per component -- is a single stack, no zero fill
+        full = sorted((p for p in used if p[0] == b0 and p[1] == b1 - b0), key=lambda p: p[2])
+        if len(used) != len(component_order) or [p[2] for p in full] != list(range(len(component_order))):
+            data = _zero_filled(run.pieces, b0, b1, len(component_order), used[0][3]._dev.device if on_device else None)
+        elif on_device:
+            data = _torch().stack([p[3]._dev for p in full]).float()
+        else:
+            data = _Rows([p[3].data.filled(0) if np.ma.isMaskedArray(p[3].data) else p[3].data for p in full])
+        yield block_dict(data, run.network, run.station, run.location, block_start(run.t_start, b0, sampling_rate))
 
 
 def _zero_filled(pieces, b0, b1, n_components, device):

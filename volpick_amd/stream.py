@@ -14,6 +14,7 @@ from __future__ import annotations
 import copy as _copy
 import fnmatch
 import math
+from collections import namedtuple
 from datetime import datetime, timedelta, timezone
 
 import numpy as np
@@ -121,8 +122,9 @@ class UTCDateTime:
         return f"UTCDateTime({str(self)!r})"
 
 
-# --- where a trace sits in its instrument's block: ``models._group_stream`` places samples with these, and ``io.plan_file_blocks``
-# places miniSEED records with the same ones, so the two cannot disagree by a sample or a microsecond
+# --- station blocks: which samples of a stream form one (C, N) array.  ``plan_blocks`` is the only statement of the rule;
+# ``models._group_stream`` fills its blocks with the samples of traces and ``io.plan_file_blocks`` with miniSEED records, so
+# the two cannot disagree by a sample or a microsecond
 def sample_offset(start, origin, sampling_rate):
     """The sample number of the time ``start`` in a block that begins at ``origin`` (both ``UTCDateTime``)."""
     return int(round((start - origin) * sampling_rate))
@@ -148,6 +150,47 @@ def warn_short_fragment():
 
     warnings.warn("Parts of the input stream consist of fragments shorter than the number of input "
                   "samples. Output might be empty.")
+
+
+BlockRun = namedtuple("BlockRun", "network station location t_start b0 b1 short pieces used")
+
+
+def plan_blocks(pieces, component_order, sampling_rate, in_samples):
+    """The station blocks of a stream, from headers alone: one ``BlockRun`` per contiguous run of one instrument, instruments
+    in sorted order, an instrument's runs ascending.  ``pieces``, in stream order: ``(network, station, location, channel,
+    start, npts, ref)`` with ``start`` a ``UTCDateTime`` and ``ref`` whatever the caller needs to find the samples again.
+
+    An instrument is ``(network, station, location, channel[:-1])``; its origin ``t_start`` is the earliest start of its
+    pieces, empty ones included.  A piece becomes ``(s0, npts, row, ref)``: first sample after the origin, length, component
+    row or -1 (the block has no row for it).  Runs are the union of ``[s0, s0 + npts)`` over the pieces with samples, of
+    every component, known or not; abutting pieces merge, gaps are not bridged.  The run covers samples ``[b0, b1)`` and
+    starts at ``block_start(t_start, b0, sampling_rate)``; ``short``: it has fewer than ``in_samples`` samples, and what to do
+    about it is the caller's.  ``pieces``: all of the instrument's; ``used``: those with a row that reach into the run; both
+    in stream order (the assembly's "among equally long traces the later one wins" depends on it)."""
+    groups = {}
+    for net, sta, loc, cha, start, npts, ref in pieces:
+        groups.setdefault((net, sta, loc, cha[:-1]), []).append((cha, start, npts, ref))
+    for (net, sta, loc, _), members in sorted(groups.items(), key=lambda g: g[0]):
+        t_start = min(m[1] for m in members)
+        placed = [(sample_offset(start, t_start, sampling_rate), npts, component_index(cha, component_order), ref)
+                  for cha, start, npts, ref in members]
+        runs = []
+        for s0, npts, _, _ in sorted(placed, key=lambda p: p[0]):
+            if npts <= 0:
+                continue
+            if runs and s0 <= runs[-1][1]:
+                runs[-1][1] = max(runs[-1][1], s0 + npts)
+            else:
+                runs.append([s0, s0 + npts])
+        for b0, b1 in runs:
+            used = [p for p in placed if p[2] >= 0 and min(p[0] + p[1], b1) > max(p[0], b0)]
+            yield BlockRun(net, sta, loc, t_start, b0, b1, b1 - b0 < in_samples, placed, used)
+
+
+def block_dict(data, network, station, location, starttime):
+    """One station block as ``classify`` / ``annotate`` take it: ``data`` (C, N), its start and whose it is."""
+    return {"data": data, "starttime": starttime, "trace_id": f"{network}.{station}.{location}", "network": network,
+            "station": station, "location": location}
 
 
 # --- ObsPy's Trace.trim(starttime, endtime) with its defaults, restated (ObsPy is not available to pin it) ------------------
