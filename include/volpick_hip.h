@@ -631,6 +631,63 @@ void* vp_train_stream(const vp_trainer* t);
 int vp_train_launch_count(const vp_trainer* t); /* kernel launches the latest vp_train_step enqueued */
 
 /* ---------------------------------------------------------------------------------------------
+ * EQTransformer: training step of the three decoder stacks and their heads with the trunk frozen -- decoder_d with conv_d,
+ * pick_decoders.{0,1} with pick_convs.{0,1}: 48 tensors, 145,731 floats.  What one EQTransformerLit.training_step + Adam
+ * optimizer.step of the reference computes (volpick/model/models.py:538-549 shared_step, torch.nn.BCELoss per head,
+ * torch.optim.Adam) when only those tensors require a gradient.  Everything is fp32; the loss value is the float64 one of
+ * vp_bce_loss.  The decoders have no BatchNorm, dropout or recurrence, so the frozen trunk is the inference path: the
+ * trainer builds a plan of its own from `weights` (the model's whole flat blob, host memory) and `cfg` (NULL: the
+ * defaults) and runs, per step, the launches in front of the first decoder stage.  It holds no reference to any vp_handle.
+ *
+ * vp_eqt_dec_train_step: x (B, 3, 6000), already normalised (the forward pass of vp_forward with preprocess = 0); y
+ * (B, 3, 6000) with the rows detection, P, S -- what vp_bank_make_batch_eqt writes for label_rows = {0, 1, 2}; both host or
+ * both device (mem).  loss_weights: three doubles on the host (detection, P, S; the reference's 0.05, 0.40, 0.55).  Forward,
+ * loss, backward and -- if update != 0 -- one Adam step at `lr` (torch's defaults: no weight decay; the caller owns the
+ * schedule).  update == 0 leaves the weights, both moments and the update count alone.  *loss (may be NULL; non-NULL
+ * synchronises) receives the batch loss.  Device x / y are read on the trainer's stream (vp_eqt_dec_train_stream): they must
+ * be complete when the call is made and stay untouched until it has synchronised.
+ * vp_eqt_dec_train_step_bank / _step_bank_aug: the batch of `rows` is generated as vp_bank_make_batch_eqt /
+ * vp_bank_make_batch_eqt_aug generate it, straight into the trainer's buffers on its stream, then the step.
+ * Refused before any launch: B outside [1, max_batch], a non-finite lr or loss weight, what the generation calls refuse
+ * (VP_ERR_INVALID); a PhaseNet blob (VP_ERR_UNSUPPORTED).  The order of every sum is fixed and there are no atomics: two
+ * trainers in the same state that take the same batches hold the same bits.
+ *
+ * vp_eqt_dec_train_read: 0 weights, 1 gradients of the last step, 2 / 3 Adam first / second moments: the
+ * vp_eqt_dec_train_weight_count() floats of the 48 tensors in the flat blob's order (vp_eqt_dec_train_param_count / _name /
+ * _size list them; host-only calls).  vp_eqt_dec_train_write_weights replaces those floats once the queued steps have
+ * finished; the moments and the update count stay.  vp_eqt_dec_train_set_hyper: as vp_train_set_hyper refuses, for
+ * beta1, beta2 and adam_eps.
+ * vp_eqt_dec_train_tensor_*: the tensors of the last step, each a dense (sets, B, channels, length) block with sets = 3
+ * decoders in the order detection, P, S: "decoder.in", "a0" .. "a6" (stage outputs after the ReLU), "logits", "gz_head"
+ * (dLoss / dlogit), "ga0" .. "ga6", "gz0" .. "gz6" (gradient with respect to a stage's output after / before its ReLU);
+ * "p" is the predictions, (1, B, 3, 6000).  B = the batch of the last step.
+ * vp_eqt_dec_train_set_timing(t, 1) records an event between the step's phases; vp_eqt_dec_train_phase_ms then waits for
+ * the last step and returns five times in ms: trunk, forward + heads + loss, input gradients, weight gradients, Adam.
+ * One thread at a time per trainer. */
+typedef struct vp_eqt_dec_trainer vp_eqt_dec_trainer;
+int vp_eqt_dec_train_param_count(void);
+const char* vp_eqt_dec_train_param_name(int index);
+size_t vp_eqt_dec_train_param_size(int index);
+size_t vp_eqt_dec_train_weight_count(void);
+int vp_eqt_dec_train_create(int device_id, const float* weights, size_t n_floats, const vp_config* cfg, int max_batch,
+                            vp_eqt_dec_trainer** out);
+int vp_eqt_dec_train_destroy(vp_eqt_dec_trainer* t);
+int vp_eqt_dec_train_set_hyper(vp_eqt_dec_trainer* t, float beta1, float beta2, float adam_eps);
+int vp_eqt_dec_train_step(vp_eqt_dec_trainer* t, const float* x, const float* y, int mem, int B, const double* loss_weights,
+                          float lr, int update, double* loss);
+int vp_eqt_dec_train_synchronize(vp_eqt_dec_trainer* t);
+int vp_eqt_dec_train_read(vp_eqt_dec_trainer* t, int which, float* out, size_t n_floats);
+int vp_eqt_dec_train_write_weights(vp_eqt_dec_trainer* t, const float* weights, size_t n_floats);
+int vp_eqt_dec_train_tensor_count(const vp_eqt_dec_trainer* t);
+int vp_eqt_dec_train_tensor_info(const vp_eqt_dec_trainer* t, int index, const char** name, int* sets, int* channels,
+                                 int* length);
+int vp_eqt_dec_train_tensor_read(vp_eqt_dec_trainer* t, int index, int B, float* out);
+void* vp_eqt_dec_train_stream(const vp_eqt_dec_trainer* t);
+int vp_eqt_dec_train_launch_count(const vp_eqt_dec_trainer* t); /* kernel launches the latest step enqueued */
+int vp_eqt_dec_train_set_timing(vp_eqt_dec_trainer* t, int on);
+int vp_eqt_dec_train_phase_ms(vp_eqt_dec_trainer* t, float* ms);
+
+/* ---------------------------------------------------------------------------------------------
  * Training batches generated on the GPU from a device-resident waveform bank: the window cut, Normalize and
  * ProbabilisticLabeller steps of the reference's augmentation block 1 (volpick/model/models.py:221-265).  The host plans
  * every random choice (volpick_amd/generate.py) and hands one vp_plan_row per window; the kernel has no RNG.
@@ -804,6 +861,13 @@ int vp_bank_make_batch_eqt(vp_bank* bank, const vp_plan_row* rows, int B, int T,
  * vp_validate_eqt_bank on such records. */
 int vp_bank_make_batch_eqt_aug(vp_bank* bank, const vp_aug_row* rows, int B, int T, float sigma, int norm,
                                const int* label_rows, float det_fixed_window, float* x, float* y, void* stream);
+/* The decoder trainer's step (above) on a batch generated by the two calls above into its own buffers. */
+int vp_eqt_dec_train_step_bank(vp_eqt_dec_trainer* t, vp_bank* bank, const vp_plan_row* rows, int B, float sigma, int norm,
+                               const int* label_rows, float det_fixed_window, const double* loss_weights, float lr, int update,
+                               double* loss);
+int vp_eqt_dec_train_step_bank_aug(vp_eqt_dec_trainer* t, vp_bank* bank, const vp_aug_row* rows, int B, float sigma, int norm,
+                                   const int* label_rows, float det_fixed_window, const double* loss_weights, float lr,
+                                   int update, double* loss);
 
 /* ---------------------------------------------------------------------------------------------
  * Validation loss on the device: the reference's vector_cross_entropy (volpick/model/models.py:34-51) of predictions

@@ -353,6 +353,39 @@ SIGNATURES = {
         C.c_int,
         [_H, _H, C.c_void_p, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_int), C.c_float, C.c_int, C.POINTER(C.c_double)],
     ),
+    "vp_eqt_dec_train_param_count": (C.c_int, []),
+    "vp_eqt_dec_train_param_name": (C.c_char_p, [C.c_int]),
+    "vp_eqt_dec_train_param_size": (C.c_size_t, [C.c_int]),
+    "vp_eqt_dec_train_weight_count": (C.c_size_t, []),
+    "vp_eqt_dec_train_create": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.POINTER(VpConfig), C.c_int, C.POINTER(_H)]),
+    "vp_eqt_dec_train_destroy": (C.c_int, [_H]),
+    "vp_eqt_dec_train_set_hyper": (C.c_int, [_H, C.c_float, C.c_float, C.c_float]),
+    "vp_eqt_dec_train_step": (
+        C.c_int,
+        [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_float, C.c_int, C.POINTER(C.c_double)],
+    ),
+    "vp_eqt_dec_train_step_bank": (
+        C.c_int,
+        [_H, _H, C.c_void_p, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_int), C.c_float, C.POINTER(C.c_double), C.c_float,
+         C.c_int, C.POINTER(C.c_double)],
+    ),
+    "vp_eqt_dec_train_step_bank_aug": (
+        C.c_int,
+        [_H, _H, C.c_void_p, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_int), C.c_float, C.POINTER(C.c_double), C.c_float,
+         C.c_int, C.POINTER(C.c_double)],
+    ),
+    "vp_eqt_dec_train_synchronize": (C.c_int, [_H]),
+    "vp_eqt_dec_train_read": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_size_t]),
+    "vp_eqt_dec_train_write_weights": (C.c_int, [_H, C.c_void_p, C.c_size_t]),
+    "vp_eqt_dec_train_tensor_count": (C.c_int, [_H]),
+    "vp_eqt_dec_train_tensor_info": (
+        C.c_int, [_H, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    ),
+    "vp_eqt_dec_train_tensor_read": (C.c_int, [_H, C.c_int, C.c_int, C.c_void_p]),
+    "vp_eqt_dec_train_stream": (C.c_void_p, [_H]),
+    "vp_eqt_dec_train_launch_count": (C.c_int, [_H]),
+    "vp_eqt_dec_train_set_timing": (C.c_int, [_H, C.c_int]),
+    "vp_eqt_dec_train_phase_ms": (C.c_int, [_H, _FP]),
     "vp_vce_loss": (
         C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p],
     ),

@@ -24,7 +24,12 @@ arithmetic, restated here without torch), the weights of the lowest validation l
 EQTransformer has the validation half alone (``EQTransformerLit``, models.py:483-879): block 1's batch with its detection
 row from a bank, or the stacked recipe's (``augmented_planner``, ``vp_bank_make_batch_eqt_aug``), and ``shared_step``'s
 weighted binary cross entropy (``bce_loss`` on the host, ``validate_batches_eqt`` / ``EQTransformerLit.validate_bank`` on the
-GPU: ``vp_validate_eqt_begin`` / ``_bank`` / ``_bank_aug`` / ``_end``).  Its training step is not implemented.
+GPU: ``vp_validate_eqt_begin`` / ``_bank`` / ``_bank_aug`` / ``_end``).
+
+EQTransformer's training step exists for the three decoder stacks and their heads with the trunk frozen
+(``EQTransformerDecoderTrainer``, ``EQTransformerLit(trainable="decoders")``; ``vp_eqt_dec_train_*``): 48 tensors, 145,731 of
+the model's trainable floats, fine-tuned from finished batches or from a bank through the same ``fit_bank`` host loop as
+PhaseNet's.  Gradients into the trunk (pick LSTMs, attentions, transformers, BiLSTMs, ResCNN, encoder) are not implemented.
 """
 from __future__ import annotations
 
@@ -355,6 +360,62 @@ LR_SCHEDULERS = {"ReduceLROnPlateau": ReduceLROnPlateau}
 VALIDATION_MODES = ("host", "device")
 
 
+def _fit_scheduler(lr_scheduler, lr_scheduler_args, val_bank, keep_best, early_stop_patience):
+    """The checks every ``fit_bank`` makes of what follows the validation loss; returns the scheduler or ``None``."""
+    if lr_scheduler is not None and lr_scheduler not in LR_SCHEDULERS:
+        raise ValueError(f"lr_scheduler must be None or one of {sorted(LR_SCHEDULERS)}, got {lr_scheduler!r}")
+    if val_bank is None and (lr_scheduler is not None or keep_best or early_stop_patience is not None):
+        raise ValueError("lr_scheduler, keep_best and early_stop_patience follow the validation loss: they need val_bank")
+    return LR_SCHEDULERS[lr_scheduler](**(lr_scheduler_args or {})) if lr_scheduler is not None else None
+
+
+def _fit_loop(lit, tr, steps, planner, val_planner, scheduler, keep_best, early_stop_patience, step, validation_losses,
+              validated_weights):
+    """The host side of ``fit_bank`` for either model's lit: epochs of ``planner`` until ``steps`` optimiser steps, the
+    warm-up of ``lit.learning_rate``, a validation after every completed epoch and after the last step, and what the
+    validation loss drives (scheduler, ``lit.best_state``, early stop; ``lit.history``).  ``step(rows, lr)`` runs one
+    optimiser step of ``tr`` and returns its loss, ``validation_losses()`` the batch losses of one validation pass,
+    ``validated_weights()`` a host copy of the weights that pass scored."""
+    losses, val_losses = [], []
+    lit.history = history = {"val_loss": val_losses, "lr": [], "best": None, "stopped_early": False}
+    lit.best_state = None
+    # the optimiser's learning rate, a state only where a scheduler writes it too
+    lr_now = lit.learning_rate(tr.global_step)
+    since_best = 0
+
+    def validate():
+        nonlocal lr_now, since_best
+        val_losses.append(float(np.mean(validation_losses())))
+        if scheduler is not None:
+            lr_now = scheduler.step(val_losses[-1], lr_now)
+        history["lr"].append(lr_now if scheduler is not None else lit.learning_rate(tr.global_step))
+        since_best += 1
+        if val_losses[-1] < (float("inf") if history["best"] is None else history["best"][2]):  # (never a NaN)
+            history["best"] = (len(val_losses) - 1, tr.global_step, val_losses[-1])
+            since_best = 0
+            if keep_best:
+                lit.best_state = validated_weights()
+        if early_stop_patience is not None and since_best >= early_stop_patience:
+            history["stopped_early"] = True
+
+    while len(losses) < steps and not history["stopped_early"]:
+        for rows in planner.epoch():
+            k = tr.global_step
+            losses.append(step(rows, lit.learning_rate(k) if scheduler is None else lr_now))
+            if scheduler is not None and k < lit.WARMUP_STEPS:
+                lr_now = lit.lr * (k + 1) / float(lit.WARMUP_STEPS)
+            if len(losses) == steps:
+                break
+        else:
+            if val_planner is not None and len(losses) < steps:
+                validate()
+    if val_planner is None:
+        return losses
+    if not history["stopped_early"]:
+        validate()
+    return losses, val_losses
+
+
 def validate_batches(model, bank, batches, sigma, eps=1e-5, predictions=False):
     """One validation pass on the GPU (``vp_validate_begin`` ... ``vp_validate_end``): every element of ``batches`` (plan
     rows or augmented rows, any number per batch) is cut from ``bank``, run through ``model``'s inference path and scored
@@ -525,11 +586,7 @@ class PhaseNetLit:
 
         if validation not in VALIDATION_MODES:
             raise ValueError(f"validation must be one of {VALIDATION_MODES}, got {validation!r}")
-        if lr_scheduler is not None and lr_scheduler not in LR_SCHEDULERS:
-            raise ValueError(f"lr_scheduler must be None or one of {sorted(LR_SCHEDULERS)}, got {lr_scheduler!r}")
-        if val_bank is None and (lr_scheduler is not None or keep_best or early_stop_patience is not None):
-            raise ValueError("lr_scheduler, keep_best and early_stop_patience follow the validation loss: they need val_bank")
-        scheduler = LR_SCHEDULERS[lr_scheduler](**(lr_scheduler_args or {})) if lr_scheduler is not None else None
+        scheduler = _fit_scheduler(lr_scheduler, lr_scheduler_args, val_bank, keep_best, early_stop_patience)
         tr = self._ensure()
         in_samples = self.model.in_samples
         if augment is None:
@@ -544,48 +601,15 @@ class PhaseNetLit:
         elif val_bank is not None:
             val_planner = augment.planner(val_bank, batch_size, seed + 1, in_samples=in_samples, sigma=self.sigma,
                                           validation=True)
-        losses, val_losses = [], []
-        self.history = history = {"val_loss": val_losses, "lr": [], "best": None, "stopped_early": False}
-        self.best_state = None
-        # the optimiser's learning rate, a state only where a scheduler writes it too
-        lr_now = self.learning_rate(tr.global_step)
-        since_best = 0
 
-        def validate():
-            nonlocal lr_now, since_best
+        def validation_losses():
             if validation == "device":
-                vl = self.validate_bank(val_bank, val_planner)
-            else:
-                vl = [self.validation_step(val_bank.make_batch(rows, self.model, self.sigma)) for rows in val_planner.validation()]
-            val_losses.append(float(np.mean(vl)))
-            if scheduler is not None:
-                lr_now = scheduler.step(val_losses[-1], lr_now)
-            history["lr"].append(lr_now if scheduler is not None else self.learning_rate(tr.global_step))
-            since_best += 1
-            if val_losses[-1] < (float("inf") if history["best"] is None else history["best"][2]):  # (never a NaN)
-                history["best"] = (len(val_losses) - 1, tr.global_step, val_losses[-1])
-                since_best = 0
-                if keep_best:
-                    self.best_state = tr.ema_weights() if self._ema else tr.weights()
-            if early_stop_patience is not None and since_best >= early_stop_patience:
-                history["stopped_early"] = True
+                return self.validate_bank(val_bank, val_planner)
+            return [self.validation_step(val_bank.make_batch(rows, self.model, self.sigma)) for rows in val_planner.validation()]
 
-        while len(losses) < steps and not history["stopped_early"]:
-            for rows in planner.epoch():
-                k = tr.global_step
-                losses.append(tr.step_bank(bank, rows, self.learning_rate(k) if scheduler is None else lr_now, self.sigma))
-                if scheduler is not None and k < self.WARMUP_STEPS:
-                    lr_now = self.lr * (k + 1) / float(self.WARMUP_STEPS)
-                if len(losses) == steps:
-                    break
-            else:
-                if val_planner is not None and len(losses) < steps:
-                    validate()
-        if val_planner is None:
-            return losses
-        if not history["stopped_early"]:
-            validate()
-        return losses, val_losses
+        return _fit_loop(self, tr, steps, planner, val_planner, scheduler, keep_best, early_stop_patience,
+                         step=lambda rows, lr: tr.step_bank(bank, rows, lr, self.sigma), validation_losses=validation_losses,
+                         validated_weights=lambda: tr.ema_weights() if self._ema else tr.weights())
 
     def enable_ema(self, decay=0.999):
         self._ensure().enable_ema(decay)
@@ -618,19 +642,205 @@ def validate_batches_eqt(model, bank, batches, sigma, loss_weights=EQT_LOSS_WEIG
     return (batch, window, heads, preds) if predictions else (batch, window, heads)
 
 
+def decoder_param_names():
+    """The 48 tensors ``EQTransformerDecoderTrainer`` trains -- ``decoder_d`` with ``conv_d``, ``pick_decoders.{0,1}`` with
+    ``pick_convs.{0,1}`` -- as ``[(name, size)]`` in the flat blob's order (``vp_eqt_dec_train_param_name`` / ``_size``)."""
+    lib = _lib.load()
+    return [(lib.vp_eqt_dec_train_param_name(i).decode(), int(lib.vp_eqt_dec_train_param_size(i)))
+            for i in range(lib.vp_eqt_dec_train_param_count())]
+
+
+class EQTransformerDecoderTrainer:
+    """The three decoder stacks and heads of one EQTransformer on the device, with their gradients and Adam state; the
+    trunk is frozen and runs as the inference path (``vp_eqt_dec_train_*``).  ``PhaseNetTrainer``'s role for
+    ``EQTransformerLit(trainable="decoders")``.  The trainer builds its own device plan from ``model``'s weights and config
+    when it is made and does not follow later changes of ``model``; ``export()`` writes the trained tensors back."""
+
+    N_SETS = 3  # detection, P, S
+
+    def __init__(self, model: EQTransformer, max_batch=256, device=0, betas=(0.9, 0.999), eps=1e-8):
+        if not isinstance(model, EQTransformer):
+            raise TypeError("the decoder training step is implemented for EQTransformer")
+        if model._weights is None:
+            raise RuntimeError("model has no weights (use from_pretrained / load / load_state_dict)")
+        from .generate import detection_label_rows
+
+        if list(detection_label_rows(model.labels)) != [0, 1, 2]:
+            raise ValueError(f"the trainer's heads are (Detection, P, S) in this order, the model's labels are {model.labels!r}")
+        self._lib = _lib.load()
+        self.model = model
+        self.max_batch = int(max_batch)
+        self.in_samples = model.in_samples
+        self.names = decoder_param_names()
+        self.n_params = int(self._lib.vp_eqt_dec_train_weight_count())
+        self._h = C.c_void_p()
+        w = np.ascontiguousarray(model._weights, dtype=np.float32)
+        cfg = model._config()
+        _lib.check(self._lib.vp_eqt_dec_train_create(int(device), _lib.ptr(w), w.size, C.byref(cfg), self.max_batch,
+                                                     C.byref(self._h)), "vp_eqt_dec_train_create")
+        try:
+            _lib.check(self._lib.vp_eqt_dec_train_set_hyper(self._h, betas[0], betas[1], eps), "vp_eqt_dec_train_set_hyper")
+        except Exception:
+            self.close()  # the handle exists already: release it with the refusal
+            raise
+        self.global_step = 0
+        self._held = None  # the device inputs / the bank of the latest step
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.vp_eqt_dec_train_destroy(self._h)
+            self._h = None
+            self._held = None
+
+    __del__ = close
+
+    @staticmethod
+    def _weights_arg(loss_weights):
+        w = np.ascontiguousarray(loss_weights, np.float64)
+        if w.shape != (3,):
+            raise ValueError(f"loss_weights: three weights (detection, P, S), got {loss_weights!r}")
+        return w
+
+    def step(self, x, y, lr, loss_weights=EQT_LOSS_WEIGHTS, update=True):
+        """Forward + loss + backward (+ Adam when ``update``); returns the loss.  x: (B, 3, 6000), normalised; y: (B, 3, 6000)
+        with the rows detection, P, S.  Both numpy arrays or both CUDA tensors (complete on torch's current stream: the call
+        waits for that stream, and for its own before it returns)."""
+        if tuple(x.shape) != tuple(y.shape) or x.ndim != 3 or x.shape[1] != 3 or x.shape[2] != self.in_samples:
+            raise ValueError(f"expected x and y of shape (B, 3, {self.in_samples}), got {tuple(x.shape)} / {tuple(y.shape)}")
+        xk, xp, xm = PhaseNetTrainer._arg(x)
+        yk, yp, ym = PhaseNetTrainer._arg(y)
+        if xm != ym:
+            raise ValueError("x and y must both be host arrays or both be device tensors")
+        if xm == _lib.VP_MEM_DEVICE:
+            _torch().cuda.current_stream(xk.device).synchronize()
+        self._held = (xk, yk)
+        w = self._weights_arg(loss_weights)
+        loss = C.c_double(float("nan"))
+        _lib.check(self._lib.vp_eqt_dec_train_step(self._h, xp, yp, xm, int(x.shape[0]), w.ctypes.data_as(C.POINTER(C.c_double)),
+                                                   float(lr), int(bool(update)), C.byref(loss)), "vp_eqt_dec_train_step")
+        if update:
+            self.global_step += 1
+        return loss.value
+
+    def step_bank(self, bank, rows, lr, sigma, loss_weights=EQT_LOSS_WEIGHTS, detection_fixed_window=None, update=True):
+        """``step`` on a batch generated on the GPU straight into the trainer's buffers: plan rows as
+        ``vp_bank_make_batch_eqt`` executes them, ``AUG_ROW`` records as ``vp_bank_make_batch_eqt_aug`` does (chosen by the
+        rows' dtype), normalised with ``model.norm``.  ``rows`` may be reused at once."""
+        from .generate import AUG_ROW, as_aug_rows, as_rows, _fixed_window, _norm
+
+        aug = getattr(rows, "dtype", None) == AUG_ROW
+        rows = as_aug_rows(rows) if aug else as_rows(rows)
+        name = "vp_eqt_dec_train_step_bank_aug" if aug else "vp_eqt_dec_train_step_bank"
+        lrows = np.array([0, 1, 2], np.int32)
+        w = self._weights_arg(loss_weights)
+        self._held = bank
+        loss = C.c_double(float("nan"))
+        _lib.check(getattr(self._lib, name)(self._h, bank.handle, _lib.ptr(rows), len(rows), float(sigma), _norm(self.model.norm),
+                                            lrows.ctypes.data_as(C.POINTER(C.c_int)), _fixed_window(detection_fixed_window),
+                                            w.ctypes.data_as(C.POINTER(C.c_double)), float(lr), int(bool(update)), C.byref(loss)),
+                   name)
+        if update:
+            self.global_step += 1
+        return loss.value
+
+    def synchronize(self):
+        _lib.check(self._lib.vp_eqt_dec_train_synchronize(self._h))
+
+    def _read(self, which):
+        out = np.empty(self.n_params, dtype=np.float32)
+        _lib.check(self._lib.vp_eqt_dec_train_read(self._h, which, _lib.ptr(out), out.size), "vp_eqt_dec_train_read")
+        return out
+
+    def _named(self, blob):
+        shapes = {k: s for k, s, is_param in self.model._state_layout if is_param}
+        out, off = {}, 0
+        for key, n in self.names:
+            out[key] = blob[off:off + n].reshape(shapes[key])
+            off += n
+        return out
+
+    def weights(self):
+        return self._named(self._read(0))
+
+    def gradients(self):
+        return self._named(self._read(1))
+
+    def adam_state(self):
+        return self._named(self._read(2)), self._named(self._read(3))
+
+    def write_weights(self, blob):
+        """Replace the 145,731 trained floats (the order of ``names``; a dict of the 48 tensors is flattened).  The Adam
+        moments and the update count stay as they are (``vp_eqt_dec_train_write_weights``)."""
+        if isinstance(blob, dict):
+            blob = np.concatenate([np.asarray(blob[k], np.float32).ravel() for k, _ in self.names])
+        blob = np.ascontiguousarray(blob, dtype=np.float32)
+        if blob.shape != (self.n_params,):
+            raise ValueError(f"expected a flat blob of {self.n_params} floats, got shape {blob.shape}")
+        _lib.check(self._lib.vp_eqt_dec_train_write_weights(self._h, _lib.ptr(blob), blob.size), "vp_eqt_dec_train_write_weights")
+
+    def tensors(self, B):
+        """Every tensor of the last step (a batch of ``B`` windows) by name: ``decoder.in``, ``a0`` .. ``a6``, ``logits``,
+        ``gz_head``, ``ga0`` .. ``ga6``, ``gz0`` .. ``gz6`` as (3, B, C, L) arrays -- decoder detection, P, S -- and the
+        predictions ``p`` as (B, 3, 6000)."""
+        lib, out = self._lib, {}
+        for i in range(lib.vp_eqt_dec_train_tensor_count(self._h)):
+            name, s, c, l = C.c_char_p(), C.c_int(), C.c_int(), C.c_int()
+            _lib.check(lib.vp_eqt_dec_train_tensor_info(self._h, i, C.byref(name), C.byref(s), C.byref(c), C.byref(l)))
+            a = np.empty((s.value, B, c.value, l.value), dtype=np.float32)
+            _lib.check(lib.vp_eqt_dec_train_tensor_read(self._h, i, B, _lib.ptr(a)))
+            out[name.value.decode()] = a[0] if s.value == 1 else a
+        return out
+
+    def launch_count(self):
+        return int(self._lib.vp_eqt_dec_train_launch_count(self._h))
+
+    def phase_ms(self):
+        """(trunk, forward + heads + loss, input gradients, weight gradients, Adam) of the last step in ms; needs
+        ``set_timing(True)`` before that step."""
+        ms = (C.c_float * 5)()
+        _lib.check(self._lib.vp_eqt_dec_train_phase_ms(self._h, ms), "vp_eqt_dec_train_phase_ms")
+        return tuple(float(v) for v in ms)
+
+    def set_timing(self, on=True):
+        _lib.check(self._lib.vp_eqt_dec_train_set_timing(self._h, int(bool(on))))
+
+    def export(self):
+        """Copy the 48 trained tensors back into ``self.model`` (``state_dict`` / ``load_state_dict``); every other tensor
+        keeps its bits."""
+        sd = self.model.state_dict()
+        sd.update(self.weights())
+        self.model.load_state_dict(sd)
+        return self.model
+
+
+TRAINABLE = ("decoders",)
+
+
 class EQTransformerLit:
-    """The validation half of the reference's ``EQTransformerLit`` (models.py:483-879): block 1's batch or the stacked
-    recipe's (``augmented_planner``; the reference's ``get_val_augmentations`` with ``stack_data``) and ``shared_step``'s loss ``loss_weights[0] BCE(detection) + loss_weights[1] BCE(P) + loss_weights[2] BCE(S)``, by which
-    the reference selects its checkpoints.  ``validation_step(batch)`` takes what ``WaveformBank.make_batch`` returns for
-    the model: ``{"X": (B, 3, 6000), "y": (B, 2, 6000), "detections": (B, 1, 6000)}``.  Training is not implemented."""
+    """The reference's ``EQTransformerLit`` (models.py:483-879): block 1's batch or the stacked recipe's
+    (``augmented_planner``; the reference's ``get_val_augmentations`` with ``stack_data``) and ``shared_step``'s loss
+    ``loss_weights[0] BCE(detection) + loss_weights[1] BCE(P) + loss_weights[2] BCE(S)``, by which the reference selects its
+    checkpoints.  ``validation_step(batch)`` takes what ``WaveformBank.make_batch`` returns for the model:
+    ``{"X": (B, 3, 6000), "y": (B, 2, 6000), "detections": (B, 1, 6000)}``.
+
+    ``trainable=None`` (default) validates only: ``training_step`` raises.  ``trainable="decoders"`` trains the three
+    decoder stacks and their heads with the trunk frozen (``EQTransformerDecoderTrainer``): ``training_step(batch)`` on the
+    same dictionaries and ``fit_bank``.  Training the trunk is not implemented."""
+
+    WARMUP_STEPS = 500
 
     def __init__(self, lr=1e-2, sigma=20, loss_weights=EQT_LOSS_WEIGHTS, detection_fixed_window=None,
-                 prob_label_shape="gaussian", model=None, device=0, **model_kwargs):
+                 prob_label_shape="gaussian", model=None, device=0, trainable=None, max_batch=256, **model_kwargs):
         if prob_label_shape != "gaussian":
             raise ValueError(f"prob_label_shape {prob_label_shape!r}: only 'gaussian' labels are implemented (every "
                              "reference config uses them)")
         if len(loss_weights) != 3:
             raise ValueError(f"loss_weights: three weights (detection, P, S), got {loss_weights!r}")
+        if trainable is not None and trainable not in TRAINABLE:
+            raise ValueError(f"trainable must be None or 'decoders' (the decoder stacks and heads, trunk frozen), got {trainable!r}")
+        self.trainable = trainable
+        self._trainer = None
+        self._max_batch = max_batch
         self.prob_label_shape = prob_label_shape
         self.lr = float(lr)
         self.sigma = sigma
@@ -640,13 +850,69 @@ class EQTransformerLit:
         self._device = device
 
     def _model_on_device(self):
+        """``self.model`` on the GPU; with a trainer, holding the trainer's current weights (exported only when an update has
+        happened since the last export)."""
+        tr = self._trainer
+        if tr is not None and getattr(self, "_exported_at", 0) != tr.global_step:
+            tr.export()
+            self._exported_at = tr.global_step
         if self.model._device_index is None:
             self.model.cuda(self._device)
         return self.model
 
+    def _ensure(self):
+        if self.trainable is None:
+            raise NotImplementedError("EQTransformer training needs trainable='decoders' (the decoder stacks and heads, trunk "
+                                      "frozen); training the trunk is not implemented: this object validates "
+                                      "(validation_step, validate_bank)")
+        if self._trainer is None:
+            self._trainer = EQTransformerDecoderTrainer(self.model, max_batch=self._max_batch, device=self._device)
+        return self._trainer
+
+    @property
+    def trainer_state(self):
+        return self._ensure()
+
+    def learning_rate(self, step):
+        """lr of optimiser step ``step`` (0-based): the reference's 500-step linear warm-up (models.py:562-570), the rule of
+        ``PhaseNetLit.learning_rate``."""
+        return PhaseNetLit.learning_rate(self, step)
+
     def training_step(self, batch, batch_idx=None):
-        raise NotImplementedError("EQTransformer training is not implemented: this class validates (validation_step, "
-                                  "validate_bank)")
+        """``trainable="decoders"``: forward, loss, backward and the Adam step on ``{"X", "y", "detections"}`` (what
+        ``make_batch`` returns); returns the loss.  Otherwise raises ``NotImplementedError``."""
+        tr = self._ensure()
+        det, y = batch["detections"], batch["y"]
+        if hasattr(y, "data_ptr"):
+            y3 = _torch().cat([det, y], dim=1)
+        else:
+            y3 = np.concatenate([np.asarray(det), np.asarray(y)], axis=1)
+        return tr.step(batch["X"], y3, self.learning_rate(tr.global_step), self.loss_weights, update=True)
+
+    def fit_bank(self, bank, steps, batch_size=256, seed=0, val_bank=None, augment=None, lr_scheduler=None,
+                 lr_scheduler_args=None, keep_best=False, early_stop_patience=None):
+        """``steps`` optimiser steps of the decoder trainer on batches generated on the GPU from ``bank``: epochs of
+        ``window_planner`` (``augment``: of ``augmented_planner``), the warm-up of ``learning_rate``, and -- with ``val_bank`` --
+        ``validate_bank`` on the exported weights after every completed epoch and after the last step, which drives
+        ``lr_scheduler``, ``keep_best`` (``self.best_state``: the 48 decoder tensors of the lowest validation loss, restored
+        into the trainer and the model when the fit ends) and ``early_stop_patience`` exactly as in ``PhaseNetLit.fit_bank``
+        (one shared host loop).  Returns the per-step losses and, with ``val_bank``, ``(losses, val_losses)``."""
+        scheduler = _fit_scheduler(lr_scheduler, lr_scheduler_args, val_bank, keep_best, early_stop_patience)
+        tr = self._ensure()
+        if len(bank.lengths) < batch_size:
+            raise ValueError(f"a bank of {len(bank.lengths)} traces holds no full batch of {batch_size}")
+        plan = (lambda b, s, v: self.window_planner(b, batch_size, seed=s)) if augment is None else \
+            (lambda b, s, v: self.augmented_planner(b, batch_size, augment, seed=s, validation=v))
+        planner = plan(bank, seed, False)
+        val_planner = plan(val_bank, seed + 1, True) if val_bank is not None else None
+        out = _fit_loop(self, tr, steps, planner, val_planner, scheduler, keep_best, early_stop_patience,
+                        step=lambda rows, lr: tr.step_bank(bank, rows, lr, self.sigma, self.loss_weights, self.detection_fixed_window),
+                        validation_losses=lambda: self.validate_bank(val_bank, val_planner), validated_weights=tr.weights)
+        if keep_best and self.best_state is not None:
+            tr.write_weights(self.best_state)
+            tr.export()
+            self._exported_at = tr.global_step
+        return out
 
     def window_planner(self, bank, batch_size, seed=0):
         """Block 1's windows for this model (models.py:606-652): around a pick with ``samples_before=6000`` in an extent of
