@@ -1,5 +1,5 @@
 """Float64 restatements and a-priori bars of what surrounds the conv / BatchNorm / weight-gradient launches of the PhaseNet
-training step (volpick_amd/csrc/train_phasenet.hip, train_kernels.h): ``adam_kernel``, the BatchNorm running statistics and
+training step (volpick_amd/csrc/train_phasenet.hip, train_kernels.h, train_optim.hip): ``adam_kernel``, the BatchNorm running statistics and
 the loss head (``head_fwd_bwd_kernel``, ``head_fwd_bwd_pair_kernel<bf16_t, 4>``, ``head_final_kernel``).  Numpy only; shared
 by tests/test_train_state_cpu.py (emulations and mutations) and tests/test_gpu_train_state.py.  Every restatement is fed the
 values the update really read (the trainer hands back gradients, moments, weights and stored tensors), so nothing here

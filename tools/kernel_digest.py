@@ -6,7 +6,8 @@
 
 digest compiles each file device-only with the project's flags and records, per kernel symbol, the sha256 of its
 instruction stream (llvm-objdump -d --no-leading-addr with the address / encoding comments cut: branch operands are
-relative, so a kernel that moved to another file compares equal) and the resource metadata of its code-object note.
+relative, so a kernel that moved to another file compares equal; the s_nop fill behind its last instruction left out) and
+the resource metadata of its code-object note.
 compare matches kernels by demangled name and, where a name is gone (a template head changed), by equal content."""
 import hashlib
 import json
@@ -52,6 +53,10 @@ def digest_file(src, include, defines, tmp):
     for sym, ins in streams.items():
         if sym not in meta:
             continue  # not a kernel
+        # the fill behind a kernel's last instruction is not its own: up to the next symbol's alignment, and for the
+        # file's last symbol the prefetch margin at the end of the section -- which kernel comes last changes with the file
+        while ins and ins[-1][0].split() == ["s_nop", "0"]:
+            ins.pop()
         name = run("c++filt", sym).strip()
         out[f"{src.name}::{name}"] = {"bytes": sum(b for _, b in ins), "sha": hashlib.sha256("\n".join(t for t, _ in ins).encode()).hexdigest(),
                                       **{k: meta[sym].get("." + k, 0) for k in META}}

@@ -9,7 +9,10 @@
 //                                                                        dec_head_dgrad_kernel, dec_conv_kernel<DGRAD>
 //   d weight   gW[co][ci][k] = sum_b sum_t gz[co][t] u[ci][t + k - pad], gb = sum gz
 //                                                                        dec_wgrad_kernel + dec_fold_kernel
-//   update     torch.optim.Adam                                          adam_kernel (train_kernels.h)
+//   update     torch.optim.Adam                                          OptimState::update (train_optim.hip)
+//
+// The weights, their gradient and Adam's state are the OptimState both trainers hold (train_optim.h); device memory is owned
+// DevArrays.  The seven stages are stated once, in StageTable: launches, tensor sizes and offsets all follow from its rows.
 //
 // Every tensor is a dense row block [3 decoders][B][C][L]; the x2 nearest up-sample and the crop of stage 2 (376 -> 375)
 // exist only as the index `s >> 1`, `s < Lout` of the operand load into LDS.  No atomics: a weight gradient is summed per
@@ -22,22 +25,44 @@
 #include "batchgen.h"
 #include "bce.h"
 #include "net.h"
+#include "train_optim.h"
 
 namespace vp {
-
-// train_kernels.h; the one definition lives in train_phasenet.hip
-__global__ void adam_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                            const float* __restrict__ mask, float* __restrict__ ema, int n, float lr, float b1, float b2, float eps,
-                            float bc1, float bc2_sqrt, float ema_decay);
-
 namespace {
 
-constexpr int NSTAGE = 7, NSET = 3, T_OUT = 6000, HK = 11, HC = 8, DIN0 = 47;
-constexpr int kDin[NSTAGE] = {47, 94, 188, 375, 750, 1500, 3000};
+// ---- the stages ----------------------------------------------------------------------------------------------------------
+// One row per stage, in order: input channels, output channels, taps, and the samples per workgroup of its forward and of its
+// input-gradient launch (0: stage 0 has no input gradient; stage 4 runs 256 forward and 128 backward).
+template <int CI_, int CO_, int K_, int TN_FWD_, int TN_DGRAD_>
+struct StageCfg {
+  static constexpr int CI = CI_, CO = CO_, K = K_, TN_FWD = TN_FWD_, TN_DGRAD = TN_DGRAD_;
+};
+template <class... S>
+struct StageList {
+  static constexpr int N = sizeof...(S);
+  static constexpr int CI[N] = {S::CI...}, CO[N] = {S::CO...}, K[N] = {S::K...};
+  // f(row i), the row as a value of its StageCfg type
+  template <class F>
+  static void at(int i, F&& f) {
+    int n = 0;
+    ((n++ == i ? f(S{}) : void()), ...);
+  }
+};
+// clang-format off
+using StageTable = StageList<
+    StageCfg<16, 64,  3, 128,   0>,
+    StageCfg<64, 64,  5, 128, 128>,
+    StageCfg<64, 32,  5, 128, 128>,
+    StageCfg<32, 32,  7, 128, 128>,
+    StageCfg<32, 16,  7, 256, 128>,
+    StageCfg<16, 16,  9, 256, 256>,
+    StageCfg<16,  8, 11, 256, 256>>;
+// clang-format on
+constexpr int NSTAGE = StageTable::N, NSET = 3, T_OUT = 6000, HK = 11, HC = 8, DIN0 = 47;
+constexpr auto &kCi = StageTable::CI, &kCo = StageTable::CO, &kK = StageTable::K;
+constexpr int kDin[NSTAGE] = {47, 94, 188, 375, 750, 1500, 3000};  // samples in / out: x2, stage 2 cropped (376 -> 375)
 constexpr int kDout[NSTAGE] = {94, 188, 375, 750, 1500, 3000, 6000};
-constexpr int kCi[NSTAGE] = {16, 64, 64, 32, 32, 16, 16};
-constexpr int kCo[NSTAGE] = {64, 64, 32, 32, 16, 16, 8};
-constexpr int kK[NSTAGE] = {3, 5, 5, 7, 7, 9, 11};
+static_assert(kCi[0] == 16 && kCo[NSTAGE - 1] == HC && kDin[0] == DIN0 && kDout[NSTAGE - 1] == T_OUT, "decoder.in is [16][47], the head reads [8][6000]");
 const char* const kDecPrefix[NSET] = {"decoder_d", "pick_decoders.0", "pick_decoders.1"};
 const char* const kHeadPrefix[NSET] = {"conv_d", "pick_convs.0", "pick_convs.1"};
 
@@ -376,23 +401,18 @@ struct DecTrainer {
   std::vector<DecParam> params;
   size_t n_params = 0;
   int w_off[NSTAGE + 1][NSET], b_off[NSTAGE + 1][NSET];  // [7] = the head
-  DevBuf<float> w, grad, adam_m, adam_v, mask;
-  DevBuf<float> din, a[NSTAGE], ga[NSTAGE], gz[NSTAGE], logit, gzh, pred, x_dev, y_dev, partial;
-  DevBuf<double> loss_dev;  // [0] the batch loss, [1 ..] per window
+  OptimState opt;  // (no EMA: selector 4 of a read is refused)
+  DevArray<float> din, a[NSTAGE], ga[NSTAGE], gz[NSTAGE], logit, gzh, pred, x_dev, y_dev, partial;
+  DevArray<double> loss_dev;  // [0] the batch loss, [1 ..] per window
   std::vector<DecTensor> tensors;
   StagingRing rows_ring;
-  long step = 0;
-  float beta1 = 0.9f, beta2 = 0.999f, adam_eps = 1e-8f;
   bool timing = false;
   hipEvent_t ev[6] = {};
-  ~DecTrainer() {
+  ~DecTrainer() {  // (the device arrays free themselves, behind the wait for the stream)
     (void)hipSetDevice(device);
     if (stream) (void)hipStreamSynchronize(stream);
     for (hipEvent_t e : ev)
       if (e) (void)hipEventDestroy(e);
-    for (DevBuf<float>* b : {&w, &grad, &adam_m, &adam_v, &mask, &din, &logit, &gzh, &pred, &x_dev, &y_dev, &partial}) b->release();
-    for (int i = 0; i < NSTAGE; ++i) a[i].release(), ga[i].release(), gz[i].release();
-    loss_dev.release();
     if (stream) (void)hipStreamDestroy(stream);
     net.release();
   }
@@ -410,7 +430,7 @@ template <int CR, int CM, int K, int TN>
 void launch_fwd(DecTrainer& tr, int i, int B) {
   ConvTArgs a{};
   a.src = i == 0 ? tr.din.p : tr.a[i - 1].p;
-  a.w = tr.w.p;
+  a.w = tr.opt.w.p;
   for (int d = 0; d < NSET; ++d) a.w_off[d] = tr.w_off[i][d], a.b_off[d] = tr.b_off[i][d];
   a.dst = tr.a[i].p;
   a.B = B, a.Ls = kDin[i], a.Lout = kDout[i], a.Lprev = kDin[i];
@@ -422,7 +442,7 @@ template <int CR, int CM, int K, int TN>
 void launch_dgrad(DecTrainer& tr, int i, int B) {
   ConvTArgs a{};
   a.src = tr.gz[i].p;
-  a.w = tr.w.p;
+  a.w = tr.opt.w.p;
   for (int d = 0; d < NSET; ++d) a.w_off[d] = tr.w_off[i][d], a.b_off[d] = tr.b_off[i][d];
   a.dst = tr.ga[i - 1].p;
   a.dst2 = tr.gz[i - 1].p;
@@ -438,45 +458,24 @@ void launch_wgrad(DecTrainer& tr, int i, const float* gz, const float* src, int 
   a.B = B, a.Ls = Ls, a.Lout = Lout, a.nchunks = (Lout + WG_TC - 1) / WG_TC, a.nblk = wgrad_blocks(B, Lout, (size_t)CO * CI * K + CO);
   DTL((dec_wgrad_kernel<CO, CI, K, UP>), dim3(a.nblk, NSET), dim3(256), 0, tr.stream, a);
   FoldArgs f{};
-  f.partial = tr.partial.p, f.grad = tr.grad.p;
+  f.partial = tr.partial.p, f.grad = tr.opt.grad.p;
   for (int d = 0; d < NSET; ++d) f.w_off[d] = tr.w_off[i][d], f.b_off[d] = tr.b_off[i][d];
   f.nblk = a.nblk, f.n_w = CO * CI * K, f.psz = CO * CI * K + CO;
   DTL(dec_fold_kernel, dim3((f.psz + 255) / 256, NSET), dim3(256), 0, tr.stream, f);
 }
 
+// the launches of stage i, instantiated from its row of the table
 void forward_stage(DecTrainer& tr, int i, int B) {
-  switch (i) {
-    case 0: launch_fwd<16, 64, 3, 128>(tr, i, B); break;
-    case 1: launch_fwd<64, 64, 5, 128>(tr, i, B); break;
-    case 2: launch_fwd<64, 32, 5, 128>(tr, i, B); break;
-    case 3: launch_fwd<32, 32, 7, 128>(tr, i, B); break;
-    case 4: launch_fwd<32, 16, 7, 256>(tr, i, B); break;
-    case 5: launch_fwd<16, 16, 9, 256>(tr, i, B); break;
-    default: launch_fwd<16, 8, 11, 256>(tr, i, B); break;
-  }
+  StageTable::at(i, [&](auto s) { launch_fwd<s.CI, s.CO, s.K, s.TN_FWD>(tr, i, B); });
 }
 void dgrad_stage(DecTrainer& tr, int i, int B) {  // CR = the conv's output channels, CM = its input channels
-  switch (i) {
-    case 1: launch_dgrad<64, 64, 5, 128>(tr, i, B); break;
-    case 2: launch_dgrad<32, 64, 5, 128>(tr, i, B); break;
-    case 3: launch_dgrad<32, 32, 7, 128>(tr, i, B); break;
-    case 4: launch_dgrad<16, 32, 7, 128>(tr, i, B); break;
-    case 5: launch_dgrad<16, 16, 9, 256>(tr, i, B); break;
-    default: launch_dgrad<8, 16, 11, 256>(tr, i, B); break;
-  }
+  StageTable::at(i, [&](auto s) {
+    if constexpr (s.TN_DGRAD != 0) launch_dgrad<s.CO, s.CI, s.K, s.TN_DGRAD>(tr, i, B);
+  });
 }
 void wgrad_stage(DecTrainer& tr, int i, int B) {
   const float* src = i == 0 ? tr.din.p : tr.a[i - 1].p;
-  const float* gz = tr.gz[i].p;
-  switch (i) {
-    case 0: launch_wgrad<64, 16, 3, true>(tr, i, gz, src, kDin[i], kDout[i], B); break;
-    case 1: launch_wgrad<64, 64, 5, true>(tr, i, gz, src, kDin[i], kDout[i], B); break;
-    case 2: launch_wgrad<32, 64, 5, true>(tr, i, gz, src, kDin[i], kDout[i], B); break;
-    case 3: launch_wgrad<32, 32, 7, true>(tr, i, gz, src, kDin[i], kDout[i], B); break;
-    case 4: launch_wgrad<16, 32, 7, true>(tr, i, gz, src, kDin[i], kDout[i], B); break;
-    case 5: launch_wgrad<16, 16, 9, true>(tr, i, gz, src, kDin[i], kDout[i], B); break;
-    default: launch_wgrad<8, 16, 11, true>(tr, i, gz, src, kDin[i], kDout[i], B); break;
-  }
+  StageTable::at(i, [&](auto s) { launch_wgrad<s.CO, s.CI, s.K, true>(tr, i, tr.gz[i].p, src, kDin[i], kDout[i], B); });
 }
 
 int build(DecTrainer& tr, const float* weights, size_t n_floats, const vp_config& cfg) {
@@ -516,18 +515,16 @@ int build(DecTrainer& tr, const float* weights, size_t n_floats, const vp_config
   }
   std::vector<float> host(tr.n_params);
   for (const DecParam& p : tr.params) memcpy(host.data() + p.off, weights + p.off_full, p.size * sizeof(float));
-  int r = VP_OK;
-  for (DevBuf<float>* b : {&tr.w, &tr.grad, &tr.adam_m, &tr.adam_v, &tr.mask})
-    if (r == VP_OK) r = b->reserve(tr.n_params, true);
+  int r = tr.opt.alloc(tr.n_params);
   if (r != VP_OK) return r;
-  VP_HIP(hipMemcpy(tr.w.p, host.data(), tr.n_params * sizeof(float), hipMemcpyHostToDevice));
+  VP_HIP(hipMemcpy(tr.opt.w.p, host.data(), tr.n_params * sizeof(float), hipMemcpyHostToDevice));
   std::fill(host.begin(), host.end(), 1.f);
-  VP_HIP(hipMemcpy(tr.mask.p, host.data(), tr.n_params * sizeof(float), hipMemcpyHostToDevice));
+  VP_HIP(hipMemcpy(tr.opt.mask.p, host.data(), tr.n_params * sizeof(float), hipMemcpyHostToDevice));
 
-  auto rows = [&](DevBuf<float>& b, const std::string& name, int sets, int C, int L) -> int {
-    const int rc2 = b.reserve((size_t)sets * tr.max_batch * C * L, true);
-    if (rc2 == VP_OK) tr.tensors.push_back({name, b.p, sets, C, L});
-    return rc2;
+  auto rows = [&](DevArray<float>& b, const std::string& name, int sets, int C, int L) -> int {
+    VP_HIP(b.alloc((size_t)sets * tr.max_batch * C * L, true));
+    tr.tensors.push_back({name, b.p, sets, C, L});
+    return VP_OK;
   };
   if ((r = rows(tr.din, "decoder.in", NSET, 16, kDin[0])) != VP_OK) return r;
   for (int i = 0; i < NSTAGE; ++i)
@@ -539,15 +536,15 @@ int build(DecTrainer& tr, const float* weights, size_t n_floats, const vp_config
     if ((r = rows(tr.ga[i], "ga" + std::to_string(i), NSET, kCo[i], kDout[i])) != VP_OK) return r;
     if ((r = rows(tr.gz[i], "gz" + std::to_string(i), NSET, kCo[i], kDout[i])) != VP_OK) return r;
   }
-  if ((r = tr.x_dev.reserve((size_t)tr.max_batch * 3 * T_OUT)) != VP_OK) return r;
-  if ((r = tr.y_dev.reserve((size_t)tr.max_batch * 3 * T_OUT)) != VP_OK) return r;
-  if ((r = tr.loss_dev.reserve((size_t)1 + tr.max_batch, true)) != VP_OK) return r;
+  VP_HIP(tr.x_dev.alloc((size_t)tr.max_batch * 3 * T_OUT));
+  VP_HIP(tr.y_dev.alloc((size_t)tr.max_batch * 3 * T_OUT));
+  VP_HIP(tr.loss_dev.alloc((size_t)1 + tr.max_batch, true));
   size_t partial = (size_t)wgrad_max_blocks(HC * HK + 1) * (HC * HK + 1);  // the largest [nblk][block] of any launch
   for (int i = 0; i < NSTAGE; ++i) {
     const size_t psz = (size_t)kCo[i] * kCi[i] * kK[i] + kCo[i];
     partial = std::max(partial, wgrad_max_blocks(psz) * psz);
   }
-  if ((r = tr.partial.reserve((size_t)NSET * partial)) != VP_OK) return r;
+  VP_HIP(tr.partial.alloc((size_t)NSET * partial));
   VP_HIP(hipStreamCreateWithFlags(&tr.stream, hipStreamNonBlocking));
   for (auto& e : tr.ev) VP_HIP(hipEventCreate(&e));
   return VP_OK;
@@ -579,7 +576,7 @@ int run_step(DecTrainer& tr, const float* x_dev, const float* y_dev, int B, cons
   if (tr.timing) (void)hipEventRecord(tr.ev[1], s);
   for (int i = 0; i < NSTAGE; ++i) forward_stage(tr, i, B);
   HeadArgs h{};
-  h.a6 = tr.a[6].p, h.w = tr.w.p, h.y = y_dev, h.logit = tr.logit.p, h.p = tr.pred.p, h.gz = tr.gzh.p, h.ga6 = tr.ga[6].p, h.gz6 = tr.gz[6].p;
+  h.a6 = tr.a[6].p, h.w = tr.opt.w.p, h.y = y_dev, h.logit = tr.logit.p, h.p = tr.pred.p, h.gz = tr.gzh.p, h.ga6 = tr.ga[6].p, h.gz6 = tr.gz[6].p;
   for (int d = 0; d < NSET; ++d) h.w_off[d] = tr.w_off[NSTAGE][d], h.b_off[d] = tr.b_off[NSTAGE][d], h.lw[d] = (float)lw[d];
   h.numel = (float)((double)B * T_OUT);
   h.B = B;
@@ -596,13 +593,7 @@ int run_step(DecTrainer& tr, const float* x_dev, const float* y_dev, int B, cons
   launch_wgrad<1, HC, HK, false>(tr, NSTAGE, tr.gzh.p, tr.a[6].p, T_OUT, T_OUT, B);
   for (int i = NSTAGE - 1; i >= 0; --i) wgrad_stage(tr, i, B);
   if (tr.timing) (void)hipEventRecord(tr.ev[4], s);
-  if (update) {
-    tr.step += 1;
-    const float bc1 = 1.f - powf(tr.beta1, (float)tr.step);
-    const float bc2 = 1.f - powf(tr.beta2, (float)tr.step);
-    DTL(adam_kernel, dim3((unsigned)((tr.n_params + 255) / 256)), dim3(256), 0, s, tr.w.p, tr.grad.p, tr.adam_m.p, tr.adam_v.p, tr.mask.p,
-        (float*)nullptr, (int)tr.n_params, lr, tr.beta1, tr.beta2, tr.adam_eps, bc1, sqrtf(bc2), 0.f);
-  }
+  if (update) tr.opt.update(s, lr, tr.launches);
   if (tr.timing) (void)hipEventRecord(tr.ev[5], s);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
@@ -695,12 +686,9 @@ int vp_eqt_dec_train_destroy(vp_eqt_dec_trainer* h) {
 
 int vp_eqt_dec_train_set_hyper(vp_eqt_dec_trainer* h, float beta1, float beta2, float adam_eps) {
   VP_REQUIRE(h, "vp_eqt_dec_train_set_hyper: null handle");
-  // (every comparison is false for a NaN; nothing is stored before all three have passed)
-  VP_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f,
-             "vp_eqt_dec_train_set_hyper: beta1 %g, beta2 %g outside [0, 1) (1 - beta^t divides the step)", (double)beta1, (double)beta2);
-  VP_REQUIRE(adam_eps > 0.f && std::isfinite(adam_eps), "vp_eqt_dec_train_set_hyper: adam_eps %g is not finite and positive", (double)adam_eps);
-  DecTrainer& tr = *reinterpret_cast<DecTrainer*>(h);
-  tr.beta1 = beta1, tr.beta2 = beta2, tr.adam_eps = adam_eps;
+  if (const int rc = check_hyper("vp_eqt_dec_train_set_hyper", beta1, beta2, adam_eps); rc != VP_OK) return rc;
+  OptimState& opt = reinterpret_cast<DecTrainer*>(h)->opt;
+  opt.beta1 = beta1, opt.beta2 = beta2, opt.adam_eps = adam_eps;
   return VP_OK;
 }
 
@@ -755,22 +743,13 @@ size_t vp_eqt_dec_train_weight_count(void) {
 int vp_eqt_dec_train_read(vp_eqt_dec_trainer* h, int which, float* out, size_t n_floats) {
   VP_REQUIRE(h && out, "vp_eqt_dec_train_read: null argument");
   DecTrainer& tr = *reinterpret_cast<DecTrainer*>(h);
-  VP_REQUIRE(n_floats == tr.n_params && which >= 0 && which <= 3, "vp_eqt_dec_train_read: bad size or selector");
-  const float* src = which == 0 ? tr.w.p : which == 1 ? tr.grad.p : which == 2 ? tr.adam_m.p : tr.adam_v.p;
-  VP_HIP(hipSetDevice(tr.device));
-  VP_HIP(hipStreamSynchronize(tr.stream));
-  VP_HIP(hipMemcpy(out, src, n_floats * sizeof(float), hipMemcpyDeviceToHost));
-  return VP_OK;
+  return tr.opt.read("vp_eqt_dec_train_read", tr.device, tr.stream, 3, which, out, n_floats);
 }
 
 int vp_eqt_dec_train_write_weights(vp_eqt_dec_trainer* h, const float* weights, size_t n_floats) {
   VP_REQUIRE(h && weights, "vp_eqt_dec_train_write_weights: null argument");
   DecTrainer& tr = *reinterpret_cast<DecTrainer*>(h);
-  VP_REQUIRE(n_floats == tr.n_params, "vp_eqt_dec_train_write_weights: expected %zu floats, got %zu", tr.n_params, n_floats);
-  VP_HIP(hipSetDevice(tr.device));
-  VP_HIP(hipStreamSynchronize(tr.stream));
-  VP_HIP(hipMemcpy(tr.w.p, weights, n_floats * sizeof(float), hipMemcpyHostToDevice));
-  return VP_OK;
+  return tr.opt.write("vp_eqt_dec_train_write_weights", tr.device, tr.stream, weights, n_floats);
 }
 
 int vp_eqt_dec_train_tensor_count(const vp_eqt_dec_trainer* h) {

@@ -7,7 +7,7 @@
 // Layout: every layer keeps z (raw conv output), a = relu(bn(z)) and the gradients gz, ga as haloed
 // [B][C][ls] rows.  Forward convs and input-gradient convs run on conv_mfma_kernel with fragments
 // re-packed from the live weights every step (gather_pack_kernel, index maps built once with the
-// inference packers); weight gradients on wgrad_kernel; everything else in train_kernels.h.
+// inference packers); weight gradients on wgrad_kernel; Adam and its state in train_optim.hip; everything else in train_kernels.h.
 // ConvTranspose outputs are kept at full length (4 L + 3): BatchNorm sees the samples the U-Net
 // crops away, and they receive gradient through the batch statistics.
 //
@@ -24,6 +24,7 @@
 #include "conv_mfma.h"
 #include "conv_train_b16.h"
 #include "train_kernels.h"
+#include "train_optim.h"
 
 namespace vp {
 namespace {
@@ -257,25 +258,6 @@ RowKernels row_kernels() {
   return k;
 }
 
-// A device array that belongs to its holder: allocated (and zeroed where something reads it before a kernel has written it)
-// in one statement, freed with the holder.  (DevBuf of api_handle.h is the other thing: it regrows, may carry a pinned host
-// mirror, and is released by hand.)
-template <class T>
-struct DevArray {
-  T* p = nullptr;
-  DevArray() = default;
-  DevArray(const DevArray&) = delete;
-  DevArray& operator=(const DevArray&) = delete;
-  ~DevArray() {
-    if (p) (void)hipFree(p);
-  }
-  hipError_t alloc(size_t n, bool zero = false) {
-    const hipError_t e = hipMalloc((void**)&p, n * sizeof(T));
-    return e == hipSuccess && zero ? hipMemset(p, 0, n * sizeof(T)) : e;
-  }
-  operator T*() const { return p; }
-};
-
 }  // namespace
 
 struct Trainer {
@@ -298,16 +280,13 @@ struct Trainer {
   size_t n_params = 0;
   // device memory
   DevArray<char> arena;  // activation / gradient tensors
-  DevArray<float> w;     // weights (flat blob, canonical order)
-  DevArray<float> grad, adam_m, adam_v, mask;
-  DevArray<float> ema;   // EMA of the weights (allocated by vp_train_set_ema)
+  OptimState opt;        // weights, gradients, Adam state; the EMA is allocated by vp_train_set_ema
   // behind the last reader of a step's x / y (the head kernel), a ring over the steps in flight:
   // vp_train_wait_inputs_consumed (the latest), vp_train_inputs_consumed_upto (which steps are past it)
   static constexpr int EV_RING = 8;
   hipEvent_t ev_inputs[EV_RING] = {};
   long long ev_inputs_seq[EV_RING] = {-1, -1, -1, -1, -1, -1, -1, -1};
   long long seq = 0;  // steps enqueued so far
-  float ema_decay = 0.f;
   DevArray<int> frag_idx;
   DevArray<float> frag;
   size_t frag_n = 0;
@@ -326,8 +305,7 @@ struct Trainer {
   RowRing plan_rows;             // vp_train_step_bank(_aug)'s rows: slot seq % EV_RING, free again at ev_inputs of that slot
                                  // (the bare ring, not a StagingRing: the step events below exist anyway and free the slots too)
   DevArray<float> p_dev;         // predictions of the last step
-  long step = 0;
-  float beta1 = 0.9f, beta2 = 0.999f, adam_eps = 1e-8f, bn_eps = 1e-3f, bn_momentum = 0.1f, loss_eps = 1e-5f;
+  float bn_eps = 1e-3f, bn_momentum = 0.1f, loss_eps = 1e-5f;
   int t_x = -1, t_ga_last = -1;
   std::vector<int> frag_idx_host;
 
@@ -554,8 +532,8 @@ int upload(Trainer& tr, const float* weights) {
   VP_HIP(tr.arena.alloc(total * tr.esize, true));  // (a zero of either type)
   for (size_t i = 0; i < tr.tensors.size(); ++i) tr.tensors[i].p = reinterpret_cast<float*>(tr.arena.p + toff[i] * tr.esize);
   const size_t np = tr.n_params;
-  for (DevArray<float>* a : {&tr.w, &tr.grad, &tr.adam_m, &tr.adam_v, &tr.mask}) VP_HIP(a->alloc(np, true));
-  VP_HIP(hipMemcpy(tr.w, weights, np * sizeof(float), hipMemcpyHostToDevice));
+  if (const int rc = tr.opt.alloc(np); rc != VP_OK) return rc;
+  VP_HIP(hipMemcpy(tr.opt.w, weights, np * sizeof(float), hipMemcpyHostToDevice));
   std::vector<float> mask(np, 1.f);
   for (auto& kv : tr.poff) {
     const std::string& n = kv.first;
@@ -563,7 +541,7 @@ int upload(Trainer& tr, const float* weights) {
     if (running)
       for (size_t i = 0; i < tr.psize[n]; ++i) mask[kv.second + i] = 0.f;
   }
-  VP_HIP(hipMemcpy(tr.mask, mask.data(), np * sizeof(float), hipMemcpyHostToDevice));
+  VP_HIP(hipMemcpy(tr.opt.mask, mask.data(), np * sizeof(float), hipMemcpyHostToDevice));
   tr.frag_n = tr.frag_idx_host.size();
   VP_HIP(tr.frag_idx.alloc(tr.frag_n));
   VP_HIP(hipMemcpy(tr.frag_idx, tr.frag_idx_host.data(), tr.frag_n * sizeof(int), hipMemcpyHostToDevice));
@@ -681,7 +659,7 @@ int run_conv(Trainer& tr, const ConvOp& op, int B, bool want_stat = false) {
   a.wsd = (long)d.win_stride();
   a.dst_halo = HALO;
   a.afrag = tr.frag + op.frag_off;
-  a.bias = op.bias_off >= 0 ? tr.w + op.bias_off : tr.zeros.p;
+  a.bias = op.bias_off >= 0 ? tr.opt.w + op.bias_off : tr.zeros.p;
   a.win_per_set = B;
   a.n_windows = B;
   a.l_out = op.l_out;
@@ -707,10 +685,10 @@ BnArgs bn_args(Trainer& tr, const BnOp& b, int B) {
   a.Lz = b.Lz;
   a.La = b.La;
   a.crop = b.crop;
-  a.gamma = tr.w + b.gamma_off;
-  a.beta = tr.w + b.beta_off;
-  a.running_mean = tr.w + b.rm_off;
-  a.running_var = tr.w + b.rv_off;
+  a.gamma = tr.opt.w + b.gamma_off;
+  a.beta = tr.opt.w + b.beta_off;
+  a.running_mean = tr.opt.w + b.rm_off;
+  a.running_var = tr.opt.w + b.rv_off;
   a.stats = tr.stats + b.stats_off;
   a.partial = tr.bn_partial;
   {  // 64 >> sl2 rows per wave and trip, ~2 k workgroups per launch at most
@@ -721,8 +699,8 @@ BnArgs bn_args(Trainer& tr, const BnOp& b, int B) {
     if (gb > (B + rows_per_block - 1) / rows_per_block) gb = (B + rows_per_block - 1) / rows_per_block;
     a.GB = gb < 1 ? 1 : (gb > 256 ? 256 : gb);
   }
-  a.g_gamma = tr.grad + b.gamma_off;
-  a.g_beta = tr.grad + b.beta_off;
+  a.g_gamma = tr.opt.grad + b.gamma_off;
+  a.g_beta = tr.opt.grad + b.beta_off;
   a.eps = tr.bn_eps;
   a.momentum = tr.bn_momentum;
   return a;
@@ -747,7 +725,7 @@ void launch_bn(Trainer& tr, const BnKernel (&by_crop)[3], const BnArgs& a, const
 // fills the job of folding `rows` partial rows of a layer's weight gradient; returns the workgroups it takes
 int fill_sum_job(SumJob& jb, Trainer& tr, const WgradOp& w, const float* partial, int rows, int first_block) {
   jb.partial = partial;
-  jb.out = tr.grad + w.grad_off;
+  jb.out = tr.opt.grad + w.grad_off;
   jb.rows = rows;
   jb.n = w.out_n;
   jb.first_block = first_block;
@@ -832,7 +810,7 @@ struct WgradQueue {
 
 // ---- the step, phase by phase ----------------------------------------------------------------------------------------
 void pack_weights(Trainer& tr) {
-  TRL(gather_pack_kernel, dim3((unsigned)((tr.frag_n + 255) / 256)), dim3(256), 0, tr.stream, tr.frag_idx, tr.w, tr.frag,
+  TRL(gather_pack_kernel, dim3((unsigned)((tr.frag_n + 255) / 256)), dim3(256), 0, tr.stream, tr.frag_idx, tr.opt.w, tr.frag,
       (long)tr.frag_n);
   if (tr.b16_blocks) TRL(conv_b16_pack_kernel, dim3(tr.b16_blocks), dim3(256), 0, tr.stream, tr.b16_jobs);
 }
@@ -859,8 +837,8 @@ void head_and_loss(Trainer& tr, const float* y_dev, int B) {
   h.ga = tr.rows(tr.t_ga_last);
   h.y = y_dev;
   h.p = tr.p_dev;
-  h.w = tr.w + tr.poff.at("out.weight");
-  h.b = tr.w + tr.poff.at("out.bias");
+  h.w = tr.opt.w + tr.poff.at("out.weight");
+  h.b = tr.opt.w + tr.poff.at("out.bias");
   h.partial = tr.head_partial;
   h.B = B;
   h.T = T0;
@@ -875,8 +853,8 @@ void head_and_loss(Trainer& tr, const float* y_dev, int B) {
   // two stages: 64 row groups, then the 64 group sums
   TRL((sum_rows_kernel<double, double>), dim3(1, 64), dim3(256), 0, s, tr.head_partial, gx * B, 28, tr.head_stage);
   TRL((sum_rows_kernel<double, double>), dim3(1, 1), dim3(256), 0, s, tr.head_stage, 64, 28, tr.head_sums);
-  TRL(head_final_kernel, dim3(1), dim3(32), 0, s, tr.head_sums, tr.head_sums + 28, tr.grad + tr.poff.at("out.bias"),
-      tr.grad + tr.poff.at("out.weight"));
+  TRL(head_final_kernel, dim3(1), dim3(32), 0, s, tr.head_sums, tr.head_sums + 28, tr.opt.grad + tr.poff.at("out.bias"),
+      tr.opt.grad + tr.poff.at("out.weight"));
 }
 
 void backward_layers(Trainer& tr, WgradQueue& wq, int B) {
@@ -892,7 +870,7 @@ void backward_layers(Trainer& tr, WgradQueue& wq, int B) {
     if (li == 0) {  // conv bias of `inc`: sum of gz per channel (zero up to rounding: BatchNorm removes the mean)
       const int GB = B < 64 ? B : 64;
       TRL(tr.rk.channel_sum, dim3(8, GB), dim3(256), 0, s, tr.rows(L.bn.gz), B, T0, GB, tr.bn_partial);
-      TRL((sum_rows_kernel<double, float>), dim3(1, 1), dim3(256), 0, s, tr.bn_partial, GB, 8, tr.grad + tr.poff.at("inc.bias"));
+      TRL((sum_rows_kernel<double, float>), dim3(1, 1), dim3(256), 0, s, tr.bn_partial, GB, 8, tr.opt.grad + tr.poff.at("inc.bias"));
     }
     if (L.dgrad.used) run_conv(tr, L.dgrad, B);
   }
@@ -907,13 +885,7 @@ void fold_and_update(Trainer& tr, const WgradQueue& wq, bool update, float lr) {
   (void)hipEventRecord(tr.ev_wg, tr.stream_wg);
   (void)hipStreamWaitEvent(s, tr.ev_wg, 0);  // every weight gradient's partial rows are written
   TRL(sum_rows_multi_kernel, dim3(wq.blocks_last), dim3(256), 0, s, wq.jobs_last);
-  if (update) {
-    tr.step += 1;
-    const float bc1 = 1.f - powf(tr.beta1, (float)tr.step);
-    const float bc2 = 1.f - powf(tr.beta2, (float)tr.step);
-    TRL(adam_kernel, dim3((unsigned)((tr.n_params + 255) / 256)), dim3(256), 0, s, tr.w, tr.grad, tr.adam_m, tr.adam_v, tr.mask,
-        tr.ema, (int)tr.n_params, lr, tr.beta1, tr.beta2, tr.adam_eps, bc1, sqrtf(bc2), tr.ema_decay);
-  }
+  if (update) tr.opt.update(s, lr, tr.launches);
 }
 
 int forward_backward(Trainer& tr, const float* x_dev, const float* y_dev, int B, bool update, float lr) {
@@ -1013,16 +985,12 @@ int vp_train_destroy(vp_trainer* h) {
 
 int vp_train_set_hyper(vp_trainer* h, float beta1, float beta2, float adam_eps, float bn_momentum, float loss_eps) {
   VP_REQUIRE(h, "vp_train_set_hyper: null handle");
-  // (every comparison is false for a NaN; nothing is stored before all five have passed)
-  VP_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f,
-             "vp_train_set_hyper: beta1 %g, beta2 %g outside [0, 1) (1 - beta^t divides the step)", (double)beta1, (double)beta2);
-  VP_REQUIRE(adam_eps > 0.f && std::isfinite(adam_eps), "vp_train_set_hyper: adam_eps %g is not finite and positive", (double)adam_eps);
+  // (nothing is stored before all five have passed)
+  if (const int rc = check_hyper("vp_train_set_hyper", beta1, beta2, adam_eps); rc != VP_OK) return rc;
   VP_REQUIRE(bn_momentum > 0.f && bn_momentum <= 1.f, "vp_train_set_hyper: bn_momentum %g outside (0, 1]", (double)bn_momentum);
   VP_REQUIRE(loss_eps > 0.f && std::isfinite(loss_eps), "vp_train_set_hyper: loss_eps %g is not finite and positive", (double)loss_eps);
   Trainer& tr = *reinterpret_cast<Trainer*>(h);
-  tr.beta1 = beta1;
-  tr.beta2 = beta2;
-  tr.adam_eps = adam_eps;
+  tr.opt.beta1 = beta1, tr.opt.beta2 = beta2, tr.opt.adam_eps = adam_eps;
   tr.bn_momentum = bn_momentum;
   tr.loss_eps = loss_eps;
   return VP_OK;
@@ -1033,12 +1001,12 @@ int vp_train_set_ema(vp_trainer* h, float decay) {
   Trainer& tr = *reinterpret_cast<Trainer*>(h);
   VP_HIP(hipSetDevice(tr.device));
   VP_HIP(hipStreamSynchronize(tr.stream));
-  if (!tr.ema) VP_HIP(tr.ema.alloc(tr.n_params));
+  if (!tr.opt.ema) VP_HIP(tr.opt.ema.alloc(tr.n_params));
   // starts at the current weights; on the trainer's (non-blocking) stream, so that the next step's Adam / EMA update is
   // ordered behind the copy (a null-stream device-to-device copy may return before it has run)
-  VP_HIP(hipMemcpyAsync(tr.ema, tr.w, tr.n_params * sizeof(float), hipMemcpyDeviceToDevice, tr.stream));
+  VP_HIP(hipMemcpyAsync(tr.opt.ema, tr.opt.w, tr.n_params * sizeof(float), hipMemcpyDeviceToDevice, tr.stream));
   VP_HIP(hipStreamSynchronize(tr.stream));
-  tr.ema_decay = decay;
+  tr.opt.ema_decay = decay;
   return VP_OK;
 }
 
@@ -1109,23 +1077,14 @@ int vp_train_synchronize(vp_trainer* h) {
 int vp_train_read(vp_trainer* h, int which, float* out, size_t n_floats) {
   VP_REQUIRE(h && out, "vp_train_read: null argument");
   Trainer& tr = *reinterpret_cast<Trainer*>(h);
-  VP_REQUIRE(n_floats == tr.n_params && which >= 0 && which <= 4, "vp_train_read: bad size or selector");
-  VP_REQUIRE(which != 4 || tr.ema, "vp_train_read: EMA is off (vp_train_set_ema)");
-  const float* src = *(which == 0 ? &tr.w : which == 1 ? &tr.grad : which == 2 ? &tr.adam_m : which == 3 ? &tr.adam_v : &tr.ema);
-  VP_HIP(hipSetDevice(tr.device));
-  VP_HIP(hipStreamSynchronize(tr.stream));
-  VP_HIP(hipMemcpy(out, src, n_floats * sizeof(float), hipMemcpyDeviceToHost));
-  return VP_OK;
+  return tr.opt.read("vp_train_read", tr.device, tr.stream, 4, which, out, n_floats);
 }
 
 int vp_train_write_weights(vp_trainer* h, const float* weights, size_t n_floats) {
   VP_REQUIRE(h && weights, "vp_train_write_weights: null argument");
   Trainer& tr = *reinterpret_cast<Trainer*>(h);
-  VP_REQUIRE(n_floats == tr.n_params, "vp_train_write_weights: bad size");
-  VP_HIP(hipSetDevice(tr.device));
-  VP_HIP(hipStreamSynchronize(tr.stream));
-  VP_HIP(hipMemcpy(tr.w, weights, n_floats * sizeof(float), hipMemcpyHostToDevice));
-  return VP_OK;
+  VP_REQUIRE(n_floats == tr.n_params, "vp_train_write_weights: bad size");  // (this entry point's own wording)
+  return tr.opt.write("vp_train_write_weights", tr.device, tr.stream, weights, n_floats);
 }
 
 // predictions (B, 3, 3001) of the last step's forward pass

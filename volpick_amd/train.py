@@ -52,6 +52,14 @@ def vector_cross_entropy(y_pred, y_true, eps=1e-5):
 EQT_LOSS_WEIGHTS = (0.05, 0.40, 0.55)  # the reference's EQTransformerLit loss_weights: detection, P, S
 
 
+def _loss_weights(loss_weights):
+    """The three loss weights as the float64 array the library reads."""
+    w = np.ascontiguousarray(loss_weights, np.float64)
+    if w.shape != (3,):
+        raise ValueError(f"loss_weights: three weights (detection, P, S), got {loss_weights!r}")
+    return w
+
+
 def bce_heads(p, y):
     """``torch.nn.BCELoss`` per window and row of (B, C, T) arrays, unreduced over both: the (B, C) float64 means over T
     of ``-(y max(log p, -100) + (1 - y) max(log(1 - p), -100))``.  The clamp is torch's and keeps a NaN."""
@@ -87,51 +95,48 @@ def gaussian_labels(p_samples, s_samples, n_samples=3001, sigma=20.0):
     return y.astype(np.float32)
 
 
-class PhaseNetTrainer:
-    """One device-resident PhaseNet with its gradients and Adam state."""
+class _Trainer:
+    """What the two trainers share, over the entry points ``<_prefix>_*`` of the library: the handle with its hyper-parameters,
+    the checks of a step's x / y, and the flat blob of ``names`` = ``[(tensor, size)]`` read and written by name."""
 
-    DTYPES = {"fp32": _lib.VP_TRAIN_FP32, "float32": _lib.VP_TRAIN_FP32, "32": _lib.VP_TRAIN_FP32, "32-true": _lib.VP_TRAIN_FP32,
-              "bf16": _lib.VP_TRAIN_BF16, "bfloat16": _lib.VP_TRAIN_BF16, "bf16-mixed": _lib.VP_TRAIN_BF16}
+    _prefix = _model_type = _wrong_model = None  # "vp_train" / "vp_eqt_dec_train", the model's class, the refusal of another
 
-    def __init__(self, model: PhaseNet, max_batch=512, device=0, betas=(0.9, 0.999), eps=1e-8, bn_momentum=0.1,
-                 loss_eps=1e-5, dtype="fp32"):
-        """``dtype="bf16"``: activation and gradient tensors stored as bfloat16 with fp32 accumulation, fp32 master
-        weights, statistics and Adam state (Lightning's ``precision="bf16-mixed"`` in spirit; BASELINE config 5);
-        ``"fp32"`` (default) is what the reference's trainer runs."""
-        if str(dtype) not in self.DTYPES:
-            raise ValueError(f"dtype must be one of {sorted(self.DTYPES)}, got {dtype!r}")
-        self.dtype = "bf16" if self.DTYPES[str(dtype)] == _lib.VP_TRAIN_BF16 else "fp32"
-        if not isinstance(model, PhaseNet):
-            raise TypeError("the training step is implemented for PhaseNet")
-        if model._weights is None:
-            raise RuntimeError("model has no weights (use from_pretrained / load / load_state_dict)")
+    def __init__(self, model, max_batch, names, hyper, create):
+        """``create(lib, weights, byref(handle))`` calls the library's constructor; ``hyper``: what follows the handle in
+        ``<_prefix>_set_hyper``."""
         self._lib = _lib.load()
         self.model = model
         self.max_batch = int(max_batch)
         self.in_samples = model.in_samples
-        self.n_params = int(model._weights.size)
+        self.names = names
+        self.n_params = sum(n for _, n in names)
         self._h = C.c_void_p()
         w = np.ascontiguousarray(model._weights, dtype=np.float32)
-        _lib.check(self._lib.vp_train_create_dtype(int(device), _lib.VP_MODEL_PHASENET, _lib.ptr(w), w.size,
-                                                   self.max_batch, self.DTYPES[str(dtype)], C.byref(self._h)), "vp_train_create")
+        _lib.check(create(self._lib, w, C.byref(self._h)), self._prefix + "_create")
         try:
-            _lib.check(self._lib.vp_train_set_hyper(self._h, betas[0], betas[1], eps, bn_momentum, loss_eps), "vp_train_set_hyper")
+            _lib.check(self._c("set_hyper")(self._h, *hyper), self._prefix + "_set_hyper")
         except Exception:
             self.close()  # the handle exists already: release it with the refusal
             raise
         self.global_step = 0
-        self._in_flight = collections.deque()  # (number of a queued step, its x, its y): device inputs kept alive
+
+    @classmethod
+    def _check_model(cls, model):
+        if not isinstance(model, cls._model_type):
+            raise TypeError(cls._wrong_model)
+        if model._weights is None:
+            raise RuntimeError("model has no weights (use from_pretrained / load / load_state_dict)")
+
+    def _c(self, name):
+        return getattr(self._lib, f"{self._prefix}_{name}")
 
     def close(self):
         if getattr(self, "_h", None):
-            if getattr(self, "_in_flight", None):
-                self._lib.vp_train_synchronize(self._h)
-                self._in_flight.clear()
-            self._lib.vp_train_destroy(self._h)
+            self._c("destroy")(self._h)
             self._h = None
-            self._last_inputs = None
 
-    __del__ = close
+    def __del__(self):
+        self.close()
 
     @staticmethod
     def _arg(a):
@@ -143,6 +148,80 @@ class PhaseNetTrainer:
         a = np.ascontiguousarray(a, dtype=np.float32)
         return a, _lib.ptr(a), _lib.VP_MEM_HOST
 
+    def _xy(self, x, y):
+        """The inputs of a step, checked: ``(x kept, its pointer, y kept, its pointer, mem)``."""
+        if tuple(x.shape) != tuple(y.shape) or x.ndim != 3 or x.shape[1] != 3 or x.shape[2] != self.in_samples:
+            raise ValueError(f"expected x and y of shape (B, 3, {self.in_samples}), got {tuple(x.shape)} / {tuple(y.shape)}")
+        xk, xp, xm = self._arg(x)
+        yk, yp, ym = self._arg(y)
+        if xm != ym:
+            raise ValueError("x and y must both be host arrays or both be device tensors")
+        return xk, xp, yk, yp, xm
+
+    def synchronize(self):
+        _lib.check(self._c("synchronize")(self._h))
+
+    def _read(self, which):
+        out = np.empty(self.n_params, dtype=np.float32)
+        _lib.check(self._c("read")(self._h, which, _lib.ptr(out), out.size), self._prefix + "_read")
+        return out
+
+    def _named(self, blob):
+        shapes = {k: s for k, s, is_param in self.model._state_layout if is_param}
+        out, off = {}, 0
+        for key, n in self.names:
+            out[key] = blob[off:off + n].reshape(shapes[key])
+            off += n
+        return out
+
+    def weights(self):
+        return self._named(self._read(0))
+
+    def gradients(self):
+        return self._named(self._read(1))
+
+    def adam_state(self):
+        return self._named(self._read(2)), self._named(self._read(3))
+
+    def write_weights(self, blob):
+        """Replace the flat blob of ``names`` (for PhaseNet: weights and BatchNorm running statistics, the layout of
+        ``model._weights``).  The Adam moments, the update count and the EMA stay as they are (``<_prefix>_write_weights``)."""
+        blob = np.ascontiguousarray(blob, dtype=np.float32)
+        if blob.shape != (self.n_params,):
+            raise ValueError(f"expected a flat blob of {self.n_params} floats, got shape {blob.shape}")
+        _lib.check(self._c("write_weights")(self._h, _lib.ptr(blob), blob.size), self._prefix + "_write_weights")
+
+
+class PhaseNetTrainer(_Trainer):
+    """One device-resident PhaseNet with its gradients and Adam state."""
+
+    DTYPES = {"fp32": _lib.VP_TRAIN_FP32, "float32": _lib.VP_TRAIN_FP32, "32": _lib.VP_TRAIN_FP32, "32-true": _lib.VP_TRAIN_FP32,
+              "bf16": _lib.VP_TRAIN_BF16, "bfloat16": _lib.VP_TRAIN_BF16, "bf16-mixed": _lib.VP_TRAIN_BF16}
+    _prefix, _model_type, _wrong_model = "vp_train", PhaseNet, "the training step is implemented for PhaseNet"
+
+    def __init__(self, model: PhaseNet, max_batch=512, device=0, betas=(0.9, 0.999), eps=1e-8, bn_momentum=0.1,
+                 loss_eps=1e-5, dtype="fp32"):
+        """``dtype="bf16"``: activation and gradient tensors stored as bfloat16 with fp32 accumulation, fp32 master
+        weights, statistics and Adam state (Lightning's ``precision="bf16-mixed"`` in spirit; BASELINE config 5);
+        ``"fp32"`` (default) is what the reference's trainer runs."""
+        if str(dtype) not in self.DTYPES:
+            raise ValueError(f"dtype must be one of {sorted(self.DTYPES)}, got {dtype!r}")
+        self.dtype = "bf16" if self.DTYPES[str(dtype)] == _lib.VP_TRAIN_BF16 else "fp32"
+        self._check_model(model)
+        lib, kind = _lib.load(), _lib.VP_MODEL_PHASENET
+        names = [(lib.vp_param_name(kind, i).decode(), int(lib.vp_param_size(kind, i))) for i in range(lib.vp_param_count(kind))]
+        self._in_flight = collections.deque()  # (number of a queued step, its x, its y): device inputs kept alive
+        super().__init__(model, max_batch, names, (betas[0], betas[1], eps, bn_momentum, loss_eps),
+                         lambda lib, w, h: lib.vp_train_create_dtype(int(device), kind, _lib.ptr(w), w.size, int(max_batch),
+                                                                     self.DTYPES[str(dtype)], h))
+
+    def close(self):
+        if getattr(self, "_h", None) and getattr(self, "_in_flight", None):
+            self._lib.vp_train_synchronize(self._h)
+            self._in_flight.clear()
+        super().close()
+        self._last_inputs = None
+
     def step(self, x, y, lr, update=True, want_loss=True, inputs_unchanged=False):
         """Forward + loss + backward (+ Adam when ``update``).  x, y: (B, 3, 3001).
 
@@ -151,13 +230,8 @@ class PhaseNetTrainer:
         wait for the producer stream again.  It is never inferred: torch's ``Tensor._version`` does not see writes through
         ``x.data``, raw-pointer kernels (this library's own device writers, DLPack consumers) or collective outputs, and a
         loader that refills a persistent buffer that way would be read half-filled."""
-        if tuple(x.shape) != tuple(y.shape) or x.ndim != 3 or x.shape[1] != 3 or x.shape[2] != self.in_samples:
-            raise ValueError(f"expected x and y of shape (B, 3, {self.in_samples}), got {tuple(x.shape)} / {tuple(y.shape)}")
-        xk, xp, xm = self._arg(x)
-        yk, yp, ym = self._arg(y)
+        xk, xp, yk, yp, xm = self._xy(x, y)
         self._drop_consumed()
-        if xm != ym:
-            raise ValueError("x and y must both be host arrays or both be device tensors")
         if xm == _lib.VP_MEM_DEVICE:
             # the trainer runs on its own stream: x / y (or their fp32 copies made above) must be complete first.  An
             # event recorded on torch's stream that the trainer's stream waits for (hipStreamWaitEvent): the host does
@@ -230,37 +304,8 @@ class PhaseNetTrainer:
                 self._in_flight.popleft()
 
     def synchronize(self):
-        _lib.check(self._lib.vp_train_synchronize(self._h))
+        super().synchronize()
         self._in_flight.clear()
-
-    def _read(self, which):
-        out = np.empty(self.n_params, dtype=np.float32)
-        _lib.check(self._lib.vp_train_read(self._h, which, _lib.ptr(out), out.size), "vp_train_read")
-        return out
-
-    def _named(self, blob):
-        lib, out, off = self._lib, {}, 0
-        shapes = {k: s for k, s, is_param in self.model._state_layout if is_param}
-        for i in range(lib.vp_param_count(_lib.VP_MODEL_PHASENET)):
-            key = lib.vp_param_name(_lib.VP_MODEL_PHASENET, i).decode()
-            n = lib.vp_param_size(_lib.VP_MODEL_PHASENET, i)
-            out[key] = blob[off:off + n].reshape(shapes[key])
-            off += n
-        return out
-
-    def weights(self):
-        return self._named(self._read(0))
-
-    def gradients(self):
-        return self._named(self._read(1))
-
-    def write_weights(self, blob):
-        """Replace the flat weight blob (weights and BatchNorm running statistics, the layout of ``model._weights``).  The Adam
-        moments, the update count and the EMA stay as they are (``vp_train_write_weights``)."""
-        blob = np.ascontiguousarray(blob, dtype=np.float32)
-        if blob.shape != (self.n_params,):
-            raise ValueError(f"expected a flat blob of {self.n_params} floats, got shape {blob.shape}")
-        _lib.check(self._lib.vp_train_write_weights(self._h, _lib.ptr(blob), blob.size), "vp_train_write_weights")
 
     def enable_ema(self, decay=0.999):
         """Exponential moving average of the weights after every update (train.py:153-176 of the reference)."""
@@ -268,9 +313,6 @@ class PhaseNetTrainer:
 
     def ema_weights(self):
         return self._named(self._read(4))
-
-    def adam_state(self):
-        return self._named(self._read(2)), self._named(self._read(3))
 
     def predictions(self, B):
         out = np.empty((B, 3, self.in_samples), dtype=np.float32)
@@ -467,41 +509,67 @@ def _validation_pass(model, bank, batches, prefix, lrows, sigma, tail, with_head
     return batch, window, heads, preds
 
 
-class PhaseNetLit:
-    """The arithmetic of the reference's ``PhaseNetLit`` (models.py:108-185): Adam at ``lr`` with the
-    500-step linear warm-up of ``optimizer_step``.  ``training_step(batch)`` takes
-    ``{"X": (B, 3, 3001), "y": (B, 3, 3001)}`` and performs forward, loss, backward AND the
-    optimiser step (Lightning's loop does the last two around the reference's ``training_step``)."""
+class _Lit:
+    """What the two models' lits share: the warm-up of the learning rate, the label check, the trainer made on first use
+    (``_ensure``, the subclass's) and the two small rules of the bank loops."""
 
     WARMUP_STEPS = 500
 
-    def __init__(self, lr=1e-2, sigma=20, max_batch=512, model=None, device=0, precision="32", prob_label_shape="gaussian",
-                 **model_kwargs):
+    def __init__(self, lr, sigma, prob_label_shape, max_batch, device):
         if prob_label_shape != "gaussian":
             raise ValueError(f"prob_label_shape {prob_label_shape!r}: only 'gaussian' labels are implemented (every "
                              "reference config uses them)")
         self.prob_label_shape = prob_label_shape
         self.lr = float(lr)
-        self.precision = str(precision)  # "32" (the reference's) or "bf16-mixed" (PhaseNetTrainer dtype="bf16")
         self.sigma = sigma
-        self.model = model if model is not None else PhaseNet(**model_kwargs)
         self._trainer = None
-        self._ema = False
         self._max_batch, self._device = max_batch, device
-
-    def _ensure(self):
-        if self._trainer is None:
-            self._trainer = PhaseNetTrainer(self.model, max_batch=self._max_batch, device=self._device, dtype=self.precision)
-        return self._trainer
 
     def learning_rate(self, step):
         """lr used by optimiser step number ``step`` (0-based).  Step 0 runs at ``lr`` (the optimiser's initial
-        value).  The reference's ``optimizer_step`` hook (models.py:177-185) runs with ``trainer.global_step`` = the
+        value).  The reference's ``optimizer_step`` hook (models.py:177-185, :562-570) runs with ``trainer.global_step`` = the
         steps completed BEFORE the current one (Lightning counts the step after the hook returns), so after step k it
         sets lr * (k + 1) / 500 for step k + 1: step s >= 1 uses lr * s / 500, and the full lr is reached at step 500."""
         if step == 0 or step >= self.WARMUP_STEPS:
             return self.lr
         return self.lr * step / float(self.WARMUP_STEPS)
+
+    @property
+    def trainer_state(self):
+        return self._ensure()
+
+    @staticmethod
+    def _batches(planner_or_rows):
+        """The batches of a planner (its ``validation()``), of one array of rows (one batch) or of an iterable of such arrays."""
+        if hasattr(planner_or_rows, "validation"):
+            return planner_or_rows.validation()
+        if getattr(getattr(planner_or_rows, "dtype", None), "names", None):
+            return [planner_or_rows]
+        return planner_or_rows
+
+    @staticmethod
+    def _check_full_batch(bank, batch_size):
+        if len(bank.lengths) < batch_size:
+            raise ValueError(f"a bank of {len(bank.lengths)} traces holds no full batch of {batch_size}")
+
+
+class PhaseNetLit(_Lit):
+    """The arithmetic of the reference's ``PhaseNetLit`` (models.py:108-185): Adam at ``lr`` with the
+    500-step linear warm-up of ``optimizer_step``.  ``training_step(batch)`` takes
+    ``{"X": (B, 3, 3001), "y": (B, 3, 3001)}`` and performs forward, loss, backward AND the
+    optimiser step (Lightning's loop does the last two around the reference's ``training_step``)."""
+
+    def __init__(self, lr=1e-2, sigma=20, max_batch=512, model=None, device=0, precision="32", prob_label_shape="gaussian",
+                 **model_kwargs):
+        super().__init__(lr, sigma, prob_label_shape, max_batch, device)
+        self.precision = str(precision)  # "32" (the reference's) or "bf16-mixed" (PhaseNetTrainer dtype="bf16")
+        self.model = model if model is not None else PhaseNet(**model_kwargs)
+        self._ema = False
+
+    def _ensure(self):
+        if self._trainer is None:
+            self._trainer = PhaseNetTrainer(self.model, max_batch=self._max_batch, device=self._device, dtype=self.precision)
+        return self._trainer
 
     def training_step(self, batch, batch_idx=None):
         tr = self._ensure()
@@ -543,12 +611,7 @@ class PhaseNetLit:
         batches with a single host wait.  Returns the list of batch losses; with ``per_window=True``
         ``(batch_losses, window_losses)``, the latter one float64 array over all windows in order."""
         model = self._exported_model()
-        if hasattr(planner_or_rows, "validation"):
-            batches = planner_or_rows.validation()
-        elif getattr(getattr(planner_or_rows, "dtype", None), "names", None):  # one array of rows: one batch
-            batches = [planner_or_rows]
-        else:
-            batches = planner_or_rows
+        batches = self._batches(planner_or_rows)
         batch, window = validate_batches(model, val_bank, batches, self.sigma)
         return (batch.tolist(), window) if per_window else batch.tolist()
 
@@ -593,8 +656,7 @@ class PhaseNetLit:
             planner = WindowPlanner(bank, batch_size, in_samples=in_samples, seed=seed)
         else:
             planner = augment.planner(bank, batch_size, seed, in_samples=in_samples, sigma=self.sigma)
-        if len(bank.lengths) < batch_size:
-            raise ValueError(f"a bank of {len(bank.lengths)} traces holds no full batch of {batch_size}")
+        self._check_full_batch(bank, batch_size)
         val_planner = None
         if val_bank is not None and augment is None:
             val_planner = WindowPlanner(val_bank, batch_size, in_samples=in_samples, seed=seed + 1)
@@ -615,10 +677,6 @@ class PhaseNetLit:
         self._ensure().enable_ema(decay)
         self._ema = True
 
-    @property
-    def trainer_state(self):
-        return self._ensure()
-
 
 def validate_batches_eqt(model, bank, batches, sigma, loss_weights=EQT_LOSS_WEIGHTS, detection_fixed_window=None,
                          predictions=False):
@@ -633,9 +691,7 @@ def validate_batches_eqt(model, bank, batches, sigma, loss_weights=EQT_LOSS_WEIG
     from .generate import detection_label_rows, _fixed_window
 
     lrows = detection_label_rows(model.labels)
-    w = np.ascontiguousarray(loss_weights, np.float64)
-    if w.shape != (3,):
-        raise ValueError(f"loss_weights: three weights (detection, P, S), got {loss_weights!r}")
+    w = _loss_weights(loss_weights)
     tail = (_fixed_window(detection_fixed_window), w.ctypes.data_as(C.POINTER(C.c_double)))
     batch, window, heads, preds = _validation_pass(model, bank, batches, "vp_validate_eqt", lrows, sigma, tail, True, predictions)
     heads = heads[:, lrows]  # by row of y -> (detection, P, S)
@@ -650,71 +706,40 @@ def decoder_param_names():
             for i in range(lib.vp_eqt_dec_train_param_count())]
 
 
-class EQTransformerDecoderTrainer:
+class EQTransformerDecoderTrainer(_Trainer):
     """The three decoder stacks and heads of one EQTransformer on the device, with their gradients and Adam state; the
     trunk is frozen and runs as the inference path (``vp_eqt_dec_train_*``).  ``PhaseNetTrainer``'s role for
     ``EQTransformerLit(trainable="decoders")``.  The trainer builds its own device plan from ``model``'s weights and config
-    when it is made and does not follow later changes of ``model``; ``export()`` writes the trained tensors back."""
+    when it is made and does not follow later changes of ``model``; ``export()`` writes the trained tensors back.
+    ``names``: the 48 trained tensors (``decoder_param_names``)."""
 
     N_SETS = 3  # detection, P, S
+    _prefix, _model_type, _wrong_model = "vp_eqt_dec_train", EQTransformer, "the decoder training step is implemented for EQTransformer"
 
     def __init__(self, model: EQTransformer, max_batch=256, device=0, betas=(0.9, 0.999), eps=1e-8):
-        if not isinstance(model, EQTransformer):
-            raise TypeError("the decoder training step is implemented for EQTransformer")
-        if model._weights is None:
-            raise RuntimeError("model has no weights (use from_pretrained / load / load_state_dict)")
+        self._check_model(model)
         from .generate import detection_label_rows
 
         if list(detection_label_rows(model.labels)) != [0, 1, 2]:
             raise ValueError(f"the trainer's heads are (Detection, P, S) in this order, the model's labels are {model.labels!r}")
-        self._lib = _lib.load()
-        self.model = model
-        self.max_batch = int(max_batch)
-        self.in_samples = model.in_samples
-        self.names = decoder_param_names()
-        self.n_params = int(self._lib.vp_eqt_dec_train_weight_count())
-        self._h = C.c_void_p()
-        w = np.ascontiguousarray(model._weights, dtype=np.float32)
+        self._held = None  # the device inputs / the bank of the latest step: this trainer's steps return complete
         cfg = model._config()
-        _lib.check(self._lib.vp_eqt_dec_train_create(int(device), _lib.ptr(w), w.size, C.byref(cfg), self.max_batch,
-                                                     C.byref(self._h)), "vp_eqt_dec_train_create")
-        try:
-            _lib.check(self._lib.vp_eqt_dec_train_set_hyper(self._h, betas[0], betas[1], eps), "vp_eqt_dec_train_set_hyper")
-        except Exception:
-            self.close()  # the handle exists already: release it with the refusal
-            raise
-        self.global_step = 0
-        self._held = None  # the device inputs / the bank of the latest step
+        super().__init__(model, max_batch, decoder_param_names(), (betas[0], betas[1], eps),
+                         lambda lib, w, h: lib.vp_eqt_dec_train_create(int(device), _lib.ptr(w), w.size, C.byref(cfg), int(max_batch), h))
 
     def close(self):
-        if getattr(self, "_h", None):
-            self._lib.vp_eqt_dec_train_destroy(self._h)
-            self._h = None
-            self._held = None
-
-    __del__ = close
-
-    @staticmethod
-    def _weights_arg(loss_weights):
-        w = np.ascontiguousarray(loss_weights, np.float64)
-        if w.shape != (3,):
-            raise ValueError(f"loss_weights: three weights (detection, P, S), got {loss_weights!r}")
-        return w
+        super().close()
+        self._held = None
 
     def step(self, x, y, lr, loss_weights=EQT_LOSS_WEIGHTS, update=True):
         """Forward + loss + backward (+ Adam when ``update``); returns the loss.  x: (B, 3, 6000), normalised; y: (B, 3, 6000)
         with the rows detection, P, S.  Both numpy arrays or both CUDA tensors (complete on torch's current stream: the call
         waits for that stream, and for its own before it returns)."""
-        if tuple(x.shape) != tuple(y.shape) or x.ndim != 3 or x.shape[1] != 3 or x.shape[2] != self.in_samples:
-            raise ValueError(f"expected x and y of shape (B, 3, {self.in_samples}), got {tuple(x.shape)} / {tuple(y.shape)}")
-        xk, xp, xm = PhaseNetTrainer._arg(x)
-        yk, yp, ym = PhaseNetTrainer._arg(y)
-        if xm != ym:
-            raise ValueError("x and y must both be host arrays or both be device tensors")
+        xk, xp, yk, yp, xm = self._xy(x, y)
         if xm == _lib.VP_MEM_DEVICE:
             _torch().cuda.current_stream(xk.device).synchronize()
         self._held = (xk, yk)
-        w = self._weights_arg(loss_weights)
+        w = _loss_weights(loss_weights)
         loss = C.c_double(float("nan"))
         _lib.check(self._lib.vp_eqt_dec_train_step(self._h, xp, yp, xm, int(x.shape[0]), w.ctypes.data_as(C.POINTER(C.c_double)),
                                                    float(lr), int(bool(update)), C.byref(loss)), "vp_eqt_dec_train_step")
@@ -732,7 +757,7 @@ class EQTransformerDecoderTrainer:
         rows = as_aug_rows(rows) if aug else as_rows(rows)
         name = "vp_eqt_dec_train_step_bank_aug" if aug else "vp_eqt_dec_train_step_bank"
         lrows = np.array([0, 1, 2], np.int32)
-        w = self._weights_arg(loss_weights)
+        w = _loss_weights(loss_weights)
         self._held = bank
         loss = C.c_double(float("nan"))
         _lib.check(getattr(self._lib, name)(self._h, bank.handle, _lib.ptr(rows), len(rows), float(sigma), _norm(self.model.norm),
@@ -743,40 +768,12 @@ class EQTransformerDecoderTrainer:
             self.global_step += 1
         return loss.value
 
-    def synchronize(self):
-        _lib.check(self._lib.vp_eqt_dec_train_synchronize(self._h))
-
-    def _read(self, which):
-        out = np.empty(self.n_params, dtype=np.float32)
-        _lib.check(self._lib.vp_eqt_dec_train_read(self._h, which, _lib.ptr(out), out.size), "vp_eqt_dec_train_read")
-        return out
-
-    def _named(self, blob):
-        shapes = {k: s for k, s, is_param in self.model._state_layout if is_param}
-        out, off = {}, 0
-        for key, n in self.names:
-            out[key] = blob[off:off + n].reshape(shapes[key])
-            off += n
-        return out
-
-    def weights(self):
-        return self._named(self._read(0))
-
-    def gradients(self):
-        return self._named(self._read(1))
-
-    def adam_state(self):
-        return self._named(self._read(2)), self._named(self._read(3))
-
     def write_weights(self, blob):
         """Replace the 145,731 trained floats (the order of ``names``; a dict of the 48 tensors is flattened).  The Adam
         moments and the update count stay as they are (``vp_eqt_dec_train_write_weights``)."""
         if isinstance(blob, dict):
             blob = np.concatenate([np.asarray(blob[k], np.float32).ravel() for k, _ in self.names])
-        blob = np.ascontiguousarray(blob, dtype=np.float32)
-        if blob.shape != (self.n_params,):
-            raise ValueError(f"expected a flat blob of {self.n_params} floats, got shape {blob.shape}")
-        _lib.check(self._lib.vp_eqt_dec_train_write_weights(self._h, _lib.ptr(blob), blob.size), "vp_eqt_dec_train_write_weights")
+        super().write_weights(blob)
 
     def tensors(self, B):
         """Every tensor of the last step (a batch of ``B`` windows) by name: ``decoder.in``, ``a0`` .. ``a6``, ``logits``,
@@ -816,7 +813,7 @@ class EQTransformerDecoderTrainer:
 TRAINABLE = ("decoders",)
 
 
-class EQTransformerLit:
+class EQTransformerLit(_Lit):
     """The reference's ``EQTransformerLit`` (models.py:483-879): block 1's batch or the stacked recipe's
     (``augmented_planner``; the reference's ``get_val_augmentations`` with ``stack_data``) and ``shared_step``'s loss
     ``loss_weights[0] BCE(detection) + loss_weights[1] BCE(P) + loss_weights[2] BCE(S)``, by which the reference selects its
@@ -827,27 +824,15 @@ class EQTransformerLit:
     decoder stacks and their heads with the trunk frozen (``EQTransformerDecoderTrainer``): ``training_step(batch)`` on the
     same dictionaries and ``fit_bank``.  Training the trunk is not implemented."""
 
-    WARMUP_STEPS = 500
-
     def __init__(self, lr=1e-2, sigma=20, loss_weights=EQT_LOSS_WEIGHTS, detection_fixed_window=None,
                  prob_label_shape="gaussian", model=None, device=0, trainable=None, max_batch=256, **model_kwargs):
-        if prob_label_shape != "gaussian":
-            raise ValueError(f"prob_label_shape {prob_label_shape!r}: only 'gaussian' labels are implemented (every "
-                             "reference config uses them)")
-        if len(loss_weights) != 3:
-            raise ValueError(f"loss_weights: three weights (detection, P, S), got {loss_weights!r}")
+        super().__init__(lr, sigma, prob_label_shape, max_batch, device)
+        self.loss_weights = tuple(float(w) for w in _loss_weights(loss_weights))
         if trainable is not None and trainable not in TRAINABLE:
             raise ValueError(f"trainable must be None or 'decoders' (the decoder stacks and heads, trunk frozen), got {trainable!r}")
         self.trainable = trainable
-        self._trainer = None
-        self._max_batch = max_batch
-        self.prob_label_shape = prob_label_shape
-        self.lr = float(lr)
-        self.sigma = sigma
-        self.loss_weights = tuple(float(w) for w in loss_weights)
         self.detection_fixed_window = detection_fixed_window
         self.model = model if model is not None else EQTransformer(**model_kwargs)
-        self._device = device
 
     def _model_on_device(self):
         """``self.model`` on the GPU; with a trainer, holding the trainer's current weights (exported only when an update has
@@ -868,16 +853,6 @@ class EQTransformerLit:
         if self._trainer is None:
             self._trainer = EQTransformerDecoderTrainer(self.model, max_batch=self._max_batch, device=self._device)
         return self._trainer
-
-    @property
-    def trainer_state(self):
-        return self._ensure()
-
-    def learning_rate(self, step):
-        """lr of optimiser step ``step`` (0-based): the reference's 500-step linear warm-up (models.py:562-570), the rule of
-        ``PhaseNetLit.learning_rate``."""
-        return PhaseNetLit.learning_rate(self, step)
-
     def training_step(self, batch, batch_idx=None):
         """``trainable="decoders"``: forward, loss, backward and the Adam step on ``{"X", "y", "detections"}`` (what
         ``make_batch`` returns); returns the loss.  Otherwise raises ``NotImplementedError``."""
@@ -899,8 +874,7 @@ class EQTransformerLit:
         (one shared host loop).  Returns the per-step losses and, with ``val_bank``, ``(losses, val_losses)``."""
         scheduler = _fit_scheduler(lr_scheduler, lr_scheduler_args, val_bank, keep_best, early_stop_patience)
         tr = self._ensure()
-        if len(bank.lengths) < batch_size:
-            raise ValueError(f"a bank of {len(bank.lengths)} traces holds no full batch of {batch_size}")
+        self._check_full_batch(bank, batch_size)
         plan = (lambda b, s, v: self.window_planner(b, batch_size, seed=s)) if augment is None else \
             (lambda b, s, v: self.augmented_planner(b, batch_size, augment, seed=s, validation=v))
         planner = plan(bank, seed, False)
@@ -949,12 +923,7 @@ class EQTransformerLit:
         ``augmented_planner`` this is the reference's validation pass), one array of rows (one batch) or an iterable of such
         arrays, plan rows or augmented rows -- on the GPU from end to end (``validate_batches_eqt``: one host wait).  Returns the list of batch losses; with ``per_window=True`` ``(batch_losses, window_losses)``, the latter one
         float64 array over all windows in order."""
-        if hasattr(planner_or_rows, "validation"):
-            batches = planner_or_rows.validation()
-        elif getattr(getattr(planner_or_rows, "dtype", None), "names", None):  # one array of rows: one batch
-            batches = [planner_or_rows]
-        else:
-            batches = planner_or_rows
+        batches = self._batches(planner_or_rows)
         batch, window, _ = validate_batches_eqt(self._model_on_device(), val_bank, batches, self.sigma, self.loss_weights,
                                                 self.detection_fixed_window)
         return (batch.tolist(), window) if per_window else batch.tolist()
