@@ -1,5 +1,6 @@
-// Convolutions on the bf16 matrix cores with EXACT operands (the PhaseNet core's five deepest layers; the EQTransformer
-// ResCNN kernel in eqt_res.hip is the same idea written out by hand).
+// Convolutions on the bf16 matrix cores with EXACT operands: the primitives every bf16-piece kernel of both models shares (split,
+// piece store, product group), the column-layout conv of the PhaseNet core's deepest layers and the chunk-plane loops of the
+// time-tiled kernels.
 //
 // An fp32 number is exactly the sum of three bfloat16 pieces (hi = rne(x), mid = rne(x - hi), lo = x - hi - mid: 8 + 8 + 8
 // significant bits), bf16 x bf16 products are exact in fp32, and v_mfma_f32_16x16x32_bf16 runs at 16x the rate of the
@@ -30,29 +31,73 @@ struct B3Image {
   int ps, c0;
 };
 
+// ---- the primitives of the bf16-piece form: every kernel's split, piece store and product group are these -------------------
+// B3_EXP (timing probes of tools/, never in the product build; results are WRONG with any of them): 4 = the piece stores compute
+// the pieces and store nothing, 16 = they do not compute them either, 32 = b3c_store4 stores them where sixteen lanes fill 128
+// contiguous bytes.  Consulted in b3_split4, b3_put4 and b3c_store4, nowhere else.
+#ifndef B3_EXP
+#define B3_EXP 0
+#endif
 __device__ __forceinline__ void b3_split(const float v, unsigned short& h, unsigned short& m, unsigned short& l) {
   h = to_bf16(v);
   const float r1 = v - from_bf16(h);
   m = to_bf16(r1);
   l = to_bf16(r1 - from_bf16(m));
 }
-// four consecutive channels ch .. ch + 3 of column col: one 8-byte store per piece
-__device__ __forceinline__ void b3_store4(bf16_t* img, const int ps, const int cs, const int col, const int ch, const float (&v)[4]) {
-  // pairs at a time: one v_cvt_pk_bf16_f32 rounds two values and leaves them packed (the same pieces as b3_split's)
+// four values -> three piece quads, pairs at a time: one v_cvt_pk_bf16_f32 rounds two values and leaves them packed (the same
+// pieces as b3_split's).  The two pairs side by side: as one pair-split helper called twice the conversions come in another
+// order, and hipcc's code for sixteen kernels changes with that (tools/kernel_digest.py).
+struct B3Quad {
+  uint2 h, m, l;
+};
+__device__ __forceinline__ B3Quad b3_split4(const float (&v)[4]) {
+  if (B3_EXP & 16) {
+    asm volatile("" ::"v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]));
+    return B3Quad{};
+  }
   const unsigned h0 = pack_bf16x2(v[0], v[1]), h1 = pack_bf16x2(v[2], v[3]);
   const float r0 = v[0] - bf16_lo(h0), r1 = v[1] - bf16_hi(h0), r2 = v[2] - bf16_lo(h1), r3 = v[3] - bf16_hi(h1);
   const unsigned m0 = pack_bf16x2(r0, r1), m1 = pack_bf16x2(r2, r3);
   const unsigned l0 = pack_bf16x2(r0 - bf16_lo(m0), r1 - bf16_hi(m0)), l1 = pack_bf16x2(r2 - bf16_lo(m1), r3 - bf16_hi(m1));
-  bf16_t* p = img + col * cs + ch;
-#ifdef B3_EXP
-  if (B3_EXP & 4) {  // timing probe (see b3c_store4): the pieces are computed, nothing is stored
-    asm volatile("" ::"v"(h0), "v"(h1), "v"(m0), "v"(m1), "v"(l0), "v"(l1), "v"(p));
+  return B3Quad{make_uint2(h0, h1), make_uint2(m0, m1), make_uint2(l0, l1)};
+}
+// one 8-byte store per piece: p, p + ps, p + 2 ps (ps in units of T); every layout's store is its addressing in front of this
+template <class T>
+__device__ __forceinline__ void b3_put4(T* p, const int ps, const B3Quad s) {
+  if (B3_EXP & 16) return;
+  if (B3_EXP & 4) {
+    asm volatile("" ::"v"(s.h.x), "v"(s.h.y), "v"(s.m.x), "v"(s.m.y), "v"(s.l.x), "v"(s.l.y), "v"(p));
     return;
   }
-#endif
-  *reinterpret_cast<uint2*>(p) = make_uint2(h0, h1);
-  *reinterpret_cast<uint2*>(p + ps) = make_uint2(m0, m1);
-  *reinterpret_cast<uint2*>(p + 2 * ps) = make_uint2(l0, l1);
+  *reinterpret_cast<uint2*>(p) = s.h;
+  *reinterpret_cast<uint2*>(p + ps) = s.m;
+  *reinterpret_cast<uint2*>(p + 2 * ps) = s.l;
+}
+// one MFMA: acc += w x over K = 32, both operands 8 bf16 per lane.  (The parameter passing of these helpers is part of their
+// spelling: b3_put4 with the pieces by reference, or b3_mfma with its operands by value, changes hipcc's code for a dozen
+// kernels -- tools/kernel_digest.py.)
+__device__ __forceinline__ f32x4 b3_mfma(const f32x4 acc, const uint4& w, const uint4& x) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_b3, w), __builtin_bit_cast(bf16x8_b3, x), acc, 0, 0, 0);
+}
+// the exact product group: (w piece, x piece) of its six MFMAs, smallest products first
+struct B3Product {
+  int w, x;
+};
+constexpr B3Product b3_product(const int t) {
+  constexpr int WP[6] = {2, 1, 0, 1, 0, 0}, XP[6] = {0, 1, 2, 0, 1, 0};
+  return B3Product{WP[t], XP[t]};
+}
+// acc += w x for three-piece operands w[3], x[3] of one K-step
+__device__ __forceinline__ f32x4 b3_mac6(const uint4* w, const uint4* x, f32x4 acc) {
+#pragma unroll
+  for (int t = 0; t < 6; ++t) acc = b3_mfma(acc, w[b3_product(t).w], x[b3_product(t).x]);
+  return acc;
+}
+
+// four consecutive channels ch .. ch + 3 of column col of a [piece][column][cs channels] image
+__device__ __forceinline__ void b3_store4(bf16_t* img, const int ps, const int cs, const int col, const int ch, const float (&v)[4]) {
+  const B3Quad s = b3_split4(v);
+  b3_put4(img + col * cs + ch, ps, s);
 }
 
 // Output side of a layer: a three-piece image.  Columns [col_lo, col_hi) are the ones the layer's tiles write (zeros
@@ -158,12 +203,10 @@ __device__ __forceinline__ void conv_b3_impl(const B3Image<C1> i1, const B3Image
         const int i = s * NB + j;
         if (i + 1 < STEPS * NB) load_b(b[(i + 1) & 1], (i + 1) / NB, (i + 1) % NB);
         __builtin_amdgcn_sched_barrier(0);
-        // (w piece, x piece), smallest products first
-        constexpr int WP[6] = {2, 1, 0, 1, 0, 0}, XP[6] = {0, 1, 2, 0, 1, 0};
+        // b3_mac6(q[s % (PF + 1)], b[i & 1], acc[j]) written out: kept for the instruction stream -- with the call in its place
+        // hipcc's code for the default pn_window_kernel changes (tools/kernel_digest.py)
 #pragma unroll
-        for (int t = 0; t < 6; ++t)
-          acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_b3, q[s % (PF + 1)][WP[t]]),
-                                                          __builtin_bit_cast(bf16x8_b3, b[i & 1][XP[t]]), acc[j], 0, 0, 0);
+        for (int t = 0; t < 6; ++t) acc[j] = b3_mfma(acc[j], q[s % (PF + 1)][b3_product(t).w], b[i & 1][b3_product(t).x]);
         __builtin_amdgcn_sched_barrier(0);
       }
     }
@@ -244,11 +287,7 @@ __device__ __forceinline__ void conv_b3_part_impl(const B3Image<32> im, const ui
       const int i = tap * NB + j;
       if (i + 1 < L::TAPS * NB) load_b(b[(i + 1) & 1], (i + 1) / NB, (i + 1) % NB);
       __builtin_amdgcn_sched_barrier(0);
-      constexpr int WP[6] = {2, 1, 0, 1, 0, 0}, XP[6] = {0, 1, 2, 0, 1, 0};
-#pragma unroll
-      for (int t = 0; t < 6; ++t)
-        acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_b3, q[tap % (PF + 1)][WP[t]]),
-                                                        __builtin_bit_cast(bf16x8_b3, b[i & 1][XP[t]]), acc[j], 0, 0, 0);
+      acc[j] = b3_mac6(q[tap % (PF + 1)], b[i & 1], acc[j]);
       __builtin_amdgcn_sched_barrier(0);
     }
   }
@@ -332,32 +371,14 @@ __device__ void b3c_dump(const bf16_t* img, const int c0, const int L, float* ds
     dst[c * ls + t] = from_bf16(p[0]) + (from_bf16(p[Q::PS]) + from_bf16(p[2 * Q::PS]));
   }
 }
-// four consecutive channels 4 quad .. 4 quad + 3 of column col, split into the three pieces (pairs at a time: v_cvt_pk_bf16_f32)
-// B3_EXP (timing probes of tools/, never in the product build; results are WRONG with any of them): 4 = b3c_store4 computes the
-// pieces and stores nothing, 16 = it does not compute them either, 32 = it stores them where sixteen lanes fill 128 contiguous bytes
-#ifndef B3_EXP
-#define B3_EXP 0
-#endif
+// four consecutive channels 4 quad .. 4 quad + 3 of column col
 template <int C, int NC>
 __device__ __forceinline__ void b3c_store4(bf16_t* img, const int col, const int quad, const float (&v)[4]) {
   using Q = B3Chunk<C, NC>;
-  if (B3_EXP & 16) {
-    asm volatile("" ::"v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]));
-    return;
-  }
-  const unsigned h0 = pack_bf16x2(v[0], v[1]), h1 = pack_bf16x2(v[2], v[3]);
-  const float r0 = v[0] - bf16_lo(h0), r1 = v[1] - bf16_hi(h0), r2 = v[2] - bf16_lo(h1), r3 = v[3] - bf16_hi(h1);
-  const unsigned m0 = pack_bf16x2(r0, r1), m1 = pack_bf16x2(r2, r3);
-  const unsigned l0 = pack_bf16x2(r0 - bf16_lo(m0), r1 - bf16_hi(m0)), l1 = pack_bf16x2(r2 - bf16_lo(m1), r3 - bf16_hi(m1));
+  const B3Quad s = b3_split4(v);
   bf16_t* p = img + (quad >> 1) * Q::CHS + col * 8 + (quad & 1) * 4;
   if (B3_EXP & 32) p = img + (quad >> 1) * Q::CHS + ((col >> 5) * 16 + (threadIdx.x & 15)) * 4;  // 16 lanes -> 128 contiguous bytes: no bank conflict
-  if (B3_EXP & 4) {
-    asm volatile("" ::"v"(h0), "v"(h1), "v"(m0), "v"(m1), "v"(l0), "v"(l1), "v"(p));
-    return;
-  }
-  *reinterpret_cast<uint2*>(p) = make_uint2(h0, h1);
-  *reinterpret_cast<uint2*>(p + Q::PS) = make_uint2(m0, m1);
-  *reinterpret_cast<uint2*>(p + 2 * Q::PS) = make_uint2(l0, l1);
+  b3_put4(p, Q::PS, s);
 }
 // the lane's pointer for b3c_mac_tiles: piece 0, its chunk, column col0 + lane % 16 + tap_of_lane
 template <int C, int NC, int TAPS>
@@ -365,6 +386,13 @@ __device__ __forceinline__ const bf16_t* b3c_lane_ptr(const bf16_t* img, const i
   using G = B3Steps<C, TAPS>;
   const int g = lane >> 4;
   return img + (G::ch_of_lane(g) / 8) * B3Chunk<C, NC>::CHS + (col0 + (lane & 15) + G::tap_of_lane(g)) * 8;
+}
+// element offset, relative to that pointer, of the fragment of K-step s at n-tile j.  C >= 32: step = (tap, 32-channel step ks),
+// four chunk planes further per ks; C < 32: TPK taps per step
+template <int C, int NC, int TAPS>
+constexpr int b3c_frag_off(const int s, const int j) {
+  using G = B3Steps<C, TAPS>;
+  return ((C >= 32 ? s / G::KS : s * G::TPK) + j * 16) * 8 + (C >= 32 ? (s % G::KS) * 4 * B3Chunk<C, NC>::CHS : 0);
 }
 // One m-tile (operand `a` in registers) x NB n-tiles, n-tile after n-tile: the accumulator of n-tile j goes to
 // finish(j, acc) -- branch-free code: bias, activation, split, stores -- while the fragments of n-tile j + 1 are on their
@@ -376,15 +404,12 @@ struct B3NoSlot {
 };
 template <int C, int NC, int TAPS, int NB, class Finish, class Slot = B3NoSlot>
 __device__ __forceinline__ void b3c_mac_tiles(const bf16_t* p, const uint4 (&a)[B3Steps<C, TAPS>::STEPS * 3], Finish finish, Slot slot = Slot()) {
-  using G = B3Steps<C, TAPS>;
   using Q = B3Chunk<C, NC>;
-  constexpr int STEPS = G::STEPS;
+  constexpr int STEPS = B3Steps<C, TAPS>::STEPS;
   constexpr int AHEAD = 2, NBUF = AHEAD + 1, PAIRS = STEPS * NB;
   uint4 b[NBUF][3];
   auto load_b = [&](const int i) {
-    const int s = i % STEPS, j = i / STEPS;
-    // C >= 32: step = (tap, 32-channel step ks): four chunk planes further per ks; C < 32: TPK taps per step
-    const int off = ((C >= 32 ? s / G::KS : s * G::TPK) + j * 16) * 8 + (C >= 32 ? (s % G::KS) * 4 * Q::CHS : 0);
+    const int off = b3c_frag_off<C, NC, TAPS>(i % STEPS, i / STEPS);
 #pragma unroll
     for (int pc = 0; pc < 3; ++pc) b[i % NBUF][pc] = *reinterpret_cast<const uint4*>(p + pc * Q::PS + off);
   };
@@ -401,11 +426,7 @@ __device__ __forceinline__ void b3c_mac_tiles(const bf16_t* p, const uint4 (&a)[
       const int i = j * STEPS + s;
       if (i + AHEAD < PAIRS) load_b(i + AHEAD);
       slot(i);
-      constexpr int WP[6] = {2, 1, 0, 1, 0, 0}, XP[6] = {0, 1, 2, 0, 1, 0};  // (w piece, x piece), smallest products first
-#pragma unroll
-      for (int t = 0; t < 6; ++t)
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_b3, a[s * 3 + WP[t]]),
-                                                     __builtin_bit_cast(bf16x8_b3, b[i % NBUF][XP[t]]), acc, 0, 0, 0);
+      acc = b3_mac6(a + s * 3, b[i % NBUF], acc);
     }
     __builtin_amdgcn_sched_barrier(0);
     prev = acc;
@@ -417,16 +438,14 @@ __device__ __forceinline__ void b3c_mac_tiles(const bf16_t* p, const uint4 (&a)[
 // wave issues them back to back (a chain into one accumulator issues every 20-26 cycles from one wave, LOG.md).  NB even.
 template <int C, int NC, int TAPS, int NB, class Finish, class Slot = B3NoSlot>
 __device__ __forceinline__ void b3c_mac_tile_pairs(const bf16_t* p, const uint4 (&a)[B3Steps<C, TAPS>::STEPS * 3], Finish finish, Slot slot = Slot()) {
-  using G = B3Steps<C, TAPS>;
   using Q = B3Chunk<C, NC>;
   static_assert(NB % 2 == 0, "pairs of n-tiles");
-  constexpr int STEPS = G::STEPS, PAIRS = STEPS * (NB / 2);
+  constexpr int STEPS = B3Steps<C, TAPS>::STEPS, PAIRS = STEPS * (NB / 2);
   uint4 b[2][2][3];  // [buffer][tile of the pair][piece]
   auto load_b = [&](const int i) {  // i = pair index * STEPS + step
-    const int s = i % STEPS, jp = i / STEPS;
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-      const int off = ((C >= 32 ? s / G::KS : s * G::TPK) + (2 * jp + h) * 16) * 8 + (C >= 32 ? (s % G::KS) * 4 * Q::CHS : 0);
+      const int off = b3c_frag_off<C, NC, TAPS>(i % STEPS, 2 * (i / STEPS) + h);
 #pragma unroll
       for (int pc = 0; pc < 3; ++pc) b[i & 1][h][pc] = *reinterpret_cast<const uint4*>(p + pc * Q::PS + off);
     }
@@ -446,13 +465,10 @@ __device__ __forceinline__ void b3c_mac_tile_pairs(const bf16_t* p, const uint4 
       const int i = jp * STEPS + s;
       if (i + 1 < PAIRS) load_b(i + 1);
       slot(i);
-      constexpr int WP[6] = {2, 1, 0, 1, 0, 0}, XP[6] = {0, 1, 2, 0, 1, 0};
 #pragma unroll
-      for (int t = 0; t < 6; ++t) {
-        acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_b3, a[s * 3 + WP[t]]),
-                                                      __builtin_bit_cast(bf16x8_b3, b[i & 1][0][XP[t]]), acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_b3, a[s * 3 + WP[t]]),
-                                                      __builtin_bit_cast(bf16x8_b3, b[i & 1][1][XP[t]]), acc1, 0, 0, 0);
+      for (int t = 0; t < 6; ++t) {  // b3_mac6's products, the two tiles alternating
+        acc0 = b3_mfma(acc0, a[s * 3 + b3_product(t).w], b[i & 1][0][b3_product(t).x]);
+        acc1 = b3_mfma(acc1, a[s * 3 + b3_product(t).w], b[i & 1][1][b3_product(t).x]);
       }
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -467,14 +483,12 @@ __device__ __forceinline__ void b3c_mac_tile_pairs(const bf16_t* p, const uint4 
 // in two passes over ONE image that is refilled in between (PhaseNet up2.same).
 template <int C, int NC, int TAPS, int NB>
 __device__ __forceinline__ void b3c_mac_tiles_acc(const bf16_t* p, const uint4 (&a)[B3Steps<C, TAPS>::STEPS * 3], f32x4 (&acc)[NB]) {
-  using G = B3Steps<C, TAPS>;
   using Q = B3Chunk<C, NC>;
-  constexpr int STEPS = G::STEPS;
+  constexpr int STEPS = B3Steps<C, TAPS>::STEPS;
   constexpr int AHEAD = 1, NBUF = AHEAD + 1, PAIRS = STEPS * NB;
   uint4 b[NBUF][3];
   auto load_b = [&](const int i) {
-    const int s = i % STEPS, j = i / STEPS;
-    const int off = ((C >= 32 ? s / G::KS : s * G::TPK) + j * 16) * 8 + (C >= 32 ? (s % G::KS) * 4 * Q::CHS : 0);
+    const int off = b3c_frag_off<C, NC, TAPS>(i % STEPS, i / STEPS);
 #pragma unroll
     for (int pc = 0; pc < 3; ++pc) b[i % NBUF][pc] = *reinterpret_cast<const uint4*>(p + pc * Q::PS + off);
   };
@@ -486,11 +500,7 @@ __device__ __forceinline__ void b3c_mac_tiles_acc(const bf16_t* p, const uint4 (
       const int i = j * STEPS + s;
       if (i + AHEAD < PAIRS) load_b(i + AHEAD);
       __builtin_amdgcn_sched_barrier(0);
-      constexpr int WP[6] = {2, 1, 0, 1, 0, 0}, XP[6] = {0, 1, 2, 0, 1, 0};
-#pragma unroll
-      for (int t = 0; t < 6; ++t)
-        acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_b3, a[s * 3 + WP[t]]),
-                                                        __builtin_bit_cast(bf16x8_b3, b[i % NBUF][XP[t]]), acc[j], 0, 0, 0);
+      acc[j] = b3_mac6(a + s * 3, b[i % NBUF], acc[j]);
       __builtin_amdgcn_sched_barrier(0);
     }
   }

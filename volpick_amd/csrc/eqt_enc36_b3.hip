@@ -113,6 +113,26 @@ __device__ __forceinline__ void zero_pads(bf16_t* img, const int len, const int 
   }
 }
 
+// Stages 3, 4, 5: this wave's block `blk` of NB n-tiles of m-tile `mt` of the conv (CI channels, TAPS taps) over the image xin
+// (NCI columns, row length N_IN), pooled into the next stage's input image xout (CO channels, NCO columns, sample t at column
+// t + KO, row length N_OUT), whose padding columns are cleared beside it; SLOT: the stage's DUMP tensor.  n, g: the kernel's
+// lane % 16 and lane / 16, handed in: derived from `lane` again in here, hipcc's code for the kernel changes (tools/kernel_digest.py)
+template <int CI, int NCI, int TAPS, int NB, int N_IN, int CO, int NCO, int KO, int N_OUT, int SLOT, class Dump>
+__device__ __forceinline__ void e3_stage(const bf16_t* xin, bf16_t* xout, const uint4 (&a)[B3Steps<CI, TAPS>::STEPS * 3], const float (&bias)[4],
+                                         const int mt, const int blk, const int tid, const int lane, const int n, const int g, const Dump& dump) {
+  zero_pads<B3Chunk<CO, NCO>, CO / 8, KO, NCO>(xout, N_OUT, tid);
+  const int colb = blk * (NB * 16);
+  b3c_mac_tiles<CI, NCI, TAPS, NB>(b3c_lane_ptr<CI, NCI, TAPS>(xin, colb, lane), a, [&](const int j, const f32x4 acc) {
+    const int c = colb + j * 16 + n;
+    float m[4];
+    pool4(acc, bias, c < N_IN, m);
+    if (!(n & 1) && (c >> 1) < N_OUT) {
+      b3c_store4<CO, NCO>(xout, (c >> 1) + KO, 4 * mt + g, m);
+      dump(SLOT, 16 * mt + 4 * g, c >> 1, m);
+    }
+  });
+}
+
 template <bool DUMP = false>
 __global__ __launch_bounds__(E3_NTH) void eqt_enc36_b3_kernel(const std::conditional_t<DUMP, Enc36B3DumpArgs, Enc36B3Args> a) {
   extern __shared__ uint4 e3_lds[];
@@ -165,55 +185,22 @@ __global__ __launch_bounds__(E3_NTH) void eqt_enc36_b3_kernel(const std::conditi
     float bias4[4];
     e3_load_a<32, 5>(a.af3[1], mt2, lane, a4);
     e3_load4(a.bs[1] + mt2 * 16, lane, bias4);
-    {  // stage 3: 16 x 750 -> 32 x 375
-      zero_pads<Q4, 4, K4, NC4>(X4, N4, tid);
-      const int colb = blk2 * (NB3 * 16);
-      b3c_mac_tiles<16, NC3, 7, NB3>(b3c_lane_ptr<16, NC3, 7>(X3, colb, lane), a3, [&](const int j, const f32x4 acc) {
-        const int c = colb + j * 16 + n;
-        float m[4];
-        pool4(acc, bias3, c < N3, m);
-        if (!(n & 1) && (c >> 1) < N4) {
-          b3c_store4<32, NC4>(X4, (c >> 1) + K4, 4 * mt2 + g, m);
-          dump(0, 16 * mt2 + 4 * g, c >> 1, m);
-        }
-      });
-    }
+    // stage 3: 16 x 750 -> 32 x 375
+    e3_stage<16, NC3, 7, NB3, N3, 32, NC4, K4, N4, 0>(X3, X4, a3, bias3, mt2, blk2, tid, lane, n, g, dump);
     __syncthreads();
     uint4 a5[B3Steps<32, 5>::STEPS * 3];
     float bias5[4];
     e3_load_a<32, 5>(a.af3[2], mt4, lane, a5);
     e3_load4(a.bs[2] + mt4 * 16, lane, bias5);
-    {  // stage 4: 32 x 375 -> 32 x 188 (odd tail pooled alone)
-      zero_pads<Q5, 4, K5, NC5>(X5, N5, tid);
-      const int colb = blk2 * (NB4 * 16);
-      b3c_mac_tiles<32, NC4, 5, NB4>(b3c_lane_ptr<32, NC4, 5>(X4, colb, lane), a4, [&](const int j, const f32x4 acc) {
-        const int c = colb + j * 16 + n;
-        float m[4];
-        pool4(acc, bias4, c < N4, m);
-        if (!(n & 1) && (c >> 1) < N5) {
-          b3c_store4<32, NC5>(X5, (c >> 1) + K5, 4 * mt2 + g, m);
-          dump(1, 16 * mt2 + 4 * g, c >> 1, m);
-        }
-      });
-    }
+    // stage 4: 32 x 375 -> 32 x 188 (odd tail pooled alone)
+    e3_stage<32, NC4, 5, NB4, N4, 32, NC5, K5, N5, 1>(X4, X5, a4, bias4, mt2, blk2, tid, lane, n, g, dump);
     __syncthreads();
     uint4 a6[B3Steps<64, 3>::STEPS * 3];
     float bias6[4];
     e3_load_a<64, 3>(a.af3[3], mt4, lane, a6);
     e3_load4(a.bs[3] + mt4 * 16, lane, bias6);
-    {  // stage 5: 32 x 188 -> 64 x 94
-      zero_pads<Q6, 8, K6, NC6>(X6, N6, tid);
-      const int colb = blk4 * (NB5 * 16);
-      b3c_mac_tiles<32, NC5, 5, NB5>(b3c_lane_ptr<32, NC5, 5>(X5, colb, lane), a5, [&](const int j, const f32x4 acc) {
-        const int c = colb + j * 16 + n;
-        float m[4];
-        pool4(acc, bias5, c < N5, m);
-        if (!(n & 1) && (c >> 1) < N6) {
-          b3c_store4<64, NC6>(X6, (c >> 1) + K6, 4 * mt4 + g, m);
-          dump(2, 16 * mt4 + 4 * g, c >> 1, m);
-        }
-      });
-    }
+    // stage 5: 32 x 188 -> 64 x 94
+    e3_stage<32, NC5, 5, NB5, N5, 64, NC6, K6, N6, 2>(X5, X6, a5, bias5, mt4, blk4, tid, lane, n, g, dump);
     __syncthreads();
     {  // stage 6: 64 x 94 -> 64 x 47, to memory with the first residual block's BN-ReLU beside it
       float* y = a.y + (long)win * a.ws_y + HALO;

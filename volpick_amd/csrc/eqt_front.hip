@@ -289,7 +289,7 @@ struct Pool0Pieces {
       float v0 = fmaxf(fmaxf(acc[j][0] + biasv[0], 0.f), fmaxf(acc[j][1] + biasv[1], 0.f));
       float v1 = fmaxf(fmaxf(acc[j][2] + biasv[2], 0.f), fmaxf(acc[j][3] + biasv[3], 0.f));
       if (!fast && !((unsigned)(s_lo + colb + j * 16 + n) < (unsigned)L0P)) v0 = v1 = 0.f;
-      const unsigned h = pack_bf16x2(v0, v1);
+      const unsigned h = pack_bf16x2(v0, v1);  // one pair: the short form of conv_b3.h's b3_split4
       const float r0 = v0 - bf16_lo(h), r1 = v1 - bf16_hi(h);
       const unsigned m = pack_bf16x2(r0, r1);
       const unsigned l = pack_bf16x2(r0 - bf16_lo(m), r1 - bf16_hi(m));

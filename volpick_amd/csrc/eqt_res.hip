@@ -5,8 +5,7 @@
 // (plan flag plan_flags[0] = 1 keeps those for A/B timing and the layer-by-layer parity test).
 #include <type_traits>
 
-#include "bf16.h"
-#include "conv_lds.h"
+#include "conv_b3.h"
 #include "eqt_kernels.h"
 #include "net.h"
 
@@ -152,28 +151,19 @@ __global__ __launch_bounds__(256) void eqt_res_kernel(const ResArgs a) {
 
 
 
-// ---- the same stack on the bf16 matrix cores, with EXACT operands --------------------------------------------------------
-// An fp32 number is exactly the sum of three bfloat16 pieces (hi = rne(x), mid = rne(x - hi), lo = x - hi - mid: 8 + 8 + 8
-// significant bits), bf16 x bf16 products are exact in fp32, and v_mfma_f32_16x16x32_bf16 runs at 16x the rate of the
-// fp32 form.  w x = sum over pieces; the six products (w_hi, w_mid, w_lo) x (x_hi, x_mid, x_lo) with i + j <= 2 carry
-// everything down to 2^-24 of |w x| (what is dropped -- mid x lo, lo x mid, lo x lo -- is of the order of the rounding
-// of a single fp32 product), so the sums agree with the fp32-MFMA kernel above to fp32 rounding, at 6 / 16 of its matrix
-// time.  (Activations cut to two pieces would need five products and move the probabilities by up to 4e-5,
-// tools/split_bf16_study.py: not done -- parity first.)
-//   K of an instruction = 32 input channels at ONE tap (a lane supplies 8 consecutive channels), so the conv inputs
-//   rest in LDS as three bf16 images (layout below): a B fragment is one 16-byte read per piece, and a
-//   lane's four accumulator rows (four consecutive output channels of one column) are one 8-byte store per piece.
-//   The residual stream stays fp32.  The A operand: [m-tile][tap * 2 + channel half][piece][lane][8], 72 / 48 registers per conv and lane,
-//   requested one conv ahead.
-typedef __bf16 bf16x8_res __attribute__((ext_vector_type(8)));
-// piece images as chunk planes [piece][8 chunks of 8 channels][64 columns][8 channels] (the layout of conv_b3.h's B3Chunk<64, 64>):
-// a fragment piece = one ds_read_b128, 16 lanes reading 256 consecutive bytes, the planes 1 KB apart -- conflict-free.
+// ---- the same stack on the bf16 matrix cores, with EXACT three-piece operands (conv_b3.h: the form, its split, piece store and
+// product group) ----
+// The sums agree with the fp32-MFMA kernel above to fp32 rounding, at 6 / 16 of its matrix time.  (Activations cut to two pieces
+// would need five products and move the probabilities by up to 4e-5, tools/split_bf16_study.py: not done -- parity first.)
+// The residual stream stays fp32.  The A operand: [m-tile][tap * 2 + channel half][piece][lane][8], 72 / 48 registers per conv
+// and lane, requested one conv ahead.
+// Piece images are chunk planes (conv_b3.h: B3Chunk), 64 columns: a fragment piece = one ds_read_b128, 16 lanes reading 256
+// consecutive bytes, the planes 1 KB apart -- conflict-free.
 // (As [column][64 + 8 channels] the reads ran 2-way conflicted, and the four waves of a window read the SAME fragments:
 // 36 KB per K-step at 128 B/clk = the 288 cycles of the step's MFMAs, one wave per SIMD to hide nothing behind:
 // 3.9 k cycles per k = 3 conv for 1.7 k of MFMA issue, tools stamps of a diagnostic build.)
 constexpr int R3_NC = 64;                    // columns: logical t at column t + 1
-constexpr int R3_CHS = R3_NC * 8;            // elements per chunk plane
-constexpr int R3_PS = 8 * R3_CHS;            // elements per piece
+using R3Q = B3Chunk<64, R3_NC>;
 constexpr int R3_XS = 49;                    // fp32 residual rows
 
 struct Res3Args {
@@ -205,23 +195,9 @@ struct Res3DumpArgs : Res3Args {
   long dbg_ws;
 };
 
-__device__ __forceinline__ void split3(const float v, unsigned short& h, unsigned short& m, unsigned short& l) {
-  h = to_bf16(v);
-  const float r1 = v - from_bf16(h);
-  m = to_bf16(r1);
-  l = to_bf16(r1 - from_bf16(m));
-}
-// four consecutive channels of one column -> one 8-byte store per piece
+// four consecutive channels ch .. ch + 3 (ch a multiple of four) of one column
 __device__ __forceinline__ void store3(bf16_t* img, const int col, const int ch, const float (&v)[4]) {
-  // pairs at a time: one v_cvt_pk_bf16_f32 rounds two values and leaves them packed (the same pieces as split3's)
-  const unsigned h0 = pack_bf16x2(v[0], v[1]), h1 = pack_bf16x2(v[2], v[3]);
-  const float r0 = v[0] - bf16_lo(h0), r1 = v[1] - bf16_hi(h0), r2 = v[2] - bf16_lo(h1), r3 = v[3] - bf16_hi(h1);
-  const unsigned m0 = pack_bf16x2(r0, r1), m1 = pack_bf16x2(r2, r3);
-  const unsigned l0 = pack_bf16x2(r0 - bf16_lo(m0), r1 - bf16_hi(m0)), l1 = pack_bf16x2(r2 - bf16_lo(m1), r3 - bf16_hi(m1));
-  bf16_t* p = img + (ch >> 3) * R3_CHS + col * 8 + (ch & 7);
-  *reinterpret_cast<uint2*>(p) = make_uint2(h0, h1);
-  *reinterpret_cast<uint2*>(p + R3_PS) = make_uint2(m0, m1);
-  *reinterpret_cast<uint2*>(p + 2 * R3_PS) = make_uint2(l0, l1);
+  b3c_store4<64, R3_NC>(img, col, ch >> 2, v);
 }
 
 // R3_EXP (timing probes of tools/, never in the product build; results are WRONG with any of them):
@@ -283,7 +259,7 @@ __device__ __forceinline__ void res3_mac(const bf16_t* src, const Res3A<TAPS>& A
   const int g = lane >> 4, n = lane & 15;
 #pragma unroll
   for (int j = 0; j < 3; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const bf16_t* bp = src + g * R3_CHS + (n + IN_OFF + 1) * 8;  // chunk g (channels 8 g ..), column of logical t = n + IN_OFF
+  const bf16_t* bp = src + g * R3Q::CHS + (n + IN_OFF + 1) * 8;  // chunk g (channels 8 g ..), column of logical t = n + IN_OFF
   uint4 bA[3][3], bB[3][3];  // [n-tile][piece], two sets: the reads of step s + 1 are issued before the MFMAs of step s
   auto load_b = [&](uint4 (&b)[3][3], const int s) {
     const int tap = s >> 1, ks = s & 1;
@@ -291,7 +267,7 @@ __device__ __forceinline__ void res3_mac(const bf16_t* src, const Res3A<TAPS>& A
     for (int j = 0; j < 3; ++j)
 #pragma unroll
       for (int pc = 0; pc < 3; ++pc)
-        b[j][pc] = *reinterpret_cast<const uint4*>(bp + pc * R3_PS + (j * 16 + tap) * 8 + ks * 4 * R3_CHS);
+        b[j][pc] = *reinterpret_cast<const uint4*>(bp + pc * R3Q::PS + (j * 16 + tap) * 8 + ks * 4 * R3Q::CHS);
   };
   load_b(bA, 0);
   if (R3_EXP & 8) load_b(bB, 1);
@@ -306,18 +282,17 @@ __device__ __forceinline__ void res3_mac(const bf16_t* src, const Res3A<TAPS>& A
     }
     __builtin_amdgcn_sched_barrier(0);
     {
-      // (w piece, x piece), smallest products first; the three n-tiles interleaved: consecutive MFMAs never share an accumulator
-      constexpr int WP[6] = {2, 1, 0, 1, 0, 0}, XP[6] = {0, 1, 2, 0, 1, 0};
+      // b3_mac6's products, the three n-tiles interleaved: consecutive MFMAs never share an accumulator
 #pragma unroll
       for (int t = 0; t < 6; ++t)
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
           const uint4(&b)[3] = (s & 1) ? bB[j] : bA[j];
+          const uint4 w = A.q[s][b3_product(t).w], x = b[b3_product(t).x];
           if (R3_EXP & 2) {
-            acc[j][0] += __uint_as_float(A.q[s][WP[t]].x ^ b[XP[t]].x);  // keeps the operands alive
+            acc[j][0] += __uint_as_float(w.x ^ x.x);  // keeps the operands alive
           } else
-          acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_res, A.q[s][WP[t]]),
-                                                          __builtin_bit_cast(bf16x8_res, b[XP[t]]), acc[j], 0, 0, 0);
+          acc[j] = b3_mfma(acc[j], w, x);
         }
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -328,8 +303,8 @@ __device__ __forceinline__ void res3_mac(const bf16_t* src, const Res3A<TAPS>& A
 // reference of eqt_res3t_kernel (plan_flags[7] bit 9; the tests hold the default to it bit for bit).
 __global__ __launch_bounds__(256) void eqt_res3_kernel(const Res3Args a) {
   __shared__ __attribute__((aligned(16))) float X_lds[64 * R3_XS];
-  __shared__ __attribute__((aligned(16))) bf16_t ACT_lds[3 * R3_PS];
-  __shared__ __attribute__((aligned(16))) bf16_t MID_lds[3 * R3_PS];
+  __shared__ __attribute__((aligned(16))) bf16_t ACT_lds[3 * R3Q::PS];
+  __shared__ __attribute__((aligned(16))) bf16_t MID_lds[3 * R3Q::PS];
   // The images through pointers and the (redundant) mask on threadIdx.x: hipcc's code for this kernel depends on both spellings,
   // and these give the instruction stream the tests' reference has had since the kernel was written (tools/kernel_digest.py).
   float* X = X_lds;
@@ -409,7 +384,7 @@ __global__ __launch_bounds__(256) void eqt_res3_kernel(const Res3Args a) {
   }
   __builtin_amdgcn_sched_barrier(0);
   R3_STAMP()
-  for (int i = tid; i < 3 * R3_PS / 8; i += 256) {  // zero halo columns (and everything else once)
+  for (int i = tid; i < 3 * R3Q::PS / 8; i += 256) {  // zero halo columns (and everything else once)
     reinterpret_cast<uint4*>(ACT)[i] = make_uint4(0u, 0u, 0u, 0u);
     reinterpret_cast<uint4*>(MID)[i] = make_uint4(0u, 0u, 0u, 0u);
   }
@@ -555,13 +530,13 @@ __device__ __forceinline__ void res3t_conv(const bf16_t* src_all, bf16_t* dst_al
     constexpr int IN_OFF = (TAPS == 3) ? -1 : 0, STEPS = TAPS * 2, SLOTS = NT * STEPS, AHEAD = 2, NBUF = AHEAD + 1;  // (read-ahead 3 / 4: 104 / 108 k cycles against 101 k)
   constexpr int NL = TN * 2 * 3;  // fragments of the next conv's operand
   const int g = lane >> 4, n = lane & 15;
-  const bf16_t* bp = src_all + g * R3_CHS + (n + IN_OFF + 1) * 8;
+  const bf16_t* bp = src_all + g * R3Q::CHS + (n + IN_OFF + 1) * 8;
   uint4 b[NBUF][3];  // [slot % NBUF][piece]
   auto load_b = [&](const int i) {
     const int u = i / STEPS, s = i - u * STEPS, tap = s >> 1, ks = s & 1, q = Q0 + u, h = q / 3, j = q - 3 * h;
 #pragma unroll
     for (int pc = 0; pc < 3; ++pc)
-      b[i % NBUF][pc] = *reinterpret_cast<const uint4*>(bp + h * 3 * R3_PS + pc * R3_PS + (j * 16 + tap) * 8 + ks * 4 * R3_CHS);
+      b[i % NBUF][pc] = *reinterpret_cast<const uint4*>(bp + h * 3 * R3Q::PS + pc * R3Q::PS + (j * 16 + tap) * 8 + ks * 4 * R3Q::CHS);
   };
   auto values = [&](const int u, const f32x4 acc, float (&v)[4]) {
     const int q = Q0 + u, j = q % 3, t = j * 16 + n;
@@ -590,7 +565,7 @@ __device__ __forceinline__ void res3t_conv(const bf16_t* src_all, bf16_t* dst_al
   };
   auto pieces = [&](const int u, const float (&v)[4]) {
     const int q = Q0 + u, h = q / 3, j = q - 3 * h, t = j * 16 + n;
-    if (!(CONV2 && LAST)) store3(dst_all + h * 3 * R3_PS, t + 1, co, v);
+    if (!(CONV2 && LAST)) store3(dst_all + h * 3 * R3Q::PS, t + 1, co, v);
   };
 #pragma unroll
   for (int i = 0; i < AHEAD; ++i) load_b(i);
@@ -610,11 +585,7 @@ __device__ __forceinline__ void res3t_conv(const bf16_t* src_all, bf16_t* dst_al
       }
       if (u > 0 && s == 0) values(u - 1, prev, v);  // the tile before: its epilogue among this tile's MFMAs
       if (u > 0 && s == 1) pieces(u - 1, v);
-      constexpr int WP[6] = {2, 1, 0, 1, 0, 0}, XP[6] = {0, 1, 2, 0, 1, 0};  // (w piece, x piece), smallest products first
-#pragma unroll
-      for (int t = 0; t < 6; ++t)
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_res, A.q[s][WP[t]]),
-                                                     __builtin_bit_cast(bf16x8_res, b[i % NBUF][XP[t]]), acc, 0, 0, 0);
+      acc = b3_mac6(A.q[s], b[i % NBUF], acc);
     }
     __builtin_amdgcn_sched_barrier(0);
     prev = acc;
@@ -666,7 +637,7 @@ __device__ __forceinline__ void res3t_body(const Args& a, bf16_t* ACT, bf16_t* M
   w1_0.load(a.af1[0], a.bs1[0], nullptr, nullptr, mt, lane);
   __builtin_amdgcn_sched_barrier(0);
   R3T_STAMP()
-  for (int i = tid; i < 3 * 3 * R3_PS / 8; i += 512) {  // zero halo columns (and everything else once)
+  for (int i = tid; i < 3 * 3 * R3Q::PS / 8; i += 512) {  // zero halo columns (and everything else once)
     reinterpret_cast<uint4*>(ACT)[i] = make_uint4(0u, 0u, 0u, 0u);
     reinterpret_cast<uint4*>(MID)[i] = make_uint4(0u, 0u, 0u, 0u);
   }
@@ -675,7 +646,7 @@ __device__ __forceinline__ void res3t_body(const Args& a, bf16_t* ACT, bf16_t* M
 #pragma unroll
   for (int k = 0; k < NAR; ++k) {
     const int i = tid + 512 * k, h = i / (16 * RT), rem = i - h * (16 * RT), cq = rem / RT, t = rem - cq * RT;
-    if (i < 3 * 16 * RT) store3(ACT + h * 3 * R3_PS, t + 1, 4 * cq, ar[k]);
+    if (i < 3 * 16 * RT) store3(ACT + h * 3 * R3Q::PS, t + 1, 4 * cq, ar[k]);
   }
   __syncthreads();
   R3T_STAMP()
@@ -723,8 +694,8 @@ __device__ __forceinline__ void res3t_body(const Args& a, bf16_t* ACT, bf16_t* M
 // DUMP (tests only, plan_flags[1] & 4): the same kernel writing every conv's epilogue values to Res3DumpArgs::dbg from registers
 template <bool DUMP = false>
 __global__ __launch_bounds__(512) void eqt_res3t_kernel(const std::conditional_t<DUMP, Res3DumpArgs, Res3Args> a) {
-  __shared__ __attribute__((aligned(16))) bf16_t ACT[3 * 3 * R3_PS];  // [window of the workgroup][piece][chunk][column][8]
-  __shared__ __attribute__((aligned(16))) bf16_t MID[3 * 3 * R3_PS];
+  __shared__ __attribute__((aligned(16))) bf16_t ACT[3 * 3 * R3Q::PS];  // [window of the workgroup][piece][chunk][column][8]
+  __shared__ __attribute__((aligned(16))) bf16_t MID[3 * 3 * R3Q::PS];
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int last = a.n_windows - 1;  // (a batch that is no multiple of three: the last window up to three times, identical stores)
   const int win[3] = {min((int)blockIdx.x * 3, last), min((int)blockIdx.x * 3 + 1, last), min((int)blockIdx.x * 3 + 2, last)};

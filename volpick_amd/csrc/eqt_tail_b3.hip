@@ -301,21 +301,7 @@ __global__ __launch_bounds__(T3_NTH) void eqt_tail3_kernel(const std::conditiona
         float v[4];
         t3_finish(acc, bias6, (unsigned)(t - lo) < (unsigned)T_OUT, v);
         if constexpr (DUMP) dump(2, 4 * (g & 1), t0 - 6 + t, t0, TW, v);
-        if (B3_EXP & 16) {
-          asm volatile("" ::"v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]));
-          return;
-        }
-        const unsigned h0 = pack_bf16x2(v[0], v[1]), h1 = pack_bf16x2(v[2], v[3]);
-        const float r0 = v[0] - bf16_lo(h0), r1 = v[1] - bf16_hi(h0), r2 = v[2] - bf16_lo(h1), r3 = v[3] - bf16_hi(h1);
-        const unsigned m0 = pack_bf16x2(r0, r1), m1 = pack_bf16x2(r2, r3);
-        const unsigned l0 = pack_bf16x2(r0 - bf16_lo(m0), r1 - bf16_hi(m0)), l1 = pack_bf16x2(r2 - bf16_lo(m1), r3 - bf16_hi(m1));
-        if (B3_EXP & 4) {
-          asm volatile("" ::"v"(h0), "v"(h1), "v"(m0), "v"(m1), "v"(l0), "v"(l1), "v"(q));
-          return;
-        }
-        q[2 * j] = make_uint2(h0, h1);
-        q[2 * j + OUT_PS] = make_uint2(m0, m1);
-        q[2 * j + 2 * OUT_PS] = make_uint2(l0, l1);
+        b3_put4(q + 2 * j, OUT_PS, b3_split4(v));
       };
       // (the next tile's stage-3 rows travel under stage 6 and the heads; the last tile asks for its own again)
       b3c_mac_tiles<16, NC6, 7, NB6>(b3c_lane_ptr<16, NC6, 7>(IN6, colb, lane), a6, finish, [&](const int i) {
@@ -347,11 +333,7 @@ __global__ __launch_bounds__(T3_NTH) void eqt_tail3_kernel(const std::conditiona
       for (int s = 0; s < 7; ++s) {
         if (s + HD < 7) load_ab(s + HD, av[(s + HD) % HB], bv[(s + HD) % HB]);
         __builtin_amdgcn_sched_barrier(0);
-        constexpr int WP[6] = {2, 1, 0, 1, 0, 0}, XP[6] = {0, 1, 2, 0, 1, 0};
-#pragma unroll
-        for (int t = 0; t < 6; ++t)
-          acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_b3, av[s % HB][WP[t]]),
-                                                       __builtin_bit_cast(bf16x8_b3, bv[s % HB][XP[t]]), acc, 0, 0, 0);
+        acc = b3_mac6(av[s % HB], bv[s % HB], acc);
         __builtin_amdgcn_sched_barrier(0);
       }
       const int blk = 16 * w + n;

@@ -445,6 +445,8 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_num_vgpr(60))) void pn_
       for (int k = 0; k < MAXE; ++k) {
         const int t = tid + k * NTH;
         if (k + 1 < MAXE || t < T0) {
+          // three values: the short form of conv_b3.h's b3_split4 (a zero fourth, its residuals not computed), kept written out for
+          // the instruction stream
           const float q0 = v[0][k], q1 = v[1][k], q2 = v[2][k];
           const unsigned h0 = pack_bf16x2(q0, q1), h1 = pack_bf16x2(q2, 0.f);
           const float r0 = q0 - bf16_lo(h0), r1 = q1 - bf16_hi(h0), r2 = q2 - bf16_lo(h1);
@@ -484,7 +486,6 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_num_vgpr(60))) void pn_
       WIN_STAMP(31)
       __syncthreads();
       WIN_STAMP(19)
-#define D0T_MFMA(ACC, W, X) ACC = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_b3, W), __builtin_bit_cast(bf16x8_b3, X), ACC, 0, 0, 0)
       float aD[W_down::CB * W_down::TAPS], bD[4];
       int cinc = 32 * wave + 2 * n + ph;                    // inc: ring column of this lane's sample of tile j
       int csame = D0T_RING - 11 + 32 * wave + 2 * n + g;     // down0.same: ring column of tap g's sample for tile j - 1
@@ -517,26 +518,21 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_num_vgpr(60))) void pn_
         }
         f32x4 ia = bI, sa = {0.f, 0.f, 0.f, 0.f}, sb = bS;
         if (j < D0T_TILES) {  // inc, n-tile `wave` of tile j: samples 512 j + 32 wave + 2 n + ph; smallest products first, bias as the accumulator input
-          D0T_MFMA(ia, aI[2], bi[0]);
-          D0T_MFMA(ia, aI[1], bi[1]);
-          D0T_MFMA(ia, aI[0], bi[2]);
-          D0T_MFMA(ia, aI[1], bi[0]);
-          D0T_MFMA(ia, aI[0], bi[1]);
-          D0T_MFMA(ia, aI[0], bi[0]);
+          ia = b3_mac6(aI, bi, ia);
         }
         if (j > 0) {  // down0.same, n-tile `wave` of tile j - 1: samples 512 (j - 1) - 8 + 32 wave + 2 n + ph read inc's samples .. - 3 + tap, tap = g + 4 step
-          D0T_MFMA(sa, aS[2], bs[0][0]);  // one chain per K-step
-          D0T_MFMA(sb, aS[5], bs[1][0]);
-          D0T_MFMA(sa, aS[1], bs[0][1]);
-          D0T_MFMA(sb, aS[4], bs[1][1]);
-          D0T_MFMA(sa, aS[0], bs[0][2]);
-          D0T_MFMA(sb, aS[3], bs[1][2]);
-          D0T_MFMA(sa, aS[1], bs[0][0]);
-          D0T_MFMA(sb, aS[4], bs[1][0]);
-          D0T_MFMA(sa, aS[0], bs[0][1]);
-          D0T_MFMA(sb, aS[3], bs[1][1]);
-          D0T_MFMA(sa, aS[0], bs[0][0]);
-          D0T_MFMA(sb, aS[3], bs[1][0]);
+          sa = b3_mfma(sa, aS[2], bs[0][0]);  // one chain per K-step
+          sb = b3_mfma(sb, aS[5], bs[1][0]);
+          sa = b3_mfma(sa, aS[1], bs[0][1]);
+          sb = b3_mfma(sb, aS[4], bs[1][1]);
+          sa = b3_mfma(sa, aS[0], bs[0][2]);
+          sb = b3_mfma(sb, aS[3], bs[1][2]);
+          sa = b3_mfma(sa, aS[1], bs[0][0]);
+          sb = b3_mfma(sb, aS[4], bs[1][0]);
+          sa = b3_mfma(sa, aS[0], bs[0][1]);
+          sb = b3_mfma(sb, aS[3], bs[1][1]);
+          sa = b3_mfma(sa, aS[0], bs[0][0]);
+          sb = b3_mfma(sb, aS[3], bs[1][0]);
         }
         if (j < D0T_TILES) {
           float o[4];
@@ -581,7 +577,6 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_num_vgpr(60))) void pn_
         if (j == 0) { WIN_STAMP(20) }
         D0T_PHASE_STAMP(j)
       }
-#undef D0T_MFMA
       // down0.same rests in H (fp32); the ring gives way to down0.down's piece image
       b3c_zero_rest<8, B3_D0_NC>(l16 + A_D0 * 2, 3, B3_D0_NC, tid, NTH);
       if (tid < 6) H[tid * W0_S + 3] = 0.f;  // word 3 = sample -1 of down0.same (padding): x's first sample rested there
@@ -1064,19 +1059,10 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_num_vgpr(60))) void pn_
     auto ring_at = [](const int c) { return (c & 1) * U3T_PL + (c >> 1) * 8; };
     // a producer's store of four channels of one column, all three pieces (+ the mirror entry behind the plane for columns 0 .. 7)
     auto ring_store = [&](bf16_t* const chunk, const int col, const int q, const float (&v)[4]) {
-      const unsigned h0 = pack_bf16x2(v[0], v[1]), h1 = pack_bf16x2(v[2], v[3]);
-      const float r0 = v[0] - bf16_lo(h0), r1 = v[1] - bf16_hi(h0), r2 = v[2] - bf16_lo(h1), r3 = v[3] - bf16_hi(h1);
-      const unsigned m0 = pack_bf16x2(r0, r1), m1 = pack_bf16x2(r2, r3);
-      const unsigned l0 = pack_bf16x2(r0 - bf16_lo(m0), r1 - bf16_hi(m0)), l1 = pack_bf16x2(r2 - bf16_lo(m1), r3 - bf16_hi(m1));
+      const B3Quad s = b3_split4(v);
       bf16_t* const p = chunk + ring_at(col) + 4 * q;
-      *reinterpret_cast<uint2*>(p) = make_uint2(h0, h1);
-      *reinterpret_cast<uint2*>(p + U3T_PS) = make_uint2(m0, m1);
-      *reinterpret_cast<uint2*>(p + 2 * U3T_PS) = make_uint2(l0, l1);
-      if (col < 2 * U3T_MIR) {
-        *reinterpret_cast<uint2*>(p + U3T_PLN * 8) = make_uint2(h0, h1);
-        *reinterpret_cast<uint2*>(p + U3T_PLN * 8 + U3T_PS) = make_uint2(m0, m1);
-        *reinterpret_cast<uint2*>(p + U3T_PLN * 8 + 2 * U3T_PS) = make_uint2(l0, l1);
-      }
+      b3_put4(p, U3T_PS, s);
+      if (col < 2 * U3T_MIR) b3_put4(p + U3T_PLN * 8, U3T_PS, s);
     };
     WIN_STAMP(23)
     const bool producer = wave >= 8;  // (uniform)
@@ -1095,7 +1081,6 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_num_vgpr(60))) void pn_
     }
     __syncthreads();
     WIN_STAMP(24)
-#define U3T_MFMA(ACC, W, X) ACC = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_b3, W), __builtin_bit_cast(bf16x8_b3, X), ACC, 0, 0, 0)
     // producer: transposed conv item (m-tile wv & 1 = phases 2 (wv & 1) + ph, n-tile wv >> 1 of the tile's 64 level-1 samples)
     const int mphase = 2 * (wv & 1) + ph;
     int ct = mphase - 2 + 4 * (16 * (wv >> 1) + n);   // sample of this lane's output in tile 0 (tile j: + 256 j), >= -2
@@ -1150,12 +1135,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_num_vgpr(60))) void pn_
     }
     auto u3_produce = [&](const int j) {  // tile j: MFMAs first, then everything that does not depend on them, then their epilogue
       f32x4 acc = bv;
-      U3T_MFMA(acc, aw[2], u3_pb[0]);
-      U3T_MFMA(acc, aw[1], u3_pb[1]);
-      U3T_MFMA(acc, aw[0], u3_pb[2]);
-      U3T_MFMA(acc, aw[1], u3_pb[0]);
-      U3T_MFMA(acc, aw[0], u3_pb[1]);
-      U3T_MFMA(acc, aw[0], u3_pb[0]);
+      acc = b3_mac6(aw, u3_pb, acc);
       up += (U3T_TS / 4) * 8;
       if (j + 1 < U3T_TILES) {
 #pragma unroll
@@ -1201,12 +1181,12 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_num_vgpr(60))) void pn_
 #pragma unroll
           for (int pc = 0; pc < 3; ++pc) b[st][pc] = *reinterpret_cast<const uint4*>(rp0 + st * 8 + pc * U3T_PS);
         }
-        U3T_MFMA(sa, aw[st * 3 + 2], b[st][0]);
-        U3T_MFMA(sb, aw[st * 3 + 1], b[st][0]);
-        U3T_MFMA(sa, aw[st * 3 + 1], b[st][1]);
-        U3T_MFMA(sb, aw[st * 3 + 0], b[st][1]);
-        U3T_MFMA(sa, aw[st * 3 + 0], b[st][2]);
-        U3T_MFMA(sb, aw[st * 3 + 0], b[st][0]);
+        sa = b3_mfma(sa, aw[st * 3 + 2], b[st][0]);
+        sb = b3_mfma(sb, aw[st * 3 + 1], b[st][0]);
+        sa = b3_mfma(sa, aw[st * 3 + 1], b[st][1]);
+        sb = b3_mfma(sb, aw[st * 3 + 0], b[st][1]);
+        sa = b3_mfma(sa, aw[st * 3 + 0], b[st][2]);
+        sb = b3_mfma(sb, aw[st * 3 + 0], b[st][0]);
       }
 #pragma unroll
       for (int r = 0; r < 4; ++r) u3_h[r] = fmaxf(sa[r] + sb[r], 0.f);  // BN + ReLU: all that crosses the barrier
@@ -1231,7 +1211,6 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_num_vgpr(60))) void pn_
       }
       u3_finish(U3T_TILES - 1, u3_h);  // the last tile's epilogue
     }
-#undef U3T_MFMA
     WIN_STAMP(28)
   } else {
     float *G0 = lds + XU_G0, *G1 = lds + XU_G1, *U = lds + XU_U;
