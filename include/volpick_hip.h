@@ -687,6 +687,39 @@ int vp_eqt_dec_train_launch_count(const vp_eqt_dec_trainer* t); /* kernel launch
 int vp_eqt_dec_train_set_timing(vp_eqt_dec_trainer* t, int on);
 int vp_eqt_dec_train_phase_ms(vp_eqt_dec_trainer* t, float* ms);
 
+/* A second training scope of the same trainer: VP_EQT_TRAIN_PICK_BRANCHES adds the two pick branches in front of the P and
+ * S decoders -- pick_lstms.{0,1} (nn.LSTM(16, 16) over 47 steps) and pick_attentions.{0,1} (additive self-attention, 32
+ * units, band of 3) -- to the trained tensors: 66 tensors, 152,261 floats, in the flat blob's order.  The bottleneck
+ * ("decoder.in" set 0, the branches' input) and everything in front of it stay frozen; gradients into it are not formed.
+ * The branches run their TRAINING forward in fp32: SeisBench's nn.Dropout(drop_rate) sits between the LSTM and its
+ * attention, hd = h mask / (1 - drop_rate).  The mask element (branch, window index in the batch, channel, time step) is a
+ * function of (seed, the trainer's count of steps, those four indices) through Philox4x32-10; the rule is stated in
+ * volpick_amd/csrc/philox.h.  Every step advances the count, also one with update == 0: two steps never share a mask.
+ * drop_rate == 0 keeps every element at scale 1: the step is then the derivative of the inference function.  The gradient of
+ * pick_attentions.*.ba is identically zero (a constant of a score row cancels against the row's maximum); +0.0 is written.
+ * vp_eqt_dec_train_create_scope: scope VP_EQT_TRAIN_DECODERS builds exactly the trainer of vp_eqt_dec_train_create (drop_rate
+ * and seed are then unused, but drop_rate is checked all the same); refused with VP_ERR_INVALID, for either scope: another
+ * scope, a drop_rate outside [0, 1) (NaN included), and what vp_eqt_dec_train_create refuses, under this entry's name.
+ * Every per-handle entry above works on a handle of either scope with the handle's own sizes
+ * (vp_eqt_dec_train_scope_weight_count(vp_eqt_dec_train_scope(t)) floats for _read / _write_weights).
+ * Tensors of scope 1 besides those above, each (2 branches, B, channels, 47) unless said: "pick.x" (1, B, 16, 47: the
+ * bottleneck), "pick.pre", "pick.act" (64 gate rows, torch's order i, f, g, o), "pick.c", "pick.h", "pick.mask" (0 / 1),
+ * "pick.hd", "pick.v" (16), "pick.q", "pick.k" (32), "pick.e" (scores) and "pick.a" (47 x 47, row i, column j), "pick.argmax"
+ * (1 row; the kept column of each row's maximum, as float); backward: "pick.gv" (stage 0's input gradient), "pick.gq",
+ * "pick.gk" (32), "pick.ghd", "pick.gh", "pick.gc" (the cell gradient entering step t's backward, f_{t+1} dc_{t+1}),
+ * "pick.gpre" (64).  vp_eqt_dec_train_pick_ms: with timing on, the three pick parts of the last step alone in ms -- forward,
+ * adjoints (stage 0's input gradient, attention, dropout, LSTM), weight gradients -- which vp_eqt_dec_train_phase_ms counts
+ * under its phases 1, 2 and 3. */
+enum { VP_EQT_TRAIN_DECODERS = 0, VP_EQT_TRAIN_PICK_BRANCHES = 1 };
+int vp_eqt_dec_train_create_scope(int device_id, const float* weights, size_t n_floats, const vp_config* cfg, int max_batch,
+                                  int scope, float drop_rate, uint64_t seed, vp_eqt_dec_trainer** out);
+int vp_eqt_dec_train_scope(const vp_eqt_dec_trainer* t);
+int vp_eqt_dec_train_scope_param_count(int scope);
+const char* vp_eqt_dec_train_scope_param_name(int scope, int index);
+size_t vp_eqt_dec_train_scope_param_size(int scope, int index);
+size_t vp_eqt_dec_train_scope_weight_count(int scope);
+int vp_eqt_dec_train_pick_ms(vp_eqt_dec_trainer* t, float* ms);
+
 /* ---------------------------------------------------------------------------------------------
  * Training batches generated on the GPU from a device-resident waveform bank: the window cut, Normalize and
  * ProbabilisticLabeller steps of the reference's augmentation block 1 (volpick/model/models.py:221-265).  The host plans

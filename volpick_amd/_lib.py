@@ -386,6 +386,14 @@ SIGNATURES = {
     "vp_eqt_dec_train_launch_count": (C.c_int, [_H]),
     "vp_eqt_dec_train_set_timing": (C.c_int, [_H, C.c_int]),
     "vp_eqt_dec_train_phase_ms": (C.c_int, [_H, _FP]),
+    "vp_eqt_dec_train_create_scope": (
+        C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.POINTER(VpConfig), C.c_int, C.c_int, C.c_float, C.c_uint64, C.POINTER(_H)]),
+    "vp_eqt_dec_train_scope": (C.c_int, [_H]),
+    "vp_eqt_dec_train_scope_param_count": (C.c_int, [C.c_int]),
+    "vp_eqt_dec_train_scope_param_name": (C.c_char_p, [C.c_int, C.c_int]),
+    "vp_eqt_dec_train_scope_param_size": (C.c_size_t, [C.c_int, C.c_int]),
+    "vp_eqt_dec_train_scope_weight_count": (C.c_size_t, [C.c_int]),
+    "vp_eqt_dec_train_pick_ms": (C.c_int, [_H, _FP]),
     "vp_vce_loss": (
         C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p],
     ),

@@ -9,6 +9,8 @@
 #include <cmath>
 #include <memory>
 
+#include "philox.h"
+
 namespace vp {
 
 namespace {
@@ -244,22 +246,6 @@ __global__ __launch_bounds__(GEN_NTH) void bank_block1_kernel(const GenArgs a) {
       else
         yw[(long long)a.row_det * T + t] = (double)t >= lo && (double)t < hi ? 1.f : 0.f;
     }
-  }
-}
-
-// Philox4x32-10 (Salmon et al., SC'11): ctr <- the bijection of ctr under key.
-__device__ __forceinline__ void philox4x32_10(uint32_t ctr[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t h0 = __umulhi(0xD2511F53u, ctr[0]), l0 = 0xD2511F53u * ctr[0];
-    const uint32_t h1 = __umulhi(0xCD9E8D57u, ctr[2]), l1 = 0xCD9E8D57u * ctr[2];
-    const uint32_t c1 = ctr[1], c3 = ctr[3];
-    ctr[0] = h1 ^ c1 ^ k0;
-    ctr[1] = l1;
-    ctr[2] = h0 ^ c3 ^ k1;
-    ctr[3] = l0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
   }
 }
 

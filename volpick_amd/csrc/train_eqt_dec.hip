@@ -18,6 +18,11 @@
 // exist only as the index `s >> 1`, `s < Lout` of the operand load into LDS.  No atomics: a weight gradient is summed per
 // workgroup over a fixed list of (window, time chunk) units and the workgroups' partial blocks are folded in index order, so
 // two runs from the same state give the same bits.
+//
+// Scope VP_EQT_TRAIN_PICK_BRANCHES adds the two pick branches in front of the P and S decoders (train_eqt_pick.hip): their
+// training forward writes sets 1 and 2 of decoder.in, stage 0's input gradient (dec_conv_kernel<DGRAD> without the ReLU gate:
+// decoder.in is no ReLU output) feeds their adjoints, and their eighteen tensors join the weight blob.  Scope
+// VP_EQT_TRAIN_DECODERS runs the launches above and nothing else.
 #include <cmath>
 #include <memory>
 
@@ -25,6 +30,7 @@
 #include "batchgen.h"
 #include "bce.h"
 #include "net.h"
+#include "train_eqt_pick.h"
 #include "train_optim.h"
 
 namespace vp {
@@ -32,10 +38,12 @@ namespace {
 
 // ---- the stages ----------------------------------------------------------------------------------------------------------
 // One row per stage, in order: input channels, output channels, taps, and the samples per workgroup of its forward and of its
-// input-gradient launch (0: stage 0 has no input gradient; stage 4 runs 256 forward and 128 backward).
-template <int CI_, int CO_, int K_, int TN_FWD_, int TN_DGRAD_>
+// input-gradient launch (stage 4 runs 256 forward and 128 backward), and whether its input is a ReLU output (decoder.in is
+// not; stage 0's input gradient is formed for the pick branches alone).
+template <int CI_, int CO_, int K_, int TN_FWD_, int TN_DGRAD_, bool RELU_IN_ = true>
 struct StageCfg {
   static constexpr int CI = CI_, CO = CO_, K = K_, TN_FWD = TN_FWD_, TN_DGRAD = TN_DGRAD_;
+  static constexpr bool RELU_IN = RELU_IN_;
 };
 template <class... S>
 struct StageList {
@@ -50,7 +58,7 @@ struct StageList {
 };
 // clang-format off
 using StageTable = StageList<
-    StageCfg<16, 64,  3, 128,   0>,
+    StageCfg<16, 64,  3, 128, 128, false>,
     StageCfg<64, 64,  5, 128, 128>,
     StageCfg<64, 32,  5, 128, 128>,
     StageCfg<32, 32,  7, 128, 128>,
@@ -74,7 +82,8 @@ const char* const kHeadPrefix[NSET] = {"conv_d", "pick_convs.0", "pick_convs.1"}
 //   DGRAD  m = input channel of the conv, c = its output channel, rows = gz[c][s] (0 outside [0, Lout)), A = W[c][m][K-1-k]:
 //          gu[m][s]; the n-tiles come in pairs that hold gu[2j] and gu[2j+1] of the same j in the same lane, so the up-sample's
 //          adjoint is one addition in registers (a chain of CR K terms and one pair sum); gu[Lout] of the cropped stage does
-//          not exist and is left out of the pair.
+//          not exist and is left out of the pair.  RELU_IN = false (stage 0): the input is no ReLU output, ga is the result
+//          and there is no gz.
 struct ConvTArgs {
   const float* src;  // [3 B][CR][Ls]
   const float* w;    // the trainer's weight blob
@@ -91,7 +100,7 @@ struct ConvTile {
   static constexpr int S = (W + 31) / 32 * 32 + 16;  // row stride = 16 mod 32: the four rows of a B fragment in four bank groups
 };
 
-template <bool DGRAD, int CR, int CM, int K, int TN>
+template <bool DGRAD, int CR, int CM, int K, int TN, bool RELU_IN = true>
 __global__ __launch_bounds__(256) void dec_conv_kernel(const ConvTArgs a) {
   constexpr int MT = (CM + 15) / 16, NG = 4 / MT, NTW = TN / 16 / NG, CB = CR / 4, STEPS = CB * K, PAD = K / 2;
   constexpr int S = ConvTile<CR, K, TN>::S, W = ConvTile<CR, K, TN>::W;
@@ -170,7 +179,7 @@ __global__ __launch_bounds__(256) void dec_conv_kernel(const ConvTArgs a) {
           const float g = (s + 1 < a.Lout) ? acc[2 * p][r] + acc[2 * p + 1][r] : acc[2 * p][r];
           const long o = base + (long)m * a.Lprev + jo;
           a.dst[o] = g;
-          a.dst2[o] = a.act[o] > 0.f ? g : 0.f;
+          if constexpr (RELU_IN) a.dst2[o] = a.act[o] > 0.f ? g : 0.f;
         }
       }
     }
@@ -367,8 +376,10 @@ struct DecParam {
   size_t size, off_full, off;  // offset in the model's flat blob / in the trainer's
 };
 
-// the 48 tensors in the flat blob's order
-std::vector<DecParam> dec_params() {
+bool scope_ok(int scope) { return scope == VP_EQT_TRAIN_DECODERS || scope == VP_EQT_TRAIN_PICK_BRANCHES; }
+
+// the scope's tensors in the flat blob's order: the 48 of the decoders and heads, with the pick branches' 18 in scope 1
+std::vector<DecParam> dec_params(int scope = VP_EQT_TRAIN_DECODERS) {
   std::vector<DecParam> out;
   const ParamDesc* t;
   const int n = param_table(VP_MODEL_EQTRANSFORMER, &t);
@@ -378,6 +389,9 @@ std::vector<DecParam> dec_params() {
     bool mine = false;
     for (int d = 0; d < NSET; ++d)
       mine = mine || nm.rfind(std::string(kDecPrefix[d]) + ".", 0) == 0 || nm.rfind(std::string(kHeadPrefix[d]) + ".", 0) == 0;
+    if (scope == VP_EQT_TRAIN_PICK_BRANCHES)
+      for (int k = 0; k < PickDims::NBR; ++k)
+        mine = mine || nm.rfind(std::string(kPickLstmPrefix[k]) + ".", 0) == 0 || nm.rfind(std::string(kPickAttPrefix[k]) + ".", 0) == 0;
     if (mine) {
       out.push_back({nm, t[i].size, full, off});
       off += t[i].size;
@@ -394,7 +408,8 @@ struct DecTensor {
 };
 
 struct DecTrainer {
-  int device = 0, max_batch = 0, launches = 0;
+  int device = 0, max_batch = 0, launches = 0, scope = VP_EQT_TRAIN_DECODERS;
+  std::unique_ptr<PickState> pick;  // scope VP_EQT_TRAIN_PICK_BRANCHES
   hipStream_t stream = nullptr;
   Net net;
   int trunk_steps = 0, t_dec_in = -1;
@@ -413,6 +428,7 @@ struct DecTrainer {
     if (stream) (void)hipStreamSynchronize(stream);
     for (hipEvent_t e : ev)
       if (e) (void)hipEventDestroy(e);
+    if (pick) pick->release_events();
     if (stream) (void)hipStreamDestroy(stream);
     net.release();
   }
@@ -437,18 +453,25 @@ void launch_fwd(DecTrainer& tr, int i, int B) {
   DTL((dec_conv_kernel<false, CR, CM, K, TN>), dim3((kDout[i] + TN - 1) / TN, NSET * B), dim3(256), 0, tr.stream, a);
 }
 
-// stage i's input gradient: gz_i -> ga_{i-1}, gz_{i-1}
-template <int CR, int CM, int K, int TN>
+// stage i's input gradient: gz_i -> ga_{i-1}, gz_{i-1}; stage 0's (RELU_IN = false), for the sets 1 and 2 alone: gz_0 -> pick.gv
+template <int CR, int CM, int K, int TN, bool RELU_IN>
 void launch_dgrad(DecTrainer& tr, int i, int B) {
   ConvTArgs a{};
-  a.src = tr.gz[i].p;
   a.w = tr.opt.w.p;
-  for (int d = 0; d < NSET; ++d) a.w_off[d] = tr.w_off[i][d], a.b_off[d] = tr.b_off[i][d];
-  a.dst = tr.ga[i - 1].p;
-  a.dst2 = tr.gz[i - 1].p;
-  a.act = tr.a[i - 1].p;
   a.B = B, a.Ls = kDout[i], a.Lout = kDout[i], a.Lprev = kDin[i];
-  DTL((dec_conv_kernel<true, CR, CM, K, TN>), dim3((kDout[i] + TN - 1) / TN, NSET * B), dim3(256), 0, tr.stream, a);
+  if constexpr (RELU_IN) {
+    a.src = tr.gz[i].p;
+    for (int d = 0; d < NSET; ++d) a.w_off[d] = tr.w_off[i][d], a.b_off[d] = tr.b_off[i][d];
+    a.dst = tr.ga[i - 1].p;
+    a.dst2 = tr.gz[i - 1].p;
+    a.act = tr.a[i - 1].p;
+    DTL((dec_conv_kernel<true, CR, CM, K, TN>), dim3((kDout[i] + TN - 1) / TN, NSET * B), dim3(256), 0, tr.stream, a);
+  } else {
+    a.src = tr.gz[i].p + (long)B * CR * kDout[i];  // behind set 0
+    for (int k = 0; k < PickDims::NBR; ++k) a.w_off[k] = tr.w_off[i][1 + k], a.b_off[k] = tr.b_off[i][1 + k];
+    a.dst = tr.pick->gv.p;
+    DTL((dec_conv_kernel<true, CR, CM, K, TN, false>), dim3((kDout[i] + TN - 1) / TN, PickDims::NBR * B), dim3(256), 0, tr.stream, a);
+  }
 }
 
 template <int CO, int CI, int K, bool UP>
@@ -469,9 +492,7 @@ void forward_stage(DecTrainer& tr, int i, int B) {
   StageTable::at(i, [&](auto s) { launch_fwd<s.CI, s.CO, s.K, s.TN_FWD>(tr, i, B); });
 }
 void dgrad_stage(DecTrainer& tr, int i, int B) {  // CR = the conv's output channels, CM = its input channels
-  StageTable::at(i, [&](auto s) {
-    if constexpr (s.TN_DGRAD != 0) launch_dgrad<s.CO, s.CI, s.K, s.TN_DGRAD>(tr, i, B);
-  });
+  StageTable::at(i, [&](auto s) { launch_dgrad<s.CO, s.CI, s.K, s.TN_DGRAD, s.RELU_IN>(tr, i, B); });
 }
 void wgrad_stage(DecTrainer& tr, int i, int B) {
   const float* src = i == 0 ? tr.din.p : tr.a[i - 1].p;
@@ -499,11 +520,19 @@ int build(DecTrainer& tr, const float* weights, size_t n_floats, const vp_config
   VP_REQUIRE(tr.trunk_steps > 0 && tr.t_dec_in >= 0, "vp_eqt_dec_train_create: the plan has no decoder.in");
   if ((rc = tr.net.upload()) != VP_OK) return rc;
 
-  tr.params = dec_params();
+  tr.params = dec_params(tr.scope);
   tr.n_params = 0;
   for (const DecParam& p : tr.params) tr.n_params += p.size;
   for (const DecParam& p : tr.params) {
     int set = -1, stage = -1;
+    bool picks = false;
+    for (int k = 0; tr.pick && k < PickDims::NBR; ++k)
+      for (int sg = 0; sg < PK_NSEG; ++sg)
+        if (p.name == std::string(sg < PK_WX ? kPickLstmPrefix[k] : kPickAttPrefix[k]) + "." + kPickSegName[sg]) {
+          VP_REQUIRE(p.size == (size_t)kPickSegSize[sg], "vp_eqt_dec_train_create: %s has %zu floats", p.name.c_str(), p.size);
+          tr.pick->off[k][sg] = (int)p.off, picks = true;
+        }
+    if (picks) continue;
     for (int d = 0; d < NSET; ++d) {
       const std::string dp = std::string(kDecPrefix[d]) + ".convs.", hp = std::string(kHeadPrefix[d]) + ".";
       if (p.name.rfind(dp, 0) == 0) set = d, stage = p.name[dp.size()] - '0';
@@ -527,6 +556,13 @@ int build(DecTrainer& tr, const float* weights, size_t n_floats, const vp_config
     return VP_OK;
   };
   if ((r = rows(tr.din, "decoder.in", NSET, 16, kDin[0])) != VP_OK) return r;
+  if (tr.pick) {
+    tr.tensors.push_back({"pick.x", tr.din.p, 1, 16, kDin[0]});  // set 0 of decoder.in: the bottleneck the branches read
+    const int pr = tr.pick->alloc(tr.max_batch, [&](const std::string& name, float* p, int sets, int C, int L) {
+      tr.tensors.push_back({name, p, sets, C, L});
+    });
+    if (pr != VP_OK) return pr;
+  }
   for (int i = 0; i < NSTAGE; ++i)
     if ((r = rows(tr.a[i], "a" + std::to_string(i), NSET, kCo[i], kDout[i])) != VP_OK) return r;
   if ((r = rows(tr.logit, "logits", NSET, 1, T_OUT)) != VP_OK) return r;
@@ -574,6 +610,14 @@ int run_step(DecTrainer& tr, const float* x_dev, const float* y_dev, int B, cons
     DTL(dec_copy_in_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, di.p, di.ls, (long)di.win_stride(), tr.din.p, n);
   }
   if (tr.timing) (void)hipEventRecord(tr.ev[1], s);
+  PickState* const pk = tr.pick.get();
+  const bool pk_timing = pk && tr.timing && pk->ev[0];
+  if (pk) {  // sets 1 and 2 of decoder.in: the branches' training forward on set 0, under this step's dropout masks
+    if (pk_timing) (void)hipEventRecord(pk->ev[0], s);
+    pick_forward(*pk, tr.opt.w.p, tr.din.p, tr.din.p, B, s, tr.launches);
+    ++pk->step;  // (every step, update or not: two steps never share a mask)
+    if (pk_timing) (void)hipEventRecord(pk->ev[1], s);
+  }
   for (int i = 0; i < NSTAGE; ++i) forward_stage(tr, i, B);
   HeadArgs h{};
   h.a6 = tr.a[6].p, h.w = tr.opt.w.p, h.y = y_dev, h.logit = tr.logit.p, h.p = tr.pred.p, h.gz = tr.gzh.p, h.ga6 = tr.ga[6].p, h.gz6 = tr.gz[6].p;
@@ -589,9 +633,20 @@ int run_step(DecTrainer& tr, const float* x_dev, const float* y_dev, int B, cons
   if (tr.timing) (void)hipEventRecord(tr.ev[2], s);
   DTL(dec_head_dgrad_kernel, hgrid, dim3(256), 0, s, h);
   for (int i = NSTAGE - 1; i >= 1; --i) dgrad_stage(tr, i, B);
+  if (pk) {
+    if (pk_timing) (void)hipEventRecord(pk->ev[2], s);
+    dgrad_stage(tr, 0, B);
+    pick_backward(*pk, tr.opt.w.p, B, s, tr.launches);
+    if (pk_timing) (void)hipEventRecord(pk->ev[3], s);
+  }
   if (tr.timing) (void)hipEventRecord(tr.ev[3], s);
   launch_wgrad<1, HC, HK, false>(tr, NSTAGE, tr.gzh.p, tr.a[6].p, T_OUT, T_OUT, B);
   for (int i = NSTAGE - 1; i >= 0; --i) wgrad_stage(tr, i, B);
+  if (pk) {
+    if (pk_timing) (void)hipEventRecord(pk->ev[4], s);
+    pick_wgrad(*pk, tr.din.p, tr.opt.grad.p, B, s, tr.launches);
+    if (pk_timing) (void)hipEventRecord(pk->ev[5], s);
+  }
   if (tr.timing) (void)hipEventRecord(tr.ev[4], s);
   if (update) tr.opt.update(s, lr, tr.launches);
   if (tr.timing) (void)hipEventRecord(tr.ev[5], s);
@@ -652,15 +707,34 @@ size_t vp_eqt_dec_train_param_size(int index) {
   return (index >= 0 && index < (int)table.size()) ? table[index].size : 0;
 }
 
-int vp_eqt_dec_train_create(int device_id, const float* weights, size_t n_floats, const vp_config* cfg, int max_batch,
-                            vp_eqt_dec_trainer** out) {
-  VP_REQUIRE(out && weights, "vp_eqt_dec_train_create: null argument");
-  VP_REQUIRE(max_batch > 0 && max_batch <= 65535 / NSET, "vp_eqt_dec_train_create: max_batch %d outside [1, %d]", max_batch, 65535 / NSET);
+int vp_eqt_dec_train_scope_param_count(int scope) { return scope_ok(scope) ? (int)dec_params(scope).size() : 0; }
+const char* vp_eqt_dec_train_scope_param_name(int scope, int index) {
+  static const std::vector<DecParam> table[2] = {dec_params(VP_EQT_TRAIN_DECODERS), dec_params(VP_EQT_TRAIN_PICK_BRANCHES)};
+  return (scope_ok(scope) && index >= 0 && index < (int)table[scope].size()) ? table[scope][index].name.c_str() : nullptr;
+}
+size_t vp_eqt_dec_train_scope_param_size(int scope, int index) {
+  static const std::vector<DecParam> table[2] = {dec_params(VP_EQT_TRAIN_DECODERS), dec_params(VP_EQT_TRAIN_PICK_BRANCHES)};
+  return (scope_ok(scope) && index >= 0 && index < (int)table[scope].size()) ? table[scope][index].size : 0;
+}
+size_t vp_eqt_dec_train_scope_weight_count(int scope) {
+  size_t n = 0;
+  if (scope_ok(scope))
+    for (const DecParam& p : dec_params(scope)) n += p.size;
+  return n;
+}
+
+// what both constructors run; `who` is the entry that was called
+static int create_trainer(const char* who, int device_id, const float* weights, size_t n_floats, const vp_config* cfg, int max_batch,
+                          int scope, float drop_rate, uint64_t seed, vp_eqt_dec_trainer** out) {
+  VP_REQUIRE(out && weights, "%s: null argument", who);
+  VP_REQUIRE(scope_ok(scope), "%s: scope %d is neither VP_EQT_TRAIN_DECODERS nor VP_EQT_TRAIN_PICK_BRANCHES", who, scope);
+  VP_REQUIRE(drop_rate >= 0.f && drop_rate < 1.f, "%s: drop_rate %g outside [0, 1)", who, (double)drop_rate);
+  VP_REQUIRE(max_batch > 0 && max_batch <= 65535 / NSET, "%s: max_batch %d outside [1, %d]", who, max_batch, 65535 / NSET);
   if (n_floats == vp_weight_count(VP_MODEL_PHASENET)) {
-    set_error("vp_eqt_dec_train_create: a PhaseNet blob (%zu floats); PhaseNet trains through vp_train_create", n_floats);
+    set_error("%s: a PhaseNet blob (%zu floats); PhaseNet trains through vp_train_create", who, n_floats);
     return VP_ERR_UNSUPPORTED;
   }
-  VP_REQUIRE(n_floats == vp_weight_count(VP_MODEL_EQTRANSFORMER), "vp_eqt_dec_train_create: expected %zu weight floats, got %zu",
+  VP_REQUIRE(n_floats == vp_weight_count(VP_MODEL_EQTRANSFORMER), "%s: expected %zu weight floats, got %zu", who,
              vp_weight_count(VP_MODEL_EQTRANSFORMER), n_floats);
   vp_config c;
   if (cfg) {
@@ -668,15 +742,30 @@ int vp_eqt_dec_train_create(int device_id, const float* weights, size_t n_floats
   } else {
     vp_default_config(VP_MODEL_EQTRANSFORMER, &c);
   }
-  for (int v : c.reserved) VP_REQUIRE(v == 0, "vp_eqt_dec_train_create: vp_config.reserved must be zero");
+  for (int v : c.reserved) VP_REQUIRE(v == 0, "%s: vp_config.reserved must be zero", who);
   VP_HIP(hipSetDevice(device_id));
   auto tr = std::make_unique<DecTrainer>();
   tr->device = device_id;
   tr->max_batch = max_batch;
+  tr->scope = scope;
+  if (scope == VP_EQT_TRAIN_PICK_BRANCHES) {
+    tr->pick = std::make_unique<PickState>();
+    tr->pick->drop_rate = drop_rate, tr->pick->scale = 1.f / (1.f - drop_rate), tr->pick->seed = seed;
+  }
   const int rc = build(*tr, weights, n_floats, c);
   if (rc != VP_OK) return rc;
   *out = reinterpret_cast<vp_eqt_dec_trainer*>(tr.release());
   return VP_OK;
+}
+
+int vp_eqt_dec_train_create(int device_id, const float* weights, size_t n_floats, const vp_config* cfg, int max_batch,
+                            vp_eqt_dec_trainer** out) {
+  return create_trainer("vp_eqt_dec_train_create", device_id, weights, n_floats, cfg, max_batch, VP_EQT_TRAIN_DECODERS, 0.f, 0, out);
+}
+
+int vp_eqt_dec_train_create_scope(int device_id, const float* weights, size_t n_floats, const vp_config* cfg, int max_batch, int scope,
+                                  float drop_rate, uint64_t seed, vp_eqt_dec_trainer** out) {
+  return create_trainer("vp_eqt_dec_train_create_scope", device_id, weights, n_floats, cfg, max_batch, scope, drop_rate, seed, out);
 }
 
 int vp_eqt_dec_train_destroy(vp_eqt_dec_trainer* h) {
@@ -777,12 +866,28 @@ int vp_eqt_dec_train_tensor_read(vp_eqt_dec_trainer* h, int index, int B, float*
   return VP_OK;
 }
 
+int vp_eqt_dec_train_scope(const vp_eqt_dec_trainer* h) { return h ? reinterpret_cast<const DecTrainer*>(h)->scope : VP_ERR_INVALID; }
 int vp_eqt_dec_train_launch_count(const vp_eqt_dec_trainer* h) { return h ? reinterpret_cast<const DecTrainer*>(h)->launches : 0; }
 void* vp_eqt_dec_train_stream(const vp_eqt_dec_trainer* h) { return h ? reinterpret_cast<const DecTrainer*>(h)->stream : nullptr; }
 
 int vp_eqt_dec_train_set_timing(vp_eqt_dec_trainer* h, int on) {
   VP_REQUIRE(h, "vp_eqt_dec_train_set_timing: null handle");
-  reinterpret_cast<DecTrainer*>(h)->timing = on != 0;
+  DecTrainer& tr = *reinterpret_cast<DecTrainer*>(h);
+  if (on && tr.pick && !tr.pick->ev[0]) {
+    VP_HIP(hipSetDevice(tr.device));
+    for (auto& e : tr.pick->ev) VP_HIP(hipEventCreate(&e));
+  }
+  tr.timing = on != 0;
+  return VP_OK;
+}
+int vp_eqt_dec_train_pick_ms(vp_eqt_dec_trainer* h, float* ms) {
+  VP_REQUIRE(h && ms, "vp_eqt_dec_train_pick_ms: null argument");
+  DecTrainer& tr = *reinterpret_cast<DecTrainer*>(h);
+  VP_REQUIRE(tr.pick, "vp_eqt_dec_train_pick_ms: the trainer's scope is VP_EQT_TRAIN_DECODERS");
+  VP_REQUIRE(tr.timing && tr.pick->ev[0], "vp_eqt_dec_train_pick_ms: timing is off (vp_eqt_dec_train_set_timing)");
+  VP_HIP(hipSetDevice(tr.device));
+  VP_HIP(hipStreamSynchronize(tr.stream));
+  for (int i = 0; i < 3; ++i) VP_HIP(hipEventElapsedTime(&ms[i], tr.pick->ev[2 * i], tr.pick->ev[2 * i + 1]));
   return VP_OK;
 }
 int vp_eqt_dec_train_phase_ms(vp_eqt_dec_trainer* h, float* ms) {

@@ -706,26 +706,55 @@ def decoder_param_names():
             for i in range(lib.vp_eqt_dec_train_param_count())]
 
 
+def _scope_param_names(scope):
+    lib = _lib.load()
+    return [(lib.vp_eqt_dec_train_scope_param_name(scope, i).decode(), int(lib.vp_eqt_dec_train_scope_param_size(scope, i)))
+            for i in range(lib.vp_eqt_dec_train_scope_param_count(scope))]
+
+
+def pick_branch_param_names():
+    """The 66 tensors of ``EQTransformerDecoderTrainer(scope="pick_branches")`` -- the 48 of ``decoder_param_names`` and
+    ``pick_lstms.{0,1}`` with ``pick_attentions.{0,1}`` -- as ``[(name, size)]`` in the flat blob's order: 152,261 floats."""
+    return _scope_param_names(TRAIN_SCOPES["pick_branches"])
+
+
+TRAIN_SCOPES = {"decoders": 0, "pick_branches": 1}  # VP_EQT_TRAIN_DECODERS, VP_EQT_TRAIN_PICK_BRANCHES
+EQT_DROP_RATE = 0.1  # SeisBench's EQTransformer default
+
+
 class EQTransformerDecoderTrainer(_Trainer):
     """The three decoder stacks and heads of one EQTransformer on the device, with their gradients and Adam state; the
     trunk is frozen and runs as the inference path (``vp_eqt_dec_train_*``).  ``PhaseNetTrainer``'s role for
-    ``EQTransformerLit(trainable="decoders")``.  The trainer builds its own device plan from ``model``'s weights and config
+    ``EQTransformerLit(trainable=...)``.  The trainer builds its own device plan from ``model``'s weights and config
     when it is made and does not follow later changes of ``model``; ``export()`` writes the trained tensors back.
-    ``names``: the 48 trained tensors (``decoder_param_names``)."""
+
+    ``scope="decoders"``: the 48 tensors of ``decoder_param_names``.  ``scope="pick_branches"`` adds the pick LSTMs and
+    attentions in front of the P and S decoders (``pick_branch_param_names``: 66 tensors) and runs their training forward:
+    dropout of rate ``drop_rate`` (``None``: SeisBench's 0.1; 0 switches it off) between each LSTM and its attention, with
+    masks that are a function of ``seed``, the count of steps and the element (Philox; ``volpick_amd/csrc/philox.h``).
+    ``names``, ``weights()``, ``gradients()``, ``write_weights``, ``export()`` and ``tensors()`` follow the scope."""
 
     N_SETS = 3  # detection, P, S
     _prefix, _model_type, _wrong_model = "vp_eqt_dec_train", EQTransformer, "the decoder training step is implemented for EQTransformer"
 
-    def __init__(self, model: EQTransformer, max_batch=256, device=0, betas=(0.9, 0.999), eps=1e-8):
+    def __init__(self, model: EQTransformer, max_batch=256, device=0, betas=(0.9, 0.999), eps=1e-8, scope="decoders",
+                 drop_rate=None, seed=0):
         self._check_model(model)
         from .generate import detection_label_rows
 
         if list(detection_label_rows(model.labels)) != [0, 1, 2]:
             raise ValueError(f"the trainer's heads are (Detection, P, S) in this order, the model's labels are {model.labels!r}")
+        if scope not in TRAIN_SCOPES:
+            raise ValueError(f"scope must be one of {tuple(TRAIN_SCOPES)}, got {scope!r}")
+        self.scope = scope
+        self.drop_rate = EQT_DROP_RATE if drop_rate is None else float(drop_rate)
+        self.seed = int(seed)
         self._held = None  # the device inputs / the bank of the latest step: this trainer's steps return complete
         cfg = model._config()
-        super().__init__(model, max_batch, decoder_param_names(), (betas[0], betas[1], eps),
-                         lambda lib, w, h: lib.vp_eqt_dec_train_create(int(device), _lib.ptr(w), w.size, C.byref(cfg), int(max_batch), h))
+        super().__init__(model, max_batch, _scope_param_names(TRAIN_SCOPES[scope]), (betas[0], betas[1], eps),
+                         lambda lib, w, h: lib.vp_eqt_dec_train_create_scope(int(device), _lib.ptr(w), w.size, C.byref(cfg),
+                                                                             int(max_batch), TRAIN_SCOPES[scope], self.drop_rate,
+                                                                             self.seed & (2 ** 64 - 1), h))
 
     def close(self):
         super().close()
@@ -769,8 +798,8 @@ class EQTransformerDecoderTrainer(_Trainer):
         return loss.value
 
     def write_weights(self, blob):
-        """Replace the 145,731 trained floats (the order of ``names``; a dict of the 48 tensors is flattened).  The Adam
-        moments and the update count stay as they are (``vp_eqt_dec_train_write_weights``)."""
+        """Replace the trained floats (145,731, or 152,261 with the pick branches; the order of ``names``; a dict of the
+        tensors is flattened).  The Adam moments and the update count stay as they are (``vp_eqt_dec_train_write_weights``)."""
         if isinstance(blob, dict):
             blob = np.concatenate([np.asarray(blob[k], np.float32).ravel() for k, _ in self.names])
         super().write_weights(blob)
@@ -778,7 +807,8 @@ class EQTransformerDecoderTrainer(_Trainer):
     def tensors(self, B):
         """Every tensor of the last step (a batch of ``B`` windows) by name: ``decoder.in``, ``a0`` .. ``a6``, ``logits``,
         ``gz_head``, ``ga0`` .. ``ga6``, ``gz0`` .. ``gz6`` as (3, B, C, L) arrays -- decoder detection, P, S -- and the
-        predictions ``p`` as (B, 3, 6000)."""
+        predictions ``p`` as (B, 3, 6000).  With ``scope="pick_branches"`` also the branches' tensors ``pick.*`` as
+        (2, B, C, 47) arrays -- P, S -- and ``pick.x`` (B, 16, 47), listed in include/volpick_hip.h."""
         lib, out = self._lib, {}
         for i in range(lib.vp_eqt_dec_train_tensor_count(self._h)):
             name, s, c, l = C.c_char_p(), C.c_int(), C.c_int(), C.c_int()
@@ -798,11 +828,18 @@ class EQTransformerDecoderTrainer(_Trainer):
         _lib.check(self._lib.vp_eqt_dec_train_phase_ms(self._h, ms), "vp_eqt_dec_train_phase_ms")
         return tuple(float(v) for v in ms)
 
+    def pick_ms(self):
+        """(forward, adjoints, weight gradients) of the pick branches in the last step in ms, the parts ``phase_ms`` counts
+        under its second, third and fourth phase; needs ``scope="pick_branches"`` and ``set_timing(True)`` before that step."""
+        ms = (C.c_float * 3)()
+        _lib.check(self._lib.vp_eqt_dec_train_pick_ms(self._h, ms), "vp_eqt_dec_train_pick_ms")
+        return tuple(float(v) for v in ms)
+
     def set_timing(self, on=True):
         _lib.check(self._lib.vp_eqt_dec_train_set_timing(self._h, int(bool(on))))
 
     def export(self):
-        """Copy the 48 trained tensors back into ``self.model`` (``state_dict`` / ``load_state_dict``); every other tensor
+        """Copy the trained tensors (``names``) back into ``self.model`` (``state_dict`` / ``load_state_dict``); every other tensor
         keeps its bits."""
         sd = self.model.state_dict()
         sd.update(self.weights())
@@ -810,7 +847,7 @@ class EQTransformerDecoderTrainer(_Trainer):
         return self.model
 
 
-TRAINABLE = ("decoders",)
+TRAINABLE = ("decoders", "pick_branches")
 
 
 class EQTransformerLit(_Lit):
@@ -822,15 +859,21 @@ class EQTransformerLit(_Lit):
 
     ``trainable=None`` (default) validates only: ``training_step`` raises.  ``trainable="decoders"`` trains the three
     decoder stacks and their heads with the trunk frozen (``EQTransformerDecoderTrainer``): ``training_step(batch)`` on the
-    same dictionaries and ``fit_bank``.  Training the trunk is not implemented."""
+    same dictionaries and ``fit_bank``.  ``trainable="pick_branches"`` trains the pick LSTMs and attentions in front of the
+    P and S decoders as well (``EQTransformerDecoderTrainer(scope="pick_branches", drop_rate=..., seed=...)``: 66 tensors,
+    dropout as in training) through the same calls.  Training the rest of the trunk (encoder, ResCNN, BiLSTMs,
+    transformers) is not implemented."""
 
     def __init__(self, lr=1e-2, sigma=20, loss_weights=EQT_LOSS_WEIGHTS, detection_fixed_window=None,
-                 prob_label_shape="gaussian", model=None, device=0, trainable=None, max_batch=256, **model_kwargs):
+                 prob_label_shape="gaussian", model=None, device=0, trainable=None, max_batch=256, drop_rate=None, seed=0,
+                 **model_kwargs):
         super().__init__(lr, sigma, prob_label_shape, max_batch, device)
         self.loss_weights = tuple(float(w) for w in _loss_weights(loss_weights))
         if trainable is not None and trainable not in TRAINABLE:
-            raise ValueError(f"trainable must be None or 'decoders' (the decoder stacks and heads, trunk frozen), got {trainable!r}")
+            raise ValueError("trainable must be None, 'decoders' (the decoder stacks and heads, trunk frozen) or 'pick_branches' "
+                             f"(those and the pick LSTMs and attentions), got {trainable!r}")
         self.trainable = trainable
+        self.drop_rate, self.seed = drop_rate, seed
         self.detection_fixed_window = detection_fixed_window
         self.model = model if model is not None else EQTransformer(**model_kwargs)
 
@@ -848,13 +891,15 @@ class EQTransformerLit(_Lit):
     def _ensure(self):
         if self.trainable is None:
             raise NotImplementedError("EQTransformer training needs trainable='decoders' (the decoder stacks and heads, trunk "
-                                      "frozen); training the trunk is not implemented: this object validates "
+                                      "frozen) or trainable='pick_branches' (those and the pick LSTMs and attentions); "
+                                      "training the rest of the trunk is not implemented: this object validates "
                                       "(validation_step, validate_bank)")
         if self._trainer is None:
-            self._trainer = EQTransformerDecoderTrainer(self.model, max_batch=self._max_batch, device=self._device)
+            self._trainer = EQTransformerDecoderTrainer(self.model, max_batch=self._max_batch, device=self._device,
+                                                        scope=self.trainable, drop_rate=self.drop_rate, seed=self.seed)
         return self._trainer
     def training_step(self, batch, batch_idx=None):
-        """``trainable="decoders"``: forward, loss, backward and the Adam step on ``{"X", "y", "detections"}`` (what
+        """``trainable="decoders"`` / ``"pick_branches"``: forward, loss, backward and the Adam step on ``{"X", "y", "detections"}`` (what
         ``make_batch`` returns); returns the loss.  Otherwise raises ``NotImplementedError``."""
         tr = self._ensure()
         det, y = batch["detections"], batch["y"]
@@ -869,7 +914,7 @@ class EQTransformerLit(_Lit):
         """``steps`` optimiser steps of the decoder trainer on batches generated on the GPU from ``bank``: epochs of
         ``window_planner`` (``augment``: of ``augmented_planner``), the warm-up of ``learning_rate``, and -- with ``val_bank`` --
         ``validate_bank`` on the exported weights after every completed epoch and after the last step, which drives
-        ``lr_scheduler``, ``keep_best`` (``self.best_state``: the 48 decoder tensors of the lowest validation loss, restored
+        ``lr_scheduler``, ``keep_best`` (``self.best_state``: the trained tensors -- 48, or 66 with the pick branches -- of the lowest validation loss, restored
         into the trainer and the model when the fit ends) and ``early_stop_patience`` exactly as in ``PhaseNetLit.fit_bank``
         (one shared host loop).  Returns the per-step losses and, with ``val_bank``, ``(losses, val_losses)``."""
         scheduler = _fit_scheduler(lr_scheduler, lr_scheduler_args, val_bank, keep_best, early_stop_patience)
